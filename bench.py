@@ -485,7 +485,12 @@ def main():
                          "512 calls of 384 tokens per group, the plugin path's calling pattern (staged on the device)")
     ap.add_argument("--actorder", choices=["static", "group", "none"], default="static",
                     help="activation ordering (default: upstream's default, static); other values are diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (packed int4 words as float64, "
+                         "scales as float32; a fixed, seeded row sample when the layer exceeds 60 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: become the launcher (nothing has touched the GPU yet)
@@ -637,6 +642,8 @@ def main():
             assert len(merged) == len(local) * world
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(kept[-1], args.dump_outputs)      # outside the timed region; rank 0's own last layer
 
     tot_ms = ctypes.c_double()
     launches = ctypes.c_int64()
@@ -782,6 +789,46 @@ def pmc_traffic():
         except Exception:
             continue
     return None
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # payload of --dump-outputs; with the .npy headers well inside 64 MB
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: what the timed path returned in its last step, as ``<out_dir>/<name>.npy``.
+
+    ``outs`` maps "<linear>.weight_packed" (int32 words, eight int4 levels each) and "<linear>.weight_scale" (bf16)
+    to device tensors.  Values are kept exactly: packed words as float64, scales as float32.  When the whole layer
+    exceeds DUMP_BUDGET_BYTES, every Linear contributes the same fraction of its rows, picked by a generator seeded
+    from the Linear's name, so two runs (or two builds) dump the same rows; "<linear>.rows.npy" lists them."""
+    import zlib
+
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    linears = sorted({k.rsplit(".", 1)[0] for k in outs})
+    row_bytes, n_rows = {}, {}
+    for lin in linears:
+        ts = [t for t in (outs.get(f"{lin}.weight_packed"), outs.get(f"{lin}.weight_scale")) if t is not None]
+        n_rows[lin] = int(ts[0].shape[0])
+        row_bytes[lin] = 8 + sum(int(t[0].numel()) * (8 if t.dtype == torch.int32 else 4) for t in ts)
+    total = sum(row_bytes[lin] * n_rows[lin] for lin in linears)
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    for lin in linears:
+        R = n_rows[lin]
+        keep = max(1, int(R * frac))
+        rows = np.arange(R) if keep >= R else np.sort(
+            np.random.default_rng(zlib.crc32(lin.encode())).choice(R, size=keep, replace=False))
+        np.save(out_dir / f"{lin}.rows.npy", rows.astype(np.float64))
+        idx = torch.from_numpy(rows).to(next(iter(outs.values())).device)
+        for s in ("weight_packed", "weight_scale"):
+            t = outs.get(f"{lin}.{s}")
+            if t is None:
+                continue
+            t = t.index_select(0, idx)
+            t = t.to(torch.float64) if t.dtype == torch.int32 else t.to(torch.float32)
+            np.save(out_dir / f"{lin}.{s}.npy", t.cpu().numpy())
 
 
 def _lib_const(name: str) -> int:

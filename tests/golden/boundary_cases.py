@@ -17,6 +17,11 @@ ONESHOT_PARAMS = ["model", "dataset", "recipe", "output_dir", "num_calibration_s
                   "calibration_dataloader", "tokenizer", "splits", "text_column", "precision", "pipeline",
                   "sequential_targets"]
 
+#: the reference files whose code the fixture exercises (paths under its ``src/``); the fixture records their sha1
+REFERENCE_FILES = ["quantool/core/registry.py", "quantool/core/base.py", "quantool/methods/llm_compressor/base.py",
+                   "quantool/methods/llm_compressor/gptq/gptq.py", "quantool/methods/llm_compressor/awq/awq.py",
+                   "quantool/methods/llm_compressor/smoothquant/smoothquant.py", "quantool/utils/dataset_textifier.py"]
+
 #: the preset names the reference lists as valid (``gptq.py:68-70`` / ``awq.py:62-64`` / ``smoothquant.py:66-68``)
 PRESETS = ["W8A16", "W4A16", "W4A16_ASYM", "W8A8", "INT8", "W4A8", "FP8", "FP8_DYNAMIC", "FP8_BLOCK", "NVFP4A16",
            "NVFP4", "UNQUANTIZED"]

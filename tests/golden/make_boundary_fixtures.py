@@ -20,7 +20,8 @@ Reference code exercised: ``quantool.core.registry`` (``registry.py:4-25``), ``L
 (``gptq.py:46-91``, ``awq.py:41-84``, ``smoothquant.py:49-90``), ``convert_row`` and helpers
 (``utils/dataset_textifier.py:15-260``).
 
-usage:  python tests/golden/make_boundary_fixtures.py        (rewrites tests/golden/boundary_reference.json)
+usage:  python tests/golden/make_boundary_fixtures.py          (rewrites tests/golden/boundary_reference.json)
+        python tests/golden/make_boundary_fixtures.py --check  (exit 1 when the reference files changed since)
 """
 from __future__ import annotations
 
@@ -116,6 +117,10 @@ def canon_recipe(r):
     if hasattr(r, "kwargs") and type(r).__name__.endswith("Modifier"):
         return {"cls": type(r).__name__, "kwargs": bc.jsonable(r.kwargs)}
     return bc.jsonable(r)
+
+
+def reference_sha1() -> dict:
+    return {f: hashlib.sha1((REF_SRC / f).read_bytes()).hexdigest() for f in bc.REFERENCE_FILES}
 
 
 def main():
@@ -310,12 +315,9 @@ def main():
     out["prepare"] = prep
 
     # ---- provenance ------------------------------------------------------------------------------
-    files = ["quantool/core/registry.py", "quantool/core/base.py", "quantool/methods/llm_compressor/base.py",
-             "quantool/methods/llm_compressor/gptq/gptq.py", "quantool/methods/llm_compressor/awq/awq.py",
-             "quantool/methods/llm_compressor/smoothquant/smoothquant.py", "quantool/utils/dataset_textifier.py"]
     out["provenance"] = {
         "generator": "tests/golden/make_boundary_fixtures.py",
-        "reference_files_sha1": {f: hashlib.sha1((REF_SRC / f).read_bytes()).hexdigest() for f in files},
+        "reference_files_sha1": reference_sha1(),
         "stand_ins": sorted(k.split("/")[0] for k in STUBS if k.count("/") == 1),
         "note": "outputs of the reference's own plumbing on this repo's probe inputs; the engine behind "
                 "oneshot and the modifiers are recording stand-ins (not installed in the container)",
@@ -325,5 +327,15 @@ def main():
           f"{len(rows)} row, {len(prep)} prepare cases")
 
 
+def check() -> int:
+    """--check: is the stored fixture current with the reference files it was generated from?"""
+    recorded = json.loads(OUT.read_text())["provenance"]["reference_files_sha1"]
+    stale = [f for f, h in reference_sha1().items() if recorded.get(f) != h]
+    print(f"{OUT.name}: " + (f"stale for {stale}" if stale else "current with the reference files"))
+    return 1 if stale else 0
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--check"]:
+        raise SystemExit(check())
     main()
