@@ -269,6 +269,41 @@ int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, fl
 /* Host-only self-check of the bf16x3 block-row planner (runs without a GPU): 0 if every k chunk of every tile is
  * covered exactly once and the slab / reduction tables are consistent, else a negative code. */
 int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, int* n_slabs_out, int* longest_out);
+/* ---- A8 runtime: W8A8 / INT8 / W4A8 checkpoints on the int8 MFMA --------------------------------------
+ * The inference side of the 8-bit dynamic per-token activation block these checkpoints carry
+ * (config_groups.group_0.input_activations): activations are quantised per row on the fly and multiplied with the
+ * stored integer weights in int32, as a served W8A8 runtime does.
+ *
+ * qt_quantize_tokens_i8: X [M, K] bf16 / fp16 (x_dtype), row pitch ldx >= K (any) -> Xq int8 [M, K] (pitch K),
+ * s_x fp32 [M], zp_x int32 [M] (asymmetric only; may be NULL when symmetric).  col_perm (int32 [K], may be NULL):
+ * Xq[m, k] = q(X[m, col_perm[k]]).  Per row, all in fp32 (SURVEY A.2 calculate_qparams / fake_quantize, 8 bits,
+ * qmin = -128, qmax = 127):
+ *   min = min(min_k x, 0), max = max(max_k x, 0)
+ *   symmetric:  s = max(|min|, |max|) / 127.5, zp = 0       (divisor recalled, not pinned: DESIGN.md 4.7)
+ *   asymmetric: s = (max - min) / 255
+ *   s = max(s, FLT_EPSILON);  asymmetric: zp = clamp(rint(qmin - min / s), qmin, qmax)
+ *   q = rint(clamp(x / s + zp, qmin, qmax))        IEEE division, round half to even, clamp before rounding
+ *
+ * qt_gemm_i8: Y [M, N] (out_dtype bf16 / fp16, row pitch ldy) = epilogue(Xq . Wq^T), both operands K-contiguous.
+ *   w_format QT_W_INT8:        Wq int8 [N, K]
+ *   w_format QT_W_INT4_PACKED: Wq int32 [N, ceil(K/8)], nibble j of word w = level of column 8w + j, plus 8
+ *                              (qt_pack_int4's layout); unpacked to int8 on chip
+ *   s_w fp32 [N, G]: G = 1 (channel-wise) or G = ceil(K/128) (groups of 128 contiguous columns)
+ *   zp_x int32 [M] (may be NULL: symmetric activations); wsum int32 [N, G] = per-group row sums of the weight levels
+ *   (read only with zp_x);  bias [N] in out_dtype (may be NULL).  K <= 32768 (the int32 accumulator cannot overflow).
+ * Fixed fp32 sequence, no contraction -- a restatement of these steps is equal to the bit:
+ *   acc_g[m, n] = sum_{k in g} Xq[m, k] * Wq[n, k]              int32, exact
+ *   t_g  = (float)(acc_g - zp_x[m] * wsum[n, g])                 int32 difference, one rounding to fp32
+ *   tot  = 0.0f;  tot = tot + s_w[n, g] * t_g  for g = 0, 1, ... ascending (product and sum rounded separately)
+ *   y    = s_x[m] * tot;  y = y + (float)bias[n]  (when bias is given)
+ *   Y[m, n] = y rounded once to out_dtype (round to nearest even) */
+enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
+int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
+                          int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
+int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+               const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+               int out_dtype, int64_t ldy, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

@@ -1,0 +1,453 @@
+// W8A8 / W4A8 inference path: dynamic per-token int8 activations and an int8 x int8 GEMM with an int32 accumulator on
+// the i8 MFMA (v_mfma_i32_32x32x32_i8), for checkpoints this project writes (include/quantool_amd.h, "A8 runtime").
+//
+// qt_quantize_tokens_i8   one workgroup per row: a min/max pass, then a quantise pass over the same row (L2-resident).
+// qt_gemm_i8              128 x 128 output tile per 4-wave workgroup, k-step 128 (= the weight group), register-staged
+//                         single LDS buffer (A and B, 144-B rows: 36 KB); each wave owns 64 x 64 = 2 x 2 MFMA tiles.
+//                         Packed int4 weights are unpacked to int8 between the global load and the LDS store.
+//
+// Numerics are the header's fixed sequence; -ffp-contract=off (csrc/build.py) keeps every multiply and add its own
+// rounding, so a torch restatement of the same steps is equal to the bit.
+#include <float.h>
+
+#include "common.h"
+
+namespace {
+
+// Symmetric activation divisor: max(|min|, |max|) / ((qmax - qmin) / 2) with qmin = -128, qmax = 127, as the weight
+// observer's /7.5 for 4 bits (SURVEY A.2 calculate_qparams, recalled, not pinned against the upstream
+// source).  vLLM's own dynamic int8 path divides by 127 instead; a checkpoint's numbers are only reproduced by the
+// divisor its calibration used, so the constant has one home.
+constexpr float kActSymDivisor = 127.5f;
+constexpr float kActAsymDivisor = 255.0f;
+constexpr float kQmin = -128.0f;
+constexpr float kQmax = 127.0f;
+
+constexpr int QT_THREADS = 256;
+
+__device__ __forceinline__ float ld_x(const unsigned short* X, int dtype, size_t idx) {
+    return qt_h16_to_f32(X[idx], dtype);
+}
+
+__device__ __forceinline__ int q_one(float x, float s, float zp) {
+    float v = x / s + zp;
+    v = fminf(fmaxf(v, kQmin), kQmax);
+    return (int)__builtin_rintf(v);
+}
+
+__global__ void __launch_bounds__(QT_THREADS) quantize_tokens_kernel(const unsigned short* __restrict__ X, int dtype,
+                                                                     int K, int64_t ldx,
+                                                                     const int32_t* __restrict__ col_perm, int symmetric,
+                                                                     int vec, int8_t* __restrict__ Xq,
+                                                                     float* __restrict__ s_x,
+                                                                     int32_t* __restrict__ zp_x) {
+    __shared__ float red[2][QT_THREADS / 64];
+    const int64_t m = blockIdx.x;
+    const unsigned short* row = X + m * ldx;
+    int8_t* qrow = Xq + m * (int64_t)K;
+    const int tid = threadIdx.x;
+
+    float mn = 0.0f, mx = 0.0f;   // min(min_k x, 0), max(max_k x, 0): start from 0
+    if (vec) {
+        for (int k = tid * 8; k < K; k += QT_THREADS * 8) {
+            const uint4 u = *(const uint4*)(row + k);
+            const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float a = qt_h16_to_f32((unsigned short)(w[i] & 0xffffu), dtype);
+                const float b = qt_h16_to_f32((unsigned short)(w[i] >> 16), dtype);
+                mn = fminf(mn, fminf(a, b));
+                mx = fmaxf(mx, fmaxf(a, b));
+            }
+        }
+    } else {
+        for (int k = tid; k < K; k += QT_THREADS) {
+            const float a = ld_x(row, dtype, k);
+            mn = fminf(mn, a);
+            mx = fmaxf(mx, a);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, off));
+        mx = fmaxf(mx, __shfl_xor(mx, off));
+    }
+    if ((tid & 63) == 0) {
+        red[0][tid >> 6] = mn;
+        red[1][tid >> 6] = mx;
+    }
+    __syncthreads();
+    mn = red[0][0];
+    mx = red[1][0];
+#pragma unroll
+    for (int w = 1; w < QT_THREADS / 64; ++w) {
+        mn = fminf(mn, red[0][w]);
+        mx = fmaxf(mx, red[1][w]);
+    }
+    float s, zp = 0.0f;
+    if (symmetric) {
+        s = fmaxf(-mn, mx) / kActSymDivisor;
+        s = fmaxf(s, FLT_EPSILON);
+    } else {
+        s = (mx - mn) / kActAsymDivisor;
+        s = fmaxf(s, FLT_EPSILON);
+        zp = fminf(fmaxf(__builtin_rintf(kQmin - mn / s), kQmin), kQmax);
+    }
+    if (tid == 0) {
+        s_x[m] = s;
+        if (zp_x) zp_x[m] = (int32_t)zp;
+    }
+
+    if (vec) {   // no col_perm, K % 8 == 0: 8 elements -> one 8-byte store
+        for (int k = tid * 8; k < K; k += QT_THREADS * 8) {
+            const uint4 u = *(const uint4*)(row + k);
+            const unsigned w[4] = {u.x, u.y, u.z, u.w};
+            unsigned o[2] = {0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int qa = q_one(qt_h16_to_f32((unsigned short)(w[i] & 0xffffu), dtype), s, zp);
+                const int qb = q_one(qt_h16_to_f32((unsigned short)(w[i] >> 16), dtype), s, zp);
+                o[i >> 1] |= (((unsigned)qa & 0xffu) | (((unsigned)qb & 0xffu) << 8)) << (16 * (i & 1));
+            }
+            *(uint2*)(qrow + k) = make_uint2(o[0], o[1]);
+        }
+    } else {
+        for (int k = tid; k < K; k += QT_THREADS) {
+            const int src = col_perm ? col_perm[k] : k;
+            qrow[k] = (int8_t)q_one(ld_x(row, dtype, src), s, zp);
+        }
+    }
+}
+
+// ---- GEMM ---------------------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
+
+constexpr int BM = 128, BN = 128, BK = 128;
+constexpr int LDS_ROW = BK + 16;            // bytes; 36-dword pitch keeps eight lanes' ds_read_b128 on disjoint banks
+constexpr int GROUP_M = 16;                 // m-tiles that walk the n-tiles together (a weight tile is read by 16
+                                            // neighbouring workgroups while it is cache-resident)
+constexpr int A_CHUNKS = BM * BK / 16 / QT_THREADS;        // 16-byte chunks of the A tile per thread: 4
+constexpr int B8_CHUNKS = BN * BK / 16 / QT_THREADS;       // int8 weights: 4
+constexpr int B4_CHUNKS = BN * BK / 2 / 16 / QT_THREADS;   // packed int4 weights (64 B per row per k-step): 2
+
+// packed word (nibble j = level + 8 of column 8w + j) -> 8 int8 levels, column order
+__device__ __forceinline__ uint2 unpack_int4_word(unsigned w) {
+    const unsigned lo = w & 0x0f0f0f0fu;          // nibbles 0, 2, 4, 6 in bytes 0..3
+    const unsigned hi = (w >> 4) & 0x0f0f0f0fu;   // nibbles 1, 3, 5, 7
+    // interleave: bytes [lo0 hi0 lo1 hi1] and [lo2 hi2 lo3 hi3] (v_perm_b32: selector byte i picks from {hi:lo}
+    // of the first / second operand: 0..3 -> second operand's bytes, 4..7 -> first operand's)
+    unsigned a = __builtin_amdgcn_perm(hi, lo, 0x05010400u);
+    unsigned b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+    // x - 8 per byte for x in 0..15 without borrows: (x + 0x78) ^ 0x80
+    a = (a + 0x78787878u) ^ 0x80808080u;
+    b = (b + 0x78787878u) ^ 0x80808080u;
+    return make_uint2(a, b);
+}
+
+// One 16-byte chunk of a K-contiguous int8 row [k, k + 16), zero beyond K / beyond the matrix.
+template <bool VEC>
+__device__ __forceinline__ uint4 load_row16(const int8_t* rowp, bool row_ok, int k, int K) {
+    if (VEC) {
+        if (row_ok && k < K) return *(const uint4*)(rowp + k);
+        return make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (row_ok) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (k + i < K) w[i >> 2] |= ((unsigned)(uint8_t)rowp[k + i]) << (8 * (i & 3));
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// 4 packed words [w, w + 4) of one weight row (32 columns), zero beyond Kw words / beyond the matrix
+template <bool VEC>
+__device__ __forceinline__ uint4 load_words4(const int32_t* rowp, bool row_ok, int w, int Kw) {
+    if (VEC) {
+        if (row_ok && w < Kw) return *(const uint4*)(rowp + w);
+        return make_uint4(0x88888888u, 0x88888888u, 0x88888888u, 0x88888888u);   // level 0
+    } else {
+        unsigned v[4] = {0x88888888u, 0x88888888u, 0x88888888u, 0x88888888u};
+        if (row_ok) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (w + i < Kw) v[i] = (unsigned)rowp[w + i];
+        }
+        return make_uint4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+struct GemmArgs {
+    const int8_t* Xq;
+    const void* Wq;
+    const float* s_x;
+    const int32_t* zp_x;
+    const float* s_w;
+    const int32_t* wsum;
+    const void* bias;
+    void* Y;
+    int64_t M;
+    int N, K, G;
+    int64_t ldy;
+    int out_dtype;
+};
+
+// INT4: Wq is int32 [N, ceil(K/8)]; else int8 [N, K].  GROUPED: G = ceil(K/128) groups of 128 columns (the epilogue
+// runs after every k-step), else one group.  ASYM: zp_x / wsum given.  VEC: 16-byte loads are in bounds and aligned.
+template <bool INT4, bool GROUPED, bool ASYM, bool VEC>
+__global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p) {
+    __shared__ __attribute__((aligned(16))) int8_t lds[(BM + BN) * LDS_ROW + BM * 4];
+    int8_t* sA = lds;
+    int8_t* sB = lds + BM * LDS_ROW;
+    int32_t* sZp = (int32_t*)(lds + (BM + BN) * LDS_ROW);
+
+    // tile order: GROUP_M m-tiles walk the n-tiles together
+    const int tiles_n = (p.N + BN - 1) / BN;
+    const int64_t tiles_m = (p.M + BM - 1) / BM;
+    const int64_t pid = blockIdx.x;
+    const int64_t per_group = (int64_t)GROUP_M * tiles_n;
+    const int64_t gid = pid / per_group;
+    const int64_t first_m = gid * GROUP_M;
+    const int64_t gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
+    const int64_t in_g = pid % per_group;
+    const int64_t tile_m = first_m + in_g % gsize;
+    const int tile_n = (int)(in_g / gsize);
+    const int64_t m0 = tile_m * BM;
+    const int n0 = tile_n * BN;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wm = (wave >> 1) * 64;      // wave's 64 x 64 sub-tile
+    const int wn = (wave & 1) * 64;
+    const int lr = lane & 31;             // A row / B column of this lane's fragment
+    const int lh = lane >> 5;             // which 16 bytes of the 32-deep k-step
+
+    if (ASYM) {
+        if (tid < BM) sZp[tid] = (m0 + tid < p.M) ? p.zp_x[m0 + tid] : 0;
+    }
+
+    const int Kw = (p.K + 7) / 8;
+    const int nk = (p.K + BK - 1) / BK;
+
+    // staging: A chunk c of thread t is row (c * 256 + t) / 8, bytes 16 * ((c * 256 + t) % 8)
+    uint4 ra[A_CHUNKS];
+    uint4 rb[INT4 ? B4_CHUNKS : B8_CHUNKS];
+
+    auto load_tiles = [&](int kt) {
+        const int k0 = kt * BK;
+#pragma unroll
+        for (int c = 0; c < A_CHUNKS; ++c) {
+            const int idx = c * QT_THREADS + tid;
+            const int r = idx >> 3;
+            const int64_t m = m0 + r;
+            ra[c] = load_row16<VEC>(p.Xq + m * (int64_t)p.K, m < p.M, k0 + 16 * (idx & 7), p.K);
+        }
+        if (INT4) {
+#pragma unroll
+            for (int c = 0; c < B4_CHUNKS; ++c) {
+                const int idx = c * QT_THREADS + tid;
+                const int r = idx >> 2;            // 4 chunks of 4 words per row
+                const int n = n0 + r;
+                rb[c] = load_words4<VEC>((const int32_t*)p.Wq + (int64_t)n * Kw, n < p.N, k0 / 8 + 4 * (idx & 3), Kw);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < B8_CHUNKS; ++c) {
+                const int idx = c * QT_THREADS + tid;
+                const int r = idx >> 3;
+                const int n = n0 + r;
+                rb[c] = load_row16<VEC>((const int8_t*)p.Wq + (int64_t)n * p.K, n < p.N, k0 + 16 * (idx & 7), p.K);
+            }
+        }
+    };
+    auto store_tiles = [&]() {
+#pragma unroll
+        for (int c = 0; c < A_CHUNKS; ++c) {
+            const int idx = c * QT_THREADS + tid;
+            *(uint4*)(sA + (idx >> 3) * LDS_ROW + 16 * (idx & 7)) = ra[c];
+        }
+        if (INT4) {
+#pragma unroll
+            for (int c = 0; c < B4_CHUNKS; ++c) {
+                const int idx = c * QT_THREADS + tid;
+                const uint2 a = unpack_int4_word(rb[c].x), b = unpack_int4_word(rb[c].y);
+                const uint2 d = unpack_int4_word(rb[c].z), e = unpack_int4_word(rb[c].w);
+                int8_t* dst = sB + (idx >> 2) * LDS_ROW + 32 * (idx & 3);
+                *(uint4*)dst = make_uint4(a.x, a.y, b.x, b.y);
+                *(uint4*)(dst + 16) = make_uint4(d.x, d.y, e.x, e.y);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < B8_CHUNKS; ++c) {
+                const int idx = c * QT_THREADS + tid;
+                *(uint4*)(sB + (idx >> 3) * LDS_ROW + 16 * (idx & 7)) = rb[c];
+            }
+        }
+    };
+
+    i32x16 acc[2][2];
+    f32x16 tot[GROUPED ? 2 : 1][GROUPED ? 2 : 1];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (i32x16){};
+    if (GROUPED) {
+#pragma unroll
+        for (int i = 0; i < (GROUPED ? 2 : 1); ++i)
+#pragma unroll
+            for (int j = 0; j < (GROUPED ? 2 : 1); ++j) tot[i][j] = (f32x16){};
+    }
+
+    // the lane's output columns (C/D map of the 32x32 MFMA: column = lane & 31; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
+    int ncol[2];
+    bool nok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        ncol[j] = n0 + wn + 32 * j + lr;
+        nok[j] = ncol[j] < p.N;
+    }
+
+    // t_g = (float)(acc_g - zp_x[m] * wsum[n, g]);  the group's weight scale applied by the caller.  zoff is an
+    // opaque 0: it keeps the 32 row zero-points of a lane in LDS, re-read per group, instead of letting the compiler
+    // hoist them into registers out of the k-loop (which spills the grouped asymmetric form).
+    auto group_term = [&](int i, int j, int r, int ws, int zoff) -> float {
+        int a = acc[i][j][r];
+        if (ASYM) {
+            const int row = wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            a = a - sZp[row + zoff] * ws;
+        }
+        return (float)a;
+    };
+    auto wsum_at = [&](int j, int g) -> int { return (ASYM && nok[j]) ? p.wsum[(int64_t)ncol[j] * p.G + g] : 0; };
+
+    load_tiles(0);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();             // previous k-step's fragment reads are done
+        store_tiles();
+        __syncthreads();
+        if (kt + 1 < nk) load_tiles(kt + 1);   // in flight during this k-step's MFMAs
+#pragma unroll
+        for (int ks = 0; ks < BK / 32; ++ks) {
+            i32x4 fa[2], fb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+                fa[i] = *(const i32x4*)(sA + (wm + 32 * i + lr) * LDS_ROW + 32 * ks + 16 * lh);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                fb[j] = *(const i32x4*)(sB + (wn + 32 * j + lr) * LDS_ROW + 32 * ks + 16 * lh);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        }
+        if (GROUPED) {   // tot += s_w[n, g] * t_g, ascending g
+            int zoff = 0;
+            if (ASYM) asm volatile("" : "+v"(zoff));
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float sw = nok[j] ? p.s_w[(int64_t)ncol[j] * p.G + kt] : 0.0f;
+                const int ws = wsum_at(j, kt);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float t = group_term(i, j, r, ws, zoff);
+                        const float prod = sw * t;
+                        tot[i][j][r] = tot[i][j][r] + prod;
+                    }
+                    acc[i][j] = (i32x16){};
+                }
+            }
+        }
+    }
+
+    // y = s_x[m] * tot (+ bias[n]), one rounding to the output dtype
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (!nok[j]) continue;
+        const int n = ncol[j];
+        float bn = 0.0f;
+        if (p.bias) bn = qt_load_w(p.bias, p.out_dtype, n);
+        const float sw0 = GROUPED ? 0.0f : p.s_w[(int64_t)n * p.G];
+        const int ws0 = GROUPED ? 0 : wsum_at(j, 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (m >= p.M) continue;
+                float tv;
+                if (GROUPED) {
+                    tv = tot[i][j][r];
+                } else {
+                    const float prod = sw0 * group_term(i, j, r, ws0, 0);
+                    tv = 0.0f + prod;
+                }
+                float y = p.s_x[m] * tv;
+                if (p.bias) y = y + bn;
+                qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n), y);
+            }
+        }
+    }
+}
+
+template <bool INT4, bool GROUPED, bool ASYM>
+void launch_vec(bool vec, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+    if (vec) hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, true>), grid, dim3(QT_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, false>), grid, dim3(QT_THREADS), 0, stream, a);
+}
+template <bool INT4, bool GROUPED>
+void launch_asym(bool asym, bool vec, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+    if (asym) launch_vec<INT4, GROUPED, true>(vec, grid, stream, a);
+    else launch_vec<INT4, GROUPED, false>(vec, grid, stream, a);
+}
+
+}  // namespace
+
+extern "C" int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
+                                     int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(X && Xq && s_x && M > 0 && K > 0 && ldx >= K, "qt_quantize_tokens_i8: bad arguments");
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "qt_quantize_tokens_i8: x_dtype %d must be bf16 or fp16", x_dtype);
+    QT_CHECK_ARG(symmetric || zp_x, "qt_quantize_tokens_i8: asymmetric activations need zp_x");
+    QT_CHECK_ARG(M <= 0x7fffffffLL, "qt_quantize_tokens_i8: M %lld too large", (long long)M);
+    const int vec = !col_perm && K % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)X & 15) == 0;
+    hipLaunchKernelGGL(quantize_tokens_kernel, dim3((unsigned)M), dim3(QT_THREADS), 0, stream,
+                       (const unsigned short*)X, x_dtype, K, ldx, col_perm, symmetric, vec, Xq, s_x,
+                       symmetric ? nullptr : zp_x);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                          const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                          int out_dtype, int64_t ldy, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && M > 0 && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8: bad arguments");
+    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8: K %d > 32768 (the int32 accumulator bound)", K);
+    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8: w_format %d unsupported", w_format);
+    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8: out_dtype %d must be bf16 or fp16", out_dtype);
+    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8: G %d must be 1 or ceil(K / 128) = %d", G, (K + 127) / 128);
+    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8: zp_x needs wsum");
+    const int64_t tiles = ((M + BM - 1) / BM) * (int64_t)((N + BN - 1) / BN);
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8: too many tiles");
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    const bool grouped = G > 1;
+    const bool asym = zp_x != nullptr;
+    const bool vec = (((uintptr_t)Xq | (uintptr_t)Wq) & 15) == 0 && K % 16 == 0 && (!int4 || ((K + 7) / 8) % 4 == 0);
+    GemmArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, G, ldy, out_dtype};
+    const dim3 grid((unsigned)tiles);
+    if (int4) {
+        if (grouped) launch_asym<true, true>(asym, vec, grid, stream, a);
+        else launch_asym<true, false>(asym, vec, grid, stream, a);
+    } else {
+        if (grouped) launch_asym<false, true>(asym, vec, grid, stream, a);
+        else launch_asym<false, false>(asym, vec, grid, stream, a);
+    }
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}

@@ -19,6 +19,7 @@ QT_ERR_HIP = -4
 QT_ERR_UNSUPPORTED = -5
 
 QT_F32, QT_BF16, QT_F16 = 0, 1, 2
+QT_W_INT8, QT_W_INT4_PACKED = 0, 1
 
 # name -> (restype, argtypes); mirrors include/quantool_amd.h one to one
 SIGNATURES = {
@@ -90,6 +91,10 @@ SIGNATURES = {
     "qt_profile_read": (c_int, [c_int, c_void_p, c_void_p]),
     "qt_dequantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                               c_int, c_int64, c_void_p]),
+    "qt_quantize_tokens_i8": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "qt_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                           c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
 }
 
 _lib = None

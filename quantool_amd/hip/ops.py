@@ -466,6 +466,92 @@ def dequantize(Qt: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor, g_of_col
     return out
 
 
+# ---- A8 runtime: dynamic per-token int8 activations, int8 x int8 GEMM ------------------------------
+def quantize_tokens_i8(X: torch.Tensor, symmetric: bool = True, col_perm: Optional[torch.Tensor] = None):
+    """X [M, K] bf16 / fp16 (unit column stride, any row pitch) -> (Xq int8 [M, K], s_x fp32 [M], zp_x int32 [M] or
+    None when symmetric); with ``col_perm`` (int32 [K]) Xq[m, k] = q(X[m, col_perm[k]])."""
+    lib = load()
+    code = _act16(X, "X")
+    if X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
+                         f"strides {X.stride()}")
+    M, K = X.shape
+    if M == 0 or K == 0:
+        raise ValueError(f"X must be non-empty, got shape {tuple(X.shape)}")
+    if col_perm is not None:
+        _req(col_perm, torch.int32, "col_perm", 1)
+        if col_perm.numel() != K or not col_perm.is_contiguous():
+            raise ValueError(f"col_perm must be contiguous int32 [{K}]")
+    Xq = torch.empty((M, K), dtype=torch.int8, device=X.device)
+    s_x = torch.empty(M, dtype=torch.float32, device=X.device)
+    zp_x = None if symmetric else torch.empty(M, dtype=torch.int32, device=X.device)
+    check("qt_quantize_tokens_i8", lib.qt_quantize_tokens_i8(
+        X.data_ptr(), code, M, K, X.stride(0), _ptr(col_perm), int(bool(symmetric)), Xq.data_ptr(), s_x.data_ptr(),
+        _ptr(zp_x), _stream()))
+    return Xq, s_x, zp_x
+
+
+def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
+            zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+            bias: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """Y [M, N] = s_x[m] * sum_g s_w[n, g] * (acc_g - zp_x[m] * wsum[n, g]) (+ bias): the fixed sequence of
+    ``qt_gemm_i8`` (include/quantool_amd.h).  Wq int8 [N, K], or packed int4 int32 [N, ceil(K/8)] (then ``K`` is
+    required); s_w fp32 [N, G], G = 1 or ceil(K/128); zp_x int32 [M] needs wsum int32 [N, G]."""
+    lib = load()
+    _req(Xq, torch.int8, "Xq", 2)
+    M, Kx = Xq.shape
+    if not Xq.is_contiguous():
+        raise ValueError("Xq must be contiguous [M, K]")
+    if not Wq.is_cuda or Wq.dim() != 2 or not Wq.is_contiguous():
+        raise ValueError("Wq must be a contiguous 2-d device tensor")
+    N = Wq.shape[0]
+    if Wq.dtype == torch.int8:
+        fmt = _lib.QT_W_INT8
+        if Wq.shape[1] != Kx or (K is not None and K != Kx):
+            raise ValueError(f"int8 Wq must be [N, {Kx}], got {tuple(Wq.shape)}")
+    elif Wq.dtype == torch.int32:
+        fmt = _lib.QT_W_INT4_PACKED
+        if K is not None and K != Kx:
+            raise ValueError(f"K={K} but Xq has {Kx} columns")
+        if Wq.shape[1] != (Kx + 7) // 8:
+            raise ValueError(f"packed int4 Wq must be [N, ceil(K/8) = {(Kx + 7) // 8}], got {tuple(Wq.shape)}")
+    else:
+        raise TypeError(f"Wq must be int8 [N, K] or packed int4 int32 [N, ceil(K/8)], got {Wq.dtype}")
+    K = Kx
+    if M == 0 or N == 0 or K == 0:
+        raise ValueError(f"empty GEMM: M={M}, N={N}, K={K}")
+    if K > 32768:
+        raise ValueError(f"K={K} > 32768: the int32 accumulator could overflow")
+    _req(s_x, torch.float32, "s_x", 1)
+    _req(s_w, torch.float32, "s_w", 2)
+    G = s_w.shape[1]
+    if s_x.numel() != M or not s_x.is_contiguous():
+        raise ValueError(f"s_x must be contiguous fp32 [{M}]")
+    if s_w.shape[0] != N or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
+        raise ValueError(f"s_w must be contiguous fp32 [{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
+    if zp_x is not None:
+        _req(zp_x, torch.int32, "zp_x", 1)
+        if zp_x.numel() != M or not zp_x.is_contiguous():
+            raise ValueError(f"zp_x must be contiguous int32 [{M}]")
+        if wsum is None:
+            raise ValueError("zp_x needs wsum (per-group row sums of the weight levels)")
+    if wsum is not None:
+        _req(wsum, torch.int32, "wsum", 2)
+        if tuple(wsum.shape) != (N, G) or not wsum.is_contiguous():
+            raise ValueError(f"wsum must be contiguous int32 [{N}, {G}]")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"out_dtype must be bf16 or fp16, got {out_dtype}")
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8", lib.qt_gemm_i8(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
 # ---- a12  AWQ ------------------------------------------------------------------------------
 def _w2d(W: torch.Tensor):
     if W.dim() != 2 or not W.is_cuda or W.stride(1) != 1:
