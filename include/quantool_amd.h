@@ -304,6 +304,45 @@ int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format,
                const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                int out_dtype, int64_t ldy, qt_stream_t stream);
 
+/* ---- Routed experts: W8A8 / INT8 / W4A8 sparse-MoE banks on the same int8 GEMM ------------------------------
+ * The A8 expert forward (engine/qlinear.py QuantizedExperts) restates transformers' MixtralExperts.forward with the
+ * two F.linear calls replaced by the A8 runtime above:
+ *   route -> quantize_tokens_i8 (all T tokens once) -> gemm_i8_grouped (gate_up, rows gathered by src_token)
+ *   -> act_fn(gate) * up in torch -> quantize_tokens_i8 (routed rows) -> gemm_i8_grouped (down, contiguous) -> combine
+ * Per-token quantisation is a function of the row alone, so quantising the T tokens and gathering equals gathering
+ * and quantising.
+ *
+ * qt_moe_route: top_k_index [T, k] (int32, or int64 when index_is_int64) -> offsets int32 [E + 1],
+ *   src_token / src_slot int32 [T k], row_of int32 [T k] (may be NULL).  The routed rows are the entries (t, j) with
+ *   0 <= top_k_index[t, j] < E (others are dropped, as transformers' loop skips expert_idx == num_experts), sorted by
+ *   expert and, within an expert, by the flat index t k + j (token ascending): a stable argsort of the flattened
+ *   table.  (transformers' torch.where(expert_mask[e]) lists an expert's rows slot-major; the order of rows within an
+ *   expert changes no output -- every row is computed alone and the combine sums per token.)
+ *   Row r in [offsets[e], offsets[e + 1]) is (src_token[r], src_slot[r]); row_of[t k + j] = its row, or -1 when
+ *   dropped; rows [offsets[E], T k) read 0.  Integer work in one workgroup, no atomics, no host read; E <= 256.
+ *
+ * qt_gemm_i8_grouped: qt_gemm_i8 over E weight matrices at once.  Y [R, N] (pitch ldy): expert e owns output rows
+ *   [offsets[e], offsets[e + 1]) (offsets int32 [E + 1], on the device, ascending, offsets[E] <= R; rows past
+ *   offsets[E] are not written) and weight matrix e of Wq ([E, N, K] int8 or [E, N, ceil(K/8)] packed int4), s_w
+ *   fp32 [E, N, G], wsum int32 [E, N, G].  A row of output row m is Xq[row_idx[m]] (row_idx int32 [R], values index
+ *   rows of Xq; the caller's contract) or Xq[m] when row_idx is NULL; s_x and zp_x are read at the same index.
+ *   Every expert's rows are equal to the bit to qt_gemm_i8 on that expert's (gathered) rows: it is the same tile code
+ *   and the same fixed fp32 epilogue.  The grid is (ceil(R/128) + E) m-tiles x n-tiles, an upper bound that needs no
+ *   host read of the counts; each workgroup finds its expert from offsets and surplus workgroups exit.  No bias.
+ *
+ * qt_moe_combine: out [T, H] (dtype bf16 / fp16) = the weighted sum of each token's routed rows of Y [R, H] (pitch
+ *   ldy), transformers' MixtralExperts.forward restated: for the token's rows r = row_of[t k + j] >= 0 in ascending
+ *   row order (= ascending expert), with w = weights[t, j] fp32 [T, k]:
+ *     c = round_to_dtype((float)Y[r, h] * w);  out = round_to_dtype(out + c),  out starting at 0
+ *   k <= 16; one workgroup per token, no atomics: deterministic. */
+int qt_moe_route(const void* top_k_index, int index_is_int64, int64_t T, int k, int E, int32_t* offsets,
+                 int32_t* src_token, int32_t* src_slot, int32_t* row_of, qt_stream_t stream);
+int qt_gemm_i8_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets, int E,
+                       const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x, const float* s_w,
+                       int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
+                   int64_t T, int k, void* out, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

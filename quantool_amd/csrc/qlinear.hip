@@ -192,11 +192,19 @@ struct GemmArgs {
     int N, K, G;
     int64_t ldy;
     int out_dtype;
+    // grouped (MOE) form only: expert e owns rows [offsets[e], offsets[e + 1]) of Y and the e-th weight matrix;
+    // A row m (and s_x / zp_x) is read at row_idx[m] when row_idx is given, else at m
+    const int32_t* offsets;
+    const int32_t* row_idx;
+    int E;
 };
 
 // INT4: Wq is int32 [N, ceil(K/8)]; else int8 [N, K].  GROUPED: G = ceil(K/128) groups of 128 columns (the epilogue
 // runs after every k-step), else one group.  ASYM: zp_x / wsum given.  VEC: 16-byte loads are in bounds and aligned.
-template <bool INT4, bool GROUPED, bool ASYM, bool VEC>
+// MOE: the grouped form (qt_gemm_i8_grouped): p.M is the routed-row count R and the grid holds ceil(R/BM) + E m-tiles
+// per n-tile, an upper bound on sum_e ceil(rows_e / BM); each workgroup finds its expert from p.offsets, surplus
+// workgroups exit.  Everything after that lookup is the same tile code.
+template <bool INT4, bool GROUPED, bool ASYM, bool VEC, bool MOE>
 __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p) {
     __shared__ __attribute__((aligned(16))) int8_t lds[(BM + BN) * LDS_ROW + BM * 4];
     int8_t* sA = lds;
@@ -205,7 +213,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
 
     // tile order: GROUP_M m-tiles walk the n-tiles together
     const int tiles_n = (p.N + BN - 1) / BN;
-    const int64_t tiles_m = (p.M + BM - 1) / BM;
+    const int64_t tiles_m = (p.M + BM - 1) / BM + (MOE ? p.E : 0);
     const int64_t pid = blockIdx.x;
     const int64_t per_group = (int64_t)GROUP_M * tiles_n;
     const int64_t gid = pid / per_group;
@@ -214,8 +222,38 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
     const int64_t in_g = pid % per_group;
     const int64_t tile_m = first_m + in_g % gsize;
     const int tile_n = (int)(in_g / gsize);
-    const int64_t m0 = tile_m * BM;
+    int64_t m0 = tile_m * BM;
+    int64_t m_end = p.M;                  // rows [m0, m_end) of this tile's matrix exist
     const int n0 = tile_n * BN;
+    const void* Wq = p.Wq;
+    const float* s_w = p.s_w;
+    const int32_t* wsum = p.wsum;
+    if constexpr (MOE) {
+        // virtual m-tile tile_m -> (expert, tile within the expert); offsets clamped to [0, R] so a bad table cannot
+        // move a write out of Y
+        int64_t start = 0;
+        int e = -1;
+        for (int j = 0; j < p.E; ++j) {
+            const int64_t lo = min(max((int64_t)p.offsets[j], (int64_t)0), p.M);
+            const int64_t hi = min(max((int64_t)p.offsets[j + 1], lo), p.M);
+            const int64_t nt = (hi - lo + BM - 1) / BM;
+            if (tile_m < start + nt) {
+                e = j;
+                m0 = lo + (tile_m - start) * BM;
+                m_end = hi;
+                break;
+            }
+            start += nt;
+        }
+        if (e < 0) return;                // surplus workgroup (uniform: before any barrier)
+        const int64_t wrow = INT4 ? (int64_t)((p.K + 7) / 8) : (int64_t)p.K;
+        Wq = INT4 ? (const void*)((const int32_t*)p.Wq + (int64_t)e * p.N * wrow)
+                  : (const void*)((const int8_t*)p.Wq + (int64_t)e * p.N * wrow);
+        s_w = p.s_w + (int64_t)e * p.N * p.G;
+        if (wsum) wsum = p.wsum + (int64_t)e * p.N * p.G;
+    }
+    // the A / s_x / zp_x row of output row m
+    auto src_row = [&](int64_t m) -> int64_t { return (MOE && p.row_idx) ? (int64_t)p.row_idx[m] : m; };
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -226,7 +264,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
     const int lh = lane >> 5;             // which 16 bytes of the 32-deep k-step
 
     if (ASYM) {
-        if (tid < BM) sZp[tid] = (m0 + tid < p.M) ? p.zp_x[m0 + tid] : 0;
+        if (tid < BM) sZp[tid] = (m0 + tid < m_end) ? p.zp_x[src_row(m0 + tid)] : 0;
     }
 
     const int Kw = (p.K + 7) / 8;
@@ -235,15 +273,27 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
     // staging: A chunk c of thread t is row (c * 256 + t) / 8, bytes 16 * ((c * 256 + t) % 8)
     uint4 ra[A_CHUNKS];
     uint4 rb[INT4 ? B4_CHUNKS : B8_CHUNKS];
+    const int8_t* arow[MOE ? A_CHUNKS : 1];   // grouped form: the gathered A rows, looked up once (nullptr: no row)
+    if constexpr (MOE) {
+#pragma unroll
+        for (int c = 0; c < A_CHUNKS; ++c) {
+            const int64_t m = m0 + ((c * QT_THREADS + tid) >> 3);
+            arow[c] = m < m_end ? p.Xq + src_row(m) * (int64_t)p.K : nullptr;
+        }
+    }
 
     auto load_tiles = [&](int kt) {
         const int k0 = kt * BK;
 #pragma unroll
         for (int c = 0; c < A_CHUNKS; ++c) {
             const int idx = c * QT_THREADS + tid;
-            const int r = idx >> 3;
-            const int64_t m = m0 + r;
-            ra[c] = load_row16<VEC>(p.Xq + m * (int64_t)p.K, m < p.M, k0 + 16 * (idx & 7), p.K);
+            if constexpr (MOE) {
+                ra[c] = load_row16<VEC>(arow[c], arow[c] != nullptr, k0 + 16 * (idx & 7), p.K);
+            } else {
+                const int r = idx >> 3;
+                const int64_t m = m0 + r;
+                ra[c] = load_row16<VEC>(p.Xq + m * (int64_t)p.K, m < p.M, k0 + 16 * (idx & 7), p.K);
+            }
         }
         if (INT4) {
 #pragma unroll
@@ -251,7 +301,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
                 const int idx = c * QT_THREADS + tid;
                 const int r = idx >> 2;            // 4 chunks of 4 words per row
                 const int n = n0 + r;
-                rb[c] = load_words4<VEC>((const int32_t*)p.Wq + (int64_t)n * Kw, n < p.N, k0 / 8 + 4 * (idx & 3), Kw);
+                rb[c] = load_words4<VEC>((const int32_t*)Wq + (int64_t)n * Kw, n < p.N, k0 / 8 + 4 * (idx & 3), Kw);
             }
         } else {
 #pragma unroll
@@ -259,7 +309,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
                 const int idx = c * QT_THREADS + tid;
                 const int r = idx >> 3;
                 const int n = n0 + r;
-                rb[c] = load_row16<VEC>((const int8_t*)p.Wq + (int64_t)n * p.K, n < p.N, k0 + 16 * (idx & 7), p.K);
+                rb[c] = load_row16<VEC>((const int8_t*)Wq + (int64_t)n * p.K, n < p.N, k0 + 16 * (idx & 7), p.K);
             }
         }
     };
@@ -321,7 +371,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
         }
         return (float)a;
     };
-    auto wsum_at = [&](int j, int g) -> int { return (ASYM && nok[j]) ? p.wsum[(int64_t)ncol[j] * p.G + g] : 0; };
+    auto wsum_at = [&](int j, int g) -> int { return (ASYM && nok[j]) ? wsum[(int64_t)ncol[j] * p.G + g] : 0; };
 
     load_tiles(0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -349,7 +399,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
             if (ASYM) asm volatile("" : "+v"(zoff));
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const float sw = nok[j] ? p.s_w[(int64_t)ncol[j] * p.G + kt] : 0.0f;
+                const float sw = nok[j] ? s_w[(int64_t)ncol[j] * p.G + kt] : 0.0f;
                 const int ws = wsum_at(j, kt);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
@@ -372,14 +422,14 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
         const int n = ncol[j];
         float bn = 0.0f;
         if (p.bias) bn = qt_load_w(p.bias, p.out_dtype, n);
-        const float sw0 = GROUPED ? 0.0f : p.s_w[(int64_t)n * p.G];
+        const float sw0 = GROUPED ? 0.0f : s_w[(int64_t)n * p.G];
         const int ws0 = GROUPED ? 0 : wsum_at(j, 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m >= p.M) continue;
+                if (m >= m_end) continue;
                 float tv;
                 if (GROUPED) {
                     tv = tot[i][j][r];
@@ -387,7 +437,7 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
                     const float prod = sw0 * group_term(i, j, r, ws0, 0);
                     tv = 0.0f + prod;
                 }
-                float y = p.s_x[m] * tv;
+                float y = p.s_x[src_row(m)] * tv;
                 if (p.bias) y = y + bn;
                 qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n), y);
             }
@@ -395,15 +445,25 @@ __global__ void __launch_bounds__(QT_THREADS, 2) gemm_i8_kernel(const GemmArgs p
     }
 }
 
-template <bool INT4, bool GROUPED, bool ASYM>
+template <bool INT4, bool GROUPED, bool ASYM, bool MOE>
 void launch_vec(bool vec, dim3 grid, hipStream_t stream, const GemmArgs& a) {
-    if (vec) hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, true>), grid, dim3(QT_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, false>), grid, dim3(QT_THREADS), 0, stream, a);
+    if (vec) hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, true, MOE>), grid, dim3(QT_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((gemm_i8_kernel<INT4, GROUPED, ASYM, false, MOE>), grid, dim3(QT_THREADS), 0, stream, a);
 }
-template <bool INT4, bool GROUPED>
+template <bool INT4, bool GROUPED, bool MOE>
 void launch_asym(bool asym, bool vec, dim3 grid, hipStream_t stream, const GemmArgs& a) {
-    if (asym) launch_vec<INT4, GROUPED, true>(vec, grid, stream, a);
-    else launch_vec<INT4, GROUPED, false>(vec, grid, stream, a);
+    if (asym) launch_vec<INT4, GROUPED, true, MOE>(vec, grid, stream, a);
+    else launch_vec<INT4, GROUPED, false, MOE>(vec, grid, stream, a);
+}
+template <bool MOE>
+void launch_gemm(bool int4, bool grouped, bool asym, bool vec, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+    if (int4) {
+        if (grouped) launch_asym<true, true, MOE>(asym, vec, grid, stream, a);
+        else launch_asym<true, false, MOE>(asym, vec, grid, stream, a);
+    } else {
+        if (grouped) launch_asym<false, true, MOE>(asym, vec, grid, stream, a);
+        else launch_asym<false, false, MOE>(asym, vec, grid, stream, a);
+    }
 }
 
 }  // namespace
@@ -439,15 +499,36 @@ extern "C" int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, in
     const bool grouped = G > 1;
     const bool asym = zp_x != nullptr;
     const bool vec = (((uintptr_t)Xq | (uintptr_t)Wq) & 15) == 0 && K % 16 == 0 && (!int4 || ((K + 7) / 8) % 4 == 0);
-    GemmArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, G, ldy, out_dtype};
-    const dim3 grid((unsigned)tiles);
-    if (int4) {
-        if (grouped) launch_asym<true, true>(asym, vec, grid, stream, a);
-        else launch_asym<true, false>(asym, vec, grid, stream, a);
-    } else {
-        if (grouped) launch_asym<false, true>(asym, vec, grid, stream, a);
-        else launch_asym<false, false>(asym, vec, grid, stream, a);
-    }
+    GemmArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, G, ldy, out_dtype, nullptr, nullptr, 0};
+    launch_gemm<false>(int4, grouped, asym, vec, dim3((unsigned)tiles), stream, a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_i8_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets,
+                                  int E, const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
+                                  const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
+                                  qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(Xq && Wq && offsets && s_x && s_w && Y && R > 0 && E > 0 && N > 0 && K > 0 && ldy >= N,
+                 "qt_gemm_i8_grouped: bad arguments");
+    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_grouped: K %d > 32768 (the int32 accumulator bound)", K);
+    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8_grouped: w_format %d unsupported",
+                 w_format);
+    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_grouped: out_dtype %d must be bf16 or fp16", out_dtype);
+    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8_grouped: G %d must be 1 or ceil(K / 128) = %d", G,
+                 (K + 127) / 128);
+    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_grouped: zp_x needs wsum");
+    QT_CHECK_ARG(R <= 0x7fffffffLL && E <= 4096, "qt_gemm_i8_grouped: R %lld or E %d too large", (long long)R, E);
+    const int64_t tiles = ((R + BM - 1) / BM + E) * (int64_t)((N + BN - 1) / BN);
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_grouped: too many tiles");
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    const int64_t wrow_bytes = int4 ? (int64_t)((K + 7) / 8) * 4 : (int64_t)K;
+    // 16-byte loads need every expert's matrix aligned as well as the base
+    const bool vec = (((uintptr_t)Xq | (uintptr_t)Wq) & 15) == 0 && K % 16 == 0 && (!int4 || ((K + 7) / 8) % 4 == 0) &&
+                     ((int64_t)N * wrow_bytes) % 16 == 0;
+    GemmArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, nullptr, Y, R, N, K, G, ldy, out_dtype, offsets, row_idx, E};
+    launch_gemm<true>(int4, G > 1, zp_x != nullptr, vec, dim3((unsigned)tiles), stream, a);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

@@ -9,9 +9,16 @@ Linear either
 * a plain ``nn.Linear`` holding the dequantised weight ``(q - zp) * scale`` (W4A16, W4A16_ASYM, W8A16), computed once in
   fp32 from the STORED scale and rounded once to the model dtype.
 
+Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up_proj [E, 2I, H]`` / ``down_proj
+[E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
+``<layer>.block_sparse_moe.experts.{e}.w1 / w3 / w2``, otherwise ``<layer>.mlp.experts.{e}.gate_proj / up_proj /
+down_proj``).  The loader inverts that write: A16 experts are dequantised into the fused parameters
+(``gate_up_proj[e] = cat(w1, w3)``, ``down_proj[e] = w2``); A8 experts replace the bank with a ``QuantizedExperts``
+that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` + ``qt_moe_combine``).
+
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
-weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward`` needs the
-HIP library.
+weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward`` and
+``QuantizedExperts.forward`` need the HIP library.
 """
 from __future__ import annotations
 
@@ -29,6 +36,8 @@ GROUP = 128   # the W4A8 group size the GEMM takes
 _LEAVES = ("weight", "weight_packed", "weight_scale", "weight_zero_point", "weight_g_idx", "weight_shape")
 # per-expert names expert_bank_checkpoint_names writes (<bank>.experts.{e}.<proj>)
 _EXPERT_RE = re.compile(r"\.experts\.\d+\.")
+# <bank>.{e}.<proj> -- a per-expert module name, split
+_EXPERT_NAME = re.compile(r"^(?P<bank>.+\.experts)\.(?P<e>\d+)\.(?P<proj>[^.]+)$")
 
 
 def unpack_int4(packed: torch.Tensor, K: int) -> torch.Tensor:
@@ -100,6 +109,63 @@ class QuantizedLinear(nn.Module):
         y = ops.gemm_i8(Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
                         wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
         return y.reshape(*lead, self.out_features)
+
+
+class QuantizedExperts(nn.Module):
+    """A W8A8 / INT8 / W4A8 routed-expert bank: ``forward(hidden_states, top_k_index, top_k_weights)`` as
+    transformers' ``MixtralExperts`` with its two ``F.linear`` calls on the int8 GEMM.
+
+    The routed rows are ordered by expert (``qt_moe_route``); the T tokens are quantised once per token and the gate_up
+    GEMM gathers them by token; ``act_fn(gate) * up`` runs in torch as the fused module does; the routed rows are
+    quantised per row and the down GEMM reads them in place; ``qt_moe_combine`` sums each token's weighted rows in
+    ascending expert order, rounding as ``index_add_`` does.  include/quantool_amd.h states every step.
+
+    Buffers: ``gate_up`` int8 [E, 2I, H] or packed int4 int32 [E, 2I, ceil(H/8)] (rows [0, I) gate, [I, 2I) up),
+    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_wsum`` int32 [E, 2I, G]; ``down`` int8 [E, H, I] or int32
+    [E, H, ceil(I/8)], ``down_scale`` fp32 [E, H, G'], ``down_wsum`` int32 [E, H, G']."""
+
+    def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
+                 down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
+        super().__init__()
+        self.num_experts = int(gate_up.shape[0])
+        self.hidden_dim = int(hidden_size)
+        self.intermediate_dim = int(intermediate_size)
+        self.act_fn = act_fn
+        self.act_symmetric = bool(act_symmetric)
+        self.int4 = gate_up.dtype == torch.int32
+        for name, w, s, K in (("gate_up", gate_up, gate_up_scale, self.hidden_dim),
+                              ("down", down, down_scale, self.intermediate_dim)):
+            E, N = w.shape[:2]
+            levels = unpack_int4(w.reshape(E * N, -1), K) if self.int4 else w.reshape(E * N, K)
+            G = s.shape[2]
+            self.register_buffer(name, w.contiguous())
+            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
+            self.register_buffer(f"{name}_wsum", group_sums(levels, G).reshape(E, N, G))
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
+                f"weights={'int4 g128' if self.int4 else 'int8'}, "
+                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
+                f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token")
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        from ..hip import ops
+
+        x = hidden_states.reshape(-1, self.hidden_dim)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
+        sym = self.act_symmetric
+        Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=sym)
+        gu = ops.gemm_i8_grouped(Xq, s_x, self.gate_up, self.gate_up_scale, offsets, row_idx=src_token,
+                                 K=self.hidden_dim, zp_x=zp_x, wsum=None if sym else self.gate_up_wsum,
+                                 out_dtype=x.dtype)
+        gate, up = gu.chunk(2, dim=-1)
+        h = self.act_fn(gate) * up
+        Hq, s_h, zp_h = ops.quantize_tokens_i8(h, symmetric=sym)
+        y = ops.gemm_i8_grouped(Hq, s_h, self.down, self.down_scale, offsets, K=self.intermediate_dim, zp_x=zp_h,
+                                wsum=None if sym else self.down_wsum, out_dtype=x.dtype)
+        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
 
 
 # ---- the loader ------------------------------------------------------------------------------------------------------
@@ -210,13 +276,144 @@ def _model_dtype(cfg: dict, dtype) -> torch.dtype:
     return {"bfloat16": torch.bfloat16, "float16": torch.float16, "float32": torch.float32}.get(name, torch.bfloat16)
 
 
+def _is_fused_bank(m: nn.Module) -> bool:
+    """A transformers >= 5 expert bank: 3-d ``gate_up_proj`` / ``down_proj`` parameters and an ``act_fn``."""
+    gu, dn = getattr(m, "gate_up_proj", None), getattr(m, "down_proj", None)
+    return (isinstance(gu, nn.Parameter) and isinstance(dn, nn.Parameter) and gu.dim() == 3 and dn.dim() == 3
+            and hasattr(m, "act_fn"))
+
+
+def _expert_banks(path, model: nn.Module, model_type, dense: Dict[str, torch.Tensor],
+                  quant: Dict[str, Dict[str, torch.Tensor]]):
+    """Undo ``expert_bank_checkpoint_names``: rename ``dense`` back to the model's names in place, and take every
+    per-expert tensor out of ``dense`` / ``quant``.  Returns ({bank: {e: {proj: ("q", leaves) | ("dense", tensor)}}},
+    {checkpoint prefix: model prefix}).  proj is gate_proj / up_proj / down_proj."""
+    from .sequential import expert_bank_module_renames, expert_layout, rename_module_prefix as _rename
+
+    banks = {n: m for n, m in model.named_modules() if _is_fused_bank(m)}
+    inverse = {v: k for k, v in expert_bank_module_renames(banks, model_type).items()}
+    _, leafs = expert_layout(model_type)
+    proj_of = {v: k for k, v in leafs.items()}            # checkpoint leaf (w1) -> fused role (gate_proj)
+    renamed = {_rename(k, inverse): v for k, v in dense.items()}
+    dense.clear()
+    dense.update(renamed)
+    found: Dict[str, Dict[int, Dict[str, tuple]]] = {}
+
+    def place(name: str, kind: str, value) -> bool:
+        m = _EXPERT_NAME.match(_rename(name, inverse))
+        if m is None:
+            return False
+        bank, e, proj = m.group("bank"), int(m.group("e")), m.group("proj")
+        if bank not in banks:
+            return False
+        if proj not in proj_of:
+            raise ValueError(f"{path}: {name}: {proj!r} is none of the expert Linears {sorted(proj_of)}")
+        E = banks[bank].gate_up_proj.shape[0]
+        if e >= E:
+            raise ValueError(f"{path}: {name}: expert {e} of a bank of {E}")
+        found.setdefault(bank, {}).setdefault(e, {})[proj_of[proj]] = (kind, value)
+        return True
+
+    for name in [n for n in quant if _EXPERT_RE.search(n + ".")]:
+        m = _EXPERT_NAME.match(_rename(name, inverse))
+        if m is None or m.group("bank") not in banks:
+            raise NotImplementedError(
+                f"{path}: routed-expert weights ({name}) without a fused expert bank at that place in the "
+                f"{type(model).__name__} built from config.json; this loader maps per-expert Linears back to a "
+                "transformers >= 5 gate_up_proj / down_proj bank only")
+        place(name, "q", quant.pop(name))
+    for key in [k for k in dense if _EXPERT_RE.search(k)]:
+        mod, _, leaf = key.rpartition(".")
+        if _EXPERT_NAME.match(mod) is None or _EXPERT_NAME.match(mod).group("bank") not in banks:
+            continue                                       # not ours: load_state_dict reports it
+        if leaf != "weight":
+            raise NotImplementedError(f"{path}: {key}: experts with a {leaf} are not supported (the expert bank "
+                                      "this loader rebuilds has no bias)")
+        place(mod, "dense", dense.pop(key))
+    for bank in found:
+        if any("bias" in n for n, _ in banks[bank].named_parameters()):
+            raise NotImplementedError(f"{path}: {bank} has expert biases, which this loader does not read")
+    return banks, found
+
+
+def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[str, tuple]], a8: bool,
+               act_symmetric: bool, mdtype: torch.dtype, dev) -> Optional[nn.Module]:
+    """Fill (A16, dense) or replace (A8: the returned ``QuantizedExperts``) one fused bank from its experts."""
+    gu, dn = bank.gate_up_proj, bank.down_proj
+    E, I2, H = gu.shape
+    I = I2 // 2
+    roles = ("gate_proj", "up_proj", "down_proj")
+    missing = [f"{e}.{r}" for e in range(E) for r in roles if r not in experts.get(e, {})]
+    if missing:
+        raise ValueError(f"{path}: {bank_name}: experts missing from the checkpoint: {missing[:6]}")
+    kinds = {experts[e][r][0] for e in range(E) for r in roles}
+    if len(kinds) > 1:
+        raise ValueError(f"{path}: {bank_name} is only partly quantized (some expert Linears are dense); the bank "
+                         "runs as one unit, so every expert Linear must share a scheme")
+    want = {"gate_proj": (I, H), "up_proj": (I, H), "down_proj": (H, I)}
+
+    def shape_check(e, r, shape):
+        if tuple(shape) != want[r]:
+            raise ValueError(f"{path}: {bank_name}.{e}.{r} has shape {tuple(shape)} in the checkpoint, {want[r]} in "
+                             "the model")
+
+    if kinds == {"dense"} or not a8:
+        for e in range(E):
+            W = {}
+            for r in roles:
+                kind, v = experts[e][r]
+                W[r] = v.to(dev).to(mdtype) if kind == "dense" else dequantized_weight(
+                    f"{bank_name}.{e}.{r}", {k: t.to(dev) for k, t in v.items()}, mdtype)
+                shape_check(e, r, W[r].shape)
+            gu.data[e] = torch.cat([W["gate_proj"], W["up_proj"]], 0)
+            dn.data[e] = W["down_proj"]
+        return None
+
+    stacked = {}
+    for part, rs in (("gate_up", ("gate_proj", "up_proj")), ("down", ("down_proj",))):
+        ws, ss = [], []
+        for e in range(E):
+            for r in rs:
+                name = f"{bank_name}.{e}.{r}"
+                t = {k: v.to(dev) for k, v in experts[e][r][1].items()}
+                if "weight_g_idx" in t:
+                    raise NotImplementedError(f"{path}: {name}: A8 expert weights with weight_g_idx (actorder "
+                                              "'group') need a per-expert column permutation, which the grouped "
+                                              "GEMM does not take; quantise with actorder 'static'")
+                if "weight_zero_point" in t:
+                    raise ValueError(f"{path}: {name}: an A8 checkpoint with weight_zero_point -- the int8 GEMM has "
+                                     "no weight zero-point term (W8A8, INT8 and W4A8 weights are symmetric)")
+                w, N, K, _ = _levels_and_shape(name, t)
+                shape_check(e, r, (N, K))
+                scale = t["weight_scale"].to(torch.float32)
+                if scale.shape[0] != N or scale.shape[1] not in (1, (K + GROUP - 1) // GROUP):
+                    raise ValueError(f"{path}: {name}: weight_scale {tuple(scale.shape)} is neither channel-wise nor "
+                                     f"groups of {GROUP} over {K} columns")
+                ws.append(w)
+                ss.append(scale)
+        if len({w.dtype for w in ws}) > 1 or len({s.shape[1] for s in ss}) > 1:
+            raise ValueError(f"{path}: {bank_name}: the {part} weights of the experts mix formats or group counts")
+        per = len(rs)
+        stacked[part] = (torch.stack([torch.cat(ws[e * per:(e + 1) * per], 0) for e in range(E)]),
+                         torch.stack([torch.cat(ss[e * per:(e + 1) * per], 0) for e in range(E)]))
+    if stacked["gate_up"][0].dtype != stacked["down"][0].dtype:
+        raise ValueError(f"{path}: {bank_name}: gate_up and down weights differ in format")
+    return QuantizedExperts(H, I, *stacked["gate_up"], *stacked["down"], bank.act_fn, act_symmetric)
+
+
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or dequantised ``nn.Linear``s (A16 schemes) in place of its quantized Linears.
 
-    Refused with ``ValueError`` / ``NotImplementedError``: float-quantized checkpoints, routed-expert banks (a grouped
-    expert GEMM does not exist yet), any ``input_activations`` block other than 8-bit dynamic per-token, and an A8
-    checkpoint that carries ``weight_zero_point``."""
+    Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
+    bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
+    ``quantization_config.ignore``): A16 experts are dequantised into ``gate_up_proj`` / ``down_proj``; A8 experts
+    replace the bank with a ``QuantizedExperts``.
+
+    Refused with ``ValueError`` / ``NotImplementedError``: float-quantized checkpoints, any ``input_activations`` block
+    other than 8-bit dynamic per-token, an A8 checkpoint that carries ``weight_zero_point``, routed-expert weights
+    where the model has no fused bank, A8 expert weights with ``weight_g_idx``, experts with a bias, and banks with
+    experts missing or only partly quantized."""
     from transformers import AutoConfig, AutoModelForCausalLM
 
     path = Path(path)
@@ -233,10 +430,6 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
                                   "activations to 8-bit integers per token, dynamically")
     state = load_state(path)
     dense, quant = _split_state(state)
-    experts = sorted(m for m in quant if _EXPERT_RE.search(m + "."))
-    if experts:
-        raise NotImplementedError(f"{path}: routed-expert weights ({experts[0]}, ... {len(experts)} modules) need a "
-                                  "grouped expert GEMM, which this runtime does not have yet")
 
     mdtype = _model_dtype(cfg, dtype)
     model_type = cfg.pop("model_type")
@@ -248,16 +441,23 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
         model = AutoModelForCausalLM.from_config(config, torch_dtype=mdtype)
     model.eval()
 
+    banks, experts = _expert_banks(path, model, model_type, dense, quant)
     missing, unexpected = model.load_state_dict(dense, strict=False)
     if unexpected:
         raise ValueError(f"{path}: unexpected tensors {sorted(unexpected)[:8]}")
     allowed = {f"{m}.weight" for m in quant}
+    allowed |= {f"{b}.{p}" for b in experts for p in ("gate_up_proj", "down_proj")}
     bad = sorted(set(missing) - allowed)
     if bad:
         raise ValueError(f"{path}: tensors missing from the checkpoint: {bad[:8]}")
 
     a8 = acts is not None
     act_symmetric = bool(acts.get("symmetric", True)) if a8 else True
+    for bank_name, by_expert in experts.items():
+        new = _load_bank(path, bank_name, banks[bank_name], by_expert, a8, act_symmetric, mdtype, dev)
+        if new is not None:
+            parent_name, _, leaf = bank_name.rpartition(".")
+            setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
     for name, t in quant.items():
         lin = model.get_submodule(name)
         if not isinstance(lin, nn.Linear):
@@ -278,5 +478,9 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
                              f"{tuple(lin.weight.shape)} in the model")
         parent_name, _, leaf = name.rpartition(".")
         setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
-    model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts}
+    from .sequential import expert_bank_module_renames, rename_module_prefix as _rename
+
+    inverse = {v: k for k, v in expert_bank_module_renames(banks, model_type).items()}
+    ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
+    model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
     return model

@@ -552,6 +552,128 @@ def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Te
     return Y
 
 
+def moe_route(top_k_index: torch.Tensor, num_experts: int):
+    """top_k_index [T, k] int32 / int64 -> (offsets int32 [E+1], src_token int32 [T k], src_slot int32 [T k],
+    row_of int32 [T k]): ``qt_moe_route`` (include/quantool_amd.h).  Rows sorted by expert, then by token; an index
+    outside [0, E) is dropped (row_of -1).  All on the device, no host read."""
+    lib = load()
+    if not top_k_index.is_cuda or top_k_index.dtype not in (torch.int32, torch.int64) or top_k_index.dim() != 2:
+        raise ValueError("top_k_index must be a 2-d int32 / int64 device tensor [T, k]")
+    top_k_index = top_k_index.contiguous()
+    T, k = top_k_index.shape
+    E = int(num_experts)
+    if T == 0 or k == 0 or not 0 < E <= 256:
+        raise ValueError(f"moe_route: T={T}, k={k}, E={E} (need T, k > 0 and 0 < E <= 256)")
+    dev = top_k_index.device
+    offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    src_token = torch.empty(T * k, dtype=torch.int32, device=dev)
+    src_slot = torch.empty(T * k, dtype=torch.int32, device=dev)
+    row_of = torch.empty(T * k, dtype=torch.int32, device=dev)
+    check("qt_moe_route", lib.qt_moe_route(
+        top_k_index.data_ptr(), int(top_k_index.dtype == torch.int64), T, k, E, offsets.data_ptr(),
+        src_token.data_ptr(), src_slot.data_ptr(), row_of.data_ptr(), _stream()))
+    return offsets, src_token, src_slot, row_of
+
+
+def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor,
+                    *, rows: Optional[int] = None, row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                    zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                    out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``qt_gemm_i8`` over E weight matrices: Y [R, N], expert e owning rows [offsets[e], offsets[e+1]) (include/
+    quantool_amd.h qt_gemm_i8_grouped).  Wq int8 [E, N, K] or packed int4 int32 [E, N, ceil(K/8)] (then ``K`` is
+    required); s_w fp32 [E, N, G]; wsum int32 [E, N, G] (needed with zp_x).  A rows: Xq[row_idx[m]] when ``row_idx``
+    (int32 [R], e.g. ``moe_route``'s src_token) is given, with s_x / zp_x read at the same index; else Xq[m] (then R
+    defaults to Xq's rows).  Rows past offsets[E] are left unwritten."""
+    lib = load()
+    _req(Xq, torch.int8, "Xq", 2)
+    Mx, Kx = Xq.shape
+    if not Xq.is_contiguous():
+        raise ValueError("Xq must be contiguous [M, K]")
+    if not Wq.is_cuda or Wq.dim() != 3 or not Wq.is_contiguous():
+        raise ValueError("Wq must be a contiguous 3-d device tensor [E, N, K or ceil(K/8)]")
+    E, N = Wq.shape[:2]
+    if Wq.dtype == torch.int8:
+        fmt = _lib.QT_W_INT8
+        if Wq.shape[2] != Kx or (K is not None and K != Kx):
+            raise ValueError(f"int8 Wq must be [E, N, {Kx}], got {tuple(Wq.shape)}")
+    elif Wq.dtype == torch.int32:
+        fmt = _lib.QT_W_INT4_PACKED
+        if K is not None and K != Kx:
+            raise ValueError(f"K={K} but Xq has {Kx} columns")
+        if Wq.shape[2] != (Kx + 7) // 8:
+            raise ValueError(f"packed int4 Wq must be [E, N, ceil(K/8) = {(Kx + 7) // 8}], got {tuple(Wq.shape)}")
+    else:
+        raise TypeError(f"Wq must be int8 [E, N, K] or packed int4 int32 [E, N, ceil(K/8)], got {Wq.dtype}")
+    K = Kx
+    if Mx == 0 or N == 0 or K == 0 or E == 0:
+        raise ValueError(f"empty GEMM: M={Mx}, E={E}, N={N}, K={K}")
+    if K > 32768:
+        raise ValueError(f"K={K} > 32768: the int32 accumulator could overflow")
+    _req(offsets, torch.int32, "offsets", 1)
+    if offsets.numel() != E + 1 or not offsets.is_contiguous():
+        raise ValueError(f"offsets must be contiguous int32 [E + 1 = {E + 1}]")
+    if row_idx is not None:
+        _req(row_idx, torch.int32, "row_idx", 1)
+        if not row_idx.is_contiguous():
+            raise ValueError("row_idx must be contiguous int32 [R]")
+        R = row_idx.numel() if rows is None else int(rows)
+        if R > row_idx.numel():
+            raise ValueError(f"rows={R} but row_idx has {row_idx.numel()} entries")
+    else:
+        R = Mx if rows is None else int(rows)
+        if R > Mx:
+            raise ValueError(f"rows={R} but Xq has {Mx} rows (contiguous A)")
+    if R <= 0:
+        raise ValueError(f"rows must be positive, got {R}")
+    _req(s_x, torch.float32, "s_x", 1)
+    _req(s_w, torch.float32, "s_w", 3)
+    G = s_w.shape[2]
+    if s_x.numel() != Mx or not s_x.is_contiguous():
+        raise ValueError(f"s_x must be contiguous fp32 [{Mx}]")
+    if tuple(s_w.shape[:2]) != (E, N) or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
+        raise ValueError(f"s_w must be contiguous fp32 [{E}, {N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
+    if zp_x is not None:
+        _req(zp_x, torch.int32, "zp_x", 1)
+        if zp_x.numel() != Mx or not zp_x.is_contiguous():
+            raise ValueError(f"zp_x must be contiguous int32 [{Mx}]")
+        if wsum is None:
+            raise ValueError("zp_x needs wsum (per-group row sums of the weight levels)")
+    if wsum is not None:
+        _req(wsum, torch.int32, "wsum", 3)
+        if tuple(wsum.shape) != (E, N, G) or not wsum.is_contiguous():
+            raise ValueError(f"wsum must be contiguous int32 [{E}, {N}, {G}]")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"out_dtype must be bf16 or fp16, got {out_dtype}")
+    Y = torch.empty((R, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8_grouped", lib.qt_gemm_i8_grouped(
+        Xq.data_ptr(), K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x),
+        s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
+def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+    """out [T, H] = each token's routed rows of Y [R, H] weighted by top_k_weights [T, k] and summed in ascending
+    expert order, rounding to Y's dtype after every product and sum (``qt_moe_combine``)."""
+    lib = load()
+    code = _act16(Y, "Y")
+    if Y.dim() != 2 or Y.stride(1) != 1:
+        raise ValueError(f"Y must be 2-d [R, H] with unit column stride, got shape {tuple(Y.shape)}")
+    _req(row_of, torch.int32, "row_of", 1)
+    if not top_k_weights.is_cuda or top_k_weights.dim() != 2 or not top_k_weights.is_floating_point():
+        raise ValueError("top_k_weights must be a 2-d floating device tensor [T, k]")
+    T, k = top_k_weights.shape
+    if row_of.numel() != T * k or not row_of.is_contiguous():
+        raise ValueError(f"row_of must be contiguous int32 [{T * k}]")
+    if T == 0 or not 0 < k <= 16:
+        raise ValueError(f"moe_combine: T={T}, k={k} (need T > 0 and 0 < k <= 16)")
+    w = top_k_weights.to(torch.float32).contiguous()      # bf16 / fp16 widen exactly
+    H = Y.shape[1]
+    out = torch.empty((T, H), dtype=Y.dtype, device=Y.device)
+    check("qt_moe_combine", lib.qt_moe_combine(
+        Y.data_ptr(), code, H, Y.stride(0), row_of.data_ptr(), w.data_ptr(), T, k, out.data_ptr(), _stream()))
+    return out
+
+
 # ---- a12  AWQ ------------------------------------------------------------------------------
 def _w2d(W: torch.Tensor):
     if W.dim() != 2 or not W.is_cuda or W.stride(1) != 1:

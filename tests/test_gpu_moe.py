@@ -1,0 +1,377 @@
+"""The routed-expert runtime on the GPU: ``qt_moe_route`` against a stable argsort, ``qt_gemm_i8_grouped`` against
+per-expert ``qt_gemm_i8`` bit for bit, ``qt_moe_combine`` against a torch restatement of transformers' loop,
+``QuantizedExperts.forward`` against a pure-torch restatement, and tiny Mixtral checkpoints end to end."""
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+EPS = torch.finfo(torch.float32).eps
+
+
+# ---- torch restatements (copied from tests/test_gpu_qlinear.py; test helpers, not part of the package) ---------------
+def ref_quantize_tokens(X, symmetric, col_perm=None):
+    x = X.detach().cpu().float()
+    mn = torch.clamp(x.amin(1), max=0.0)
+    mx = torch.clamp(x.amax(1), min=0.0)
+    if symmetric:
+        s = torch.maximum(-mn, mx) / 127.5
+        s = torch.clamp(s, min=EPS)
+        zp = torch.zeros_like(s)
+    else:
+        s = (mx - mn) / 255.0
+        s = torch.clamp(s, min=EPS)
+        zp = torch.clamp(torch.round(-128.0 - mn / s), -128.0, 127.0)
+    if col_perm is not None:
+        x = x[:, col_perm.cpu().long()]
+    q = torch.round(torch.clamp(x / s[:, None] + zp[:, None], -128.0, 127.0)).to(torch.int8)
+    return q, s, (None if symmetric else zp.to(torch.int32))
+
+
+def ref_acc(Xq, Wq8, G):
+    """acc_g [G, M, N] int64 from exact fp64 products."""
+    X = Xq.cpu().double()
+    W = Wq8.cpu().double()
+    K = X.shape[1]
+    step = K if G == 1 else 128
+    return torch.stack([(X[:, g * step:(g + 1) * step] @ W[:, g * step:(g + 1) * step].T).round().long()
+                        for g in range(G)])
+
+
+def ref_gemm(Xq, s_x, Wq8, s_w, zp_x=None, wsum=None, bias=None, out_dtype=torch.bfloat16):
+    G = s_w.shape[1]
+    acc = ref_acc(Xq, Wq8, G)
+    s_w = s_w.cpu()
+    tot = torch.zeros(acc.shape[1:], dtype=torch.float32)
+    for g in range(G):
+        a = acc[g]
+        if zp_x is not None:
+            a = a - zp_x.cpu().long()[:, None] * wsum.cpu().long()[None, :, g]
+        t = a.to(torch.float32)
+        prod = s_w[None, :, g] * t
+        tot = tot + prod
+    y = s_x.cpu()[:, None] * tot
+    if bias is not None:
+        y = y + bias.cpu().float()[None, :]
+    return y.to(out_dtype)
+
+
+def _bits_equal(a, b):
+    a, b = a.cpu(), b.cpu()
+    assert a.shape == b.shape and a.dtype == b.dtype
+    if a.is_floating_point():
+        a, b = a.view(torch.int16), b.view(torch.int16)
+    bad = (a != b).nonzero()
+    assert bad.numel() == 0, f"{bad.shape[0]} of {a.numel()} differ, first at {bad[0].tolist()}"
+
+
+def _levels(shape, bits, seed):
+    g = torch.Generator().manual_seed(seed)
+    lo, hi = (-8, 8) if bits == 4 else (-128, 128)
+    return torch.randint(lo, hi, shape, generator=g, dtype=torch.int8)
+
+
+def _acts(M, K, dtype, dev, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, K, generator=g)
+    x[:, torch.randperm(K, generator=g)[: max(1, K // 64)]] *= 10
+    return x.to(dtype).to(dev)
+
+
+# ---- routing references ---------------------------------------------------------------------------------------------
+def ref_route(idx, E):
+    """Stable argsort of the flattened table by expert; entries outside [0, E) dropped."""
+    flat = idx.cpu().long().reshape(-1)
+    k = idx.shape[1]
+    valid = (flat >= 0) & (flat < E)
+    key = torch.where(valid, flat, torch.full_like(flat, E))
+    order = torch.argsort(key, stable=True)
+    n = int(valid.sum())
+    order = order[:n]
+    offsets = torch.zeros(E + 1, dtype=torch.int32)
+    offsets[1:] = torch.cumsum(torch.bincount(flat[valid], minlength=E), 0).to(torch.int32)
+    row_of = torch.full((flat.numel(),), -1, dtype=torch.int32)
+    row_of[order] = torch.arange(n, dtype=torch.int32)
+    return offsets, (order // k).to(torch.int32), (order % k).to(torch.int32), row_of
+
+
+def ref_combine(Y, idx, w, E, row_of):
+    """transformers' MixtralExperts loop: per expert ascending, out = round(out + round(y * w))."""
+    Y, w, row_of = Y.cpu(), w.cpu().float(), row_of.cpu().long()
+    T, k = idx.shape
+    idx = idx.cpu().long()
+    out = torch.zeros(T, Y.shape[1], dtype=Y.dtype)
+    for e in range(E):
+        tok, pos = torch.where(idx == e)
+        if tok.numel() == 0:
+            continue
+        rows = row_of[tok * k + pos]
+        c = (Y[rows].float() * w[tok, pos, None]).to(Y.dtype)
+        out[tok] = (out[tok].float() + c.float()).to(Y.dtype)
+    return out
+
+
+def _random_routing(T, k, E, seed, experts=None):
+    g = torch.Generator().manual_seed(seed)
+    pool = torch.arange(E) if experts is None else torch.tensor(experts)
+    return torch.stack([pool[torch.randperm(len(pool), generator=g)[:k]] for _ in range(T)])
+
+
+# ---- qt_moe_route ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T,k,E,experts,dtype", [(513, 2, 8, None, torch.int64), (1, 2, 8, None, torch.int64),
+                                                 (300, 2, 8, [1, 5, 6], torch.int32), (4096, 4, 64, None, torch.int64),
+                                                 (777, 8, 256, None, torch.int32), (1000, 1, 3, None, torch.int64)])
+def test_route_is_a_stable_argsort(ops, dev, T, k, E, experts, dtype):
+    idx = _random_routing(T, k, E, seed=T + E, experts=experts).to(dtype)
+    offsets, src_token, src_slot, row_of = ops.moe_route(idx.to(dev), E)
+    torch.cuda.synchronize()
+    ro, rt, rs, rr = ref_route(idx, E)
+    _bits_equal(offsets, ro)
+    _bits_equal(src_token, rt)
+    _bits_equal(src_slot, rs)
+    _bits_equal(row_of, rr)
+
+
+def test_route_drops_out_of_range_indices(ops, dev):
+    E = 4
+    idx = _random_routing(50, 2, E, seed=1)
+    idx[3, 0] = E                 # transformers' loop skips expert_idx == num_experts
+    idx[7, 1] = -1
+    idx[49, 0] = 99
+    offsets, src_token, src_slot, row_of = ops.moe_route(idx.to(dev), E)
+    torch.cuda.synchronize()
+    ro, rt, rs, rr = ref_route(idx, E)
+    assert int(offsets[-1]) == 100 - 3
+    _bits_equal(offsets, ro)
+    _bits_equal(src_token[:97], rt)
+    _bits_equal(src_slot[:97], rs)
+    assert int(src_token[97:].abs().sum()) == 0
+    _bits_equal(row_of, rr)
+
+
+# ---- qt_gemm_i8_grouped ---------------------------------------------------------------------------------------------
+def _grouped_case(dev, E, counts, N, K, bits, grouped, asym, dtype, seed):
+    """Routing with the given rows per expert (k = 1 over T = sum(counts) tokens), weights and activations."""
+    T = sum(counts)
+    idx = torch.cat([torch.full((c,), e, dtype=torch.int64) for e, c in enumerate(counts)])
+    idx = idx[torch.randperm(T, generator=torch.Generator().manual_seed(seed))].reshape(T, 1)
+    X = _acts(T, K, dtype, dev, seed)
+    Xq, s_x, zp_x = ops_mod().quantize_tokens_i8(X, symmetric=not asym)
+    q8 = _levels((E, N, K), bits, seed + 1)
+    from quantool_amd.engine.qlinear import group_sums, pack_int4
+
+    Wq = (torch.stack([pack_int4(q8[e]) for e in range(E)]) if bits == 4 else q8).to(dev)
+    G = (K + 127) // 128 if grouped else 1
+    g = torch.Generator().manual_seed(seed + 2)
+    s_w = (torch.rand(E, N, G, generator=g) * 0.02 + 1e-4).to(torch.bfloat16).float().to(dev)
+    wsum = torch.stack([group_sums(q8[e], G) for e in range(E)]).to(dev)
+    return idx.to(dev), Xq, s_x, zp_x, Wq, s_w, wsum, q8
+
+
+def ops_mod():
+    from quantool_amd.hip import ops
+
+    return ops
+
+
+GROUPED_CASES = [
+    # E, rows per expert, N, K
+    (4, [130, 0, 1, 257], 200, 1024),
+    (8, [0, 0, 0, 300, 0, 0, 0, 0], 128, 640),
+    (3, [128, 256, 127], 96, 136),
+]
+
+
+@pytest.mark.parametrize("E,counts,N,K", GROUPED_CASES)
+@pytest.mark.parametrize("bits,grouped", [(8, False), (4, True), (8, True)])
+@pytest.mark.parametrize("asym", [False, True])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("gather", [True, False])
+def test_grouped_gemm_equals_per_expert_gemm(ops, dev, E, counts, N, K, bits, grouped, asym, dtype, gather):
+    idx, Xq, s_x, zp_x, Wq, s_w, wsum, _ = _grouped_case(dev, E, counts, N, K, bits, grouped, asym, dtype,
+                                                         seed=sum(counts) + K)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    ws = wsum if asym else None
+    if gather:
+        Y = ops.gemm_i8_grouped(Xq, s_x, Wq, s_w, offsets, row_idx=src_token, K=K, zp_x=zp_x, wsum=ws,
+                                out_dtype=dtype)
+        A, sa, za = Xq, s_x, zp_x
+        src = src_token.long()
+    else:
+        # contiguous A: the routed rows already in expert order
+        src = src_token.long()
+        A, sa = Xq[src].contiguous(), s_x[src].contiguous()
+        za = None if zp_x is None else zp_x[src].contiguous()
+        Y = ops.gemm_i8_grouped(A, sa, Wq, s_w, offsets, K=K, zp_x=za, wsum=ws, out_dtype=dtype)
+        src = torch.arange(len(src), device=dev)
+    torch.cuda.synchronize()
+    off = offsets.cpu().tolist()
+    assert off[-1] == sum(counts)
+    for e in range(E):
+        lo, hi = off[e], off[e + 1]
+        assert hi - lo == counts[e]
+        if hi == lo:
+            continue
+        rows = src[lo:hi]
+        want = ops.gemm_i8(A[rows].contiguous(), sa[rows].contiguous(), Wq[e], s_w[e], K=K,
+                           zp_x=None if za is None else za[rows].contiguous(), wsum=None if ws is None else ws[e],
+                           out_dtype=dtype)
+        torch.cuda.synchronize()
+        _bits_equal(Y[lo:hi], want)
+
+
+@pytest.mark.parametrize("N,K,bits", [(2 * 14336, 4096, 8), (4096, 14336, 4), (2 * 14336, 4096, 4)])
+def test_grouped_gemm_mixtral_shapes(ops, dev, N, K, bits):
+    E, counts = 8, [300, 0, 129, 411, 256, 1, 200, 383]
+    grouped = bits == 4
+    idx, Xq, s_x, zp_x, Wq, s_w, wsum, q8 = _grouped_case(dev, E, counts, N, K, bits, grouped, False,
+                                                          torch.bfloat16, seed=N + K)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    Y = ops.gemm_i8_grouped(Xq, s_x, Wq, s_w, offsets, row_idx=src_token, K=K)
+    torch.cuda.synchronize()
+    off = offsets.cpu().tolist()
+    src = src_token.long()
+    for e in range(E):
+        lo, hi = off[e], off[e + 1]
+        if hi == lo:
+            continue
+        rows = src[lo:hi]
+        want = ops.gemm_i8(Xq[rows].contiguous(), s_x[rows].contiguous(), Wq[e], s_w[e], K=K)
+        torch.cuda.synchronize()
+        _bits_equal(Y[lo:hi], want)
+    # and some rows of one expert against the torch restatement, so a fault shared by both GEMMs cannot hide
+    if not grouped:
+        e = 3
+        rows = src[off[e]:off[e] + 64]
+        _bits_equal(Y[off[e]:off[e] + 64], ref_gemm(Xq[rows], s_x[rows], q8[e], s_w[e].cpu()))
+
+
+def test_grouped_gemm_refuses_bad_shapes(ops, dev):
+    Xq = torch.zeros(4, 256, dtype=torch.int8, device=dev)
+    s_x = torch.ones(4, device=dev)
+    W = torch.zeros(2, 8, 256, dtype=torch.int8, device=dev)
+    off = torch.tensor([0, 2, 4], dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError):
+        ops.gemm_i8_grouped(Xq, s_x, W, torch.ones(2, 8, 3, device=dev), off)
+    with pytest.raises(ValueError):
+        ops.gemm_i8_grouped(Xq, s_x, W, torch.ones(2, 8, 1, device=dev), off[:2])
+    with pytest.raises(ValueError):
+        ops.gemm_i8_grouped(Xq, s_x, W[0], torch.ones(2, 8, 1, device=dev), off)
+    with pytest.raises(ValueError):
+        ops.gemm_i8_grouped(Xq, s_x, W, torch.ones(2, 8, 1, device=dev), off, rows=5)
+
+
+# ---- qt_moe_combine -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("T,k,E,H", [(1, 2, 8, 4096), (333, 2, 8, 256), (64, 4, 16, 100), (500, 2, 4, 1000)])
+def test_combine_equals_the_transformers_loop(ops, dev, dtype, T, k, E, H):
+    idx = _random_routing(T, k, E, seed=T * k + H)
+    if T > 10:
+        idx[5, 1] = E                                   # a dropped slot
+    offsets, src_token, src_slot, row_of = ops.moe_route(idx.to(dev), E)
+    R = T * k
+    g = torch.Generator().manual_seed(H)
+    Y = (torch.randn(R, H, generator=g) * 3).to(dtype).to(dev)
+    w = torch.softmax(torch.randn(T, k, generator=g), -1).to(dev)
+    out = ops.moe_combine(Y, row_of, w)
+    torch.cuda.synchronize()
+    _bits_equal(out, ref_combine(Y, idx, w, E, row_of))
+
+
+# ---- QuantizedExperts -----------------------------------------------------------------------------------------------
+def _quantized_experts(dev, E, H, I, bits, asym, seed):
+    from quantool_amd.engine.qlinear import QuantizedExperts, pack_int4
+    from transformers.activations import ACT2FN
+
+    q_gu = _levels((E, 2 * I, H), bits, seed)
+    q_dn = _levels((E, H, I), bits, seed + 1)
+    g = torch.Generator().manual_seed(seed + 2)
+    G1, G2 = ((H + 127) // 128, (I + 127) // 128) if bits == 4 else (1, 1)
+    s_gu = (torch.rand(E, 2 * I, G1, generator=g) * 0.01 / (1 if bits == 4 else 16) + 1e-4).to(torch.bfloat16)
+    s_dn = (torch.rand(E, H, G2, generator=g) * 0.01 / (1 if bits == 4 else 16) + 1e-4).to(torch.bfloat16)
+    pk = (lambda q: torch.stack([pack_int4(q[e]) for e in range(E)])) if bits == 4 else (lambda q: q)
+    qe = QuantizedExperts(H, I, pk(q_gu), s_gu, pk(q_dn), s_dn, ACT2FN["silu"], not asym).to(dev)
+    return qe, q_gu, q_dn
+
+
+def ref_experts(qe, q_gu, q_dn, x, idx, w):
+    """Pure torch: quantise, per-expert reference GEMMs on the routed rows, act_fn(gate) * up, quantise, down GEMM,
+    then transformers' weighted per-expert accumulation."""
+    E, T = qe.num_experts, x.shape[0]
+    sym = qe.act_symmetric
+    xq, sx, zx = ref_quantize_tokens(x, sym)
+    out = torch.zeros(T, x.shape[1], dtype=x.dtype)
+    idx, w = idx.cpu().long(), w.cpu().float()
+    for e in range(E):
+        tok = torch.nonzero((idx == e).any(1)).flatten()      # token ascending
+        if tok.numel() == 0:
+            continue
+        pos = (idx[tok] == e).long().argmax(1)
+        gu = ref_gemm(xq[tok], sx[tok], q_gu[e], qe.gate_up_scale[e].cpu(), None if sym else zx[tok],
+                      None if sym else qe.gate_up_wsum[e].cpu(), None, x.dtype)
+        gate, up = gu.chunk(2, dim=-1)
+        h = (qe.act_fn(gate.to(x.device)) * up.to(x.device)).cpu()
+        hq, sh, zh = ref_quantize_tokens(h, sym)
+        y = ref_gemm(hq, sh, q_dn[e], qe.down_scale[e].cpu(), zh, None if sym else qe.down_wsum[e].cpu(), None,
+                     x.dtype)
+        c = (y.float() * w[tok, pos, None]).to(x.dtype)
+        out[tok] = (out[tok].float() + c.float()).to(x.dtype)
+    return out
+
+
+@pytest.mark.parametrize("bits,asym", [(8, False), (4, False), (8, True), (4, True)])
+@pytest.mark.parametrize("T", [1, 37, 600])
+def test_quantized_experts_forward_bit_exact(dev, bits, asym, T):
+    E, H, I, k = 4, 256, 384, 2
+    qe, q_gu, q_dn = _quantized_experts(dev, E, H, I, bits, asym, seed=bits + T)
+    x = _acts(T, H, torch.bfloat16, dev, seed=T)
+    idx = _random_routing(T, k, E, seed=T + 1, experts=[0, 2, 3] if T == 37 else None).to(dev)
+    w = torch.softmax(torch.randn(T, k, generator=torch.Generator().manual_seed(T)), -1).to(dev)
+    with torch.no_grad():
+        out = qe(x, idx, w)
+    torch.cuda.synchronize()
+    _bits_equal(out, ref_experts(qe, q_gu, q_dn, x, idx, w))
+
+
+# ---- end to end -----------------------------------------------------------------------------------------------------
+def _tiny_mixtral(dev):
+    from transformers import MixtralConfig, MixtralForCausalLM
+
+    cfg = MixtralConfig(hidden_size=256, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4,
+                        num_key_value_heads=2, num_local_experts=4, num_experts_per_tok=2, vocab_size=512,
+                        max_position_embeddings=128, tie_word_embeddings=False)
+    torch.manual_seed(0)
+    return MixtralForCausalLM(cfg).to(torch.bfloat16).to(dev).eval()
+
+
+@pytest.mark.parametrize("method,level", [("smoothquant", "W8A8"), ("smoothquant", "W4A8"), ("gptq", "W4A16")])
+def test_end_to_end_on_tiny_mixtral(dev, tmp_path, monkeypatch, method, level):
+    import quantool_amd.methods  # noqa: F401
+    from quantool_amd.core import QuantizerRegistry
+    from quantool_amd.engine.qlinear import QuantizedExperts, load_quantized
+    from quantool_amd.evaluate import perplexity
+
+    monkeypatch.chdir(tmp_path)
+    model = _tiny_mixtral(dev)
+    g = torch.Generator().manual_seed(2)
+    data = [{"input_ids": torch.randint(0, 512, (48,), generator=g)} for _ in range(8)]
+    q = QuantizerRegistry.create(method, model_id="synthetic/tiny-mixtral")
+    q.quantize(model=model, level=level, dataset=data, num_calibration_samples=8, max_seq_length=64,
+               shuffle_calibration_samples=False)
+    torch.cuda.synchronize()
+    q.save_pretrained(str(tmp_path / "ckpt"))
+    mem = q.last_model
+    ids = torch.randint(0, 512, (6, 96), generator=torch.Generator().manual_seed(11))
+    ppl_mem = perplexity(mem, ids, batch_size=4)["perplexity"]
+    del mem, model
+    loaded = load_quantized(tmp_path / "ckpt", device=dev)
+    banks = [m for m in loaded.modules() if isinstance(m, QuantizedExperts)]
+    assert len(banks) == (0 if level == "W4A16" else 2)
+    ppl = perplexity(loaded, ids, batch_size=4)["perplexity"]
+    assert math.isfinite(ppl)
+    if level == "W4A16":
+        assert abs(ppl - ppl_mem) / ppl_mem < 1e-2, (ppl, ppl_mem)
+    else:
+        assert ppl != ppl_mem, ppl
