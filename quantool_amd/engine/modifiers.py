@@ -10,7 +10,7 @@ from __future__ import annotations
 import fnmatch
 import re
 from dataclasses import dataclass, field
-from typing import Any, List, Optional, Sequence, Union
+from typing import Any, List, Optional, Sequence, Tuple, Union
 
 from .schemes import QuantArgs, QuantScheme, preset_name_to_scheme
 
@@ -100,3 +100,14 @@ class SmoothQuantModifier:
     smoothing_strength: float = 0.5
     mappings: Optional[List[Any]] = None
     ignore: Optional[List[str]] = None
+
+
+def select_modifiers(recipe) -> Tuple[Optional[SmoothQuantModifier], Optional[GPTQModifier], Optional[AWQModifier]]:
+    """(SmoothQuant, GPTQ, AWQ) modifiers of a recipe (one modifier or a list), None where absent."""
+    mods = recipe if isinstance(recipe, (list, tuple)) else [recipe]
+    sq = next((m for m in mods if isinstance(m, SmoothQuantModifier)), None)
+    gp = next((m for m in mods if isinstance(m, GPTQModifier)), None)
+    aw = next((m for m in mods if isinstance(m, AWQModifier)), None)
+    if gp is None and aw is None:
+        raise ValueError("recipe must contain a GPTQModifier or an AWQModifier")
+    return sq, gp, aw

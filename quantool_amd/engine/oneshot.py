@@ -16,14 +16,14 @@ from __future__ import annotations
 import logging
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Optional
 
 import torch
 
 from ..hip import ops
 from .gptq_linear import (HessianAccumulator, batch_chains_enabled, batchable, gptq_quantize_batched,
                           gptq_quantize_shared)
-from .modifiers import AWQModifier, GPTQModifier, SmoothQuantModifier
+from .modifiers import select_modifiers
 
 logger = logging.getLogger(__name__)
 
@@ -99,18 +99,8 @@ def _iter_batches(acts) -> Iterable[torch.Tensor]:
             yield a
 
 
-def _select_modifiers(recipe) -> Tuple[Optional[SmoothQuantModifier], Optional[GPTQModifier], Optional[AWQModifier]]:
-    mods = recipe if isinstance(recipe, (list, tuple)) else [recipe]
-    sq = next((m for m in mods if isinstance(m, SmoothQuantModifier)), None)
-    gp = next((m for m in mods if isinstance(m, GPTQModifier)), None)
-    aw = next((m for m in mods if isinstance(m, AWQModifier)), None)
-    if gp is None and aw is None:
-        raise ValueError("recipe must contain a GPTQModifier or an AWQModifier")
-    return sq, gp, aw
-
-
 def _oneshot_linears(cal: LinearCalibrationSet, recipe, device) -> QuantizedLinears:
-    sq, gp, aw = _select_modifiers(recipe)
+    sq, gp, aw = select_modifiers(recipe)
     results: Dict[str, Any] = {}
     smoothed: Dict[str, torch.Tensor] = {}
     smoothing_scales: Dict[str, torch.Tensor] = {}

@@ -19,9 +19,8 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from .gptq_linear import (HessianAccumulator, batch_chains_enabled, batchable, gptq_quantize_batched,
-                          gptq_quantize_shared)
-from .modifiers import AWQModifier, GPTQModifier, SmoothQuantModifier
+from .gptq_linear import HessianAccumulator, batch_chains_enabled, batchable, gptq_quantize_batched
+from .modifiers import GPTQModifier, select_modifiers
 from .streams import GroupStreams
 
 logger = logging.getLogger(__name__)
@@ -370,33 +369,12 @@ def _save_compressed(model: nn.Module, save_directory, save_compressed: bool = T
 def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int, max_seq_length: int, shuffle: bool,
                    tokenizer=None, dataloader=None, dataset_path=None, text_column: str = "text",
                    trust_remote_code: bool = False, seed: int = 42, precision="auto", sequential_targets=None):
-    mods = recipe if isinstance(recipe, (list, tuple)) else [recipe]
-    gp = next((m for m in mods if isinstance(m, GPTQModifier)), None)
-    sq = next((m for m in mods if isinstance(m, SmoothQuantModifier)), None)
-    aw = next((m for m in mods if isinstance(m, AWQModifier)), None)
-    if gp is None and aw is None:
-        raise ValueError("recipe must contain a GPTQModifier or an AWQModifier")
+    sq, gp, aw = select_modifiers(recipe)
     if gp is not None and aw is not None:
         raise ValueError("GPTQModifier and AWQModifier in one recipe: pick one weight quantizer")
     qm = gp if gp is not None else aw
     if isinstance(model, (str, Path)):
-        from transformers import AutoModelForCausalLM, AutoTokenizer
-
-        path = str(model)
-        # the checkpoint's own dtype unless the caller says otherwise: the reference passes the model
-        # path through with no dtype (base.py:222-241), upstream's `precision` defaults to "auto"
-        table = {"auto": "auto", None: "auto", "float16": torch.float16, "fp16": torch.float16, "half": torch.float16,
-                 "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float32": torch.float32, "fp32": torch.float32,
-                 "full": torch.float32}
-        dt = precision if isinstance(precision, torch.dtype) else table.get(precision, precision)
-        model = AutoModelForCausalLM.from_pretrained(path, dtype=dt, trust_remote_code=trust_remote_code,
-                                                     local_files_only=True)
-        if tokenizer is None:
-            try:
-                tokenizer = AutoTokenizer.from_pretrained(path, trust_remote_code=trust_remote_code,
-                                                          local_files_only=True)
-            except Exception:  # noqa: BLE001
-                tokenizer = None
+        model, tokenizer = _load_model(model, precision, trust_remote_code, tokenizer)
     if dataset is None and dataset_path is not None:
         import json
 
@@ -410,7 +388,7 @@ def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int,
     # the model and forwards its own share), each input group's Gram sum is all-reduced once per layer,
     # every rank factorises the same Hessian and sweeps its slice of the rows, and the rows are
     # all-gathered -- partitioning B of SURVEY 8e for every group, so the replicated models stay equal.
-    from .sharding import allreduce_accumulator, dist_world, gptq_quantize_row_split
+    from .sharding import dist_world
 
     world, rank = dist_world()
     if world > 1 and aw is None:
@@ -422,19 +400,77 @@ def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int,
     n_banks = unfuse_expert_banks(model)
     if n_banks:
         logger.info(f"unfused {n_banks} sparse-MoE expert bank(s) into per-expert Linears")
-    seq_targets = sequential_targets or getattr(qm, "sequential_targets", None)
-    layers = find_decoder_layers(model, seq_targets)
+    layers = find_decoder_layers(model, sequential_targets or getattr(qm, "sequential_targets", None))
     qargs = qm.weight_args()
+    ph = _Phases(dev)
+    ph.start()
+    cache = _first_layer_inputs(model, layers, batches, dev)
+    ph.stop("first-layer inputs")
+    prefix_of = {id(m): n for n, m in model.named_modules()}
+    results: Dict[str, Any] = _ResultStore()
+    with torch.no_grad():
+        for li, layer in enumerate(layers):
+            lname, last = prefix_of[id(layer)], li + 1 == len(layers)
+            if aw is not None:
+                from .awq_module import awq_layer
 
-    # ---- inputs of the first decoder layer -------------------------------------------------------
+                results.update(awq_layer(layer, lname, cache, aw, dev))
+                if not last:
+                    cache = _advance(layer, cache)
+                continue
+            linears = _targeted_linears(layer, lname, gp)
+            if sq is not None:
+                _smooth_layer(layer, cache, sq.smoothing_strength, dev, sq.mappings, lname)
+            ph.start()
+            leaders, accs = _calibrate_layer(layer, linears, cache, world, dev)
+            ph.stop("calibration forwards + Gram")
+            ph.start()
+            _quantize_layer(linears, leaders, accs, gp, qargs, world, results, dev)
+            del accs
+            ph.stop("factorise + sweep + pack")
+            ph.start()
+            if not last:       # nobody reads the last layer's outputs: no propagate pass behind it
+                cache = _advance(layer, cache)
+            ph.stop("propagate")
+            logger.info(f"quantized {lname}: {len(linears)} Linears in {len(leaders)} input groups")
+    ph.report()
+    model._qt_results = results
+    acts = qm.resolved_scheme.input_activations
+    model._qt_meta = {"weights": qargs.to_config(), "format": qm.resolved_scheme.format, "ignore": list(qm.ignore),
+                      "input_activations": acts.to_config() if acts is not None else None}
+    model.save_pretrained = types.MethodType(_save_compressed, model)
+    return model
+
+
+def _load_model(path, precision, trust_remote_code: bool, tokenizer):
+    """A local checkpoint directory -> (model, tokenizer); the checkpoint's own tokenizer unless one is given."""
+    from transformers import AutoModelForCausalLM, AutoTokenizer
+
+    path = str(path)
+    # the checkpoint's own dtype unless the caller says otherwise: the reference passes the model
+    # path through with no dtype (base.py:222-241), upstream's `precision` defaults to "auto"
+    table = {"auto": "auto", None: "auto", "float16": torch.float16, "fp16": torch.float16, "half": torch.float16,
+             "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float32": torch.float32, "fp32": torch.float32,
+             "full": torch.float32}
+    dt = precision if isinstance(precision, torch.dtype) else table.get(precision, precision)
+    model = AutoModelForCausalLM.from_pretrained(path, dtype=dt, trust_remote_code=trust_remote_code,
+                                                 local_files_only=True)
+    if tokenizer is None:
+        try:
+            tokenizer = AutoTokenizer.from_pretrained(path, trust_remote_code=trust_remote_code, local_files_only=True)
+        except Exception:  # noqa: BLE001
+            tokenizer = None
+    return model, tokenizer
+
+
+def _first_layer_inputs(model: nn.Module, layers: List[nn.Module], batches, dev) -> List[tuple]:
+    """The (args, kwargs) the first decoder layer is called with, one entry per forward."""
     cache: List[tuple] = []
 
     def grab(_mod, args, kwargs):
         cache.append((args, kwargs))
         raise _StopForward
 
-    ph = _Phases(dev)
-    ph.start()
     h = layers[0].register_forward_pre_hook(grab, with_kwargs=True)
     batch_tokens = int(os.environ.get("QT_CALIB_BATCH_TOKENS", "32768"))
     with torch.no_grad():
@@ -447,226 +483,185 @@ def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int,
                 pass
     h.remove()
     # whatever could not be stacked before the forward (extra inputs of unequal shape) is merged after it
-    cache = merge_cache(cache, batch_tokens)
-    ph.stop("first-layer inputs")
+    return merge_cache(cache, batch_tokens)
 
-    prefix_of = {id(m): n for n, m in model.named_modules()}
-    results: Dict[str, Any] = _ResultStore()
-    with torch.no_grad():
-        for li, layer in enumerate(layers):
-            lname = prefix_of[id(layer)]
-            if aw is not None:
-                from .awq_module import awq_layer
 
-                results.update(awq_layer(layer, lname, cache, aw, dev))
-                if li + 1 < len(layers):
-                    cache = _advance(layer, cache)
-                continue
-            linears = {f"{lname}.{n}" if n else lname: m for n, m in layer.named_modules()
-                       if isinstance(m, nn.Linear) and gp.wants(f"{lname}.{n}", m)}
-            miss = uncovered_weight_fraction(layer, linears)
-            if miss > 0.10:
-                logger.warning(f"{lname}: {100 * miss:.0f}% of the layer's matrix weights are held by no targeted "
-                               "nn.Linear and stay dense (fused or custom-op weights?) although the saved config "
-                               f"declares targets={list(qm.targets)}")
-            if sq is not None:
-                _smooth_layer(layer, cache, sq.smoothing_strength, dev, sq.mappings, lname)
-            # Discovery on batch 0: which Linears read the same tensor.  This forward is ALSO batch 0's calibration
-            # forward -- the inputs it shows are kept (that keeps them alive, too: a freed activation's address can be
-            # handed to a later, unrelated tensor of the same shape, and pointer equality would then lie) and go into
-            # the accumulators as soon as the grouping is known.  (Rounds 1-4 ran batch 0 twice: once to discover, once
-            # to accumulate -- a sixth of a calibration pass per layer.)  It runs to its end: the call counts of a
-            # whole forward decide whether the later ones may stop early.
-            seen: Dict[str, List[torch.Tensor]] = {}      # every input a Linear was called with, in call order
-            seen_version: Dict[str, List[int]] = {}       # ... and its version counter at that moment
-            calls: Dict[str, int] = {}
+def _targeted_linears(layer: nn.Module, lname: str, gp: GPTQModifier) -> Dict[str, nn.Module]:
+    linears = {f"{lname}.{n}" if n else lname: m for n, m in layer.named_modules()
+               if isinstance(m, nn.Linear) and gp.wants(f"{lname}.{n}", m)}
+    miss = uncovered_weight_fraction(layer, linears)
+    if miss > 0.10:
+        logger.warning(f"{lname}: {100 * miss:.0f}% of the layer's matrix weights are held by no targeted "
+                       "nn.Linear and stay dense (fused or custom-op weights?) although the saved config "
+                       f"declares targets={list(gp.targets)}")
+    return linears
 
-            def discover(name):
-                def fn(_m, a):
-                    seen.setdefault(name, []).append(a[0])
-                    seen_version.setdefault(name, []).append(a[0]._version)
-                    calls[name] = calls.get(name, 0) + 1
-                return fn
 
-            ph.start()
-            hooks = [m.register_forward_pre_hook(discover(n)) for n, m in linears.items()]
-            args, kwargs = cache[0]
+def _set_batch(args) -> None:
+    """Tell the hooks (``_CALIB_CTX``) how many samples of how many tokens the forward about to run carries."""
+    h0 = args[0] if args else None
+    stacked = torch.is_tensor(h0) and h0.dim() >= 3
+    _CALIB_CTX["samples"] = int(h0.shape[0]) if stacked else 1
+    _CALIB_CTX["tokens_per_sample"] = int(h0.shape[1]) if stacked else None
+
+
+def _accumulate(acc, x: torch.Tensor, samples: int) -> None:
+    """One Linear input into its group's accumulator.  Upstream counts one sample per forward of a batch-size-1
+    pipeline (num_added); with several samples per forward a [B, T, K] input counts B, and a flattened [tokens, K]
+    input (OPT's fc1, routed expert tokens) counts ``samples``: those of the forward it came from, as
+    ``_CALIB_CTX`` said when the Linear was called."""
+    if x.dim() >= 3:
+        acc.add(x.reshape(-1, x.shape[-2], x.shape[-1]))
+    else:
+        acc.add(x.unsqueeze(0), num_samples=samples)
+
+
+def _group_by_input(linears: Dict[str, nn.Module], seen: Dict[str, list], world: int) -> Dict[str, List[str]]:
+    """{leader: Linears that read the same tensor as the leader} from the first call of each Linear in ``seen``."""
+    groups: Dict[tuple, List[str]] = {}
+    for n in linears:
+        if n not in seen:
+            # not reached by batch 0 (a sparse-MoE expert none of its tokens was routed to):
+            # sharing cannot be established, so the Linear keeps a Hessian of its own
+            groups[("solo", n)] = [n]
+            continue
+        t = seen[n][0][0]
+        key = (t.untyped_storage().data_ptr(), t.storage_offset(), tuple(t.shape), tuple(t.stride()))
+        groups.setdefault(key, []).append(n)
+    grouping = list(groups.values())
+    if world > 1:
+        # every rank discovered the sharing on ITS batch 0, and a Linear one rank's batch did not reach
+        # (a sparse-MoE expert) would be a solo group there only: the ranks would then issue different
+        # all-reduce sequences.  Rank 0's grouping is everybody's (a solo group is always valid: it
+        # only forgoes the sharing).
+        import torch.distributed as dist
+
+        box = [grouping]
+        dist.broadcast_object_list(box, src=0)
+        grouping = box[0]
+    return {names[0]: names for names in grouping}
+
+
+def _calibrate_layer(layer: nn.Module, linears: Dict[str, nn.Module], cache: List[tuple], world: int, dev):
+    """Every cached forward through ``layer`` with hooks on its targeted Linears -> ``(leaders, accs)``: {leader: the
+    Linears that read its input}, {leader: its flushed HessianAccumulator}.
+
+    Batch 0's forward discovers which Linears read the same tensor and is also its calibration forward: the inputs it
+    shows are kept (alive, so that no later tensor reuses an address) with the sample count of each call, and go into
+    the accumulators once the grouping is known -- unless one was written in place behind its Linear (its version
+    counter moved): then batch 0 is forwarded again through the hooks.  A later forward stops once every group has
+    seen its rows (the propagate pass recomputes the rest with the quantised weights), but only when batch 0 called
+    every targeted Linear exactly once (no shared weight, no expert left out by the router)."""
+    seen: Dict[str, list] = {}      # every call of a Linear, in order: (input, its version counter, samples)
+
+    def discover(name):
+        def fn(_m, a):
+            seen.setdefault(name, []).append((a[0], a[0]._version, _CALIB_CTX["samples"]))
+        return fn
+
+    _set_batch(cache[0][0])
+    hooks = [m.register_forward_pre_hook(discover(n)) for n, m in linears.items()]
+    layer(*cache[0][0], **cache[0][1])
+    for hk in hooks:
+        hk.remove()
+    leaders = _group_by_input(linears, seen, world)
+    accs = {lead: HessianAccumulator(linears[lead].in_features, dev) for lead in leaders}
+    early_stop = all(len(seen.get(n, ())) == 1 for n in linears)
+    moved = [n for n, calls in seen.items() if any(x._version != v for x, v, _ in calls)]
+    if moved:
+        logger.info(f"{moved[0]}: the Linear's input is modified in place behind it; batch 0 is forwarded twice")
+    else:
+        for lead in [n for n in seen if n in leaders]:      # group by group, in the order the hooks would fire
+            for x, _, samples in seen[lead]:
+                _accumulate(accs[lead], x, samples)
+    seen.clear()
+    fired = set()
+
+    def add_hook(lead):
+        def fn(_m, a):
+            _accumulate(accs[lead], a[0], _CALIB_CTX["samples"])
+            fired.add(lead)
+            if early_stop and len(fired) == len(leaders):
+                raise _StopForward
+        return fn
+
+    hooks = [linears[lead].register_forward_pre_hook(add_hook(lead)) for lead in leaders]
+    for args, kwargs in (cache if moved else cache[1:]):
+        _set_batch(args)
+        fired.clear()
+        try:
             layer(*args, **kwargs)
-            for hk in hooks:
-                hk.remove()
-            groups: Dict[tuple, List[str]] = {}
-            for n in linears:
-                if n not in seen:
-                    # not reached by batch 0 (a sparse-MoE expert none of its tokens was routed to):
-                    # sharing cannot be established, so the Linear keeps a Hessian of its own
-                    groups[("solo", n)] = [n]
-                    continue
-                t = seen[n][0]
-                key = (t.untyped_storage().data_ptr(), t.storage_offset(), tuple(t.shape), tuple(t.stride()))
-                groups.setdefault(key, []).append(n)
-            grouping = list(groups.values())
-            if world > 1:
-                # every rank discovered the sharing on ITS batch 0, and a Linear one rank's batch did not reach
-                # (a sparse-MoE expert) would be a solo group there only: the ranks would then issue different
-                # all-reduce sequences.  Rank 0's grouping is everybody's (a solo group is always valid: it
-                # only forgoes the sharing).
-                import torch.distributed as dist
+        except _StopForward:
+            pass
+    for hk in hooks:
+        hk.remove()
+    for acc in accs.values():
+        acc.flush()
+    return leaders, accs
 
-                box = [grouping]
-                dist.broadcast_object_list(box, src=0)
-                grouping = box[0]
-            leaders = {names[0]: names for names in grouping}
-            accs = {lead: HessianAccumulator(linears[lead].in_features, dev) for lead in leaders}
-            # upstream counts one sample per forward of a batch-size-1 pipeline (num_added); with several samples
-            # per forward a [B, T, K] input counts B, and a flattened [tokens, K] input (OPT's fc1, routed expert
-            # tokens) counts the samples of the forward it came from
-            cur = _CALIB_CTX
-            # A calibration forward is over once every input group has seen its rows: what the layer computes behind
-            # its last hooked Linear (that Linear's own GEMM -- down_proj is a quarter of a Llama layer's flops -- and
-            # the residual add) is recomputed by the propagate pass with the quantised weights anyway.  Only when the
-            # discovery pass reached every targeted Linear exactly once (no weight shared between two call sites, no
-            # expert left out by the router); a forward in which some group does not fire simply runs to its end.
-            early_stop = (os.environ.get("QT_CALIB_EARLY_STOP", "1") != "0"
-                          and all(calls.get(n, 0) == 1 for n in linears))
-            fired = set()
 
-            def add_hook(lead):
-                def fn(_m, a):
-                    x = a[0]
-                    if x.dim() >= 3:
-                        accs[lead].add(x.reshape(-1, x.shape[-2], x.shape[-1]))
-                    else:
-                        accs[lead].add(x.unsqueeze(0), num_samples=cur["samples"])
-                    fired.add(lead)
-                    if early_stop and len(fired) == len(leaders):
-                        raise _StopForward
-                return fn
+def _quantize_layer(linears: Dict[str, nn.Module], leaders: Dict[str, List[str]], accs: Dict[str, Any],
+                    gp: GPTQModifier, qargs, world: int, results: Dict[str, Any], dev) -> None:
+    """Quantise a layer's input groups and write the results back, one work unit per side stream (streams.py),
+    largest in_features (longest chain) first.  A unit is a group no token reached (round to nearest), or in one
+    process the groups ``batchable`` puts through one chain (a Llama layer's q/k/v + o + gate/up, a sparse-MoE layer's
+    experts), or under ranks one group, all-reduced and row-split.  The collectives inside a unit are issued by this
+    one host thread in the same order on every rank whatever stream is current (torch.distributed orders them on the
+    process group's own stream behind an event of the current one); QT_DIST_GROUP_STREAMS=0: one stream."""
+    by_size = sorted(leaders, key=lambda lead: (-linears[lead].in_features, lead))
+    if world == 1 and batch_chains_enabled():
+        live = [lead for lead in by_size if accs[lead].n > 0]
+        units = [[lead] for lead in by_size if accs[lead].n == 0]
+        units += [[live[i] for i in idx]
+                  for idx in batchable([([linears[n].weight.data for n in leaders[lead]], accs[lead]) for lead in live])]
+    else:
+        units = [[lead] for lead in by_size]
+    pool = GroupStreams(dev) if (world == 1 or os.environ.get("QT_DIST_GROUP_STREAMS", "1") != "0") else None
+    for unit in units:
+        if pool is None:
+            _quantize_unit(unit, linears, leaders, accs, gp, qargs, world, results)
+        else:
+            pool.run(lambda unit=unit: _quantize_unit(unit, linears, leaders, accs, gp, qargs, world, results))
+    # joined BEFORE the propagate pass: letting a chain overlap it was tried and dropped (DESIGN 7 (vi))
+    if pool is not None:
+        pool.join()
 
-            def set_batch(args):
-                h0 = args[0] if args else None
-                cur["samples"] = int(h0.shape[0]) if torch.is_tensor(h0) and h0.dim() >= 3 else 1
-                cur["tokens_per_sample"] = int(h0.shape[1]) if torch.is_tensor(h0) and h0.dim() >= 3 else None
 
-            # batch 0: what the discovery forward saw, group by group in the order the hooks would have fired
-            # (QT_CALIB_MERGED_DISCOVERY=0: batch 0 is forwarded a second time, as up to round 4 -- A/B only)
-            merged = os.environ.get("QT_CALIB_MERGED_DISCOVERY", "1") != "0"
-            if merged and any(t._version != v for n in seen for t, v in zip(seen[n], seen_version[n])):
-                # a kept input was written in place later in the forward (its version counter moved): what it holds now
-                # is not what the Linear read.  Forward batch 0 again and take the inputs at hook time, as before.
-                logger.info(f"{lname}: a Linear's input is modified in place behind it; batch 0 is forwarded twice")
-                merged = False
-            if merged:
-                set_batch(cache[0][0])
-                for lead in [n for n in seen if n in leaders]:
-                    for x in seen[lead]:
-                        if x.dim() >= 3:
-                            accs[lead].add(x.reshape(-1, x.shape[-2], x.shape[-1]))
-                        else:
-                            accs[lead].add(x.unsqueeze(0), num_samples=cur["samples"])
-            seen.clear()
-            hooks = [linears[lead].register_forward_pre_hook(add_hook(lead)) for lead in leaders]
-            for args, kwargs in (cache[1:] if merged else cache):
-                set_batch(args)
-                fired.clear()
-                try:
-                    layer(*args, **kwargs)
-                except _StopForward:
-                    pass
-            for hk in hooks:
-                hk.remove()
-            for a_ in accs.values():
-                a_.flush()
-            ph.stop("calibration forwards + Gram")
-            ph.start()
-            # one stream per input group, largest in_features first (longest chain): see streams.py.  Also under
-            # torchrun: the collectives inside a group's chain (the all-reduce of its Gram sum, the all-gather of its
-            # rows) are issued by this one host thread in the same order on every rank whatever stream is current
-            # (torch.distributed orders them on the process group's own stream behind an event of the current one);
-            # QT_DIST_GROUP_STREAMS=0 puts everything back on one stream
-            pool = GroupStreams(dev) if (world == 1 or os.environ.get("QT_DIST_GROUP_STREAMS", "1") != "0") else None
+def _quantize_unit(unit: List[str], linears, leaders, accs, gp: GPTQModifier, qargs, world: int, results) -> None:
+    if world > 1:
+        from .sharding import allreduce_accumulator, gptq_quantize_row_split
 
-            def quantize_group(lead, names):
-                ws = [linears[n].weight.data for n in names]
-                if world > 1:
-                    allreduce_accumulator(accs[lead])
-                if accs[lead].n == 0:
-                    # e.g. a sparse-MoE expert no calibration token was routed to.  Upstream would sweep
-                    # with an all-zero Hessian (every column "dead", weights zeroed); keep the weights
-                    # and round to nearest instead, loudly.
-                    logger.warning(f"{names}: no calibration token reached this input; falling back to "
-                                   "round-to-nearest for these Linears")
-                    from .awq_linear import rtn_finalize
+        allreduce_accumulator(accs[unit[0]])        # under ranks a unit is one group
+    if accs[unit[0]].n == 0:                        # a unit of one group, too
+        # e.g. a sparse-MoE expert no calibration token was routed to.  Upstream would sweep with an all-zero Hessian
+        # (every column "dead", weights zeroed); keep the weights and round to nearest instead, loudly.
+        from .awq_linear import rtn_finalize
 
-                    for n, w in zip(names, ws):
-                        r = rtn_finalize(w, qargs)
-                        linears[n].weight.data.copy_(r.dequantized(linears[n].weight.dtype))
-                        results[n] = r
-                    return
-                keep = {} if DEBUG_KEEP is not None else None
-                if world > 1:
-                    res = gptq_quantize_row_split(ws, accs[lead], qargs, block_size=gp.block_size,
-                                                  dampening_frac=gp.dampening_frac, with_dequantized=True)
-                else:
-                    res = gptq_quantize_shared(ws, accs[lead], qargs, block_size=gp.block_size,
-                                               dampening_frac=gp.dampening_frac, keep=keep)
-                if keep is not None and world == 1:
-                    DEBUG_KEEP[lead] = dict(keep, names=list(names), n=accs[lead].n, G=accs[lead].G.clone())
-                for n, r in zip(names, res):
-                    linears[n].weight.data.copy_(r.dequantized(linears[n].weight.dtype))
-                    results[n] = r
+        names = leaders[unit[0]]
+        logger.warning(f"{names}: no calibration token reached this input; falling back to "
+                       "round-to-nearest for these Linears")
+        _store(linears, results, names, [rtn_finalize(linears[n].weight.data, qargs) for n in names])
+        return
+    groups = [([linears[n].weight.data for n in leaders[lead]], accs[lead]) for lead in unit]
+    keeps = [{} for _ in unit] if DEBUG_KEEP is not None and world == 1 else None
+    if world > 1:
+        res = [gptq_quantize_row_split(*groups[0], qargs, block_size=gp.block_size, dampening_frac=gp.dampening_frac,
+                                       with_dequantized=True)]
+    else:
+        res = gptq_quantize_batched(groups, qargs, block_size=gp.block_size, dampening_frac=gp.dampening_frac,
+                                    keeps=keeps)
+    for i, lead in enumerate(unit):
+        _store(linears, results, leaders[lead], res[i], None if keeps is None else keeps[i], accs[lead])
 
-            def quantize_batch(leads):
-                """Input groups of equal in_features through ONE chain of launches (gptq_quantize_batched): a Llama
-                layer's q/k/v + o + gate/up, a sparse-MoE layer's experts.  Per group bit-identical to quantize_group."""
-                keeps = [{} for _ in leads] if DEBUG_KEEP is not None else None
-                res = gptq_quantize_batched([([linears[n].weight.data for n in leaders[lead]], accs[lead]) for lead in leads],
-                                            qargs, block_size=gp.block_size, dampening_frac=gp.dampening_frac, keeps=keeps)
-                for i, lead in enumerate(leads):
-                    if keeps is not None:
-                        DEBUG_KEEP[lead] = dict(keeps[i], names=list(leaders[lead]), n=accs[lead].n, G=accs[lead].G.clone())
-                    for n, r in zip(leaders[lead], res[i]):
-                        linears[n].weight.data.copy_(r.dequantized(linears[n].weight.dtype))
-                        results[n] = r
 
-            by_size = sorted(leaders.items(), key=lambda kv: (-linears[kv[0]].in_features, kv[0]))
-            if world == 1 and pool is not None and batch_chains_enabled():     # (under ranks every group is row-split instead)
-                live = [lead for lead, _ in by_size if accs[lead].n > 0]
-                for lead, names in by_size:
-                    if accs[lead].n == 0:
-                        pool.run(lambda lead=lead, names=names: quantize_group(lead, names))      # the RTN fallback
-                for idx in batchable([([linears[n].weight.data for n in leaders[lead]], accs[lead]) for lead in live]):
-                    leads = [live[i] for i in idx]
-                    if len(leads) == 1:
-                        pool.run(lambda lead=leads[0]: quantize_group(lead, leaders[lead]))
-                    else:
-                        pool.run(lambda leads=leads: quantize_batch(leads))
-            else:
-                for lead, names in by_size:
-                    if pool is not None:
-                        pool.run(lambda lead=lead, names=names: quantize_group(lead, names))
-                    else:
-                        quantize_group(lead, names)
-            # The chains are joined BEFORE the propagate pass.  (Tried in round 4: no join, every quantised Linear waiting
-            # for its own chain's event in a forward pre-hook, so that a Llama layer's down_proj chain runs beside the
-            # quantised layer's attention and gate / up GEMMs.  One of eight runs of test_gpu_config1_opt.py then
-            # disagreed with the oracle in 6 packed words of the one Linear whose chain overlapped the pass; the cause
-            # was not found, so the overlap is not shipped.)
-            if pool is not None:
-                pool.join()
-            accs.clear()
-            ph.stop("factorise + sweep + pack")
-            ph.start()
-            if li + 1 < len(layers):       # nobody reads the last layer's outputs: no propagate pass behind it
-                cache = _advance(layer, cache)
-            ph.stop("propagate")
-            logger.info(f"quantized {lname}: {len(linears)} Linears in {len(leaders)} input groups")
-    ph.report()
-    model._qt_results = results
-    acts = qm.resolved_scheme.input_activations
-    model._qt_meta = {"weights": qargs.to_config(), "format": qm.resolved_scheme.format, "ignore": list(qm.ignore),
-                      "input_activations": acts.to_config() if acts is not None else None}
-    model.save_pretrained = types.MethodType(_save_compressed, model)
-    return model
+def _store(linears, results, names: List[str], res, keep: Optional[dict] = None, acc=None) -> None:
+    """A group's results: the dequantised weights into the modules, the results by name, and (``DEBUG_KEEP``) the
+    group's stage boundaries under its leader's name."""
+    if keep is not None:
+        DEBUG_KEEP[names[0]] = dict(keep, names=list(names), n=acc.n, G=acc.G.clone())
+    for n, r in zip(names, res):
+        linears[n].weight.data.copy_(r.dequantized(linears[n].weight.dtype))
+        results[n] = r
 
 
 class _Phases:
