@@ -343,6 +343,38 @@ int qt_gemm_i8_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t 
 int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
                    int64_t T, int k, void* out, qt_stream_t stream);
 
+/* ---- A16 runtime: W4A16 / W4A16_ASYM / W8A16 checkpoints on their stored integer weights ----------------------
+ * Both kernels take one weight description:
+ *   Wq    w_format QT_W_INT4_PACKED: int32 [N, ceil(K/8)] (qt_gemm_i8's nibble layout), or QT_W_INT8: int8 [N, K]
+ *   s_w   fp32 [N, G], G = 1 (channel-wise) or ceil(K/128)
+ *   zp_w  int8 [N, G] or NULL (symmetric)
+ *   g_idx int32 [K] or NULL: the group of every column (actorder "group"; values clamped to [0, G)); when NULL the group of
+ *         column k is k / 128 (G > 1) or 0.  Columns stay in their original order: no permutation anywhere.
+ * The weight both kernels multiply is defined as engine/qlinear.py dequantized_weight computes it:
+ *   w[n, k] = round_to_dtype( ((float)q[n, k] - (float)zp[n, g(k)]) * s_w[n, g(k)] )     fp32, one rounding each
+ * (q - zp is exact in fp32; the product rounds once; round_to_dtype is round to nearest even.)
+ *
+ * qt_dequantize_weight: W [N, K] (dtype bf16 / fp16, row pitch ldw) = w, bit-identical to dequantized_weight.
+ *
+ * qt_gemm_wq_skinny: the decode GEMV, 1 <= M <= 16.  X [M, K] and Y [M, N] in x_dtype (bf16 / fp16), row pitches ldx /
+ *   ldy; bias [N] in x_dtype or NULL.
+ *     Y[m, n] = round_to_dtype( sum_k (float)x[m, k] * w[n, k]  (+ (float)bias[n]) )
+ *   The products run on v_mfma_f32_16x16x32_{bf16,f16} with the activations as the B operand, M padded to 16 with zero
+ *   rows: a workgroup owns 16 columns n, its 4 waves take the 128-column k-blocks kb = wave, wave + 4, ... in ascending
+ *   order (one MFMA per 8 columns, fp32 accumulator), and the waves' partial sums are added in wave order, then the bias.
+ *   The order is fixed and there are no atomics: two runs give the same bits.  The exact-input guarantee rests on two
+ *   facts: a product of two bf16 (or two fp16) values is exact in fp32, and the MFMA's fp32 accumulation is exact
+ *   whenever every partial sum is representable in fp32 (no denormals).  Inputs whose partial sums are all exact (small
+ *   integer x, power-of-two scales, bounded K) therefore give round_to_dtype of the exact sum, bit for bit; for any
+ *   other input |y - y_exact| <= ulp_dtype(y) / 2 + K 2^-24 sum_k |x w|.
+ *   Without a zero-point the kernel forms w as fma(q + OFF, s, -OFF s) (OFF = 8 or 128, so -OFF s is exact): the same
+ *   value, except that a zero weight is +0 whatever the sign of s. */
+int qt_dequantize_weight(const void* Wq, int w_format, int N, int K, const float* s_w, int G, const int8_t* zp_w,
+                         const int32_t* g_idx, void* W, int dtype, int64_t ldw, qt_stream_t stream);
+int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format, int N,
+                      const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
+                      int64_t ldy, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

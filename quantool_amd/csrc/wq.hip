@@ -1,0 +1,377 @@
+// W4A16 / W8A16 weight-only runtime: the integer weights of an A16 checkpoint stay on the device and are dequantised on
+// chip (include/quantool_amd.h, "A16 runtime").
+//
+// qt_dequantize_weight   one thread per 8 columns of a row: one packed word (int4) or 8 bytes (int8) in, one 16-byte
+//                        store out; four such chunks per thread, 256 threads per row piece.  HBM-bound.
+// qt_gemm_wq_skinny      the decode GEMV (1 <= M <= 16).  A workgroup owns 16 output columns n (weight rows) and splits
+//                        K over its 4 waves (k-block kb of 128 columns goes to wave kb % 4).  Per k-block a lane loads
+//                        one 16-byte chunk of its weight row straight into VGPRs (non-temporal: the weights are read
+//                        once), dequantises it and feeds v_mfma_f32_16x16x32_{bf16,f16} with M padded to 16 (the
+//                        activations are the B operand).  Four k-blocks are in flight per wave before the first MFMA.
+//                        The 4 waves' fp32 partials are summed through LDS in wave order: no atomics.
+//
+// -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own unless written as __builtin_fmaf.
+#include "common.h"
+
+namespace {
+
+constexpr int WQ_THREADS = 256;
+constexpr int WQ_WAVES = WQ_THREADS / 64;
+constexpr int WQ_KB = 128;      // columns per k-block (= the weight group)
+constexpr int WQ_UNROLL = 4;    // k-blocks in flight per wave
+
+struct WqArgs {
+    const unsigned short* X;
+    int64_t ldx;
+    int M;
+    const void* Wq;
+    int N, K, Kw;               // Kw: int32 words per packed row (int4)
+    const float* s_w;
+    int G;
+    const int8_t* zp_w;
+    const int32_t* g_idx;
+    const unsigned short* bias;
+    unsigned short* Y;          // Y (GEMV) or W (dequantise)
+    int64_t ldy;
+    int vec;                    // 16-byte weight / activation / output accesses are aligned and in bounds
+};
+
+template <int DT>
+__device__ __forceinline__ unsigned pack2(float a, float b) {
+    if constexpr (DT == QT_F16) {
+        const unsigned lo = __builtin_bit_cast(unsigned short, (_Float16)a);
+        const unsigned hi = __builtin_bit_cast(unsigned short, (_Float16)b);
+        return lo | (hi << 16);
+    } else {
+        const unsigned lo = __builtin_bit_cast(unsigned short, (__bf16)a);
+        const unsigned hi = __builtin_bit_cast(unsigned short, (__bf16)b);
+        return lo | (hi << 16);
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ float h2f(unsigned short h) {
+    return DT == QT_F16 ? qt_f16_to_f32(h) : qt_bf16_to_f32(h);
+}
+
+// The group of column c and its scale / zero-point offset.  cz = OFF + zp: the stored level plus OFF is the unsigned
+// value u the kernels convert (u - cz = q - zp exactly).  g_idx values are clamped to [0, G).
+template <bool INT4, bool ZP, bool GIDX>
+__device__ __forceinline__ void group_params(const WqArgs& p, int64_t n, int c, float& s, float& cz) {
+    int g;
+    if constexpr (GIDX) {
+        g = p.g_idx[c];
+        g = min(max(g, 0), p.G - 1);
+    } else {
+        g = p.G == 1 ? 0 : c / WQ_KB;
+    }
+    s = p.s_w[n * p.G + g];
+    cz = INT4 ? 8.0f : 128.0f;
+    if constexpr (ZP) cz = cz + (float)p.zp_w[n * p.G + g];
+}
+
+// unsigned value u = level + OFF of column c of row n (any alignment)
+template <bool INT4>
+__device__ __forceinline__ float level_u(const WqArgs& p, int64_t n, int c) {
+    if constexpr (INT4) {
+        const unsigned w = (unsigned)((const int32_t*)p.Wq)[n * p.Kw + (c >> 3)];
+        return (float)((w >> (4 * (c & 7))) & 0xfu);
+    } else {
+        return (float)(((unsigned)(uint8_t)((const int8_t*)p.Wq)[n * p.K + c]) ^ 0x80u);
+    }
+}
+
+// ---- qt_dequantize_weight -------------------------------------------------------------------------------------------
+constexpr int DQ_CHUNKS = 4;    // 8-column chunks per thread
+
+template <bool INT4, int DT, bool ZP, bool GIDX>
+__global__ void __launch_bounds__(WQ_THREADS) dequant_kernel(const WqArgs p, int chunks_per_row, int blocks_per_row) {
+    const int64_t n = blockIdx.x / blocks_per_row;
+    const int base = (blockIdx.x % blocks_per_row) * (WQ_THREADS * DQ_CHUNKS);
+    unsigned short* out = p.Y + n * p.ldy;
+#pragma unroll
+    for (int u = 0; u < DQ_CHUNKS; ++u) {
+        const int ch = base + u * WQ_THREADS + threadIdx.x;
+        if (ch >= chunks_per_row) break;
+        const int c0 = ch * 8;
+        if (p.vec && c0 + 8 <= p.K) {
+            unsigned v[8];
+            if constexpr (INT4) {
+                const unsigned w = (unsigned)((const int32_t*)p.Wq)[n * p.Kw + ch];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (w >> (4 * j)) & 0xfu;
+            } else {
+                const uint2 b = *(const uint2*)((const int8_t*)p.Wq + n * p.K + c0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = ((b.x >> (8 * j)) & 0xffu) ^ 0x80u;
+                    v[4 + j] = ((b.y >> (8 * j)) & 0xffu) ^ 0x80u;
+                }
+            }
+            float s, cz;
+            if constexpr (!GIDX) group_params<INT4, ZP, GIDX>(p, n, c0, s, cz);
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (GIDX) group_params<INT4, ZP, GIDX>(p, n, c0 + j, s, cz);
+                const float t = (float)v[j] - cz;   // q - zp, exact
+                f[j] = t * s;
+            }
+            *(uint4*)(out + c0) = make_uint4(pack2<DT>(f[0], f[1]), pack2<DT>(f[2], f[3]), pack2<DT>(f[4], f[5]),
+                                             pack2<DT>(f[6], f[7]));
+        } else {
+            for (int c = c0; c < c0 + 8 && c < p.K; ++c) {
+                float s, cz;
+                group_params<INT4, ZP, GIDX>(p, n, c, s, cz);
+                const float t = level_u<INT4>(p, n, c) - cz;
+                const float f = t * s;
+                out[c] = (unsigned short)(pack2<DT>(f, 0.0f) & 0xffffu);
+            }
+        }
+    }
+}
+
+// ---- qt_gemm_wq_skinny ----------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// a once-read 16-byte weight chunk: non-temporal load (MI355X_MICROARCH nt-weights)
+__device__ __forceinline__ uint4 ld_nt16(const void* p) {
+    const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+template <int DT>
+__device__ __forceinline__ f32x4 mfma16(const u32x4 a, const u32x4 b, f32x4 c) {
+    if constexpr (DT == QT_F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
+                                                      0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
+                                                       0, 0, 0);
+}
+
+// The A fragment of one MFMA step: 8 consecutive weight columns, w = round_to_dtype(dequantised value).
+// Without a zero-point the value is fma(u, s, -OFF s): -OFF s is exact (OFF a power of two), so this is one rounding
+// of q s, the same value as (u - OFF) * s.  With a zero-point: (u - cz) * s, the difference exact.
+template <int DT, bool ZP>
+__device__ __forceinline__ u32x4 frag_from_u(const float (&u)[8], float s, float cz, float noff) {
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if constexpr (ZP) {
+            const float t = u[j] - cz;
+            f[j] = t * s;
+        } else {
+            f[j] = __builtin_fmaf(u[j], s, noff);
+        }
+    }
+    return (u32x4){pack2<DT>(f[0], f[1]), pack2<DT>(f[2], f[3]), pack2<DT>(f[4], f[5]), pack2<DT>(f[6], f[7])};
+}
+
+// one packed word (8 int4 columns) -> u values in column order (nibble j = column j)
+__device__ __forceinline__ void u_int4(unsigned w, float (&u)[8]) {
+    const unsigned lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u[2 * i] = (float)((lo >> (8 * i)) & 0xffu);       // v_cvt_f32_ubyte{i}
+        u[2 * i + 1] = (float)((hi >> (8 * i)) & 0xffu);
+    }
+}
+
+// two dwords (8 int8 columns) -> u = level + 128
+__device__ __forceinline__ void u_int8(unsigned a, unsigned b, float (&u)[8]) {
+    a ^= 0x80808080u;
+    b ^= 0x80808080u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u[i] = (float)((a >> (8 * i)) & 0xffu);
+        u[4 + i] = (float)((b >> (8 * i)) & 0xffu);
+    }
+}
+
+template <bool INT4, int DT, bool ZP, bool GIDX>
+__global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs p) {
+    __shared__ f32x4 red[WQ_WAVES - 1][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int r = lane & 15;            // A row (weight row n0 + r) and B column (activation row m = r)
+    const int kq = lane >> 4;           // which 32 columns of the k-block
+    const int64_t n0 = (int64_t)blockIdx.x * 16;
+    const int64_t n = n0 + r;
+    const bool n_ok = n < p.N;
+    const bool m_ok = r < p.M;
+    const int64_t nrow = n_ok ? n : 0;
+    const unsigned short* xrow = p.X + (int64_t)(m_ok ? r : 0) * p.ldx;
+    const int nkb = (p.K + WQ_KB - 1) / WQ_KB;
+    const int nfull = (GIDX || !p.vec) ? 0 : p.K / WQ_KB;   // k-blocks on the 16-byte path
+    const float off = INT4 ? 8.0f : 128.0f;
+
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    constexpr int WV = INT4 ? 1 : 2;    // 16-byte weight chunks per lane per k-block
+
+    // 16-byte path: batches of WQ_UNROLL k-blocks, every load issued before the first MFMA.  A k-block past nfull in
+    // the last batch re-reads k-block `wave` (in bounds) and is zeroed before use.
+    for (int kb = wave; kb < nfull; kb += WQ_UNROLL * WQ_WAVES) {
+        uint4 wv[WQ_UNROLL][WV];
+        uint4 xv[WQ_UNROLL][4];
+        float sc[WQ_UNROLL], cz[WQ_UNROLL];
+#pragma unroll
+        for (int u = 0; u < WQ_UNROLL; ++u) {
+            const int kbu = kb + u * WQ_WAVES < nfull ? kb + u * WQ_WAVES : wave;
+            const int c0 = kbu * WQ_KB + 32 * kq;
+            if constexpr (INT4) {
+                const uint4* src = (const uint4*)((const int32_t*)p.Wq + nrow * p.Kw + c0 / 8);
+                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x88888888u, 0x88888888u, 0x88888888u,
+                                                                                 0x88888888u);
+            } else {
+                const uint4* src = (const uint4*)((const int8_t*)p.Wq + nrow * p.K + c0);
+                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x80808080u, 0x80808080u, 0x80808080u,
+                                                                                 0x80808080u);
+                wv[u][1] = n_ok ? ld_nt16(src + 1)
+                                : make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                xv[u][s] = m_ok ? *(const uint4*)(xrow + c0 + 8 * s) : make_uint4(0u, 0u, 0u, 0u);
+            float sv = 0.0f, czv = off;
+            if (n_ok) group_params<INT4, ZP, false>(p, nrow, c0, sv, czv);
+            sc[u] = sv;
+            cz[u] = czv;
+        }
+#pragma unroll
+        for (int u = 0; u < WQ_UNROLL; ++u) {
+            const bool live = kb + u * WQ_WAVES < nfull;   // uniform
+            const float s = live ? sc[u] : 0.0f;
+            const float noff = -(off * s);
+            const unsigned wd[8] = {wv[u][0].x, wv[u][0].y, wv[u][0].z, wv[u][0].w, wv[u][WV - 1].x,
+                                    wv[u][WV - 1].y, wv[u][WV - 1].z, wv[u][WV - 1].w};
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                float uu[8];
+                if constexpr (INT4) u_int4(wd[s4], uu);
+                else u_int8(wd[2 * s4], wd[2 * s4 + 1], uu);
+                const u32x4 a = frag_from_u<DT, ZP>(uu, s, cz[u], noff);
+                const uint4 x4 = xv[u][s4];
+                const u32x4 b = live ? (u32x4){x4.x, x4.y, x4.z, x4.w} : (u32x4){0u, 0u, 0u, 0u};
+                acc = mfma16<DT>(a, b, acc);
+            }
+        }
+    }
+    // element-wise path: the partial last k-block, unaligned operands, or g_idx (a scale per column)
+    for (int kb = (nfull > wave ? wave + ((nfull - wave + WQ_WAVES - 1) / WQ_WAVES) * WQ_WAVES : wave); kb < nkb;
+         kb += WQ_WAVES) {
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            float f[8], x[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int c = kb * WQ_KB + 32 * kq + 8 * s4 + j;
+                f[j] = 0.0f;
+                x[j] = 0.0f;
+                if (c < p.K) {
+                    if (n_ok) {
+                        float s, czv;
+                        group_params<INT4, ZP, GIDX>(p, nrow, c, s, czv);
+                        const float t = level_u<INT4>(p, nrow, c) - czv;
+                        f[j] = t * s;
+                    }
+                    if (m_ok) x[j] = h2f<DT>(xrow[c]);
+                }
+            }
+            const u32x4 a = {pack2<DT>(f[0], f[1]), pack2<DT>(f[2], f[3]), pack2<DT>(f[4], f[5]), pack2<DT>(f[6], f[7])};
+            const u32x4 b = {pack2<DT>(x[0], x[1]), pack2<DT>(x[2], x[3]), pack2<DT>(x[4], x[5]), pack2<DT>(x[6], x[7])};
+            acc = mfma16<DT>(a, b, acc);
+        }
+    }
+
+    // D[row 4 kq + i][col r]: output column n0 + 4 kq + i of activation row r.  y = ((w0 + w1) + w2) + w3 (+ bias)
+    if (wave > 0) red[wave - 1][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && m_ok) {
+#pragma unroll
+        for (int w = 0; w < WQ_WAVES - 1; ++w) {
+            const f32x4 o = red[w][lane];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = acc[i] + o[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t nn = n0 + 4 * kq + i;
+            if (nn >= p.N) continue;
+            float y = acc[i];
+            if (p.bias) y = y + h2f<DT>(p.bias[nn]);
+            p.Y[(int64_t)r * p.ldy + nn] = (unsigned short)(pack2<DT>(y, 0.0f) & 0xffffu);
+        }
+    }
+}
+
+template <template <bool, int, bool, bool> class L, typename... A>
+void dispatch(bool int4, int dtype, bool zp, bool gidx, A&&... a) {
+#define QT_WQ_CASE(I4, D, Z, GI) \
+    if (int4 == I4 && dtype == D && zp == Z && gidx == GI) return L<I4, D, Z, GI>::run(a...);
+#define QT_WQ_CASES(I4, D) QT_WQ_CASE(I4, D, false, false) QT_WQ_CASE(I4, D, false, true) \
+    QT_WQ_CASE(I4, D, true, false) QT_WQ_CASE(I4, D, true, true)
+    QT_WQ_CASES(true, QT_BF16) QT_WQ_CASES(true, QT_F16) QT_WQ_CASES(false, QT_BF16) QT_WQ_CASES(false, QT_F16)
+#undef QT_WQ_CASES
+#undef QT_WQ_CASE
+}
+
+template <bool I4, int D, bool Z, bool GI>
+struct LaunchDequant {
+    static void run(dim3 grid, hipStream_t stream, const WqArgs& a, int chunks, int bpr) {
+        hipLaunchKernelGGL((dequant_kernel<I4, D, Z, GI>), grid, dim3(WQ_THREADS), 0, stream, a, chunks, bpr);
+    }
+};
+template <bool I4, int D, bool Z, bool GI>
+struct LaunchSkinny {
+    static void run(dim3 grid, hipStream_t stream, const WqArgs& a) {
+        hipLaunchKernelGGL((wq_skinny_kernel<I4, D, Z, GI>), grid, dim3(WQ_THREADS), 0, stream, a);
+    }
+};
+
+int check_weight(const char* fn, const void* Wq, int w_format, int N, int K, const float* s_w, int G) {
+    QT_CHECK_ARG(Wq && s_w && N > 0 && K > 0, "%s: bad weight arguments", fn);
+    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "%s: w_format %d unsupported", fn, w_format);
+    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "%s: G %d must be 1 or ceil(K / 128) = %d", fn, G, (K + 127) / 128);
+    return QT_OK;
+}
+
+}  // namespace
+
+extern "C" int qt_dequantize_weight(const void* Wq, int w_format, int N, int K, const float* s_w, int G,
+                                    const int8_t* zp_w, const int32_t* g_idx, void* W, int dtype, int64_t ldw,
+                                    qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int e = check_weight("qt_dequantize_weight", Wq, w_format, N, K, s_w, G)) return e;
+    QT_CHECK_ARG(W && ldw >= K, "qt_dequantize_weight: bad output arguments");
+    QT_CHECK_ARG(qt_dtype_is16(dtype), "qt_dequantize_weight: dtype %d must be bf16 or fp16", dtype);
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    const int chunks = (K + 7) / 8;
+    const int bpr = (chunks + WQ_THREADS * DQ_CHUNKS - 1) / (WQ_THREADS * DQ_CHUNKS);
+    QT_CHECK_ARG((int64_t)N * bpr <= 0x7fffffffLL, "qt_dequantize_weight: too many rows");
+    const bool vec = ((uintptr_t)W & 15) == 0 && ldw % 8 == 0 && (int4 || (((uintptr_t)Wq & 7) == 0 && K % 8 == 0));
+    WqArgs a{nullptr, 0, 0, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx, nullptr, (unsigned short*)W, ldw, (int)vec};
+    dispatch<LaunchDequant>(int4, dtype, zp_w != nullptr, g_idx != nullptr, dim3((unsigned)((int64_t)N * bpr)), stream,
+                            a, chunks, bpr);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format,
+                                 int N, const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx,
+                                 const void* bias, void* Y, int64_t ldy, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int e = check_weight("qt_gemm_wq_skinny", Wq, w_format, N, K, s_w, G)) return e;
+    QT_CHECK_ARG(X && Y && M >= 1 && M <= 16 && ldx >= K && ldy >= N,
+                 "qt_gemm_wq_skinny: bad arguments (1 <= M <= 16, ldx >= K, ldy >= N)");
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "qt_gemm_wq_skinny: x_dtype %d must be bf16 or fp16", x_dtype);
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    const bool vec = (((uintptr_t)X | (uintptr_t)Wq) & 15) == 0 && ldx % 8 == 0 &&
+                     (int4 ? ((K + 7) / 8) % 4 == 0 : K % 16 == 0);
+    WqArgs a{(const unsigned short*)X, ldx, M, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx,
+             (const unsigned short*)bias, (unsigned short*)Y, ldy, (int)vec};
+    dispatch<LaunchSkinny>(int4, x_dtype, zp_w != nullptr, g_idx != nullptr, dim3((unsigned)((N + 15) / 16)), stream,
+                           a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}

@@ -7,7 +7,10 @@ Linear either
   activations are quantised per row on the fly and multiplied with the stored integer weights on the int8 MFMA
   (``qt_quantize_tokens_i8`` + ``qt_gemm_i8``, include/quantool_amd.h), as a served W8A8 runtime does; or
 * a plain ``nn.Linear`` holding the dequantised weight ``(q - zp) * scale`` (W4A16, W4A16_ASYM, W8A16), computed once in
-  fp32 from the STORED scale and rounded once to the model dtype.
+  fp32 from the STORED scale and rounded once to the model dtype (the default, ``a16="dequantized"``); or
+* with ``a16="packed"``, a ``WeightOnlyLinear`` that keeps the stored integer weights on the device: decode-sized inputs
+  (M <= ``skinny_max_m`` rows) run the GEMV ``qt_gemm_wq_skinny``, larger ones dequantise the weight into a transient
+  buffer (``qt_dequantize_weight``, bit-identical to the dequantised ``nn.Linear``) and call ``F.linear``.
 
 Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up_proj [E, 2I, H]`` / ``down_proj
 [E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
@@ -17,8 +20,8 @@ down_proj``).  The loader inverts that write: A16 experts are dequantised into t
 that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` + ``qt_moe_combine``).
 
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
-weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward`` and
-``QuantizedExperts.forward`` need the HIP library.
+weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,
+``QuantizedExperts.forward`` and ``WeightOnlyLinear.forward`` on device tensors need the HIP library.
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .serialization import load_state
 
@@ -109,6 +113,75 @@ class QuantizedLinear(nn.Module):
         y = ops.gemm_i8(Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
                         wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
         return y.reshape(*lead, self.out_features)
+
+
+class WeightOnlyLinear(nn.Module):
+    """One W4A16 / W4A16_ASYM / W8A16 Linear of a checkpoint on its stored integer weights.
+
+    ``forward(x)`` with M = rows of ``x``: M <= ``skinny_max_m`` runs ``qt_gemm_wq_skinny`` (the weights read once,
+    dequantised on chip; fp32 sums in the kernel's own fixed order); otherwise ``qt_dequantize_weight`` fills a transient
+    dense weight -- bit-identical to the default loader's ``nn.Linear.weight`` -- and ``F.linear`` runs on it, so the
+    output equals that ``nn.Linear``'s to the bit.  On CPU tensors ``forward`` is ``F.linear`` on ``dequantized_weight``.
+
+    Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
+    ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
+    (optional, model dtype).  Columns stay in their original order."""
+
+    # Decode GEMV up to this many rows, dequantise + F.linear above: at 16 rows the GEMV is still faster than the
+    # dequantise + F.linear pair on every measured Llama-3-8B shape (DESIGN.md 4.9).
+    skinny_max_m = 16
+
+    def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
+                 weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.in_features = int(in_features)
+        self.out_features = int(out_features)
+        self.int4 = weight.dtype == torch.int32
+        self.register_buffer("weight_packed" if self.int4 else "weight", weight.contiguous())
+        self.register_buffer("weight_scale", weight_scale.to(torch.float32).contiguous())
+        self.register_buffer("weight_zero_point", None if weight_zero_point is None
+                             else weight_zero_point.to(torch.int8).contiguous())
+        self.register_buffer("g_idx", None if g_idx is None else g_idx.to(torch.int32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.contiguous())
+
+    @property
+    def qweight(self) -> torch.Tensor:
+        return self.weight_packed if self.int4 else self.weight
+
+    def checkpoint_tensors(self) -> Dict[str, torch.Tensor]:
+        """The module's weight as the checkpoint leaves ``dequantized_weight`` reads."""
+        t = {"weight_packed" if self.int4 else "weight": self.qweight, "weight_scale": self.weight_scale,
+             "weight_shape": torch.tensor([self.out_features, self.in_features])}
+        if self.weight_zero_point is not None:
+            t["weight_zero_point"] = self.weight_zero_point
+        if self.g_idx is not None:
+            t["weight_g_idx"] = self.g_idx
+        return t
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, "
+                f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
+                f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
+                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        bias = None if self.bias is None else self.bias.to(x.dtype)
+        if not x.is_cuda:
+            return F.linear(x, dequantized_weight("WeightOnlyLinear", self.checkpoint_tensors(), x.dtype), bias)
+        from ..hip import ops
+
+        x2 = x.reshape(-1, self.in_features)
+        M = x2.shape[0]
+        if 1 <= M <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
+            if x2.stride(1) != 1:
+                x2 = x2.contiguous()
+            y = ops.gemm_wq_skinny(x2, self.qweight, self.weight_scale, zp_w=self.weight_zero_point, g_idx=self.g_idx,
+                                   bias=bias)
+            return y.reshape(*x.shape[:-1], self.out_features)
+        W = ops.dequantize_weight(self.qweight, self.weight_scale, K=self.in_features, zp_w=self.weight_zero_point,
+                                  g_idx=self.g_idx, dtype=x.dtype)
+        return F.linear(x, W, bias)
 
 
 class QuantizedExperts(nn.Module):
@@ -260,6 +333,23 @@ def quantized_linear_from_tensors(name: str, t: Dict[str, torch.Tensor], act_sym
     return QuantizedLinear(K, N, w, scale, act_symmetric, col_perm=col_perm, bias=bias)
 
 
+def weight_only_linear_from_tensors(name: str, t: Dict[str, torch.Tensor],
+                                    bias: Optional[torch.Tensor] = None) -> WeightOnlyLinear:
+    """A ``WeightOnlyLinear`` from one module's checkpoint tensors (A16 schemes, ``a16="packed"``)."""
+    w, N, K, packed = _levels_and_shape(name, t)
+    scale = t["weight_scale"].to(torch.float32)            # bf16 / fp16 -> fp32 is exact
+    G = scale.shape[1]
+    if scale.dim() != 2 or scale.shape[0] != N or G not in (1, (K + GROUP - 1) // GROUP):
+        raise ValueError(f"{name}: weight_scale {tuple(scale.shape)} is neither channel-wise nor groups of {GROUP} "
+                         f"over {K} columns; load it with a16='dequantized'")
+    zp = t.get("weight_zero_point")
+    if zp is not None:
+        if tuple(zp.shape) != (N, G) or zp.is_floating_point() or int(zp.min()) < -128 or int(zp.max()) > 127:
+            raise ValueError(f"{name}: weight_zero_point must be integers in [-128, 127] of shape {(N, G)}")
+    g_idx = _group_of_columns(name, t, K, G).to(torch.int32) if "weight_g_idx" in t else None
+    return WeightOnlyLinear(K, N, w, scale, weight_zero_point=zp, g_idx=g_idx, bias=bias)
+
+
 def _read_config(path: Path) -> Tuple[dict, dict]:
     cfg = json.loads((path / "config.json").read_text())
     qcfg = cfg.pop("quantization_config", None)
@@ -401,9 +491,15 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
     return QuantizedExperts(H, I, *stacked["gate_up"], *stacked["down"], bank.act_fn, act_symmetric)
 
 
-def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> nn.Module:
+A16_MODES = ("dequantized", "packed")
+
+
+def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized") -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
-    ``QuantizedLinear``s (A8 schemes) or dequantised ``nn.Linear``s (A16 schemes) in place of its quantized Linears.
+    ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
+    default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
+    A8 checkpoints ignore ``a16``.  In packed mode A16 routed-expert banks are still dequantised into the fused bank;
+    ``model._qt_checkpoint`` then records ``"a16": "packed"`` and those banks under ``"dense_expert_banks"``.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -416,6 +512,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
     experts missing or only partly quantized."""
     from transformers import AutoConfig, AutoModelForCausalLM
 
+    if a16 not in A16_MODES:
+        raise ValueError(f"a16={a16!r}: expected one of {A16_MODES}")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -466,6 +564,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
         if a8:
             new = quantized_linear_from_tensors(name, t, act_symmetric, bias=lin.bias.data if lin.bias is not None
                                                 else None)
+        elif a16 == "packed":
+            new = weight_only_linear_from_tensors(name, t, bias=lin.bias.data if lin.bias is not None else None)
         else:
             W = dequantized_weight(name, t, mdtype)
             if tuple(W.shape) != tuple(lin.weight.shape):
@@ -483,4 +583,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None) -> 
     inverse = {v: k for k, v in expert_bank_module_renames(banks, model_type).items()}
     ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
+    if not a8 and a16 == "packed":
+        model._qt_checkpoint["a16"] = "packed"
+        model._qt_checkpoint["dense_expert_banks"] = sorted(experts)
     return model

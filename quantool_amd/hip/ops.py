@@ -674,6 +674,98 @@ def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tens
     return out
 
 
+# ---- A16 runtime: W4A16 / W8A16 weights dequantised on chip -------------------------------------------------------
+def _wq_weight(Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor], g_idx: Optional[torch.Tensor],
+               K: Optional[int]):
+    """Checks one weight description of ``qt_dequantize_weight`` / ``qt_gemm_wq_skinny``; returns (format, N, K, G)."""
+    if not Wq.is_cuda or Wq.dim() != 2 or not Wq.is_contiguous():
+        raise ValueError("Wq must be a contiguous 2-d device tensor")
+    N = Wq.shape[0]
+    if Wq.dtype == torch.int8:
+        fmt = _lib.QT_W_INT8
+        if K is not None and K != Wq.shape[1]:
+            raise ValueError(f"int8 Wq must be [N, K = {K}], got {tuple(Wq.shape)}")
+        K = Wq.shape[1]
+    elif Wq.dtype == torch.int32:
+        fmt = _lib.QT_W_INT4_PACKED
+        if K is None:
+            raise ValueError("packed int4 Wq needs K")
+        if Wq.shape[1] != (K + 7) // 8:
+            raise ValueError(f"packed int4 Wq must be [N, ceil(K/8) = {(K + 7) // 8}], got {tuple(Wq.shape)}")
+    else:
+        raise TypeError(f"Wq must be int8 [N, K] or packed int4 int32 [N, ceil(K/8)], got {Wq.dtype}")
+    K = int(K)
+    if N == 0 or K <= 0:
+        raise ValueError(f"empty weight: N={N}, K={K}")
+    _req(s_w, torch.float32, "s_w", 2)
+    G = s_w.shape[1]
+    if s_w.shape[0] != N or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
+        raise ValueError(f"s_w must be contiguous fp32 [{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
+    if zp_w is not None:
+        _req(zp_w, torch.int8, "zp_w", 2)
+        if tuple(zp_w.shape) != (N, G) or not zp_w.is_contiguous():
+            raise ValueError(f"zp_w must be contiguous int8 [{N}, {G}], got {tuple(zp_w.shape)}")
+    if g_idx is not None:
+        _req(g_idx, torch.int32, "g_idx", 1)
+        if g_idx.numel() != K or not g_idx.is_contiguous():
+            raise ValueError(f"g_idx must be contiguous int32 [{K}]")
+    for t, name in ((s_w, "s_w"), (zp_w, "zp_w"), (g_idx, "g_idx")):
+        if t is not None and t.device != Wq.device:
+            raise ValueError(f"{name} is on {t.device}, Wq on {Wq.device}")
+    return fmt, N, K, G
+
+
+def dequantize_weight(Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
+                      zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                      dtype=torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W [N, K] = round_to_dtype((q - zp) * s_w) per column group (``qt_dequantize_weight``, include/quantool_amd.h):
+    bit-identical to ``engine.qlinear.dequantized_weight``.  Wq int8 [N, K] or packed int4 int32 [N, ceil(K/8)] (then
+    ``K`` is required); s_w fp32 [N, G]; zp_w int8 [N, G]; g_idx int32 [K].  ``out`` (optional) receives W: [N, K] with
+    unit column stride, any row pitch."""
+    lib = load()
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"dtype must be bf16 or fp16, got {dtype}")
+    if out is None:
+        out = torch.empty((N, K), dtype=dtype, device=Wq.device)
+    elif (out.dtype != dtype or tuple(out.shape) != (N, K) or out.stride(1) != 1 or out.device != Wq.device):
+        raise ValueError(f"out must be a {dtype} [{N}, {K}] tensor on {Wq.device} with unit column stride")
+    check("qt_dequantize_weight", lib.qt_dequantize_weight(
+        Wq.data_ptr(), fmt, N, K, s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx), out.data_ptr(), _dtype_code(out),
+        out.stride(0), _stream()))
+    return out
+
+
+SKINNY_MAX_M = 16   # rows of X qt_gemm_wq_skinny takes
+
+
+def gemm_wq_skinny(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w: Optional[torch.Tensor] = None,
+                   g_idx: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y [M, N] = X [M, K] . w^T (+ bias) with w the dequantised weight, fp32 accumulation, one rounding to X's dtype
+    (``qt_gemm_wq_skinny``): the decode GEMV, 1 <= M <= 16.  X bf16 / fp16 with unit column stride (any row pitch);
+    weight arguments as ``dequantize_weight``; bias [N] in X's dtype."""
+    lib = load()
+    code = _act16(X, "X")
+    if X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
+                         f"strides {X.stride()}")
+    M, K = X.shape
+    if not 1 <= M <= SKINNY_MAX_M:
+        raise ValueError(f"gemm_wq_skinny takes 1 <= M <= {SKINNY_MAX_M} rows, got {M}")
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    if bias is not None:
+        _req(bias, X.dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+    Y = torch.empty((M, N), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_skinny", lib.qt_gemm_wq_skinny(
+        X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx),
+        _ptr(bias), Y.data_ptr(), Y.stride(0), _stream()))
+    return Y
+
+
 # ---- a12  AWQ ------------------------------------------------------------------------------
 def _w2d(W: torch.Tensor):
     if W.dim() != 2 or not W.is_cuda or W.stride(1) != 1:

@@ -1,0 +1,130 @@
+"""Batch-1 greedy decoding of a W4A16 g128 checkpoint, loaded dequantised and packed.
+
+  python tools/decode_bench.py <checkpoint dir> [--layers 32] [--prompt 128] [--new 128] [--modes dequantized,packed]
+
+Writes (once: an existing checkpoint in the directory is reused) a W4A16 g128 checkpoint of a random-init
+Llama-3-8B-shaped model: round-to-nearest levels of every decoder Linear, scale = absmax / 7.5 per group of 128 columns
+(no calibration: the timing does not depend on the values).  Then, per mode, ``load_quantized(dir, a16=mode)`` and a
+KV-cached greedy decode of --new tokens after a --prompt-token prompt.  Prints one JSON line: per mode ms per generated
+token (the decode steps after the prompt, wall time with the device synchronised), the resident bytes of the decoder
+Linears, ``memory_allocated`` after loading and ``max_memory_allocated`` during the decode; and how many generated tokens
+agree between the modes (and the first position where they differ).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from quantool_amd.engine.qlinear import A16_MODES, WeightOnlyLinear, load_quantized, pack_int4  # noqa: E402
+from quantool_amd.engine.schemes import PRESET_SCHEMES  # noqa: E402
+from quantool_amd.engine.serialization import quantization_config, save_state  # noqa: E402
+
+LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj",
+           "mlp.up_proj", "mlp.down_proj")
+
+
+def write_checkpoint(path: Path, layers: int, dev) -> None:
+    from transformers import LlamaConfig, LlamaForCausalLM
+
+    cfg = LlamaConfig(hidden_size=4096, intermediate_size=14336, num_hidden_layers=layers, num_attention_heads=32,
+                      num_key_value_heads=8, vocab_size=128256, max_position_embeddings=8192, rope_theta=500000.0,
+                      tie_word_embeddings=False)
+    torch.manual_seed(0)
+    with dev:
+        model = LlamaForCausalLM(cfg).to(torch.bfloat16)
+    state = {}
+    quantized = {f"model.layers.{i}.{l}" for i in range(layers) for l in LINEARS}
+    for k, v in model.state_dict().items():
+        mod = k.rpartition(".")[0]
+        if mod not in quantized:
+            state[k] = v.cpu()
+            continue
+        W = v.float()
+        N, K = W.shape
+        s = (W.reshape(N, K // 128, 128).abs().amax(-1) / 7.5).clamp(min=1e-8).to(torch.bfloat16)
+        q = torch.round(W.reshape(N, K // 128, 128) / s.float()[..., None]).clamp(-8, 7).reshape(N, K).to(torch.int8)
+        state[f"{mod}.weight_packed"] = pack_int4(q).cpu()
+        state[f"{mod}.weight_scale"] = s.cpu()
+        state[f"{mod}.weight_shape"] = torch.tensor([N, K])
+    wa = PRESET_SCHEMES["W4A16"]
+    qcfg = quantization_config(wa.weights.to_config(), wa.format, ["lm_head"], None)
+    save_state(state, qcfg, path, model.config.to_dict())
+    del model, state
+    torch.cuda.empty_cache()
+
+
+def decode(model, prompt: torch.Tensor, new: int):
+    """Greedy tokens and the wall time of the decode steps after the prompt."""
+    with torch.no_grad():
+        out = model(input_ids=prompt, use_cache=True)
+        past = out.past_key_values
+        tok = out.logits[:, -1].argmax(-1, keepdim=True)
+        toks = [tok]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(new - 1):
+            out = model(input_ids=tok, past_key_values=past, use_cache=True)
+            past = out.past_key_values
+            tok = out.logits[:, -1].argmax(-1, keepdim=True)
+            toks.append(tok)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+    return torch.cat(toks, 1)[0].tolist(), (t1 - t0) / max(new - 1, 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("checkpoint")
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--modes", default=",".join(A16_MODES))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench needs a GPU")
+    dev = torch.device("cuda:0")
+    path = Path(args.checkpoint)
+    if not (path / "config.json").exists():
+        path.mkdir(parents=True, exist_ok=True)
+        write_checkpoint(path, args.layers, dev)
+    prompt = torch.randint(0, 128256, (1, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
+    result = {"tool": "decode_bench", "checkpoint": str(path), "prompt": args.prompt, "new": args.new, "modes": {}}
+    tokens = {}
+    for mode in args.modes.split(","):
+        torch.cuda.empty_cache()
+        model = load_quantized(path, device=dev, a16=mode)
+        lin_bytes = 0
+        for n, m in model.named_modules():
+            if n.rpartition(".")[2] in {l.rpartition(".")[2] for l in LINEARS} and ".layers." in n:
+                lin_bytes += sum(t.numel() * t.element_size() for t in list(m.parameters()) + list(m.buffers()))
+        torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()
+        decode(model, prompt[:, :8], 4)                          # warm-up: kernels, allocator
+        torch.cuda.reset_peak_memory_stats()
+        toks, per_tok = decode(model, prompt, args.new)
+        result["modes"][mode] = {
+            "ms_per_token": round(per_tok * 1e3, 3), "decoder_linear_bytes": lin_bytes,
+            "memory_allocated_after_load": resident, "max_memory_allocated_decode": torch.cuda.max_memory_allocated(),
+            "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules())}
+        tokens[mode] = toks
+        del model
+    if len(tokens) == 2:
+        a, b = tokens.values()
+        same = [x == y for x, y in zip(a, b)]
+        result["tokens_agree"] = sum(same)
+        result["first_difference"] = same.index(False) if not all(same) else None
+        d, p = (result["modes"][m] for m in A16_MODES)
+        result["linear_bytes_ratio"] = round(p["decoder_linear_bytes"] / d["decoder_linear_bytes"], 4)
+        result["speedup"] = round(d["ms_per_token"] / p["ms_per_token"], 3)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,10 +1,12 @@
 """Perplexity of a saved checkpoint (any scheme this backend writes) on stored token ids.
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
+                                  [--a16 dequantized|packed]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
-on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights.  Prints one JSON
-line: perplexity, mean NLL, predicted tokens, load and evaluation wall times.
+on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
+on ``WeightOnlyLinear``s that keep the integer weights).  Prints one JSON line: perplexity, mean NLL, predicted tokens,
+the module counts, load and evaluation wall times.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from quantool_amd.engine.qlinear import QuantizedLinear, load_quantized  # noqa: E402
+from quantool_amd.engine.qlinear import A16_MODES, QuantizedLinear, WeightOnlyLinear, load_quantized  # noqa: E402
 from quantool_amd.evaluate import perplexity  # noqa: E402
 
 
@@ -29,11 +31,12 @@ def main():
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--dtype", default=None, choices=[None, "bfloat16", "float16"])
+    ap.add_argument("--a16", default="dequantized", choices=list(A16_MODES))
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
     model = load_quantized(args.checkpoint, device=args.device,
-                           dtype=getattr(torch, args.dtype) if args.dtype else None)
+                           dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -43,6 +46,7 @@ def main():
     t2 = time.perf_counter()
     r.update({"checkpoint": str(args.checkpoint), "format": model._qt_checkpoint["format"],
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()),
+              "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
     print(json.dumps(r))
 
