@@ -375,6 +375,24 @@ int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64_t ldx, con
                       const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
                       int64_t ldy, qt_stream_t stream);
 
+/* qt_gemm_wq_grouped: qt_gemm_wq_skinny over E weight matrices at once, for routed-expert banks (engine/qlinear.py
+ *   WeightOnlyExperts).  Y [R, N] in x_dtype (pitch ldy): expert e owns output rows
+ *   [offsets[e], offsets[e + 1]) (offsets int32 [E + 1], on the device, ascending, offsets[E] <= R; rows past
+ *   offsets[E] are not written) and weight matrix e: Wq [E, N, ceil(K/8)] packed int4 or [E, N, K] int8, s_w fp32
+ *   [E, N, G], zp_w int8 [E, N, G] or NULL, g_idx int32 [E, K] or NULL, each with the meaning above.  The X row of
+ *   output row m is X[row_idx[m]] (row_idx int32 [R], values index rows of X [., K] of pitch ldx; the caller's
+ *   contract) or X[m] when row_idx is NULL.  No bias.
+ *   Every expert's rows are processed in tiles of 16 rows, in ascending order, and every row is equal to the bit to
+ *   qt_gemm_wq_skinny with that expert's weight applied to that row: it is the same tile code with the same k-block
+ *   order, wave order and fixed reduction, and a row of the MFMA depends on its own input row alone, so the padding
+ *   rows and the other rows of the tile change nothing.  Deterministic, no atomics, no host read of the counts: the
+ *   grid is ceil(N/16) column tiles x (floor(R/16) + min(E, R)) row-tile slots, an upper bound on
+ *   sum_e ceil(rows_e / 16); each workgroup finds its expert and tile by walking offsets, and a surplus one exits
+ *   before any weight load.  Only the experts that own rows have their weights read.  R / 16 + min(E, R) <= 65535. */
+int qt_gemm_wq_grouped(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                       const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w, int G,
+                       const int8_t* zp_w, const int32_t* g_idx, void* Y, int64_t ldy, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

@@ -9,6 +9,10 @@
 //                        once), dequantises it and feeds v_mfma_f32_16x16x32_{bf16,f16} with M padded to 16 (the
 //                        activations are the B operand).  Four k-blocks are in flight per wave before the first MFMA.
 //                        The 4 waves' fp32 partials are summed through LDS in wave order: no atomics.
+// qt_gemm_wq_grouped     the same kernel over E weight matrices (MOE = true): grid (column tiles, slots), one slot per
+//                        16-row tile of one expert's rows.  The slot count floor(R/16) + min(E, R) bounds the tiles of
+//                        any routing without reading the counts; a workgroup finds its (expert, tile) by walking
+//                        offsets and a surplus one returns before its first weight load and its barrier.
 //
 // -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own unless written as __builtin_fmaf.
 #include "common.h"
@@ -34,6 +38,11 @@ struct WqArgs {
     unsigned short* Y;          // Y (GEMV) or W (dequantise)
     int64_t ldy;
     int vec;                    // 16-byte weight / activation / output accesses are aligned and in bounds
+    // grouped form only (qt_gemm_wq_grouped): M is the routed-row count R; expert e owns output rows
+    // [offsets[e], offsets[e + 1]) and weight matrix e; X row of output row m is row_idx[m] (or m when NULL)
+    const int32_t* offsets;
+    const int32_t* row_idx;
+    int E;
 };
 
 template <int DT>
@@ -189,9 +198,40 @@ __device__ __forceinline__ void u_int8(unsigned a, unsigned b, float (&u)[8]) {
     }
 }
 
-template <bool INT4, int DT, bool ZP, bool GIDX>
-__global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs p) {
+// MOE: the grouped form.  blockIdx.y is a slot: the walk over offsets (clamped to [0, R], so a bad table cannot move a
+// write out of Y) maps it to expert e and rows [m0, m0 + M) of that expert, M <= 16; the expert's weight, scale,
+// zero-point and g_idx rows are then the arguments of the same tile code.  Rows are independent through the MFMA (row m
+// of D reads B column m only), so each row equals the skinny kernel's on that expert alone.
+template <bool INT4, int DT, bool ZP, bool GIDX, bool MOE = false>
+__global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs args) {
     __shared__ f32x4 red[WQ_WAVES - 1][64];
+    WqArgs p = args;
+    int64_t m0 = 0;                     // output row of activation row 0 of the tile
+    if constexpr (MOE) {
+        const int64_t slot = blockIdx.y;
+        int64_t start = 0;
+        int e = -1;
+        int64_t hi = 0;
+        for (int j = 0; j < p.E; ++j) {
+            const int64_t lo = min(max((int64_t)p.offsets[j], (int64_t)0), (int64_t)p.M);
+            hi = min(max((int64_t)p.offsets[j + 1], lo), (int64_t)p.M);
+            const int64_t nt = (hi - lo + 15) / 16;
+            if (slot < start + nt) {
+                e = j;
+                m0 = lo + (slot - start) * 16;
+                break;
+            }
+            start += nt;
+        }
+        if (e < 0) return;              // surplus slot (uniform: before any load of the weights and the barrier)
+        p.M = (int)min(hi - m0, (int64_t)16);
+        const int64_t wrow = INT4 ? (int64_t)p.Kw : (int64_t)p.K;
+        p.Wq = INT4 ? (const void*)((const int32_t*)p.Wq + (int64_t)e * p.N * wrow)
+                    : (const void*)((const int8_t*)p.Wq + (int64_t)e * p.N * wrow);
+        p.s_w += (int64_t)e * p.N * p.G;
+        if constexpr (ZP) p.zp_w += (int64_t)e * p.N * p.G;
+        if constexpr (GIDX) p.g_idx += (int64_t)e * p.K;
+    }
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int r = lane & 15;            // A row (weight row n0 + r) and B column (activation row m = r)
@@ -201,7 +241,9 @@ __global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs p) {
     const bool n_ok = n < p.N;
     const bool m_ok = r < p.M;
     const int64_t nrow = n_ok ? n : 0;
-    const unsigned short* xrow = p.X + (int64_t)(m_ok ? r : 0) * p.ldx;
+    int64_t xr = m_ok ? r : 0;
+    if constexpr (MOE) xr = p.row_idx ? (int64_t)p.row_idx[m0 + xr] : m0 + xr;
+    const unsigned short* xrow = p.X + xr * p.ldx;
     const int nkb = (p.K + WQ_KB - 1) / WQ_KB;
     const int nfull = (GIDX || !p.vec) ? 0 : p.K / WQ_KB;   // k-blocks on the 16-byte path
     const float off = INT4 ? 8.0f : 128.0f;
@@ -300,7 +342,7 @@ __global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs p) {
             if (nn >= p.N) continue;
             float y = acc[i];
             if (p.bias) y = y + h2f<DT>(p.bias[nn]);
-            p.Y[(int64_t)r * p.ldy + nn] = (unsigned short)(pack2<DT>(y, 0.0f) & 0xffffu);
+            p.Y[(m0 + r) * p.ldy + nn] = (unsigned short)(pack2<DT>(y, 0.0f) & 0xffffu);
         }
     }
 }
@@ -328,6 +370,12 @@ struct LaunchSkinny {
         hipLaunchKernelGGL((wq_skinny_kernel<I4, D, Z, GI>), grid, dim3(WQ_THREADS), 0, stream, a);
     }
 };
+template <bool I4, int D, bool Z, bool GI>
+struct LaunchGrouped {
+    static void run(dim3 grid, hipStream_t stream, const WqArgs& a) {
+        hipLaunchKernelGGL((wq_skinny_kernel<I4, D, Z, GI, true>), grid, dim3(WQ_THREADS), 0, stream, a);
+    }
+};
 
 int check_weight(const char* fn, const void* Wq, int w_format, int N, int K, const float* s_w, int G) {
     QT_CHECK_ARG(Wq && s_w && N > 0 && K > 0, "%s: bad weight arguments", fn);
@@ -350,7 +398,8 @@ extern "C" int qt_dequantize_weight(const void* Wq, int w_format, int N, int K, 
     const int bpr = (chunks + WQ_THREADS * DQ_CHUNKS - 1) / (WQ_THREADS * DQ_CHUNKS);
     QT_CHECK_ARG((int64_t)N * bpr <= 0x7fffffffLL, "qt_dequantize_weight: too many rows");
     const bool vec = ((uintptr_t)W & 15) == 0 && ldw % 8 == 0 && (int4 || (((uintptr_t)Wq & 7) == 0 && K % 8 == 0));
-    WqArgs a{nullptr, 0, 0, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx, nullptr, (unsigned short*)W, ldw, (int)vec};
+    WqArgs a{nullptr, 0, 0, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx, nullptr, (unsigned short*)W, ldw, (int)vec,
+             nullptr, nullptr, 0};
     dispatch<LaunchDequant>(int4, dtype, zp_w != nullptr, g_idx != nullptr, dim3((unsigned)((int64_t)N * bpr)), stream,
                             a, chunks, bpr);
     QT_LAUNCH_CHECK();
@@ -369,9 +418,35 @@ extern "C" int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64
     const bool vec = (((uintptr_t)X | (uintptr_t)Wq) & 15) == 0 && ldx % 8 == 0 &&
                      (int4 ? ((K + 7) / 8) % 4 == 0 : K % 16 == 0);
     WqArgs a{(const unsigned short*)X, ldx, M, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx,
-             (const unsigned short*)bias, (unsigned short*)Y, ldy, (int)vec};
+             (const unsigned short*)bias, (unsigned short*)Y, ldy, (int)vec, nullptr, nullptr, 0};
     dispatch<LaunchSkinny>(int4, x_dtype, zp_w != nullptr, g_idx != nullptr, dim3((unsigned)((N + 15) / 16)), stream,
                            a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_wq_grouped(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                                  const int32_t* offsets, int E, const void* Wq, int w_format, int N,
+                                  const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, void* Y,
+                                  int64_t ldy, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int e = check_weight("qt_gemm_wq_grouped", Wq, w_format, N, K, s_w, G)) return e;
+    QT_CHECK_ARG(X && Y && offsets && R > 0 && E > 0 && ldx >= K && ldy >= N,
+                 "qt_gemm_wq_grouped: bad arguments (R, E > 0, ldx >= K, ldy >= N)");
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "qt_gemm_wq_grouped: x_dtype %d must be bf16 or fp16", x_dtype);
+    QT_CHECK_ARG(R <= 0x7fffffffLL && E <= 4096, "qt_gemm_wq_grouped: R %lld or E %d too large", (long long)R, E);
+    const int64_t slots = R / 16 + (E < R ? E : R);
+    QT_CHECK_ARG(slots <= 65535, "qt_gemm_wq_grouped: %lld row-tile slots (R = %lld) exceed the grid", (long long)slots,
+                 (long long)R);
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    const int64_t wrow_bytes = int4 ? (int64_t)((K + 7) / 8) * 4 : (int64_t)K;
+    // as qt_gemm_wq_skinny, and every expert's matrix 16-byte aligned as well as the base
+    const bool vec = (((uintptr_t)X | (uintptr_t)Wq) & 15) == 0 && ldx % 8 == 0 &&
+                     (int4 ? ((K + 7) / 8) % 4 == 0 : K % 16 == 0) && ((int64_t)N * wrow_bytes) % 16 == 0;
+    WqArgs a{(const unsigned short*)X, ldx, (int)R, Wq, N, K, (K + 7) / 8, s_w, G, zp_w, g_idx, nullptr,
+             (unsigned short*)Y, ldy, (int)vec, offsets, row_idx, E};
+    dispatch<LaunchGrouped>(int4, x_dtype, zp_w != nullptr, g_idx != nullptr,
+                            dim3((unsigned)((N + 15) / 16), (unsigned)slots), stream, a);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

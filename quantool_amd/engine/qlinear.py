@@ -16,12 +16,15 @@ Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up
 [E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
 ``<layer>.block_sparse_moe.experts.{e}.w1 / w3 / w2``, otherwise ``<layer>.mlp.experts.{e}.gate_proj / up_proj /
 down_proj``).  The loader inverts that write: A16 experts are dequantised into the fused parameters
-(``gate_up_proj[e] = cat(w1, w3)``, ``down_proj[e] = w2``); A8 experts replace the bank with a ``QuantizedExperts``
-that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` + ``qt_moe_combine``).
+(``gate_up_proj[e] = cat(w1, w3)``, ``down_proj[e] = w2``), or with ``a16_experts="packed"`` replace the bank with a
+``WeightOnlyExperts`` on the stored integer weights (``qt_gemm_wq_grouped`` at decode); A8 experts replace the bank with
+a ``QuantizedExperts`` that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` +
+``qt_moe_combine``).
 
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
 weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,
-``QuantizedExperts.forward`` and ``WeightOnlyLinear.forward`` on device tensors need the HIP library.
+``QuantizedExperts.forward``, ``WeightOnlyLinear.forward`` and ``WeightOnlyExperts.forward`` on device tensors need
+the HIP library.
 """
 from __future__ import annotations
 
@@ -241,6 +244,111 @@ class QuantizedExperts(nn.Module):
         return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
 
 
+class WeightOnlyExperts(nn.Module):
+    """A W4A16 / W4A16_ASYM / W8A16 routed-expert bank on its stored integer weights: ``forward(hidden_states,
+    top_k_index, top_k_weights)`` as the fused transformers bank it replaces.
+
+    With T = rows of ``hidden_states`` (known on the host) and 1 <= T <= ``grouped_max_tokens``: ``qt_moe_route`` orders
+    the routed rows by expert, the gate_up GEMV (``qt_gemm_wq_grouped``) gathers them by token, ``act_fn(gate) * up``
+    runs in torch as the fused module does, the down GEMV reads the routed rows in place and ``qt_moe_combine`` sums
+    each token's weighted rows in ascending expert order.  Only the experts that were hit are read, and nothing waits on
+    the host.  Larger T: both banks are dequantised into transient [E, 2I, H] / [E, H, I] tensors
+    (``qt_dequantize_weight``, bit-identical to the dense bank ``a16_experts="dequantized"`` loads) and the bank's own
+    transformers forward runs on them (honouring ``config._experts_implementation``), so the output equals the dense
+    bank's to the bit.  On CPU tensors ``forward`` is that bank forward on ``dequantized_weight``.
+
+    Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
+    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
+    [E, H] (optional, actorder ``group``); ``down`` int32 [E, H, ceil(I/8)] or int8 [E, H, I] and its ``down_scale``,
+    ``down_zero_point``, ``down_g_idx`` likewise.  Columns stay in the checkpoint's order.
+
+    ``bank`` is the fused module replaced: its ``gate_up_proj`` / ``down_proj`` are swapped for empty stand-ins and it
+    is kept (not as a submodule) for its forward alone."""
+
+    # Grouped GEMV up to this many tokens, dequantise + the bank's forward above.  At Mixtral-8x7B's shapes the GEMV pair
+    # re-reads an expert's weights once per 16 of its rows and still beats the dequantise path (2.7 ms) up to T = 192;
+    # at 128 it takes 1.2 ms (DESIGN.md 4.10).
+    grouped_max_tokens = 128
+
+    def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
+                 down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
+                 gate_up_g_idx: Optional[torch.Tensor] = None, down_zero_point: Optional[torch.Tensor] = None,
+                 down_g_idx: Optional[torch.Tensor] = None):
+        super().__init__()
+        E, I2, H = bank.gate_up_proj.shape
+        self.num_experts, self.hidden_dim, self.intermediate_dim = int(E), int(H), int(I2) // 2
+        self.act_fn = bank.act_fn
+        self.int4 = gate_up.dtype == torch.int32
+        for name, w, s, zp, gi in (("gate_up", gate_up, gate_up_scale, gate_up_zero_point, gate_up_g_idx),
+                                   ("down", down, down_scale, down_zero_point, down_g_idx)):
+            self.register_buffer(name, w.contiguous())
+            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
+            self.register_buffer(f"{name}_zero_point", None if zp is None else zp.to(torch.int8).contiguous())
+            self.register_buffer(f"{name}_g_idx", None if gi is None else gi.to(torch.int32).contiguous())
+        p = bank.gate_up_proj
+        for n in ("gate_up_proj", "down_proj"):
+            setattr(bank, n, nn.Parameter(torch.empty(0, dtype=p.dtype, device=p.device), requires_grad=False))
+        self.__dict__["_bank"] = bank
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
+                f"weights={'int4' if self.int4 else 'int8'}, "
+                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
+                f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
+                f"grouped_max_tokens={self.grouped_max_tokens}")
+
+    def _part(self, part: str):
+        return (getattr(self, part), getattr(self, f"{part}_scale"), getattr(self, f"{part}_zero_point"),
+                getattr(self, f"{part}_g_idx"), self.hidden_dim if part == "gate_up" else self.intermediate_dim)
+
+    def dense_weight(self, part: str, dtype: torch.dtype) -> torch.Tensor:
+        """The ``part`` ("gate_up" / "down") bank dequantised, [E, N, K] in ``dtype``: the dense bank's parameter."""
+        w, s, zp, gi, K = self._part(part)
+        E, N = w.shape[:2]
+        if not w.is_cuda:
+            def leaves(e):
+                t = {"weight_packed" if self.int4 else "weight": w[e], "weight_scale": s[e],
+                     "weight_shape": torch.tensor([N, K])}
+                if zp is not None:
+                    t["weight_zero_point"] = zp[e]
+                if gi is not None:
+                    t["weight_g_idx"] = gi[e]
+                return t
+
+            return torch.stack([dequantized_weight(f"{part}[{e}]", leaves(e), dtype) for e in range(E)])
+        from ..hip import ops
+
+        out = torch.empty((E, N, K), dtype=dtype, device=w.device)
+        if gi is None:                      # one call over the stacked [E N, .] rows
+            ops.dequantize_weight(w.view(E * N, -1), s.view(E * N, -1), K=K,
+                                  zp_w=None if zp is None else zp.view(E * N, -1), dtype=dtype, out=out.view(E * N, K))
+        else:
+            for e in range(E):
+                ops.dequantize_weight(w[e], s[e], K=K, zp_w=None if zp is None else zp[e], g_idx=gi[e], dtype=dtype,
+                                      out=out[e])
+        return out
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        x = hidden_states.reshape(-1, self.hidden_dim)
+        T = x.shape[0]
+        if not x.is_cuda or not 1 <= T <= self.grouped_max_tokens:
+            dense = {"gate_up_proj": self.dense_weight("gate_up", hidden_states.dtype),
+                     "down_proj": self.dense_weight("down", hidden_states.dtype)}
+            return torch.func.functional_call(self._bank, dense, (hidden_states, top_k_index, top_k_weights))
+        from ..hip import ops
+
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
+        w, s, zp, gi, K = self._part("gate_up")
+        gu = ops.gemm_wq_grouped(x, w, s, offsets, row_idx=src_token, K=K, zp_w=zp, g_idx=gi)
+        gate, up = gu.chunk(2, dim=-1)
+        h = self.act_fn(gate) * up
+        w, s, zp, gi, K = self._part("down")
+        y = ops.gemm_wq_grouped(h, w, s, offsets, K=K, zp_w=zp, g_idx=gi)
+        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
+
+
 # ---- the loader ------------------------------------------------------------------------------------------------------
 def _is_a8(block) -> bool:
     """The 8-bit dynamic per-token integer block W8A8 / INT8 / W4A8 write (schemes.py _A8_TOKEN_DYN)."""
@@ -427,8 +535,9 @@ def _expert_banks(path, model: nn.Module, model_type, dense: Dict[str, torch.Ten
 
 
 def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[str, tuple]], a8: bool,
-               act_symmetric: bool, mdtype: torch.dtype, dev) -> Optional[nn.Module]:
-    """Fill (A16, dense) or replace (A8: the returned ``QuantizedExperts``) one fused bank from its experts."""
+               act_symmetric: bool, mdtype: torch.dtype, dev, packed_experts: bool = False) -> Optional[nn.Module]:
+    """Fill (A16, dense) or replace (A8: the returned ``QuantizedExperts``; A16 with ``packed_experts``: the returned
+    ``WeightOnlyExperts``) one fused bank from its experts."""
     gu, dn = bank.gate_up_proj, bank.down_proj
     E, I2, H = gu.shape
     I = I2 // 2
@@ -447,7 +556,7 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
             raise ValueError(f"{path}: {bank_name}.{e}.{r} has shape {tuple(shape)} in the checkpoint, {want[r]} in "
                              "the model")
 
-    if kinds == {"dense"} or not a8:
+    if kinds == {"dense"} or not (a8 or packed_experts):
         for e in range(E):
             W = {}
             for r in roles:
@@ -459,13 +568,22 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
             dn.data[e] = W["down_proj"]
         return None
 
+    # stacked[part] = (weights, scales, zero-points or None, g_idx [E, K] or None), gate rows before up rows
     stacked = {}
     for part, rs in (("gate_up", ("gate_proj", "up_proj")), ("down", ("down_proj",))):
-        ws, ss = [], []
+        ws, ss, zs, gs = [], [], [], []
         for e in range(E):
             for r in rs:
                 name = f"{bank_name}.{e}.{r}"
                 t = {k: v.to(dev) for k, v in experts[e][r][1].items()}
+                if not a8:                 # A16: the checks and buffers of a WeightOnlyLinear
+                    m = weight_only_linear_from_tensors(name, t)
+                    shape_check(e, r, (m.out_features, m.in_features))
+                    ws.append(m.qweight)
+                    ss.append(m.weight_scale)
+                    zs.append(m.weight_zero_point)
+                    gs.append(m.g_idx)
+                    continue
                 if "weight_g_idx" in t:
                     raise NotImplementedError(f"{path}: {name}: A8 expert weights with weight_g_idx (actorder "
                                               "'group') need a per-expert column permutation, which the grouped "
@@ -481,25 +599,45 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
                                      f"groups of {GROUP} over {K} columns")
                 ws.append(w)
                 ss.append(scale)
-        if len({w.dtype for w in ws}) > 1 or len({s.shape[1] for s in ss}) > 1:
+                zs.append(None)
+                gs.append(None)
+        if (len({w.dtype for w in ws}) > 1 or len({s.shape[1] for s in ss}) > 1 or len({z is None for z in zs}) > 1
+                or len({g is None for g in gs}) > 1):
             raise ValueError(f"{path}: {bank_name}: the {part} weights of the experts mix formats or group counts")
         per = len(rs)
-        stacked[part] = (torch.stack([torch.cat(ws[e * per:(e + 1) * per], 0) for e in range(E)]),
-                         torch.stack([torch.cat(ss[e * per:(e + 1) * per], 0) for e in range(E)]))
+        g_idx = None
+        if gs[0] is not None:
+            for e in range(E):
+                if not all(torch.equal(gs[e * per], g) for g in gs[e * per:(e + 1) * per]):
+                    raise ValueError(f"{path}: {bank_name}.{e}: gate_proj and up_proj group their columns differently "
+                                     "(weight_g_idx); the grouped GEMV takes one column grouping per expert")
+            g_idx = torch.stack(gs[::per])
+
+        def stack(xs):
+            return None if xs[0] is None else torch.stack([torch.cat(xs[e * per:(e + 1) * per], 0) for e in range(E)])
+
+        stacked[part] = (stack(ws), stack(ss), stack(zs), g_idx)
     if stacked["gate_up"][0].dtype != stacked["down"][0].dtype:
         raise ValueError(f"{path}: {bank_name}: gate_up and down weights differ in format")
-    return QuantizedExperts(H, I, *stacked["gate_up"], *stacked["down"], bank.act_fn, act_symmetric)
+    (gu_w, gu_s, gu_z, gu_g), (dn_w, dn_s, dn_z, dn_g) = stacked["gate_up"], stacked["down"]
+    if a8:
+        return QuantizedExperts(H, I, gu_w, gu_s, dn_w, dn_s, bank.act_fn, act_symmetric)
+    return WeightOnlyExperts(bank, gu_w, gu_s, dn_w, dn_s, gate_up_zero_point=gu_z, gate_up_g_idx=gu_g,
+                             down_zero_point=dn_z, down_g_idx=dn_g)
 
 
 A16_MODES = ("dequantized", "packed")
 
 
-def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized") -> nn.Module:
+def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
+                   a16_experts: str = "dequantized") -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
-    A8 checkpoints ignore ``a16``.  In packed mode A16 routed-expert banks are still dequantised into the fused bank;
-    ``model._qt_checkpoint`` then records ``"a16": "packed"`` and those banks under ``"dense_expert_banks"``.
+    A8 checkpoints ignore ``a16`` and ``a16_experts``.  In packed mode A16 routed-expert banks are still dequantised
+    into the fused bank unless ``a16_experts="packed"`` (which needs ``a16="packed"``) replaces each with a
+    ``WeightOnlyExperts``; ``model._qt_checkpoint`` then records ``"a16": "packed"``, the banks left dense under
+    ``"dense_expert_banks"`` and, with ``a16_experts="packed"``, the packed ones under ``"packed_expert_banks"``.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -508,12 +646,18 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
 
     Refused with ``ValueError`` / ``NotImplementedError``: float-quantized checkpoints, any ``input_activations`` block
     other than 8-bit dynamic per-token, an A8 checkpoint that carries ``weight_zero_point``, routed-expert weights
-    where the model has no fused bank, A8 expert weights with ``weight_g_idx``, experts with a bias, and banks with
-    experts missing or only partly quantized."""
+    where the model has no fused bank, A8 expert weights with ``weight_g_idx``, experts with a bias, banks with
+    experts missing or only partly quantized, and (packed A16 experts) banks whose experts mix formats, group counts
+    or zero-points, or whose gate and up halves group their columns differently."""
     from transformers import AutoConfig, AutoModelForCausalLM
 
     if a16 not in A16_MODES:
         raise ValueError(f"a16={a16!r}: expected one of {A16_MODES}")
+    if a16_experts not in A16_MODES:
+        raise ValueError(f"a16_experts={a16_experts!r}: expected one of {A16_MODES}")
+    if a16_experts == "packed" and a16 != "packed":
+        raise ValueError("a16_experts='packed' needs a16='packed' (packed expert banks beside dequantised Linears "
+                         "is not a mode this loader offers)")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -551,9 +695,13 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
 
     a8 = acts is not None
     act_symmetric = bool(acts.get("symmetric", True)) if a8 else True
+    packed_experts = not a8 and a16_experts == "packed"
+    replaced = []
     for bank_name, by_expert in experts.items():
-        new = _load_bank(path, bank_name, banks[bank_name], by_expert, a8, act_symmetric, mdtype, dev)
+        new = _load_bank(path, bank_name, banks[bank_name], by_expert, a8, act_symmetric, mdtype, dev,
+                         packed_experts=packed_experts)
         if new is not None:
+            replaced.append(bank_name)
             parent_name, _, leaf = bank_name.rpartition(".")
             setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
     for name, t in quant.items():
@@ -585,5 +733,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
-        model._qt_checkpoint["dense_expert_banks"] = sorted(experts)
+        model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))
+        if packed_experts:
+            model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)
     return model

@@ -676,39 +676,43 @@ def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tens
 
 # ---- A16 runtime: W4A16 / W8A16 weights dequantised on chip -------------------------------------------------------
 def _wq_weight(Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor], g_idx: Optional[torch.Tensor],
-               K: Optional[int]):
-    """Checks one weight description of ``qt_dequantize_weight`` / ``qt_gemm_wq_skinny``; returns (format, N, K, G)."""
-    if not Wq.is_cuda or Wq.dim() != 2 or not Wq.is_contiguous():
-        raise ValueError("Wq must be a contiguous 2-d device tensor")
-    N = Wq.shape[0]
+               K: Optional[int], experts: bool = False):
+    """Checks one weight description of ``qt_dequantize_weight`` / ``qt_gemm_wq_skinny`` -- or, with ``experts``, E of
+    them stacked along a leading dimension (``qt_gemm_wq_grouped``); returns (format, N, K, G)."""
+    nd = 3 if experts else 2
+    if not Wq.is_cuda or Wq.dim() != nd or not Wq.is_contiguous():
+        raise ValueError(f"Wq must be a contiguous {nd}-d device tensor")
+    L = [int(Wq.shape[0])] if experts else []
+    E = "E, " if experts else ""
+    N = Wq.shape[-2]
     if Wq.dtype == torch.int8:
         fmt = _lib.QT_W_INT8
-        if K is not None and K != Wq.shape[1]:
-            raise ValueError(f"int8 Wq must be [N, K = {K}], got {tuple(Wq.shape)}")
-        K = Wq.shape[1]
+        if K is not None and K != Wq.shape[-1]:
+            raise ValueError(f"int8 Wq must be [{E}N, K = {K}], got {tuple(Wq.shape)}")
+        K = Wq.shape[-1]
     elif Wq.dtype == torch.int32:
         fmt = _lib.QT_W_INT4_PACKED
         if K is None:
             raise ValueError("packed int4 Wq needs K")
-        if Wq.shape[1] != (K + 7) // 8:
-            raise ValueError(f"packed int4 Wq must be [N, ceil(K/8) = {(K + 7) // 8}], got {tuple(Wq.shape)}")
+        if Wq.shape[-1] != (K + 7) // 8:
+            raise ValueError(f"packed int4 Wq must be [{E}N, ceil(K/8) = {(K + 7) // 8}], got {tuple(Wq.shape)}")
     else:
-        raise TypeError(f"Wq must be int8 [N, K] or packed int4 int32 [N, ceil(K/8)], got {Wq.dtype}")
+        raise TypeError(f"Wq must be int8 [{E}N, K] or packed int4 int32 [{E}N, ceil(K/8)], got {Wq.dtype}")
     K = int(K)
-    if N == 0 or K <= 0:
-        raise ValueError(f"empty weight: N={N}, K={K}")
-    _req(s_w, torch.float32, "s_w", 2)
-    G = s_w.shape[1]
-    if s_w.shape[0] != N or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
-        raise ValueError(f"s_w must be contiguous fp32 [{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
+    if N == 0 or K <= 0 or 0 in L:
+        raise ValueError(f"empty weight: {tuple(Wq.shape)}, K={K}")
+    _req(s_w, torch.float32, "s_w", 2 + len(L))
+    G = s_w.shape[-1]
+    if list(s_w.shape[:-1]) != L + [N] or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
+        raise ValueError(f"s_w must be contiguous fp32 [{E}{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
     if zp_w is not None:
-        _req(zp_w, torch.int8, "zp_w", 2)
-        if tuple(zp_w.shape) != (N, G) or not zp_w.is_contiguous():
-            raise ValueError(f"zp_w must be contiguous int8 [{N}, {G}], got {tuple(zp_w.shape)}")
+        _req(zp_w, torch.int8, "zp_w", 2 + len(L))
+        if list(zp_w.shape) != L + [N, G] or not zp_w.is_contiguous():
+            raise ValueError(f"zp_w must be contiguous int8 [{E}{N}, {G}], got {tuple(zp_w.shape)}")
     if g_idx is not None:
-        _req(g_idx, torch.int32, "g_idx", 1)
-        if g_idx.numel() != K or not g_idx.is_contiguous():
-            raise ValueError(f"g_idx must be contiguous int32 [{K}]")
+        _req(g_idx, torch.int32, "g_idx", 1 + len(L))
+        if list(g_idx.shape) != L + [K] or not g_idx.is_contiguous():
+            raise ValueError(f"g_idx must be contiguous int32 [{E}{K}]")
     for t, name in ((s_w, "s_w"), (zp_w, "zp_w"), (g_idx, "g_idx")):
         if t is not None and t.device != Wq.device:
             raise ValueError(f"{name} is on {t.device}, Wq on {Wq.device}")
@@ -763,6 +767,46 @@ def gemm_wq_skinny(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w
     check("qt_gemm_wq_skinny", lib.qt_gemm_wq_skinny(
         X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx),
         _ptr(bias), Y.data_ptr(), Y.stride(0), _stream()))
+    return Y
+
+
+def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
+                    row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                    zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``qt_gemm_wq_skinny`` over E weight matrices: Y [R, N] in X's dtype, expert e owning rows
+    [offsets[e], offsets[e+1]) (include/quantool_amd.h qt_gemm_wq_grouped).  Wq int8 [E, N, K] or packed int4 int32
+    [E, N, ceil(K/8)] (then ``K`` is required); s_w fp32 [E, N, G]; zp_w int8 [E, N, G]; g_idx int32 [E, K].  X rows:
+    X[row_idx[m]] when ``row_idx`` (int32 [R], e.g. ``moe_route``'s src_token) is given, else X[m] with R = X's rows.
+    Every row equals ``gemm_wq_skinny`` of that expert on that row, to the bit; rows past offsets[E] are left
+    unwritten."""
+    lib = load()
+    code = _act16(X, "X")
+    if X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
+                         f"strides {X.stride()}")
+    Mx, Kx = X.shape
+    if K is not None and K != Kx:
+        raise ValueError(f"K={K} but X has {Kx} columns")
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, Kx, experts=True)
+    E = Wq.shape[0]
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    _req(offsets, torch.int32, "offsets", 1)
+    if offsets.numel() != E + 1 or not offsets.is_contiguous() or offsets.device != X.device:
+        raise ValueError(f"offsets must be contiguous int32 [E + 1 = {E + 1}] on {X.device}")
+    if row_idx is not None:
+        _req(row_idx, torch.int32, "row_idx", 1)
+        if not row_idx.is_contiguous() or row_idx.device != X.device:
+            raise ValueError(f"row_idx must be contiguous int32 [R] on {X.device}")
+        R = row_idx.numel()
+    else:
+        R = Mx
+    if R == 0 or Mx == 0:
+        raise ValueError(f"empty GEMV: R={R}, X rows={Mx}")
+    Y = torch.empty((R, N), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_grouped", lib.qt_gemm_wq_grouped(
+        X.data_ptr(), code, K, X.stride(0), _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N,
+        s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx), Y.data_ptr(), Y.stride(0), _stream()))
     return Y
 
 

@@ -1,6 +1,7 @@
 """Batch-1 greedy decoding of a W4A16 g128 checkpoint, loaded dequantised and packed.
 
   python tools/decode_bench.py <checkpoint dir> [--layers 32] [--prompt 128] [--new 128] [--modes dequantized,packed]
+  python tools/decode_bench.py <checkpoint dir> --model mixtral --layers 8 [--modes dequantized,packed,packed_experts]
 
 Writes (once: an existing checkpoint in the directory is reused) a W4A16 g128 checkpoint of a random-init
 Llama-3-8B-shaped model: round-to-nearest levels of every decoder Linear, scale = absmax / 7.5 per group of 128 columns
@@ -9,6 +10,12 @@ KV-cached greedy decode of --new tokens after a --prompt-token prompt.  Prints o
 token (the decode steps after the prompt, wall time with the device synchronised), the resident bytes of the decoder
 Linears, ``memory_allocated`` after loading and ``max_memory_allocated`` during the decode; and how many generated tokens
 agree between the modes (and the first position where they differ).
+
+``--model mixtral``: a Mixtral-8x7B-shaped model instead (8 experts, top-2, H = 4096, I = 14336; ``--layers 8`` keeps
+the write and the three loads short).  Every expert's gate / up / down and the attention Linears are quantised the same
+way and written per expert through ``expert_bank_checkpoint_names`` (``block_sparse_moe.experts.{e}.w1 / w3 / w2``).
+Modes ``dequantized``, ``packed`` (``a16="packed"``: the banks stay dense bf16) and ``packed_experts`` (``a16="packed",
+a16_experts="packed"``: ``WeightOnlyExperts``); each mode also reports the resident bytes of the expert banks.
 """
 from __future__ import annotations
 
@@ -22,12 +29,60 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from quantool_amd.engine.qlinear import A16_MODES, WeightOnlyLinear, load_quantized, pack_int4  # noqa: E402
+from quantool_amd.engine.qlinear import (A16_MODES, WeightOnlyExperts, WeightOnlyLinear, load_quantized,  # noqa: E402
+                                         pack_int4)
 from quantool_amd.engine.schemes import PRESET_SCHEMES  # noqa: E402
 from quantool_amd.engine.serialization import quantization_config, save_state  # noqa: E402
 
 LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj",
            "mlp.up_proj", "mlp.down_proj")
+
+
+def _rtn(W: torch.Tensor):
+    """Round-to-nearest int4 g128 of W [N, K]: (packed int32 [N, K/8], bf16 scales [N, K/128]) on the CPU."""
+    W = W.float()
+    N, K = W.shape
+    s = (W.reshape(N, K // 128, 128).abs().amax(-1) / 7.5).clamp(min=1e-8).to(torch.bfloat16)
+    q = torch.round(W.reshape(N, K // 128, 128) / s.float()[..., None]).clamp(-8, 7).reshape(N, K).to(torch.int8)
+    return pack_int4(q).cpu(), s.cpu()
+
+
+def write_mixtral_checkpoint(path: Path, layers: int, dev) -> None:
+    from transformers import MixtralConfig, MixtralForCausalLM
+
+    from quantool_amd.engine.sequential import expert_bank_checkpoint_names
+
+    cfg = MixtralConfig(hidden_size=4096, intermediate_size=14336, num_hidden_layers=layers, num_attention_heads=32,
+                        num_key_value_heads=8, num_local_experts=8, num_experts_per_tok=2, vocab_size=32000,
+                        max_position_embeddings=8192, rope_theta=1e6, tie_word_embeddings=False)
+    torch.manual_seed(0)
+    with dev:
+        model = MixtralForCausalLM(cfg).to(torch.bfloat16)
+    attn = {f"model.layers.{i}.{l}" for i in range(layers) for l in LINEARS[:4]}
+    banks = {f"model.layers.{i}.mlp.experts": None for i in range(layers)}
+    state = {}
+    for k, v in model.state_dict().items():
+        mod, _, leaf = k.rpartition(".")
+        if mod in banks:                                   # the fused bank, per expert as the save path holds it
+            proj = leaf
+            for e in range(v.shape[0]):
+                packed, s = _rtn(v[e])
+                pre = f"{mod}.experts.{e}.{proj}"
+                state[f"{pre}.weight_packed"], state[f"{pre}.weight_scale"] = packed, s
+                state[f"{pre}.weight_shape"] = torch.tensor(list(v[e].shape))
+        elif mod in attn:
+            packed, s = _rtn(v)
+            state[f"{mod}.weight_packed"], state[f"{mod}.weight_scale"] = packed, s
+            state[f"{mod}.weight_shape"] = torch.tensor(list(v.shape))
+        else:
+            state[k] = v.cpu()
+    state = expert_bank_checkpoint_names(state, banks, "mixtral")
+    wa = PRESET_SCHEMES["W4A16"]
+    ignore = ["lm_head"] + [f"model.layers.{i}.block_sparse_moe.gate" for i in range(layers)]
+    qcfg = quantization_config(wa.weights.to_config(), wa.format, ignore, None)
+    save_state(state, qcfg, path, model.config.to_dict())
+    del model, state
+    torch.cuda.empty_cache()
 
 
 def write_checkpoint(path: Path, layers: int, dev) -> None:
@@ -46,13 +101,8 @@ def write_checkpoint(path: Path, layers: int, dev) -> None:
         if mod not in quantized:
             state[k] = v.cpu()
             continue
-        W = v.float()
-        N, K = W.shape
-        s = (W.reshape(N, K // 128, 128).abs().amax(-1) / 7.5).clamp(min=1e-8).to(torch.bfloat16)
-        q = torch.round(W.reshape(N, K // 128, 128) / s.float()[..., None]).clamp(-8, 7).reshape(N, K).to(torch.int8)
-        state[f"{mod}.weight_packed"] = pack_int4(q).cpu()
-        state[f"{mod}.weight_scale"] = s.cpu()
-        state[f"{mod}.weight_shape"] = torch.tensor([N, K])
+        state[f"{mod}.weight_packed"], state[f"{mod}.weight_scale"] = _rtn(v)
+        state[f"{mod}.weight_shape"] = torch.tensor(list(v.shape))
     wa = PRESET_SCHEMES["W4A16"]
     qcfg = quantization_config(wa.weights.to_config(), wa.format, ["lm_head"], None)
     save_state(state, qcfg, path, model.config.to_dict())
@@ -85,25 +135,38 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
-    ap.add_argument("--modes", default=",".join(A16_MODES))
+    ap.add_argument("--model", default="llama", choices=["llama", "mixtral"])
+    ap.add_argument("--modes", default=None,
+                    help="default: dequantized,packed (llama) / dequantized,packed,packed_experts (mixtral)")
     args = ap.parse_args()
+    mixtral = args.model == "mixtral"
+    modes = (args.modes or ",".join(A16_MODES + (("packed_experts",) if mixtral else ()))).split(",")
+    vocab = 32000 if mixtral else 128256
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs a GPU")
     dev = torch.device("cuda:0")
     path = Path(args.checkpoint)
     if not (path / "config.json").exists():
         path.mkdir(parents=True, exist_ok=True)
-        write_checkpoint(path, args.layers, dev)
-    prompt = torch.randint(0, 128256, (1, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
-    result = {"tool": "decode_bench", "checkpoint": str(path), "prompt": args.prompt, "new": args.new, "modes": {}}
+        (write_mixtral_checkpoint if mixtral else write_checkpoint)(path, args.layers, dev)
+    prompt = torch.randint(0, vocab, (1, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
+    result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
+              "new": args.new, "modes": {}}
     tokens = {}
-    for mode in args.modes.split(","):
+    for mode in modes:
         torch.cuda.empty_cache()
-        model = load_quantized(path, device=dev, a16=mode)
-        lin_bytes = 0
+        if mode == "packed_experts":
+            model = load_quantized(path, device=dev, a16="packed", a16_experts="packed")
+        else:
+            model = load_quantized(path, device=dev, a16=mode)
+        lin_bytes = bank_bytes = 0
         for n, m in model.named_modules():
-            if n.rpartition(".")[2] in {l.rpartition(".")[2] for l in LINEARS} and ".layers." in n:
-                lin_bytes += sum(t.numel() * t.element_size() for t in list(m.parameters()) + list(m.buffers()))
+            own = sum(t.numel() * t.element_size() for t in list(m.parameters(recurse=False)) +
+                      list(m.buffers(recurse=False)))
+            if n.endswith(".mlp.experts"):
+                bank_bytes += own
+            elif n.rpartition(".")[2] in {l.rpartition(".")[2] for l in LINEARS} and ".layers." in n:
+                lin_bytes += own
         torch.cuda.synchronize()
         resident = torch.cuda.memory_allocated()
         decode(model, prompt[:, :8], 4)                          # warm-up: kernels, allocator
@@ -111,11 +174,13 @@ def main():
         toks, per_tok = decode(model, prompt, args.new)
         result["modes"][mode] = {
             "ms_per_token": round(per_tok * 1e3, 3), "decoder_linear_bytes": lin_bytes,
+            "expert_bank_bytes": bank_bytes,
+            "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
             "memory_allocated_after_load": resident, "max_memory_allocated_decode": torch.cuda.max_memory_allocated(),
             "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules())}
         tokens[mode] = toks
         del model
-    if len(tokens) == 2:
+    if not mixtral and len(tokens) == 2:
         a, b = tokens.values()
         same = [x == y for x, y in zip(a, b)]
         result["tokens_agree"] = sum(same)
@@ -123,6 +188,15 @@ def main():
         d, p = (result["modes"][m] for m in A16_MODES)
         result["linear_bytes_ratio"] = round(p["decoder_linear_bytes"] / d["decoder_linear_bytes"], 4)
         result["speedup"] = round(d["ms_per_token"] / p["ms_per_token"], 3)
+    if mixtral and "dequantized" in tokens:
+        d = result["modes"]["dequantized"]
+        for mode in (m for m in tokens if m != "dequantized"):
+            same = [x == y for x, y in zip(tokens["dequantized"], tokens[mode])]
+            r = result["modes"][mode]
+            r["tokens_agree_with_dequantized"] = sum(same)
+            r["first_difference"] = same.index(False) if not all(same) else None
+            r["speedup_over_dequantized"] = round(d["ms_per_token"] / r["ms_per_token"], 3)
+            r["expert_bytes_ratio"] = round(r["expert_bank_bytes"] / d["expert_bank_bytes"], 4)
     print(json.dumps(result))
 
 

@@ -1,12 +1,13 @@
 """Perplexity of a saved checkpoint (any scheme this backend writes) on stored token ids.
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
-                                  [--a16 dequantized|packed]
+                                  [--a16 dequantized|packed] [--a16-experts dequantized|packed]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
-on ``WeightOnlyLinear``s that keep the integer weights).  Prints one JSON line: perplexity, mean NLL, predicted tokens,
-the module counts, load and evaluation wall times.
+on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed`` with it: routed-expert banks on
+``WeightOnlyExperts``).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
+evaluation wall times.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from quantool_amd.engine.qlinear import A16_MODES, QuantizedLinear, WeightOnlyLinear, load_quantized  # noqa: E402
+from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, WeightOnlyExperts, WeightOnlyLinear,  # noqa: E402
+                                         load_quantized)
 from quantool_amd.evaluate import perplexity  # noqa: E402
 
 
@@ -32,11 +34,13 @@ def main():
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--dtype", default=None, choices=[None, "bfloat16", "float16"])
     ap.add_argument("--a16", default="dequantized", choices=list(A16_MODES))
+    ap.add_argument("--a16-experts", default="dequantized", choices=list(A16_MODES))
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
     model = load_quantized(args.checkpoint, device=args.device,
-                           dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16)
+                           dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
+                           a16_experts=args.a16_experts)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -47,6 +51,7 @@ def main():
     r.update({"checkpoint": str(args.checkpoint), "format": model._qt_checkpoint["format"],
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()),
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
+              "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
               "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
     print(json.dumps(r))
 

@@ -1,6 +1,7 @@
-"""Routed-expert A8 path vs separate per-expert GEMMs vs transformers' bf16 loop at Mixtral-8x7B's shapes.
+"""Routed-expert A8 / A16 paths vs separate per-expert launches vs transformers' bf16 loop at Mixtral-8x7B's shapes.
 
   python tools/moe_bench.py [--tokens 2048,8192] [--schemes W4A8,W8A8] [--reps 10] [--warmup 3]
+  python tools/moe_bench.py --schemes W4A16,W4A16_ASYM,W8A16 --tokens 1,2,4,8,16,32,64,2048
 
 One MoE layer (8 experts, top-2 with random routing, H = 4096, I = 14336).  Per scheme (W8A8 = int8 channel-wise
 weights, symmetric activations; W4A8 = packed int4 g128 weights, asymmetric activations) and token count T: device
@@ -14,7 +15,19 @@ time (HIP events, mean over --reps after --warmup) of
   experts      QuantizedExperts.forward end to end (route, both quantise passes, act_fn(gate) * up, GEMMs, combine)
   hf_bf16      transformers' MixtralExperts.forward in bf16
 
-and grouped / separate (the GEMM pair; <= 1.1 is the issue's bar).  Prints one JSON line.
+and grouped / separate (the GEMM pair; <= 1.1 is the issue's bar).
+
+A16 schemes (W4A16 = packed int4 g128, W4A16_ASYM = the same with int8 zero-points, W8A16 = int8 channel-wise; the
+weights of a ``WeightOnlyExperts``), every time from cold weights (each call reads the next of several copies of the bank,
+> 1.4 GB apart, so the hit experts are not in the 256 MB MALL):
+
+  gate_up, down  qt_gemm_wq_grouped (rows gathered by token / contiguous); grouped = the pair
+  separate       the same pair as one qt_gemm_wq_skinny launch per 16 rows of each hit expert (rows pre-gathered)
+  experts        WeightOnlyExperts.forward end to end (the grouped pair up to grouped_max_tokens, else dequantise)
+  dequant        WeightOnlyExperts.forward on the dequantise path (both banks dequantised, then the bf16 loop)
+  hf_bf16        transformers' MixtralExperts.forward in bf16
+
+with grouped_tbs = bytes of the hit experts' weights, scales and zero-points / grouped time.  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -62,6 +75,106 @@ def _experts(scheme, dev, g):
     return QuantizedExperts(H, I, q_gu, s_gu, q_dn, s_dn, ACT2FN["silu"], act_symmetric=not int4)
 
 
+A16 = ("W4A16", "W4A16_ASYM", "W8A16")
+
+
+def _time_i(fn, reps, warmup):
+    """Mean device time of fn(i), i = the call's index (cold-weight rotation)."""
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(reps):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def _wo_experts(scheme, bank, dev, g):
+    """A WeightOnlyExperts with random levels in ``scheme``'s format (``bank`` gives its shape and act_fn)."""
+    from quantool_amd.engine.qlinear import WeightOnlyExperts
+
+    int4 = scheme != "W8A16"
+    parts = []
+    for N, K in ((2 * I, H), (H, I)):
+        if int4:
+            w = torch.randint(-2 ** 31, 2 ** 31 - 1, (E, N, K // 8), device=dev, generator=g, dtype=torch.int32)
+        else:
+            w = torch.randint(-128, 128, (E, N, K), device=dev, generator=g, dtype=torch.int8)
+        G = K // 128 if int4 else 1
+        s = torch.rand(E, N, G, device=dev, generator=g) * (1e-2 if int4 else 1e-3)
+        zp = torch.randint(-8, 8, (E, N, G), device=dev, generator=g, dtype=torch.int8) if scheme == "W4A16_ASYM" \
+            else None
+        parts.append((w, s, zp))
+    (gw, gs, gz), (dw, ds, dz) = parts
+    return WeightOnlyExperts(bank, gw, gs, dw, ds, gate_up_zero_point=gz, down_zero_point=dz)
+
+
+def _bench_a16(scheme, T, x, idx, w, banks, hf, args):
+    """One A16 row: the grouped pair, the separate launches, the module's two paths and the bf16 loop, cold."""
+    n = len(banks)
+    woe = banks[0]
+    offsets, src_token, _, row_of = ops.moe_route(idx, E)
+    off = offsets.cpu().tolist()
+    src = src_token.long()
+    gu = ops.gemm_wq_grouped(x, woe.gate_up, woe.gate_up_scale, offsets, row_idx=src_token, K=H,
+                             zp_w=woe.gate_up_zero_point)
+    gate, up = gu.chunk(2, dim=-1)
+    h = woe.act_fn(gate) * up
+    chunks = []                                     # (expert, gathered x rows, h rows), <= 16 rows each
+    for e in range(E):
+        for lo in range(off[e], off[e + 1], 16):
+            hi = min(lo + 16, off[e + 1])
+            chunks.append((e, x[src[lo:hi]].contiguous(), h[lo:hi]))
+
+    def grouped(i):
+        b = banks[i % n]
+        ops.gemm_wq_grouped(x, b.gate_up, b.gate_up_scale, offsets, row_idx=src_token, K=H,
+                            zp_w=b.gate_up_zero_point)
+        ops.gemm_wq_grouped(h, b.down, b.down_scale, offsets, K=I, zp_w=b.down_zero_point)
+
+    def separate(i):
+        b = banks[i % n]
+        zg, zd = b.gate_up_zero_point, b.down_zero_point
+        for e, a, hr in chunks:
+            ops.gemm_wq_skinny(a, b.gate_up[e], b.gate_up_scale[e], zp_w=None if zg is None else zg[e])
+            ops.gemm_wq_skinny(hr, b.down[e], b.down_scale[e], zp_w=None if zd is None else zd[e])
+
+    def dequant(i):
+        b = banks[i % n]
+        keep, b.grouped_max_tokens = b.grouped_max_tokens, 0
+        b(x, idx, w)
+        b.grouped_max_tokens = keep
+
+    reps, warm = args.reps, args.warmup
+    with torch.no_grad():
+        t = {"gate_up": _time_i(lambda i: ops.gemm_wq_grouped(x, banks[i % n].gate_up, banks[i % n].gate_up_scale,
+                                                              offsets, row_idx=src_token, K=H,
+                                                              zp_w=banks[i % n].gate_up_zero_point), reps, warm),
+             "down": _time_i(lambda i: ops.gemm_wq_grouped(h, banks[i % n].down, banks[i % n].down_scale, offsets,
+                                                           K=I, zp_w=banks[i % n].down_zero_point), reps, warm),
+             "grouped": _time_i(grouped, reps, warm),
+             "separate": _time_i(separate, reps, warm),
+             "experts": _time_i(lambda i: banks[i % n](x, idx, w), reps, warm),
+             "dequant": _time_i(dequant, max(2, reps // 4), 1),
+             "hf_bf16": _time(lambda: hf(x, idx, w), reps, warm)}
+    hit = [e for e in range(E) if off[e + 1] > off[e]]
+    per_expert = sum(getattr(woe, f"{p}{s}")[0].numel() * getattr(woe, f"{p}{s}").element_size()
+                     for p in ("gate_up", "down") for s in ("", "_scale", "_zero_point")
+                     if getattr(woe, f"{p}{s}") is not None)
+    nbytes = per_expert * len(hit)
+    return {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
+            "cold_copies": n, "ms": {k: round(v, 4) for k, v in t.items()},
+            "hit_expert_bytes": nbytes, "grouped_tbs": round(nbytes / (t["grouped"] * 1e-3) / 1e12, 3),
+            "gate_up_tbs": round(nbytes * 2 / 3 / (t["gate_up"] * 1e-3) / 1e12, 3),
+            "down_tbs": round(nbytes / 3 / (t["down"] * 1e-3) / 1e12, 3),
+            "grouped_over_separate": round(t["grouped"] / t["separate"], 3),
+            "hf_bf16_over_experts": round(t["hf_bf16"] / t["experts"], 3),
+            "dequant_over_experts": round(t["dequant"] / t["experts"], 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
@@ -84,6 +197,24 @@ def main():
         hf.gate_up_proj.normal_(0, 0.02, generator=g)
         hf.down_proj.normal_(0, 0.02, generator=g)
     for scheme in args.schemes.split(","):
+        if scheme in A16:
+            # copies of the bank > 1.4 GB in all, rotated per call (the int4 bank is 0.7 GB, the int8 one 1.4 GB)
+            n = 3 if scheme != "W8A16" else 2
+            with torch.device("meta"):          # the bank's shape and act_fn only: no dense weights anywhere
+                shells = [MixtralExperts(hf.config) for _ in range(n)]
+            banks = [_wo_experts(scheme, b, dev, g) for b in shells]
+            for T in (int(t) for t in args.tokens.split(",")):
+                x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+                logits = torch.randn(T, E, device=dev, generator=g)
+                w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+                w = (w / w.sum(-1, keepdim=True)).to(torch.bfloat16)
+                row = _bench_a16(scheme, T, x, idx, w, banks, hf, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del banks
+            torch.cuda.empty_cache()
+            continue
         qe = _experts(scheme, dev, g)
         sym = qe.act_symmetric
         for T in (int(t) for t in args.tokens.split(",")):
@@ -144,7 +275,7 @@ def main():
             torch.cuda.empty_cache()
         del qe
         torch.cuda.empty_cache()
-    print(json.dumps({"metric": "Mixtral-8x7B MoE layer: grouped int8 expert GEMM vs E launches vs bf16 loop",
+    print(json.dumps({"metric": "Mixtral-8x7B MoE layer: grouped expert GEMM / GEMV vs E launches vs bf16 loop",
                       "E": E, "top_k": TOPK, "H": H, "I": I, "rows": rows}))
 
 
