@@ -375,3 +375,7 @@ def test_end_to_end_on_tiny_mixtral(dev, tmp_path, monkeypatch, method, level):
         assert abs(ppl - ppl_mem) / ppl_mem < 1e-2, (ppl, ppl_mem)
     else:
         assert ppl != ppl_mem, ppl
+    from tests.test_gpu_ckpt_e2e import check_modules_against_files
+
+    # every quantized Linear and expert bank against what the checkpoint files define (fp64, no shared decoding)
+    assert check_modules_against_files(loaded, tmp_path / "ckpt", dev, tokens=(1, 17)) > 0

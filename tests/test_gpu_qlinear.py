@@ -282,3 +282,7 @@ def test_end_to_end_on_tiny_llama(dev, tmp_path, monkeypatch, method, level):
     # a path goes through load_quantized
     assert perplexity(str(tmp_path / "ckpt"), ids, batch_size=4, device=dev)["perplexity"] == pytest.approx(ppl,
                                                                                                             rel=1e-9)
+    # every quantized module against what the checkpoint files define (an fp64 reference that shares no decoding)
+    from tests.test_gpu_ckpt_e2e import check_modules_against_files
+
+    assert check_modules_against_files(model, tmp_path / "ckpt", dev, tokens=(1, 17)) == 2 * 14

@@ -367,3 +367,8 @@ def test_end_to_end_packed_experts(dev, tmp_path, monkeypatch, source):
     diff = (got - ref).abs().max().item()
     scale = ref.abs().max().item()
     assert diff <= 2.0 ** -4 * scale, (diff, scale)
+    # every Linear and packed expert bank against what the checkpoint files define (fp64, no shared decoding): the
+    # grouped GEMV and the dequantise paths
+    from tests.test_gpu_ckpt_e2e import check_modules_against_files
+
+    assert check_modules_against_files(packed, ckpt, dev, tokens=(1, 129, 200)) > 0
