@@ -14,6 +14,7 @@ from typing import Iterable, List, Optional, Sequence
 import torch
 
 from ..hip import ops
+from .gptq_linear import _on_device
 from .schemes import QuantArgs
 
 
@@ -39,6 +40,8 @@ class AWQResult:
         if self.Qt is None:
             raise RuntimeError("the integer levels of this result were released (sequential driver, "
                                "QT_RESULT_DETAIL_BYTES): the module's weight holds the dequantised values")
+        if self.Qt.device.type == "cpu":       # a streamed run keeps its results on the host
+            return ops.dequantize(*_on_device(self.Qt, self.scale_f32, self.zp_f32, self.g_of_col, None), dtype).cpu()
         return ops.dequantize(self.Qt, self.scale_f32, self.zp_f32, self.g_of_col, None, dtype)
 
 

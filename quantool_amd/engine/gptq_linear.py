@@ -139,6 +139,12 @@ def _launch_token_limit() -> int:
         return 0
 
 
+def _on_device(*tensors):
+    """Host tensors (a streamed run's results) on the current device for a HIP kernel; None stays None."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return tuple(None if t is None else t.to(dev) for t in tensors)
+
+
 @dataclass
 class GPTQResult:
     """Outputs for one Linear, named as the compressed-tensors state_dict names them (a14)."""
@@ -161,6 +167,8 @@ class GPTQResult:
         if self.Qt is None:
             raise RuntimeError("the integer levels of this result were released (sequential driver, "
                                "QT_RESULT_DETAIL_BYTES): the module's weight holds the dequantised values")
+        if self.Qt.device.type == "cpu":       # a streamed run keeps its results on the host
+            return ops.dequantize(*_on_device(self.Qt, self.scale_f32, self.zp_f32, self.g_of_col, self.col_src), dtype).cpu()
         return ops.dequantize(self.Qt, self.scale_f32, self.zp_f32, self.g_of_col, self.col_src, dtype)
 
 

@@ -72,3 +72,12 @@ def scaled(shape: LayerShape, divisor: int) -> LayerShape:
 
     return LayerShape(f"{shape.name}/{divisor}", shape.n_layers,
                       tuple((g, dim(K), tuple((n, dim(R)) for n, R in lins)) for g, K, lins in shape.groups))
+
+
+#: Models larger than one MI355X's HBM (public configs), for the placement decision (``sequential.should_stream``):
+#: Mixtral-8x22B (hidden 6144, intermediate 16384, 48 heads / 8 KV heads, 56 layers, 8 experts) and Llama-3.1-405B
+#: (hidden 16384, intermediate 53248, 128 heads / 8 KV heads, 126 layers).  Not ``bench.py`` workloads.
+LARGE_MODEL_SHAPES: Dict[str, LayerShape] = {
+    "mixtral-8x22b": _mixtral("mixtral-8x22b", 6144, 16384, 1024, 56, 8),
+    "llama-3.1-405b": _llama("llama-3.1-405b", 16384, 53248, 1024, 126),
+}

@@ -396,43 +396,79 @@ def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int,
             raise ValueError(f"{len(batches)} calibration samples cannot be split over {world} ranks")
         batches = batches[rank::world]
     model.eval()
-    model.to(dev)
+    targets = sequential_targets or getattr(qm, "sequential_targets", None)
+    stream = _streams_layers(model, find_decoder_layers(model, targets), qm, batches, dev)
+    if stream and world > 1:
+        raise ValueError(f"the model does not fit on one device and would be streamed from the host, which needs one "
+                         f"host copy of it per rank: run it with one process (world size {world} here)")
+    if not stream:
+        model.to(dev)
     n_banks = unfuse_expert_banks(model)
     if n_banks:
         logger.info(f"unfused {n_banks} sparse-MoE expert bank(s) into per-expert Linears")
-    layers = find_decoder_layers(model, sequential_targets or getattr(qm, "sequential_targets", None))
+    layers = find_decoder_layers(model, targets)
     qargs = qm.weight_args()
-    ph = _Phases(dev)
+    ph = _Phases(dev, stream_only=stream)
     ph.start()
-    cache = _first_layer_inputs(model, layers, batches, dev)
+    if stream:
+        from .placement import outside_layers_on_device
+
+        with outside_layers_on_device(model, layers, dev):
+            cache = _first_layer_inputs(model, layers, batches, dev)
+    else:
+        cache = _first_layer_inputs(model, layers, batches, dev)
     ph.stop("first-layer inputs")
     prefix_of = {id(m): n for n, m in model.named_modules()}
     results: Dict[str, Any] = _ResultStore()
-    with torch.no_grad():
-        for li, layer in enumerate(layers):
-            lname, last = prefix_of[id(layer)], li + 1 == len(layers)
-            if aw is not None:
-                from .awq_module import awq_layer
 
-                results.update(awq_layer(layer, lname, cache, aw, dev))
-                if not last:
-                    cache = _advance(layer, cache)
-                continue
-            linears = _targeted_linears(layer, lname, gp)
-            if sq is not None:
-                _smooth_layer(layer, cache, sq.smoothing_strength, dev, sq.mappings, lname)
-            ph.start()
-            leaders, accs = _calibrate_layer(layer, linears, cache, world, dev)
-            ph.stop("calibration forwards + Gram")
-            ph.start()
-            _quantize_layer(linears, leaders, accs, gp, qargs, world, results, dev)
-            del accs
-            ph.stop("factorise + sweep + pack")
-            ph.start()
-            if not last:       # nobody reads the last layer's outputs: no propagate pass behind it
-                cache = _advance(layer, cache)
-            ph.stop("propagate")
-            logger.info(f"quantized {lname}: {len(linears)} Linears in {len(leaders)} input groups")
+    def quantize(li, between=lambda: None):
+        """Layer ``li``'s smoothing / search, calibration and quantisation; ``between`` runs once its calibration
+        forwards are issued (the streamed driver uploads the next layer there)."""
+        layer = layers[li]
+        lname = prefix_of[id(layer)]
+        if aw is not None:
+            from .awq_module import awq_layer
+
+            between()
+            results.update(awq_layer(layer, lname, cache, aw, dev))
+            return
+        linears = _targeted_linears(layer, lname, gp)
+        if sq is not None:
+            _smooth_layer(layer, cache, sq.smoothing_strength, dev, sq.mappings, lname)
+        ph.start()
+        leaders, accs = _calibrate_layer(layer, linears, cache, world, dev)
+        ph.stop("calibration forwards + Gram")
+        between()
+        ph.start()
+        _quantize_layer(linears, leaders, accs, gp, qargs, world, results, dev)
+        del accs
+        ph.stop("factorise + sweep + pack")
+        logger.info(f"quantized {lname}: {len(linears)} Linears in {len(leaders)} input groups")
+
+    def propagate(li):
+        nonlocal cache
+        ph.start()
+        cache = _advance(layers[li], cache)
+        ph.stop("propagate")
+
+    with torch.no_grad():
+        if stream:
+            from .placement import LayerMover
+
+            mover = LayerMover(layers, dev, ph)
+            try:
+                _stream_layers(len(layers), mover, quantize, propagate, results)
+            except BaseException:
+                mover.abort()
+                raise
+            model._qt_placement = dict(mode="stream", **mover.stats)
+            logger.info(f"streamed {len(layers)} decoder layers: {mover.stats}")
+        else:
+            for li in range(len(layers)):
+                quantize(li)
+                if li + 1 < len(layers):       # nobody reads the last layer's outputs: no propagate pass behind it
+                    propagate(li)
+            model._qt_placement = {"mode": "resident"}
     ph.report()
     model._qt_results = results
     acts = qm.resolved_scheme.input_activations
@@ -440,6 +476,61 @@ def oneshot_module(model, dataset, recipe, dev, *, num_calibration_samples: int,
                       "input_activations": acts.to_config() if acts is not None else None}
     model.save_pretrained = types.MethodType(_save_compressed, model)
     return model
+
+
+def _streams_layers(model: nn.Module, layers: List[nn.Module], qm, batches, dev) -> bool:
+    """``placement.should_stream`` on what the model shows: its decoder layers' place and shapes, its parameter bytes,
+    the scheme, the calibration tokens and the free device memory."""
+    from . import placement
+
+    params = [t for layer in layers for t in layer.parameters()]
+    on_host = bool(params) and all(t.device.type == "cpu" for t in params)
+    if not on_host:
+        return False
+    shape = placement.layer_shape(layers)
+    param_bytes = sum(t.numel() * t.element_size() for t in model.parameters())
+    tokens = sum(int(next(iter(b.values())).numel()) for b in batches)
+    cfg = getattr(model, "config", None)
+    hidden = int(getattr(cfg, "hidden_size", 0) or min(K for _, K, _ in shape.groups))
+    dtype_bytes = params[0].element_size()
+    free = placement.free_device_bytes(dev)
+    stream = placement.should_stream(shape, hidden, param_bytes, qm.weight_args(), tokens, free, on_host=on_host,
+                                     dtype_bytes=dtype_bytes)
+    need = param_bytes + placement.calibration_bytes(shape, hidden, tokens, qm.weight_args(), dtype_bytes=dtype_bytes)
+    logger.info(f"placement: {'streamed from the host' if stream else 'resident'} ({param_bytes / 2**30:.1f} GiB of "
+                f"parameters, {need / 2**30:.1f} GiB estimated resident, {free / 2**30:.1f} GiB free)")
+    return stream
+
+
+def _stream_layers(n: int, mover, quantize, propagate, results: Dict[str, Any]) -> None:
+    """The streamed schedule.  Layer i+1 is staged when layer i starts and uploaded once layer i's calibration forwards
+    are issued (before its quantisation ends); layer i's write-back is queued behind its propagate pass and runs beside
+    layer i+1's calibration; layer i leaves the device before layer i+1 is attached and layer i+2 uploaded, so at most
+    two layers are allocated on the device."""
+    mover.stage(0)
+    mover.upload(0)
+    mover.attach(0)
+    for i in range(n):
+        nxt = i + 1 < n
+        if nxt:
+            mover.stage(i + 1)
+        uploaded = []
+
+        def between():
+            if nxt and not uploaded:
+                mover.upload(i + 1)
+                uploaded.append(True)
+
+        before = set(results)
+        quantize(i, between)
+        between()
+        if nxt:
+            propagate(i)
+        mover.writeback(i, [results[k] for k in results if k not in before])
+        mover.release(i)
+        if nxt:
+            mover.attach(i + 1)
+    mover.finish()
 
 
 def _load_model(path, precision, trust_remote_code: bool, tokenizer):
@@ -667,22 +758,31 @@ def _store(linears, results, names: List[str], res, keep: Optional[dict] = None,
 class _Phases:
     """QT_CALIB_TIMING=1: wall time per phase of the driver (device-synchronised; diagnostics only)."""
 
-    def __init__(self, dev):
+    def __init__(self, dev, stream_only: bool = False):
         self.on = os.environ.get("QT_CALIB_TIMING", "0") not in ("", "0")
         self.dev, self.t, self.acc = dev, 0.0, {}
+        # streamed placement: the copy streams keep running across the phases; only the current stream is waited for,
+        # so "onload" / "write-back" show the copy time left exposed
+        self.stream_only = stream_only
+
+    def _sync(self):
+        if self.stream_only:
+            torch.cuda.current_stream(self.dev).synchronize()
+        else:
+            torch.cuda.synchronize(self.dev)
 
     def start(self):
         if self.on:
             import time
 
-            torch.cuda.synchronize(self.dev)
+            self._sync()
             self.t = time.perf_counter()
 
     def stop(self, name):
         if self.on:
             import time
 
-            torch.cuda.synchronize(self.dev)
+            self._sync()
             self.acc[name] = self.acc.get(name, 0.0) + time.perf_counter() - self.t
 
     def report(self):
