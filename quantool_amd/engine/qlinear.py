@@ -25,6 +25,10 @@ Loading needs no GPU: every load-time step (int4 unpacking, the column permutati
 weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,
 ``QuantizedExperts.forward``, ``WeightOnlyLinear.forward`` and ``WeightOnlyExperts.forward`` on device tensors need
 the HIP library.
+
+The four modules are defined in ``qmodules.py`` and one stored weight as a value (``StoredWeight``: the only reader of a
+module's checkpoint tensors, the kernels' layout rules, ``dequantize``, the stacking of experts into a bank) in
+``stored_weight.py``; both are re-exported here, and this file is the loader.
 """
 from __future__ import annotations
 
@@ -35,321 +39,19 @@ from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
+from .qmodules import QuantizedExperts, QuantizedLinear, WeightOnlyExperts, WeightOnlyLinear
 from .serialization import load_state
+from .stored_weight import GROUP, StoredWeight, group_sums, pack_int4, unpack_int4  # noqa: F401 (re-exported)
 
-GROUP = 128   # the W4A8 group size the GEMM takes
 _LEAVES = ("weight", "weight_packed", "weight_scale", "weight_zero_point", "weight_g_idx", "weight_shape")
 # per-expert names expert_bank_checkpoint_names writes (<bank>.experts.{e}.<proj>)
 _EXPERT_RE = re.compile(r"\.experts\.\d+\.")
 # <bank>.{e}.<proj> -- a per-expert module name, split
 _EXPERT_NAME = re.compile(r"^(?P<bank>.+\.experts)\.(?P<e>\d+)\.(?P<proj>[^.]+)$")
+_A16_HINT = "; load it with a16='dequantized'"
 
 
-def unpack_int4(packed: torch.Tensor, K: int) -> torch.Tensor:
-    """int32 [R, ceil(K/8)] (nibble j of word w = level of column 8w + j, plus 8) -> int8 levels [R, K]."""
-    shifts = torch.arange(0, 32, 4, device=packed.device, dtype=torch.int32)
-    nib = (packed.unsqueeze(-1) >> shifts) & 0xF
-    return (nib.reshape(packed.shape[0], -1)[:, :K] - 8).to(torch.int8)
-
-
-def pack_int4(q: torch.Tensor) -> torch.Tensor:
-    """int8 levels [R, K] in [-8, 7] -> int32 [R, ceil(K/8)], the inverse of ``unpack_int4``."""
-    R, K = q.shape
-    Kw = (K + 7) // 8
-    v = torch.full((R, Kw * 8), 8, dtype=torch.int64, device=q.device)
-    v[:, :K] = q.to(torch.int64) + 8
-    shifts = torch.arange(0, 32, 4, device=q.device, dtype=torch.int64)
-    words = (v.reshape(R, Kw, 8) << shifts).sum(-1)
-    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
-
-
-def group_sums(q: torch.Tensor, G: int) -> torch.Tensor:
-    """wsum [R, G] int32: sums of the levels q [R, K] over each group of 128 contiguous columns (G = 1: whole rows)."""
-    R, K = q.shape
-    if G == 1:
-        return q.to(torch.int32).sum(1, dtype=torch.int32).reshape(R, 1).contiguous()
-    pad = G * GROUP - K
-    qp = torch.nn.functional.pad(q.to(torch.int32), (0, pad)) if pad else q.to(torch.int32)
-    return qp.reshape(R, G, GROUP).sum(-1, dtype=torch.int32).contiguous()
-
-
-class QuantizedLinear(nn.Module):
-    """One W8A8 / INT8 / W4A8 Linear of a checkpoint: ``forward(x)`` quantises the rows of ``x`` to int8 (per token,
-    dynamic) and runs the int8 x int8 GEMM with the checkpoint's weight scales.
-
-    Buffers: ``weight`` int8 [N, K] or packed int4 int32 [N, ceil(K/8)] (columns permuted by ``col_perm`` when the
-    checkpoint used actorder ``group``), ``weight_scale`` fp32 [N, G], ``wsum`` int32 [N, G], ``col_perm`` int32 [K]
-    (optional), ``bias`` (optional, model dtype)."""
-
-    def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
-                 act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
-        super().__init__()
-        self.in_features = int(in_features)
-        self.out_features = int(out_features)
-        self.act_symmetric = bool(act_symmetric)
-        self.int4 = weight.dtype == torch.int32
-        levels = unpack_int4(weight, in_features) if self.int4 else weight
-        G = weight_scale.shape[1]
-        self.register_buffer("weight", weight.contiguous())
-        self.register_buffer("weight_scale", weight_scale.to(torch.float32).contiguous())
-        self.register_buffer("wsum", group_sums(levels, G))
-        self.register_buffer("col_perm", None if col_perm is None else col_perm.to(torch.int32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.contiguous())
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"weights={'int4 g128' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
-                f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token, "
-                f"col_perm={self.col_perm is not None}, bias={self.bias is not None}")
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        from ..hip import ops
-
-        lead = x.shape[:-1]
-        x2 = x.reshape(-1, self.in_features)
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()
-        Xq, s_x, zp_x = ops.quantize_tokens_i8(x2, symmetric=self.act_symmetric, col_perm=self.col_perm)
-        bias = None if self.bias is None else self.bias.to(x.dtype)
-        y = ops.gemm_i8(Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
-                        wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
-        return y.reshape(*lead, self.out_features)
-
-
-class WeightOnlyLinear(nn.Module):
-    """One W4A16 / W4A16_ASYM / W8A16 Linear of a checkpoint on its stored integer weights.
-
-    ``forward(x)`` with M = rows of ``x``: M <= ``skinny_max_m`` runs ``qt_gemm_wq_skinny`` (the weights read once,
-    dequantised on chip; fp32 sums in the kernel's own fixed order); otherwise ``qt_dequantize_weight`` fills a transient
-    dense weight -- bit-identical to the default loader's ``nn.Linear.weight`` -- and ``F.linear`` runs on it, so the
-    output equals that ``nn.Linear``'s to the bit.  On CPU tensors ``forward`` is ``F.linear`` on ``dequantized_weight``.
-
-    Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
-    ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
-    (optional, model dtype).  Columns stay in their original order."""
-
-    # Decode GEMV up to this many rows, dequantise + F.linear above: at 16 rows the GEMV is still faster than the
-    # dequantise + F.linear pair on every measured Llama-3-8B shape (DESIGN.md 4.9).
-    skinny_max_m = 16
-
-    def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
-                 weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
-                 bias: Optional[torch.Tensor] = None):
-        super().__init__()
-        self.in_features = int(in_features)
-        self.out_features = int(out_features)
-        self.int4 = weight.dtype == torch.int32
-        self.register_buffer("weight_packed" if self.int4 else "weight", weight.contiguous())
-        self.register_buffer("weight_scale", weight_scale.to(torch.float32).contiguous())
-        self.register_buffer("weight_zero_point", None if weight_zero_point is None
-                             else weight_zero_point.to(torch.int8).contiguous())
-        self.register_buffer("g_idx", None if g_idx is None else g_idx.to(torch.int32).contiguous())
-        self.register_buffer("bias", None if bias is None else bias.contiguous())
-
-    @property
-    def qweight(self) -> torch.Tensor:
-        return self.weight_packed if self.int4 else self.weight
-
-    def checkpoint_tensors(self) -> Dict[str, torch.Tensor]:
-        """The module's weight as the checkpoint leaves ``dequantized_weight`` reads."""
-        t = {"weight_packed" if self.int4 else "weight": self.qweight, "weight_scale": self.weight_scale,
-             "weight_shape": torch.tensor([self.out_features, self.in_features])}
-        if self.weight_zero_point is not None:
-            t["weight_zero_point"] = self.weight_zero_point
-        if self.g_idx is not None:
-            t["weight_g_idx"] = self.g_idx
-        return t
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, out_features={self.out_features}, "
-                f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
-                f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
-                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}")
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        bias = None if self.bias is None else self.bias.to(x.dtype)
-        if not x.is_cuda:
-            return F.linear(x, dequantized_weight("WeightOnlyLinear", self.checkpoint_tensors(), x.dtype), bias)
-        from ..hip import ops
-
-        x2 = x.reshape(-1, self.in_features)
-        M = x2.shape[0]
-        if 1 <= M <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
-            if x2.stride(1) != 1:
-                x2 = x2.contiguous()
-            y = ops.gemm_wq_skinny(x2, self.qweight, self.weight_scale, zp_w=self.weight_zero_point, g_idx=self.g_idx,
-                                   bias=bias)
-            return y.reshape(*x.shape[:-1], self.out_features)
-        W = ops.dequantize_weight(self.qweight, self.weight_scale, K=self.in_features, zp_w=self.weight_zero_point,
-                                  g_idx=self.g_idx, dtype=x.dtype)
-        return F.linear(x, W, bias)
-
-
-class QuantizedExperts(nn.Module):
-    """A W8A8 / INT8 / W4A8 routed-expert bank: ``forward(hidden_states, top_k_index, top_k_weights)`` as
-    transformers' ``MixtralExperts`` with its two ``F.linear`` calls on the int8 GEMM.
-
-    The routed rows are ordered by expert (``qt_moe_route``); the T tokens are quantised once per token and the gate_up
-    GEMM gathers them by token; ``act_fn(gate) * up`` runs in torch as the fused module does; the routed rows are
-    quantised per row and the down GEMM reads them in place; ``qt_moe_combine`` sums each token's weighted rows in
-    ascending expert order, rounding as ``index_add_`` does.  include/quantool_amd.h states every step.
-
-    Buffers: ``gate_up`` int8 [E, 2I, H] or packed int4 int32 [E, 2I, ceil(H/8)] (rows [0, I) gate, [I, 2I) up),
-    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_wsum`` int32 [E, 2I, G]; ``down`` int8 [E, H, I] or int32
-    [E, H, ceil(I/8)], ``down_scale`` fp32 [E, H, G'], ``down_wsum`` int32 [E, H, G']."""
-
-    def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
-                 down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
-        super().__init__()
-        self.num_experts = int(gate_up.shape[0])
-        self.hidden_dim = int(hidden_size)
-        self.intermediate_dim = int(intermediate_size)
-        self.act_fn = act_fn
-        self.act_symmetric = bool(act_symmetric)
-        self.int4 = gate_up.dtype == torch.int32
-        for name, w, s, K in (("gate_up", gate_up, gate_up_scale, self.hidden_dim),
-                              ("down", down, down_scale, self.intermediate_dim)):
-            E, N = w.shape[:2]
-            levels = unpack_int4(w.reshape(E * N, -1), K) if self.int4 else w.reshape(E * N, K)
-            G = s.shape[2]
-            self.register_buffer(name, w.contiguous())
-            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
-            self.register_buffer(f"{name}_wsum", group_sums(levels, G).reshape(E, N, G))
-
-    def extra_repr(self) -> str:
-        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
-                f"weights={'int4 g128' if self.int4 else 'int8'}, "
-                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
-                f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token")
-
-    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
-        from ..hip import ops
-
-        x = hidden_states.reshape(-1, self.hidden_dim)
-        if x.stride(1) != 1:
-            x = x.contiguous()
-        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
-        sym = self.act_symmetric
-        Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=sym)
-        gu = ops.gemm_i8_grouped(Xq, s_x, self.gate_up, self.gate_up_scale, offsets, row_idx=src_token,
-                                 K=self.hidden_dim, zp_x=zp_x, wsum=None if sym else self.gate_up_wsum,
-                                 out_dtype=x.dtype)
-        gate, up = gu.chunk(2, dim=-1)
-        h = self.act_fn(gate) * up
-        Hq, s_h, zp_h = ops.quantize_tokens_i8(h, symmetric=sym)
-        y = ops.gemm_i8_grouped(Hq, s_h, self.down, self.down_scale, offsets, K=self.intermediate_dim, zp_x=zp_h,
-                                wsum=None if sym else self.down_wsum, out_dtype=x.dtype)
-        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
-
-
-class WeightOnlyExperts(nn.Module):
-    """A W4A16 / W4A16_ASYM / W8A16 routed-expert bank on its stored integer weights: ``forward(hidden_states,
-    top_k_index, top_k_weights)`` as the fused transformers bank it replaces.
-
-    With T = rows of ``hidden_states`` (known on the host) and 1 <= T <= ``grouped_max_tokens``: ``qt_moe_route`` orders
-    the routed rows by expert, the gate_up GEMV (``qt_gemm_wq_grouped``) gathers them by token, ``act_fn(gate) * up``
-    runs in torch as the fused module does, the down GEMV reads the routed rows in place and ``qt_moe_combine`` sums
-    each token's weighted rows in ascending expert order.  Only the experts that were hit are read, and nothing waits on
-    the host.  Larger T: both banks are dequantised into transient [E, 2I, H] / [E, H, I] tensors
-    (``qt_dequantize_weight``, bit-identical to the dense bank ``a16_experts="dequantized"`` loads) and the bank's own
-    transformers forward runs on them (honouring ``config._experts_implementation``), so the output equals the dense
-    bank's to the bit.  On CPU tensors ``forward`` is that bank forward on ``dequantized_weight``.
-
-    Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
-    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
-    [E, H] (optional, actorder ``group``); ``down`` int32 [E, H, ceil(I/8)] or int8 [E, H, I] and its ``down_scale``,
-    ``down_zero_point``, ``down_g_idx`` likewise.  Columns stay in the checkpoint's order.
-
-    ``bank`` is the fused module replaced: its ``gate_up_proj`` / ``down_proj`` are swapped for empty stand-ins and it
-    is kept (not as a submodule) for its forward alone."""
-
-    # Grouped GEMV up to this many tokens, dequantise + the bank's forward above.  At Mixtral-8x7B's shapes the GEMV pair
-    # re-reads an expert's weights once per 16 of its rows and still beats the dequantise path (2.7 ms) up to T = 192;
-    # at 128 it takes 1.2 ms (DESIGN.md 4.10).
-    grouped_max_tokens = 128
-
-    def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
-                 down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
-                 gate_up_g_idx: Optional[torch.Tensor] = None, down_zero_point: Optional[torch.Tensor] = None,
-                 down_g_idx: Optional[torch.Tensor] = None):
-        super().__init__()
-        E, I2, H = bank.gate_up_proj.shape
-        self.num_experts, self.hidden_dim, self.intermediate_dim = int(E), int(H), int(I2) // 2
-        self.act_fn = bank.act_fn
-        self.int4 = gate_up.dtype == torch.int32
-        for name, w, s, zp, gi in (("gate_up", gate_up, gate_up_scale, gate_up_zero_point, gate_up_g_idx),
-                                   ("down", down, down_scale, down_zero_point, down_g_idx)):
-            self.register_buffer(name, w.contiguous())
-            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
-            self.register_buffer(f"{name}_zero_point", None if zp is None else zp.to(torch.int8).contiguous())
-            self.register_buffer(f"{name}_g_idx", None if gi is None else gi.to(torch.int32).contiguous())
-        p = bank.gate_up_proj
-        for n in ("gate_up_proj", "down_proj"):
-            setattr(bank, n, nn.Parameter(torch.empty(0, dtype=p.dtype, device=p.device), requires_grad=False))
-        self.__dict__["_bank"] = bank
-
-    def extra_repr(self) -> str:
-        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
-                f"weights={'int4' if self.int4 else 'int8'}, "
-                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
-                f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
-                f"grouped_max_tokens={self.grouped_max_tokens}")
-
-    def _part(self, part: str):
-        return (getattr(self, part), getattr(self, f"{part}_scale"), getattr(self, f"{part}_zero_point"),
-                getattr(self, f"{part}_g_idx"), self.hidden_dim if part == "gate_up" else self.intermediate_dim)
-
-    def dense_weight(self, part: str, dtype: torch.dtype) -> torch.Tensor:
-        """The ``part`` ("gate_up" / "down") bank dequantised, [E, N, K] in ``dtype``: the dense bank's parameter."""
-        w, s, zp, gi, K = self._part(part)
-        E, N = w.shape[:2]
-        if not w.is_cuda:
-            def leaves(e):
-                t = {"weight_packed" if self.int4 else "weight": w[e], "weight_scale": s[e],
-                     "weight_shape": torch.tensor([N, K])}
-                if zp is not None:
-                    t["weight_zero_point"] = zp[e]
-                if gi is not None:
-                    t["weight_g_idx"] = gi[e]
-                return t
-
-            return torch.stack([dequantized_weight(f"{part}[{e}]", leaves(e), dtype) for e in range(E)])
-        from ..hip import ops
-
-        out = torch.empty((E, N, K), dtype=dtype, device=w.device)
-        if gi is None:                      # one call over the stacked [E N, .] rows
-            ops.dequantize_weight(w.view(E * N, -1), s.view(E * N, -1), K=K,
-                                  zp_w=None if zp is None else zp.view(E * N, -1), dtype=dtype, out=out.view(E * N, K))
-        else:
-            for e in range(E):
-                ops.dequantize_weight(w[e], s[e], K=K, zp_w=None if zp is None else zp[e], g_idx=gi[e], dtype=dtype,
-                                      out=out[e])
-        return out
-
-    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
-        x = hidden_states.reshape(-1, self.hidden_dim)
-        T = x.shape[0]
-        if not x.is_cuda or not 1 <= T <= self.grouped_max_tokens:
-            dense = {"gate_up_proj": self.dense_weight("gate_up", hidden_states.dtype),
-                     "down_proj": self.dense_weight("down", hidden_states.dtype)}
-            return torch.func.functional_call(self._bank, dense, (hidden_states, top_k_index, top_k_weights))
-        from ..hip import ops
-
-        if x.stride(1) != 1:
-            x = x.contiguous()
-        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
-        w, s, zp, gi, K = self._part("gate_up")
-        gu = ops.gemm_wq_grouped(x, w, s, offsets, row_idx=src_token, K=K, zp_w=zp, g_idx=gi)
-        gate, up = gu.chunk(2, dim=-1)
-        h = self.act_fn(gate) * up
-        w, s, zp, gi, K = self._part("down")
-        y = ops.gemm_wq_grouped(h, w, s, offsets, K=K, zp_w=zp, g_idx=gi)
-        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
-
-
-# ---- the loader ------------------------------------------------------------------------------------------------------
 def _is_a8(block) -> bool:
     """The 8-bit dynamic per-token integer block W8A8 / INT8 / W4A8 write (schemes.py _A8_TOKEN_DYN)."""
     return (isinstance(block, dict) and block.get("num_bits") == 8 and block.get("type", "int") == "int"
@@ -370,92 +72,40 @@ def _split_state(state: Dict[str, torch.Tensor]) -> Tuple[Dict[str, torch.Tensor
     return dense, quant
 
 
-def _levels_and_shape(name: str, t: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, int, int, bool]:
-    """(stored weight tensor, N, K, packed int4?) of one quantized module."""
-    if "weight_shape" in t:
-        N, K = (int(v) for v in t["weight_shape"].tolist())
-    elif "weight" in t:
-        N, K = t["weight"].shape
-    else:
-        raise ValueError(f"{name}: packed weight without weight_shape")
-    if "weight_packed" in t:
-        w = t["weight_packed"]
-        if w.dtype != torch.int32 or tuple(w.shape) != (N, (K + 7) // 8):
-            raise ValueError(f"{name}: weight_packed must be int32 [{N}, {(K + 7) // 8}], got {w.dtype} "
-                             f"{tuple(w.shape)}")
-        return w, N, K, True
-    w = t.get("weight")
-    if w is None or w.dtype != torch.int8 or tuple(w.shape) != (N, K):
-        raise ValueError(f"{name}: expected an int8 weight [{N}, {K}] or a weight_packed tensor")
-    return w, N, K, False
-
-
-def _group_of_columns(name: str, t: Dict[str, torch.Tensor], K: int, G: int) -> torch.Tensor:
-    """int64 [K]: the group of every original column (weight_g_idx when present, else column // (K / G))."""
-    if "weight_g_idx" in t:
-        g = t["weight_g_idx"].to(torch.int64)
-        if g.numel() != K or int(g.min()) < 0 or int(g.max()) >= G:
-            raise ValueError(f"{name}: weight_g_idx does not match {G} groups of {K} columns")
-        return g
-    if G == 1:
-        return torch.zeros(K, dtype=torch.int64, device=t["weight_scale"].device)
-    return torch.arange(K, device=t["weight_scale"].device) // GROUP
-
-
 def dequantized_weight(name: str, t: Dict[str, torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
     """(q - zp) * scale in fp32 from the stored scale (and zero-point), rounded once to ``dtype``: [N, K]."""
-    w, N, K, packed = _levels_and_shape(name, t)
-    q = unpack_int4(w, K) if packed else w
-    scale = t["weight_scale"].to(torch.float32)
-    G = scale.shape[1]
-    g = _group_of_columns(name, t, K, G)
-    s_col = scale[:, g]
-    q = q.to(torch.float32)
-    if "weight_zero_point" in t:
-        q = q - t["weight_zero_point"].to(torch.float32)[:, g]
-    return (q * s_col).to(dtype)
+    return StoredWeight.from_leaves(name, t).dequantize(dtype)
+
+
+def _refuse_zero_point(name: str, w: StoredWeight) -> None:
+    if w.zero_point is not None:
+        raise ValueError(f"{name}: an A8 checkpoint with weight_zero_point -- the int8 GEMM has no weight zero-point "
+                         "term (W8A8, INT8 and W4A8 weights are symmetric)")
 
 
 def quantized_linear_from_tensors(name: str, t: Dict[str, torch.Tensor], act_symmetric: bool,
                                   bias: Optional[torch.Tensor] = None) -> QuantizedLinear:
     """A ``QuantizedLinear`` from one module's checkpoint tensors (A8 schemes)."""
-    if "weight_zero_point" in t:
-        raise ValueError(f"{name}: an A8 checkpoint with weight_zero_point -- the int8 GEMM has no weight zero-point "
-                         "term (W8A8, INT8 and W4A8 weights are symmetric)")
-    w, N, K, packed = _levels_and_shape(name, t)
-    scale = t["weight_scale"].to(torch.float32)            # bf16 / fp16 -> fp32 is exact
-    G = scale.shape[1]
-    if scale.shape[0] != N or G not in (1, (K + GROUP - 1) // GROUP):
-        raise ValueError(f"{name}: weight_scale {tuple(scale.shape)} is neither channel-wise nor groups of {GROUP} "
-                         f"over {K} columns")
-    col_perm = None
-    if "weight_g_idx" in t:
-        g = _group_of_columns(name, t, K, G)
+    w = StoredWeight.from_leaves(name, t)
+    _refuse_zero_point(name, w)
+    w = w.require_kernel_layout(name)
+    levels, col_perm = w.levels, None
+    if w.g_idx is not None:             # actorder "group": the GEMM takes contiguous groups, so permute the columns
+        g = w.g_idx.to(torch.int64)
         perm = torch.argsort(g, stable=True)
-        if not torch.equal(g[perm], torch.arange(K, device=g.device) // GROUP):
+        if not torch.equal(g[perm], torch.arange(w.K, device=g.device) // GROUP):
             raise ValueError(f"{name}: weight_g_idx groups are not {GROUP} columns each")
-        q = unpack_int4(w, K) if packed else w
-        q = q[:, perm]
-        w = pack_int4(q) if packed else q.contiguous()
+        q = (unpack_int4(levels, w.K) if w.int4 else levels)[:, perm]
+        levels = pack_int4(q) if w.int4 else q.contiguous()
         col_perm = perm.to(torch.int32)
-    return QuantizedLinear(K, N, w, scale, act_symmetric, col_perm=col_perm, bias=bias)
+    return QuantizedLinear(w.K, w.N, levels, w.scale, act_symmetric, col_perm=col_perm, bias=bias)
 
 
 def weight_only_linear_from_tensors(name: str, t: Dict[str, torch.Tensor],
                                     bias: Optional[torch.Tensor] = None) -> WeightOnlyLinear:
     """A ``WeightOnlyLinear`` from one module's checkpoint tensors (A16 schemes, ``a16="packed"``)."""
-    w, N, K, packed = _levels_and_shape(name, t)
-    scale = t["weight_scale"].to(torch.float32)            # bf16 / fp16 -> fp32 is exact
-    G = scale.shape[1]
-    if scale.dim() != 2 or scale.shape[0] != N or G not in (1, (K + GROUP - 1) // GROUP):
-        raise ValueError(f"{name}: weight_scale {tuple(scale.shape)} is neither channel-wise nor groups of {GROUP} "
-                         f"over {K} columns; load it with a16='dequantized'")
-    zp = t.get("weight_zero_point")
-    if zp is not None:
-        if tuple(zp.shape) != (N, G) or zp.is_floating_point() or int(zp.min()) < -128 or int(zp.max()) > 127:
-            raise ValueError(f"{name}: weight_zero_point must be integers in [-128, 127] of shape {(N, G)}")
-    g_idx = _group_of_columns(name, t, K, G).to(torch.int32) if "weight_g_idx" in t else None
-    return WeightOnlyLinear(K, N, w, scale, weight_zero_point=zp, g_idx=g_idx, bias=bias)
+    w = StoredWeight.from_leaves(name, t).require_kernel_layout(name, _A16_HINT)
+    return WeightOnlyLinear(w.K, w.N, w.levels, w.scale, weight_zero_point=w.zero_point, g_idx=w.g_idx, bias=bias)
 
 
 def _read_config(path: Path) -> Tuple[dict, dict]:
@@ -484,8 +134,8 @@ def _is_fused_bank(m: nn.Module) -> bool:
 def _expert_banks(path, model: nn.Module, model_type, dense: Dict[str, torch.Tensor],
                   quant: Dict[str, Dict[str, torch.Tensor]]):
     """Undo ``expert_bank_checkpoint_names``: rename ``dense`` back to the model's names in place, and take every
-    per-expert tensor out of ``dense`` / ``quant``.  Returns ({bank: {e: {proj: ("q", leaves) | ("dense", tensor)}}},
-    {checkpoint prefix: model prefix}).  proj is gate_proj / up_proj / down_proj."""
+    per-expert tensor out of ``dense`` / ``quant``.  Returns ({bank name: module}, {bank name: {e: {proj: ("q", leaves) |
+    ("dense", tensor)}}}, {checkpoint prefix: model prefix}).  proj is gate_proj / up_proj / down_proj."""
     from .sequential import expert_bank_module_renames, expert_layout, rename_module_prefix as _rename
 
     banks = {n: m for n, m in model.named_modules() if _is_fused_bank(m)}
@@ -531,7 +181,17 @@ def _expert_banks(path, model: nn.Module, model_type, dense: Dict[str, torch.Ten
     for bank in found:
         if any("bias" in n for n, _ in banks[bank].named_parameters()):
             raise NotImplementedError(f"{path}: {bank} has expert biases, which this loader does not read")
-    return banks, found
+    return banks, found, inverse
+
+
+def _check_shape(name: str, shape, lin_shape) -> None:
+    if tuple(shape) != tuple(lin_shape):
+        raise ValueError(f"{name} has shape {tuple(shape)} in the checkpoint, {tuple(lin_shape)} in the model")
+
+
+def _set_submodule(model: nn.Module, name: str, new: nn.Module) -> None:
+    parent_name, _, leaf = name.rpartition(".")
+    setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
 
 
 def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[str, tuple]], a8: bool,
@@ -541,89 +201,59 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
     gu, dn = bank.gate_up_proj, bank.down_proj
     E, I2, H = gu.shape
     I = I2 // 2
-    roles = ("gate_proj", "up_proj", "down_proj")
-    missing = [f"{e}.{r}" for e in range(E) for r in roles if r not in experts.get(e, {})]
+    want = {"gate_proj": (I, H), "up_proj": (I, H), "down_proj": (H, I)}
+    missing = [f"{e}.{r}" for e in range(E) for r in want if r not in experts.get(e, {})]
     if missing:
         raise ValueError(f"{path}: {bank_name}: experts missing from the checkpoint: {missing[:6]}")
-    kinds = {experts[e][r][0] for e in range(E) for r in roles}
+    kinds = {experts[e][r][0] for e in range(E) for r in want}
     if len(kinds) > 1:
         raise ValueError(f"{path}: {bank_name} is only partly quantized (some expert Linears are dense); the bank "
                          "runs as one unit, so every expert Linear must share a scheme")
-    want = {"gate_proj": (I, H), "up_proj": (I, H), "down_proj": (H, I)}
 
-    def shape_check(e, r, shape):
-        if tuple(shape) != want[r]:
-            raise ValueError(f"{path}: {bank_name}.{e}.{r} has shape {tuple(shape)} in the checkpoint, {want[r]} in "
-                             "the model")
+    def read(e: int, r: str):
+        """(name, expert e's Linear r on ``dev``: a ``StoredWeight``, or the tensor of a dense one), shape checked."""
+        name = f"{path}: {bank_name}.{e}.{r}"
+        kind, v = experts[e][r]
+        if kind == "dense":
+            w = v.to(dev)
+            _check_shape(name, w.shape, want[r])
+        else:
+            w = StoredWeight.from_leaves(name, {k: t.to(dev) for k, t in v.items()})
+            _check_shape(name, (w.N, w.K), want[r])
+        return name, w
 
     if kinds == {"dense"} or not (a8 or packed_experts):
         for e in range(E):
             W = {}
-            for r in roles:
-                kind, v = experts[e][r]
-                W[r] = v.to(dev).to(mdtype) if kind == "dense" else dequantized_weight(
-                    f"{bank_name}.{e}.{r}", {k: t.to(dev) for k, t in v.items()}, mdtype)
-                shape_check(e, r, W[r].shape)
+            for r in want:
+                w = read(e, r)[1]
+                W[r] = w.dequantize(mdtype) if isinstance(w, StoredWeight) else w.to(mdtype)
             gu.data[e] = torch.cat([W["gate_proj"], W["up_proj"]], 0)
             dn.data[e] = W["down_proj"]
         return None
 
-    # stacked[part] = (weights, scales, zero-points or None, g_idx [E, K] or None), gate rows before up rows
-    stacked = {}
-    for part, rs in (("gate_up", ("gate_proj", "up_proj")), ("down", ("down_proj",))):
-        ws, ss, zs, gs = [], [], [], []
-        for e in range(E):
-            for r in rs:
-                name = f"{bank_name}.{e}.{r}"
-                t = {k: v.to(dev) for k, v in experts[e][r][1].items()}
-                if not a8:                 # A16: the checks and buffers of a WeightOnlyLinear
-                    m = weight_only_linear_from_tensors(name, t)
-                    shape_check(e, r, (m.out_features, m.in_features))
-                    ws.append(m.qweight)
-                    ss.append(m.weight_scale)
-                    zs.append(m.weight_zero_point)
-                    gs.append(m.g_idx)
-                    continue
-                if "weight_g_idx" in t:
-                    raise NotImplementedError(f"{path}: {name}: A8 expert weights with weight_g_idx (actorder "
-                                              "'group') need a per-expert column permutation, which the grouped "
-                                              "GEMM does not take; quantise with actorder 'static'")
-                if "weight_zero_point" in t:
-                    raise ValueError(f"{path}: {name}: an A8 checkpoint with weight_zero_point -- the int8 GEMM has "
-                                     "no weight zero-point term (W8A8, INT8 and W4A8 weights are symmetric)")
-                w, N, K, _ = _levels_and_shape(name, t)
-                shape_check(e, r, (N, K))
-                scale = t["weight_scale"].to(torch.float32)
-                if scale.shape[0] != N or scale.shape[1] not in (1, (K + GROUP - 1) // GROUP):
-                    raise ValueError(f"{path}: {name}: weight_scale {tuple(scale.shape)} is neither channel-wise nor "
-                                     f"groups of {GROUP} over {K} columns")
-                ws.append(w)
-                ss.append(scale)
-                zs.append(None)
-                gs.append(None)
-        if (len({w.dtype for w in ws}) > 1 or len({s.shape[1] for s in ss}) > 1 or len({z is None for z in zs}) > 1
-                or len({g is None for g in gs}) > 1):
-            raise ValueError(f"{path}: {bank_name}: the {part} weights of the experts mix formats or group counts")
-        per = len(rs)
-        g_idx = None
-        if gs[0] is not None:
-            for e in range(E):
-                if not all(torch.equal(gs[e * per], g) for g in gs[e * per:(e + 1) * per]):
-                    raise ValueError(f"{path}: {bank_name}.{e}: gate_proj and up_proj group their columns differently "
-                                     "(weight_g_idx); the grouped GEMV takes one column grouping per expert")
-            g_idx = torch.stack(gs[::per])
+    def kernel_weight(e: int, r: str) -> StoredWeight:
+        name, w = read(e, r)
+        if a8:
+            if w.g_idx is not None:
+                raise NotImplementedError(f"{name}: A8 expert weights with weight_g_idx (actorder 'group') need a "
+                                          "per-expert column permutation, which the grouped GEMM does not take; "
+                                          "quantise with actorder 'static'")
+            _refuse_zero_point(name, w)
+        return w.require_kernel_layout(name, "" if a8 else _A16_HINT)
 
-        def stack(xs):
-            return None if xs[0] is None else torch.stack([torch.cat(xs[e * per:(e + 1) * per], 0) for e in range(E)])
-
-        stacked[part] = (stack(ws), stack(ss), stack(zs), g_idx)
-    if stacked["gate_up"][0].dtype != stacked["down"][0].dtype:
+    # gate rows before up rows
+    gate_up = StoredWeight.stack(f"{path}: {bank_name} gate_up",
+                                 [[kernel_weight(e, r) for r in ("gate_proj", "up_proj")] for e in range(E)])
+    down = StoredWeight.stack(f"{path}: {bank_name} down", [[kernel_weight(e, "down_proj")] for e in range(E)])
+    if gate_up.int4 != down.int4:
         raise ValueError(f"{path}: {bank_name}: gate_up and down weights differ in format")
-    (gu_w, gu_s, gu_z, gu_g), (dn_w, dn_s, dn_z, dn_g) = stacked["gate_up"], stacked["down"]
     if a8:
-        return QuantizedExperts(H, I, gu_w, gu_s, dn_w, dn_s, bank.act_fn, act_symmetric)
-    return WeightOnlyExperts(bank, gu_w, gu_s, dn_w, dn_s, gate_up_zero_point=gu_z, gate_up_g_idx=gu_g,
-                             down_zero_point=dn_z, down_g_idx=dn_g)
+        return QuantizedExperts(H, I, gate_up.levels, gate_up.scale, down.levels, down.scale, bank.act_fn,
+                                act_symmetric)
+    return WeightOnlyExperts(bank, gate_up.levels, gate_up.scale, down.levels, down.scale,
+                             gate_up_zero_point=gate_up.zero_point, gate_up_g_idx=gate_up.g_idx,
+                             down_zero_point=down.zero_point, down_g_idx=down.g_idx)
 
 
 A16_MODES = ("dequantized", "packed")
@@ -683,7 +313,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         model = AutoModelForCausalLM.from_config(config, torch_dtype=mdtype)
     model.eval()
 
-    banks, experts = _expert_banks(path, model, model_type, dense, quant)
+    banks, experts, inverse = _expert_banks(path, model, model_type, dense, quant)
     missing, unexpected = model.load_state_dict(dense, strict=False)
     if unexpected:
         raise ValueError(f"{path}: unexpected tensors {sorted(unexpected)[:8]}")
@@ -702,33 +332,24 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                          packed_experts=packed_experts)
         if new is not None:
             replaced.append(bank_name)
-            parent_name, _, leaf = bank_name.rpartition(".")
-            setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
+            _set_submodule(model, bank_name, new)
     for name, t in quant.items():
         lin = model.get_submodule(name)
         if not isinstance(lin, nn.Linear):
             raise ValueError(f"{path}: {name} is quantized in the checkpoint but is a {type(lin).__name__} here")
         t = {k: v.to(dev) for k, v in t.items()}
-        if a8:
-            new = quantized_linear_from_tensors(name, t, act_symmetric, bias=lin.bias.data if lin.bias is not None
-                                                else None)
-        elif a16 == "packed":
-            new = weight_only_linear_from_tensors(name, t, bias=lin.bias.data if lin.bias is not None else None)
+        if a8 or a16 == "packed":
+            bias = None if lin.bias is None else lin.bias.data
+            new = (quantized_linear_from_tensors(name, t, act_symmetric, bias=bias) if a8
+                   else weight_only_linear_from_tensors(name, t, bias=bias))
+            _check_shape(f"{path}: {name}", (new.out_features, new.in_features), lin.weight.shape)
+            _set_submodule(model, name, new)
         else:
             W = dequantized_weight(name, t, mdtype)
-            if tuple(W.shape) != tuple(lin.weight.shape):
-                raise ValueError(f"{path}: {name} has shape {tuple(W.shape)} in the checkpoint, "
-                                 f"{tuple(lin.weight.shape)} in the model")
+            _check_shape(f"{path}: {name}", W.shape, lin.weight.shape)
             lin.weight.data = W
-            continue
-        if (new.out_features, new.in_features) != tuple(lin.weight.shape):
-            raise ValueError(f"{path}: {name} has shape {(new.out_features, new.in_features)} in the checkpoint, "
-                             f"{tuple(lin.weight.shape)} in the model")
-        parent_name, _, leaf = name.rpartition(".")
-        setattr(model.get_submodule(parent_name) if parent_name else model, leaf, new)
-    from .sequential import expert_bank_module_renames, rename_module_prefix as _rename
+    from .sequential import rename_module_prefix as _rename
 
-    inverse = {v: k for k, v in expert_bank_module_renames(banks, model_type).items()}
     ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
     if not a8 and a16 == "packed":

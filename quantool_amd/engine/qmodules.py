@@ -1,0 +1,274 @@
+"""The four modules ``load_quantized`` (engine/qlinear.py) installs in place of a checkpoint's quantized Linears and
+routed-expert banks.  Each keeps the checkpoint's integer weights in registered buffers; the weight-only pair hands them
+to the kernels, to ``dequantize`` and back to checkpoint tensors as one ``StoredWeight`` (engine/stored_weight.py).
+Only ``forward`` on device tensors needs the HIP library."""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .stored_weight import StoredWeight, group_sums, unpack_int4
+
+
+def _rows(x: torch.Tensor, K: int) -> torch.Tensor:
+    """x [..., K] as the [M, K] rows with unit column stride the kernels read (a copy only where no view gives them)."""
+    x2 = x.reshape(-1, K)
+    return x2 if x2.stride(1) == 1 else x2.contiguous()
+
+
+class QuantizedLinear(nn.Module):
+    """One W8A8 / INT8 / W4A8 Linear of a checkpoint: ``forward(x)`` quantises the rows of ``x`` to int8 (per token,
+    dynamic) and runs the int8 x int8 GEMM with the checkpoint's weight scales.
+
+    Buffers: ``weight`` int8 [N, K] or packed int4 int32 [N, ceil(K/8)] (columns permuted by ``col_perm`` when the
+    checkpoint used actorder ``group``), ``weight_scale`` fp32 [N, G], ``wsum`` int32 [N, G], ``col_perm`` int32 [K]
+    (optional), ``bias`` (optional, model dtype)."""
+
+    def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
+                 act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.in_features = int(in_features)
+        self.out_features = int(out_features)
+        self.act_symmetric = bool(act_symmetric)
+        self.int4 = weight.dtype == torch.int32
+        levels = unpack_int4(weight, in_features) if self.int4 else weight
+        self.register_buffer("weight", weight.contiguous())
+        self.register_buffer("weight_scale", weight_scale.to(torch.float32).contiguous())
+        self.register_buffer("wsum", group_sums(levels, weight_scale.shape[1]))
+        self.register_buffer("col_perm", None if col_perm is None else col_perm.to(torch.int32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.contiguous())
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, "
+                f"weights={'int4 g128' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
+                f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token, "
+                f"col_perm={self.col_perm is not None}, bias={self.bias is not None}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from ..hip import ops
+
+        Xq, s_x, zp_x = ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric,
+                                               col_perm=self.col_perm)
+        bias = None if self.bias is None else self.bias.to(x.dtype)
+        y = ops.gemm_i8(Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
+                        wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+
+class WeightOnlyLinear(nn.Module):
+    """One W4A16 / W4A16_ASYM / W8A16 Linear of a checkpoint on its stored integer weights.
+
+    ``forward(x)`` with M = rows of ``x``: M <= ``skinny_max_m`` runs ``qt_gemm_wq_skinny`` (the weights read once,
+    dequantised on chip; fp32 sums in the kernel's own fixed order); otherwise ``qt_dequantize_weight`` fills a transient
+    dense weight -- bit-identical to the default loader's ``nn.Linear.weight`` -- and ``F.linear`` runs on it, so the
+    output equals that ``nn.Linear``'s to the bit.  On CPU tensors ``forward`` is ``F.linear`` on
+    ``stored.dequantize``.
+
+    Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
+    ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
+    (optional, model dtype).  Columns stay in their original order."""
+
+    # Decode GEMV up to this many rows, dequantise + F.linear above: at 16 rows the GEMV is still faster than the
+    # dequantise + F.linear pair on every measured Llama-3-8B shape.
+    skinny_max_m = 16
+
+    def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
+                 weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.in_features = int(in_features)
+        self.out_features = int(out_features)
+        self.int4 = weight.dtype == torch.int32
+        self.register_buffer("weight_packed" if self.int4 else "weight", weight.contiguous())
+        self.register_buffer("weight_scale", weight_scale.to(torch.float32).contiguous())
+        self.register_buffer("weight_zero_point", None if weight_zero_point is None
+                             else weight_zero_point.to(torch.int8).contiguous())
+        self.register_buffer("g_idx", None if g_idx is None else g_idx.to(torch.int32).contiguous())
+        self.register_buffer("bias", None if bias is None else bias.contiguous())
+
+    @property
+    def qweight(self) -> torch.Tensor:
+        return self.weight_packed if self.int4 else self.weight
+
+    @property
+    def stored(self) -> StoredWeight:
+        """The buffers as they are now (after any ``.to(device)``), as one value."""
+        b = self._buffers   # on the decode path: four lookups through nn.Module.__getattr__ cost more than all the rest
+        return StoredWeight(b["weight_packed" if self.int4 else "weight"], b["weight_scale"], b["weight_zero_point"],
+                            b["g_idx"], self.out_features, self.in_features)
+
+    def checkpoint_tensors(self) -> Dict[str, torch.Tensor]:
+        """The module's weight as the checkpoint leaves ``dequantized_weight`` reads."""
+        return self.stored.leaves()
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, "
+                f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
+                f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
+                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        bias = None if self.bias is None else self.bias.to(x.dtype)
+        w = self.stored
+        if not x.is_cuda:
+            return F.linear(x, w.dequantize(x.dtype), bias)
+        from ..hip import ops
+
+        if 1 <= x.numel() // w.K <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
+            y = ops.gemm_wq_skinny(_rows(x, w.K), w.levels, w.scale, zp_w=w.zero_point, g_idx=w.g_idx, bias=bias)
+            return y.reshape(*x.shape[:-1], w.N)
+        W = ops.dequantize_weight(w.levels, w.scale, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx, dtype=x.dtype)
+        return F.linear(x, W, bias)
+
+
+class _RoutedExperts(nn.Module):
+    """The forward both expert banks run on the device, as transformers' fused bank with its two ``F.linear`` calls
+    replaced: ``qt_moe_route`` orders the routed rows by expert, the gate_up product gathers them by token,
+    ``act_fn(gate) * up`` runs in torch as the fused module does, the down product reads the routed rows in place and
+    ``qt_moe_combine`` sums each token's weighted rows in ascending expert order, rounding as ``index_add_`` does.
+    Nothing waits on the host.  A subclass gives the product: ``_product(part, x, offsets, row_idx)``, rows
+    ``x[row_idx]`` (or ``x``) times the ``part`` ("gate_up" / "down") weights of the expert that owns each row."""
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        from ..hip import ops
+
+        x = _rows(hidden_states, self.hidden_dim)
+        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
+        gate, up = self._product("gate_up", x, offsets, src_token).chunk(2, dim=-1)
+        y = self._product("down", self.act_fn(gate) * up, offsets, None)
+        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
+
+
+class QuantizedExperts(_RoutedExperts):
+    """A W8A8 / INT8 / W4A8 routed-expert bank: ``forward(hidden_states, top_k_index, top_k_weights)`` as
+    transformers' ``MixtralExperts`` with its two ``F.linear`` calls on the int8 GEMM (``_RoutedExperts``): the T tokens
+    are quantised once per token for the gate_up GEMM, the routed rows of ``act_fn(gate) * up`` per row for the down
+    GEMM.  include/quantool_amd.h states every step.
+
+    Buffers: ``gate_up`` int8 [E, 2I, H] or packed int4 int32 [E, 2I, ceil(H/8)] (rows [0, I) gate, [I, 2I) up),
+    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_wsum`` int32 [E, 2I, G]; ``down`` int8 [E, H, I] or int32
+    [E, H, ceil(I/8)], ``down_scale`` fp32 [E, H, G'], ``down_wsum`` int32 [E, H, G']."""
+
+    def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
+                 down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
+        super().__init__()
+        self.num_experts = int(gate_up.shape[0])
+        self.hidden_dim = int(hidden_size)
+        self.intermediate_dim = int(intermediate_size)
+        self.act_fn = act_fn
+        self.act_symmetric = bool(act_symmetric)
+        self.int4 = gate_up.dtype == torch.int32
+        for name, w, s, K in (("gate_up", gate_up, gate_up_scale, self.hidden_dim),
+                              ("down", down, down_scale, self.intermediate_dim)):
+            self.register_buffer(name, w.contiguous())
+            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
+            self.register_buffer(f"{name}_wsum", group_sums(unpack_int4(w, K) if self.int4 else w, s.shape[2]))
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
+                f"weights={'int4 g128' if self.int4 else 'int8'}, "
+                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
+                f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token")
+
+    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor]):
+        from ..hip import ops
+
+        Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=self.act_symmetric)
+        return ops.gemm_i8_grouped(Xq, s_x, getattr(self, part), getattr(self, f"{part}_scale"), offsets,
+                                   row_idx=row_idx, K=x.shape[1], zp_x=zp_x,
+                                   wsum=None if zp_x is None else getattr(self, f"{part}_wsum"), out_dtype=x.dtype)
+
+
+class WeightOnlyExperts(_RoutedExperts):
+    """A W4A16 / W4A16_ASYM / W8A16 routed-expert bank on its stored integer weights: ``forward(hidden_states,
+    top_k_index, top_k_weights)`` as the fused transformers bank it replaces.
+
+    With T = rows of ``hidden_states`` (known on the host) and 1 <= T <= ``grouped_max_tokens``: the routed forward of
+    ``_RoutedExperts`` on the grouped GEMV (``qt_gemm_wq_grouped``).  Only the experts that were hit are read.  Larger
+    T: both banks are dequantised into transient [E, 2I, H] / [E, H, I] tensors
+    (``qt_dequantize_weight``, bit-identical to the dense bank ``a16_experts="dequantized"`` loads) and the bank's own
+    transformers forward runs on them (honouring ``config._experts_implementation``), so the output equals the dense
+    bank's to the bit.  On CPU tensors ``forward`` is that bank forward on ``stored(part).dequantize``.
+
+    Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
+    ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
+    [E, H] (optional, actorder ``group``); ``down`` int32 [E, H, ceil(I/8)] or int8 [E, H, I] and its ``down_scale``,
+    ``down_zero_point``, ``down_g_idx`` likewise.  Columns stay in the checkpoint's order.
+
+    ``bank`` is the fused module replaced: its ``gate_up_proj`` / ``down_proj`` are swapped for empty stand-ins and it
+    is kept (not as a submodule) for its forward alone."""
+
+    # Grouped GEMV up to this many tokens, dequantise + the bank's forward above.  At Mixtral-8x7B's shapes the GEMV pair
+    # re-reads an expert's weights once per 16 of its rows and still beats the dequantise path (2.7 ms) up to T = 192;
+    # at 128 it takes 1.2 ms.
+    grouped_max_tokens = 128
+
+    def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
+                 down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
+                 gate_up_g_idx: Optional[torch.Tensor] = None, down_zero_point: Optional[torch.Tensor] = None,
+                 down_g_idx: Optional[torch.Tensor] = None):
+        super().__init__()
+        E, I2, H = bank.gate_up_proj.shape
+        self.num_experts, self.hidden_dim, self.intermediate_dim = int(E), int(H), int(I2) // 2
+        self.act_fn = bank.act_fn
+        self.int4 = gate_up.dtype == torch.int32
+        for name, w, s, zp, gi in (("gate_up", gate_up, gate_up_scale, gate_up_zero_point, gate_up_g_idx),
+                                   ("down", down, down_scale, down_zero_point, down_g_idx)):
+            self.register_buffer(name, w.contiguous())
+            self.register_buffer(f"{name}_scale", s.to(torch.float32).contiguous())
+            self.register_buffer(f"{name}_zero_point", None if zp is None else zp.to(torch.int8).contiguous())
+            self.register_buffer(f"{name}_g_idx", None if gi is None else gi.to(torch.int32).contiguous())
+        p = bank.gate_up_proj
+        for n in ("gate_up_proj", "down_proj"):
+            setattr(bank, n, nn.Parameter(torch.empty(0, dtype=p.dtype, device=p.device), requires_grad=False))
+        self.__dict__["_bank"] = bank
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, "
+                f"weights={'int4' if self.int4 else 'int8'}, "
+                f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
+                f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
+                f"grouped_max_tokens={self.grouped_max_tokens}")
+
+    def stored(self, part: str) -> StoredWeight:
+        """The ``part`` ("gate_up" / "down") buffers as they are now, as one bank weight [E, ...]."""
+        b = self._buffers   # on the decode path, as ``WeightOnlyLinear.stored``
+        H, I = self.hidden_dim, self.intermediate_dim
+        N, K = (2 * I, H) if part == "gate_up" else (H, I)
+        return StoredWeight(b[part], b[f"{part}_scale"], b[f"{part}_zero_point"], b[f"{part}_g_idx"], N, K)
+
+    def dense_weight(self, part: str, dtype: torch.dtype) -> torch.Tensor:
+        """The ``part`` ("gate_up" / "down") bank dequantised, [E, N, K] in ``dtype``: the dense bank's parameter."""
+        w = self.stored(part)
+        if not w.levels.is_cuda:
+            return w.dequantize(dtype)
+        from ..hip import ops
+
+        E = self.num_experts
+        out = torch.empty((E, w.N, w.K), dtype=dtype, device=w.levels.device)
+        if w.g_idx is None:                 # one call over the stacked [E N, .] rows
+            ops.dequantize_weight(w.levels.flatten(0, 1), w.scale.flatten(0, 1), K=w.K,
+                                  zp_w=None if w.zero_point is None else w.zero_point.flatten(0, 1), dtype=dtype,
+                                  out=out.flatten(0, 1))
+        else:
+            for e in range(E):
+                ops.dequantize_weight(w.levels[e], w.scale[e], K=w.K, zp_w=None if w.zero_point is None
+                                      else w.zero_point[e], g_idx=w.g_idx[e], dtype=dtype, out=out[e])
+        return out
+
+    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor]):
+        from ..hip import ops
+
+        w = self.stored(part)
+        return ops.gemm_wq_grouped(x, w.levels, w.scale, offsets, row_idx=row_idx, K=w.K, zp_w=w.zero_point,
+                                   g_idx=w.g_idx)
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        if hidden_states.is_cuda and 1 <= hidden_states.numel() // self.hidden_dim <= self.grouped_max_tokens:
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        dense = {"gate_up_proj": self.dense_weight("gate_up", hidden_states.dtype),
+                 "down_proj": self.dense_weight("down", hidden_states.dtype)}
+        return torch.func.functional_call(self._bank, dense, (hidden_states, top_k_index, top_k_weights))

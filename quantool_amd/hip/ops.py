@@ -467,14 +467,20 @@ def dequantize(Qt: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor, g_of_col
 
 
 # ---- A8 runtime: dynamic per-token int8 activations, int8 x int8 GEMM ------------------------------
+def _x2d(X: torch.Tensor, name: str) -> int:
+    """The dtype code of ``X``, a bf16 / fp16 device matrix [rows, columns] with unit column stride (any row pitch)."""
+    code = _act16(X, name)
+    if X.dim() != 2 or X.stride(1) != 1:
+        raise ValueError(f"{name} must be 2-d [rows, columns] with unit column stride, got shape {tuple(X.shape)} "
+                         f"strides {X.stride()}")
+    return code
+
+
 def quantize_tokens_i8(X: torch.Tensor, symmetric: bool = True, col_perm: Optional[torch.Tensor] = None):
     """X [M, K] bf16 / fp16 (unit column stride, any row pitch) -> (Xq int8 [M, K], s_x fp32 [M], zp_x int32 [M] or
     None when symmetric); with ``col_perm`` (int32 [K]) Xq[m, k] = q(X[m, col_perm[k]])."""
     lib = load()
-    code = _act16(X, "X")
-    if X.dim() != 2 or X.stride(1) != 1:
-        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
-                         f"strides {X.stride()}")
+    code = _x2d(X, "X")
     M, K = X.shape
     if M == 0 or K == 0:
         raise ValueError(f"X must be non-empty, got shape {tuple(X.shape)}")
@@ -491,44 +497,44 @@ def quantize_tokens_i8(X: torch.Tensor, symmetric: bool = True, col_perm: Option
     return Xq, s_x, zp_x
 
 
-def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
-            zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
-            bias: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16) -> torch.Tensor:
-    """Y [M, N] = s_x[m] * sum_g s_w[n, g] * (acc_g - zp_x[m] * wsum[n, g]) (+ bias): the fixed sequence of
-    ``qt_gemm_i8`` (include/quantool_amd.h).  Wq int8 [N, K], or packed int4 int32 [N, ceil(K/8)] (then ``K`` is
-    required); s_w fp32 [N, G], G = 1 or ceil(K/128); zp_x int32 [M] needs wsum int32 [N, G]."""
-    lib = load()
+def _i8_operands(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, K: Optional[int],
+                 zp_x: Optional[torch.Tensor], wsum: Optional[torch.Tensor], out_dtype, experts: bool = False):
+    """Checks the operands of ``qt_gemm_i8`` -- or, with ``experts``, of ``qt_gemm_i8_grouped``: E weights stacked
+    along a leading dimension; returns (format, N, K, G)."""
     _req(Xq, torch.int8, "Xq", 2)
     M, Kx = Xq.shape
     if not Xq.is_contiguous():
         raise ValueError("Xq must be contiguous [M, K]")
-    if not Wq.is_cuda or Wq.dim() != 2 or not Wq.is_contiguous():
-        raise ValueError("Wq must be a contiguous 2-d device tensor")
-    N = Wq.shape[0]
+    nd = 3 if experts else 2
+    if not Wq.is_cuda or Wq.dim() != nd or not Wq.is_contiguous():
+        raise ValueError(f"Wq must be a contiguous {nd}-d device tensor")
+    E = "E, " if experts else ""
+    rows = list(Wq.shape[:-1])                             # [E, N] or [N]
+    N = rows[-1]
+    if K is not None and K != Kx:
+        raise ValueError(f"K={K} but Xq has {Kx} columns")
+    K = Kx
     if Wq.dtype == torch.int8:
         fmt = _lib.QT_W_INT8
-        if Wq.shape[1] != Kx or (K is not None and K != Kx):
-            raise ValueError(f"int8 Wq must be [N, {Kx}], got {tuple(Wq.shape)}")
+        if Wq.shape[-1] != K:
+            raise ValueError(f"int8 Wq must be [{E}N, {K}], got {tuple(Wq.shape)}")
     elif Wq.dtype == torch.int32:
         fmt = _lib.QT_W_INT4_PACKED
-        if K is not None and K != Kx:
-            raise ValueError(f"K={K} but Xq has {Kx} columns")
-        if Wq.shape[1] != (Kx + 7) // 8:
-            raise ValueError(f"packed int4 Wq must be [N, ceil(K/8) = {(Kx + 7) // 8}], got {tuple(Wq.shape)}")
+        if Wq.shape[-1] != (K + 7) // 8:
+            raise ValueError(f"packed int4 Wq must be [{E}N, ceil(K/8) = {(K + 7) // 8}], got {tuple(Wq.shape)}")
     else:
-        raise TypeError(f"Wq must be int8 [N, K] or packed int4 int32 [N, ceil(K/8)], got {Wq.dtype}")
-    K = Kx
-    if M == 0 or N == 0 or K == 0:
-        raise ValueError(f"empty GEMM: M={M}, N={N}, K={K}")
+        raise TypeError(f"Wq must be int8 [{E}N, K] or packed int4 int32 [{E}N, ceil(K/8)], got {Wq.dtype}")
+    if 0 in (M, K, *rows):
+        raise ValueError(f"empty GEMM: Xq {tuple(Xq.shape)}, Wq {tuple(Wq.shape)}")
     if K > 32768:
         raise ValueError(f"K={K} > 32768: the int32 accumulator could overflow")
     _req(s_x, torch.float32, "s_x", 1)
-    _req(s_w, torch.float32, "s_w", 2)
-    G = s_w.shape[1]
+    _req(s_w, torch.float32, "s_w", nd)
+    G = s_w.shape[-1]
     if s_x.numel() != M or not s_x.is_contiguous():
         raise ValueError(f"s_x must be contiguous fp32 [{M}]")
-    if s_w.shape[0] != N or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
-        raise ValueError(f"s_w must be contiguous fp32 [{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
+    if list(s_w.shape[:-1]) != rows or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
+        raise ValueError(f"s_w must be contiguous fp32 [{E}{N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
     if zp_x is not None:
         _req(zp_x, torch.int32, "zp_x", 1)
         if zp_x.numel() != M or not zp_x.is_contiguous():
@@ -536,11 +542,23 @@ def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Te
         if wsum is None:
             raise ValueError("zp_x needs wsum (per-group row sums of the weight levels)")
     if wsum is not None:
-        _req(wsum, torch.int32, "wsum", 2)
-        if tuple(wsum.shape) != (N, G) or not wsum.is_contiguous():
-            raise ValueError(f"wsum must be contiguous int32 [{N}, {G}]")
+        _req(wsum, torch.int32, "wsum", nd)
+        if list(wsum.shape) != rows + [G] or not wsum.is_contiguous():
+            raise ValueError(f"wsum must be contiguous int32 [{E}{N}, {G}]")
     if out_dtype not in (torch.bfloat16, torch.float16):
         raise TypeError(f"out_dtype must be bf16 or fp16, got {out_dtype}")
+    return fmt, N, K, G
+
+
+def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
+            zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+            bias: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """Y [M, N] = s_x[m] * sum_g s_w[n, g] * (acc_g - zp_x[m] * wsum[n, g]) (+ bias): the fixed sequence of
+    ``qt_gemm_i8`` (include/quantool_amd.h).  Wq int8 [N, K], or packed int4 int32 [N, ceil(K/8)] (then ``K`` is
+    required); s_w fp32 [N, G], G = 1 or ceil(K/128); zp_x int32 [M] needs wsum int32 [N, G]."""
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    M = Xq.shape[0]
     if bias is not None:
         _req(bias, out_dtype, "bias", 1)
         if bias.numel() != N or not bias.is_contiguous():
@@ -585,30 +603,8 @@ def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
     (int32 [R], e.g. ``moe_route``'s src_token) is given, with s_x / zp_x read at the same index; else Xq[m] (then R
     defaults to Xq's rows).  Rows past offsets[E] are left unwritten."""
     lib = load()
-    _req(Xq, torch.int8, "Xq", 2)
-    Mx, Kx = Xq.shape
-    if not Xq.is_contiguous():
-        raise ValueError("Xq must be contiguous [M, K]")
-    if not Wq.is_cuda or Wq.dim() != 3 or not Wq.is_contiguous():
-        raise ValueError("Wq must be a contiguous 3-d device tensor [E, N, K or ceil(K/8)]")
-    E, N = Wq.shape[:2]
-    if Wq.dtype == torch.int8:
-        fmt = _lib.QT_W_INT8
-        if Wq.shape[2] != Kx or (K is not None and K != Kx):
-            raise ValueError(f"int8 Wq must be [E, N, {Kx}], got {tuple(Wq.shape)}")
-    elif Wq.dtype == torch.int32:
-        fmt = _lib.QT_W_INT4_PACKED
-        if K is not None and K != Kx:
-            raise ValueError(f"K={K} but Xq has {Kx} columns")
-        if Wq.shape[2] != (Kx + 7) // 8:
-            raise ValueError(f"packed int4 Wq must be [E, N, ceil(K/8) = {(Kx + 7) // 8}], got {tuple(Wq.shape)}")
-    else:
-        raise TypeError(f"Wq must be int8 [E, N, K] or packed int4 int32 [E, N, ceil(K/8)], got {Wq.dtype}")
-    K = Kx
-    if Mx == 0 or N == 0 or K == 0 or E == 0:
-        raise ValueError(f"empty GEMM: M={Mx}, E={E}, N={N}, K={K}")
-    if K > 32768:
-        raise ValueError(f"K={K} > 32768: the int32 accumulator could overflow")
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype, experts=True)
+    Mx, E = Xq.shape[0], Wq.shape[0]
     _req(offsets, torch.int32, "offsets", 1)
     if offsets.numel() != E + 1 or not offsets.is_contiguous():
         raise ValueError(f"offsets must be contiguous int32 [E + 1 = {E + 1}]")
@@ -625,25 +621,6 @@ def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
             raise ValueError(f"rows={R} but Xq has {Mx} rows (contiguous A)")
     if R <= 0:
         raise ValueError(f"rows must be positive, got {R}")
-    _req(s_x, torch.float32, "s_x", 1)
-    _req(s_w, torch.float32, "s_w", 3)
-    G = s_w.shape[2]
-    if s_x.numel() != Mx or not s_x.is_contiguous():
-        raise ValueError(f"s_x must be contiguous fp32 [{Mx}]")
-    if tuple(s_w.shape[:2]) != (E, N) or G not in (1, (K + 127) // 128) or not s_w.is_contiguous():
-        raise ValueError(f"s_w must be contiguous fp32 [{E}, {N}, 1 or {(K + 127) // 128}], got {tuple(s_w.shape)}")
-    if zp_x is not None:
-        _req(zp_x, torch.int32, "zp_x", 1)
-        if zp_x.numel() != Mx or not zp_x.is_contiguous():
-            raise ValueError(f"zp_x must be contiguous int32 [{Mx}]")
-        if wsum is None:
-            raise ValueError("zp_x needs wsum (per-group row sums of the weight levels)")
-    if wsum is not None:
-        _req(wsum, torch.int32, "wsum", 3)
-        if tuple(wsum.shape) != (E, N, G) or not wsum.is_contiguous():
-            raise ValueError(f"wsum must be contiguous int32 [{E}, {N}, {G}]")
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f"out_dtype must be bf16 or fp16, got {out_dtype}")
     Y = torch.empty((R, N), dtype=out_dtype, device=Xq.device)
     check("qt_gemm_i8_grouped", lib.qt_gemm_i8_grouped(
         Xq.data_ptr(), K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x),
@@ -655,9 +632,7 @@ def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tens
     """out [T, H] = each token's routed rows of Y [R, H] weighted by top_k_weights [T, k] and summed in ascending
     expert order, rounding to Y's dtype after every product and sum (``qt_moe_combine``)."""
     lib = load()
-    code = _act16(Y, "Y")
-    if Y.dim() != 2 or Y.stride(1) != 1:
-        raise ValueError(f"Y must be 2-d [R, H] with unit column stride, got shape {tuple(Y.shape)}")
+    code = _x2d(Y, "Y")
     _req(row_of, torch.int32, "row_of", 1)
     if not top_k_weights.is_cuda or top_k_weights.dim() != 2 or not top_k_weights.is_floating_point():
         raise ValueError("top_k_weights must be a 2-d floating device tensor [T, k]")
@@ -749,10 +724,7 @@ def gemm_wq_skinny(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w
     (``qt_gemm_wq_skinny``): the decode GEMV, 1 <= M <= 16.  X bf16 / fp16 with unit column stride (any row pitch);
     weight arguments as ``dequantize_weight``; bias [N] in X's dtype."""
     lib = load()
-    code = _act16(X, "X")
-    if X.dim() != 2 or X.stride(1) != 1:
-        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
-                         f"strides {X.stride()}")
+    code = _x2d(X, "X")
     M, K = X.shape
     if not 1 <= M <= SKINNY_MAX_M:
         raise ValueError(f"gemm_wq_skinny takes 1 <= M <= {SKINNY_MAX_M} rows, got {M}")
@@ -780,10 +752,7 @@ def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offset
     Every row equals ``gemm_wq_skinny`` of that expert on that row, to the bit; rows past offsets[E] are left
     unwritten."""
     lib = load()
-    code = _act16(X, "X")
-    if X.dim() != 2 or X.stride(1) != 1:
-        raise ValueError(f"X must be 2-d [M, K] with unit column stride, got shape {tuple(X.shape)} "
-                         f"strides {X.stride()}")
+    code = _x2d(X, "X")
     Mx, Kx = X.shape
     if K is not None and K != Kx:
         raise ValueError(f"K={K} but X has {Kx} columns")
