@@ -1,6 +1,5 @@
-// See gemm3_tn.h.  The kernel is xtx.hip's pipeline (unit = 16 k-rows x (256 A + 256 B columns) = 16 KiB,
-// ring of 8 units, LDS-DMA of unit u+6 issued in phase u behind a counted vmcnt(10), waves 4-7 one barrier
-// behind waves 0-3; hazard analysis at xtx_kernel) with two changes:
+// See gemm3_tn.h.  The kernel runs the LDS-ring pipeline of ring_pipe.h exactly as xtx_kernel does (R = 8, L = 6,
+// unit = 16 k-rows x (256 A + 256 B columns) = 16 KiB, 2 LDS-DMA per wave and unit), with two differences:
 //   * the A and B panels of a unit come from two plane sets, and the unit sequence of an item walks
 //     k-chunk (128 rows) -> plane product (6) -> 8 units, so one 8-phase body stays inside one plane pair;
 //   * the epilogue applies the tile to C (C -= acc / C = acc) or stores a slab for the ordered reduction.
@@ -16,12 +15,7 @@
 
 namespace {
 
-constexpr int BT = 256;
-constexpr int UT = 16;
-constexpr int UNIT_BYTES = UT * 2 * BT * 2;
-constexpr int RING = 8;
-constexpr int NTHREADS = 512;
-constexpr int NUM_CU = 256;
+constexpr int RING = 8;                         // units resident in LDS (128 KiB)
 constexpr int CH_ROWS = G3_CHUNK_ROWS;          // k rows per chunk (64)
 constexpr int CH_UNITS = 6 * (CH_ROWS / UT);    // 24 units: 6 plane products x 4 units
 static_assert(CH_ROWS / UT == 4, "the phase code below recomputes the source pointers every 4 units");
@@ -125,14 +119,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
 
     s16x8 fa[4], fb[2];
+    // stays a lambda: with the ladder called straight from phase() hipcc emits a different kernel (see profiles/
+    // ring_pipe_isa_parent_vs_refactor.txt)
     auto drain_wait = [&](int u) {
-        const int later = nu - u - 2;
-        if (later >= 5) wait_vmcnt<10>();
-        else if (later == 4) wait_vmcnt<8>();
-        else if (later == 3) wait_vmcnt<6>();
-        else if (later == 2) wait_vmcnt<4>();
-        else if (later == 1) wait_vmcnt<2>();
-        else wait_vmcnt<0>();
+        ring_drain_wait<2, LEAD>(nu - u - 2);
     };
     auto phase = [&](auto slot_c, auto steady_c, int u) {
         constexpr int S = decltype(slot_c)::value;
@@ -149,52 +139,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
             glds16_pair2(voffA, voffB, runA, runB, d, d + 8192);
             runA += ustride;
             runB += ustrideB;
-            wait_vmcnt<10>();
+            wait_vmcnt<2 * (LEAD - 1)>();
         } else if (u + LEAD < nu) {
             issue(u + LEAD, ISLOT);
-            wait_vmcnt<10>();
+            wait_vmcnt<2 * (LEAD - 1)>();
         } else {
             drain_wait(u);
         }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-                acc[mi][ni] = mfma16<false>(fa[mi], fb[ni], acc[mi][ni]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        ring_sync_math([&] { ring_mma32<false>(fa, fb, acc); });
     };
     auto body8 = [&](auto steady_c, int u) {
-        phase(std::integral_constant<int, 0>{}, steady_c, u);
-        phase(std::integral_constant<int, 1>{}, steady_c, u + 1);
-        phase(std::integral_constant<int, 2>{}, steady_c, u + 2);
-        phase(std::integral_constant<int, 3>{}, steady_c, u + 3);
-        phase(std::integral_constant<int, 4>{}, steady_c, u + 4);
-        phase(std::integral_constant<int, 5>{}, steady_c, u + 5);
-        phase(std::integral_constant<int, 6>{}, steady_c, u + 6);
-        phase(std::integral_constant<int, 7>{}, steady_c, u + 7);
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, steady_c, uu); }, u);
     };
 
     if (nu > 0) {
 #pragma unroll
         for (int i = 0; i < LEAD; ++i) issue(i, i);   // nu >= 24 > LEAD
         wait_vmcnt<2 * (LEAD - 1)>();
-        __builtin_amdgcn_s_barrier();
-        if (group_b) __builtin_amdgcn_s_barrier();   // stagger: group B runs one interval behind
-        __builtin_amdgcn_sched_barrier(0);
+        ring_stagger_begin(group_b);
         unit_src(LEAD, runA, runB);
         int u = 0;
         for (; u + 8 + LEAD <= nu; u += 8) body8(std::true_type{}, u);
         for (; u + 8 <= nu; u += 8) body8(std::false_type{}, u);
-        if (!group_b) __builtin_amdgcn_s_barrier();   // pairs with group B's last barrier
-        wait_vmcnt<0>();
+        ring_stagger_end(group_b);
     }
 
     // ---- epilogue ----

@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "ring_pipe.h"
 #include "sgemm_tn.h"
 
 namespace {
@@ -319,21 +320,6 @@ struct RingArgs {
     int group_m_end[SG_MAX_GROUPS];
 };
 
-__device__ __forceinline__ void glds16_one(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile(
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_dst)
-        : "memory");
-}
-
-template <int NW>
-__device__ __forceinline__ void ring_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW) : "memory");
-}
-
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sgemm_ring_kernel(RingArgs p) {
     __shared__ __attribute__((aligned(16))) char ring[RS * RSTAGE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -485,8 +471,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int ch = 0; ch < nchains; ++ch) {
             zero_acc();      // every chain starts from zero (its own accumulator live range: no copies at the loop edges)
             for (int ps = 0; ps < pairs_per_chain; ++ps, g += 2) {
-                if (batch_prev) ring_wait_vmcnt<32>();
-                else ring_wait_vmcnt<0>();
+                if (batch_prev) wait_vmcnt<32>();
+                else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 if (g + 2 < total) {
                     issue_next();

@@ -10,14 +10,9 @@
 // channel-contiguous, the natural staging unit is a slice of TOKENS, not of channels:
 //   unit  = 16 tokens x (256 A-panel + 256 B-panel channels) = 16 KiB = exactly one
 //           v_mfma_f32_32x32x16_bf16 k-step for the whole 256x256 tile;
-//   ring  = 8 units of LDS (128 KiB); unit u is consumed in phase u and its slot is re-filled
-//           with unit u+8; the LDS-DMA of unit u+6 is issued in phase u, so FIVE units (80 KiB per
-//           CU) are always in flight behind a COUNTED s_waitcnt vmcnt(10) -- never 0 in the loop;
-//   phase = { 12 transposing reads of unit u ; issue unit u+6 ; vmcnt(10) ; s_barrier ;
-//             lgkmcnt(0) ; 8 MFMAs ; s_barrier };
-//   waves 4-7 run the same program one barrier behind waves 0-3, so on every SIMD one wave's
-//   LDS reads / DMA issue run under its partner's 8 MFMAs (ping-pong), and a unit's slot is free
-//   two phases after it was read (hazard analysis at the kernel).
+// the units run through the LDS-ring pipeline of ring_pipe.h (phase, stagger and hazard analysis there) with a
+// ring of 8 units (128 KiB) and a lead of 6: FIVE units (80 KiB per CU) are always in flight behind a COUNTED
+// s_waitcnt vmcnt(10), and a phase is 12 transposing reads, one unit's issue and 8 MFMAs per wave.
 //
 // Work decomposition: lower-triangular 256x256 output tiles.  Whole "rounds" of 256 tiles run one
 // workgroup per tile over ALL tokens and add their tile straight into G from the epilogue (no slab
@@ -37,13 +32,8 @@
 
 namespace {
 
-constexpr int BT = 256;                       // output tile edge (channels)
 constexpr int BKT = 64;                       // tokens per token tile (split / tail granularity)
-constexpr int UT = 16;                        // tokens per unit = one MFMA k-step
-constexpr int UNIT_BYTES = UT * 2 * BT * 2;   // A + B panels, 16 KiB
 constexpr int RING = 8;                       // units resident in LDS (128 KiB)
-constexpr int NTHREADS = 512;                 // 8 waves: 2 (M) x 4 (N), 128x64 outputs per wave
-constexpr int NUM_CU = 256;
 
 struct XtxParams {
     const void* X;       // [tokens, ldx] 16-bit elements (bf16 or fp16: the kernel is instantiated for each)
@@ -72,6 +62,38 @@ struct XtxParams {
     int64_t x_batch_bytes;    // ... whose X matrices lie this many bytes apart
 };
 
+// Workgroup -> logical item.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share one; speed only, never
+// correctness).  Within each round of 256 consecutive blocks, the 32 blocks of one XCD take 32 consecutive logical
+// items = one 4x8 block of tiles of the table (map_mode 0), or identity.
+__device__ __forceinline__ int xtx_logical(int map_mode) {
+    const int b = blockIdx.x, nwg = gridDim.x;
+    if (map_mode != 0) return b;
+    const int round = b >> 8, rb = b & 255;
+    const int m = min(256, nwg - (round << 8));
+    const int xcd = rb & 7, idx = rb >> 3, q8 = m >> 3, r8 = m & 7;
+    return (round << 8) + (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+}
+
+// Logical item -> tile (ti, tj), token tiles [tt0, tt0 + cnt) and slab (-1: a direct item, added into G).
+__device__ __forceinline__ int xtx_item(const XtxParams& p, int logical, int& tt0, int& cnt, int& slab_idx) {
+    int tile_idx;
+    slab_idx = -1;
+    if (logical < p.n_direct) {
+        tile_idx = logical;
+        tt0 = 0;
+        cnt = p.n_tt;
+    } else {
+        const int l2 = logical - p.n_direct;
+        const int chunk = l2 / p.n_rem;
+        tile_idx = p.n_direct + (l2 - chunk * p.n_rem);
+        const int base_cnt = p.n_tt / p.s2, rem = p.n_tt % p.s2;
+        tt0 = chunk * base_cnt + (chunk < rem ? chunk : rem);
+        cnt = base_cnt + (chunk < rem ? 1 : 0);
+        slab_idx = l2;
+    }
+    return p.tile_tab[tile_idx];
+}
+
 // WRAP = true is a TIMING-ONLY ablation (wrong results; only in builds with -DQT_XTX_ABLATION, then
 // QT_XTX_ABLATE_WRAP=<units>): the source
 // pointer wraps every wrap_units units, so the footprint every workgroup streams is that window --
@@ -89,7 +111,7 @@ struct XtxParams {
 
 template <bool WRAP, bool F16, bool THROTTLE>
 __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
-    constexpr int LEAD = 6;     // unit u+LEAD is issued in phase u  (LEAD <= RING-2, see the hazard analysis)
+    constexpr int LEAD = 6;     // unit u+LEAD is issued in phase u  (LEAD <= RING-2: hazard analysis in ring_pipe.h)
     // ONE LDS object: the ring (+ 1 KiB of scratch for the throttle's progress snapshot).
     // Unit image: [4 channel groups: A-lo, A-hi, B-lo, B-hi][16 tokens][256 B].
     __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES + (THROTTLE ? 1024 : 0)];
@@ -99,37 +121,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
     const int wave_m = wave >> 2, wave_n = wave & 3;
     const bool group_b = wave >= 4;  // wave-uniform
 
-    // ---- workgroup -> work item ------------------------------------------------------------
-    // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share one; speed only, never
-    // correctness).  Within each round of 256 consecutive blocks, the 32 blocks of one XCD take 32
-    // consecutive logical items = one 4x8 block of tiles of the table.
-    int logical;
-    {
-        const int b = blockIdx.x, nwg = gridDim.x;
-        if (p.map_mode == 0) {
-            const int round = b >> 8, rb = b & 255;
-            const int m = min(256, nwg - (round << 8));
-            const int xcd = rb & 7, idx = rb >> 3, q8 = m >> 3, r8 = m & 7;
-            logical = (round << 8) + (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        } else {
-            logical = b;
-        }
-    }
-    int tile_idx, tt0, cnt, slab_idx = -1;
-    if (logical < p.n_direct) {
-        tile_idx = logical;
-        tt0 = 0;
-        cnt = p.n_tt;
-    } else {
-        const int l2 = logical - p.n_direct;
-        const int chunk = l2 / p.n_rem;
-        tile_idx = p.n_direct + (l2 - chunk * p.n_rem);
-        const int base_cnt = p.n_tt / p.s2, rem = p.n_tt % p.s2;
-        tt0 = chunk * base_cnt + (chunk < rem ? chunk : rem);
-        cnt = base_cnt + (chunk < rem ? 1 : 0);
-        slab_idx = l2;
-    }
-    const int tt_packed = p.tile_tab[tile_idx];
+    const int logical = xtx_logical(p.map_mode);
+    int tt0, cnt, slab_idx;
+    const int tt_packed = xtx_item(p, logical, tt0, cnt, slab_idx);
     const int ti = tt_packed >> 16, tj = tt_packed & 0xFFFF;
     const int nu = cnt * (BKT / UT);  // units of this item (a multiple of 4)
     const int K = p.K;
@@ -240,27 +234,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
 
-    // ---- the pipeline --------------------------------------------------------------------------
-    // Intervals between consecutive workgroup barriers are numbered; waves 0-3 (group A) run
-    // LOAD(u) in interval 2u and MATH(u) in 2u+1, waves 4-7 (group B) one interval later.
-    //   RAW: unit u is read in intervals 2u (A) / 2u+1 (B).  Every wave waits for its own DMA of
-    //        unit u (counted vmcnt) in LOAD(u-1), i.e. in intervals 2u-2 / 2u-1, and the barrier
-    //        that ends interval 2u-1 follows both: "read one phase after the wait that retires it".
-    //   WAR: unit u's reads retire at the lgkmcnt(0) that opens MATH(u): intervals 2u+1 (A) / 2u+2 (B).
-    //        Its slot is re-filled with unit u+8, issued in LOAD(u+2): intervals 2u+4 / 2u+5, after
-    //        the barriers that end 2u+2 and 2u+3.  (LEAD 7 would put group A's issue into 2u+2, beside
-    //        group B's outstanding reads.)
-    //   In flight at every wait: 5 units = 10 LDS-DMA instructions per wave (80 KiB per CU).
+    // ---- the pipeline (ring_pipe.h): R = RING = 8, L = LEAD = 6, unit = 16 tokens, 2 LDS-DMA per wave and unit ----
     s16x8 fa[4], fb[2];
+    // stays a lambda: with the ladder called straight from phase() hipcc emits a different kernel (see profiles/
+    // ring_pipe_isa_parent_vs_refactor.txt)
     auto drain_wait = [&](int u) {
-        // no unit beyond nu-1 exists: allow exactly the units after u+1 to stay in flight
-        const int later = nu - u - 2;
-        if (later >= 5) wait_vmcnt<10>();
-        else if (later == 4) wait_vmcnt<8>();
-        else if (later == 3) wait_vmcnt<6>();
-        else if (later == 2) wait_vmcnt<4>();
-        else if (later == 1) wait_vmcnt<2>();
-        else wait_vmcnt<0>();
+        ring_drain_wait<2, LEAD>(nu - u - 2);
     };
     auto phase = [&](auto slot_c, auto steady_c, int u) {
         constexpr int S = decltype(slot_c)::value;
@@ -279,44 +258,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
 #endif
         if (STEADY) {
             issue_running(ISLOT);
-            wait_vmcnt<10>();   // everything up to unit u+1 has landed; 5 units stay in flight
+            wait_vmcnt<2 * (LEAD - 1)>();   // everything up to unit u+1 has landed; 5 units stay in flight
         } else if (u + LEAD < nu) {
             issue(u + LEAD, ISLOT);
-            wait_vmcnt<10>();
+            wait_vmcnt<2 * (LEAD - 1)>();
         } else {
             drain_wait(u);
         }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
         // ---- MATH ----
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
 #ifdef QT_XTX_ABL_HALF   // lab builds only, TIMING-ONLY (wrong results): half of the MFMAs of every phase
         constexpr int MI_N = 2;
 #else
         constexpr int MI_N = 4;
 #endif
-#pragma unroll
-        for (int mi = 0; mi < MI_N; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-                acc[mi][ni] = mfma16<F16>(fa[mi], fb[ni], acc[mi][ni]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        ring_sync_math([&] { ring_mma32<F16, MI_N>(fa, fb, acc); });
     };
     auto body8 = [&](auto steady_c, int u) {
         if (THROTTLE && throttled && (u & (p.thr_chk - 1)) == 0) throttle_step(u);
-        phase(std::integral_constant<int, 0>{}, steady_c, u);
-        phase(std::integral_constant<int, 1>{}, steady_c, u + 1);
-        phase(std::integral_constant<int, 2>{}, steady_c, u + 2);
-        phase(std::integral_constant<int, 3>{}, steady_c, u + 3);
-        phase(std::integral_constant<int, 4>{}, steady_c, u + 4);
-        phase(std::integral_constant<int, 5>{}, steady_c, u + 5);
-        phase(std::integral_constant<int, 6>{}, steady_c, u + 6);
-        phase(std::integral_constant<int, 7>{}, steady_c, u + 7);
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, steady_c, uu); }, u);
     };
 
     if (nu > 0) {
@@ -326,9 +285,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
             if (i < nu) issue(i, i);
         if (nu >= LEAD) wait_vmcnt<2 * (LEAD - 1)>();
         else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (group_b) __builtin_amdgcn_s_barrier();  // stagger: group B runs one interval behind
-        __builtin_amdgcn_sched_barrier(0);
+        ring_stagger_begin(group_b);
 
         // steady body: every phase issues a unit that exists and does not come from the tail staging
         const int steady_end = (nu < i_tail ? nu : i_tail);
@@ -342,8 +299,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
             phase(std::integral_constant<int, 2>{}, std::false_type{}, u + 2);
             phase(std::integral_constant<int, 3>{}, std::false_type{}, u + 3);
         }
-        if (!group_b) __builtin_amdgcn_s_barrier();  // pairs with group B's last barrier
-        wait_vmcnt<0>();
+        ring_stagger_end(group_b);
         if (THROTTLE && throttled && lane == 0) {   // finished: never the slowest member again
             unsigned* dst = prog_round + prog_member;
             const unsigned val = 0x7fffffffu;
@@ -396,18 +352,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
 // 16-31 from the second; inside a 32-lane half the two groups read token rows r and r+8 of one unit,
 // so the source-side swizzle also folds token-row bit 3 into the chunk index (conflict-free: the 32
 // lanes of a half then cover all 16 chunks x 2 halves of a 256-byte bank row exactly once).
-//   RAW / WAR: as above with "unit" := double, 5 slots, LEAD 3 doubles: two doubles (8 LDS-DMA
-//   instructions per wave, 64 KiB per CU) stay in flight behind a counted vmcnt(8).
+// The pipeline (ring_pipe.h): R = ND = 5, L = LEAD = 3, unit = double, 4 LDS-DMA per wave and double; two doubles
+// (64 KiB per CU) stay in flight behind a counted vmcnt(8).
 constexpr int RING16 = 10;          // units
 constexpr int DBL_BYTES = 2 * UNIT_BYTES;
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma32(s16x8 a, s16x8 b, f32x4 c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 template <bool F16, bool DOT = false>
 __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
@@ -420,18 +368,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
     const int wave_m = wave >> 2, wave_n = wave & 3;
     const bool group_b = wave >= 4;
 
-    int logical;
-    {
-        const int b = blockIdx.x, nwg = gridDim.x;
-        if (p.map_mode == 0) {
-            const int round = b >> 8, rb = b & 255;
-            const int m = min(256, nwg - (round << 8));
-            const int xcd = rb & 7, idx = rb >> 3, q8 = m >> 3, r8 = m & 7;
-            logical = (round << 8) + (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        } else {
-            logical = b;
-        }
-    }
+    int logical = xtx_logical(p.map_mode);
     // DOT: several problems (one X each, same K / n_tokens / H) in one launch; item index inside the problem
     const int item_global = logical;
     const char* Xb = (const char*)p.X;
@@ -440,21 +377,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
         logical -= prob * p.batch_items;
         Xb += (size_t)prob * (size_t)p.x_batch_bytes;
     }
-    int tile_idx, tt0, cnt, slab_idx = -1;
-    if (logical < p.n_direct) {
-        tile_idx = logical;
-        tt0 = 0;
-        cnt = p.n_tt;
-    } else {
-        const int l2 = logical - p.n_direct;
-        const int chunk = l2 / p.n_rem;
-        tile_idx = p.n_direct + (l2 - chunk * p.n_rem);
-        const int base_cnt = p.n_tt / p.s2, rem = p.n_tt % p.s2;
-        tt0 = chunk * base_cnt + (chunk < rem ? chunk : rem);
-        cnt = base_cnt + (chunk < rem ? 1 : 0);
-        slab_idx = l2;
-    }
-    const int tt_packed = p.tile_tab[tile_idx];
+    int tt0, cnt, slab_idx;
+    const int tt_packed = xtx_item(p, logical, tt0, cnt, slab_idx);
     const int ti = tt_packed >> 16, tj = tt_packed & 0xFFFF;
     const int nd = cnt * (BKT / (2 * UT));  // doubles of this item (2 per 64-token tile)
     const int K = p.K;
@@ -509,10 +433,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
 
     s16x8 fa[8], fb[4];
     auto drain_wait = [&](int d) {
-        const int later = nd - d - 2;      // doubles after d+1 that exist
-        if (later >= 2) wait_vmcnt<8>();
-        else if (later == 1) wait_vmcnt<4>();
-        else wait_vmcnt<0>();
+        ring_drain_wait<4, LEAD>(nd - d - 2);
     };
     auto phase = [&](auto slot_c, auto steady_c, int d) {
         constexpr int S = decltype(slot_c)::value;
@@ -526,26 +447,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
         if (STEADY) {
             issue_at(run_src, ISLOT);
             run_src += 2 * ustride;
-            wait_vmcnt<8>();        // everything up to double d+1 has landed; 2 doubles stay in flight
+            wait_vmcnt<4 * (LEAD - 1)>();   // everything up to double d+1 has landed; 2 doubles stay in flight
         } else if (d + LEAD < nd) {
             issue_at(dbl_src(d + LEAD), ISLOT);
-            wait_vmcnt<8>();
+            wait_vmcnt<4 * (LEAD - 1)>();
         } else {
             drain_wait(d);
         }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ai = 0; ai < 8; ++ai)
-#pragma unroll
-            for (int bj = 0; bj < 4; ++bj) acc[ai][bj] = mfma32<F16>(fa[ai], fb[bj], acc[ai][bj]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        ring_sync_math([&] { ring_mma16<F16>(fa, fb, acc); });
     };
 
     if (nd > 0) {
@@ -554,20 +463,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
             if (i < nd) issue_at(dbl_src(i), i);
         if (nd >= LEAD) wait_vmcnt<4 * (LEAD - 1)>();
         else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (group_b) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        ring_stagger_begin(group_b);
 
         const int steady_end = (nd < d_tail ? nd : d_tail);
         run_src += (size_t)LEAD * 2 * ustride;
         int d = 0;
-        for (; d + ND + LEAD <= steady_end; d += ND) {
-            phase(std::integral_constant<int, 0>{}, std::true_type{}, d);
-            phase(std::integral_constant<int, 1>{}, std::true_type{}, d + 1);
-            phase(std::integral_constant<int, 2>{}, std::true_type{}, d + 2);
-            phase(std::integral_constant<int, 3>{}, std::true_type{}, d + 3);
-            phase(std::integral_constant<int, 4>{}, std::true_type{}, d + 4);
-        }
+        for (; d + ND + LEAD <= steady_end; d += ND)
+            ring_body<ND>([&](auto slot_c, int dd) { phase(slot_c, std::true_type{}, dd); }, d);
         // d is a multiple of 5 here: the remaining phases take slots 0, 1, 2, ... in turn
         for (; d < nd; d += ND) {
             phase(std::integral_constant<int, 0>{}, std::false_type{}, d);
@@ -576,8 +478,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
             if (d + 3 < nd) phase(std::integral_constant<int, 3>{}, std::false_type{}, d + 3);
             if (d + 4 < nd) phase(std::integral_constant<int, 4>{}, std::false_type{}, d + 4);
         }
-        if (!group_b) __builtin_amdgcn_s_barrier();
-        wait_vmcnt<0>();
+        ring_stagger_end(group_b);
     }
 
     // epilogue: 16x16 tiles, lane = column (B channel), registers = 4 consecutive rows (A channels)
