@@ -10,7 +10,11 @@
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless it says host;
  *   - the caller owns every buffer; nothing persistent is allocated here.  Scratch comes in
- *     through (workspace, workspace_bytes); sizes from the matching *_workspace_bytes();
+ *     through (workspace, workspace_bytes); sizes from the matching *_workspace_bytes().  An entry point writes
+ *     nothing outside those bytes and asks no alignment of `workspace` (it aligns the pointer up to 256 itself; the
+ *     sizes carry the slack).  A NULL or shorter workspace is refused with QT_ERR_WORKSPACE before anything is
+ *     launched.  Where an environment variable changes a size (QT_PREPARE_TWO_PASS, QT_CHOL_G3*, QT_CHOL_NBO / NBI,
+ *     QT_G3_TARGET_ITEMS, QT_SWEEP_FAR), the size function and the entry point must be called under the same setting;
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*); calls are
  *     asynchronous and re-entrant per stream; the current HIP device is used;
  *   - return value: QT_OK (0) or a negative qt_status; qt_last_error() gives a message for
@@ -182,7 +186,9 @@ int qt_dequantize(const int8_t* Qt, int R, int K, const int32_t* col_src, const 
 
 /* ---- a12  AWQ scale search (AWQModifier under awq.py:81) ----------------------------------------
  * w_sum[K] += sum_rows |w| / (group absmax + 1e-6) (call once per balance layer; w_mean = w_sum /
- * total rows).  group_size: any divisor of K; <= 0 = one group per row (W8A16). */
+ * total rows).  group_size: any divisor of K; <= 0 = one group per row (W8A16).  The workspace size holds for every
+ * group size (it has no such argument).  Group sizes of 64 and more that are above 512 or not a multiple of 64 take
+ * R <= 65535 rows per call. */
 size_t qt_awq_weight_mean_workspace_bytes(int R, int K);
 int qt_awq_weight_mean_accumulate(const void* W, int w_dtype, int R, int K, int64_t ldw, int group_size,
                                   float* w_sum, void* workspace, size_t workspace_bytes,
@@ -238,7 +244,9 @@ int qt_smoothquant_scales(const float* cmin, const float* cmax, const float* wma
  * acc[m][n] = sum_{k ascending} A[k*lda + m] * B[k*ldb + n]   (bit-for-bit an fmaf chain from 0)
  * mode 0: Cout = Cin - acc   1: Cout = acc   2: Cout = -acc.   skip_zero_k: B[k][n] == 0 for k < n.
  * allow_split_k != 0 lets latency-bound shapes split k over workgroups (ordered slab reduction:
- * deterministic, but no longer the single ascending chain -- the sweep never allows it). */
+ * deterministic, but no longer the single ascending chain -- the sweep never allows it).  The workspace is read
+ * only with allow_split_k != 0, and is then required in full (QT_ERR_WORKSPACE otherwise: whether k is split must
+ * follow from the shape alone); with allow_split_k == 0 it may be NULL. */
 size_t qt_sgemm_tn_f32_workspace_bytes(int M, int N);
 int qt_sgemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Cin,
                     int64_t ldcin, float* Cout, int64_t ldcout, int M, int N, int kdim, int skip_zero_k,

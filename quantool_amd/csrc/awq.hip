@@ -87,6 +87,28 @@ __global__ __launch_bounds__(256) void awq_wmean_cols_kernel(const void* __restr
     partial[(size_t)chunk * K + k] = acc;
 }
 
+// Short groups (group_size < 64): a row has more than K / 64 of them, so the maxima table of the long-group path would
+// outgrow what qt_awq_weight_mean_workspace_bytes(R, K) -- which does not know the group size -- can promise.  No table
+// here: one thread per column takes its own group's maximum (at most 63 loads of one row segment, served by the caches)
+// and adds its term; per column the operations and their order are those of the two kernels above (a maximum does not
+// depend on the order it is taken in), so the three paths agree to the bit.
+__global__ __launch_bounds__(256) void awq_wmean_short_kernel(const void* __restrict__ W, int dtype, int R, int K,
+                                                              int64_t ldw, int gs, float* __restrict__ partial) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int chunk = blockIdx.y;
+    if (k >= K) return;
+    const int c0 = k / gs * gs;
+    const int r0 = chunk * WM_ROWS, r1 = (r0 + WM_ROWS < R) ? r0 + WM_ROWS : R;
+    float acc = 0.0f;
+    for (int r = r0; r < r1; ++r) {
+        float m = 0.0f;
+        for (int c = 0; c < gs; ++c) m = fmaxf(m, fabsf(qt_load_w(W, dtype, (size_t)r * ldw + c0 + c)));
+        m = m + 1e-6f;
+        acc = acc + fabsf(qt_load_w(W, dtype, (size_t)r * ldw + k)) / m;
+    }
+    partial[(size_t)chunk * K + k] = acc;
+}
+
 __global__ __launch_bounds__(256) void chunk_sum_kernel(const float* __restrict__ partial, int n_chunks, int K,
                                                         float* __restrict__ out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -459,7 +481,9 @@ __global__ __launch_bounds__(256) void rtn_kernel(const void* __restrict__ W, in
 
 extern "C" size_t qt_awq_weight_mean_workspace_bytes(int R, int K) {
     if (R <= 0 || K <= 0) return 0;
-    // per-chunk partial sums + (long groups only) one maximum per (row, group); K / 64 bounds the groups
+    // per-chunk partial sums + one maximum per (row, group) for the groups that need the table: sizes above 512 or not a
+    // multiple of 64, and at least 64 -- so at most K / 64 <= ceil(K / 64) groups per row.  Groups shorter than 64 (up
+    // to K per row) take awq_wmean_short_kernel, which has no table.
     return (size_t)((R + WM_ROWS - 1) / WM_ROWS) * K * 4 + qt_align_up((size_t)R * ((K + 63) / 64) * 4, 256) + 512;
 }
 
@@ -485,9 +509,13 @@ extern "C" int qt_awq_weight_mean_accumulate(const void* W, int w_dtype, int R, 
         hipLaunchKernelGGL(awq_wmean_partial_kernel, dim3(K / gs, chunks), dim3(64), 0, stream, W, w_dtype, R, K, ldw,
                            gs, partial);
         QT_LAUNCH_CHECK();
+    } else if (gs < 64) {
+        hipLaunchKernelGGL(awq_wmean_short_kernel, dim3((K + 255) / 256, chunks), dim3(256), 0, stream, W, w_dtype, R, K,
+                           ldw, gs, partial);
+        QT_LAUNCH_CHECK();
     } else {
         QT_CHECK_ARG(R <= 65535, "qt_awq_weight_mean_accumulate: R=%d > 65535 rows per call with long groups", R);
-        float* amax = partial + (size_t)chunks * K;
+        float* amax = partial + (size_t)chunks * K;   // R * (K / gs) <= R * ceil(K / 64) floats: gs >= 64 here
         hipLaunchKernelGGL(row_group_absmax_kernel, dim3(K / gs, R), dim3(64), 0, stream, W, w_dtype, R, K, ldw, gs,
                            amax);
         QT_LAUNCH_CHECK();

@@ -735,9 +735,16 @@ extern "C" int qt_sgemm_tn_f32(const float* A, int64_t lda, const float* B, int6
     g.M = M; g.N = N; g.kdim = kdim;
     g.k_mode = skip_zero_k ? SG_K_FROM_N0 : SG_K_FULL;
     g.mode = mode;
-    if (allow_split_k && workspace) {
+    if (allow_split_k) {
+        // refused as by every other entry point: were a shorter workspace to switch the split off, the summation order
+        // -- the bits of the result -- would depend on how much the caller happened to pass
+        const size_t need = qt_sgemm_tn_f32_workspace_bytes(M, N);
+        if (!workspace || workspace_bytes < need) {
+            qt_set_error("qt_sgemm_tn_f32: workspace %zu < required %zu", workspace_bytes, need);
+            return QT_ERR_WORKSPACE;
+        }
         g.split_ws = (float*)qt_align_up((size_t)workspace, 256);
-        g.split_ws_bytes = workspace_bytes >= 256 ? workspace_bytes - 256 : 0;
+        g.split_ws_bytes = workspace_bytes - 256;
     }
     return qt_sgemm_tn(g, stream);
 }
