@@ -80,15 +80,70 @@ def test_linear_vs_independent_oracle_mismatch_rate(dev, oracle):
     np.testing.assert_array_equal(res[0].scale_f32.cpu().numpy(), o["scale"])
 
 
-def test_w8a16_channelwise(dev, oracle):
-    K, n_samples, T = 256, 4, 128
-    kw = dict(num_bits=8, symmetric=True, group_size=None, strategy="channel")
-    xb, Wf, res, keep, Gfull, n = _run(dev, oracle, [64], K, n_samples, T, kw, None, seed=9)
+def _run_w8(dev, oracle, R_list, K, n_samples, T, sym, actorder, dtype, seed):
+    """``_run`` for the 8-bit channel-wise cases: weights and activations in ``dtype`` (bf16 or fp16).  The Gram
+    kernel takes K % 8 == 0 only; for another K (1100) the accumulator is handed an fp32 Gram product through its
+    ``G`` setter -- everything from ``hessian_prepare`` on, which is what these cases are about, runs unchanged."""
+    from quantool_amd.engine.gptq_linear import HessianAccumulator, gptq_quantize_shared
+    from quantool_amd.engine.schemes import QuantArgs
+
+    xb = synth_activations(n_samples * T, K, seed=seed)
+    X = bits_to_bf16_tensor(xb, dev).to(dtype).reshape(n_samples, T, K)
+    Ws = [torch.from_numpy(synth_weight(R, K, seed=seed + 10 + i)).to(dev).to(dtype) for i, R in enumerate(R_list)]
+    Wf = [w.float().cpu().numpy() for w in Ws]
+    acc = HessianAccumulator(K, dev)
+    if K % 8 == 0:
+        for b in range(n_samples):
+            acc.add(X[b:b + 1])
+    else:
+        X2 = X.reshape(-1, K).float()
+        acc.G = torch.tril(X2.t() @ X2).contiguous()
+        acc.n = n_samples
+    qa = QuantArgs(num_bits=8, symmetric=sym, group_size=None, strategy="channel", actorder=actorder)
+    keep = {}
+    res = gptq_quantize_shared(Ws, acc, qa, keep=keep)
+    torch.cuda.synchronize()
+    Gl = np.tril(acc.G.cpu().numpy())
+    return Wf, res, keep, Gl + np.tril(Gl, -1).T, acc.n
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("R_list", [[64], [200, 72]], ids=["r64", "r200+72"])
+@pytest.mark.parametrize("K", [256, 1100])
+@pytest.mark.parametrize("sym", [True, False], ids=["sym", "asym"])
+@pytest.mark.parametrize("actorder", [None, "static", "group"])
+def test_w8a16_channelwise(dev, oracle, actorder, sym, K, R_list, dtype):
+    """The 8-bit channel-wise path (W8A16 / W8A8 / INT8) end to end against the oracle given the GPU's factor:
+    K = 1100 has far updates and a ragged last block, two Linears share one Hessian (272 stacked rows), the
+    un-permuting ``weight_q`` gather runs under both activation orderings, zero points travel as int8."""
+    n_samples = 4
+    T = 128 if K == 256 else 576          # 2 K tokens and more: a well-conditioned Hessian
+    Wf, res, keep, Gfull, n = _run_w8(dev, oracle, R_list, K, n_samples, T, sym, actorder, dtype, seed=9)
     H = oracle.hessian_from_gram_f32(Gfull, n)
-    o = oracle.quantize_weight(Wf[0], H, group_size=-1, symmetric=True, num_bits=8, actorder=None,
-                               U_override=keep["U"].cpu().numpy())
-    assert res[0].weight_packed is None
-    np.testing.assert_array_equal(res[0].weight_q.cpu().numpy(), o["q"])
+    U_gpu = keep["U"].cpu().numpy()
+    for w, r in zip(Wf, res):
+        o = oracle.quantize_weight(w, H, group_size=-1, symmetric=sym, num_bits=8, actorder=actorder, U_override=U_gpu)
+        if actorder is not None:
+            assert np.array_equal(keep["perm"].cpu().numpy(), o["perm"].astype(np.int32))
+        np.testing.assert_array_equal(r.scale_f32.cpu().numpy(), o["scale"])
+        np.testing.assert_array_equal(r.zp_f32.cpu().numpy(), o["zp"])
+        assert r.weight_packed is None
+        assert r.weight_q.dtype == torch.int8
+        np.testing.assert_array_equal(r.weight_q.cpu().numpy(), o["q"])
+        assert o["q"].min() == -128 and o["q"].max() == 127          # the clamp and the int8 cast are reached
+        if sym:
+            assert r.weight_zero_point is None
+        else:
+            assert r.weight_zero_point.dtype == torch.int8
+            np.testing.assert_array_equal(r.weight_zero_point.cpu().numpy(), o["zp"].astype(np.int8))
+            np.testing.assert_array_equal(r.weight_zero_point.cpu().numpy().astype(np.float32), o["zp"])
+        if actorder == "group":
+            np.testing.assert_array_equal(r.weight_g_idx.cpu().numpy(), o["g_idx"])
+        else:
+            assert r.weight_g_idx is None
+        np.testing.assert_array_equal(r.dequantized().cpu().numpy(), o["w_dq"])
+        assert r.weight_scale.dtype == dtype
+        assert int(r.info.item()) == 0
 
 
 def test_non_pd_hessian_falls_back_to_rtn(dev, oracle):

@@ -127,6 +127,36 @@ def test_c_and_numpy_sweeps_agree_across_blocks(oracle):
             assert np.array_equal(a["w_dq"], b["w_dq"])
 
 
+@pytest.mark.parametrize("num_bits", [2, 3, 8])
+@pytest.mark.parametrize("sym", [True, False])
+@pytest.mark.parametrize("gs", [56, -1])
+def test_c_and_numpy_sweeps_agree_at_other_widths(oracle, num_bits, sym, gs):
+    """The yardstick of the GPU sweep tests at the widths besides 4: the C sweep and the independent numpy one, bit
+    for bit, over a far update and a ragged last block (392 = 3 * 128 + 8), grouped (7 groups of 56) and
+    channel-wise, with a permuted g_idx.  At 8 bits the levels span [-128, 127]: the clamp and the int8 cast."""
+    from tests.util import synth_activations, synth_weight
+
+    R, K = 70, 392
+    W = synth_weight(R, K, seed=num_bits)
+    H = oracle.hessian_from_gram(oracle.gram_f64(synth_activations(2 * K, K, seed=num_bits + 1)), 4)
+    Hd, _, _ = oracle.hessian_dead_and_damp(H)
+    U = oracle.cholesky_inverse_upper_f64(Hd).astype(np.float32)
+    scale, zp = oracle.minmax_qparams(W, gs, sym, num_bits)
+    g_idx = (np.arange(K) // (K if gs <= 0 else gs)).astype(np.int32)[np.random.default_rng(0).permutation(K)]
+    Qc, Wc, lc = oracle.gptq_sweep_c(W, U, scale, zp, g_idx, 128, num_bits)
+    Qn, Wn, ln = oracle.gptq_sweep_numpy(W, U, scale, zp, g_idx, 128, num_bits)
+    assert np.array_equal(Qc, Qn)
+    assert np.array_equal(Wc, Wn)
+    np.testing.assert_allclose(lc, ln, rtol=1e-6)
+    qmin, qmax = oracle.calculate_range(num_bits)
+    assert Qc.min() >= qmin and Qc.max() <= qmax
+    if num_bits in (2, 8):
+        assert Qc.min() == qmin and Qc.max() == qmax
+    # error feedback at work: the swept levels are not plain round-to-nearest
+    q_rtn, _ = oracle.fake_quantize(W, scale[:, g_idx], zp[:, g_idx], num_bits)
+    assert (q_rtn.astype(np.int8) != Qc).mean() > 0.05
+
+
 def test_actorder_semantics(oracle):
     rng = np.random.default_rng(5)
     K = 256
