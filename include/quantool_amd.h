@@ -304,13 +304,26 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   t_g  = (float)(acc_g - zp_x[m] * wsum[n, g])                 int32 difference, one rounding to fp32
  *   tot  = 0.0f;  tot = tot + s_w[n, g] * t_g  for g = 0, 1, ... ascending (product and sum rounded separately)
  *   y    = s_x[m] * tot;  y = y + (float)bias[n]  (when bias is given)
- *   Y[m, n] = y rounded once to out_dtype (round to nearest even) */
+ *   Y[m, n] = y rounded once to out_dtype (round to nearest even)
+ *
+ * qt_gemm_i8_skinny: the decode form of qt_gemm_i8, 1 <= M <= 16 (any other M is QT_ERR_INVALID before any launch).
+ *   Same arguments, same meanings, same refusals, and for every legal input Y is bit-identical to qt_gemm_i8's on the
+ *   same arguments: both weight formats, G = 1 and G = ceil(K/128), with and without zp_x / wsum and bias, bf16 and fp16
+ *   output, ragged K, N not a multiple of 16, operands not 16-byte aligned, K <= 32768.  A workgroup owns 16 output
+ *   columns and splits K over its 4 waves (128-column k-block kb to wave kb % 4), the weights go from global memory
+ *   straight to registers and are read once, v_mfma_i32_16x16x64_i8 with M padded to 16.  The sequence above is integer
+ *   up to t_g, so acc_g does not depend on how K was split; the waves hand their acc_g over as int32 through LDS and one
+ *   thread per output element runs the chain t_g -> tot -> y literally, g ascending.  No wave ever holds an fp32
+ *   partial.  Deterministic, no atomics, no workspace.   */
 enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
 int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
                           int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
 int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_gemm_i8_skinny(const int8_t* Xq, int M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                      const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                      int out_dtype, int64_t ldy, qt_stream_t stream);
 
 /* ---- Routed experts: W8A8 / INT8 / W4A8 sparse-MoE banks on the same int8 GEMM ------------------------------
  * The A8 expert forward (engine/qlinear.py QuantizedExperts) restates transformers' MixtralExperts.forward with the
@@ -338,6 +351,14 @@ int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format,
  *   and the same fixed fp32 epilogue.  The grid is (ceil(R/128) + E) m-tiles x n-tiles, an upper bound that needs no
  *   host read of the counts; each workgroup finds its expert from offsets and surplus workgroups exit.  No bias.
  *
+ * qt_gemm_i8_skinny_grouped: the decode form of qt_gemm_i8_grouped: same arguments, same meanings, same refusals, and Y
+ *   bit-identical to qt_gemm_i8_grouped's on the same arguments (rows past offsets[E] are not written).  It is
+ *   qt_gemm_i8_skinny's tile over E weight matrices: every expert's rows go in tiles of 16, the grid is ceil(N/16)
+ *   column tiles x (floor(R/16) + min(E, R)) row-tile slots, an upper bound on sum_e ceil(rows_e / 16) that needs no
+ *   host read of offsets; a workgroup finds its expert and tile by walking the clamped offsets and a surplus one exits
+ *   before any weight load.  Only the experts that own rows have their weights read, each once per 16 of its rows, so
+ *   this is the form for a few tokens.  R / 16 + min(E, R) <= 65535, else QT_ERR_INVALID.  Deterministic, no atomics.
+ *
  * qt_moe_combine: out [T, H] (dtype bf16 / fp16) = the weighted sum of each token's routed rows of Y [R, H] (pitch
  *   ldy), transformers' MixtralExperts.forward restated: for the token's rows r = row_of[t k + j] >= 0 in ascending
  *   row order (= ascending expert), with w = weights[t, j] fp32 [T, k]:
@@ -348,6 +369,10 @@ int qt_moe_route(const void* top_k_index, int index_is_int64, int64_t T, int k, 
 int qt_gemm_i8_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets, int E,
                        const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x, const float* s_w,
                        int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_gemm_i8_skinny_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets,
+                              int E, const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
+                              const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
+                              qt_stream_t stream);
 int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
                    int64_t T, int k, void* out, qt_stream_t stream);
 

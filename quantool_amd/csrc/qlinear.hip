@@ -5,12 +5,14 @@
 // qt_gemm_i8              128 x 128 output tile per 4-wave workgroup, k-step 128 (= the weight group), register-staged
 //                         single LDS buffer (A and B, 144-B rows: 36 KB); each wave owns 64 x 64 = 2 x 2 MFMA tiles.
 //                         Packed int4 weights are unpacked to int8 between the global load and the LDS store.
+// (decode sizes, 1 <= M <= 16: qlinear_skinny.hip, equal to qt_gemm_i8 to the bit)
 //
 // Numerics are the header's fixed sequence; -ffp-contract=off (csrc/build.py) keeps every multiply and add its own
 // rounding, so a torch restatement of the same steps is equal to the bit.
 #include <float.h>
 
 #include "common.h"
+#include "i8_unpack.h"
 
 namespace {
 
@@ -130,20 +132,6 @@ constexpr int GROUP_M = 16;                 // m-tiles that walk the n-tiles tog
 constexpr int A_CHUNKS = BM * BK / 16 / QT_THREADS;        // 16-byte chunks of the A tile per thread: 4
 constexpr int B8_CHUNKS = BN * BK / 16 / QT_THREADS;       // int8 weights: 4
 constexpr int B4_CHUNKS = BN * BK / 2 / 16 / QT_THREADS;   // packed int4 weights (64 B per row per k-step): 2
-
-// packed word (nibble j = level + 8 of column 8w + j) -> 8 int8 levels, column order
-__device__ __forceinline__ uint2 unpack_int4_word(unsigned w) {
-    const unsigned lo = w & 0x0f0f0f0fu;          // nibbles 0, 2, 4, 6 in bytes 0..3
-    const unsigned hi = (w >> 4) & 0x0f0f0f0fu;   // nibbles 1, 3, 5, 7
-    // interleave: bytes [lo0 hi0 lo1 hi1] and [lo2 hi2 lo3 hi3] (v_perm_b32: selector byte i picks from {hi:lo}
-    // of the first / second operand: 0..3 -> second operand's bytes, 4..7 -> first operand's)
-    unsigned a = __builtin_amdgcn_perm(hi, lo, 0x05010400u);
-    unsigned b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
-    // x - 8 per byte for x in 0..15 without borrows: (x + 0x78) ^ 0x80
-    a = (a + 0x78787878u) ^ 0x80808080u;
-    b = (b + 0x78787878u) ^ 0x80808080u;
-    return make_uint2(a, b);
-}
 
 // One 16-byte chunk of a K-contiguous int8 row [k, k + 16), zero beyond K / beyond the matrix.
 template <bool VEC>

@@ -5,7 +5,8 @@ Linear either
 
 * a ``QuantizedLinear`` (W8A8 / INT8 / W4A8: the checkpoint's 8-bit dynamic per-token ``input_activations`` block):
   activations are quantised per row on the fly and multiplied with the stored integer weights on the int8 MFMA
-  (``qt_quantize_tokens_i8`` + ``qt_gemm_i8``, include/quantool_amd.h), as a served W8A8 runtime does; or
+  (``qt_quantize_tokens_i8`` + ``qt_gemm_i8``, or its bit-identical decode form ``qt_gemm_i8_skinny`` for up to
+  ``skinny_max_m`` rows; include/quantool_amd.h), as a served W8A8 runtime does; or
 * a plain ``nn.Linear`` holding the dequantised weight ``(q - zp) * scale`` (W4A16, W4A16_ASYM, W8A16), computed once in
   fp32 from the STORED scale and rounded once to the model dtype (the default, ``a16="dequantized"``); or
 * with ``a16="packed"``, a ``WeightOnlyLinear`` that keeps the stored integer weights on the device: decode-sized inputs
@@ -19,7 +20,7 @@ down_proj``).  The loader inverts that write: A16 experts are dequantised into t
 (``gate_up_proj[e] = cat(w1, w3)``, ``down_proj[e] = w2``), or with ``a16_experts="packed"`` replace the bank with a
 ``WeightOnlyExperts`` on the stored integer weights (``qt_gemm_wq_grouped`` at decode); A8 experts replace the bank with
 a ``QuantizedExperts`` that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` +
-``qt_moe_combine``).
+``qt_moe_combine``; ``qt_gemm_i8_skinny_grouped`` in place of the GEMM for up to ``grouped_max_tokens`` tokens).
 
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
 weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,

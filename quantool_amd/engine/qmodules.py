@@ -25,7 +25,14 @@ class QuantizedLinear(nn.Module):
 
     Buffers: ``weight`` int8 [N, K] or packed int4 int32 [N, ceil(K/8)] (columns permuted by ``col_perm`` when the
     checkpoint used actorder ``group``), ``weight_scale`` fp32 [N, G], ``wsum`` int32 [N, G], ``col_perm`` int32 [K]
-    (optional), ``bias`` (optional, model dtype)."""
+    (optional), ``bias`` (optional, model dtype).
+
+    M = rows of ``x``: 1 <= M <= ``skinny_max_m`` runs the decode form ``qt_gemm_i8_skinny`` (the weights read once, 16
+    output columns per workgroup), larger M the 128 x 128-tile ``qt_gemm_i8``.  The two agree to the bit, so the
+    attribute changes speed alone; 0 sends every M to the tiled kernel."""
+
+    # Decode GEMV up to this many rows: the measured crossover (DESIGN.md 4.11).
+    skinny_max_m = 16
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -53,8 +60,10 @@ class QuantizedLinear(nn.Module):
         Xq, s_x, zp_x = ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric,
                                                col_perm=self.col_perm)
         bias = None if self.bias is None else self.bias.to(x.dtype)
-        y = ops.gemm_i8(Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
-                        wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
+        skinny = 1 <= Xq.shape[0] <= min(self.skinny_max_m, ops.I8_SKINNY_MAX_M)
+        y = (ops.gemm_i8_skinny if skinny else ops.gemm_i8)(
+            Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
+            wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
         return y.reshape(*x.shape[:-1], self.out_features)
 
 
@@ -129,7 +138,7 @@ class _RoutedExperts(nn.Module):
     replaced: ``qt_moe_route`` orders the routed rows by expert, the gate_up product gathers them by token,
     ``act_fn(gate) * up`` runs in torch as the fused module does, the down product reads the routed rows in place and
     ``qt_moe_combine`` sums each token's weighted rows in ascending expert order, rounding as ``index_add_`` does.
-    Nothing waits on the host.  A subclass gives the product: ``_product(part, x, offsets, row_idx)``, rows
+    Nothing waits on the host.  A subclass gives the product: ``_product(part, x, offsets, row_idx, tokens)``, rows
     ``x[row_idx]`` (or ``x``) times the ``part`` ("gate_up" / "down") weights of the expert that owns each row."""
 
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
@@ -137,8 +146,9 @@ class _RoutedExperts(nn.Module):
 
         x = _rows(hidden_states, self.hidden_dim)
         offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
-        gate, up = self._product("gate_up", x, offsets, src_token).chunk(2, dim=-1)
-        y = self._product("down", self.act_fn(gate) * up, offsets, None)
+        T = x.shape[0]
+        gate, up = self._product("gate_up", x, offsets, src_token, T).chunk(2, dim=-1)
+        y = self._product("down", self.act_fn(gate) * up, offsets, None, T)
         return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
 
 
@@ -150,7 +160,14 @@ class QuantizedExperts(_RoutedExperts):
 
     Buffers: ``gate_up`` int8 [E, 2I, H] or packed int4 int32 [E, 2I, ceil(H/8)] (rows [0, I) gate, [I, 2I) up),
     ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_wsum`` int32 [E, 2I, G]; ``down`` int8 [E, H, I] or int32
-    [E, H, ceil(I/8)], ``down_scale`` fp32 [E, H, G'], ``down_wsum`` int32 [E, H, G']."""
+    [E, H, ceil(I/8)], ``down_scale`` fp32 [E, H, G'], ``down_wsum`` int32 [E, H, G'].
+
+    With T = rows of ``hidden_states`` (known on the host) and 1 <= T <= ``grouped_max_tokens`` both products run the
+    decode form ``qt_gemm_i8_skinny_grouped`` (16-row tiles, only the experts that were hit are read), otherwise the
+    128-row-tile ``qt_gemm_i8_grouped``.  The two agree to the bit; 0 sends every T to the tiled kernel."""
+
+    # Decode form up to this many tokens: the measured crossover at Mixtral-8x7B's bank shapes (DESIGN.md 4.11).
+    grouped_max_tokens = 16
 
     def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
                  down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
@@ -173,13 +190,15 @@ class QuantizedExperts(_RoutedExperts):
                 f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
                 f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token")
 
-    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor]):
+    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor],
+                 tokens: int):
         from ..hip import ops
 
         Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=self.act_symmetric)
-        return ops.gemm_i8_grouped(Xq, s_x, getattr(self, part), getattr(self, f"{part}_scale"), offsets,
-                                   row_idx=row_idx, K=x.shape[1], zp_x=zp_x,
-                                   wsum=None if zp_x is None else getattr(self, f"{part}_wsum"), out_dtype=x.dtype)
+        gemm = ops.gemm_i8_skinny_grouped if 1 <= tokens <= self.grouped_max_tokens else ops.gemm_i8_grouped
+        return gemm(Xq, s_x, getattr(self, part), getattr(self, f"{part}_scale"), offsets, row_idx=row_idx,
+                    K=x.shape[1], zp_x=zp_x, wsum=None if zp_x is None else getattr(self, f"{part}_wsum"),
+                    out_dtype=x.dtype)
 
 
 class WeightOnlyExperts(_RoutedExperts):
@@ -259,7 +278,8 @@ class WeightOnlyExperts(_RoutedExperts):
                                       else w.zero_point[e], g_idx=w.g_idx[e], dtype=dtype, out=out[e])
         return out
 
-    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor]):
+    def _product(self, part: str, x: torch.Tensor, offsets: torch.Tensor, row_idx: Optional[torch.Tensor],
+                 tokens: int):
         from ..hip import ops
 
         w = self.stored(part)

@@ -95,6 +95,11 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "qt_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "qt_gemm_i8_skinny": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "qt_gemm_i8_skinny_grouped": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64,
+                                          c_void_p]),
     "qt_moe_route": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p]),
     "qt_gemm_i8_grouped": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,

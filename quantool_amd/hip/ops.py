@@ -570,6 +570,31 @@ def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Te
     return Y
 
 
+I8_SKINNY_MAX_M = 16   # rows of Xq qt_gemm_i8_skinny takes
+
+
+def gemm_i8_skinny(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                   K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                   wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                   out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8`` for 1 <= M <= 16 rows (``qt_gemm_i8_skinny``): the decode GEMV.  Same arguments; Y equals
+    ``gemm_i8``'s to the bit."""
+    M = Xq.shape[0] if Xq.dim() == 2 else -1
+    if not 1 <= M <= I8_SKINNY_MAX_M:
+        raise ValueError(f"gemm_i8_skinny takes 1 <= M <= {I8_SKINNY_MAX_M} rows, got Xq {tuple(Xq.shape)}")
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8_skinny", lib.qt_gemm_i8_skinny(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
 def moe_route(top_k_index: torch.Tensor, num_experts: int):
     """top_k_index [T, k] int32 / int64 -> (offsets int32 [E+1], src_token int32 [T k], src_slot int32 [T k],
     row_of int32 [T k]): ``qt_moe_route`` (include/quantool_amd.h).  Rows sorted by expert, then by token; an index
@@ -593,15 +618,8 @@ def moe_route(top_k_index: torch.Tensor, num_experts: int):
     return offsets, src_token, src_slot, row_of
 
 
-def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor,
-                    *, rows: Optional[int] = None, row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
-                    zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
-                    out_dtype=torch.bfloat16) -> torch.Tensor:
-    """``qt_gemm_i8`` over E weight matrices: Y [R, N], expert e owning rows [offsets[e], offsets[e+1]) (include/
-    quantool_amd.h qt_gemm_i8_grouped).  Wq int8 [E, N, K] or packed int4 int32 [E, N, ceil(K/8)] (then ``K`` is
-    required); s_w fp32 [E, N, G]; wsum int32 [E, N, G] (needed with zp_x).  A rows: Xq[row_idx[m]] when ``row_idx``
-    (int32 [R], e.g. ``moe_route``'s src_token) is given, with s_x / zp_x read at the same index; else Xq[m] (then R
-    defaults to Xq's rows).  Rows past offsets[E] are left unwritten."""
+def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype) -> torch.Tensor:
+    """The operand checks and the call both grouped int8 GEMMs share; ``fn`` names the entry point."""
     lib = load()
     fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype, experts=True)
     Mx, E = Xq.shape[0], Wq.shape[0]
@@ -622,10 +640,34 @@ def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
     if R <= 0:
         raise ValueError(f"rows must be positive, got {R}")
     Y = torch.empty((R, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8_grouped", lib.qt_gemm_i8_grouped(
+    check(fn, getattr(lib, fn)(
         Xq.data_ptr(), K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x),
         s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
     return Y
+
+
+def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor,
+                    *, rows: Optional[int] = None, row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                    zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                    out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``qt_gemm_i8`` over E weight matrices: Y [R, N], expert e owning rows [offsets[e], offsets[e+1]) (include/
+    quantool_amd.h qt_gemm_i8_grouped).  Wq int8 [E, N, K] or packed int4 int32 [E, N, ceil(K/8)] (then ``K`` is
+    required); s_w fp32 [E, N, G]; wsum int32 [E, N, G] (needed with zp_x).  A rows: Xq[row_idx[m]] when ``row_idx``
+    (int32 [R], e.g. ``moe_route``'s src_token) is given, with s_x / zp_x read at the same index; else Xq[m] (then R
+    defaults to Xq's rows).  Rows past offsets[E] are left unwritten."""
+    return _gemm_i8_grouped("qt_gemm_i8_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
+
+
+def gemm_i8_skinny_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                           offsets: torch.Tensor, *, rows: Optional[int] = None,
+                           row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                           zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                           out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8_grouped`` on the decode tile (``qt_gemm_i8_skinny_grouped``): every expert's rows in tiles of 16, only
+    the experts that own rows read, each once per tile.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit.
+    R // 16 + min(E, R) row-tile slots must fit a grid dimension (65535)."""
+    return _gemm_i8_grouped("qt_gemm_i8_skinny_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
+                            out_dtype)
 
 
 def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:

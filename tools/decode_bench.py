@@ -16,6 +16,14 @@ the write and the three loads short).  Every expert's gate / up / down and the a
 way and written per expert through ``expert_bank_checkpoint_names`` (``block_sparse_moe.experts.{e}.w1 / w3 / w2``).
 Modes ``dequantized``, ``packed`` (``a16="packed"``: the banks stay dense bf16) and ``packed_experts`` (``a16="packed",
 a16_experts="packed"``: ``WeightOnlyExperts``); each mode also reports the resident bytes of the expert banks.
+
+  python tools/decode_bench.py <checkpoint dir> --scheme W8A8 [--model mixtral --layers 8]      # or --scheme W4A8
+
+An A8 checkpoint instead (W8A8: int8 levels, one scale per row = absmax / 127.5, symmetric activations; W4A8: int4
+g128 with asymmetric activations; both round-to-nearest), loaded once and decoded in two modes in the same process:
+``a8_tiled`` (``QuantizedLinear.skinny_max_m`` and ``QuantizedExperts.grouped_max_tokens`` set to 0: every Linear on
+the 128 x 128-tile ``qt_gemm_i8``) and ``a8_skinny`` (the class defaults: the decode GEMV).  The two compute the same
+bits, so ``tokens_agree`` must equal --new.
 """
 from __future__ import annotations
 
@@ -38,16 +46,32 @@ LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_att
            "mlp.up_proj", "mlp.down_proj")
 
 
-def _rtn(W: torch.Tensor):
-    """Round-to-nearest int4 g128 of W [N, K]: (packed int32 [N, K/8], bf16 scales [N, K/128]) on the CPU."""
+def _rtn(W: torch.Tensor, scheme: str = "W4A16"):
+    """Round-to-nearest int4 g128 of W [N, K]: (packed int32 [N, K/8], bf16 scales [N, K/128]) on the CPU; for W8A8,
+    int8 levels [N, K] and one scale per row."""
     W = W.float()
     N, K = W.shape
+    if scheme == "W8A8":
+        s = (W.abs().amax(-1, keepdim=True) / 127.5).clamp(min=1e-8).to(torch.bfloat16)
+        return torch.round(W / s.float()).clamp(-128, 127).to(torch.int8).cpu(), s.cpu()
     s = (W.reshape(N, K // 128, 128).abs().amax(-1) / 7.5).clamp(min=1e-8).to(torch.bfloat16)
     q = torch.round(W.reshape(N, K // 128, 128) / s.float()[..., None]).clamp(-8, 7).reshape(N, K).to(torch.int8)
     return pack_int4(q).cpu(), s.cpu()
 
 
-def write_mixtral_checkpoint(path: Path, layers: int, dev) -> None:
+def _leaves(state: dict, pre: str, W: torch.Tensor, scheme: str) -> None:
+    q, s = _rtn(W, scheme)
+    state[f"{pre}.weight" if scheme == "W8A8" else f"{pre}.weight_packed"], state[f"{pre}.weight_scale"] = q, s
+    state[f"{pre}.weight_shape"] = torch.tensor(list(W.shape))
+
+
+def _qconfig(scheme: str, ignore):
+    wa = PRESET_SCHEMES[scheme]
+    acts = None if wa.input_activations is None else wa.input_activations.to_config()
+    return quantization_config(wa.weights.to_config(), wa.format, ignore, acts)
+
+
+def write_mixtral_checkpoint(path: Path, layers: int, dev, scheme: str = "W4A16") -> None:
     from transformers import MixtralConfig, MixtralForCausalLM
 
     from quantool_amd.engine.sequential import expert_bank_checkpoint_names
@@ -66,26 +90,19 @@ def write_mixtral_checkpoint(path: Path, layers: int, dev) -> None:
         if mod in banks:                                   # the fused bank, per expert as the save path holds it
             proj = leaf
             for e in range(v.shape[0]):
-                packed, s = _rtn(v[e])
-                pre = f"{mod}.experts.{e}.{proj}"
-                state[f"{pre}.weight_packed"], state[f"{pre}.weight_scale"] = packed, s
-                state[f"{pre}.weight_shape"] = torch.tensor(list(v[e].shape))
+                _leaves(state, f"{mod}.experts.{e}.{proj}", v[e], scheme)
         elif mod in attn:
-            packed, s = _rtn(v)
-            state[f"{mod}.weight_packed"], state[f"{mod}.weight_scale"] = packed, s
-            state[f"{mod}.weight_shape"] = torch.tensor(list(v.shape))
+            _leaves(state, mod, v, scheme)
         else:
             state[k] = v.cpu()
     state = expert_bank_checkpoint_names(state, banks, "mixtral")
-    wa = PRESET_SCHEMES["W4A16"]
     ignore = ["lm_head"] + [f"model.layers.{i}.block_sparse_moe.gate" for i in range(layers)]
-    qcfg = quantization_config(wa.weights.to_config(), wa.format, ignore, None)
-    save_state(state, qcfg, path, model.config.to_dict())
+    save_state(state, _qconfig(scheme, ignore), path, model.config.to_dict())
     del model, state
     torch.cuda.empty_cache()
 
 
-def write_checkpoint(path: Path, layers: int, dev) -> None:
+def write_checkpoint(path: Path, layers: int, dev, scheme: str = "W4A16") -> None:
     from transformers import LlamaConfig, LlamaForCausalLM
 
     cfg = LlamaConfig(hidden_size=4096, intermediate_size=14336, num_hidden_layers=layers, num_attention_heads=32,
@@ -101,11 +118,8 @@ def write_checkpoint(path: Path, layers: int, dev) -> None:
         if mod not in quantized:
             state[k] = v.cpu()
             continue
-        state[f"{mod}.weight_packed"], state[f"{mod}.weight_scale"] = _rtn(v)
-        state[f"{mod}.weight_shape"] = torch.tensor(list(v.shape))
-    wa = PRESET_SCHEMES["W4A16"]
-    qcfg = quantization_config(wa.weights.to_config(), wa.format, ["lm_head"], None)
-    save_state(state, qcfg, path, model.config.to_dict())
+        _leaves(state, mod, v, scheme)
+    save_state(state, _qconfig(scheme, ["lm_head"]), path, model.config.to_dict())
     del model, state
     torch.cuda.empty_cache()
 
@@ -129,6 +143,31 @@ def decode(model, prompt: torch.Tensor, new: int):
     return torch.cat(toks, 1)[0].tolist(), (t1 - t0) / max(new - 1, 1)
 
 
+def a8_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """One loaded A8 model decoded as ``a8_tiled`` (class attributes 0) and ``a8_skinny`` (their defaults)."""
+    from quantool_amd.engine.qlinear import QuantizedExperts, QuantizedLinear
+
+    model = load_quantized(path, device=dev)
+    defaults = (QuantizedLinear.skinny_max_m, QuantizedExperts.grouped_max_tokens)
+    result["skinny_max_m"], result["grouped_max_tokens"] = defaults
+    result["quantized_linears"] = sum(isinstance(m, QuantizedLinear) for m in model.modules())
+    result["quantized_expert_banks"] = sum(isinstance(m, QuantizedExperts) for m in model.modules())
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, (a, b) in (("a8_tiled", (0, 0)), ("a8_skinny", defaults)):
+            QuantizedLinear.skinny_max_m, QuantizedExperts.grouped_max_tokens = a, b
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_token": []})["ms_per_token"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    QuantizedLinear.skinny_max_m, QuantizedExperts.grouped_max_tokens = defaults
+    same = [x == y for x, y in zip(tokens["a8_tiled"], tokens["a8_skinny"])]
+    result["tokens_agree"] = sum(same)
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_token"]) for m in ("a8_tiled", "a8_skinny"))
+    result["speedup"] = round(t / k, 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint")
@@ -136,6 +175,8 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--model", default="llama", choices=["llama", "mixtral"])
+    ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
+                    help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--modes", default=None,
                     help="default: dequantized,packed (llama) / dequantized,packed,packed_experts (mixtral)")
     args = ap.parse_args()
@@ -148,10 +189,14 @@ def main():
     path = Path(args.checkpoint)
     if not (path / "config.json").exists():
         path.mkdir(parents=True, exist_ok=True)
-        (write_mixtral_checkpoint if mixtral else write_checkpoint)(path, args.layers, dev)
+        (write_mixtral_checkpoint if mixtral else write_checkpoint)(path, args.layers, dev, args.scheme)
     prompt = torch.randint(0, vocab, (1, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
-              "new": args.new, "modes": {}}
+              "new": args.new, "scheme": args.scheme, "layers": args.layers, "modes": {}}
+    if args.scheme != "W4A16":
+        a8_modes(path, dev, prompt, args.new, result)
+        print(json.dumps(result))
+        return
     tokens = {}
     for mode in modes:
         torch.cuda.empty_cache()

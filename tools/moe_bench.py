@@ -28,6 +28,13 @@ weights of a ``WeightOnlyExperts``), every time from cold weights (each call rea
   hf_bf16        transformers' MixtralExperts.forward in bf16
 
 with grouped_tbs = bytes of the hit experts' weights, scales and zero-points / grouped time.  Prints one JSON line.
+
+  python tools/moe_bench.py --decode-tokens 1,8,16,32,64,128 [--schemes W8A8,W4A8]
+
+The A8 decode comparison: the GEMM pair (gate_up gathered by token, then down) as qt_gemm_i8_grouped and as
+qt_gemm_i8_skinny_grouped on the same operands, alternating call by call in one loop, each pair between its own HIP
+events, the two forms reading different copies of the bank in a rep (a bank is 0.7 / 1.4 GB, so every call reads its
+hit experts cold).  Reported per form: median microseconds and the hit experts' weight + scale (+ wsum) bytes over it.
 """
 from __future__ import annotations
 
@@ -175,9 +182,50 @@ def _bench_a16(scheme, T, x, idx, w, banks, hf, args):
             "dequant_over_experts": round(t["dequant"] / t["experts"], 3)}
 
 
+def _bench_a8_decode(scheme, T, banks, dev, g, args):
+    """One decode row: both grouped forms of the GEMM pair on the same routing and rows, cold banks."""
+    from qlinear_bench import summarize, time_pair
+
+    qe = banks[0]
+    sym = qe.act_symmetric
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    _, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=sym)
+
+    def pair(gemm, b, h=None):
+        gu = gemm(Xq, s_x, b.gate_up, b.gate_up_scale, offsets, row_idx=src_token, K=H, zp_x=zp_x,
+                  wsum=None if sym else b.gate_up_wsum)
+        if h is None:
+            gate, up = gu.chunk(2, dim=-1)
+            return ops.quantize_tokens_i8(b.act_fn(gate) * up, symmetric=sym)
+        return gemm(h[0], h[1], b.down, b.down_scale, offsets, K=I, zp_x=h[2], wsum=None if sym else b.down_wsum)
+
+    with torch.no_grad():
+        h = pair(ops.gemm_i8_grouped, qe)
+        n = len(banks)
+        t = time_pair({"tiled": lambda i: pair(ops.gemm_i8_grouped, banks[i % n], h),
+                       "skinny": lambda i: pair(ops.gemm_i8_skinny_grouped, banks[(i + 1) % n], h)},
+                      args.reps, args.warmup)
+        same = torch.equal(pair(ops.gemm_i8_grouped, qe, h).view(torch.int16),
+                           pair(ops.gemm_i8_skinny_grouped, qe, h).view(torch.int16))
+    off = offsets.cpu().tolist()
+    hit = [e for e in range(E) if off[e + 1] > off[e]]
+    per_expert = sum(getattr(qe, f"{p}{sfx}")[0].numel() * getattr(qe, f"{p}{sfx}").element_size()
+                     for p in ("gate_up", "down") for sfx in ("", "_scale") + (() if sym else ("_wsum",)))
+    nbytes = per_expert * len(hit)
+    row = {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)], "bits_equal": same,
+           "hit_expert_bytes": nbytes, "tiled": summarize(t["tiled"], nbytes), "skinny": summarize(t["skinny"], nbytes)}
+    row["speedup"] = round(row["tiled"]["us"] / row["skinny"]["us"], 2)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
+    ap.add_argument("--decode-tokens", default="",
+                    help="A8 schemes: compare the two grouped GEMM forms at these token counts instead")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -196,6 +244,21 @@ def main():
     with torch.no_grad():
         hf.gate_up_proj.normal_(0, 0.02, generator=g)
         hf.down_proj.normal_(0, 0.02, generator=g)
+    if args.decode_tokens:
+        for scheme in args.schemes.split(","):
+            if scheme in A16:
+                raise SystemExit("--decode-tokens compares the A8 grouped GEMMs (W8A8 / W4A8)")
+            banks = [_experts(scheme, dev, g) for _ in range(2)]
+            for T in (int(t) for t in args.decode_tokens.split(",")):
+                row = _bench_a8_decode(scheme, T, banks, dev, g, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+            del banks
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A8 decode: qt_gemm_i8_grouped vs qt_gemm_i8_skinny_grouped",
+                          "E": E, "top_k": TOPK, "H": H, "I": I, "device": torch.cuda.get_device_name(0),
+                          "rows": rows}))
+        return
     for scheme in args.schemes.split(","):
         if scheme in A16:
             # copies of the bank > 1.4 GB in all, rotated per call (the int4 bank is 0.7 GB, the int8 one 1.4 GB)

@@ -1,6 +1,8 @@
-"""W8A8 / W4A8 linear on the int8 MFMA vs bf16 F.linear at Llama-3-8B's prefill shapes.
+"""W8A8 / W4A8 linear on the int8 MFMA vs bf16 F.linear at Llama-3-8B's prefill shapes, and the decode GEMV against the
+tiled GEMM at decode sizes.
 
   python tools/qlinear_bench.py [--ms 4096,8192] [--reps 20] [--warmup 5]
+  python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
 
 Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N = 4096, K = 14336) and M: device time
 (HIP events, mean over --reps after --warmup) of the activation pass (qt_quantize_tokens_i8), the GEMM (qt_gemm_i8:
@@ -8,6 +10,12 @@ W8A8 = int8 channel-wise weights, symmetric activations; W4A8 = packed int4 g128
 QuantizedLinear end to end, bf16 F.linear and torch._int_mm (when this torch build runs it; else the reason).
 Prints one JSON line: TOPS (2 M N K / time), the share of the 5 PF int8 dense peak, the activation pass's GB/s and the
 ratio of bf16 F.linear time to the W8A8 / W4A8 QuantizedLinear time (> 1: the quantized linear is faster).
+
+Every M <= 16 in --ms is a decode size and gets a "decode" row instead: qt_gemm_i8 and qt_gemm_i8_skinny on the same
+operands, alternating call by call in one loop, each call between its own pair of HIP events (so host gaps between
+launches are not counted), the weights rotating over distinct copies totalling more than 512 MiB (twice the Infinity
+Cache) so that every call reads them cold, as a decode step does.  Reported per kernel: median and mean microseconds,
+weight + scale (+ wsum) bytes over the median, and that as a share of 8 TB/s.
 """
 from __future__ import annotations
 
@@ -26,6 +34,73 @@ from quantool_amd.hip import ops  # noqa: E402
 
 SHAPES = {"qkv": (6144, 4096), "gate_up": (28672, 4096), "down": (4096, 14336)}
 INT8_PEAK = 5.0e15     # MI355X dense int8 MFMA ops/s (MI355X_MICROARCH.md, Matrix cores: 2x the bf16 rate)
+HBM_PEAK = 8.0e12      # bytes/s
+COLD_BYTES = 512 << 20
+DECODE_MAX_M = ops.I8_SKINNY_MAX_M
+
+
+def time_pair(fns, reps, warmup):
+    """{name: [seconds per call]}: the callables of ``fns`` run in turn, rep by rep (fn(i) with i the call's index), each
+    call between its own pair of events."""
+    names = list(fns)
+    for i in range(warmup):
+        for n in names:
+            fns[n](i)
+    torch.cuda.synchronize()
+    ev = {n: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+          for n in names}
+    for i in range(reps):
+        for n in names:
+            a, b = ev[n][i]
+            a.record()
+            fns[n](warmup + i)
+            b.record()
+    torch.cuda.synchronize()
+    return {n: [a.elapsed_time(b) * 1e-3 for a, b in ev[n]] for n in names}
+
+
+def summarize(times, nbytes):
+    t = sorted(times)
+    med = t[len(t) // 2]
+    return {"us": round(med * 1e6, 2), "mean_us": round(sum(t) / len(t) * 1e6, 2), "min_us": round(t[0] * 1e6, 2),
+            "tbs": round(nbytes / med / 1e12, 3), "hbm_frac": round(nbytes / med / HBM_PEAK, 3)}
+
+
+def decode_rows(shape, N, K, ms, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_gemm_i8_skinny at decode sizes, W8A8 (int8 channel-wise, symmetric activations) and W4A8
+    (packed int4 g128, asymmetric activations), cold weights."""
+    rows = []
+    for scheme in ("W8A8", "W4A8"):
+        int4 = scheme == "W4A8"
+        G = K // 128 if int4 else 1
+        q = torch.randint(-8 if int4 else -128, 8 if int4 else 128, (N, K), device=dev, generator=g, dtype=torch.int8)
+        W0 = pack_int4(q) if int4 else q
+        s0 = torch.rand(N, G, device=dev, generator=g) * 1e-2
+        ws0 = group_sums(q, G) if int4 else None
+        del q
+        nbytes = W0.numel() * W0.element_size() + s0.numel() * 4 + (ws0.numel() * 4 if int4 else 0)
+        n_cp = max(2, -(-int(COLD_BYTES * 1.1) // nbytes))
+        cps = [(W0.clone(), s0.clone(), None if ws0 is None else ws0.clone()) for _ in range(n_cp)]
+        for M in ms:
+            X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            Xq, s_x, zp_x = ops.quantize_tokens_i8(X, symmetric=not int4)
+
+            def call(fn):
+                return lambda i: fn(Xq, s_x, cps[i % n_cp][0], cps[i % n_cp][1], K=K, zp_x=zp_x, wsum=cps[i % n_cp][2])
+
+            # the two kernels must read different copies in one rep, or the second finds the first's weights cached
+            t = time_pair({"gemm_i8": call(ops.gemm_i8), "gemm_i8_skinny": lambda i: call(ops.gemm_i8_skinny)(i + 1)},
+                          reps, warmup)
+            same = torch.equal(call(ops.gemm_i8)(0).view(torch.int16), call(ops.gemm_i8_skinny)(0).view(torch.int16))
+            row = {"shape": shape, "scheme": scheme, "M": M, "N": N, "K": K, "weight_mb": round(nbytes / 1e6, 2),
+                   "cold_copies": n_cp, "bits_equal": same, "gemm_i8": summarize(t["gemm_i8"], nbytes),
+                   "gemm_i8_skinny": summarize(t["gemm_i8_skinny"], nbytes)}
+            row["speedup"] = round(row["gemm_i8"]["us"] / row["gemm_i8_skinny"]["us"], 2)
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr)
+        del cps
+        torch.cuda.empty_cache()
+    return rows
 
 
 def _time(fn, reps, warmup):
@@ -54,8 +129,16 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     rows = []
     int_mm_note = None
+    all_ms = [int(m) for m in args.ms.split(",") if m]
+    decode_ms = [m for m in all_ms if m <= DECODE_MAX_M]
+    large_ms = [m for m in all_ms if m > DECODE_MAX_M]
+    decode = []
     for shape in args.shapes.split(","):
         N, K = SHAPES[shape]
+        if decode_ms:
+            decode += decode_rows(shape, N, K, decode_ms, args.reps, args.warmup, dev, g)
+        if not large_ms:
+            continue
         q8 = torch.randint(-128, 128, (N, K), device=dev, generator=g, dtype=torch.int8)
         q4 = torch.randint(-8, 8, (N, K), device=dev, generator=g, dtype=torch.int8)
         w4 = pack_int4(q4)
@@ -65,7 +148,7 @@ def main():
         lin8 = QuantizedLinear(K, N, q8, s_w1, act_symmetric=True)
         lin4 = QuantizedLinear(K, N, w4, s_wg, act_symmetric=False)
         Wbf = (torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
-        for M in (int(m) for m in args.ms.split(",")):
+        for M in large_ms:
             X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
             Xq, s_x, _ = ops.quantize_tokens_i8(X, symmetric=True)
             Xqa, s_xa, zp_xa = ops.quantize_tokens_i8(X, symmetric=False)
@@ -99,7 +182,8 @@ def main():
         del q8, q4, w4, lin8, lin4, Wbf
         torch.cuda.empty_cache()
     print(json.dumps({"metric": "W8A8 / W4A8 linear vs bf16 F.linear, Llama-3-8B prefill shapes", "int8_peak": INT8_PEAK,
-                      "torch_int_mm": int_mm_note or "runs (timed as torch_int_mm)", "rows": rows}))
+                      "torch_int_mm": int_mm_note or "runs (timed as torch_int_mm)", "rows": rows,
+                      "hbm_peak": HBM_PEAK, "device": torch.cuda.get_device_name(0), "decode": decode}))
 
 
 if __name__ == "__main__":
