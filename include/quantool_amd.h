@@ -314,7 +314,23 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   straight to registers and are read once, v_mfma_i32_16x16x64_i8 with M padded to 16.  The sequence above is integer
  *   up to t_g, so acc_g does not depend on how K was split; the waves hand their acc_g over as int32 through LDS and one
  *   thread per output element runs the chain t_g -> tot -> y literally, g ascending.  No wave ever holds an fp32
- *   partial.  Deterministic, no atomics, no workspace.   */
+ *   partial.  Deterministic, no atomics, no workspace.  
+ *
+ * qt_gemm_i8_ring: the prefill form of qt_gemm_i8 for W8A8 / INT8: w_format == QT_W_INT8 with G == 1 (int8 weights,
+ *   channel-wise scales), K a multiple of QT_I8_RING_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned.  Same arguments,
+ *   same meanings; with and without zp_x / wsum and bias, bf16 and fp16 output, any M >= 1, any N >= 1, any ldy >= N.
+ *   Everything else -- packed int4, G > 1, a ragged K, a misaligned operand -- is QT_ERR_INVALID before any launch, and
+ *   qt_last_error names the reason.  For every legal input Y is bit-identical to qt_gemm_i8's on the same arguments: acc
+ *   is an exact int32 sum, whatever the order, and the chain t -> tot = 0.0f + s_w t -> y above runs literally, once per
+ *   output element, in the lane that holds it.  One 8-wave workgroup per 256 x 256 output tile streams the reduction
+ *   QT_I8_RING_K_UNIT k-bytes (one cache line per row) at a time, as half panels of 128 rows, through a ring of
+ *   QT_I8_RING_SLOTS LDS slots filled by LDS-DMA QT_I8_RING_LEAD half panels ahead (csrc/ring_pipe.h,
+ *   csrc/qlinear_ring.hip), v_mfma_i32_32x32x32_i8.  A tile row past M or N re-reads row M - 1
+ *   or N - 1 and is never stored: no byte outside Xq[M, K] and Wq[N, K] is read, no element outside Y[m < M, n < N] is
+ *   written.  Deterministic, no atomics, no workspace.   */
+#define QT_I8_RING_K_UNIT 128
+#define QT_I8_RING_SLOTS 8
+#define QT_I8_RING_LEAD 6
 enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
 int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
                           int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
@@ -324,6 +340,9 @@ int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format,
 int qt_gemm_i8_skinny(const int8_t* Xq, int M, int K, const void* Wq, int w_format, int N, const float* s_x,
                       const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                       int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                    const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                    int out_dtype, int64_t ldy, qt_stream_t stream);
 
 /* ---- Routed experts: W8A8 / INT8 / W4A8 sparse-MoE banks on the same int8 GEMM ------------------------------
  * The A8 expert forward (engine/qlinear.py QuantizedExperts) restates transformers' MixtralExperts.forward with the

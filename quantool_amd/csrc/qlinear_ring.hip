@@ -1,0 +1,255 @@
+// qt_gemm_i8_ring: the prefill / perplexity form of qt_gemm_i8 for W8A8 / INT8 (int8 weights, channel-wise scales):
+// a 256 x 256 output tile per 8-wave workgroup, the reduction streamed through the LDS-DMA ring of ring_pipe.h.
+// Y is equal to qt_gemm_i8's to the bit (include/quantool_amd.h): the int32 sum is exact and the
+// epilogue below is qlinear.hip's, statement for statement, under the same -ffp-contract=off.
+//
+// THE INSTANCE.  Both operands are K-contiguous, so what a DMA fetches from one row is a run of k-bytes, and a run
+// shorter than a 128-byte cache line is paid for as a whole line every time (measured: the 32-k-byte unit the ring of
+// xtx_kernel translates to, 16 B per lane and row, ran at 0.6 of the tiled kernel).  So the k-unit is 128
+// bytes = one line per row, and what moves through the ring is a HALF PANEL: 128 rows x 128 k-bytes = 16 KiB of A or
+// of B, two LDS-DMA instructions per wave, as a unit of xtx_kernel.  K-tile t (k-bytes [128 t, 128 t + 128)) is the
+// four units 4t .. 4t+3 = A0, B0, B1, A1 (rows 0-127 / 128-255 of the tile's A and B panels), and its four phases
+// 4t .. 4t+3 are the quadrants A0 x B0, A0 x B1, A1 x B0, A1 x B1 of the output tile over that k-range: per wave
+// (2 (M) x 4 (N) waves per quadrant, 64 x 32 outputs each) 2 x 1 MFMA tiles x 4 k-steps = 8 v_mfma_i32_32x32x32_i8,
+// the count of an xtx_kernel phase.  Fragments stay in registers across the phases that share them: phase 4t reads A0
+// and B0 (12 ds_read_b128), 4t+1 B1 (4), 4t+2 A1 (8), 4t+3 nothing.
+//   R 8 slots (slot = unit % 8: two K-tiles), L 6 (unit u+6 is issued in phase u), N 2 per wave.
+//   RAW: unit i is first read in phase i - 1 at the earliest (B0, B1, A1; A0 in phase i), so the counted wait of phase
+//        u leaves only units u+3 .. u+6 in flight: vmcnt(2 * 4 = 8), and unit u+2 is read one phase after the wait
+//        that retired it.  64 KiB per CU in flight.
+//   WAR: unit i is last read in phase i at the latest, and its slot is re-filled by unit i+8, issued in phase i+2:
+//        ring_pipe.h's case L = R - 2.
+// LDS image of a unit: 16 pieces of 1 KiB, piece = 8 rows x 128 B; the 16-byte chunk c of row r (of the half panel) sits
+// at chunk c ^ ((r >> 1) & 7) of its row.  A wave-instruction of the DMA fills one piece lane-linear (the XOR is on the
+// source address); a fragment read (lane l: row l & 31 of its MFMA tile, chunk 2 s + (l >> 5) of k-step s) is one
+// ds_read_b128 whose 16-lane groups each cover all 64 banks once.
+// A tile row past M (or N) is fetched from row M - 1 (N - 1): the source row is clamped, the value is computed and
+// never stored.  K is a whole number of K-tiles, so no byte outside Xq[M, K] and Wq[N, K] is read.
+#include "common.h"
+#include "ring_pipe.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
+
+constexpr int RING = 8;                      // units (half panels) resident in LDS (128 KiB)
+constexpr int LEAD = 6;                      // unit u + LEAD is issued in phase u (LEAD <= RING - 2)
+constexpr int KU = 128;                      // k-bytes per K-tile: one cache line per row and fetch
+constexpr int HP = 128;                      // rows of a half panel
+constexpr int GROUP_M = 32;                  // m-tiles that walk the n-tiles together: workgroups are dealt round-robin
+                                             // over 8 XCDs of 32 CUs, so the 32 tiles resident on one XCD are
+                                             // 4 m-tiles x 8 n-tiles = 12 panels
+static_assert(HP * KU == UNIT_BYTES, "a unit is a half panel of 128 rows x 128 k-bytes");
+static_assert(LEAD <= RING - 2, "ring_pipe.h, WAR");
+
+struct RingArgs {
+    const int8_t* Xq;
+    const int8_t* Wq;
+    const float* s_x;
+    const int32_t* zp_x;
+    const float* s_w;
+    const int32_t* wsum;
+    const void* bias;
+    void* Y;
+    int64_t M;
+    int N, K;
+    int64_t ldy;
+    int out_dtype;
+};
+
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArgs p) {
+    __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_m = wave >> 2, wave_n = wave & 3;
+    const bool group_b = wave >= 4;  // wave-uniform
+
+    // tile order: GROUP_M m-tiles walk the n-tiles together (as gemm_i8_kernel)
+    const int tiles_n = (p.N + BT - 1) / BT;
+    const int tiles_m = (int)((p.M + BT - 1) / BT);
+    const int pid = blockIdx.x;
+    const int per_group = GROUP_M * tiles_n;
+    const int first_m = pid / per_group * GROUP_M;
+    const int gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
+    const int in_g = pid % per_group;
+    const int64_t m0 = (int64_t)(first_m + in_g % gsize) * BT;
+    const int n0 = (in_g / gsize) * BT;
+    const int K = p.K;
+    const int nu = K / KU * 4;                        // units = phases
+
+    // ---- staging geometry: two LDS-DMA instructions per thread per unit (pieces 2 wave, 2 wave + 1) ----
+    // lane: row lane >> 3 of its piece, physical chunk lane & 7; the logical chunk goes into the source address
+    const int64_t a_last = p.M - 1 - m0;              // last valid row of the A / B panel, relative to the tile
+    const int b_last = p.N - 1 - n0;
+    unsigned voff[4][2];                              // [A0, B0, B1, A1][instruction]
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = 16 * wave + 8 * i + (lane >> 3);                   // row of the half panel
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const int64_t ra0 = r < a_last ? r : a_last, ra1 = HP + r < a_last ? HP + r : a_last;   // clamped: a valid row
+        const int rb0 = r < b_last ? r : b_last, rb1 = HP + r < b_last ? HP + r : b_last;
+        voff[0][i] = (unsigned)((size_t)ra0 * K + 16 * c);               // < 256 * 32768
+        voff[1][i] = (unsigned)((size_t)rb0 * K + 16 * c);
+        voff[2][i] = (unsigned)((size_t)rb1 * K + 16 * c);
+        voff[3][i] = (unsigned)((size_t)ra1 * K + 16 * c);
+    }
+    const unsigned ring_lds = (unsigned)(size_t)(QT_LDS char*)ring;
+    const unsigned dst_wave = __builtin_amdgcn_readfirstlane(ring_lds + wave * 2048);  // wave-uniform
+    const int8_t* srcA = p.Xq + m0 * (int64_t)K;      // scalar: k-byte 0 of the tile's first row
+    const int8_t* srcB = p.Wq + (int64_t)n0 * K;
+    // unit i = 4 t + J: J is a compile-time constant wherever the slot is
+    auto issue = [&](auto j_c, int t, int slot) {
+        constexpr int J = decltype(j_c)::value;
+        const unsigned d = dst_wave + (unsigned)slot * UNIT_BYTES;
+        glds16_pair(voff[J][0], voff[J][1], ((J == 0 || J == 3) ? srcA : srcB) + (size_t)t * KU, d, d + 1024);
+    };
+
+    // ---- fragment read geometry (per lane), byte offsets inside a unit ----
+    const int lr = lane & 31, lh = lane >> 5;
+    auto frag_off = [&](int r, int s) {               // row r of the half panel, k-step s
+        const int x = (r >> 1) & 7;
+        return (r >> 3) * 1024 + (r & 7) * 128 + 16 * ((2 * s + lh) ^ x);
+    };
+    int aoff[2][4], boff[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) aoff[mi][s] = frag_off(wave_m * 64 + mi * 32 + lr, s);
+        boff[s] = frag_off(wave_n * 32 + lr, s);
+    }
+
+    i32x16 acc[2][2][2];                              // [A half][B half][mi]
+#pragma unroll
+    for (int qa = 0; qa < 2; ++qa)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) acc[qa][qb][mi] = (i32x16){};
+
+    // ---- the pipeline (ring_pipe.h): R 8, L 6, unit = a half panel, 2 LDS-DMA per wave and unit ----
+    i32x4 fa[2][4], fb[2][4];                         // A: [mi][k-step], B: [half][k-step]
+    // waits of ring_pipe.h one unit earlier: lead LEAD - 1 in its terms (units u+3 .. u+LEAD may stay in flight)
+    auto drain_wait = [&](int u) { ring_drain_wait<2, LEAD - 1>(nu - u - 3); };
+    auto phase = [&](auto slot_c, auto steady_c, int u) {
+        constexpr int S = decltype(slot_c)::value;
+        constexpr bool STEADY = decltype(steady_c)::value;
+        constexpr int Q = S & 3, QA = Q >> 1, QB = Q & 1;
+        constexpr int ISLOT = (S + LEAD) & (RING - 1);
+        // ---- LOAD: the K-tile's units sit in slots (S & 4) + {0: A0, 1: B0, 2: B1, 3: A1} ----
+        const char* tile = ring + (S & 4) * UNIT_BYTES;
+        if constexpr (Q == 0 || Q == 2) {
+            const char* base = tile + (Q == 0 ? 0 : 3) * UNIT_BYTES;
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi) fa[mi][s] = *(const i32x4*)(base + aoff[mi][s]);
+        }
+        if constexpr (Q == 0 || Q == 1) {
+            const char* base = tile + (1 + QB) * UNIT_BYTES;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) fb[QB][s] = *(const i32x4*)(base + boff[s]);
+        }
+        if (STEADY || u + LEAD < nu) {
+            issue(std::integral_constant<int, (S + LEAD) & 3>{}, (u + LEAD) >> 2, ISLOT);
+            wait_vmcnt<2 * (LEAD - 2)>();   // everything up to unit u+2 has landed; 4 units stay in flight
+        } else {
+            drain_wait(u);
+        }
+        // ---- MATH ----
+        ring_sync_math([&] {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+                    acc[QA][QB][mi] =
+                        __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[mi][s], fb[QB][s], acc[QA][QB][mi], 0, 0, 0);
+        });
+    };
+
+    // prologue: units 0..LEAD-1 in flight (nu is 4 or at least 8), units 0 and 1 landed
+    issue(std::integral_constant<int, 0>{}, 0, 0);
+    issue(std::integral_constant<int, 1>{}, 0, 1);
+    issue(std::integral_constant<int, 2>{}, 0, 2);
+    issue(std::integral_constant<int, 3>{}, 0, 3);
+    if (nu > 4) {
+        issue(std::integral_constant<int, 0>{}, 1, 4);
+        issue(std::integral_constant<int, 1>{}, 1, 5);
+        wait_vmcnt<2 * (LEAD - 2)>();
+    } else {
+        wait_vmcnt<4>();
+    }
+    ring_stagger_begin(group_b);
+
+    int u = 0;
+    for (; u + 8 + LEAD <= nu; u += 8)   // every phase issues a unit that exists
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, std::true_type{}, uu); }, u);
+    for (; u + 8 <= nu; u += 8)
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, std::false_type{}, uu); }, u);
+    if (u < nu) {  // nu is a multiple of 4: one K-tile left
+        phase(std::integral_constant<int, 0>{}, std::false_type{}, u);
+        phase(std::integral_constant<int, 1>{}, std::false_type{}, u + 1);
+        phase(std::integral_constant<int, 2>{}, std::false_type{}, u + 2);
+        phase(std::integral_constant<int, 3>{}, std::false_type{}, u + 3);
+    }
+    ring_stagger_end(group_b);
+
+    // ---- epilogue: qt_gemm_i8's sequence, once per output element, by the lane that holds it ----
+    // C/D map of the 32x32 MFMA: column = lane & 31; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    const bool asym = p.zp_x != nullptr;
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+        const int n = n0 + qb * HP + wave_n * 32 + lr;
+        if (n >= p.N) continue;
+        float bn = 0.0f;
+        if (p.bias) bn = qt_load_w(p.bias, p.out_dtype, n);
+        const float sw0 = p.s_w[n];
+        const int ws0 = asym ? p.wsum[n] : 0;
+#pragma unroll
+        for (int qa = 0; qa < 2; ++qa) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t m = m0 + qa * HP + wave_m * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (m >= p.M) continue;
+                    int a = acc[qa][qb][mi][r];
+                    if (asym) a = a - p.zp_x[m] * ws0;
+                    const float prod = sw0 * (float)a;
+                    const float tv = 0.0f + prod;
+                    float y = p.s_x[m] * tv;
+                    if (p.bias) y = y + bn;
+                    qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n), y);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N,
+                               const float* s_x, const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum,
+                               const void* bias, void* Y, int out_dtype, int64_t ldy, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && M > 0 && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8_ring: bad arguments");
+    QT_CHECK_ARG(w_format == QT_W_INT8, "qt_gemm_i8_ring: w_format %d unsupported: int8 weights only (packed int4 runs "
+                 "on qt_gemm_i8)", w_format);
+    QT_CHECK_ARG(G == 1, "qt_gemm_i8_ring: G %d unsupported: one scale group per row only (grouped scales run on "
+                 "qt_gemm_i8)", G);
+    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_ring: K %d > 32768 (the int32 accumulator bound)", K);
+    QT_CHECK_ARG(K % QT_I8_RING_K_UNIT == 0, "qt_gemm_i8_ring: K %d is not a multiple of the k-unit %d", K,
+                 QT_I8_RING_K_UNIT);
+    QT_CHECK_ARG(((uintptr_t)Xq & 15) == 0, "qt_gemm_i8_ring: Xq is not 16-byte aligned");
+    QT_CHECK_ARG(((uintptr_t)Wq & 15) == 0, "qt_gemm_i8_ring: Wq is not 16-byte aligned");
+    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_ring: out_dtype %d must be bf16 or fp16", out_dtype);
+    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_ring: zp_x needs wsum");
+    static_assert(QT_I8_RING_K_UNIT == KU && QT_I8_RING_SLOTS == RING && QT_I8_RING_LEAD == LEAD, "header constants");
+    const int64_t tiles = ((M + BT - 1) / BT) * (int64_t)((N + BT - 1) / BT);
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_ring: too many tiles");
+    RingArgs a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, ldy, out_dtype};
+    hipLaunchKernelGGL(gemm_i8_ring_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}

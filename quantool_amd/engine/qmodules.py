@@ -29,10 +29,15 @@ class QuantizedLinear(nn.Module):
 
     M = rows of ``x``: 1 <= M <= ``skinny_max_m`` runs the decode form ``qt_gemm_i8_skinny`` (the weights read once, 16
     output columns per workgroup), larger M the 128 x 128-tile ``qt_gemm_i8``.  The two agree to the bit, so the
-    attribute changes speed alone; 0 sends every M to the tiled kernel."""
+    attribute changes speed alone; 0 sends every M to the tiled kernel.  M >= ``ring_min_m`` (when that is not 0) runs
+    an int8 weight with one scale group on the 256 x 256 LDS-ring kernel ``qt_gemm_i8_ring`` where
+    ``ops.gemm_i8_ring_supported`` holds; it agrees with the tiled kernel to the bit as well, and 0 never uses it."""
 
     # Decode GEMV up to this many rows: the measured crossover (DESIGN.md 4.11).
     skinny_max_m = 16
+    # LDS-ring GEMM from this many rows (0: never): the smallest measured M from which the ring is no slower than the
+    # tiled kernel on all three Llama-3-8B shapes, in both runs (DESIGN.md 4.12).
+    ring_min_m = 2048
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -60,8 +65,15 @@ class QuantizedLinear(nn.Module):
         Xq, s_x, zp_x = ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric,
                                                col_perm=self.col_perm)
         bias = None if self.bias is None else self.bias.to(x.dtype)
-        skinny = 1 <= Xq.shape[0] <= min(self.skinny_max_m, ops.I8_SKINNY_MAX_M)
-        y = (ops.gemm_i8_skinny if skinny else ops.gemm_i8)(
+        M = Xq.shape[0]
+        if 1 <= M <= min(self.skinny_max_m, ops.I8_SKINNY_MAX_M):
+            gemm = ops.gemm_i8_skinny
+        elif (self.ring_min_m > 0 and M >= self.ring_min_m and not self.int4 and self.weight_scale.shape[1] == 1
+              and ops.gemm_i8_ring_supported(Xq, self.weight, self.weight_scale)):
+            gemm = ops.gemm_i8_ring
+        else:
+            gemm = ops.gemm_i8
+        y = gemm(
             Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
             wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
         return y.reshape(*x.shape[:-1], self.out_features)

@@ -595,6 +595,56 @@ def gemm_i8_skinny(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: t
     return Y
 
 
+I8_RING_K_UNIT = 128   # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
+I8_RING_SLOTS = 8      # half panels (128 rows x 128 k-bytes) resident in LDS (QT_I8_RING_SLOTS)
+I8_RING_LEAD = 6       # half panels the LDS-DMA runs ahead of the MFMAs (QT_I8_RING_LEAD)
+
+
+def _i8_ring_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
+    """Why ``qt_gemm_i8_ring`` would refuse these operands, or None.  Host-only: touches no library."""
+    if Wq.dtype != torch.int8:
+        return f"int8 weights only, got {Wq.dtype} (packed int4 runs on gemm_i8)"
+    if s_w.dim() != 2 or s_w.shape[-1] != 1:
+        return f"one scale group per row only, got s_w {tuple(s_w.shape)} (grouped scales run on gemm_i8)"
+    K = Xq.shape[-1]
+    if K % I8_RING_K_UNIT != 0:
+        return f"K={K} is not a multiple of the k-unit {I8_RING_K_UNIT}"
+    if K > 32768:
+        return f"K={K} > 32768: the int32 accumulator could overflow"
+    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
+        return "Xq and Wq must be 16-byte aligned"
+    return None
+
+
+def gemm_i8_ring_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
+    """Whether ``gemm_i8_ring`` takes these operands: an int8 weight with one scale group, K a multiple of
+    ``I8_RING_K_UNIT`` and at most 32768, both operands 16-byte aligned.  Host-only."""
+    return _i8_ring_refusal(Xq, Wq, s_w) is None
+
+
+def gemm_i8_ring(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                 K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                 wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                 out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8`` on the 256 x 256 LDS-ring kernel (``qt_gemm_i8_ring``): the prefill form for W8A8 / INT8.  Same
+    arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where ``gemm_i8_ring_supported`` is false."""
+    why = _i8_ring_refusal(Xq, Wq, s_w)
+    if why is not None:
+        raise ValueError(f"gemm_i8_ring: {why}")
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    M = Xq.shape[0]
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8_ring", lib.qt_gemm_i8_ring(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
 def moe_route(top_k_index: torch.Tensor, num_experts: int):
     """top_k_index [T, k] int32 / int64 -> (offsets int32 [E+1], src_token int32 [T k], src_slot int32 [T k],
     row_of int32 [T k]): ``qt_moe_route`` (include/quantool_amd.h).  Rows sorted by expert, then by token; an index

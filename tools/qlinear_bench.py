@@ -16,6 +16,12 @@ operands, alternating call by call in one loop, each call between its own pair o
 launches are not counted), the weights rotating over distinct copies totalling more than 512 MiB (twice the Infinity
 Cache) so that every call reads them cold, as a decode step does.  Reported per kernel: median and mean microseconds,
 weight + scale (+ wsum) bytes over the median, and that as a share of 8 TB/s.
+
+Every M > 16 also gets a "ring" row (W8A8, symmetric activations): the tiled qt_gemm_i8 and the LDS-ring qt_gemm_i8_ring
+on the same operands, with qt_quantize_tokens_i8, bf16 F.linear and torch._int_mm, all alternating in that one loop
+under the same harness (per-call events, weights rotating over more than 512 MiB of copies, medians).  Reported:
+median microseconds and TOPS per kernel, tiled / ring ("speedup"), and bf16 F.linear over quantize_tokens + ring
+("bf16_over_act_plus_ring", > 1: the W8A8 linear on the ring is faster than bf16).
 """
 from __future__ import annotations
 
@@ -103,6 +109,51 @@ def decode_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+def ring_rows(shape, N, K, ms, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_gemm_i8_ring at prefill sizes, W8A8 (int8 channel-wise, symmetric activations), beside the
+    activation pass, bf16 F.linear and torch._int_mm."""
+    rows = []
+    q = torch.randint(-128, 128, (N, K), device=dev, generator=g, dtype=torch.int8)
+    s_w = torch.rand(N, 1, device=dev, generator=g) * 1e-3
+    n_cp = max(2, -(-int(COLD_BYTES * 1.1) // q.numel()))
+    cps = [q.clone() for _ in range(n_cp)]
+    cps_t = [c.t() for c in cps]
+    n_bf = max(2, -(-int(COLD_BYTES * 1.1) // (2 * q.numel())))
+    bfs = [(torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16) for _ in range(n_bf)]
+    del q
+    for M in ms:
+        X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        Xq, s_x, _ = ops.quantize_tokens_i8(X, symmetric=True)
+        # kernels that share a rep read different copies, or the second finds the first's weights cached
+        fns = {"gemm_i8": lambda i: ops.gemm_i8(Xq, s_x, cps[i % n_cp], s_w),
+               "gemm_i8_ring": lambda i: ops.gemm_i8_ring(Xq, s_x, cps[(i + 1) % n_cp], s_w),
+               "quantize_tokens": lambda i: ops.quantize_tokens_i8(X, symmetric=True),
+               "bf16_linear": lambda i: F.linear(X, bfs[i % n_bf])}
+        try:
+            torch._int_mm(Xq, cps_t[0])
+            fns["torch_int_mm"] = lambda i: torch._int_mm(Xq, cps_t[(i + 2) % n_cp])
+        except Exception:  # noqa: BLE001  (the prefill rows report the reason)
+            pass
+        t = time_pair(fns, reps, warmup)
+        same = torch.equal(fns["gemm_i8"](0).view(torch.int16), fns["gemm_i8_ring"](0).view(torch.int16))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        ops_n = 2.0 * M * N * K
+        row = {"shape": shape, "scheme": "W8A8", "M": M, "N": N, "K": K, "cold_copies": n_cp, "bits_equal": same,
+               "us": {k: round(v * 1e6, 2) for k, v in med.items()},
+               "min_us": {k: round(min(v) * 1e6, 2) for k, v in t.items()},
+               "tops": {k: round(ops_n / v / 1e12, 1) for k, v in med.items() if k != "quantize_tokens"},
+               "int8_peak_frac": {k: round(ops_n / med[k] / INT8_PEAK, 3) for k in ("gemm_i8", "gemm_i8_ring")},
+               "speedup": round(med["gemm_i8"] / med["gemm_i8_ring"], 3),
+               "bf16_over_act_plus_tiled": round(med["bf16_linear"] / (med["quantize_tokens"] + med["gemm_i8"]), 3),
+               "bf16_over_act_plus_ring": round(med["bf16_linear"] / (med["quantize_tokens"] + med["gemm_i8_ring"]), 3)}
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr)
+        del X, Xq
+    del cps, cps_t, bfs
+    torch.cuda.empty_cache()
+    return rows
+
+
 def _time(fn, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -122,6 +173,8 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-ring", action="store_true", help="leave out the tiled-vs-ring rows")
+    ap.add_argument("--ring-only", action="store_true", help="only the tiled-vs-ring rows at M > 16")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qlinear_bench needs a GPU")
@@ -133,11 +186,16 @@ def main():
     decode_ms = [m for m in all_ms if m <= DECODE_MAX_M]
     large_ms = [m for m in all_ms if m > DECODE_MAX_M]
     decode = []
+    ring = []
     for shape in args.shapes.split(","):
         N, K = SHAPES[shape]
         if decode_ms:
             decode += decode_rows(shape, N, K, decode_ms, args.reps, args.warmup, dev, g)
         if not large_ms:
+            continue
+        if not args.no_ring and K % ops.I8_RING_K_UNIT == 0:
+            ring += ring_rows(shape, N, K, large_ms, args.reps, args.warmup, dev, g)
+        if args.ring_only:
             continue
         q8 = torch.randint(-128, 128, (N, K), device=dev, generator=g, dtype=torch.int8)
         q4 = torch.randint(-8, 8, (N, K), device=dev, generator=g, dtype=torch.int8)
@@ -183,7 +241,7 @@ def main():
         torch.cuda.empty_cache()
     print(json.dumps({"metric": "W8A8 / W4A8 linear vs bf16 F.linear, Llama-3-8B prefill shapes", "int8_peak": INT8_PEAK,
                       "torch_int_mm": int_mm_note or "runs (timed as torch_int_mm)", "rows": rows,
-                      "hbm_peak": HBM_PEAK, "device": torch.cuda.get_device_name(0), "decode": decode}))
+                      "hbm_peak": HBM_PEAK, "device": torch.cuda.get_device_name(0), "decode": decode, "ring": ring}))
 
 
 if __name__ == "__main__":
