@@ -378,6 +378,19 @@ int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_fo
  *   before any weight load.  Only the experts that own rows have their weights read, each once per 16 of its rows, so
  *   this is the form for a few tokens.  R / 16 + min(E, R) <= 65535, else QT_ERR_INVALID.  Deterministic, no atomics.
  *
+ * qt_gemm_i8_ring_grouped: the prefill form of qt_gemm_i8_grouped for W8A8 / INT8 banks: qt_gemm_i8_ring's 256 x 256
+ *   LDS-ring tile over E weight matrices.  qt_gemm_i8_grouped's arguments with the same meanings, plus x_rows, the
+ *   number of rows of Xq.  Taken: w_format == QT_W_INT8 with G == 1, K a multiple of QT_I8_RING_K_UNIT, K <= 32768, Xq
+ *   and Wq 16-byte aligned, E <= 4096, and with row_idx x_rows K <= 2^32 (a gathered row is addressed by a 32-bit byte
+ *   offset from Xq), without it x_rows >= R; anything else is QT_ERR_INVALID before any launch and qt_last_error names
+ *   the reason.  For every legal input Y is bit-identical to qt_gemm_i8_grouped's on the same arguments: the int32 sum
+ *   is exact and the chain t -> tot = 0.0f + s_w t -> y runs literally, once per output element.  The grid is
+ *   (ceil(R/256) + E) m-tile slots x ceil(N/256) n-tiles, an upper bound that needs no host read of the counts; a
+ *   workgroup walks offsets (clamped to [0, R] and made ascending) to its expert and tile, and a surplus one exits
+ *   before its first load.  row_idx values are clamped into [0, x_rows); a tile row past the expert's last row re-reads
+ *   that expert's last row and is never stored: no byte outside Xq[x_rows, K] and Wq[E, N, K] is read, no element
+ *   outside Y[m < offsets[E], n < N] is written.  No bias, no workspace, no atomics: deterministic.  
+ *
  * qt_moe_combine: out [T, H] (dtype bf16 / fp16) = the weighted sum of each token's routed rows of Y [R, H] (pitch
  *   ldy), transformers' MixtralExperts.forward restated: for the token's rows r = row_of[t k + j] >= 0 in ascending
  *   row order (= ascending expert), with w = weights[t, j] fp32 [T, k]:
@@ -392,6 +405,10 @@ int qt_gemm_i8_skinny_grouped(const int8_t* Xq, int K, const int32_t* row_idx, i
                               int E, const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
                               const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
                               qt_stream_t stream);
+int qt_gemm_i8_ring_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets, int E,
+                            const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
+                            const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
+                            int64_t x_rows, qt_stream_t stream);
 int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
                    int64_t T, int k, void* out, qt_stream_t stream);
 

@@ -25,6 +25,14 @@
 // ds_read_b128 whose 16-lane groups each cover all 64 banks once.
 // A tile row past M (or N) is fetched from row M - 1 (N - 1): the source row is clamped, the value is computed and
 // never stored.  K is a whole number of K-tiles, so no byte outside Xq[M, K] and Wq[N, K] is read.
+//
+// qt_gemm_i8_ring_grouped: the same tile over E weight matrices (ring_tile<true>), equal to qt_gemm_i8_grouped to the
+// bit.  The grid holds ceil(R/256) + E m-tile slots per n-tile, an upper bound on
+// sum_e ceil(rows_e / 256) that needs no host read of the counts; a workgroup walks the clamped offsets to its (expert,
+// tile) and a surplus one returns before its first LDS-DMA and before any barrier.  The expert and the tile's first
+// row are wave-uniform, so the B base (expert e's matrix) and, for contiguous rows, the A base stay scalar.  With row_idx
+// the A base is Xq itself and each lane's 32-bit offset is row_idx[m] K + 16 c (the host refuses x_rows K > 2^32; the
+// index is clamped into [0, x_rows)).  A tile row past the expert's last row re-reads that expert's last row.
 #include "common.h"
 #include "ring_pipe.h"
 
@@ -57,8 +65,18 @@ struct RingArgs {
     int64_t ldy;
     int out_dtype;
 };
+// grouped (MOE) form only: expert e owns rows [offsets[e], offsets[e + 1]) of Y and the e-th weight matrix; p.M is the
+// routed-row count R; A row m (and s_x / zp_x) is read at row_idx[m], clamped into [0, x_rows), when row_idx is
+// given, else at m
+struct RingMoe {
+    const int32_t* offsets;
+    const int32_t* row_idx;
+    int64_t x_rows;
+    int E;
+};
 
-__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArgs p) {
+template <bool MOE>
+__device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -68,20 +86,57 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArg
 
     // tile order: GROUP_M m-tiles walk the n-tiles together (as gemm_i8_kernel)
     const int tiles_n = (p.N + BT - 1) / BT;
-    const int tiles_m = (int)((p.M + BT - 1) / BT);
+    const int tiles_m = (int)((p.M + BT - 1) / BT) + (MOE ? g.E : 0);
     const int pid = blockIdx.x;
     const int per_group = GROUP_M * tiles_n;
     const int first_m = pid / per_group * GROUP_M;
     const int gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
     const int in_g = pid % per_group;
-    const int64_t m0 = (int64_t)(first_m + in_g % gsize) * BT;
+    int64_t m0 = (int64_t)(first_m + in_g % gsize) * BT;
+    int64_t m_end = p.M;                              // rows [m0, m_end) of this tile's matrix exist
     const int n0 = (in_g / gsize) * BT;
     const int K = p.K;
+    const int8_t* Wq = p.Wq;
+    const float* s_w = p.s_w;
+    const int32_t* wsum = p.wsum;
+    if constexpr (MOE) {
+        // m-tile slot -> (expert, tile within the expert); offsets clamped to [0, R] and made ascending, so a bad
+        // table cannot move a write out of Y (as gemm_i8_kernel)
+        const int slot = first_m + in_g % gsize;
+        const int R = (int)p.M;                       // <= 0x7fffffff (host)
+        int start = 0, e = -1, lo_e = 0, hi_e = 0;
+        for (int j = 0; j < g.E; ++j) {
+            const int lo = min(max(g.offsets[j], 0), R);
+            const int hi = min(max(g.offsets[j + 1], lo), R);
+            const int nt = (int)(((int64_t)hi - lo + BT - 1) / BT);
+            if (slot < start + nt) {
+                e = j;
+                lo_e = lo + (slot - start) * BT;
+                hi_e = hi;
+                break;
+            }
+            start += nt;
+        }
+        if (e < 0) return;                            // surplus workgroup: uniform, before any LDS-DMA or barrier
+        e = __builtin_amdgcn_readfirstlane(e);        // wave-uniform: the A and B bases below stay scalar
+        m0 = __builtin_amdgcn_readfirstlane(lo_e);
+        m_end = __builtin_amdgcn_readfirstlane(hi_e);
+        Wq = p.Wq + (int64_t)e * p.N * K;
+        s_w = p.s_w + (int64_t)e * p.N;
+        if (wsum) wsum = p.wsum + (int64_t)e * p.N;
+    }
+    // the Xq / s_x / zp_x row of output row m (m < m_end)
+    auto src_row = [&](int64_t m) -> int64_t {
+        if constexpr (MOE) {
+            if (g.row_idx) return min(max((int64_t)g.row_idx[m], (int64_t)0), g.x_rows - 1);
+        }
+        return m;
+    };
     const int nu = K / KU * 4;                        // units = phases
 
     // ---- staging geometry: two LDS-DMA instructions per thread per unit (pieces 2 wave, 2 wave + 1) ----
     // lane: row lane >> 3 of its piece, physical chunk lane & 7; the logical chunk goes into the source address
-    const int64_t a_last = p.M - 1 - m0;              // last valid row of the A / B panel, relative to the tile
+    const int64_t a_last = m_end - 1 - m0;            // last valid row of the A / B panel, relative to the tile
     const int b_last = p.N - 1 - n0;
     unsigned voff[4][2];                              // [A0, B0, B1, A1][instruction]
 #pragma unroll
@@ -98,7 +153,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArg
     const unsigned ring_lds = (unsigned)(size_t)(QT_LDS char*)ring;
     const unsigned dst_wave = __builtin_amdgcn_readfirstlane(ring_lds + wave * 2048);  // wave-uniform
     const int8_t* srcA = p.Xq + m0 * (int64_t)K;      // scalar: k-byte 0 of the tile's first row
-    const int8_t* srcB = p.Wq + (int64_t)n0 * K;
+    const int8_t* srcB = Wq + (int64_t)n0 * K;
+    if constexpr (MOE) {
+        if (g.row_idx) {                              // gathered rows: offsets from Xq itself, < x_rows K <= 2^32
+            srcA = p.Xq;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = 16 * wave + 8 * i + (lane >> 3);
+                const int c = (lane & 7) ^ ((r >> 1) & 7);
+                const int64_t ra0 = r < a_last ? r : a_last, ra1 = HP + r < a_last ? HP + r : a_last;
+                voff[0][i] = (unsigned)((size_t)src_row(m0 + ra0) * K + 16 * c);
+                voff[3][i] = (unsigned)((size_t)src_row(m0 + ra1) * K + 16 * c);
+            }
+        }
+    }
     // unit i = 4 t + J: J is a compile-time constant wherever the slot is
     auto issue = [&](auto j_c, int t, int slot) {
         constexpr int J = decltype(j_c)::value;
@@ -203,9 +271,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArg
         const int n = n0 + qb * HP + wave_n * 32 + lr;
         if (n >= p.N) continue;
         float bn = 0.0f;
-        if (p.bias) bn = qt_load_w(p.bias, p.out_dtype, n);
-        const float sw0 = p.s_w[n];
-        const int ws0 = asym ? p.wsum[n] : 0;
+        const bool has_bias = !MOE && p.bias;         // the grouped form has none
+        if (has_bias) bn = qt_load_w(p.bias, p.out_dtype, n);
+        const float sw0 = s_w[n];
+        const int ws0 = asym ? wsum[n] : 0;
 #pragma unroll
         for (int qa = 0; qa < 2; ++qa) {
 #pragma unroll
@@ -213,18 +282,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArg
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = m0 + qa * HP + wave_m * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (m >= p.M) continue;
+                    if (m >= m_end) continue;
+                    const int64_t ms = src_row(m);
                     int a = acc[qa][qb][mi][r];
-                    if (asym) a = a - p.zp_x[m] * ws0;
+                    if (asym) a = a - p.zp_x[ms] * ws0;
                     const float prod = sw0 * (float)a;
                     const float tv = 0.0f + prod;
-                    float y = p.s_x[m] * tv;
-                    if (p.bias) y = y + bn;
+                    float y = p.s_x[ms] * tv;
+                    if (has_bias) y = y + bn;
                     qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n), y);
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArgs p) { ring_tile<false>(p, RingMoe{}); }
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_moe_kernel(const RingArgs p, const RingMoe g) {
+    ring_tile<true>(p, g);
 }
 
 }  // namespace
@@ -250,6 +325,41 @@ extern "C" int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* W
     QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_ring: too many tiles");
     RingArgs a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, ldy, out_dtype};
     hipLaunchKernelGGL(gemm_i8_ring_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_i8_ring_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R,
+                                       const int32_t* offsets, int E, const void* Wq, int w_format, int N,
+                                       const float* s_x, const int32_t* zp_x, const float* s_w, int G,
+                                       const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, int64_t x_rows,
+                                       qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(Xq && Wq && offsets && s_x && s_w && Y && R > 0 && E > 0 && N > 0 && K > 0 && ldy >= N && x_rows > 0,
+                 "qt_gemm_i8_ring_grouped: bad arguments");
+    QT_CHECK_ARG(w_format == QT_W_INT8, "qt_gemm_i8_ring_grouped: w_format %d unsupported: int8 weights only (packed "
+                 "int4 runs on qt_gemm_i8_grouped)", w_format);
+    QT_CHECK_ARG(G == 1, "qt_gemm_i8_ring_grouped: G %d unsupported: one scale group per row only (grouped scales run "
+                 "on qt_gemm_i8_grouped)", G);
+    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_ring_grouped: K %d > 32768 (the int32 accumulator bound)", K);
+    QT_CHECK_ARG(K % QT_I8_RING_K_UNIT == 0, "qt_gemm_i8_ring_grouped: K %d is not a multiple of the k-unit %d", K,
+                 QT_I8_RING_K_UNIT);
+    QT_CHECK_ARG(((uintptr_t)Xq & 15) == 0, "qt_gemm_i8_ring_grouped: Xq is not 16-byte aligned");
+    QT_CHECK_ARG(((uintptr_t)Wq & 15) == 0, "qt_gemm_i8_ring_grouped: Wq is not 16-byte aligned");
+    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_ring_grouped: out_dtype %d must be bf16 or fp16", out_dtype);
+    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_ring_grouped: zp_x needs wsum");
+    QT_CHECK_ARG(R <= 0x7fffffffLL, "qt_gemm_i8_ring_grouped: R %lld too large", (long long)R);
+    QT_CHECK_ARG(E <= 4096, "qt_gemm_i8_ring_grouped: E %d > 4096", E);
+    // gathered rows are addressed by a 32-bit byte offset from Xq; contiguous rows need R of them
+    QT_CHECK_ARG(!row_idx || x_rows * (int64_t)K <= (1LL << 32), "qt_gemm_i8_ring_grouped: x_rows %lld x K %d > 2^32 "
+                 "bytes: a gathered row is addressed by a 32-bit offset", (long long)x_rows, K);
+    QT_CHECK_ARG(row_idx || x_rows >= R, "qt_gemm_i8_ring_grouped: x_rows %lld < R %lld without row_idx",
+                 (long long)x_rows, (long long)R);
+    const int64_t tiles = ((R + BT - 1) / BT + E) * (int64_t)((N + BT - 1) / BT);
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_ring_grouped: too many tiles");
+    RingArgs a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, nullptr, Y, R, N, K, ldy, out_dtype};
+    RingMoe g{offsets, row_idx, x_rows, E};
+    hipLaunchKernelGGL(gemm_i8_ring_moe_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a, g);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

@@ -176,10 +176,18 @@ class QuantizedExperts(_RoutedExperts):
 
     With T = rows of ``hidden_states`` (known on the host) and 1 <= T <= ``grouped_max_tokens`` both products run the
     decode form ``qt_gemm_i8_skinny_grouped`` (16-row tiles, only the experts that were hit are read), otherwise the
-    128-row-tile ``qt_gemm_i8_grouped``.  The two agree to the bit; 0 sends every T to the tiled kernel."""
+    128-row-tile ``qt_gemm_i8_grouped``.  The two agree to the bit; 0 sends every T to the tiled kernel.  Past the
+    decode range a product of R routed rows with R / E >= ``ring_min_rows_per_expert`` (when that is not 0) runs an
+    int8 bank with one scale group on the 256-row LDS-ring tile ``qt_gemm_i8_ring_grouped`` where
+    ``ops.gemm_i8_ring_grouped_supported`` holds; it agrees with the tiled kernel to the bit as well, so the attribute
+    changes speed alone, and 0 never uses it.  Packed int4 (W4A8) banks never reach it."""
 
     # Decode form up to this many tokens: the measured crossover at Mixtral-8x7B's bank shapes (DESIGN.md 4.11).
     grouped_max_tokens = 16
+    # LDS-ring form from this many routed rows per expert (R / E; 0: never): the smallest measured R / E from which the
+    # ring is no slower than the tiled grouped kernel on both products at Mixtral-8x7B's bank shapes, at that size and
+    # every larger one, in both runs (DESIGN.md 4.13).
+    ring_min_rows_per_expert = 1024
 
     def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
                  down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
@@ -207,8 +215,17 @@ class QuantizedExperts(_RoutedExperts):
         from ..hip import ops
 
         Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=self.act_symmetric)
-        gemm = ops.gemm_i8_skinny_grouped if 1 <= tokens <= self.grouped_max_tokens else ops.gemm_i8_grouped
-        return gemm(Xq, s_x, getattr(self, part), getattr(self, f"{part}_scale"), offsets, row_idx=row_idx,
+        w, s_w = getattr(self, part), getattr(self, f"{part}_scale")
+        R = x.shape[0] if row_idx is None else row_idx.numel()
+        ring = self.ring_min_rows_per_expert
+        if 1 <= tokens <= self.grouped_max_tokens:
+            gemm = ops.gemm_i8_skinny_grouped
+        elif (ring > 0 and R >= ring * self.num_experts and not self.int4 and s_w.shape[2] == 1
+              and ops.gemm_i8_ring_grouped_supported(Xq, w, s_w, row_idx)):
+            gemm = ops.gemm_i8_ring_grouped
+        else:
+            gemm = ops.gemm_i8_grouped
+        return gemm(Xq, s_x, w, s_w, offsets, row_idx=row_idx,
                     K=x.shape[1], zp_x=zp_x, wsum=None if zp_x is None else getattr(self, f"{part}_wsum"),
                     out_dtype=x.dtype)
 

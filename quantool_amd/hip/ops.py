@@ -668,8 +668,10 @@ def moe_route(top_k_index: torch.Tensor, num_experts: int):
     return offsets, src_token, src_slot, row_of
 
 
-def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype) -> torch.Tensor:
-    """The operand checks and the call both grouped int8 GEMMs share; ``fn`` names the entry point."""
+def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype,
+                     x_rows: bool = False) -> torch.Tensor:
+    """The operand checks and the call the grouped int8 GEMMs share; ``fn`` names the entry point (``x_rows``: it takes
+    the number of rows of Xq behind ldy)."""
     lib = load()
     fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype, experts=True)
     Mx, E = Xq.shape[0], Wq.shape[0]
@@ -692,7 +694,8 @@ def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x,
     Y = torch.empty((R, N), dtype=out_dtype, device=Xq.device)
     check(fn, getattr(lib, fn)(
         Xq.data_ptr(), K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x),
-        s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+        s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), *((Mx,) if x_rows else ()),
+        _stream()))
     return Y
 
 
@@ -718,6 +721,57 @@ def gemm_i8_skinny_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor
     R // 16 + min(E, R) row-tile slots must fit a grid dimension (65535)."""
     return _gemm_i8_grouped("qt_gemm_i8_skinny_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
                             out_dtype)
+
+
+I8_RING_GROUPED_MAX_E = 4096   # experts qt_gemm_i8_ring_grouped walks per workgroup
+
+
+def _i8_ring_grouped_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                             row_idx: Optional[torch.Tensor]) -> Optional[str]:
+    """Why ``qt_gemm_i8_ring_grouped`` would refuse these operands, or None.  Host-only: touches no library."""
+    if Wq.dtype != torch.int8:
+        return f"int8 weights only, got {Wq.dtype} (packed int4 runs on gemm_i8_grouped)"
+    if s_w.dim() != 3 or s_w.shape[-1] != 1:
+        return f"one scale group per row only, got s_w {tuple(s_w.shape)} (grouped scales run on gemm_i8_grouped)"
+    x_rows, K = Xq.shape[0], Xq.shape[-1]
+    if K % I8_RING_K_UNIT != 0:
+        return f"K={K} is not a multiple of the k-unit {I8_RING_K_UNIT}"
+    if K > 32768:
+        return f"K={K} > 32768: the int32 accumulator could overflow"
+    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
+        return "Xq and Wq must be 16-byte aligned"
+    if row_idx is not None and x_rows * K > 2 ** 32:
+        return f"Xq has {x_rows} rows x K={K} > 2^32 bytes: a gathered row is addressed by a 32-bit offset"
+    E, N = Wq.shape[0], Wq.shape[-2]
+    if E > I8_RING_GROUPED_MAX_E:
+        return f"E={E} > {I8_RING_GROUPED_MAX_E} experts"
+    R = x_rows if row_idx is None else row_idx.numel()
+    if ((R + 255) // 256 + E) * ((N + 255) // 256) > 0x7fffffff:
+        return f"too many tiles: R={R}, E={E}, N={N}"
+    return None
+
+
+def gemm_i8_ring_grouped_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                                   row_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_i8_ring_grouped`` takes these operands: an int8 bank [E, N, K] with one scale group, K a multiple
+    of ``I8_RING_K_UNIT`` and at most 32768, both operands 16-byte aligned, at most 4096 experts, a grid that fits,
+    and, with ``row_idx``, an Xq of at most 2^32 bytes.  Host-only."""
+    return _i8_ring_grouped_refusal(Xq, Wq, s_w, row_idx) is None
+
+
+def gemm_i8_ring_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                         offsets: torch.Tensor, *, rows: Optional[int] = None,
+                         row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                         zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                         out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8_grouped`` on the 256 x 256 LDS-ring tile (``qt_gemm_i8_ring_grouped``): the prefill form for W8A8 /
+    INT8 banks.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit; ``row_idx`` values are clamped into Xq's
+    rows.  ``ValueError`` where ``gemm_i8_ring_grouped_supported`` is false."""
+    why = _i8_ring_grouped_refusal(Xq, Wq, s_w, row_idx)
+    if why is not None:
+        raise ValueError(f"gemm_i8_ring_grouped: {why}")
+    return _gemm_i8_grouped("qt_gemm_i8_ring_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
+                            out_dtype, x_rows=True)
 
 
 def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:

@@ -35,6 +35,14 @@ The A8 decode comparison: the GEMM pair (gate_up gathered by token, then down) a
 qt_gemm_i8_skinny_grouped on the same operands, alternating call by call in one loop, each pair between its own HIP
 events, the two forms reading different copies of the bank in a rep (a bank is 0.7 / 1.4 GB, so every call reads its
 hit experts cold).  Reported per form: median microseconds and the hit experts' weight + scale (+ wsum) bytes over it.
+
+  python tools/moe_bench.py --ring-tokens 512,1024,2048,4096,8192,16384
+
+The W8A8 prefill comparison: per product (gate_up gathered by token, down contiguous) and per T, qt_gemm_i8_grouped and
+qt_gemm_i8_ring_grouped on the same operands, alternating call by call in one loop, each call between its own HIP
+events: median / mean / min microseconds per form, ring speedup (tiled median / ring median), bits_equal.  Then
+QuantizedExperts.forward end to end with ring_min_rows_per_expert 0 and at the class default (or at
+--ring-min-rows-per-expert), alternating likewise.
 """
 from __future__ import annotations
 
@@ -221,11 +229,67 @@ def _bench_a8_decode(scheme, T, banks, dev, g, args):
     return row
 
 
+def _us(times):
+    t = sorted(times)
+    return {"us": round(t[len(t) // 2] * 1e6, 2), "mean_us": round(sum(t) / len(t) * 1e6, 2),
+            "min_us": round(t[0] * 1e6, 2)}
+
+
+def _bench_a8_ring(T, qe, dev, g, args):
+    """One prefill row: both grouped forms of each product on the same routing and rows, and the bank's forward."""
+    from qlinear_bench import time_pair
+
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = w / w.sum(-1, keepdim=True)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    off = offsets.cpu().tolist()
+    Xq, s_x, _ = ops.quantize_tokens_i8(x, symmetric=True)
+    row = {"scheme": "W8A8", "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
+           "R_over_E": T * TOPK / E}
+    default = QuantizedExperts.ring_min_rows_per_expert
+    ring_at = default if args.ring_min_rows_per_expert < 0 else args.ring_min_rows_per_expert
+    with torch.no_grad():
+        gu = ops.gemm_i8_grouped(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H)
+        gate, up = gu.chunk(2, dim=-1)
+        hq, s_h, _ = ops.quantize_tokens_i8(qe.act_fn(gate) * up, symmetric=True)
+        del gu, gate, up
+        products = {"gate_up": lambda fn: fn(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H),
+                    "down": lambda fn: fn(hq, s_h, qe.down, qe.down_scale, offsets, K=I)}
+        for name, call in products.items():
+            t = time_pair({"tiled": lambda i: call(ops.gemm_i8_grouped),
+                           "ring": lambda i: call(ops.gemm_i8_ring_grouped)}, args.reps, args.warmup)
+            same = torch.equal(call(ops.gemm_i8_grouped).view(torch.int16),
+                               call(ops.gemm_i8_ring_grouped).view(torch.int16))
+            row[name] = {"tiled": _us(t["tiled"]), "ring": _us(t["ring"]), "bits_equal": same}
+            row[name]["speedup"] = round(row[name]["tiled"]["us"] / row[name]["ring"]["us"], 3)
+
+        def bank(setting):
+            def run(i):
+                QuantizedExperts.ring_min_rows_per_expert = setting
+                qe(x, idx, w)
+            return run
+
+        try:
+            t = time_pair({"attr_0": bank(0), "attr_ring": bank(ring_at)}, args.reps, args.warmup)
+        finally:
+            QuantizedExperts.ring_min_rows_per_expert = default
+    row["experts"] = {"ring_min_rows_per_expert": ring_at, "on_ring": bool(0 < ring_at <= T * TOPK / E),
+                      "attr_0": _us(t["attr_0"]), "attr_ring": _us(t["attr_ring"])}
+    row["experts"]["speedup"] = round(row["experts"]["attr_0"]["us"] / row["experts"]["attr_ring"]["us"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
     ap.add_argument("--decode-tokens", default="",
                     help="A8 schemes: compare the two grouped GEMM forms at these token counts instead")
+    ap.add_argument("--ring-tokens", default="",
+                    help="W8A8: compare qt_gemm_i8_grouped and qt_gemm_i8_ring_grouped at these token counts instead")
+    ap.add_argument("--ring-min-rows-per-expert", type=int, default=-1,
+                    help="with --ring-tokens: the attribute of the bank's second timing (default: the class's)")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -235,6 +299,18 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     rows = []
+
+    if args.ring_tokens:
+        qe = _experts("W8A8", dev, g)
+        for T in (int(t) for t in args.ring_tokens.split(",")):
+            row = _bench_a8_ring(T, qe, dev, g, args)
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr)
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, W8A8 prefill: qt_gemm_i8_grouped vs "
+                                    "qt_gemm_i8_ring_grouped", "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
 
     from transformers import MixtralConfig
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts
