@@ -273,6 +273,15 @@ int qt_xtx_dot(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx,
 size_t qt_gemm3_tn_f32_workspace_bytes(int M, int N, int k);
 int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
                     int N, int k, int kind, void* workspace, size_t workspace_bytes, qt_stream_t stream);
+/* Test face, as qt_gemm3_tn_f32 (not part of the quantisation path): the same for `batch` >= 1 problems of one shape
+ * in one launch (problem b at A + b * bsA, B + b * bsB, C + b * bsC,
+ * strides in elements; workspace: batch * qt_gemm3_tn_f32_workspace_bytes(M, N, k)).  tri != 0: B is lower-triangular
+ * in 256-blocks (B[k][n] == 0 for k < 256 * (n / 256)) and a tile column's k range starts at its own column, as in the
+ * factorisation's block-row products; needs k > 256 * ((N - 1) / 256).  tight != 0: the internal planes are pitched
+ * max(M, N) rounded up to 8 instead of 256, so edge tiles clamp their loads (M, N multiples of 8). */
+int qt_gemm3_tn_f32_ex(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N,
+                       int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB, int64_t bsC,
+                       void* workspace, size_t workspace_bytes, qt_stream_t stream);
 
 /* Host-only self-check of the bf16x3 block-row planner (runs without a GPU): 0 if every k chunk of every tile is
  * covered exactly once and the slab / reduction tables are consistent, else a negative code. */

@@ -57,7 +57,7 @@ static int chol_block_env(const char* name) {
 // then LEFT-looking at the outer level (block row J gathers  A[J, J:] -= R[:J0, J]^T R[:J0, J:]  in one
 // long-k product: each element of A is read and written once, where the right-looking k = 256 update of
 // the whole trailing matrix is bound by that read-modify-write), and the inverse's T_I product is the same
-// shape.  QT_CHOL_G3=0 disables; QT_CHOL_G3_MIN_CHUNKS = 128-row k-chunks a product needs (256 =
+// shape.  QT_CHOL_G3=0 disables; QT_CHOL_G3_MIN_CHUNKS = k rows a product needs, in units of 128 (two 64-row chunks of gemm3_tn.h; 256 =
 // one per CU in rounds 2-3; K = 14336 / 8192 / 4096: 24.2 / 9.5 / 3.6 ms at 64...256, 24.6 at 640, 24.9 at 768; off: 34.0 /
 // 10.7 / 3.6.  Round 4: 64 -- with the short f32 products split less (sgemm_tn.hip) and the chains batched, more of
 // the K = 4096 steps pay on the bf16 MFMA: single chain 3.82 -> 3.70 ms, three batched 5.55 -> 5.23, ten batched

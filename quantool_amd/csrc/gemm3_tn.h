@@ -4,10 +4,17 @@
 // weight is >= 2^-16 of hi*hi summed in one fp32 MFMA accumulator, smallest first:
 //     lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi              (dropped: mid*lo, lo*mid, lo*lo <= 2^-24)
 // -- 6 bf16-MFMA flops per fp32 flop at 16x the f32-MFMA rate.  The kernel is xtx.hip's LDS-ring pipeline
-// (ring_pipe.h) with the A and B panels of a unit taken from two plane sets; it serves the two products
-// that carry the K^3 of qt_cholesky_inverse_upper (cholesky.hip), which are not bit-pinned by the oracle
-// (the factor U is compared through the sweep's outputs, not bit for bit).  NOT used by the
-// GPTQ sweep's trailing update, whose ascending-k fmaf order is part of the parity contract (sgemm_tn.h).
+// (ring_pipe.h) on "tri-units": 16 k-rows of all three planes of both operands (48 KiB) per ring slot, three
+// slots, so each plane panel of a k-slab is staged into LDS once and its fragments are read once for all six
+// products (48 MFMAs per wave between barrier pairs).  Summation order inside a tile: 16-row slab -> product
+// (smallest first).  QT_G3_LOOP=chunk selects the earlier loop (one plane pair per 16 KiB unit, 64-row chunk ->
+// product -> 16-row unit: every product stages its own two panels, 12 stagings per chunk for 6 distinct
+// panels) for A/B runs; the two loops sum the same products in a different order, so their bits differ.
+// The kernel serves the two products that carry the K^3 of qt_cholesky_inverse_upper (cholesky.hip), which
+// are not bit-pinned by the oracle (the factor U is compared through the sweep's outputs, not bit
+// for bit), the opt-in QT_SWEEP_FAR=bf16x3 and the fp32-activation Gram sum (qt_xtx_accumulate_f32).  NOT used
+// by the GPTQ sweep's default trailing update, whose ascending-k fmaf order is part of the parity contract
+// (sgemm_tn.h).
 #pragma once
 #include <vector>
 

@@ -1,9 +1,16 @@
-// See gemm3_tn.h.  The kernel runs the LDS-ring pipeline of ring_pipe.h exactly as xtx_kernel does (R = 8, L = 6,
-// unit = 16 k-rows x (256 A + 256 B columns) = 16 KiB, 2 LDS-DMA per wave and unit), with two differences:
-//   * the A and B panels of a unit come from two plane sets, and the unit sequence of an item walks
-//     k-chunk (128 rows) -> plane product (6) -> 8 units, so one 8-phase body stays inside one plane pair;
-//   * the epilogue applies the tile to C (C -= acc / C = acc) or stores a slab for the ordered reduction.
+// See gemm3_tn.h.  The kernel runs the LDS-ring pipeline of ring_pipe.h (the functions xtx_kernel calls) on TRI-UNITS:
+// 16 k-rows of all three planes of both operands = 3 x (8 KiB A + 8 KiB B) = 48 KiB, three of them resident (144 KiB),
+// 6 LDS-DMA per wave and tri-unit, one tri-unit in flight behind a counted vmcnt(6) (ring_pipe.h, instance
+// "gemm3_kernel").  A phase reads the 18 fragments of its tri-unit once (A hi / mid / lo x 4, B hi / mid / lo x 2) and
+// runs all six plane products on them, smallest first: 48 MFMAs per wave between two barrier pairs, and every plane
+// panel of a k-slab is staged from L2 once -- 6 panel stagings per 64 rows for the 6 products.
+// The loop this replaces (QT_G3_LOOP=chunk, kept for the A/B: R = 8, L = 6, unit = 16 k-rows of ONE plane pair = 16 KiB)
+// walks k-chunk (64 rows) -> plane product (6) -> 4 units and stages the two panels of every product again: 12
+// stagings per chunk (hi three times, mid twice), 8 MFMAs per wave between barrier pairs.  Both sum the same products
+// in the same accumulator; the order differs (chunk -> product -> unit there, 16-row slab -> product here).
+// The epilogue applies the tile to C (C -= acc / C = acc / C += acc) or stores a slab for the ordered reduction.
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <map>
@@ -15,9 +22,12 @@
 
 namespace {
 
-constexpr int RING = 8;                         // units resident in LDS (128 KiB)
+constexpr int RING = 8;                         // chunk loop: units resident in LDS (128 KiB)
 constexpr int CH_ROWS = G3_CHUNK_ROWS;          // k rows per chunk (64)
-constexpr int CH_UNITS = 6 * (CH_ROWS / UT);    // 24 units: 6 plane products x 4 units
+constexpr int CH_UNITS = 6 * (CH_ROWS / UT);    // chunk loop: 24 units per chunk, 6 plane products x 4 units
+constexpr int TRING = 3;                        // tri-unit loop: tri-units resident in LDS (144 KiB)
+constexpr int TRI_BYTES = 3 * UNIT_BYTES;       // planes hi, mid, lo, each the 16 KiB image of ring_pipe.h
+constexpr int TRI_DMA = 6;                      // LDS-DMA instructions per wave and tri-unit
 static_assert(CH_ROWS / UT == 4, "the phase code below recomputes the source pointers every 4 units");
 // plane (0 = hi, 1 = mid, 2 = lo) of the A / B operand in product pr, two bits each, smallest product first:
 //   pr:  0      1      2       3       4       5
@@ -25,6 +35,8 @@ static_assert(CH_ROWS / UT == 4, "the phase code below recomputes the source poi
 //   B :  hi     lo     mid     hi      mid     hi
 constexpr unsigned PA_BITS = 2u | (0u << 2) | (1u << 4) | (1u << 6) | (0u << 8) | (0u << 10);
 constexpr unsigned PB_BITS = 0u | (2u << 2) | (1u << 4) | (0u << 6) | (1u << 8) | (0u << 10);
+constexpr int g3_plane_a(int pr) { return (PA_BITS >> (2 * pr)) & 3u; }
+constexpr int g3_plane_b(int pr) { return (PB_BITS >> (2 * pr)) & 3u; }
 
 struct G3Params {
     const char* Apl;
@@ -41,10 +53,10 @@ struct G3Params {
     int64_t bsA_bytes, bsB_bytes, bsC, bsSlabs;   // problem blockIdx.y of a batch
 };
 
-template <int MODE>
+// TRI: the tri-unit loop (default); !TRI: the chunk loop (QT_G3_LOOP=chunk)
+template <int MODE, bool TRI>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
-    constexpr int LEAD = 6;
-    __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES];
+    __shared__ __attribute__((aligned(16))) char ring[TRI ? TRING * TRI_BYTES : RING * UNIT_BYTES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -63,7 +75,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     const int c_hi = __builtin_amdgcn_readfirstlane(itp->c_hi);
     const int slab_idx = __builtin_amdgcn_readfirstlane(itp->slab);
     const int ti = it_tile >> 16, tj = it_tile & 0xFFFF;
-    const int nu = (c_hi - c_lo) * CH_UNITS;   // a multiple of 24 (items are >= 2 chunks: nu >= 48)
+    // chunk loop: a multiple of 24 (items are >= 2 chunks: nu >= 48); tri-unit loop: a multiple of 4, >= 8
+    const int nu = (c_hi - c_lo) * (TRI ? CH_ROWS / UT : CH_UNITS);
 
     // staging geometry: as xtx_kernel (wave w fills k rows 4*(w&3)..+3 of column group w>>2; XOR swizzle of
     // the 16-B chunk index on the SOURCE address)
@@ -80,25 +93,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     const unsigned dst_wave =
         __builtin_amdgcn_readfirstlane(ring_lds + (wave >> 2) * 4096 + (wave & 3) * 1024);
 
-    // unit i of the item -> (k chunk, plane product, 16-row slice): scalar source pointers of both panels
     const int64_t ustride = (int64_t)UT * p.ld2, ustrideB = (int64_t)UT * p.ld2B;
-    auto unit_src = [&](int i, const char*& a, const char*& b) {
-        const int g = i >> 2, j = i & 3;
-        const int c = g / 6, pr = g - 6 * c;
-        const int64_t plA = (PA_BITS >> (2 * pr)) & 3u, plB = (PB_BITS >> (2 * pr)) & 3u;
-        const int64_t row = (int64_t)(c_lo + c) * CH_ROWS + j * UT;
-        a = p.Apl + plA * p.plane_bytes + (p.rowA0 + row) * p.ld2;
-        b = p.Bpl + plB * p.plane_bytesB + (p.rowB0 + row) * p.ld2B;
-    };
-    auto issue = [&](int i, int slot) {
-        const char *a, *b;
-        unit_src(i, a, b);
-        const unsigned d = dst_wave + (unsigned)slot * UNIT_BYTES;
-        glds16_pair2(voffA, voffB, a, b, d, d + 8192);
-    };
-    // steady state: running pointers; a body of 8 phases issues units u+6 .. u+13, the plane pair changes
-    // at units u+8 and u+12 (phase slots 2 and 6), where the pointers are recomputed
-    const char *runA = nullptr, *runB = nullptr;
 
     // fragment read geometry: as xtx_kernel
     const int g = lane >> 4, il = lane & 15, q = il >> 2, pp = il & 3;
@@ -118,50 +113,130 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
 
-    s16x8 fa[4], fb[2];
-    // stays a lambda: with the ladder called straight from phase() hipcc emits a different kernel (see profiles/
-    // ring_pipe_isa_parent_vs_refactor.txt)
-    auto drain_wait = [&](int u) {
-        ring_drain_wait<2, LEAD>(nu - u - 2);
-    };
-    auto phase = [&](auto slot_c, auto steady_c, int u) {
-        constexpr int S = decltype(slot_c)::value;
-        constexpr bool STEADY = decltype(steady_c)::value;
-        constexpr int ISLOT = (S + LEAD) & (RING - 1);
-        const char* base = ring + S * UNIT_BYTES;
+    if constexpr (TRI) {
+        // running scalar source pointers (plane hi) of the next tri-unit to issue
+        const char* runA = p.Apl + (p.rowA0 + (int64_t)c_lo * CH_ROWS) * p.ld2;
+        const char* runB = p.Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
+        auto issue3 = [&](int slot) {
+            const unsigned d = dst_wave + (unsigned)slot * TRI_BYTES;
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) fa[mi] = tr_load8(base + aoff[mi]);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) fb[ni] = tr_load8(base + boff[ni]);
-        if (STEADY) {
-            if (S == 2 || S == 6) unit_src(u + LEAD, runA, runB);
-            const unsigned d = dst_wave + (unsigned)ISLOT * UNIT_BYTES;
-            glds16_pair2(voffA, voffB, runA, runB, d, d + 8192);
+            for (int pl = 0; pl < 3; ++pl)
+                glds16_pair2(voffA, voffB, runA + pl * p.plane_bytes, runB + pl * p.plane_bytesB, d + pl * UNIT_BYTES,
+                             d + pl * UNIT_BYTES + 8192);
             runA += ustride;
             runB += ustrideB;
-            wait_vmcnt<2 * (LEAD - 1)>();
-        } else if (u + LEAD < nu) {
-            issue(u + LEAD, ISLOT);
-            wait_vmcnt<2 * (LEAD - 1)>();
-        } else {
-            drain_wait(u);
-        }
-        ring_sync_math([&] { ring_mma32<false>(fa, fb, acc); });
-    };
-    auto body8 = [&](auto steady_c, int u) {
-        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, steady_c, uu); }, u);
-    };
-
-    if (nu > 0) {
+        };
+        s16x8 fa[3][4], fb[3][2];   // [plane][tile]: every fragment of a tri-unit is read once and serves 2-3 products
+        // Phase u: tri-unit u+2 is issued into the slot tri-unit u-1 has left, and tri-unit u+1 is retired with u+2
+        // still in flight -- by group A behind the barrier that opens MATH(u) and at its end, by group B at both ends
+        // of LOAD(u): the same barrier interval for both (ring_pipe.h, instance "gemm3_kernel").
+        auto phase = [&](auto slot_c, int u) {
+            constexpr int S = decltype(slot_c)::value;
+            constexpr int ISLOT = (S + 2) % TRING;
+            const bool more = u + 2 < nu;
+            if (group_b && more) issue3(ISLOT);
+            const char* base = ring + S * TRI_BYTES;
 #pragma unroll
-        for (int i = 0; i < LEAD; ++i) issue(i, i);   // nu >= 24 > LEAD
-        wait_vmcnt<2 * (LEAD - 1)>();
-        ring_stagger_begin(group_b);
-        unit_src(LEAD, runA, runB);
-        int u = 0;
-        for (; u + 8 + LEAD <= nu; u += 8) body8(std::true_type{}, u);
-        for (; u + 8 <= nu; u += 8) body8(std::false_type{}, u);
-        ring_stagger_end(group_b);
+            for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) fa[pl][mi] = tr_load8(base + pl * UNIT_BYTES + aoff[mi]);
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) fb[pl][ni] = tr_load8(base + pl * UNIT_BYTES + boff[ni]);
+            }
+            if (group_b) ring_drain_wait<TRI_DMA, 2>(nu - u - 2);
+            ring_sync_math(
+                [&] {
+                    if (!group_b && more) issue3(ISLOT);
+                },
+                [&] {
+                    ring_mma32<false>(fa[g3_plane_a(0)], fb[g3_plane_b(0)], acc);
+                    ring_mma32<false>(fa[g3_plane_a(1)], fb[g3_plane_b(1)], acc);
+                    ring_mma32<false>(fa[g3_plane_a(2)], fb[g3_plane_b(2)], acc);
+                    ring_mma32<false>(fa[g3_plane_a(3)], fb[g3_plane_b(3)], acc);
+                    ring_mma32<false>(fa[g3_plane_a(4)], fb[g3_plane_b(4)], acc);
+                    ring_mma32<false>(fa[g3_plane_a(5)], fb[g3_plane_b(5)], acc);
+                },
+                [&] {
+                    if (!group_b) ring_drain_wait<TRI_DMA, 2>(nu - u - 2);
+                });
+        };
+        if (nu > 0) {
+            issue3(0);
+            issue3(1);   // nu >= 8
+            wait_vmcnt<TRI_DMA>();
+            ring_stagger_begin(group_b);
+            int u = 0;
+            for (; u + TRING <= nu; u += TRING) ring_body<TRING>(phase, u);
+            if (u < nu) phase(std::integral_constant<int, 0>{}, u);   // u is a multiple of 3 here: slots 0, 1
+            if (u + 1 < nu) phase(std::integral_constant<int, 1>{}, u + 1);
+            ring_stagger_end(group_b);
+        }
+    } else {
+        constexpr int LEAD = 6;
+        // unit i of the item -> (k chunk, plane product, 16-row slice): scalar source pointers of both panels
+        auto unit_src = [&](int i, const char*& a, const char*& b) {
+            const int g = i >> 2, j = i & 3;
+            const int c = g / 6, pr = g - 6 * c;
+            const int64_t plA = (PA_BITS >> (2 * pr)) & 3u, plB = (PB_BITS >> (2 * pr)) & 3u;
+            const int64_t row = (int64_t)(c_lo + c) * CH_ROWS + j * UT;
+            a = p.Apl + plA * p.plane_bytes + (p.rowA0 + row) * p.ld2;
+            b = p.Bpl + plB * p.plane_bytesB + (p.rowB0 + row) * p.ld2B;
+        };
+        auto issue = [&](int i, int slot) {
+            const char *a, *b;
+            unit_src(i, a, b);
+            const unsigned d = dst_wave + (unsigned)slot * UNIT_BYTES;
+            glds16_pair2(voffA, voffB, a, b, d, d + 8192);
+        };
+        // steady state: running pointers; a body of 8 phases issues units u+6 .. u+13, the plane pair changes
+        // at units u+8 and u+12 (phase slots 2 and 6), where the pointers are recomputed
+        const char *runA = nullptr, *runB = nullptr;
+
+        s16x8 fa[4], fb[2];
+        // stays a lambda: with the ladder called straight from phase() hipcc emits a different kernel (see profiles/
+        // ring_pipe_isa_parent_vs_refactor.txt)
+        auto drain_wait = [&](int u) {
+            ring_drain_wait<2, LEAD>(nu - u - 2);
+        };
+        auto phase = [&](auto slot_c, auto steady_c, int u) {
+            constexpr int S = decltype(slot_c)::value;
+            constexpr bool STEADY = decltype(steady_c)::value;
+            constexpr int ISLOT = (S + LEAD) & (RING - 1);
+            const char* base = ring + S * UNIT_BYTES;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) fa[mi] = tr_load8(base + aoff[mi]);
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb[ni] = tr_load8(base + boff[ni]);
+            if (STEADY) {
+                if (S == 2 || S == 6) unit_src(u + LEAD, runA, runB);
+                const unsigned d = dst_wave + (unsigned)ISLOT * UNIT_BYTES;
+                glds16_pair2(voffA, voffB, runA, runB, d, d + 8192);
+                runA += ustride;
+                runB += ustrideB;
+                wait_vmcnt<2 * (LEAD - 1)>();
+            } else if (u + LEAD < nu) {
+                issue(u + LEAD, ISLOT);
+                wait_vmcnt<2 * (LEAD - 1)>();
+            } else {
+                drain_wait(u);
+            }
+            ring_sync_math([&] { ring_mma32<false>(fa, fb, acc); });
+        };
+        auto body8 = [&](auto steady_c, int u) {
+            ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, steady_c, uu); }, u);
+        };
+
+        if (nu > 0) {
+#pragma unroll
+            for (int i = 0; i < LEAD; ++i) issue(i, i);   // nu >= 24 > LEAD
+            wait_vmcnt<2 * (LEAD - 1)>();
+            ring_stagger_begin(group_b);
+            unit_src(LEAD, runA, runB);
+            int u = 0;
+            for (; u + 8 + LEAD <= nu; u += 8) body8(std::true_type{}, u);
+            for (; u + 8 <= nu; u += 8) body8(std::false_type{}, u);
+            ring_stagger_end(group_b);
+        }
     }
 
     // ---- epilogue ----
@@ -314,9 +389,17 @@ int qt_gemm3_launch(const G3Args& a, hipStream_t stream) {
     p.bsC = a.bsC;
     p.bsSlabs = a.bsSlabs;
     const dim3 grid(a.n_items, nb);
-    if (a.mode == G3_SUB) hipLaunchKernelGGL((gemm3_kernel<G3_SUB>), grid, dim3(NTHREADS), 0, stream, p);
-    else if (a.mode == G3_ADD) hipLaunchKernelGGL((gemm3_kernel<G3_ADD>), grid, dim3(NTHREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gemm3_kernel<G3_SET>), grid, dim3(NTHREADS), 0, stream, p);
+    // read per call: the tests run both loops on the same inputs in one process
+    const char* loop_env = getenv("QT_G3_LOOP");
+    const bool chunk_loop = loop_env && strcmp(loop_env, "chunk") == 0;
+    auto launch = [&](auto tri_c) {
+        constexpr bool TRI = decltype(tri_c)::value;
+        if (a.mode == G3_SUB) hipLaunchKernelGGL((gemm3_kernel<G3_SUB, TRI>), grid, dim3(NTHREADS), 0, stream, p);
+        else if (a.mode == G3_ADD) hipLaunchKernelGGL((gemm3_kernel<G3_ADD, TRI>), grid, dim3(NTHREADS), 0, stream, p);
+        else hipLaunchKernelGGL((gemm3_kernel<G3_SET, TRI>), grid, dim3(NTHREADS), 0, stream, p);
+    };
+    if (chunk_loop) launch(std::false_type{});
+    else launch(std::true_type{});
     QT_LAUNCH_CHECK();
     if (a.n_red > 0) {
         hipLaunchKernelGGL(gemm3_reduce_kernel, dim3(a.n_red, 16, nb), dim3(256), 0, stream, (const float*)a.slabs, a.red,
@@ -417,11 +500,13 @@ void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items,
 // ---- C-ABI face (tests and micro-benchmarks; the hot path calls qt_gemm3_launch from cholesky.hip) ----
 // C (-)= A^T B with A [k][lda], B [k][ldb] fp32, k a multiple of 128.  kind 0: every tile whole (C -= A^T B);
 // kind 1: split along k into slabs (C = A^T B), as the inverse's block-row product.  Synchronous table upload.
+constexpr size_t G3_TEST_TABLE_BYTES = (size_t)1 << 20;   // item + reduction tables
+constexpr size_t G3_TEST_SLACK = 1024;                     // alignment of the caller's pointer
 static size_t g3_test_layout(int M, int N, int k, int64_t& ldp, size_t& planes_bytes, size_t& slabs_bytes) {
     ldp = (int64_t)qt_align_up((size_t)std::max(M, N), 256);
     planes_bytes = (size_t)3 * k * ldp * 2;
     slabs_bytes = (size_t)2 * NUM_CU * BT * BT * 4;
-    return 2 * planes_bytes + slabs_bytes + (size_t)(1 << 20) + 1024;
+    return 2 * planes_bytes + slabs_bytes + G3_TEST_TABLE_BYTES + G3_TEST_SLACK;
 }
 
 extern "C" size_t qt_gemm3_tn_f32_workspace_bytes(int M, int N, int k) {
@@ -431,55 +516,65 @@ extern "C" size_t qt_gemm3_tn_f32_workspace_bytes(int M, int N, int k) {
     return g3_test_layout(M, N, k, ldp, pb, sb);
 }
 
-extern "C" int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
-                               int N, int k, int kind, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(A && B && C && M > 0 && N > 0 && k > 0 && k % 128 == 0, "qt_gemm3_tn_f32: k=%d must be a positive multiple of 128", k);
-    QT_CHECK_ARG(M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0, "qt_gemm3_tn_f32: M, N, lda, ldb must be multiples of 4");
+// The face's work, with what the _ex entry point adds: tri (B lower-triangular in 256-blocks: a tile column's k range
+// starts at its own column, as the block-row products of the Cholesky chain), tight (plane pitch = max(M, N) rounded
+// up to 8 instead of 256: the edge tiles' loads are clamped at colmax) and a batch of problems in one launch.
+static int g3_test_run(const char* who, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
+                       int M, int N, int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB, int64_t bsC,
+                       void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    QT_CHECK_ARG(A && B && C && M > 0 && N > 0 && k > 0 && k % 128 == 0, "%s: k=%d must be a positive multiple of 128", who, k);
+    QT_CHECK_ARG(M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0, "%s: M, N, lda, ldb must be multiples of 4", who);
+    QT_CHECK_ARG(batch >= 1 && bsA % 4 == 0 && bsB % 4 == 0, "%s: batch %d / strides unsupported", who, batch);
     int64_t ldp;
     size_t pb, sb;
     const size_t need = g3_test_layout(M, N, k, ldp, pb, sb);
-    if (!workspace || workspace_bytes < need) {
-        qt_set_error("qt_gemm3_tn_f32: workspace %zu < required %zu", workspace_bytes, need);
+    if (!workspace || workspace_bytes < need * (size_t)batch) {
+        qt_set_error("%s: workspace %zu < required %zu", who, workspace_bytes, need * (size_t)batch);
         return QT_ERR_WORKSPACE;
     }
+    const size_t per = need - G3_TEST_SLACK;   // one problem's planes, slabs and table area: a multiple of 256
+    if (tight) ldp = (int64_t)qt_align_up((size_t)std::max(M, N), 8);   // planes then use less than their share pb
+    const int64_t plane_stride = (int64_t)k * ldp;
     char* ws = (char*)qt_align_up((size_t)workspace, 256);
     unsigned short* Apl = (unsigned short*)ws;
     unsigned short* Bpl = (unsigned short*)(ws + pb);
     float* slabs = (float*)(ws + 2 * pb);
-    char* tab = ws + 2 * pb + sb;
-    QT_HIP(hipMemsetAsync(ws, 0, 2 * pb, stream));   // columns M..ldp / N..ldp of the planes
-    int rc = qt_split3_launch(A, lda, k, M, Apl, ldp, (int64_t)k * ldp, 0, 0, 0, stream);
+    char* tab = ws + 2 * pb + sb;   // problem 0's table serves the batch
+    for (int b = 0; b < batch; ++b) QT_HIP(hipMemsetAsync(ws + (size_t)b * per, 0, 2 * pb, stream));   // columns M.. / N.. of the planes
+    int rc = qt_split3_launch(A, lda, k, M, Apl, ldp, plane_stride, 0, 0, 0, stream, batch, bsA, (int64_t)(per / 2));
     if (rc) return rc;
-    rc = qt_split3_launch(B, ldb, k, N, Bpl, ldp, (int64_t)k * ldp, 0, 0, 0, stream);
+    rc = qt_split3_launch(B, ldb, k, N, Bpl, ldp, plane_stride, 0, 0, 0, stream, batch, bsB, (int64_t)(per / 2));
     if (rc) return rc;
     const int Tm = (M + BT - 1) / BT, Tn = (N + BT - 1) / BT, nch = k / CH_ROWS;
+    constexpr int TRI_STEP = 256 / G3_CHUNK_ROWS;
+    QT_CHECK_ARG(!tri || TRI_STEP * (Tn - 1) < nch, "%s: tri needs k > 256 * (tile columns - 1)", who);
     std::vector<G3Item> items;
     std::vector<G3Red> red;
     if (kind == 0) {
         for (int ti = 0; ti < Tm; ++ti)
-            for (int tj = 0; tj < Tn; ++tj) items.push_back({(ti << 16) | tj, 0, nch, -1});
+            for (int tj = 0; tj < Tn; ++tj) items.push_back({(ti << 16) | tj, tri ? TRI_STEP * tj : 0, nch, -1});
     } else {
         // every tile cut into pieces of <= 2 chunks (bounded by the slab area)
         int next = 0;
         for (int ti = 0; ti < Tm; ++ti)
             for (int tj = 0; tj < Tn; ++tj) {
-                const int pieces = std::min(nch / 2, std::max(1, 2 * NUM_CU / (Tm * Tn)));   // >= 2 chunks each
+                const int lo = tri ? TRI_STEP * tj : 0, n = nch - lo;
+                const int pieces = std::min(n / 2, std::max(1, 2 * NUM_CU / (Tm * Tn)));   // >= 2 chunks each
                 red.push_back({(ti << 16) | tj, next, pieces, 0});
                 for (int s = 0; s < pieces; ++s)
-                    items.push_back({(ti << 16) | tj, (int)((long)nch * s / pieces), (int)((long)nch * (s + 1) / pieces), next++});
+                    items.push_back({(ti << 16) | tj, lo + (int)((long)n * s / pieces), lo + (int)((long)n * (s + 1) / pieces), next++});
             }
-        QT_CHECK_ARG((size_t)next * BT * BT * 4 <= sb, "qt_gemm3_tn_f32: too many tiles for the test face");
+        QT_CHECK_ARG((size_t)next * BT * BT * 4 <= sb, "%s: too many tiles for the test face", who);
     }
     const size_t ib = items.size() * sizeof(G3Item), rb = red.size() * sizeof(G3Red);
-    QT_CHECK_ARG(qt_align_up(ib, 256) + rb <= (size_t)(1 << 20), "qt_gemm3_tn_f32: table too large for the test face");
+    QT_CHECK_ARG(qt_align_up(ib, 256) + rb <= G3_TEST_TABLE_BYTES, "%s: table too large for the test face", who);
     QT_HIP(hipStreamSynchronize(stream));
     QT_HIP(hipMemcpy(tab, items.data(), ib, hipMemcpyHostToDevice));
     if (rb) QT_HIP(hipMemcpy(tab + qt_align_up(ib, 256), red.data(), rb, hipMemcpyHostToDevice));
     G3Args g;
     g.Apl = Apl;
     g.Bpl = Bpl;
-    g.plane_stride = (int64_t)k * ldp;
+    g.plane_stride = plane_stride;
     g.ld = ldp;
     g.rowA0 = g.rowB0 = 0;
     g.colA0 = g.colB0 = 0;
@@ -494,7 +589,26 @@ extern "C" int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int6
     g.n_items = (int)items.size();
     g.red = (const G3Red*)(tab + qt_align_up(ib, 256));
     g.n_red = (int)red.size();
+    g.batch = batch;
+    g.bsApl = g.bsBpl = (int64_t)(per / 2);
+    g.bsC = bsC;
+    g.bsSlabs = (int64_t)(per / 4);
     return qt_gemm3_launch(g, stream);
+}
+
+extern "C" int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
+                               int N, int k, int kind, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+    return g3_test_run("qt_gemm3_tn_f32", A, lda, B, ldb, C, ldc, M, N, k, kind, 0, 0, 1, 0, 0, 0, workspace, workspace_bytes,
+                       (hipStream_t)stream_);
+}
+
+// The same for `batch` problems of one shape (problem b at A + b * bsA, B + b * bsB, C + b * bsC; workspace: batch times
+// qt_gemm3_tn_f32_workspace_bytes), with a block-triangular B (tri) and / or unpadded planes (tight): see g3_test_run.
+extern "C" int qt_gemm3_tn_f32_ex(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
+                                  int N, int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB,
+                                  int64_t bsC, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+    return g3_test_run("qt_gemm3_tn_f32_ex", A, lda, B, ldb, C, ldc, M, N, k, kind, tri, tight, batch, bsA, bsB, bsC, workspace,
+                       workspace_bytes, (hipStream_t)stream_);
 }
 
 // ---- a7 for fp32 activations (an fp32 checkpoint): G += X^T X with X fp32 [n_tokens, K] --------------------------

@@ -29,7 +29,27 @@
 // The three instances:
 //   xtx_kernel    R 8, L 6, unit = 16 tokens (16 KiB),             N 2: vmcnt(10), 5 units = 80 KiB per CU in flight
 //   xtx16_kernel  R 5, L 3, unit = a pair of those ("double", 32 KiB), N 4: vmcnt(8), 2 doubles = 64 KiB in flight
-//   gemm3_kernel  R 8, L 6, unit = 16 k-rows of one plane pair (16 KiB), N 2: vmcnt(10), 5 units = 80 KiB in flight
+//   gemm3_kernel  (chunk loop, QT_G3_LOOP=chunk)  R 8, L 6, unit = 16 k-rows of one plane pair (16 KiB), N 2:
+//                 vmcnt(10), 5 units = 80 KiB in flight
+//   gemm3_kernel  R 3, unit = 16 k-rows of all three planes of both operands ("tri-unit", 48 KiB), N 6: vmcnt(6), one
+//                 tri-unit = 48 KiB in flight -- the half-phase form below
+//
+// R = 3, HALF-PHASE ISSUE (gemm3_kernel).  Three 48 KiB tri-units are all the LDS holds, and the scheme above then
+// allows L = 1 only: its wait would be vmcnt(0) right behind the issue, with nothing in flight under the MFMAs.  What
+// forbids L = 2 = R-1 is group A alone (its issue in LOAD(u), interval 2u, beside group B's reads of unit u-1 that
+// retire in 2u), so this instance leads by two units and moves group A's issue and wait half a phase down
+// (ring_sync_math's pre / post hooks); group B keeps them in LOAD.  Phase u:
+//   group A: LOAD(u) = { reads of unit u } ; MATH(u) = { lgkmcnt(0) ; issue unit u+2 ; MFMAs ; vmcnt(6) }
+//   group B: LOAD(u) = { issue unit u+2 ; reads of unit u ; vmcnt(6) } ; MATH(u) = { lgkmcnt(0) ; MFMAs }
+//   Unit v is issued by A in MATH(v-2) and by B in LOAD(v-2): both interval 2v-3; it is retired by A at the end of
+//   MATH(v-1) and by B at the end of LOAD(v-1): both interval 2v-1, the wait a vmcnt(6) because unit v+1 (6 DMA
+//   instructions per wave) was issued earlier in that interval and stays in flight.
+//   WAR: the slot's previous unit v-3 had its reads retired at the lgkmcnt(0) of MATH(v-3): intervals 2v-5 (A) /
+//        2v-4 (B); the issue in 2v-3 follows the barrier that ends 2v-4, and A's also follows its own barrier + wait.
+//   RAW: unit v is first read in interval 2v (A), after the barrier that ends 2v-1, where every wave has retired it.
+//   Prologue: units 0 and 1 are issued, vmcnt(6) retires unit 0 in front of the stagger's first barrier; unit 1 is
+//   retired in interval 1 by the waits of phase 0.  Drain: nothing is issued from phase nu-2 on, whose wait is
+//   vmcnt(0) (ring_drain_wait<6, 2>).  A tri-unit has three barrier intervals (about three MATH lengths) to land.
 //
 // LDS-DMA from inline asm: hipcc does not track it, so it inserts no vmcnt drain in front of later
 // ds_reads or barriers.  Every completion is ordered by hand (counted vmcnt + s_barrier, as above).
@@ -147,7 +167,7 @@ __device__ __forceinline__ void ring_mma16(const s16x8 (&fa)[8], const s16x8 (&f
 
 // The counted wait of a phase that has nothing left to issue: `later` units after u+1 exist (later = nu - u - 2),
 // and exactly those may stay in flight.  N DMA instructions per unit and wave, lead L:
-// N 2, L 6 -> vmcnt 10/8/6/4/2/0;  N 4, L 3 -> 8/4/0.
+// N 2, L 6 -> vmcnt 10/8/6/4/2/0;  N 4, L 3 -> 8/4/0;  N 6, L 2 (the half-phase form) -> 6/0.
 template <int N, int K>
 __device__ __forceinline__ void ring_drain_step(int later) {
     if constexpr (K == 0) wait_vmcnt<0>();
@@ -177,6 +197,26 @@ __device__ __forceinline__ void ring_sync_math(Math&& math) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// The same with a hook behind the opening barrier and the lgkmcnt(0) (pre: e.g. an LDS-DMA issue into a slot whose last
+// readers that barrier has just passed) and one in front of the closing barrier (post: a counted vmcnt).
+template <class Pre, class Math, class Post>
+__device__ __forceinline__ void ring_sync_math(Pre&& pre, Math&& math, Post&& post) {
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    pre();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+    math();
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    post();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // The two-group stagger.  Begin (behind the prologue's wait for unit 0): one barrier for everyone, one more for
 // group B, which from here on runs one interval behind.  End: group A's barrier that pairs with group B's last.
 __device__ __forceinline__ void ring_stagger_begin(bool group_b) {
@@ -190,15 +230,17 @@ __device__ __forceinline__ void ring_stagger_end(bool group_b) {
 }
 
 // One trip round a ring of SLOTS slots: phase(slot as an integral_constant, unit index), so that every LDS address
-// of a phase is an immediate.  8: xtx_kernel / gemm3_kernel, 5: xtx16_kernel.
+// of a phase is an immediate.  8: xtx_kernel / gemm3_kernel's chunk loop, 5: xtx16_kernel, 3: gemm3_kernel.
 template <int SLOTS, class Phase>
 __device__ __forceinline__ void ring_body(Phase&& phase, int u) {
-    static_assert(SLOTS == 5 || SLOTS == 8, "unrolled by hand");
+    static_assert(SLOTS == 3 || SLOTS == 5 || SLOTS == 8, "unrolled by hand");
     phase(std::integral_constant<int, 0>{}, u);
     phase(std::integral_constant<int, 1>{}, u + 1);
     phase(std::integral_constant<int, 2>{}, u + 2);
-    phase(std::integral_constant<int, 3>{}, u + 3);
-    phase(std::integral_constant<int, 4>{}, u + 4);
+    if constexpr (SLOTS >= 5) {
+        phase(std::integral_constant<int, 3>{}, u + 3);
+        phase(std::integral_constant<int, 4>{}, u + 4);
+    }
     if constexpr (SLOTS == 8) {
         phase(std::integral_constant<int, 5>{}, u + 5);
         phase(std::integral_constant<int, 6>{}, u + 6);

@@ -1106,6 +1106,29 @@ def gemm3_tn(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, kind: int = 0):
     return C
 
 
+def gemm3_tn_ex(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, kind: int = 0, tri: bool = False, tight: bool = False):
+    """``gemm3_tn`` for one problem (A [k, M], B [k, N], C [M, N]) or a batch in one launch (A [n, k, M], B [n, k, N],
+    C [n, M, N], contiguous).  tri: B is lower-triangular in 256-blocks and every tile column's k range starts at its own
+    column; tight: unpadded internal planes (edge tiles clamp their loads)."""
+    lib = load()
+    if A.dim() == 2:
+        A, B, C3 = A[None], B[None], C[None]
+    else:
+        C3 = C
+    _req(A, torch.float32, "A", 3)
+    _req(B, torch.float32, "B", 3)
+    _req(C3, torch.float32, "C", 3)
+    n, k, M = A.shape
+    n2, k2, N = B.shape
+    assert n == n2 and k == k2 and tuple(C3.shape) == (n, M, N)
+    assert A.is_contiguous() and B.is_contiguous() and C3.is_contiguous()
+    ws = workspace(n * lib.qt_gemm3_tn_f32_workspace_bytes(M, N, k), A.device, "gemm3")
+    check("qt_gemm3_tn_f32_ex", lib.qt_gemm3_tn_f32_ex(A.data_ptr(), M, B.data_ptr(), N, C3.data_ptr(), N, M, N, k, kind,
+                                                       int(tri), int(tight), n, k * M, k * N, M * N, ws.data_ptr(),
+                                                       ws.numel(), _stream()))
+    return C
+
+
 # ---- fp32 TN GEMM (tests / micro-benchmarks) ------------------------------------------------
 def sgemm_tn(A: torch.Tensor, B: torch.Tensor, Cin: Optional[torch.Tensor] = None, mode: int = 1,
              skip_zero_k: bool = False, allow_split_k: bool = False, out: Optional[torch.Tensor] = None):
