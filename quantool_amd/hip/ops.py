@@ -45,6 +45,15 @@ def _act16(X: torch.Tensor, name: str) -> int:
     return QT_BF16 if X.dtype == torch.bfloat16 else QT_F16
 
 
+def _rows16(X2: torch.Tensor) -> torch.Tensor:
+    """[n, K] 16-bit rows as the Gram and statistics kernels load them (16 bytes per lane): unit column stride, a start
+    that is 16-byte aligned and a pitch that is a multiple of 8 elements.  A view that is none of that (a column range
+    of a wider tensor) is copied to a contiguous tensor first, as ``xtx_accumulate_f32`` does."""
+    if X2.stride(1) != 1 or X2.data_ptr() % 16 or (X2.shape[0] > 1 and X2.stride(0) % 8):
+        X2 = X2.contiguous()
+    return X2
+
+
 _FP32_ACT_WARNED = False
 
 
@@ -126,9 +135,7 @@ def xtx_accumulate(X: torch.Tensor, G: torch.Tensor) -> None:
         raise ValueError("G must be contiguous [K, K]")
     if X.shape[-1] != K:
         raise ValueError(f"X last dim {X.shape[-1]} != K {K}")
-    X2 = X.reshape(-1, K)
-    if X2.stride(1) != 1:
-        X2 = X2.contiguous()
+    X2 = _rows16(X.reshape(-1, K))
     n = X2.shape[0]
     if n == 0:
         return
@@ -170,9 +177,7 @@ def act_stats_accumulate(X: torch.Tensor, abs_sum: Optional[torch.Tensor] = None
     lib = load()
     xdt = _act16(X, "X")
     K = X.shape[-1]
-    X2 = X.reshape(-1, K)
-    if X2.stride(1) != 1:
-        X2 = X2.contiguous()
+    X2 = _rows16(X.reshape(-1, K))
     n = X2.shape[0]
     for name, t in (("abs_sum", abs_sum), ("cmin", cmin), ("cmax", cmax)):
         if t is not None:

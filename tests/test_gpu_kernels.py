@@ -158,6 +158,7 @@ def test_xtx_rejects_bad_shapes(ops, dev):
 # ------------------------------------------------------------------------------------ a12/a13
 @pytest.mark.parametrize("n_tokens,K", [(50, 64), (1000, 264), (5000, 4096)])
 def test_act_stats(ops, oracle, dev, n_tokens, K):
+    """The full grid for this kernel is in tests/test_gpu_plumbing_kernels.py."""
     xb = synth_activations(n_tokens, K, seed=7)
     X = bits_to_bf16_tensor(xb, dev)
     s = torch.zeros(K, dtype=torch.float32, device=dev)
@@ -388,6 +389,7 @@ def test_cholesky_reports_non_pd(ops, dev):
 @pytest.mark.parametrize("R,K,gs,sym,dtype", [(16, 256, 128, True, "f32"), (33, 384, 128, False, "f32"),
                                              (8, 512, -1, True, "f32"), (16, 256, 64, True, "bf16")])
 def test_qparams_exact(ops, oracle, dev, R, K, gs, sym, dtype):
+    """The full grid for this kernel is in tests/test_gpu_plumbing_kernels.py."""
     Wn = synth_weight(R, K, seed=R)
     if dtype == "bf16":
         bits = oracle.f32_to_bf16_bits(Wn)
@@ -405,6 +407,7 @@ def test_qparams_exact(ops, oracle, dev, R, K, gs, sym, dtype):
 
 
 def test_weight_gather(ops, dev):
+    """The full grid for this kernel is in tests/test_gpu_plumbing_kernels.py."""
     R, K = 20, 136
     W = torch.randn(R, K, device=dev).to(torch.bfloat16)
     perm = torch.randperm(K, device=dev).to(torch.int32)
@@ -456,6 +459,7 @@ def test_sweep_bit_exact_given_same_U(ops, oracle, dev, R, K, gs, sym):
 # ------------------------------------------------------------------------------------- a14
 @pytest.mark.parametrize("R,K,perm", [(16, 64, False), (70, 264, True), (64, 4096, True), (5, 20, False), (300, 520, True), (516, 36, False)])
 def test_pack_and_dequant_exact(ops, oracle, dev, R, K, perm):
+    """The full grid for this kernel is in tests/test_gpu_plumbing_kernels.py."""
     rng = np.random.default_rng(R * K)
     Q = rng.integers(-8, 8, size=(R, K)).astype(np.int8)  # levels in ORIGINAL column order
     col_src_np = rng.permutation(K).astype(np.int32) if perm else None

@@ -51,6 +51,28 @@ def test_qparams_asymmetric_known_answer(oracle):
     assert np.array_equal(s, sc) and np.array_equal(z, zc)
 
 
+@pytest.mark.parametrize("bits", [2, 3])
+def test_qparams_at_two_and_three_bits_follow_upstreams_formula(oracle, bits):
+    """tests/test_gpu_plumbing_kernels.py holds the observer to the oracle at 2 and 3 bits too: there the oracle is
+    upstream's (max - min) / (qmax - qmin), respectively amax / ((qmax - qmin) / 2), on the range [-2^(b-1), 2^(b-1) - 1]."""
+    qmin, qmax = np.float32(-(2 ** (bits - 1))), np.float32(2 ** (bits - 1) - 1)
+    assert oracle.calculate_range(bits) == (float(qmin), float(qmax)) and qmax - qmin == 2 ** bits - 1
+    W = (np.random.default_rng(bits).standard_normal((9, 120)) * 0.05).astype(np.float32)
+    W[0, :40] = np.abs(W[0, :40]) + np.float32(0.01)                     # all-positive: min clamps to 0
+    W[1, 40:80] = 0                                                      # all-zero: the eps clamp
+    Wg = W.reshape(9, 3, 40)
+    mn, mx = np.minimum(Wg.min(axis=2), np.float32(0)), np.maximum(Wg.max(axis=2), np.float32(0))
+    eps = np.finfo(np.float32).eps
+    s, z = oracle.minmax_qparams(W, 40, True, bits)
+    assert np.array_equal(s, np.maximum(np.maximum(np.abs(mn), np.abs(mx)) / ((qmax - qmin) / np.float32(2)), eps))
+    assert not z.any() and s[1, 1] == eps
+    s, z = oracle.minmax_qparams(W, 40, False, bits)
+    want = np.maximum((mx - mn) / (qmax - qmin), eps)
+    assert np.array_equal(s, want) and s.dtype == np.float32
+    assert np.array_equal(z, np.clip(np.rint(qmin - mn / want), qmin, qmax))
+    assert z[0, 0] == qmin and z[1, 1] == qmin and z.min() >= qmin and z.max() <= qmax and len(np.unique(z)) > 2
+
+
 def test_fake_quantize_ties_round_half_even_and_clamp(oracle):
     s = np.float32(1.0)
     x = np.array([0.5, 1.5, 2.5, -0.5, -1.5, 7.5, 8.4, -8.5, -9.0], dtype=np.float32)
