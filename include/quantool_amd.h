@@ -336,7 +336,26 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   QT_I8_RING_SLOTS LDS slots filled by LDS-DMA QT_I8_RING_LEAD half panels ahead (csrc/ring_pipe.h,
  *   csrc/qlinear_ring.hip), v_mfma_i32_32x32x32_i8.  A tile row past M or N re-reads row M - 1
  *   or N - 1 and is never stored: no byte outside Xq[M, K] and Wq[N, K] is read, no element outside Y[m < M, n < N] is
- *   written.  Deterministic, no atomics, no workspace.   */
+ *   written.  Deterministic, no atomics, no workspace.  
+ *
+ * qt_gemm_i8_mid: the form of qt_gemm_i8 for a few tiles of rows, 1 <= M <= QT_I8_MID_MAX_M.  qt_gemm_i8's arguments
+ *   with the same meanings.  Taken: both weight formats, G = 1 and G = K/128, with and without zp_x / wsum and bias, bf16
+ *   and fp16 output, any N >= 1, any ldy >= N, K a multiple of QT_I8_MID_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned.
+ *   Everything else -- M = 0 or M > QT_I8_MID_MAX_M, a ragged K, a misaligned operand, a null pointer, a G that is
+ *   neither 1 nor K/128 -- is QT_ERR_INVALID before any launch, and qt_last_error names the reason.  For every legal
+ *   input Y is bit-identical to qt_gemm_i8's on the same arguments, for qt_gemm_i8_skinny's reason: acc_g is an exact
+ *   int32 sum whatever its order, the waves hand their acc_g over as int32 through LDS, and one thread per output
+ *   element runs the chain t_g -> tot -> y literally, g ascending from 0.0f, with one rounding to out_dtype; no wave ever
+ *   holds an fp32 partial of another wave's groups.  It is qt_gemm_i8_skinny's tile widened in M: a workgroup owns 16
+ *   output columns and all M rows as ceil(M/16) m-tiles (2, 4 or 8 compiled), splits K over its 4 waves (k-block kb to
+ *   wave kb % 4), the weights go from global memory straight to registers, non-temporal, and every weight byte is read
+ *   from memory once per launch; v_mfma_i32_16x16x64_i8 with the weights as A and 16 activation rows as B.  An
+ *   activation row past M is zero in registers, a weight row past N re-reads row N - 1, neither is stored: no byte
+ *   outside Xq[M, K], Wq[N, K] (int4: [N, K/8] words), s_w / wsum[N, G], s_x / zp_x[M] is read, no element outside
+ *   Y[m < M, n < N] is written.  Deterministic, no atomics, no workspace, no communication between workgroups.
+ *    */
+#define QT_I8_MID_MAX_M 128
+#define QT_I8_MID_K_UNIT 128
 #define QT_I8_RING_K_UNIT 128
 #define QT_I8_RING_SLOTS 8
 #define QT_I8_RING_LEAD 6
@@ -352,6 +371,9 @@ int qt_gemm_i8_skinny(const int8_t* Xq, int M, int K, const void* Wq, int w_form
 int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                     const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                     int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                   const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                   int out_dtype, int64_t ldy, qt_stream_t stream);
 
 /* ---- Routed experts: W8A8 / INT8 / W4A8 sparse-MoE banks on the same int8 GEMM ------------------------------
  * The A8 expert forward (engine/qlinear.py QuantizedExperts) restates transformers' MixtralExperts.forward with the

@@ -6,8 +6,9 @@ Linear either
 * a ``QuantizedLinear`` (W8A8 / INT8 / W4A8: the checkpoint's 8-bit dynamic per-token ``input_activations`` block):
   activations are quantised per row on the fly and multiplied with the stored integer weights on the int8 MFMA
   (``qt_quantize_tokens_i8`` + ``qt_gemm_i8``, or its bit-identical decode form ``qt_gemm_i8_skinny`` for up to
-  ``skinny_max_m`` rows and, for int8 weights with channel-wise scales, its bit-identical prefill form
-  ``qt_gemm_i8_ring`` from ``ring_min_m`` rows; include/quantool_amd.h), as a served W8A8 runtime does; or
+  ``skinny_max_m`` rows, its bit-identical weight-streaming form ``qt_gemm_i8_mid`` above that up to ``mid_max_m``
+  rows and, for int8 weights with channel-wise scales, its bit-identical prefill form ``qt_gemm_i8_ring`` from
+  ``ring_min_m`` rows; include/quantool_amd.h), as a served W8A8 runtime does; or
 * a plain ``nn.Linear`` holding the dequantised weight ``(q - zp) * scale`` (W4A16, W4A16_ASYM, W8A16), computed once in
   fp32 from the STORED scale and rounded once to the model dtype (the default, ``a16="dequantized"``); or
 * with ``a16="packed"``, a ``WeightOnlyLinear`` that keeps the stored integer weights on the device: decode-sized inputs

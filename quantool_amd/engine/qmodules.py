@@ -31,13 +31,23 @@ class QuantizedLinear(nn.Module):
     output columns per workgroup), larger M the 128 x 128-tile ``qt_gemm_i8``.  The two agree to the bit, so the
     attribute changes speed alone; 0 sends every M to the tiled kernel.  M >= ``ring_min_m`` (when that is not 0) runs
     an int8 weight with one scale group on the 256 x 256 LDS-ring kernel ``qt_gemm_i8_ring`` where
-    ``ops.gemm_i8_ring_supported`` holds; it agrees with the tiled kernel to the bit as well, and 0 never uses it."""
+    ``ops.gemm_i8_ring_supported`` holds; it agrees with the tiled kernel to the bit as well, and 0 never uses it.
+    Between the two, ``skinny_max_m`` < M <= ``mid_max_m`` runs the weight-streaming ``qt_gemm_i8_mid`` (both weight
+    formats, bit-identical too) on a Linear with ``in_features`` >= ``mid_min_k`` and, when ``mid_max_n`` is not 0,
+    ``out_features`` <= ``mid_max_n``, where ``ops.gemm_i8_mid_supported`` holds; ``mid_max_m`` = 0 never uses it."""
 
     # Decode GEMV up to this many rows: the measured crossover (DESIGN.md 4.11).
     skinny_max_m = 16
     # LDS-ring GEMM from this many rows (0: never): the smallest measured M from which the ring is no slower than the
     # tiled kernel on all three Llama-3-8B shapes, in both runs (DESIGN.md 4.12).
     ring_min_m = 2048
+    # Mid-M GEMM up to this many rows (0: never), up to this many output features (0: no bound) and from this many
+    # input features: the measured crossovers against the tiled kernel (DESIGN.md 4.14).  N = 28672 (gate/up) loses from
+    # 17 rows on; K = 256 would qualify, but Linears below 512 are launch-bound and stay on the tiled kernel.
+    # 128 rests on a tie on one shape (q/k/v W8A8: 52.0 against 51.7 / 51.4 us); the next clear win is 96 (1.20x).
+    mid_max_m = 128
+    mid_max_n = 6144
+    mid_min_k = 512
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -71,6 +81,11 @@ class QuantizedLinear(nn.Module):
         elif (self.ring_min_m > 0 and M >= self.ring_min_m and not self.int4 and self.weight_scale.shape[1] == 1
               and ops.gemm_i8_ring_supported(Xq, self.weight, self.weight_scale)):
             gemm = ops.gemm_i8_ring
+        elif (self.mid_max_m > 0 and self.skinny_max_m < M <= self.mid_max_m and self.in_features >= self.mid_min_k
+              and (self.mid_max_n == 0 or self.out_features <= self.mid_max_n) and M <= ops.I8_MID_MAX_M
+              and ops.gemm_i8_mid_supported(Xq, self.weight, self.weight_scale)):
+            # the attributes and the two sizes decide first: ops' mid names are read only past them
+            gemm = ops.gemm_i8_mid
         else:
             gemm = ops.gemm_i8
         y = gemm(

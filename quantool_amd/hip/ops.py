@@ -650,6 +650,59 @@ def gemm_i8_ring(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: tor
     return Y
 
 
+I8_MID_MAX_M = 128    # rows of Xq qt_gemm_i8_mid takes (QT_I8_MID_MAX_M)
+I8_MID_K_UNIT = 128   # columns per k-block of qt_gemm_i8_mid (QT_I8_MID_K_UNIT): K must be a multiple
+
+
+def _i8_mid_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
+    """Why ``qt_gemm_i8_mid`` would refuse these operands, or None.  Host-only: touches no library."""
+    M = Xq.shape[0] if Xq.dim() == 2 else -1
+    if not 1 <= M <= I8_MID_MAX_M:
+        return f"1 <= M <= {I8_MID_MAX_M} rows only, got Xq {tuple(Xq.shape)}"
+    if Wq.dtype not in (torch.int8, torch.int32):
+        return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
+    K = Xq.shape[-1]
+    if K % I8_MID_K_UNIT != 0:
+        return f"K={K} is not a multiple of the k-unit {I8_MID_K_UNIT}"
+    if K > 32768:
+        return f"K={K} > 32768: the int32 accumulator could overflow"
+    if s_w.dim() != 2 or s_w.shape[-1] not in (1, K // I8_MID_K_UNIT):
+        return f"G must be 1 or K / {I8_MID_K_UNIT} = {K // I8_MID_K_UNIT}, got s_w {tuple(s_w.shape)}"
+    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
+        return "Xq and Wq must be 16-byte aligned"
+    return None
+
+
+def gemm_i8_mid_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
+    """Whether ``gemm_i8_mid`` takes these operands: 1 to ``I8_MID_MAX_M`` rows, K a multiple of ``I8_MID_K_UNIT`` and at
+    most 32768, G = 1 or K/128, both operands 16-byte aligned.  Host-only."""
+    return _i8_mid_refusal(Xq, Wq, s_w) is None
+
+
+def gemm_i8_mid(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8`` for 1 <= M <= 128 rows on the weight-streaming 16-column tile (``qt_gemm_i8_mid``): batched decode,
+    speculative verification, short prompts.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where
+    ``gemm_i8_mid_supported`` is false."""
+    why = _i8_mid_refusal(Xq, Wq, s_w)
+    if why is not None:
+        raise ValueError(f"gemm_i8_mid: {why}")
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    M = Xq.shape[0]
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8_mid", lib.qt_gemm_i8_mid(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
 def moe_route(top_k_index: torch.Tensor, num_experts: int):
     """top_k_index [T, k] int32 / int64 -> (offsets int32 [E+1], src_token int32 [T k], src_slot int32 [T k],
     row_of int32 [T k]): ``qt_moe_route`` (include/quantool_amd.h).  Rows sorted by expert, then by token; an index

@@ -23,7 +23,16 @@ An A8 checkpoint instead (W8A8: int8 levels, one scale per row = absmax / 127.5,
 g128 with asymmetric activations; both round-to-nearest), loaded once and decoded in two modes in the same process:
 ``a8_tiled`` (``QuantizedLinear.skinny_max_m`` and ``QuantizedExperts.grouped_max_tokens`` set to 0: every Linear on
 the 128 x 128-tile ``qt_gemm_i8``) and ``a8_skinny`` (the class defaults: the decode GEMV).  The two compute the same
-bits, so ``tokens_agree`` must equal --new.
+bits, so ``tokens_agree`` must equal --new (B x --new with ``--batch B``).
+
+  python tools/decode_bench.py <checkpoint dir> --scheme W4A8 --layers 8 --batch 32 --pair mid
+
+``--batch B`` (default 1) decodes B sequences at once (B random prompts of --prompt tokens): every decode step is a
+B-row GEMM per Linear, and in every scheme and mode (the W4A16 ones included) ``tokens_agree``, ``first_difference``
+and ``tokens_agree_with_dequantized`` count over all B x --new generated tokens, sequence by sequence.
+``--pair mid`` (A8 schemes) replaces the mode pair by one that differs only in ``QuantizedLinear.mid_max_m``:
+``a8_mid_off`` (0: rows 17 .. 128 on the tiled ``qt_gemm_i8``) against ``a8_mid`` (the class default:
+``qt_gemm_i8_mid``); everything else stays at its default in both.
 """
 from __future__ import annotations
 
@@ -140,7 +149,32 @@ def decode(model, prompt: torch.Tensor, new: int):
             toks.append(tok)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-    return torch.cat(toks, 1)[0].tolist(), (t1 - t0) / max(new - 1, 1)
+    return torch.cat(toks, 1).flatten().tolist(), (t1 - t0) / max(new - 1, 1)
+
+
+def a8_mid_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """One loaded A8 model decoded as ``a8_mid_off`` (``mid_max_m`` = 0) and ``a8_mid`` (its default)."""
+    from quantool_amd.engine.qlinear import QuantizedLinear
+
+    model = load_quantized(path, device=dev)
+    default = QuantizedLinear.mid_max_m
+    for name in ("skinny_max_m", "mid_max_m", "mid_max_n", "mid_min_k", "ring_min_m"):
+        result[name] = getattr(QuantizedLinear, name)
+    result["quantized_linears"] = sum(isinstance(m, QuantizedLinear) for m in model.modules())
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, a in (("a8_mid_off", 0), ("a8_mid", default)):
+            QuantizedLinear.mid_max_m = a
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    QuantizedLinear.mid_max_m = default
+    same = [x == y for x, y in zip(tokens["a8_mid_off"], tokens["a8_mid"])]
+    result["tokens_agree"] = sum(same)
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_step"]) for m in ("a8_mid_off", "a8_mid"))
+    result["speedup"] = round(t / k, 3)
 
 
 def a8_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
@@ -177,6 +211,9 @@ def main():
     ap.add_argument("--model", default="llama", choices=["llama", "mixtral"])
     ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
+    ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid"],
+                    help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid")
     ap.add_argument("--modes", default=None,
                     help="default: dequantized,packed (llama) / dequantized,packed,packed_experts (mixtral)")
     args = ap.parse_args()
@@ -190,11 +227,13 @@ def main():
     if not (path / "config.json").exists():
         path.mkdir(parents=True, exist_ok=True)
         (write_mixtral_checkpoint if mixtral else write_checkpoint)(path, args.layers, dev, args.scheme)
-    prompt = torch.randint(0, vocab, (1, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
+    if args.batch < 1:
+        raise SystemExit("--batch must be at least 1")
+    prompt = torch.randint(0, vocab, (args.batch, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
-              "new": args.new, "scheme": args.scheme, "layers": args.layers, "modes": {}}
+              "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
     if args.scheme != "W4A16":
-        a8_modes(path, dev, prompt, args.new, result)
+        (a8_mid_modes if args.pair == "mid" else a8_modes)(path, dev, prompt, args.new, result)
         print(json.dumps(result))
         return
     tokens = {}

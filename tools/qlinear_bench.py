@@ -3,6 +3,7 @@ tiled GEMM at decode sizes.
 
   python tools/qlinear_bench.py [--ms 4096,8192] [--reps 20] [--warmup 5]
   python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
+  python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
 
 Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N = 4096, K = 14336) and M: device time
 (HIP events, mean over --reps after --warmup) of the activation pass (qt_quantize_tokens_i8), the GEMM (qt_gemm_i8:
@@ -22,6 +23,14 @@ on the same operands, with qt_quantize_tokens_i8, bf16 F.linear and torch._int_m
 under the same harness (per-call events, weights rotating over more than 512 MiB of copies, medians).  Reported:
 median microseconds and TOPS per kernel, tiled / ring ("speedup"), and bf16 F.linear over quantize_tokens + ring
 ("bf16_over_act_plus_ring", > 1: the W8A8 linear on the ring is faster than bf16).
+
+--mid prints only "mid" rows: the tiled qt_gemm_i8 (the yardstick) and qt_gemm_i8_mid on the same operands at M = 17, 24,
+32, 48, 64, 96, 128, with M = 16 (where qt_gemm_i8_skinny joins the loop) and M = 256 (tiled alone) as neighbours, on the
+three shapes above plus o_proj (4096 x 4096) and k/v (1024 x 4096), and on N = 4096 at K = 256 .. 2048 (the sweep that
+sets ``QuantizedLinear.mid_min_k``; ``--mid-shapes`` picks among them, and knows ``gate_or_up`` = 14336 x 4096
+besides), W8A8 (int8, G = 1, symmetric) and W4A8 (int4, G = K/128, asymmetric), under the
+decode rows' harness (alternating call by call, per-call events, weights rotating over more than 512 MiB of copies,
+medians), with ``bits_equal`` per cell.
 """
 from __future__ import annotations
 
@@ -109,6 +118,59 @@ def decode_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+MID_MS = (16, 17, 24, 32, 48, 64, 96, 128, 256)
+MID_SHAPES = {"o_proj": (4096, 4096), "kv": (1024, 4096), "qkv": (6144, 4096), "gate_up": (28672, 4096),
+              "down": (4096, 14336), "n4096_k256": (4096, 256), "n4096_k512": (4096, 512),
+              "n4096_k1024": (4096, 1024), "n4096_k2048": (4096, 2048)}
+MID_EXTRA_SHAPES = {"gate_or_up": (14336, 4096)}       # one of gate / up alone (an unfused MLP): --mid-shapes gate_or_up
+
+
+def mid_rows(shape, N, K, ms, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_gemm_i8_mid from 17 to 128 rows (and their neighbours), W8A8 and W4A8, cold weights."""
+    rows = []
+    for scheme in ("W8A8", "W4A8"):
+        int4 = scheme == "W4A8"
+        G = K // 128 if int4 else 1
+        q = torch.randint(-8 if int4 else -128, 8 if int4 else 128, (N, K), device=dev, generator=g, dtype=torch.int8)
+        W0 = pack_int4(q) if int4 else q
+        s0 = torch.rand(N, G, device=dev, generator=g) * 1e-2
+        ws0 = group_sums(q, G) if int4 else None
+        del q
+        nbytes = W0.numel() * W0.element_size() + s0.numel() * 4 + (ws0.numel() * 4 if int4 else 0)
+        n_cp = max(3, -(-int(COLD_BYTES * 1.1) // nbytes))
+        cps = [(W0.clone(), s0.clone(), None if ws0 is None else ws0.clone()) for _ in range(n_cp)]
+        for M in ms:
+            X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+            Xq, s_x, zp_x = ops.quantize_tokens_i8(X, symmetric=not int4)
+
+            def call(fn, shift):
+                # kernels that share a rep read different copies, or the second finds the first's weights cached
+                def run(i):
+                    W, s, ws = cps[(i + shift) % n_cp]
+                    return fn(Xq, s_x, W, s, K=K, zp_x=zp_x, wsum=ws)
+                return run
+
+            fns = {"gemm_i8": call(ops.gemm_i8, 0)}
+            if M <= ops.I8_MID_MAX_M:
+                fns["gemm_i8_mid"] = call(ops.gemm_i8_mid, 1)
+            if M <= ops.I8_SKINNY_MAX_M:
+                fns["gemm_i8_skinny"] = call(ops.gemm_i8_skinny, 2)
+            t = time_pair(fns, reps, warmup)
+            want = fns["gemm_i8"](0).view(torch.int16)
+            row = {"shape": shape, "scheme": scheme, "M": M, "N": N, "K": K, "weight_mb": round(nbytes / 1e6, 2),
+                   "cold_copies": n_cp,
+                   "bits_equal": all(torch.equal(want, fns[k](0).view(torch.int16)) for k in fns if k != "gemm_i8")}
+            for k in fns:
+                row[k] = summarize(t[k], nbytes)
+            if "gemm_i8_mid" in fns:
+                row["speedup"] = round(row["gemm_i8"]["us"] / row["gemm_i8_mid"]["us"], 2)
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr)
+        del cps
+        torch.cuda.empty_cache()
+    return rows
+
+
 def ring_rows(shape, N, K, ms, reps, warmup, dev, g):
     """qt_gemm_i8 vs qt_gemm_i8_ring at prefill sizes, W8A8 (int8 channel-wise, symmetric activations), beside the
     activation pass, bf16 F.linear and torch._int_mm."""
@@ -175,11 +237,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-ring", action="store_true", help="leave out the tiled-vs-ring rows")
     ap.add_argument("--ring-only", action="store_true", help="only the tiled-vs-ring rows at M > 16")
+    ap.add_argument("--mid", action="store_true", help="only the tiled-vs-mid rows (17 .. 128 rows and neighbours)")
+    ap.add_argument("--mid-shapes", default=",".join(MID_SHAPES))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qlinear_bench needs a GPU")
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
+    if args.mid:
+        mid = []
+        for shape in args.mid_shapes.split(","):
+            N, K = {**MID_SHAPES, **MID_EXTRA_SHAPES}[shape]
+            mid += mid_rows(shape, N, K, MID_MS, args.reps, args.warmup, dev, g)
+        print(json.dumps({"metric": "qt_gemm_i8 vs qt_gemm_i8_mid, 17 .. 128 rows, cold weights", "hbm_peak": HBM_PEAK,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "mid": mid}))
+        return
     rows = []
     int_mm_note = None
     all_ms = [int(m) for m in args.ms.split(",") if m]
