@@ -338,6 +338,22 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   or N - 1 and is never stored: no byte outside Xq[M, K] and Wq[N, K] is read, no element outside Y[m < M, n < N] is
  *   written.  Deterministic, no atomics, no workspace.  
  *
+ * qt_gemm_i8_ring_w4: the prefill form of qt_gemm_i8 for W4A8: w_format == QT_W_INT4_PACKED with G == K / 128 (packed
+ *   int4 weights, one scale per group of 128 columns), K a multiple of QT_I8_RING_W4_K_UNIT, K <= 32768, Xq and Wq
+ *   16-byte aligned.  Same arguments, same meanings; with and without zp_x / wsum and bias, bf16 and fp16 output, any
+ *   M >= 1, any N >= 1, any ldy >= N.  Everything else -- int8 weights, channel-wise scales (G == 1 with K > 128), a
+ *   ragged K, a misaligned operand -- is QT_ERR_INVALID before any launch, and qt_last_error names the reason.  (At
+ *   K == 128 the one group is the whole row: G = K / 128 = 1 is taken.)  For every legal input Y is bit-identical to
+ *   qt_gemm_i8's on the same arguments: it is qt_gemm_i8_ring's 256 x 256 tile and LDS ring, and because a K-tile of
+ *   that ring is exactly one weight group, the int32 result of a phase is the complete acc_g of its outputs; the chain
+ *   t_g -> tot = tot + s_w t_g -> y above runs literally, once per output element and group, g ascending, in the
+ *   lane that holds the element.  wsum must be what its name says (|wsum[n, g]| <= 128 * 8): zp_x * wsum is a 24-bit
+ *   multiply.  B half panels travel packed (64 B per row and K-tile) and are unpacked between LDS and the MFMA; s_w
+ *   and wsum of a K-tile ride with the ring as a counted LDS-DMA gather (csrc/qlinear_ring_w4.hip).  A tile row past M
+ *   or N re-reads row M - 1 or N - 1 and is never stored: no byte outside Xq[M, K], Wq[N, K/8], s_w / wsum[N, G],
+ *   s_x / zp_x[M] is read, no element outside Y[m < M, n < N] is written.  Deterministic, no atomics, no workspace.
+ *   
+ *
  * qt_gemm_i8_mid: the form of qt_gemm_i8 for a few tiles of rows, 1 <= M <= QT_I8_MID_MAX_M.  qt_gemm_i8's arguments
  *   with the same meanings.  Taken: both weight formats, G = 1 and G = K/128, with and without zp_x / wsum and bias, bf16
  *   and fp16 output, any N >= 1, any ldy >= N, K a multiple of QT_I8_MID_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned.
@@ -359,6 +375,9 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
 #define QT_I8_RING_K_UNIT 128
 #define QT_I8_RING_SLOTS 8
 #define QT_I8_RING_LEAD 6
+#define QT_I8_RING_W4_K_UNIT 128
+#define QT_I8_RING_W4_SLOTS 8
+#define QT_I8_RING_W4_LEAD 6
 enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
 int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
                           int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
@@ -371,6 +390,9 @@ int qt_gemm_i8_skinny(const int8_t* Xq, int M, int K, const void* Wq, int w_form
 int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                     const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                     int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_gemm_i8_ring_w4(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                       const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                       int out_dtype, int64_t ldy, qt_stream_t stream);
 int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                    const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                    int out_dtype, int64_t ldy, qt_stream_t stream);

@@ -106,6 +106,17 @@ __device__ __forceinline__ void glds16_one(unsigned voff, const void* sbase, uns
         : "v"(voff), "s"(sbase), "s"(lds_dst)
         : "memory");
 }
+// One dword per lane (64 x 4 B = 256 B of LDS per wave-instruction): a gather of strided scalars, e.g. one column of a
+// row-major scale table (gemm_i8_ring_w4_kernel).  Counted in vmcnt like every other LDS-DMA.
+__device__ __forceinline__ void glds4_one(unsigned voff, const void* sbase, unsigned lds_dst) {
+    asm volatile(
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dword %0, %1"
+        :
+        : "v"(voff), "s"(sbase), "s"(lds_dst)
+        : "memory");
+}
 __device__ __forceinline__ void glds16_snapshot(unsigned voff, const void* sbase, unsigned lds_dst) {
     // 1 KiB of progress words -> LDS scratch; sc1: served by L2, never by this CU's L1 copy of the line
     asm volatile(

@@ -32,6 +32,9 @@ class QuantizedLinear(nn.Module):
     attribute changes speed alone; 0 sends every M to the tiled kernel.  M >= ``ring_min_m`` (when that is not 0) runs
     an int8 weight with one scale group on the 256 x 256 LDS-ring kernel ``qt_gemm_i8_ring`` where
     ``ops.gemm_i8_ring_supported`` holds; it agrees with the tiled kernel to the bit as well, and 0 never uses it.
+    M >= ``ring_w4_min_m`` (when that is not 0) runs a packed int4 weight with one scale per 128 columns on the same
+    ring with packed weight panels, ``qt_gemm_i8_ring_w4``, where ``ops.gemm_i8_ring_w4_supported`` holds: bit-identical
+    again, and 0 never uses it.
     Between the two, ``skinny_max_m`` < M <= ``mid_max_m`` runs the weight-streaming ``qt_gemm_i8_mid`` (both weight
     formats, bit-identical too) on a Linear with ``in_features`` >= ``mid_min_k`` and, when ``mid_max_n`` is not 0,
     ``out_features`` <= ``mid_max_n``, where ``ops.gemm_i8_mid_supported`` holds; ``mid_max_m`` = 0 never uses it."""
@@ -41,6 +44,11 @@ class QuantizedLinear(nn.Module):
     # LDS-ring GEMM from this many rows (0: never): the smallest measured M from which the ring is no slower than the
     # tiled kernel on all three Llama-3-8B shapes, in both runs.
     ring_min_m = 2048
+    # The same for packed int4 weights (qt_gemm_i8_ring_w4; 0: never): the smallest of M = 2048, 4096, 8192 at which the
+    # ring beats the tiled kernel on all three Llama-3-8B shapes, in both runs, by more than the tiled kernel's largest
+    # run-to-run spread in those runs (3.9 %).  At 2048 down loses (0.74x), at 4096 q/k/v wins by 1.4 / 1.8 % only
+    # (gate/up 1.26x, down 1.40x), at 8192 the margins are 1.27 - 1.37x.  Never below 2048.
+    ring_w4_min_m = 8192
     # Mid-M GEMM up to this many rows (0: never), up to this many output features (0: no bound) and from this many
     # input features: the measured crossovers against the tiled kernel.  N = 28672 (gate/up) loses from
     # 17 rows on; K = 256 would qualify, but Linears below 512 are launch-bound and stay on the tiled kernel.
@@ -67,7 +75,8 @@ class QuantizedLinear(nn.Module):
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"weights={'int4 g128' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token, "
-                f"col_perm={self.col_perm is not None}, bias={self.bias is not None}")
+                f"col_perm={self.col_perm is not None}, bias={self.bias is not None}, "
+                f"ring_w4_min_m={self.ring_w4_min_m}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from ..hip import ops
@@ -81,6 +90,11 @@ class QuantizedLinear(nn.Module):
         elif (self.ring_min_m > 0 and M >= self.ring_min_m and not self.int4 and self.weight_scale.shape[1] == 1
               and ops.gemm_i8_ring_supported(Xq, self.weight, self.weight_scale)):
             gemm = ops.gemm_i8_ring
+        elif (self.ring_w4_min_m > 0 and M >= self.ring_w4_min_m and self.int4
+              and self.weight_scale.shape[1] * 128 == self.in_features
+              and ops.gemm_i8_ring_w4_supported(Xq, self.weight, self.weight_scale)):
+            # the attribute and M decide first: ops' ring_w4 names are read only past them
+            gemm = ops.gemm_i8_ring_w4
         elif (self.mid_max_m > 0 and self.skinny_max_m < M <= self.mid_max_m and self.in_features >= self.mid_min_k
               and (self.mid_max_n == 0 or self.out_features <= self.mid_max_n) and M <= ops.I8_MID_MAX_M
               and ops.gemm_i8_mid_supported(Xq, self.weight, self.weight_scale)):

@@ -101,6 +101,8 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_ring": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "qt_gemm_i8_ring_w4": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_mid": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_skinny_grouped": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -650,6 +650,58 @@ def gemm_i8_ring(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: tor
     return Y
 
 
+I8_RING_W4_K_UNIT = 128   # k per K-tile of qt_gemm_i8_ring_w4 = the weight group (QT_I8_RING_W4_K_UNIT): K a multiple
+I8_RING_W4_SLOTS = 8      # half panels resident in LDS (QT_I8_RING_W4_SLOTS)
+I8_RING_W4_LEAD = 6       # half panels the LDS-DMA runs ahead of the MFMAs (QT_I8_RING_W4_LEAD)
+
+
+def _i8_ring_w4_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
+    """Why ``qt_gemm_i8_ring_w4`` would refuse these operands, or None.  Host-only: touches no library."""
+    if Wq.dtype != torch.int32:
+        return f"packed int4 (int32) weights only, got {Wq.dtype} (int8 weights run on gemm_i8_ring)"
+    K = Xq.shape[-1]
+    if K % I8_RING_W4_K_UNIT != 0:
+        return f"K={K} is not a multiple of the k-unit {I8_RING_W4_K_UNIT}"
+    if K > 32768:
+        return f"K={K} > 32768: the int32 accumulator could overflow"
+    if s_w.dim() != 2 or s_w.shape[-1] != K // I8_RING_W4_K_UNIT:
+        return (f"one scale per group of {I8_RING_W4_K_UNIT} columns only, G = K / {I8_RING_W4_K_UNIT} = "
+                f"{K // I8_RING_W4_K_UNIT}, got s_w {tuple(s_w.shape)} (channel-wise scales run on gemm_i8)")
+    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
+        return "Xq and Wq must be 16-byte aligned"
+    return None
+
+
+def gemm_i8_ring_w4_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
+    """Whether ``gemm_i8_ring_w4`` takes these operands: a packed int4 weight with one scale per 128 columns, K a
+    multiple of ``I8_RING_W4_K_UNIT`` and at most 32768, both operands 16-byte aligned.  Host-only."""
+    return _i8_ring_w4_refusal(Xq, Wq, s_w) is None
+
+
+def gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                    K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                    wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                    out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8`` on the 256 x 256 LDS-ring kernel for packed int4 weights (``qt_gemm_i8_ring_w4``): the prefill form
+    for W4A8.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where ``gemm_i8_ring_w4_supported``
+    is false."""
+    why = _i8_ring_w4_refusal(Xq, Wq, s_w)
+    if why is not None:
+        raise ValueError(f"gemm_i8_ring_w4: {why}")
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    M = Xq.shape[0]
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check("qt_gemm_i8_ring_w4", lib.qt_gemm_i8_ring_w4(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
+    return Y
+
+
 I8_MID_MAX_M = 128    # rows of Xq qt_gemm_i8_mid takes (QT_I8_MID_MAX_M)
 I8_MID_K_UNIT = 128   # columns per k-block of qt_gemm_i8_mid (QT_I8_MID_K_UNIT): K must be a multiple
 

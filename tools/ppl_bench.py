@@ -1,11 +1,12 @@
-"""evaluate.perplexity on a W8A8 checkpoint with and without the LDS-ring GEMM (QuantizedLinear.ring_min_m).
+"""evaluate.perplexity on a W8A8 / W4A8 checkpoint with and without the LDS-ring GEMM (QuantizedLinear.ring_min_m,
+or ring_w4_min_m for W4A8).
 
-  python tools/ppl_bench.py <dir> [--layers 8] [--batch 8] [--seq 2048]
+  python tools/ppl_bench.py <dir> [--layers 8] [--batch 8] [--seq 2048] [--scheme W8A8|W4A8] [--ring-min-m M]
 
-The checkpoint is the random-init Llama-3-8B-shaped RTN W8A8 model of tools/decode_bench.py (written to <dir> when it
-is not there yet).  One loaded model runs ``perplexity`` over --batch x --seq random tokens as ``tiled``
-(``ring_min_m = 0``) and ``ring`` (the class default), each twice after one warm-up pass; wall seconds with the device
-synchronised.  The Linears agree to the bit, so the perplexities must be equal as floats.  Prints one JSON line.
+The checkpoint is the random-init Llama-3-8B-shaped RTN model of tools/decode_bench.py in that scheme (written to <dir>
+when it is not there yet).  One loaded model runs ``perplexity`` over --batch x --seq random tokens as ``tiled`` (the
+attribute at 0) and ``ring`` (the class default, or --ring-min-m: the way to time a ring that ships turned off), each
+twice after one warm-up pass; wall seconds with the device synchronised.  The Linears agree to the bit, so the perplexities must be equal as floats.  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -32,23 +33,28 @@ def main():
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--seq", type=int, default=2048)
+    ap.add_argument("--scheme", default="W8A8", choices=["W8A8", "W4A8"])
+    ap.add_argument("--ring-min-m", type=int, default=None, help="the 'ring' mode's attribute value (default: the class's)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppl_bench needs a GPU")
     dev = torch.device("cuda:0")
     path = Path(args.checkpoint)
     if not (path / "config.json").exists():
-        write_checkpoint(path, args.layers, dev, "W8A8")
+        write_checkpoint(path, args.layers, dev, args.scheme)
     model = load_quantized(path, device=dev)
     ids = torch.randint(0, model.config.vocab_size, (args.batch, args.seq), generator=torch.Generator().manual_seed(0))
-    default = QuantizedLinear.ring_min_m
-    result = {"metric": "evaluate.perplexity wall seconds, W8A8, ring_min_m = 0 vs default", "layers": args.layers,
-              "tokens": args.batch * args.seq, "ring_min_m": default, "device": torch.cuda.get_device_name(0),
+    attr = "ring_min_m" if args.scheme == "W8A8" else "ring_w4_min_m"
+    default = getattr(QuantizedLinear, attr)
+    ring = default if args.ring_min_m is None else args.ring_min_m
+    result = {"metric": f"evaluate.perplexity wall seconds, {args.scheme}, {attr} = 0 vs {ring}", "layers": args.layers,
+              "tokens": args.batch * args.seq, attr: ring, "class_default": default,
+              "device": torch.cuda.get_device_name(0),
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()), "modes": {}}
     try:
         for rep in range(3):                                   # pass 0 warms up; both modes twice: the spread
-            for mode, setting in (("tiled", 0), ("ring", default)):
-                QuantizedLinear.ring_min_m = setting
+            for mode, setting in (("tiled", 0), ("ring", ring)):
+                setattr(QuantizedLinear, attr, setting)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 ppl = perplexity(model, ids, batch_size=args.batch)["perplexity"]
@@ -59,7 +65,7 @@ def main():
                 if rep:
                     m["seconds"].append(round(dt, 4))
     finally:
-        QuantizedLinear.ring_min_m = default
+        setattr(QuantizedLinear, attr, default)
     t, r = (min(result["modes"][m]["seconds"]) for m in ("tiled", "ring"))
     result["perplexities_equal"] = result["modes"]["tiled"]["perplexity"] == result["modes"]["ring"]["perplexity"]
     result["speedup"] = round(t / r, 3)

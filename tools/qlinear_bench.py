@@ -4,6 +4,7 @@ tiled GEMM at decode sizes.
   python tools/qlinear_bench.py [--ms 4096,8192] [--reps 20] [--warmup 5]
   python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
   python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
+  python tools/qlinear_bench.py --ring-w4 [--ms 2048,4096,8192]   # W4A8 prefill: qt_gemm_i8 vs qt_gemm_i8_ring_w4
 
 Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N = 4096, K = 14336) and M: device time
 (HIP events, mean over --reps after --warmup) of the activation pass (qt_quantize_tokens_i8), the GEMM (qt_gemm_i8:
@@ -31,6 +32,11 @@ sets ``QuantizedLinear.mid_min_k``; ``--mid-shapes`` picks among them, and knows
 besides), W8A8 (int8, G = 1, symmetric) and W4A8 (int4, G = K/128, asymmetric), under the
 decode rows' harness (alternating call by call, per-call events, weights rotating over more than 512 MiB of copies,
 medians), with ``bits_equal`` per cell.
+
+--ring-w4 prints only "ring_w4" rows (W4A8: packed int4 g128 weights, asymmetric activations): the tiled qt_gemm_i8 and
+the LDS-ring qt_gemm_i8_ring_w4 on the same operands, with qt_quantize_tokens_i8 and bf16 F.linear, under the "ring"
+rows' harness, at --ms (default 2048,4096,8192) on the three shapes, with ``bits_equal`` per cell and tiled / ring as
+"speedup".  ``QuantizedLinear.ring_w4_min_m`` is set from two such runs.
 """
 from __future__ import annotations
 
@@ -216,6 +222,54 @@ def ring_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+def ring_w4_rows(shape, N, K, ms, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_gemm_i8_ring_w4 at prefill sizes, W4A8 (packed int4 g128, asymmetric activations), beside the
+    activation pass and bf16 F.linear."""
+    rows = []
+    G = K // 128
+    q = torch.randint(-8, 8, (N, K), device=dev, generator=g, dtype=torch.int8)
+    W0, s0, ws0 = pack_int4(q), torch.rand(N, G, device=dev, generator=g) * 1e-2, group_sums(q, G)
+    del q
+    nbytes = W0.numel() * 4 + s0.numel() * 4 + ws0.numel() * 4
+    n_cp = max(3, -(-int(COLD_BYTES * 1.1) // nbytes))
+    cps = [(W0.clone(), s0.clone(), ws0.clone()) for _ in range(n_cp)]
+    n_bf = max(2, -(-int(COLD_BYTES * 1.1) // (2 * N * K)))
+    bfs = [(torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16) for _ in range(n_bf)]
+    for M in ms:
+        X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        Xq, s_x, zp_x = ops.quantize_tokens_i8(X, symmetric=False)
+
+        def call(fn, shift):
+            # kernels that share a rep read different copies, or the second finds the first's weights cached
+            def run(i):
+                W, s, ws = cps[(i + shift) % n_cp]
+                return fn(Xq, s_x, W, s, K=K, zp_x=zp_x, wsum=ws)
+            return run
+
+        fns = {"gemm_i8": call(ops.gemm_i8, 0), "gemm_i8_ring_w4": call(ops.gemm_i8_ring_w4, 1),
+               "quantize_tokens": lambda i: ops.quantize_tokens_i8(X, symmetric=False),
+               "bf16_linear": lambda i: F.linear(X, bfs[i % n_bf])}
+        t = time_pair(fns, reps, warmup)
+        same = torch.equal(fns["gemm_i8"](0).view(torch.int16), call(ops.gemm_i8_ring_w4, 0)(0).view(torch.int16))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        ops_n = 2.0 * M * N * K
+        row = {"shape": shape, "scheme": "W4A8", "M": M, "N": N, "K": K, "cold_copies": n_cp, "bits_equal": same,
+               "us": {k: round(v * 1e6, 2) for k, v in med.items()},
+               "min_us": {k: round(min(v) * 1e6, 2) for k, v in t.items()},
+               "tops": {k: round(ops_n / v / 1e12, 1) for k, v in med.items() if k != "quantize_tokens"},
+               "int8_peak_frac": {k: round(ops_n / med[k] / INT8_PEAK, 3) for k in ("gemm_i8", "gemm_i8_ring_w4")},
+               "speedup": round(med["gemm_i8"] / med["gemm_i8_ring_w4"], 3),
+               "bf16_over_act_plus_tiled": round(med["bf16_linear"] / (med["quantize_tokens"] + med["gemm_i8"]), 3),
+               "bf16_over_act_plus_ring": round(med["bf16_linear"] / (med["quantize_tokens"] + med["gemm_i8_ring_w4"]),
+                                                3)}
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr)
+        del X, Xq
+    del cps, bfs
+    torch.cuda.empty_cache()
+    return rows
+
+
 def _time(fn, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -239,6 +293,7 @@ def main():
     ap.add_argument("--ring-only", action="store_true", help="only the tiled-vs-ring rows at M > 16")
     ap.add_argument("--mid", action="store_true", help="only the tiled-vs-mid rows (17 .. 128 rows and neighbours)")
     ap.add_argument("--mid-shapes", default=",".join(MID_SHAPES))
+    ap.add_argument("--ring-w4", action="store_true", help="only the W4A8 tiled-vs-ring rows (qt_gemm_i8_ring_w4)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qlinear_bench needs a GPU")
@@ -251,6 +306,16 @@ def main():
             mid += mid_rows(shape, N, K, MID_MS, args.reps, args.warmup, dev, g)
         print(json.dumps({"metric": "qt_gemm_i8 vs qt_gemm_i8_mid, 17 .. 128 rows, cold weights", "hbm_peak": HBM_PEAK,
                           "device": torch.cuda.get_device_name(0), "reps": args.reps, "mid": mid}))
+        return
+    if args.ring_w4:
+        ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else "2048,4096,8192").split(",") if m]
+        w4 = []
+        for shape in args.shapes.split(","):
+            N, K = SHAPES[shape]
+            w4 += ring_w4_rows(shape, N, K, ms, args.reps, args.warmup, dev, g)
+        print(json.dumps({"metric": "qt_gemm_i8 vs qt_gemm_i8_ring_w4, W4A8 prefill sizes, cold weights",
+                          "int8_peak": INT8_PEAK, "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                          "ring_w4": w4}))
         return
     rows = []
     int_mm_note = None
