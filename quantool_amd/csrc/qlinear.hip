@@ -12,6 +12,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "i8_args.h"
 #include "i8_unpack.h"
 
 namespace {
@@ -475,12 +476,8 @@ extern "C" int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, in
                           const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                           int out_dtype, int64_t ldy, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && M > 0 && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8: bad arguments");
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8: K %d > 32768 (the int32 accumulator bound)", K);
-    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8: w_format %d unsupported", w_format);
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8: G %d must be 1 or ceil(K / 128) = %d", G, (K + 127) / 128);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8: zp_x needs wsum");
+    if (int st = qt_i8_check_dense("qt_gemm_i8", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype, ldy))
+        return st;
     const int64_t tiles = ((M + BM - 1) / BM) * (int64_t)((N + BN - 1) / BN);
     QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8: too many tiles");
     const bool int4 = w_format == QT_W_INT4_PACKED;
@@ -498,16 +495,9 @@ extern "C" int qt_gemm_i8_grouped(const int8_t* Xq, int K, const int32_t* row_id
                                   const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
                                   qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && offsets && s_x && s_w && Y && R > 0 && E > 0 && N > 0 && K > 0 && ldy >= N,
-                 "qt_gemm_i8_grouped: bad arguments");
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_grouped: K %d > 32768 (the int32 accumulator bound)", K);
-    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8_grouped: w_format %d unsupported",
-                 w_format);
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_grouped: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8_grouped: G %d must be 1 or ceil(K / 128) = %d", G,
-                 (K + 127) / 128);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_grouped: zp_x needs wsum");
-    QT_CHECK_ARG(R <= 0x7fffffffLL && E <= 4096, "qt_gemm_i8_grouped: R %lld or E %d too large", (long long)R, E);
+    if (int st = qt_i8_check_grouped("qt_gemm_i8_grouped", Xq, K, R, offsets, E, Wq, w_format, N, s_x, zp_x, s_w, G, wsum,
+                                     Y, out_dtype, ldy))
+        return st;
     const int64_t tiles = ((R + BM - 1) / BM + E) * (int64_t)((N + BN - 1) / BN);
     QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_grouped: too many tiles");
     const bool int4 = w_format == QT_W_INT4_PACKED;

@@ -23,6 +23,7 @@
 //
 // -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own.
 #include "common.h"
+#include "i8_args.h"
 #include "i8_unpack.h"
 #pragma clang fp contract(off)
 
@@ -272,16 +273,12 @@ extern "C" int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq
                               const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias,
                               void* Y, int out_dtype, int64_t ldy, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8_mid: bad arguments");
     QT_CHECK_ARG(M >= 1 && M <= MID_MAX_M, "qt_gemm_i8_mid: M %lld outside 1 .. %d", (long long)M, MID_MAX_M);
     QT_CHECK_ARG(K % MID_KB == 0, "qt_gemm_i8_mid: K %d is not a multiple of the k-unit %d", K, MID_KB);
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_mid: K %d > 32768 (the int32 accumulator bound)", K);
-    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8_mid: w_format %d unsupported",
-                 w_format);
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_mid: out_dtype %d must be bf16 or fp16", out_dtype);
     QT_CHECK_ARG(G == 1 || G == K / MID_KB, "qt_gemm_i8_mid: G %d must be 1 or K / 128 = %d", G, K / MID_KB);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_mid: zp_x needs wsum");
     QT_CHECK_ARG((((uintptr_t)Xq | (uintptr_t)Wq) & 15) == 0, "qt_gemm_i8_mid: Xq and Wq must be 16-byte aligned");
+    if (int st = qt_i8_check_dense("qt_gemm_i8_mid", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype, ldy))
+        return st;
     const bool int4 = w_format == QT_W_INT4_PACKED;
     MidArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, bias, Y, (int)M, N, K, K / 8, G, ldy, out_dtype};
     const dim3 grid((unsigned)((N + MID_COLS - 1) / MID_COLS));

@@ -34,22 +34,10 @@
 // the A base is Xq itself and each lane's 32-bit offset is row_idx[m] K + 16 c (the host refuses x_rows K > 2^32; the
 // index is clamped into [0, x_rows)).  A tile row past the expert's last row re-reads that expert's last row.
 #include "common.h"
-#include "ring_pipe.h"
+#include "i8_args.h"
+#include "i8_ring_tile.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(16))) int i32x16;
-
-constexpr int RING = 8;                      // units (half panels) resident in LDS (128 KiB)
-constexpr int LEAD = 6;                      // unit u + LEAD is issued in phase u (LEAD <= RING - 2)
-constexpr int KU = 128;                      // k-bytes per K-tile: one cache line per row and fetch
-constexpr int HP = 128;                      // rows of a half panel
-constexpr int GROUP_M = 32;                  // m-tiles that walk the n-tiles together: workgroups are dealt round-robin
-                                             // over 8 XCDs of 32 CUs, so the 32 tiles resident on one XCD are
-                                             // 4 m-tiles x 8 n-tiles = 12 panels
-static_assert(HP * KU == UNIT_BYTES, "a unit is a half panel of 128 rows x 128 k-bytes");
-static_assert(LEAD <= RING - 2, "ring_pipe.h, WAR");
 
 struct RingArgs {
     const int8_t* Xq;
@@ -84,17 +72,13 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     const int wave_m = wave >> 2, wave_n = wave & 3;
     const bool group_b = wave >= 4;  // wave-uniform
 
-    // tile order: GROUP_M m-tiles walk the n-tiles together (as gemm_i8_kernel)
     const int tiles_n = (p.N + BT - 1) / BT;
     const int tiles_m = (int)((p.M + BT - 1) / BT) + (MOE ? g.E : 0);
-    const int pid = blockIdx.x;
-    const int per_group = GROUP_M * tiles_n;
-    const int first_m = pid / per_group * GROUP_M;
-    const int gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-    const int in_g = pid % per_group;
-    int64_t m0 = (int64_t)(first_m + in_g % gsize) * BT;
+    int m_tile, n_tile;                               // the grouped form: m_tile is an m-tile slot
+    i8_ring_tile_of(blockIdx.x, tiles_m, tiles_n, m_tile, n_tile);
+    int64_t m0 = (int64_t)m_tile * BT;
     int64_t m_end = p.M;                              // rows [m0, m_end) of this tile's matrix exist
-    const int n0 = (in_g / gsize) * BT;
+    const int n0 = n_tile * BT;
     const int K = p.K;
     const int8_t* Wq = p.Wq;
     const float* s_w = p.s_w;
@@ -102,7 +86,7 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     if constexpr (MOE) {
         // m-tile slot -> (expert, tile within the expert); offsets clamped to [0, R] and made ascending, so a bad
         // table cannot move a write out of Y (as gemm_i8_kernel)
-        const int slot = first_m + in_g % gsize;
+        const int slot = m_tile;
         const int R = (int)p.M;                       // <= 0x7fffffff (host)
         int start = 0, e = -1, lo_e = 0, hi_e = 0;
         for (int j = 0; j < g.E; ++j) {
@@ -158,13 +142,9 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
         if (g.row_idx) {                              // gathered rows: offsets from Xq itself, < x_rows K <= 2^32
             srcA = p.Xq;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r = 16 * wave + 8 * i + (lane >> 3);
-                const int c = (lane & 7) ^ ((r >> 1) & 7);
-                const int64_t ra0 = r < a_last ? r : a_last, ra1 = HP + r < a_last ? HP + r : a_last;
-                voff[0][i] = (unsigned)((size_t)src_row(m0 + ra0) * K + 16 * c);
-                voff[3][i] = (unsigned)((size_t)src_row(m0 + ra1) * K + 16 * c);
-            }
+            for (int i = 0; i < 2; ++i)
+                i8_ring_a_voff(wave, lane, i, a_last, K, [&](int64_t ra) { return src_row(m0 + ra); }, voff[0][i],
+                               voff[3][i]);
         }
     }
     // unit i = 4 t + J: J is a compile-time constant wherever the slot is
@@ -264,7 +244,6 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     ring_stagger_end(group_b);
 
     // ---- epilogue: qt_gemm_i8's sequence, once per output element, by the lane that holds it ----
-    // C/D map of the 32x32 MFMA: column = lane & 31; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const bool asym = p.zp_x != nullptr;
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
@@ -281,7 +260,7 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
             for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int64_t m = m0 + qa * HP + wave_m * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int64_t m = i8_ring_cd_row(m0 + qa * HP + wave_m * 64 + mi * 32, r, lh);
                     if (m >= m_end) continue;
                     const int64_t ms = src_row(m);
                     int a = acc[qa][qb][mi][r];
@@ -308,18 +287,15 @@ extern "C" int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* W
                                const float* s_x, const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum,
                                const void* bias, void* Y, int out_dtype, int64_t ldy, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && M > 0 && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8_ring: bad arguments");
     QT_CHECK_ARG(w_format == QT_W_INT8, "qt_gemm_i8_ring: w_format %d unsupported: int8 weights only (packed int4 runs "
                  "on qt_gemm_i8)", w_format);
     QT_CHECK_ARG(G == 1, "qt_gemm_i8_ring: G %d unsupported: one scale group per row only (grouped scales run on "
                  "qt_gemm_i8)", G);
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_ring: K %d > 32768 (the int32 accumulator bound)", K);
     QT_CHECK_ARG(K % QT_I8_RING_K_UNIT == 0, "qt_gemm_i8_ring: K %d is not a multiple of the k-unit %d", K,
                  QT_I8_RING_K_UNIT);
-    QT_CHECK_ARG(((uintptr_t)Xq & 15) == 0, "qt_gemm_i8_ring: Xq is not 16-byte aligned");
-    QT_CHECK_ARG(((uintptr_t)Wq & 15) == 0, "qt_gemm_i8_ring: Wq is not 16-byte aligned");
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_ring: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_ring: zp_x needs wsum");
+    if (int st = qt_i8_check_dense("qt_gemm_i8_ring", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype, ldy,
+                                   true))
+        return st;
     static_assert(QT_I8_RING_K_UNIT == KU && QT_I8_RING_SLOTS == RING && QT_I8_RING_LEAD == LEAD, "header constants");
     const int64_t tiles = ((M + BT - 1) / BT) * (int64_t)((N + BT - 1) / BT);
     QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_gemm_i8_ring: too many tiles");
@@ -335,21 +311,18 @@ extern "C" int qt_gemm_i8_ring_grouped(const int8_t* Xq, int K, const int32_t* r
                                        const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, int64_t x_rows,
                                        qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && offsets && s_x && s_w && Y && R > 0 && E > 0 && N > 0 && K > 0 && ldy >= N && x_rows > 0,
-                 "qt_gemm_i8_ring_grouped: bad arguments");
+    QT_CHECK_ARG(x_rows > 0, "qt_gemm_i8_ring_grouped: bad arguments");
     QT_CHECK_ARG(w_format == QT_W_INT8, "qt_gemm_i8_ring_grouped: w_format %d unsupported: int8 weights only (packed "
                  "int4 runs on qt_gemm_i8_grouped)", w_format);
     QT_CHECK_ARG(G == 1, "qt_gemm_i8_ring_grouped: G %d unsupported: one scale group per row only (grouped scales run "
                  "on qt_gemm_i8_grouped)", G);
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_ring_grouped: K %d > 32768 (the int32 accumulator bound)", K);
     QT_CHECK_ARG(K % QT_I8_RING_K_UNIT == 0, "qt_gemm_i8_ring_grouped: K %d is not a multiple of the k-unit %d", K,
                  QT_I8_RING_K_UNIT);
-    QT_CHECK_ARG(((uintptr_t)Xq & 15) == 0, "qt_gemm_i8_ring_grouped: Xq is not 16-byte aligned");
-    QT_CHECK_ARG(((uintptr_t)Wq & 15) == 0, "qt_gemm_i8_ring_grouped: Wq is not 16-byte aligned");
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_ring_grouped: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_ring_grouped: zp_x needs wsum");
     QT_CHECK_ARG(R <= 0x7fffffffLL, "qt_gemm_i8_ring_grouped: R %lld too large", (long long)R);
     QT_CHECK_ARG(E <= 4096, "qt_gemm_i8_ring_grouped: E %d > 4096", E);
+    if (int st = qt_i8_check_grouped("qt_gemm_i8_ring_grouped", Xq, K, R, offsets, E, Wq, w_format, N, s_x, zp_x, s_w, G,
+                                     wsum, Y, out_dtype, ldy, true))
+        return st;
     // gathered rows are addressed by a 32-bit byte offset from Xq; contiguous rows need R of them
     QT_CHECK_ARG(!row_idx || x_rows * (int64_t)K <= (1LL << 32), "qt_gemm_i8_ring_grouped: x_rows %lld x K %d > 2^32 "
                  "bytes: a gathered row is addressed by a 32-bit offset", (long long)x_rows, K);

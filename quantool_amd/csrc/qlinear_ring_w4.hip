@@ -1,6 +1,7 @@
 // qt_gemm_i8_ring_w4: the prefill / perplexity form of qt_gemm_i8 for W4A8 (packed int4 weights, one scale per group of
 // 128 columns): qlinear_ring.hip's 256 x 256 tile and pipeline (ring_pipe.h: 8 waves, units A0, B0, B1, A1 per K-tile,
-// one unit issued per phase, counted vmcnt, two-group stagger) with packed B units and the grouped fold in every phase.
+// one unit issued per phase, counted vmcnt, two-group stagger; what the two files share is in i8_ring_tile.h) with
+// packed B units and the grouped fold in every phase.
 // Y is equal to qt_gemm_i8's to the bit (include/quantool_amd.h).
 //
 // WHY THE FOLD FITS.  A K-tile is 128 k-bytes = exactly one weight group g = t, and phase 4t + q computes quadrant q
@@ -15,7 +16,7 @@
 // zero offset keeps hipcc from hoisting 64 of them per lane into registers, as in gemm_i8_kernel).
 //
 // THE UNITS.  K-tile t = units 4t .. 4t+3, slot = unit % 8 of 16 KiB each (A0, B0, B1, A1 at slots (4t & 4) + 0..3):
-//   A0, A1  128 rows x 128 k-bytes, 16 KiB, 2 LDS-DMA (dwordx4) per wave: qlinear_ring.hip's unit and LDS image
+//   A0, A1  128 rows x 128 k-bytes, 16 KiB, 2 LDS-DMA (dwordx4) per wave: i8_ring_tile.h's unit and LDS image
 //           (piece = 8 rows x 128 B, 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7)).
 //   B0, B1  128 rows x 128 k = 64 packed bytes per row, 8 KiB (the lower half of the slot), 1 LDS-DMA per wave.
 //           LDS image: 8 pieces of 1 KiB, piece = 16 rows x 64 B (wave w fills piece w lane-linear); the 16-byte
@@ -49,22 +50,14 @@
 // computed and never stored; K is a whole number of K-tiles and G = K / 128, so no byte outside Xq[M, K],
 // Wq[N, K/8], s_w / wsum[N, G], s_x / zp_x[M] is read.
 #include "common.h"
+#include "i8_args.h"
 #include "i8_unpack.h"
-#include "ring_pipe.h"
+#include "i8_ring_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(16))) int i32x16;
-
-constexpr int RING = 8;                      // slots of 16 KiB (a B unit fills the lower half of its slot)
-constexpr int LEAD = 6;                      // unit u + LEAD is issued in phase u (LEAD <= RING - 2)
-constexpr int KU = 128;                      // k per K-tile = the weight group
-constexpr int HP = 128;                      // rows of a half panel
-constexpr int GROUP_M = 32;                  // m-tiles that walk the n-tiles together (as qlinear_ring.hip)
+// i8_ring_tile.h's instance with KU = the weight group; a B unit fills the lower half of its slot
 constexpr int SC_BYTES = 2048;               // one K-tile's scales: 256 s_w, 256 wsum
-static_assert(HP * KU == UNIT_BYTES, "an A unit is a half panel of 128 rows x 128 k-bytes");
-static_assert(LEAD <= RING - 2, "ring_pipe.h, WAR");
 
 struct RingW4Args {
     const int8_t* Xq;
@@ -99,17 +92,13 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     const int wave_m = wave >> 2, wave_n = wave & 3;
     const bool group_b = wave >= 4;  // wave-uniform
 
-    // tile order: GROUP_M m-tiles walk the n-tiles together (as gemm_i8_kernel)
     const int tiles_n = (p.N + BT - 1) / BT;
     const int tiles_m = (int)((p.M + BT - 1) / BT);
-    const int pid = blockIdx.x;
-    const int per_group = GROUP_M * tiles_n;
-    const int first_m = pid / per_group * GROUP_M;
-    const int gsize = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-    const int in_g = pid % per_group;
-    const int64_t m0 = (int64_t)(first_m + in_g % gsize) * BT;
+    int m_tile, n_tile;
+    i8_ring_tile_of(blockIdx.x, tiles_m, tiles_n, m_tile, n_tile);
+    const int64_t m0 = (int64_t)m_tile * BT;
     const int64_t m_end = p.M;
-    const int n0 = (in_g / gsize) * BT;
+    const int n0 = n_tile * BT;
     const int K = p.K, G = p.G;
     const int nu = K / KU * 4;                        // units = phases
 
@@ -120,7 +109,7 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     __syncthreads();
 
     // ---- staging geometry ----
-    // A: two LDS-DMA instructions per thread and unit (pieces 2 wave, 2 wave + 1), qlinear_ring.hip's
+    // A: two LDS-DMA instructions per thread and unit (i8_ring_tile.h)
     // B: one; lane: row 16 wave + (lane >> 2) of the half panel, physical chunk lane & 3
     // scales: one dword per lane, column 64 (wave & 3) + lane of the tile
     const int64_t a_last = m_end - 1 - m0;            // last valid row of the A / B panel, relative to the tile
@@ -129,13 +118,8 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     {
         unsigned voffA[2][2], voffB[2], voffS;        // [half][instruction], [half]
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = 16 * wave + 8 * i + (lane >> 3);
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            const int64_t ra0 = r < a_last ? r : a_last, ra1 = HP + r < a_last ? HP + r : a_last;   // clamped: a valid row
-            voffA[0][i] = (unsigned)((size_t)ra0 * K + 16 * c);          // < 256 * 32768
-            voffA[1][i] = (unsigned)((size_t)ra1 * K + 16 * c);
-        }
+        for (int i = 0; i < 2; ++i)
+            i8_ring_a_voff(wave, lane, i, a_last, K, [](int64_t ra) { return ra; }, voffA[0][i], voffA[1][i]);
         const int r = 16 * wave + (lane >> 2);
         const int c = (lane & 3) ^ ((r >> 2) & 3);
         const int rb0 = r < b_last ? r : b_last, rb1 = HP + r < b_last ? HP + r : b_last;
@@ -332,7 +316,6 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     fold(std::integral_constant<int, 3>{});           // the last phase's acc_g
 
     // ---- epilogue: y = s_x[m] * tot (+ bias[n]), once per output element, by the lane that holds it ----
-    // C/D map of the 32x32 MFMA: column = lane & 31; row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int ob = lane_bits();
     const int lr_e = (ob >> 5) & 31, lh_e = (ob >> 10) & 1;
 #pragma unroll
@@ -347,7 +330,7 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
             for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int64_t m = m0 + qa * HP + wave_m * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh_e;
+                    const int64_t m = i8_ring_cd_row(m0 + qa * HP + wave_m * 64 + mi * 32, r, lh_e);
                     if (m >= m_end) continue;
                     float y = p.s_x[m] * tot[qa][qb][mi][r];
                     if (p.bias) y = y + bn;
@@ -367,20 +350,16 @@ extern "C" int qt_gemm_i8_ring_w4(const int8_t* Xq, int64_t M, int K, const void
                                   const float* s_x, const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum,
                                   const void* bias, void* Y, int out_dtype, int64_t ldy, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && M > 0 && N > 0 && K > 0 && ldy >= N,
-                 "qt_gemm_i8_ring_w4: bad arguments");
     QT_CHECK_ARG(w_format == QT_W_INT4_PACKED, "qt_gemm_i8_ring_w4: w_format %d unsupported: packed int4 weights only "
                  "(int8 weights run on qt_gemm_i8_ring)", w_format);
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_ring_w4: K %d > 32768 (the int32 accumulator bound)", K);
     QT_CHECK_ARG(K % QT_I8_RING_W4_K_UNIT == 0, "qt_gemm_i8_ring_w4: K %d is not a multiple of the k-unit %d", K,
                  QT_I8_RING_W4_K_UNIT);
     QT_CHECK_ARG(G == K / QT_I8_RING_W4_K_UNIT, "qt_gemm_i8_ring_w4: G %d unsupported: one scale per group of %d "
                  "columns only, G = K / %d = %d (channel-wise scales run on qt_gemm_i8)", G, QT_I8_RING_W4_K_UNIT,
                  QT_I8_RING_W4_K_UNIT, K / QT_I8_RING_W4_K_UNIT);
-    QT_CHECK_ARG(((uintptr_t)Xq & 15) == 0, "qt_gemm_i8_ring_w4: Xq is not 16-byte aligned");
-    QT_CHECK_ARG(((uintptr_t)Wq & 15) == 0, "qt_gemm_i8_ring_w4: Wq is not 16-byte aligned");
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_ring_w4: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_ring_w4: zp_x needs wsum");
+    if (int st = qt_i8_check_dense("qt_gemm_i8_ring_w4", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype,
+                                   ldy, true))
+        return st;
     static_assert(QT_I8_RING_W4_K_UNIT == KU && QT_I8_RING_W4_SLOTS == RING && QT_I8_RING_W4_LEAD == LEAD,
                   "header constants");
     const int64_t tiles = ((M + BT - 1) / BT) * (int64_t)((N + BT - 1) / BT);

@@ -21,6 +21,7 @@
 //
 // -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own.
 #include "common.h"
+#include "i8_args.h"
 #include "i8_unpack.h"
 
 namespace {
@@ -294,15 +295,10 @@ extern "C" int qt_gemm_i8_skinny(const int8_t* Xq, int M, int K, const void* Wq,
                                  const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias,
                                  void* Y, int out_dtype, int64_t ldy, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && s_x && s_w && Y && N > 0 && K > 0 && ldy >= N, "qt_gemm_i8_skinny: bad arguments");
     QT_CHECK_ARG(M >= 1 && M <= SK_MAX_M, "qt_gemm_i8_skinny: M %d outside 1 .. %d", M, SK_MAX_M);
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_skinny: K %d > 32768 (the int32 accumulator bound)", K);
-    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_i8_skinny: w_format %d unsupported",
-                 w_format);
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_skinny: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8_skinny: G %d must be 1 or ceil(K / 128) = %d", G,
-                 (K + 127) / 128);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_skinny: zp_x needs wsum");
+    if (int st = qt_i8_check_dense("qt_gemm_i8_skinny", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype,
+                                   ldy))
+        return st;
     const bool int4 = w_format == QT_W_INT4_PACKED;
     const bool vec = (((uintptr_t)Xq | (uintptr_t)Wq) & 15) == 0 && K % 16 == 0 && (!int4 || ((K + 7) / 8) % 4 == 0);
     SkinnyArgs a{Xq, Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, (K + 7) / 8, G, ldy, out_dtype, nullptr, nullptr, 0};
@@ -317,16 +313,9 @@ extern "C" int qt_gemm_i8_skinny_grouped(const int8_t* Xq, int K, const int32_t*
                                          const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
                                          qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(Xq && Wq && offsets && s_x && s_w && Y && R > 0 && E > 0 && N > 0 && K > 0 && ldy >= N,
-                 "qt_gemm_i8_skinny_grouped: bad arguments");
-    QT_CHECK_ARG(K <= 32768, "qt_gemm_i8_skinny_grouped: K %d > 32768 (the int32 accumulator bound)", K);
-    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED,
-                 "qt_gemm_i8_skinny_grouped: w_format %d unsupported", w_format);
-    QT_CHECK_ARG(qt_dtype_is16(out_dtype), "qt_gemm_i8_skinny_grouped: out_dtype %d must be bf16 or fp16", out_dtype);
-    QT_CHECK_ARG(G == 1 || G == (K + 127) / 128, "qt_gemm_i8_skinny_grouped: G %d must be 1 or ceil(K / 128) = %d", G,
-                 (K + 127) / 128);
-    QT_CHECK_ARG(!zp_x || wsum, "qt_gemm_i8_skinny_grouped: zp_x needs wsum");
-    QT_CHECK_ARG(R <= 0x7fffffffLL && E <= 4096, "qt_gemm_i8_skinny_grouped: R %lld or E %d too large", (long long)R, E);
+    if (int st = qt_i8_check_grouped("qt_gemm_i8_skinny_grouped", Xq, K, R, offsets, E, Wq, w_format, N, s_x, zp_x, s_w, G,
+                                     wsum, Y, out_dtype, ldy))
+        return st;
     const int64_t slots = R / SK_MAX_M + (E < R ? E : R);
     QT_CHECK_ARG(slots <= 65535, "qt_gemm_i8_skinny_grouped: %lld row-tile slots (R = %lld) exceed the grid",
                  (long long)slots, (long long)R);

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import logging
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -555,12 +556,101 @@ def _i8_operands(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: tor
     return fmt, N, K, G
 
 
-def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
-            zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
-            bias: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16) -> torch.Tensor:
-    """Y [M, N] = s_x[m] * sum_g s_w[n, g] * (acc_g - zp_x[m] * wsum[n, g]) (+ bias): the fixed sequence of
-    ``qt_gemm_i8`` (include/quantool_amd.h).  Wq int8 [N, K], or packed int4 int32 [N, ceil(K/8)] (then ``K`` is
-    required); s_w fp32 [N, G], G = 1 or ceil(K/128); zp_x int32 [M] needs wsum int32 [N, G]."""
+@dataclass(frozen=True)
+class I8Form:
+    """One int8 GEMM entry point and what it takes of the operands ``_i8_operands`` admits.  ``groups`` is the rule for
+    G = s_w.shape[-1]: "any" (1 or ceil(K/128)), "one", "per_unit" (K / k_unit) or "one_or_per_unit".  A form without
+    a ``k_unit`` takes every K, weight format, G and alignment the tiled kernel takes."""
+    entry: str
+    min_m: int = 1
+    max_m: Optional[int] = None
+    dtypes: tuple = (torch.int8, torch.int32)
+    k_unit: Optional[int] = None
+    groups: str = "any"
+    aligned16: bool = False
+    experts: bool = False
+    max_e: Optional[int] = None      # experts a workgroup walks
+    x_rows: bool = False             # the entry point takes the number of rows of Xq behind ldy
+    slots: Optional[int] = None      # half panels resident in LDS
+    lead: Optional[int] = None       # half panels the LDS-DMA runs ahead of the MFMAs
+
+
+_RING = dict(dtypes=(torch.int8,), k_unit=128, groups="one", aligned16=True, slots=8, lead=6)
+I8_FORMS = {f.entry: f for f in (
+    I8Form("qt_gemm_i8"),
+    I8Form("qt_gemm_i8_skinny", max_m=16),
+    I8Form("qt_gemm_i8_mid", max_m=128, k_unit=128, groups="one_or_per_unit", aligned16=True),
+    I8Form("qt_gemm_i8_ring", **_RING),
+    I8Form("qt_gemm_i8_ring_w4", **{**_RING, "dtypes": (torch.int32,), "groups": "per_unit"}),
+    I8Form("qt_gemm_i8_grouped", experts=True),
+    I8Form("qt_gemm_i8_skinny_grouped", experts=True),
+    I8Form("qt_gemm_i8_ring_grouped", experts=True, max_e=4096, x_rows=True, **_RING),
+)}
+
+I8_SKINNY_MAX_M = I8_FORMS["qt_gemm_i8_skinny"].max_m   # rows of Xq qt_gemm_i8_skinny takes
+# k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
+I8_RING_K_UNIT = I8_FORMS["qt_gemm_i8_ring"].k_unit
+I8_RING_SLOTS = I8_FORMS["qt_gemm_i8_ring"].slots       # half panels (128 rows x 128 k-bytes) resident in LDS
+I8_RING_LEAD = I8_FORMS["qt_gemm_i8_ring"].lead         # half panels the LDS-DMA runs ahead of the MFMAs
+# k per K-tile of qt_gemm_i8_ring_w4 = the weight group (QT_I8_RING_W4_K_UNIT): K a multiple
+I8_RING_W4_K_UNIT = I8_FORMS["qt_gemm_i8_ring_w4"].k_unit
+I8_RING_W4_SLOTS = I8_FORMS["qt_gemm_i8_ring_w4"].slots
+I8_RING_W4_LEAD = I8_FORMS["qt_gemm_i8_ring_w4"].lead
+I8_MID_MAX_M = I8_FORMS["qt_gemm_i8_mid"].max_m         # rows of Xq qt_gemm_i8_mid takes (QT_I8_MID_MAX_M)
+I8_MID_K_UNIT = I8_FORMS["qt_gemm_i8_mid"].k_unit       # columns per k-block of qt_gemm_i8_mid: K must be a multiple
+I8_RING_GROUPED_MAX_E = I8_FORMS["qt_gemm_i8_ring_grouped"].max_e   # experts qt_gemm_i8_ring_grouped walks per workgroup
+
+
+def _i8_refusal(form: I8Form, Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                row_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``form``'s entry point would refuse these operands, or None.  Host-only: touches no library."""
+    if form.max_m is not None:
+        M = Xq.shape[0] if Xq.dim() == 2 else -1
+        if not form.min_m <= M <= form.max_m:
+            return f"{form.min_m} <= M <= {form.max_m} rows only, got Xq {tuple(Xq.shape)}"
+    U = form.k_unit
+    if U is None:
+        return None
+    tiled = "gemm_i8_grouped" if form.experts else "gemm_i8"
+    if Wq.dtype not in form.dtypes:
+        if form.dtypes == (torch.int8,):
+            return f"int8 weights only, got {Wq.dtype} (packed int4 runs on {tiled})"
+        if form.dtypes == (torch.int32,):
+            return f"packed int4 (int32) weights only, got {Wq.dtype} (int8 weights run on gemm_i8_ring)"
+        return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
+    x_rows, K = Xq.shape[0], Xq.shape[-1]
+    if K % U != 0:
+        return f"K={K} is not a multiple of the k-unit {U}"
+    if K > 32768:
+        return f"K={K} > 32768: the int32 accumulator could overflow"
+    G = s_w.shape[-1] if s_w.dim() == (3 if form.experts else 2) else -1
+    if form.groups == "one" and G != 1:
+        return f"one scale group per row only, got s_w {tuple(s_w.shape)} (grouped scales run on {tiled})"
+    if form.groups == "per_unit" and G != K // U:
+        return (f"one scale per group of {U} columns only, G = K / {U} = {K // U}, got s_w {tuple(s_w.shape)} "
+                f"(channel-wise scales run on {tiled})")
+    if form.groups == "one_or_per_unit" and G not in (1, K // U):
+        return f"G must be 1 or K / {U} = {K // U}, got s_w {tuple(s_w.shape)}"
+    if form.aligned16 and (Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0):
+        return "Xq and Wq must be 16-byte aligned"
+    if form.experts:
+        if row_idx is not None and x_rows * K > 2 ** 32:
+            return f"Xq has {x_rows} rows x K={K} > 2^32 bytes: a gathered row is addressed by a 32-bit offset"
+        E, N = Wq.shape[0], Wq.shape[-2]
+        if E > form.max_e:
+            return f"E={E} > {form.max_e} experts"
+        R = x_rows if row_idx is None else row_idx.numel()
+        if ((R + 255) // 256 + E) * ((N + 255) // 256) > 0x7fffffff:
+            return f"too many tiles: R={R}, E={E}, N={N}"
+    return None
+
+
+def _gemm_i8_dense(form: I8Form, Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype) -> torch.Tensor:
+    """The refusal, the operand checks and the call the dense int8 GEMMs share; ``form`` is the entry point's row of
+    ``I8_FORMS``."""
+    why = _i8_refusal(form, Xq, Wq, s_w)
+    if why is not None:
+        raise ValueError(f"{form.entry[3:]}: {why}")
     lib = load()
     fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
     M = Xq.shape[0]
@@ -569,13 +659,19 @@ def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Te
         if bias.numel() != N or not bias.is_contiguous():
             raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
     Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8", lib.qt_gemm_i8(
+    check(form.entry, getattr(lib, form.entry)(
         Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
         _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
     return Y
 
 
-I8_SKINNY_MAX_M = 16   # rows of Xq qt_gemm_i8_skinny takes
+def gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, K: Optional[int] = None,
+            zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+            bias: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """Y [M, N] = s_x[m] * sum_g s_w[n, g] * (acc_g - zp_x[m] * wsum[n, g]) (+ bias): the fixed sequence of
+    ``qt_gemm_i8`` (include/quantool_amd.h).  Wq int8 [N, K], or packed int4 int32 [N, ceil(K/8)] (then ``K`` is
+    required); s_w fp32 [N, G], G = 1 or ceil(K/128); zp_x int32 [M] needs wsum int32 [N, G]."""
+    return _gemm_i8_dense(I8_FORMS["qt_gemm_i8"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def gemm_i8_skinny(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
@@ -584,47 +680,13 @@ def gemm_i8_skinny(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: t
                    out_dtype=torch.bfloat16) -> torch.Tensor:
     """``gemm_i8`` for 1 <= M <= 16 rows (``qt_gemm_i8_skinny``): the decode GEMV.  Same arguments; Y equals
     ``gemm_i8``'s to the bit."""
-    M = Xq.shape[0] if Xq.dim() == 2 else -1
-    if not 1 <= M <= I8_SKINNY_MAX_M:
-        raise ValueError(f"gemm_i8_skinny takes 1 <= M <= {I8_SKINNY_MAX_M} rows, got Xq {tuple(Xq.shape)}")
-    lib = load()
-    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
-    if bias is not None:
-        _req(bias, out_dtype, "bias", 1)
-        if bias.numel() != N or not bias.is_contiguous():
-            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
-    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8_skinny", lib.qt_gemm_i8_skinny(
-        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
-        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
-    return Y
-
-
-I8_RING_K_UNIT = 128   # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
-I8_RING_SLOTS = 8      # half panels (128 rows x 128 k-bytes) resident in LDS (QT_I8_RING_SLOTS)
-I8_RING_LEAD = 6       # half panels the LDS-DMA runs ahead of the MFMAs (QT_I8_RING_LEAD)
-
-
-def _i8_ring_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
-    """Why ``qt_gemm_i8_ring`` would refuse these operands, or None.  Host-only: touches no library."""
-    if Wq.dtype != torch.int8:
-        return f"int8 weights only, got {Wq.dtype} (packed int4 runs on gemm_i8)"
-    if s_w.dim() != 2 or s_w.shape[-1] != 1:
-        return f"one scale group per row only, got s_w {tuple(s_w.shape)} (grouped scales run on gemm_i8)"
-    K = Xq.shape[-1]
-    if K % I8_RING_K_UNIT != 0:
-        return f"K={K} is not a multiple of the k-unit {I8_RING_K_UNIT}"
-    if K > 32768:
-        return f"K={K} > 32768: the int32 accumulator could overflow"
-    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
-        return "Xq and Wq must be 16-byte aligned"
-    return None
+    return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_skinny"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def gemm_i8_ring_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
     """Whether ``gemm_i8_ring`` takes these operands: an int8 weight with one scale group, K a multiple of
     ``I8_RING_K_UNIT`` and at most 32768, both operands 16-byte aligned.  Host-only."""
-    return _i8_ring_refusal(Xq, Wq, s_w) is None
+    return _i8_refusal(I8_FORMS["qt_gemm_i8_ring"], Xq, Wq, s_w) is None
 
 
 def gemm_i8_ring(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
@@ -633,49 +695,13 @@ def gemm_i8_ring(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: tor
                  out_dtype=torch.bfloat16) -> torch.Tensor:
     """``gemm_i8`` on the 256 x 256 LDS-ring kernel (``qt_gemm_i8_ring``): the prefill form for W8A8 / INT8.  Same
     arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where ``gemm_i8_ring_supported`` is false."""
-    why = _i8_ring_refusal(Xq, Wq, s_w)
-    if why is not None:
-        raise ValueError(f"gemm_i8_ring: {why}")
-    lib = load()
-    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
-    M = Xq.shape[0]
-    if bias is not None:
-        _req(bias, out_dtype, "bias", 1)
-        if bias.numel() != N or not bias.is_contiguous():
-            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
-    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8_ring", lib.qt_gemm_i8_ring(
-        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
-        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
-    return Y
-
-
-I8_RING_W4_K_UNIT = 128   # k per K-tile of qt_gemm_i8_ring_w4 = the weight group (QT_I8_RING_W4_K_UNIT): K a multiple
-I8_RING_W4_SLOTS = 8      # half panels resident in LDS (QT_I8_RING_W4_SLOTS)
-I8_RING_W4_LEAD = 6       # half panels the LDS-DMA runs ahead of the MFMAs (QT_I8_RING_W4_LEAD)
-
-
-def _i8_ring_w4_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
-    """Why ``qt_gemm_i8_ring_w4`` would refuse these operands, or None.  Host-only: touches no library."""
-    if Wq.dtype != torch.int32:
-        return f"packed int4 (int32) weights only, got {Wq.dtype} (int8 weights run on gemm_i8_ring)"
-    K = Xq.shape[-1]
-    if K % I8_RING_W4_K_UNIT != 0:
-        return f"K={K} is not a multiple of the k-unit {I8_RING_W4_K_UNIT}"
-    if K > 32768:
-        return f"K={K} > 32768: the int32 accumulator could overflow"
-    if s_w.dim() != 2 or s_w.shape[-1] != K // I8_RING_W4_K_UNIT:
-        return (f"one scale per group of {I8_RING_W4_K_UNIT} columns only, G = K / {I8_RING_W4_K_UNIT} = "
-                f"{K // I8_RING_W4_K_UNIT}, got s_w {tuple(s_w.shape)} (channel-wise scales run on gemm_i8)")
-    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
-        return "Xq and Wq must be 16-byte aligned"
-    return None
+    return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_ring"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def gemm_i8_ring_w4_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
     """Whether ``gemm_i8_ring_w4`` takes these operands: a packed int4 weight with one scale per 128 columns, K a
     multiple of ``I8_RING_W4_K_UNIT`` and at most 32768, both operands 16-byte aligned.  Host-only."""
-    return _i8_ring_w4_refusal(Xq, Wq, s_w) is None
+    return _i8_refusal(I8_FORMS["qt_gemm_i8_ring_w4"], Xq, Wq, s_w) is None
 
 
 def gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
@@ -685,50 +711,13 @@ def gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
     """``gemm_i8`` on the 256 x 256 LDS-ring kernel for packed int4 weights (``qt_gemm_i8_ring_w4``): the prefill form
     for W4A8.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where ``gemm_i8_ring_w4_supported``
     is false."""
-    why = _i8_ring_w4_refusal(Xq, Wq, s_w)
-    if why is not None:
-        raise ValueError(f"gemm_i8_ring_w4: {why}")
-    lib = load()
-    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
-    M = Xq.shape[0]
-    if bias is not None:
-        _req(bias, out_dtype, "bias", 1)
-        if bias.numel() != N or not bias.is_contiguous():
-            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
-    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8_ring_w4", lib.qt_gemm_i8_ring_w4(
-        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
-        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
-    return Y
-
-
-I8_MID_MAX_M = 128    # rows of Xq qt_gemm_i8_mid takes (QT_I8_MID_MAX_M)
-I8_MID_K_UNIT = 128   # columns per k-block of qt_gemm_i8_mid (QT_I8_MID_K_UNIT): K must be a multiple
-
-
-def _i8_mid_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> Optional[str]:
-    """Why ``qt_gemm_i8_mid`` would refuse these operands, or None.  Host-only: touches no library."""
-    M = Xq.shape[0] if Xq.dim() == 2 else -1
-    if not 1 <= M <= I8_MID_MAX_M:
-        return f"1 <= M <= {I8_MID_MAX_M} rows only, got Xq {tuple(Xq.shape)}"
-    if Wq.dtype not in (torch.int8, torch.int32):
-        return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
-    K = Xq.shape[-1]
-    if K % I8_MID_K_UNIT != 0:
-        return f"K={K} is not a multiple of the k-unit {I8_MID_K_UNIT}"
-    if K > 32768:
-        return f"K={K} > 32768: the int32 accumulator could overflow"
-    if s_w.dim() != 2 or s_w.shape[-1] not in (1, K // I8_MID_K_UNIT):
-        return f"G must be 1 or K / {I8_MID_K_UNIT} = {K // I8_MID_K_UNIT}, got s_w {tuple(s_w.shape)}"
-    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
-        return "Xq and Wq must be 16-byte aligned"
-    return None
+    return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_ring_w4"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def gemm_i8_mid_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
     """Whether ``gemm_i8_mid`` takes these operands: 1 to ``I8_MID_MAX_M`` rows, K a multiple of ``I8_MID_K_UNIT`` and at
     most 32768, G = 1 or K/128, both operands 16-byte aligned.  Host-only."""
-    return _i8_mid_refusal(Xq, Wq, s_w) is None
+    return _i8_refusal(I8_FORMS["qt_gemm_i8_mid"], Xq, Wq, s_w) is None
 
 
 def gemm_i8_mid(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
@@ -738,21 +727,7 @@ def gemm_i8_mid(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torc
     """``gemm_i8`` for 1 <= M <= 128 rows on the weight-streaming 16-column tile (``qt_gemm_i8_mid``): batched decode,
     speculative verification, short prompts.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where
     ``gemm_i8_mid_supported`` is false."""
-    why = _i8_mid_refusal(Xq, Wq, s_w)
-    if why is not None:
-        raise ValueError(f"gemm_i8_mid: {why}")
-    lib = load()
-    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
-    M = Xq.shape[0]
-    if bias is not None:
-        _req(bias, out_dtype, "bias", 1)
-        if bias.numel() != N or not bias.is_contiguous():
-            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
-    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
-    check("qt_gemm_i8_mid", lib.qt_gemm_i8_mid(
-        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
-        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), _stream()))
-    return Y
+    return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_mid"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def moe_route(top_k_index: torch.Tensor, num_experts: int):
@@ -778,10 +753,12 @@ def moe_route(top_k_index: torch.Tensor, num_experts: int):
     return offsets, src_token, src_slot, row_of
 
 
-def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype,
-                     x_rows: bool = False) -> torch.Tensor:
-    """The operand checks and the call the grouped int8 GEMMs share; ``fn`` names the entry point (``x_rows``: it takes
-    the number of rows of Xq behind ldy)."""
+def _gemm_i8_grouped(form: I8Form, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype) -> torch.Tensor:
+    """The refusal, the operand checks and the call the grouped int8 GEMMs share; ``form`` is the entry point's row of
+    ``I8_FORMS``."""
+    why = _i8_refusal(form, Xq, Wq, s_w, row_idx)
+    if why is not None:
+        raise ValueError(f"{form.entry[3:]}: {why}")
     lib = load()
     fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype, experts=True)
     Mx, E = Xq.shape[0], Wq.shape[0]
@@ -802,9 +779,9 @@ def _gemm_i8_grouped(fn: str, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x,
     if R <= 0:
         raise ValueError(f"rows must be positive, got {R}")
     Y = torch.empty((R, N), dtype=out_dtype, device=Xq.device)
-    check(fn, getattr(lib, fn)(
+    check(form.entry, getattr(lib, form.entry)(
         Xq.data_ptr(), K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x),
-        s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), *((Mx,) if x_rows else ()),
+        s_w.data_ptr(), G, _ptr(wsum), Y.data_ptr(), _dtype_code(Y), Y.stride(0), *((Mx,) if form.x_rows else ()),
         _stream()))
     return Y
 
@@ -818,7 +795,7 @@ def gemm_i8_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
     required); s_w fp32 [E, N, G]; wsum int32 [E, N, G] (needed with zp_x).  A rows: Xq[row_idx[m]] when ``row_idx``
     (int32 [R], e.g. ``moe_route``'s src_token) is given, with s_x / zp_x read at the same index; else Xq[m] (then R
     defaults to Xq's rows).  Rows past offsets[E] are left unwritten."""
-    return _gemm_i8_grouped("qt_gemm_i8_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
+    return _gemm_i8_grouped(I8_FORMS["qt_gemm_i8_grouped"], Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
 
 
 def gemm_i8_skinny_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
@@ -829,36 +806,8 @@ def gemm_i8_skinny_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor
     """``gemm_i8_grouped`` on the decode tile (``qt_gemm_i8_skinny_grouped``): every expert's rows in tiles of 16, only
     the experts that own rows read, each once per tile.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit.
     R // 16 + min(E, R) row-tile slots must fit a grid dimension (65535)."""
-    return _gemm_i8_grouped("qt_gemm_i8_skinny_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
+    return _gemm_i8_grouped(I8_FORMS["qt_gemm_i8_skinny_grouped"], Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
                             out_dtype)
-
-
-I8_RING_GROUPED_MAX_E = 4096   # experts qt_gemm_i8_ring_grouped walks per workgroup
-
-
-def _i8_ring_grouped_refusal(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
-                             row_idx: Optional[torch.Tensor]) -> Optional[str]:
-    """Why ``qt_gemm_i8_ring_grouped`` would refuse these operands, or None.  Host-only: touches no library."""
-    if Wq.dtype != torch.int8:
-        return f"int8 weights only, got {Wq.dtype} (packed int4 runs on gemm_i8_grouped)"
-    if s_w.dim() != 3 or s_w.shape[-1] != 1:
-        return f"one scale group per row only, got s_w {tuple(s_w.shape)} (grouped scales run on gemm_i8_grouped)"
-    x_rows, K = Xq.shape[0], Xq.shape[-1]
-    if K % I8_RING_K_UNIT != 0:
-        return f"K={K} is not a multiple of the k-unit {I8_RING_K_UNIT}"
-    if K > 32768:
-        return f"K={K} > 32768: the int32 accumulator could overflow"
-    if Xq.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0:
-        return "Xq and Wq must be 16-byte aligned"
-    if row_idx is not None and x_rows * K > 2 ** 32:
-        return f"Xq has {x_rows} rows x K={K} > 2^32 bytes: a gathered row is addressed by a 32-bit offset"
-    E, N = Wq.shape[0], Wq.shape[-2]
-    if E > I8_RING_GROUPED_MAX_E:
-        return f"E={E} > {I8_RING_GROUPED_MAX_E} experts"
-    R = x_rows if row_idx is None else row_idx.numel()
-    if ((R + 255) // 256 + E) * ((N + 255) // 256) > 0x7fffffff:
-        return f"too many tiles: R={R}, E={E}, N={N}"
-    return None
 
 
 def gemm_i8_ring_grouped_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
@@ -866,7 +815,7 @@ def gemm_i8_ring_grouped_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torc
     """Whether ``gemm_i8_ring_grouped`` takes these operands: an int8 bank [E, N, K] with one scale group, K a multiple
     of ``I8_RING_K_UNIT`` and at most 32768, both operands 16-byte aligned, at most 4096 experts, a grid that fits,
     and, with ``row_idx``, an Xq of at most 2^32 bytes.  Host-only."""
-    return _i8_ring_grouped_refusal(Xq, Wq, s_w, row_idx) is None
+    return _i8_refusal(I8_FORMS["qt_gemm_i8_ring_grouped"], Xq, Wq, s_w, row_idx) is None
 
 
 def gemm_i8_ring_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
@@ -877,11 +826,8 @@ def gemm_i8_ring_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, 
     """``gemm_i8_grouped`` on the 256 x 256 LDS-ring tile (``qt_gemm_i8_ring_grouped``): the prefill form for W8A8 /
     INT8 banks.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit; ``row_idx`` values are clamped into Xq's
     rows.  ``ValueError`` where ``gemm_i8_ring_grouped_supported`` is false."""
-    why = _i8_ring_grouped_refusal(Xq, Wq, s_w, row_idx)
-    if why is not None:
-        raise ValueError(f"gemm_i8_ring_grouped: {why}")
-    return _gemm_i8_grouped("qt_gemm_i8_ring_grouped", Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum,
-                            out_dtype, x_rows=True)
+    return _gemm_i8_grouped(I8_FORMS["qt_gemm_i8_ring_grouped"], Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x,
+                            wsum, out_dtype)
 
 
 def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:

@@ -3,45 +3,36 @@
 touch the library, and ``QuantizedLinear`` picks the kernel by ``mid_max_m`` / ``mid_max_n`` / ``mid_min_k`` (with
 ``quantool_amd.hip.ops`` replaced by a recording fake, so nothing reaches a device)."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.i8_fake_ops import aligned_i8 as _aligned_i8
+from tests.i8_fake_ops import check_surface, fake_ops, header_constants, header_text  # noqa: F401
+
 NAME = "qt_gemm_i8_mid"
+WATCH = "gemm_i8_mid_supported"
+# the dispatch rules under test, whatever the measured class defaults are
+LINEAR_ATTRS = {"skinny_max_m": 16, "ring_min_m": 2048, "mid_max_m": 96, "mid_max_n": 0, "mid_min_k": 512}
 
 
 # ---- surface --------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_point_and_the_constants():
     from quantool_amd.hip import ops
 
-    raw = (ROOT / "include" / "quantool_amd.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert NAME in set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text))
-    consts = dict(re.findall(r"#define\s+(QT_I8_MID_[A-Z_]+)\s+(\d+)", text))
-    assert {k: int(v) for k, v in consts.items()} == {"QT_I8_MID_MAX_M": ops.I8_MID_MAX_M,
-                                                      "QT_I8_MID_K_UNIT": ops.I8_MID_K_UNIT}
+    check_surface("header", NAME)
+    assert header_constants("QT_I8_MID_") == {"QT_I8_MID_MAX_M": ops.I8_MID_MAX_M,
+                                              "QT_I8_MID_K_UNIT": ops.I8_MID_K_UNIT}
     assert ops.I8_MID_MAX_M == 128 and ops.I8_MID_K_UNIT == 128
-    assert f"{NAME}:" in raw                              # documented in the A8 block's comment
+    assert f"{NAME}:" in header_text()[0]                 # documented in the A8 block's comment
 
 
 def test_ctypes_table_holds_it_with_the_tiled_signature():
-    from quantool_amd.hip import _lib
-
-    assert _lib.SIGNATURES[NAME] == _lib.SIGNATURES["qt_gemm_i8"]
+    check_surface("ctypes", NAME, "qt_gemm_i8")
 
 
 def test_library_exports_it():
-    from quantool_amd.hip import _lib
-
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-
-        g.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
-    assert NAME in {line.split()[-1] for line in out.splitlines() if " T " in line}
+    check_surface("library", NAME)
 
 
 def test_no_workspace_function_was_added():
@@ -71,12 +62,6 @@ def test_build_audits_cover_the_new_file():
 
 
 # ---- refusals before the library ------------------------------------------------------------------------------------
-def _aligned_i8(rows, cols, shift=0):
-    buf = torch.zeros(rows * cols + 32, dtype=torch.int8)
-    off = (-buf.data_ptr()) % 16 + shift
-    return buf[off:off + rows * cols].view(rows, cols)
-
-
 REFUSED = {
     "M = 0": (lambda: (_aligned_i8(0, 256), _aligned_i8(8, 256), torch.ones(8, 1)), "1 <= M <= 128"),
     "M = 129": (lambda: (_aligned_i8(129, 256), _aligned_i8(8, 256), torch.ones(8, 1)), "1 <= M <= 128"),
@@ -102,7 +87,7 @@ def test_unsupported_operands_are_refused_before_the_library(monkeypatch, case):
     make, reason = REFUSED[case]
     Xq, Wq, s_w = make()
     assert ops.gemm_i8_mid_supported(Xq, Wq, s_w) is False
-    assert reason in ops._i8_mid_refusal(Xq, Wq, s_w)
+    assert reason in ops._i8_refusal(ops.I8_FORMS[NAME], Xq, Wq, s_w)
     with pytest.raises(ValueError, match=reason):
         ops.gemm_i8_mid(Xq, torch.ones(Xq.shape[0]), Wq, s_w, K=Xq.shape[1])
 
@@ -121,66 +106,6 @@ def test_supported_operands(monkeypatch):
 
 
 # ---- dispatch -------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for quantool_amd.hip.ops: the four GEMMs of a Linear record (name, rows); quantize_tokens_i8 returns
-    tensors of the right shapes on the CPU."""
-
-    I8_SKINNY_MAX_M = 16
-    I8_MID_MAX_M = 128
-
-    def __init__(self):
-        self.calls = []
-        self.supported = True
-        self.asked = 0
-        self.ring_asked = 0
-
-    def quantize_tokens_i8(self, X, symmetric=True, col_perm=None):
-        M = X.shape[0]
-        zp = None if symmetric else torch.zeros(M, dtype=torch.int32)
-        return torch.zeros(X.shape, dtype=torch.int8), torch.ones(M), zp
-
-    def _gemm(self, name, Xq, Wq, out_dtype):
-        self.calls.append((name, Xq.shape[0]))
-        return torch.zeros(Xq.shape[0], Wq.shape[-2], dtype=out_dtype)
-
-    def gemm_i8(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_skinny(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_skinny", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_ring(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_ring", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_mid(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_mid", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_ring_supported(self, Xq, Wq, s_w):
-        self.ring_asked += 1
-        return True
-
-    def gemm_i8_mid_supported(self, Xq, Wq, s_w):
-        self.asked += 1
-        return self.supported
-
-
-@pytest.fixture
-def fake_ops(monkeypatch):
-    import quantool_amd.hip as hip
-    from quantool_amd.engine.qmodules import QuantizedLinear
-    from quantool_amd.hip import ops as real   # noqa: F401  (the attribute the modules import must exist first)
-
-    rec = _Recorder()
-    monkeypatch.setattr(hip, "ops", rec)
-    # the dispatch rules under test, whatever the measured class defaults are
-    monkeypatch.setattr(QuantizedLinear, "skinny_max_m", 16)
-    monkeypatch.setattr(QuantizedLinear, "ring_min_m", 2048)
-    monkeypatch.setattr(QuantizedLinear, "mid_max_m", 96)
-    monkeypatch.setattr(QuantizedLinear, "mid_max_n", 0)
-    monkeypatch.setattr(QuantizedLinear, "mid_min_k", 512)
-    return rec
-
-
 def _linear(K=512, N=24, int4=False):
     from quantool_amd.engine.qmodules import QuantizedLinear
 

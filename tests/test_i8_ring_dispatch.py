@@ -2,28 +2,23 @@
 ``qt_gemm_i8_ring``, ``ops.gemm_i8_ring_supported`` / ``ops.gemm_i8_ring`` refuse what the kernel does not take before
 they touch the library, and ``QuantizedLinear`` picks the ring by ``ring_min_m`` (with ``quantool_amd.hip.ops`` replaced
 by a recording fake, so nothing reaches a device)."""
-import re
-import subprocess
-from pathlib import Path
-
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.i8_fake_ops import aligned_i8, check_surface, fake_ops, header_constants  # noqa: F401
+
 NAME = "qt_gemm_i8_ring"
+WATCH = "gemm_i8_ring_supported"
 
 
 # ---- surface --------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_point_and_the_ring_constants():
     from quantool_amd.hip import ops
 
-    raw = (ROOT / "include" / "quantool_amd.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert NAME in set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text))
-    consts = dict(re.findall(r"#define\s+(QT_I8_RING_[A-Z_]+)\s+(\d+)", text))
-    assert {k: int(v) for k, v in consts.items()} == {"QT_I8_RING_K_UNIT": ops.I8_RING_K_UNIT,
-                                                      "QT_I8_RING_SLOTS": ops.I8_RING_SLOTS,
-                                                      "QT_I8_RING_LEAD": ops.I8_RING_LEAD}
+    check_surface("header", NAME)
+    assert header_constants("QT_I8_RING_") == {"QT_I8_RING_K_UNIT": ops.I8_RING_K_UNIT,
+                                               "QT_I8_RING_SLOTS": ops.I8_RING_SLOTS,
+                                               "QT_I8_RING_LEAD": ops.I8_RING_LEAD}
     # the contract's limits: a unit of at most 128 that divides both Llama-3-8B reduction lengths, lead <= slots - 2
     U = ops.I8_RING_K_UNIT
     assert 0 < U <= 128 and 4096 % U == 0 and 14336 % U == 0
@@ -31,20 +26,11 @@ def test_header_declares_the_entry_point_and_the_ring_constants():
 
 
 def test_ctypes_table_holds_it_with_the_tiled_signature():
-    from quantool_amd.hip import _lib
-
-    assert _lib.SIGNATURES[NAME] == _lib.SIGNATURES["qt_gemm_i8"]
+    check_surface("ctypes", NAME, "qt_gemm_i8")
 
 
 def test_library_exports_it():
-    from quantool_amd.hip import _lib
-
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-
-        g.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
-    assert NAME in {line.split()[-1] for line in out.splitlines() if " T " in line}
+    check_surface("library", NAME)
 
 
 def test_no_workspace_function_was_added():
@@ -102,10 +88,7 @@ def test_supported_operands_and_alignment(monkeypatch):
     monkeypatch.setattr(ops, "load", lambda: (_ for _ in ()).throw(AssertionError("the library was touched")))
     U = ops.I8_RING_K_UNIT
     Wq, s_w = torch.zeros(8, 4 * U, dtype=torch.int8), torch.ones(8, 1)
-    buf = torch.zeros(4 * 4 * U + 32, dtype=torch.int8)
-    off = (-buf.data_ptr()) % 16
-    aligned = buf[off:off + 16 * U].view(4, 4 * U)
-    shifted = buf[off + 1:off + 1 + 16 * U].view(4, 4 * U)
+    aligned, shifted = aligned_i8(4, 4 * U), aligned_i8(4, 4 * U, shift=1)
     assert aligned.data_ptr() % 16 == 0 and Wq.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 1
     assert ops.gemm_i8_ring_supported(aligned, Wq, s_w) is True
     assert ops.gemm_i8_ring_supported(shifted, Wq, s_w) is False
@@ -115,50 +98,6 @@ def test_supported_operands_and_alignment(monkeypatch):
 
 
 # ---- dispatch -------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for quantool_amd.hip.ops: the three GEMMs of a Linear record (name, rows); quantize_tokens_i8 returns
-    tensors of the right shapes on the CPU."""
-
-    I8_SKINNY_MAX_M = 16
-
-    def __init__(self):
-        self.calls = []
-        self.supported = True
-        self.asked = 0
-
-    def quantize_tokens_i8(self, X, symmetric=True, col_perm=None):
-        M = X.shape[0]
-        zp = None if symmetric else torch.zeros(M, dtype=torch.int32)
-        return torch.zeros(X.shape, dtype=torch.int8), torch.ones(M), zp
-
-    def _gemm(self, name, Xq, Wq, out_dtype):
-        self.calls.append((name, Xq.shape[0]))
-        return torch.zeros(Xq.shape[0], Wq.shape[-2], dtype=out_dtype)
-
-    def gemm_i8(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_skinny(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_skinny", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_ring(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_ring", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_ring_supported(self, Xq, Wq, s_w):
-        self.asked += 1
-        return self.supported
-
-
-@pytest.fixture
-def fake_ops(monkeypatch):
-    import quantool_amd.hip as hip
-    from quantool_amd.hip import ops as real   # noqa: F401  (the attribute the modules import must exist first)
-
-    rec = _Recorder()
-    monkeypatch.setattr(hip, "ops", rec)
-    return rec
-
-
 def _linear(K=256, N=24, int4=False):
     from quantool_amd.engine.qmodules import QuantizedLinear
 

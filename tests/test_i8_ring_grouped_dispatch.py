@@ -3,21 +3,21 @@
 does not take before they touch the library, and ``QuantizedExperts`` picks the ring by ``ring_min_rows_per_expert``
 (with ``quantool_amd.hip.ops`` replaced by a recording fake, so nothing reaches a device)."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 import torch
 import torch.nn as nn
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.i8_fake_ops import Recorder, aligned_i8, check_surface, fake_ops, header_text  # noqa: F401
+
 NAME = "qt_gemm_i8_ring_grouped"
+WATCH = "gemm_i8_ring_grouped_supported"
 
 
 # ---- surface --------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_point():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "quantool_amd.h").read_text(), flags=re.S)
-    assert NAME in set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text))
+    check_surface("header", NAME)
+    text = header_text()[1]
     decl = re.search(NAME + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
     args = [a.strip() for a in decl.split(",")]
     assert args[-2:] == ["int64_t x_rows", "qt_stream_t stream"]
@@ -37,14 +37,7 @@ def test_ctypes_table_holds_the_grouped_signature_plus_one_int64():
 
 
 def test_library_exports_it():
-    from quantool_amd.hip import _lib
-
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-
-        g.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
-    assert NAME in {line.split()[-1] for line in out.splitlines() if " T " in line}
+    check_surface("library", NAME)
 
 
 def test_no_workspace_function_was_added():
@@ -135,10 +128,7 @@ def test_supported_operands_and_alignment(monkeypatch):
     monkeypatch.setattr(ops, "load", lambda: (_ for _ in ()).throw(AssertionError("the library was touched")))
     U = ops.I8_RING_K_UNIT
     Wq, s_w = torch.zeros(2, 8, 4 * U, dtype=torch.int8), torch.ones(2, 8, 1)
-    buf = torch.zeros(4 * 4 * U + 32, dtype=torch.int8)
-    off = (-buf.data_ptr()) % 16
-    aligned = buf[off:off + 16 * U].view(4, 4 * U)
-    shifted = buf[off + 1:off + 1 + 16 * U].view(4, 4 * U)
+    aligned, shifted = aligned_i8(4, 4 * U), aligned_i8(4, 4 * U, shift=1)
     assert aligned.data_ptr() % 16 == 0 and Wq.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 1
     assert ops.gemm_i8_ring_grouped_supported(aligned, Wq, s_w) is True
     assert ops.gemm_i8_ring_grouped_supported(aligned, Wq, s_w, torch.zeros(9, dtype=torch.int32)) is True
@@ -149,57 +139,6 @@ def test_supported_operands_and_alignment(monkeypatch):
 
 
 # ---- dispatch -------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for quantool_amd.hip.ops: the three grouped GEMMs record (name, rows); the passes around them return
-    tensors of the right shapes on the CPU."""
-
-    def __init__(self):
-        self.calls = []
-        self.supported = True
-        self.asked = []
-
-    def quantize_tokens_i8(self, X, symmetric=True, col_perm=None):
-        M = X.shape[0]
-        zp = None if symmetric else torch.zeros(M, dtype=torch.int32)
-        return torch.zeros(X.shape, dtype=torch.int8), torch.ones(M), zp
-
-    def _grouped(self, name, Xq, Wq, kw):
-        rows = kw["row_idx"].numel() if kw.get("row_idx") is not None else Xq.shape[0]
-        self.calls.append((name, rows))
-        return torch.zeros(rows, Wq.shape[-2], dtype=kw["out_dtype"])
-
-    def gemm_i8_grouped(self, Xq, s_x, Wq, s_w, offsets, **kw):
-        return self._grouped("gemm_i8_grouped", Xq, Wq, kw)
-
-    def gemm_i8_skinny_grouped(self, Xq, s_x, Wq, s_w, offsets, **kw):
-        return self._grouped("gemm_i8_skinny_grouped", Xq, Wq, kw)
-
-    def gemm_i8_ring_grouped(self, Xq, s_x, Wq, s_w, offsets, **kw):
-        return self._grouped("gemm_i8_ring_grouped", Xq, Wq, kw)
-
-    def gemm_i8_ring_grouped_supported(self, Xq, Wq, s_w, row_idx=None):
-        self.asked.append(None if row_idx is None else row_idx.numel())
-        return self.supported
-
-    def moe_route(self, top_k_index, num_experts):
-        R = top_k_index.numel()
-        z = torch.zeros(R, dtype=torch.int32)
-        return torch.zeros(num_experts + 1, dtype=torch.int32), z, z, z
-
-    def moe_combine(self, Y, row_of, top_k_weights):
-        return torch.zeros(top_k_weights.shape[0], Y.shape[1], dtype=Y.dtype)
-
-
-@pytest.fixture
-def fake_ops(monkeypatch):
-    import quantool_amd.hip as hip
-    from quantool_amd.hip import ops as real   # noqa: F401  (the attribute the modules import must exist first)
-
-    rec = _Recorder()
-    monkeypatch.setattr(hip, "ops", rec)
-    return rec
-
-
 E, TOPK = 4, 2
 
 
@@ -283,7 +222,7 @@ def test_a_ragged_k_falls_to_the_tiled_gemm(monkeypatch):
     from quantool_amd.engine.qmodules import QuantizedExperts
     from quantool_amd.hip import ops as real
 
-    rec = _Recorder()
+    rec = Recorder(WATCH)
     rec.gemm_i8_ring_grouped_supported = real.gemm_i8_ring_grouped_supported
     monkeypatch.setattr(real, "load", lambda: (_ for _ in ()).throw(AssertionError("the library was touched")))
     monkeypatch.setattr(hip, "ops", rec)

@@ -2,28 +2,23 @@
 ``qt_gemm_i8_ring_w4``, ``ops.gemm_i8_ring_w4_supported`` / ``ops.gemm_i8_ring_w4`` refuse what the kernel does not take
 before they touch the library, and ``QuantizedLinear`` picks it by ``ring_w4_min_m`` (with ``quantool_amd.hip.ops``
 replaced by a recording fake, so nothing reaches a device)."""
-import re
-import subprocess
-from pathlib import Path
-
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.i8_fake_ops import aligned_i8, aligned_i32, check_surface, fake_ops, header_constants  # noqa: F401
+
 NAME = "qt_gemm_i8_ring_w4"
+WATCH = "gemm_i8_ring_w4_supported"
 
 
 # ---- surface --------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_point_and_the_instance_constants():
     from quantool_amd.hip import ops
 
-    raw = (ROOT / "include" / "quantool_amd.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert NAME in set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text))
-    consts = dict(re.findall(r"#define\s+(QT_I8_RING_W4_[A-Z_]+)\s+(\d+)", text))
-    assert {k: int(v) for k, v in consts.items()} == {"QT_I8_RING_W4_K_UNIT": ops.I8_RING_W4_K_UNIT,
-                                                      "QT_I8_RING_W4_SLOTS": ops.I8_RING_W4_SLOTS,
-                                                      "QT_I8_RING_W4_LEAD": ops.I8_RING_W4_LEAD}
+    check_surface("header", NAME)
+    assert header_constants("QT_I8_RING_W4_") == {"QT_I8_RING_W4_K_UNIT": ops.I8_RING_W4_K_UNIT,
+                                                  "QT_I8_RING_W4_SLOTS": ops.I8_RING_W4_SLOTS,
+                                                  "QT_I8_RING_W4_LEAD": ops.I8_RING_W4_LEAD}
     # a K-tile is one weight group, and the ring's WAR argument needs lead <= slots - 2
     assert ops.I8_RING_W4_K_UNIT == 128
     assert 1 <= ops.I8_RING_W4_LEAD <= ops.I8_RING_W4_SLOTS - 2
@@ -31,20 +26,11 @@ def test_header_declares_the_entry_point_and_the_instance_constants():
 
 
 def test_ctypes_table_holds_it_with_the_tiled_signature():
-    from quantool_amd.hip import _lib
-
-    assert _lib.SIGNATURES[NAME] == _lib.SIGNATURES["qt_gemm_i8"]
+    check_surface("ctypes", NAME, "qt_gemm_i8")
 
 
 def test_library_exports_it():
-    from quantool_amd.hip import _lib
-
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-
-        g.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
-    assert NAME in {line.split()[-1] for line in out.splitlines() if " T " in line}
+    check_surface("library", NAME)
 
 
 def test_build_audits_cover_the_new_file():
@@ -98,13 +84,8 @@ def test_supported_operands_and_alignment(monkeypatch):
     U = ops.I8_RING_W4_K_UNIT
     K = 4 * U
     Wq, s_w = torch.zeros(8, K // 8, dtype=torch.int32), torch.ones(8, 4)
-    buf = torch.zeros(4 * K + 32, dtype=torch.int8)
-    off = (-buf.data_ptr()) % 16
-    aligned = buf[off:off + 4 * K].view(4, K)
-    shifted = buf[off + 1:off + 1 + 4 * K].view(4, K)
-    wbuf = torch.zeros(8 * K // 8 + 8, dtype=torch.int32)
-    woff = ((-wbuf.data_ptr()) % 16) // 4
-    w_shifted = wbuf[woff + 1:woff + 1 + 8 * K // 8].view(8, K // 8)
+    aligned, shifted = aligned_i8(4, K), aligned_i8(4, K, shift=1)
+    w_shifted = aligned_i32(8, K // 8, shift=1)
     assert aligned.data_ptr() % 16 == 0 and Wq.data_ptr() % 16 == 0
     assert shifted.data_ptr() % 16 == 1 and w_shifted.data_ptr() % 16 == 4
     assert ops.gemm_i8_ring_w4_supported(aligned, Wq, s_w) is True
@@ -118,53 +99,6 @@ def test_supported_operands_and_alignment(monkeypatch):
 
 
 # ---- dispatch -------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for quantool_amd.hip.ops: the GEMMs of a Linear record (name, rows); quantize_tokens_i8 returns tensors
-    of the right shapes on the CPU."""
-
-    I8_SKINNY_MAX_M = 16
-    I8_MID_MAX_M = 128
-
-    def __init__(self):
-        self.calls = []
-        self.supported = True      # gemm_i8_ring_w4_supported's answer
-        self.asked = 0             # ... and how often it was asked
-        for name in ("gemm_i8", "gemm_i8_skinny", "gemm_i8_mid", "gemm_i8_ring", "gemm_i8_ring_w4"):
-            setattr(self, name, self._gemm(name))
-
-    def quantize_tokens_i8(self, X, symmetric=True, col_perm=None):
-        M = X.shape[0]
-        zp = None if symmetric else torch.zeros(M, dtype=torch.int32)
-        return torch.zeros(X.shape, dtype=torch.int8), torch.ones(M), zp
-
-    def _gemm(self, name):
-        def gemm(Xq, s_x, Wq, s_w, **kw):
-            self.calls.append((name, Xq.shape[0]))
-            return torch.zeros(Xq.shape[0], Wq.shape[-2], dtype=kw["out_dtype"])
-
-        return gemm
-
-    def gemm_i8_ring_supported(self, Xq, Wq, s_w):
-        return True
-
-    def gemm_i8_mid_supported(self, Xq, Wq, s_w):
-        return True
-
-    def gemm_i8_ring_w4_supported(self, Xq, Wq, s_w):
-        self.asked += 1
-        return self.supported
-
-
-@pytest.fixture
-def fake_ops(monkeypatch):
-    import quantool_amd.hip as hip
-    from quantool_amd.hip import ops as real   # noqa: F401  (the attribute the modules import must exist first)
-
-    rec = _Recorder()
-    monkeypatch.setattr(hip, "ops", rec)
-    return rec
-
-
 def _linear(K=512, N=24, int4=True, G=None):
     from quantool_amd.engine.qmodules import QuantizedLinear
 

@@ -2,23 +2,18 @@
 points, ``ops.gemm_i8_skinny`` refuses M outside 1..16 before it touches the library, and ``QuantizedLinear`` /
 ``QuantizedExperts`` pick the decode form by the row / token count (with ``quantool_amd.hip.ops`` replaced by recording
 fakes, so nothing reaches a device)."""
-import re
-import subprocess
-from pathlib import Path
-
 import pytest
 import torch
 import torch.nn as nn
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.i8_fake_ops import check_surface, fake_ops  # noqa: F401
+
 NAMES = ("qt_gemm_i8_skinny", "qt_gemm_i8_skinny_grouped")
 
 
 def test_header_declares_both_entry_points():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "quantool_amd.h").read_text(), flags=re.S)
-    declared = set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text))
     for n in NAMES:
-        assert n in declared
+        check_surface("header", n)
 
 
 def test_ctypes_table_holds_both_with_the_tiled_signatures():
@@ -29,23 +24,15 @@ def test_ctypes_table_holds_both_with_the_tiled_signatures():
     for n in NAMES:
         assert n in _lib.SIGNATURES
     # the grouped form takes qt_gemm_i8_grouped's arguments; the GEMV qt_gemm_i8's, with M an int
-    assert _lib.SIGNATURES["qt_gemm_i8_skinny_grouped"] == _lib.SIGNATURES["qt_gemm_i8_grouped"]
+    check_surface("ctypes", "qt_gemm_i8_skinny_grouped", "qt_gemm_i8_grouped")
     tiled, skinny = _lib.SIGNATURES["qt_gemm_i8"], _lib.SIGNATURES["qt_gemm_i8_skinny"]
     assert tiled[1][1] is c_int64 and skinny[1][1] is c_int
     assert skinny[0] is tiled[0] and skinny[1][:1] + skinny[1][2:] == tiled[1][:1] + tiled[1][2:]
 
 
 def test_library_exports_both():
-    from quantool_amd.hip import _lib
-
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-
-        g.build()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     for n in NAMES:
-        assert n in exported
+        check_surface("library", n)
 
 
 def test_no_workspace_function_was_added():
@@ -69,61 +56,6 @@ def test_ops_refuses_m_out_of_range_before_the_library(monkeypatch, M):
 
 
 # ---- dispatch -------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for quantool_amd.hip.ops: the four GEMMs record (name, rows); the passes around them return tensors of
-    the right shapes on the CPU."""
-
-    I8_SKINNY_MAX_M = 16
-
-    def __init__(self, top_k=2):
-        self.calls = []
-        self.top_k = top_k
-
-    def quantize_tokens_i8(self, X, symmetric=True, col_perm=None):
-        M = X.shape[0]
-        zp = None if symmetric else torch.zeros(M, dtype=torch.int32)
-        return torch.zeros(X.shape, dtype=torch.int8), torch.ones(M), zp
-
-    def _gemm(self, name, Xq, Wq, out_dtype):
-        self.calls.append((name, Xq.shape[0]))
-        return torch.zeros(Xq.shape[0], Wq.shape[-2], dtype=out_dtype)
-
-    def gemm_i8(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8", Xq, Wq, kw["out_dtype"])
-
-    def gemm_i8_skinny(self, Xq, s_x, Wq, s_w, **kw):
-        return self._gemm("gemm_i8_skinny", Xq, Wq, kw["out_dtype"])
-
-    def _grouped(self, name, Xq, Wq, kw):
-        rows = kw["row_idx"].numel() if kw.get("row_idx") is not None else Xq.shape[0]
-        self.calls.append((name, rows))
-        return torch.zeros(rows, Wq.shape[-2], dtype=kw["out_dtype"])
-
-    def gemm_i8_grouped(self, Xq, s_x, Wq, s_w, offsets, **kw):
-        return self._grouped("gemm_i8_grouped", Xq, Wq, kw)
-
-    def gemm_i8_skinny_grouped(self, Xq, s_x, Wq, s_w, offsets, **kw):
-        return self._grouped("gemm_i8_skinny_grouped", Xq, Wq, kw)
-
-    def moe_route(self, top_k_index, num_experts):
-        R = top_k_index.numel()
-        z = torch.zeros(R, dtype=torch.int32)
-        return torch.zeros(num_experts + 1, dtype=torch.int32), z, z, z
-
-    def moe_combine(self, Y, row_of, top_k_weights):
-        return torch.zeros(top_k_weights.shape[0], Y.shape[1], dtype=Y.dtype)
-
-
-@pytest.fixture
-def fake_ops(monkeypatch):
-    import quantool_amd.hip as hip
-    from quantool_amd.hip import ops as real   # noqa: F401  (the attribute the modules import must exist first)
-
-    rec = _Recorder()
-    monkeypatch.setattr(hip, "ops", rec)
-    return rec
-
-
 def _linear(K=256, N=24, int4=False):
     from quantool_amd.engine.qmodules import QuantizedLinear
 
