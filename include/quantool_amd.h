@@ -497,6 +497,30 @@ int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64_t ldx, con
                       const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
                       int64_t ldy, qt_stream_t stream);
 
+/* qt_gemm_wq_stream: qt_gemm_wq_skinny for a few tiles of rows, 1 <= M <= QT_WQ_STREAM_MAX_M (batched decode,
+ *   speculative verification, short prompts).  The arguments and the weight definition are
+ *   qt_gemm_wq_skinny's.  Taken: QT_W_INT4_PACKED and QT_W_INT8, G = 1 and G = K / 128, with and without zp_w and bias,
+ *   bf16 and fp16, any N >= 1, ldy >= N, K <= ldx <= QT_WQ_STREAM_MAX_LDX, K a multiple of QT_WQ_STREAM_K_UNIT, and X,
+ *   Wq and ldx * 2 multiples of 16 bytes (the skinny kernel's 16-byte path).  Everything else -- g_idx != NULL (actorder group runs on
+ *   qt_dequantize_weight + a dense GEMM), a ragged K, M = 0 or M > QT_WQ_STREAM_MAX_M, a misaligned operand or pitch, a
+ *   null pointer, a G that is neither 1 nor K / 128, a dtype that is not 16-bit -- returns QT_ERR_INVALID before any
+ *   launch, and qt_last_error names the reason.
+ *   Row m of Y is bit-identical to qt_gemm_wq_skinny applied to row m alone (equivalently: to row m of the skinny kernel
+ *   on any slice of at most 16 rows that holds it).  A workgroup owns 16 columns n and all M rows; wave w accumulates
+ *   the k-blocks kb = w, w + 4, ... in ascending order on the same MFMA, with column 128 kb + 32 kq + 8 s + j at the
+ *   same (step s, lane quarter kq, element j), one fp32 accumulator per tile of 16 rows; then ((c0 + c1) + c2) + c3,
+ *   the bias, one rounding.  The weight fragment is formed by the skinny kernel's statements, once per k-block, and used
+ *   for every tile of rows; a row of the MFMA's output reads its own activation row only, so a row's result depends
+ *   neither on M nor on the other rows.  qt_gemm_wq_skinny's error bound and exact-input guarantee carry over.
+ *   Deterministic, no atomics, no workspace.  Every weight byte is read from memory once per launch.  No byte outside
+ *   X [M, K] (pitch ldx), Wq, s_w / zp_w [N, G] and bias [N] is read; nothing outside Y[m < M, n < N] is written. */
+int qt_gemm_wq_stream(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format, int N,
+                      const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
+                      int64_t ldy, qt_stream_t stream);
+#define QT_WQ_STREAM_MAX_M 128
+#define QT_WQ_STREAM_K_UNIT 128
+#define QT_WQ_STREAM_MAX_LDX 33554432 /* 2^25 elements: a tile of 16 rows is addressed by 32-bit byte offsets */
+
 /* qt_gemm_wq_grouped: qt_gemm_wq_skinny over E weight matrices at once, for routed-expert banks (engine/qlinear.py
  *   WeightOnlyExperts).  Y [R, N] in x_dtype (pitch ldy): expert e owns output rows
  *   [offsets[e], offsets[e + 1]) (offsets int32 [E + 1], on the device, ascending, offsets[E] <= R; rows past

@@ -9,6 +9,9 @@
 //                        once), dequantises it and feeds v_mfma_f32_16x16x32_{bf16,f16} with M padded to 16 (the
 //                        activations are the B operand).  Four k-blocks are in flight per wave before the first MFMA.
 //                        The 4 waves' fp32 partials are summed through LDS in wave order: no atomics.
+// qt_gemm_wq_stream      the skinny tile over up to 8 m-tiles of 16 rows (M <= 128): a k-block's weight
+//                        chunk is loaded and dequantised once and multiplied with every live m-tile; each m-tile's
+//                        accumulator runs the skinny kernel's chain, so every row equals the skinny kernel's to the bit.
 // qt_gemm_wq_grouped     the same kernel over E weight matrices (MOE = true): grid (column tiles, slots), one slot per
 //                        16-row tile of one expert's rows.  The slot count floor(R/16) + min(E, R) bounds the tiles of
 //                        any routing without reading the counts; a workgroup finds its (expert, tile) by walking
@@ -347,6 +350,168 @@ __global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs args
     }
 }
 
+// ---- qt_gemm_wq_stream ----------------------------------------------------------------------------------------------
+// The skinny tile over MT m-tiles of 16 activation rows (17 <= M <= 128 is what it is for; 1 <= M is taken): the same
+// workgroup shape, the same k-block -> wave map and the same statements for the weight chunk, the group parameters and
+// the A fragment, so accumulator t of wave w runs the chain the skinny kernel's wave w runs on rows [16 t, 16 t + 16).
+// The A fragments of a k-block are formed once and kept for every m-tile.  The B fragments (activation rows) come from
+// L2 in fragment shape, WQ_XB - 1 (k-block, m-tile) steps ahead of the MFMAs that use them.
+// One instance per tile count MT = ceil(M / 16), and a wave takes its k-blocks in batches of WQ_SB (then 4, 2, 1 for the
+// rest), so nothing in a batch is conditional: no dead k-block, no dead m-tile.  (The skinny kernel pads its last batch
+// with all-zero products instead, which leave a sum that started at +0 unchanged; the batch length is no part of the
+// summation order.)  Instances for 2 / 4 / 8 tiles with uniform branches around the dead tiles' loads and MFMAs were
+// tried first: every branch made the compiler merge the whole accumulator array, and the 8-tile instance needed 256
+// VGPRs and 200 AGPRs of copies.
+constexpr int WQ_XB = 4;        // activation fragment sets resident per wave: the one in use and WQ_XB - 1 in flight
+
+template <int V>
+struct WqInt {
+    static constexpr int value = V;
+};
+
+template <bool INT4, int DT, bool ZP, int MT>
+__global__ void __launch_bounds__(WQ_THREADS) wq_stream_kernel(const WqArgs p) {
+    __shared__ f32x4 red[WQ_WAVES - 1][MT][64];
+    // k-blocks in flight per wave: 32 VGPRs of weight chunks in either format
+    constexpr int WQ_SB = INT4 ? 2 * WQ_UNROLL : WQ_UNROLL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // in an SGPR: the k-block offsets are scalar
+    const int r = lane & 15;            // A row (weight row n0 + r) and B column (activation row 16 t + r)
+    const int kq = lane >> 4;           // which 32 columns of the k-block
+    const int64_t n0 = (int64_t)blockIdx.x * 16;
+    const int64_t n = n0 + r;
+    const bool n_ok = n < p.N;
+    const int64_t nrow = n_ok ? n : 0;
+    const int nfull = p.K / WQ_KB;      // K is a multiple of WQ_KB
+    const float off = INT4 ? 8.0f : 128.0f;
+    constexpr int WV = INT4 ? 1 : 2;    // 16-byte weight chunks per lane per k-block
+    // Activations come through buffer loads: m-tile t's descriptor starts at row 16 t and ends with the last column of
+    // row min(M, 16 t + 16) - 1, so a lane whose row is >= M is out of range (ldx >= K): it gets zeros and no memory
+    // access is made for it.  The host bounds ldx, so the byte offsets fit 32 bits.
+    const int xoff = (int)(((int64_t)r * p.ldx + 32 * kq) * 2);
+
+    f32x4 acc[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+    // UC k-blocks kb, kb + 4, ... of this wave: every weight load issued before the first MFMA
+    auto batch = [&](const int kb, auto uc) {
+        constexpr int UC = decltype(uc)::value;
+        constexpr int STEPS = UC * MT;
+        uint4 wv[UC][WV];
+        u32x4 xv[WQ_XB][4];
+        float sc[UC], cz[UC];
+        // step i = (k-block u = i / MT, m-tile t = i % MT): its four 16-byte activation loads
+        auto load_x = [&](int i, u32x4 (&dst)[4]) {
+            const int u = i / MT, t = i % MT;
+            const int rows = min(p.M - 16 * t, 16);
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(p.X + (int64_t)(16 * t) * p.ldx), 0, (int)(((int64_t)(rows - 1) * p.ldx + p.K) * 2), 0x00020000);
+            const int soff = (kb + u * WQ_WAVES) * (WQ_KB * 2);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                dst[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xoff + 16 * s, soff, 0));
+        };
+#pragma unroll
+        for (int i = 0; i < WQ_XB - 1 && i < STEPS; ++i) load_x(i, xv[i]);
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+            const int c0 = (kb + u * WQ_WAVES) * WQ_KB + 32 * kq;
+            if constexpr (INT4) {
+                const uint4* src = (const uint4*)((const int32_t*)p.Wq + nrow * p.Kw + c0 / 8);
+                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x88888888u, 0x88888888u, 0x88888888u,
+                                                                                 0x88888888u);
+            } else {
+                const uint4* src = (const uint4*)((const int8_t*)p.Wq + nrow * p.K + c0);
+                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x80808080u, 0x80808080u, 0x80808080u,
+                                                                                 0x80808080u);
+                wv[u][1] = n_ok ? ld_nt16(src + 1)
+                                : make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+            }
+            float sv = 0.0f, czv = off;
+            if (n_ok) group_params<INT4, ZP, false>(p, nrow, c0, sv, czv);
+            sc[u] = sv;
+            cz[u] = czv;
+        }
+#pragma unroll
+        for (int u = 0; u < UC; ++u) {
+            const float s = sc[u];
+            const float noff = -(off * s);
+            const unsigned wd[8] = {wv[u][0].x, wv[u][0].y, wv[u][0].z, wv[u][0].w, wv[u][WV - 1].x,
+                                    wv[u][WV - 1].y, wv[u][WV - 1].z, wv[u][WV - 1].w};
+            u32x4 a[4];
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                float uu[8];
+                if constexpr (INT4) u_int4(wd[s4], uu);
+                else u_int8(wd[2 * s4], wd[2 * s4 + 1], uu);
+                a[s4] = frag_from_u<DT, ZP>(uu, s, cz[u], noff);
+            }
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                const int i = u * MT + t;
+                if (i + WQ_XB - 1 < STEPS) load_x(i + WQ_XB - 1, xv[(i + WQ_XB - 1) % WQ_XB]);
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) acc[t] = mfma16<DT>(a[s4], xv[i % WQ_XB][s4], acc[t]);
+            }
+        }
+    };
+    int kb = wave;
+    int left = nfull > wave ? (nfull - wave + WQ_WAVES - 1) / WQ_WAVES : 0;   // this wave's k-blocks: kb, kb + 4, ...
+    for (; left >= WQ_SB; left -= WQ_SB, kb += WQ_SB * WQ_WAVES) batch(kb, WqInt<WQ_SB>{});
+    if constexpr (WQ_SB > 4) {
+        if (left & 4) {
+            batch(kb, WqInt<4>{});
+            kb += 4 * WQ_WAVES;
+        }
+    }
+    if (left & 2) {
+        batch(kb, WqInt<2>{});
+        kb += 2 * WQ_WAVES;
+    }
+    if (left & 1) batch(kb, WqInt<1>{});
+
+    // as the skinny kernel, per m-tile: y = ((w0 + w1) + w2) + w3 (+ bias), one rounding
+    if (wave > 0) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) red[wave - 1][t][lane] = acc[t];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            const int64_t m = 16 * t + r;
+            f32x4 y4 = acc[t];
+#pragma unroll
+            for (int w = 0; w < WQ_WAVES - 1; ++w) {
+                const f32x4 o = red[w][t][lane];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) y4[i] = y4[i] + o[i];
+            }
+            if (m >= p.M) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t nn = n0 + 4 * kq + i;
+                if (nn >= p.N) continue;
+                float y = y4[i];
+                if (p.bias) y = y + h2f<DT>(p.bias[nn]);
+                p.Y[m * p.ldy + nn] = (unsigned short)(pack2<DT>(y, 0.0f) & 0xffffu);
+            }
+        }
+    }
+}
+
+template <bool I4, int D, bool Z>
+void launch_stream(int mtiles, dim3 grid, hipStream_t stream, const WqArgs& a) {
+#define QT_WQ_STREAM_MT(T) \
+    case T: hipLaunchKernelGGL((wq_stream_kernel<I4, D, Z, T>), grid, dim3(WQ_THREADS), 0, stream, a); break;
+    switch (mtiles) {
+        QT_WQ_STREAM_MT(1) QT_WQ_STREAM_MT(2) QT_WQ_STREAM_MT(3) QT_WQ_STREAM_MT(4) QT_WQ_STREAM_MT(5)
+        QT_WQ_STREAM_MT(6) QT_WQ_STREAM_MT(7) QT_WQ_STREAM_MT(8)
+    }
+#undef QT_WQ_STREAM_MT
+}
+
 template <template <bool, int, bool, bool> class L, typename... A>
 void dispatch(bool int4, int dtype, bool zp, bool gidx, A&&... a) {
 #define QT_WQ_CASE(I4, D, Z, GI) \
@@ -421,6 +586,43 @@ extern "C" int qt_gemm_wq_skinny(const void* X, int x_dtype, int M, int K, int64
              (const unsigned short*)bias, (unsigned short*)Y, ldy, (int)vec, nullptr, nullptr, 0};
     dispatch<LaunchSkinny>(int4, x_dtype, zp_w != nullptr, g_idx != nullptr, dim3((unsigned)((N + 15) / 16)), stream,
                            a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_gemm_wq_stream(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format,
+                                 int N, const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx,
+                                 const void* bias, void* Y, int64_t ldy, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(X && Wq && s_w && Y, "qt_gemm_wq_stream: null pointer (X, Wq, s_w and Y are required)");
+    QT_CHECK_ARG(g_idx == nullptr,
+                 "qt_gemm_wq_stream: g_idx is not taken (actorder group runs on qt_dequantize_weight + a dense GEMM)");
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "qt_gemm_wq_stream: x_dtype %d must be bf16 or fp16", x_dtype);
+    QT_CHECK_ARG(w_format == QT_W_INT8 || w_format == QT_W_INT4_PACKED, "qt_gemm_wq_stream: w_format %d unsupported",
+                 w_format);
+    QT_CHECK_ARG(M >= 1 && M <= QT_WQ_STREAM_MAX_M, "qt_gemm_wq_stream: 1 <= M <= %d rows only, got M = %d",
+                 QT_WQ_STREAM_MAX_M, M);
+    QT_CHECK_ARG(N >= 1 && K >= 1, "qt_gemm_wq_stream: empty weight (N = %d, K = %d)", N, K);
+    QT_CHECK_ARG(K % QT_WQ_STREAM_K_UNIT == 0, "qt_gemm_wq_stream: K = %d is not a multiple of the k-unit %d", K,
+                 QT_WQ_STREAM_K_UNIT);
+    QT_CHECK_ARG(G == 1 || G == K / QT_WQ_STREAM_K_UNIT, "qt_gemm_wq_stream: G must be 1 or K / %d = %d, got %d",
+                 QT_WQ_STREAM_K_UNIT, K / QT_WQ_STREAM_K_UNIT, G);
+    QT_CHECK_ARG(ldx >= K && ldy >= N && ldx <= QT_WQ_STREAM_MAX_LDX,
+                 "qt_gemm_wq_stream: bad pitch (ldx >= K, ldy >= N, ldx <= %d)", QT_WQ_STREAM_MAX_LDX);
+    QT_CHECK_ARG((((uintptr_t)X | (uintptr_t)Wq) & 15) == 0 && ldx % 8 == 0,
+                 "qt_gemm_wq_stream: X, Wq and the row pitch of X must be 16-byte aligned");
+    const bool int4 = w_format == QT_W_INT4_PACKED;
+    WqArgs a{(const unsigned short*)X, ldx, M, Wq, N, K, K / 8, s_w, G, zp_w, nullptr,
+             (const unsigned short*)bias, (unsigned short*)Y, ldy, 1, nullptr, nullptr, 0};
+    const dim3 grid((unsigned)(((int64_t)N + 15) / 16));
+    const int mtiles = (M + 15) / 16;
+#define QT_WQ_STREAM_CASE(I4, D, Z) \
+    if (int4 == I4 && x_dtype == D && (zp_w != nullptr) == Z) launch_stream<I4, D, Z>(mtiles, grid, stream, a);
+    QT_WQ_STREAM_CASE(true, QT_BF16, false) QT_WQ_STREAM_CASE(true, QT_BF16, true)
+    QT_WQ_STREAM_CASE(true, QT_F16, false) QT_WQ_STREAM_CASE(true, QT_F16, true)
+    QT_WQ_STREAM_CASE(false, QT_BF16, false) QT_WQ_STREAM_CASE(false, QT_BF16, true)
+    QT_WQ_STREAM_CASE(false, QT_F16, false) QT_WQ_STREAM_CASE(false, QT_F16, true)
+#undef QT_WQ_STREAM_CASE
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

@@ -13,7 +13,8 @@ Linear either
   fp32 from the STORED scale and rounded once to the model dtype (the default, ``a16="dequantized"``); or
 * with ``a16="packed"``, a ``WeightOnlyLinear`` that keeps the stored integer weights on the device: decode-sized inputs
   (M <= ``skinny_max_m`` rows) run the GEMV ``qt_gemm_wq_skinny``, larger ones dequantise the weight into a transient
-  buffer (``qt_dequantize_weight``, bit-identical to the dequantised ``nn.Linear``) and call ``F.linear``.
+  buffer (``qt_dequantize_weight``, bit-identical to the dequantised ``nn.Linear``) and call ``F.linear``; with
+  ``a16_stream_rows`` inputs of 17 to that many rows run the weight-streaming ``qt_gemm_wq_stream`` instead.
 
 Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up_proj [E, 2I, H]`` / ``down_proj
 [E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
@@ -264,7 +265,7 @@ A16_MODES = ("dequantized", "packed")
 
 
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
-                   a16_experts: str = "dequantized") -> nn.Module:
+                   a16_experts: str = "dequantized", a16_stream_rows: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -272,6 +273,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     into the fused bank unless ``a16_experts="packed"`` (which needs ``a16="packed"``) replaces each with a
     ``WeightOnlyExperts``; ``model._qt_checkpoint`` then records ``"a16": "packed"``, the banks left dense under
     ``"dense_expert_banks"`` and, with ``a16_experts="packed"``, the packed ones under ``"packed_expert_banks"``.
+    ``a16_stream_rows`` (0, the default, or 17 ... 128; needs ``a16="packed"``) sets ``stream_max_m`` on every
+    ``WeightOnlyLinear`` built, so inputs of 17 to that many rows run ``qt_gemm_wq_stream`` on the stored weights
+    instead of dequantise + ``F.linear`` (``WeightOnlyExperts`` are not touched); it is recorded under
+    ``"a16_stream_rows"``.  A8 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -292,6 +297,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if a16_experts == "packed" and a16 != "packed":
         raise ValueError("a16_experts='packed' needs a16='packed' (packed expert banks beside dequantised Linears "
                          "is not a mode this loader offers)")
+    if type(a16_stream_rows) is not int or not (a16_stream_rows == 0 or 17 <= a16_stream_rows <= 128):
+        raise ValueError(f"a16_stream_rows={a16_stream_rows!r}: expected 0 or 17 ... 128")
+    if a16_stream_rows and a16 != "packed":
+        raise ValueError("a16_stream_rows needs a16='packed' (dequantised Linears have no stored weights to stream)")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -347,6 +356,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             new = (quantized_linear_from_tensors(name, t, act_symmetric, bias=bias) if a8
                    else weight_only_linear_from_tensors(name, t, bias=bias))
             _check_shape(f"{path}: {name}", (new.out_features, new.in_features), lin.weight.shape)
+            if not a8 and a16_stream_rows:
+                new.stream_max_m = a16_stream_rows
             _set_submodule(model, name, new)
         else:
             W = dequantized_weight(name, t, mdtype)
@@ -358,6 +369,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
+        model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))
         if packed_experts:
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)

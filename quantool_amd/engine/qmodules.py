@@ -117,6 +117,11 @@ class WeightOnlyLinear(nn.Module):
     output equals that ``nn.Linear``'s to the bit.  On CPU tensors ``forward`` is ``F.linear`` on
     ``stored.dequantize``.
 
+    Opt-in: with ``stream_max_m`` > 0, ``skinny_max_m`` < M <= ``stream_max_m`` runs ``qt_gemm_wq_stream`` (the weights
+    read once as well; every row bit-identical to the skinny kernel's, not to ``F.linear``'s) on a Linear with
+    ``in_features`` >= ``stream_min_k`` and, when ``stream_max_n`` is not 0, ``out_features`` <= ``stream_max_n``, where
+    ``ops.gemm_wq_stream_supported`` holds (no ``g_idx``, K a multiple of 128, aligned rows).
+
     Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
     ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
     (optional, model dtype).  Columns stay in their original order."""
@@ -124,6 +129,14 @@ class WeightOnlyLinear(nn.Module):
     # Decode GEMV up to this many rows, dequantise + F.linear above: at 16 rows the GEMV is still faster than the
     # dequantise + F.linear pair on every measured Llama-3-8B shape.
     skinny_max_m = 16
+    # Weight-streaming GEMM up to this many rows.  0, the default: never -- a fused kernel cannot equal F.linear's
+    # summation order, so it is the caller's choice (``load_quantized(..., a16_stream_rows=)``; the measurements support
+    # 32: from 48 rows on the first Llama-3-8B shapes lose to dequantise + F.linear).  Used only when
+    # it is not 0: up to this many output features (0: no bound) and from this many input features, the largest N and
+    # the smallest K measured, at both of which the kernel wins at 17 and 32 rows in both runs and all three schemes.
+    stream_max_m = 0
+    stream_max_n = 28672
+    stream_min_k = 512
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
@@ -158,7 +171,7 @@ class WeightOnlyLinear(nn.Module):
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
-                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}")
+                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         bias = None if self.bias is None else self.bias.to(x.dtype)
@@ -167,9 +180,17 @@ class WeightOnlyLinear(nn.Module):
             return F.linear(x, w.dequantize(x.dtype), bias)
         from ..hip import ops
 
-        if 1 <= x.numel() // w.K <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
+        M = x.numel() // w.K
+        if 1 <= M <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
             y = ops.gemm_wq_skinny(_rows(x, w.K), w.levels, w.scale, zp_w=w.zero_point, g_idx=w.g_idx, bias=bias)
             return y.reshape(*x.shape[:-1], w.N)
+        if (self.stream_max_m > 0 and self.skinny_max_m < M <= self.stream_max_m and w.K >= self.stream_min_k
+                and (self.stream_max_n == 0 or w.N <= self.stream_max_n) and M <= ops.WQ_STREAM_MAX_M):
+            # the attributes and the sizes decide first: ops' stream names are read only past them
+            x2 = _rows(x, w.K)
+            if ops.gemm_wq_stream_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
+                y = ops.gemm_wq_stream(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
+                return y.reshape(*x.shape[:-1], w.N)
         W = ops.dequantize_weight(w.levels, w.scale, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx, dtype=x.dtype)
         return F.linear(x, W, bias)
 

@@ -121,6 +121,8 @@ SIGNATURES = {
                                      c_int, c_int64, c_void_p]),
     "qt_gemm_wq_skinny": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "qt_gemm_wq_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_gemm_wq_grouped": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }

@@ -944,6 +944,73 @@ def gemm_wq_skinny(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w
     return Y
 
 
+WQ_STREAM_MAX_M = 128    # rows of X qt_gemm_wq_stream takes (QT_WQ_STREAM_MAX_M)
+WQ_STREAM_K_UNIT = 128   # columns per k-block of qt_gemm_wq_stream: K must be a multiple (QT_WQ_STREAM_K_UNIT)
+WQ_STREAM_MAX_LDX = 1 << 25   # largest row pitch of X in elements (QT_WQ_STREAM_MAX_LDX)
+
+
+def _wq_stream_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                       g_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_gemm_wq_stream`` would refuse these operands whatever the number of rows, or None.  Host-only: touches
+    no library, and reads shapes, dtypes, strides and addresses alone, so CPU tensors are judged like device ones."""
+    U = WQ_STREAM_K_UNIT
+    if g_idx is not None:
+        return "g_idx is not taken (actorder group runs on qt_dequantize_weight + a dense GEMM)"
+    if X.dtype not in (torch.bfloat16, torch.float16):
+        return f"X must be bf16 or fp16, got {X.dtype}"
+    if X.dim() != 2 or X.stride(1) != 1:
+        return f"X must be 2-d with unit column stride, got shape {tuple(X.shape)} strides {X.stride()}"
+    if Wq.dtype not in (torch.int8, torch.int32):
+        return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
+    K = X.shape[1]
+    if K == 0 or K % U != 0:
+        return f"K={K} is not a multiple of the k-unit {U}"
+    G = s_w.shape[-1] if s_w.dim() == 2 else -1
+    if G not in (1, K // U):
+        return f"G must be 1 or K / {U} = {K // U}, got s_w {tuple(s_w.shape)}"
+    if X.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0 or (X.stride(0) * 2) % 16 != 0:
+        return "X, Wq and the row pitch of X must be 16-byte aligned"
+    if X.stride(0) > WQ_STREAM_MAX_LDX:
+        return f"the row pitch of X, {X.stride(0)} elements, is above {WQ_STREAM_MAX_LDX}"
+    return None
+
+
+def gemm_wq_stream_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                             zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_wq_stream`` takes these operands at 1 to ``WQ_STREAM_MAX_M`` rows: no ``g_idx``, 16-bit X with unit
+    column stride, K a multiple of ``WQ_STREAM_K_UNIT``, G = 1 or K/128, X, Wq and X's row pitch 16-byte aligned.
+    Host-only."""
+    return _wq_stream_refusal(X, Wq, s_w, zp_w, g_idx) is None
+
+
+def gemm_wq_stream(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w: Optional[torch.Tensor] = None,
+                   g_idx: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_wq_skinny`` for 1 <= M <= ``WQ_STREAM_MAX_M`` rows (``qt_gemm_wq_stream``): batched decode, speculative
+    verification, short prompts.  Same arguments; every row of Y equals ``gemm_wq_skinny`` of that row to the bit.
+    ``ValueError`` where ``gemm_wq_stream_supported`` is false or M is out of range, before the library is touched."""
+    M = X.shape[0] if X.dim() == 2 else -1
+    why = _wq_stream_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is None and not 1 <= M <= WQ_STREAM_MAX_M:
+        why = f"1 <= M <= {WQ_STREAM_MAX_M} rows only, got X {tuple(X.shape)}"
+    if why is not None:
+        raise ValueError(f"gemm_wq_stream: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    if bias is not None:
+        _req(bias, X.dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+    Y = torch.empty((M, N), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_stream", lib.qt_gemm_wq_stream(
+        X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx),
+        _ptr(bias), Y.data_ptr(), Y.stride(0), _stream()))
+    return Y
+
+
 def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
                     row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
                     zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -14,6 +14,10 @@ agree between the modes (and the first position where they differ).
 ``--model mixtral``: a Mixtral-8x7B-shaped model instead (8 experts, top-2, H = 4096, I = 14336; ``--layers 8`` keeps
 the write and the three loads short).  Every expert's gate / up / down and the attention Linears are quantised the same
 way and written per expert through ``expert_bank_checkpoint_names`` (``block_sparse_moe.experts.{e}.w1 / w3 / w2``).
+``--scheme W4A16 --batch B --modes packed,packed_stream`` compares the packed runtime with and without
+``a16_stream_rows=128`` (B rows per decode-step GEMM: ``qt_gemm_wq_stream`` against dequantise + ``F.linear``), each mode
+decoded twice.
+
 Modes ``dequantized``, ``packed`` (``a16="packed"``: the banks stay dense bf16) and ``packed_experts`` (``a16="packed",
 a16_experts="packed"``: ``WeightOnlyExperts``); each mode also reports the resident bytes of the expert banks.
 
@@ -241,6 +245,8 @@ def main():
         torch.cuda.empty_cache()
         if mode == "packed_experts":
             model = load_quantized(path, device=dev, a16="packed", a16_experts="packed")
+        elif mode == "packed_stream":                            # 17 - 128 rows on qt_gemm_wq_stream
+            model = load_quantized(path, device=dev, a16="packed", a16_stream_rows=128)
         else:
             model = load_quantized(path, device=dev, a16=mode)
         lin_bytes = bank_bytes = 0
@@ -256,15 +262,26 @@ def main():
         decode(model, prompt[:, :8], 4)                          # warm-up: kernels, allocator
         torch.cuda.reset_peak_memory_stats()
         toks, per_tok = decode(model, prompt, args.new)
+        steps = [round(per_tok * 1e3, 3)]
+        if "packed_stream" in modes:                             # each mode twice: the second pass is the spread
+            toks2, per_tok2 = decode(model, prompt, args.new)
+            assert toks2 == toks, f"{mode}: two runs gave different tokens"
+            steps.append(round(per_tok2 * 1e3, 3))
         result["modes"][mode] = {
-            "ms_per_token": round(per_tok * 1e3, 3), "decoder_linear_bytes": lin_bytes,
+            "ms_per_token": round(per_tok * 1e3, 3), "ms_per_step": steps, "decoder_linear_bytes": lin_bytes,
             "expert_bank_bytes": bank_bytes,
             "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
             "memory_allocated_after_load": resident, "max_memory_allocated_decode": torch.cuda.max_memory_allocated(),
             "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules())}
         tokens[mode] = toks
         del model
-    if not mixtral and len(tokens) == 2:
+    if not mixtral and set(tokens) == {"packed", "packed_stream"}:
+        same = [x == y for x, y in zip(tokens["packed"], tokens["packed_stream"])]
+        result["tokens_agree"] = sum(same)                       # not expected on a random-init model
+        result["first_difference"] = same.index(False) if not all(same) else None
+        p, k = (min(result["modes"][m]["ms_per_step"]) for m in ("packed", "packed_stream"))
+        result["speedup"] = round(p / k, 3)
+    if not mixtral and set(tokens) == set(A16_MODES):
         a, b = tokens.values()
         same = [x == y for x, y in zip(a, b)]
         result["tokens_agree"] = sum(same)

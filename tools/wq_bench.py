@@ -10,6 +10,15 @@ Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N =
 * large M (--large-ms): qt_dequantize_weight alone (GB/s over the bytes it reads plus the bf16 bytes it writes, cold)
   and the whole WeightOnlyLinear (dequantise + F.linear) against F.linear on the dense weight.
 Prints one JSON line.  Device time from HIP events, mean over --reps after --warmup.
+
+  python tools/wq_bench.py --stream [--stream-ms 17,32,48,64,96,128] [--reps 30] [--warmup 5]
+
+The 17 - 128 row range: per shape (q/k/v, o, k/v, gate/up, gate or up alone, down, and K = 512 / 1024 /
+2048 at N = 4096), scheme and M, ``ops.gemm_wq_stream`` against what a default WeightOnlyLinear does for those rows --
+``ops.dequantize_weight`` into a fresh transient weight, then ``F.linear``, timed as a pair.  The two alternate call by
+call in one loop, each call between its own HIP events, the weights rotating over more than 512 MiB of copies; median
+us.  ``bits_equal_skinny`` says whether every 16-row slice of the kernel's output equals the skinny kernel's bits;
+``skinny16_us`` is the skinny kernel at M = 16 on the same weights, so the step at row 17 shows.
 """
 from __future__ import annotations
 
@@ -49,8 +58,86 @@ def _copies(nbytes):
     return max(2, -(-int(COLD_BYTES * 1.1) // nbytes))
 
 
+STREAM_SHAPES = {"qkv": (6144, 4096), "o": (4096, 4096), "kv": (1024, 4096), "gate_up": (28672, 4096),
+                 "gate": (14336, 4096), "down": (4096, 14336), "k512": (4096, 512), "k1024": (4096, 1024),
+                 "k2048": (4096, 2048)}
+
+
+def _median_us(pairs):
+    ts = sorted(a.elapsed_time(b) for a, b in pairs)
+    return round(ts[len(ts) // 2] * 1e3, 2)
+
+
+def _alternate(fns, reps, warmup):
+    """Median device time (us) of each of ``fns``, called in turn in one loop, every call between its own events."""
+    ev = [[] for _ in fns]
+    for i in range(warmup + reps):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn(i)
+            b.record()
+            if i >= warmup:
+                ev[k].append((a, b))
+    torch.cuda.synchronize()
+    return [_median_us(e) for e in ev]
+
+
+def stream_main(args):
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    names = [k for k in args.shapes.split(",") if k] if args.shapes != ",".join(SHAPES) else list(STREAM_SHAPES)
+    ms = [int(m) for m in args.stream_ms.split(",") if m]
+    rows = []
+    for shape in names:
+        N, K = STREAM_SHAPES[shape]
+        G = K // 128
+        for scheme in args.schemes.split(","):
+            bits, asym = SCHEMES[scheme]
+            lo, hi = (-8, 8) if bits == 4 else (-128, 128)
+            q = torch.randint(lo, hi, (N, K), device=dev, generator=g, dtype=torch.int8)
+            Wq0 = pack_int4(q) if bits == 4 else q
+            del q
+            s0 = (torch.rand(N, G if bits == 4 else 1, device=dev, generator=g) * 0.01 + 1e-3)
+            z0 = torch.randint(-8, 8, s0.shape, device=dev, generator=g, dtype=torch.int8) if asym else None
+            qbytes = Wq0.numel() * Wq0.element_size() + s0.numel() * 4 + (z0.numel() if asym else 0)
+            n_cp = _copies(qbytes)
+            cps = [(Wq0.clone(), s0.clone(), None if z0 is None else z0.clone()) for _ in range(n_cp)]
+
+            def pair(i, X):
+                Wq, s, z = cps[i % n_cp]
+                return F.linear(X, ops.dequantize_weight(Wq, s, K=K, zp_w=z, dtype=X.dtype))
+
+            def stream(i, X):
+                Wq, s, z = cps[i % n_cp]
+                return ops.gemm_wq_stream(X, Wq, s, zp_w=z)
+
+            X16 = torch.randn(16, K, device=dev, generator=g).to(torch.bfloat16)
+            skinny16, = _alternate([lambda i: ops.gemm_wq_skinny(X16, cps[i % n_cp][0], cps[i % n_cp][1],
+                                                                 zp_w=cps[i % n_cp][2])], args.reps, args.warmup)
+            row = {"shape": shape, "N": N, "K": K, "scheme": scheme, "packed_mb": round(qbytes / 1e6, 2),
+                   "cold_copies": n_cp, "skinny16_us": skinny16, "stream": {}}
+            for M in ms:
+                X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+                Y = stream(0, X)
+                same = all(torch.equal(Y[i:i + 16].view(torch.int16),
+                                       ops.gemm_wq_skinny(X[i:i + 16], Wq0, s0, zp_w=z0).view(torch.int16))
+                           for i in range(0, M, 16))
+                t_pair, t_stream = _alternate([lambda i: pair(i, X), lambda i: stream(i, X)], args.reps, args.warmup)
+                row["stream"][M] = {"pair_us": t_pair, "stream_us": t_stream, "speedup": round(t_pair / t_stream, 2),
+                                    "stream_tbs": round(qbytes / t_stream / 1e6, 3), "bits_equal_skinny": bool(same)}
+            rows.append(row)
+            del cps
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "wq_bench --stream", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                      "warmup": args.warmup, "rows": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true", help="the 17 - 128 row range: qt_gemm_wq_stream against "
+                    "dequantise + F.linear")
+    ap.add_argument("--stream-ms", default="17,32,48,64,96,128")
     ap.add_argument("--skinny-ms", default="1,2,4,8,16")
     ap.add_argument("--large-ms", default="4096,8192")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -61,6 +148,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wq_bench needs a GPU")
+    if args.stream:
+        return stream_main(args)
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     shapes = {k: SHAPES[k] for k in args.shapes.split(",") if k}
