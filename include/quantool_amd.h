@@ -90,6 +90,11 @@ size_t qt_hessian_prepare_workspace_bytes(int K);
 int qt_hessian_prepare(const float* G, int K, int64_t n_samples, float percdamp,
                        const int32_t* perm, float* A, uint8_t* dead, float* diag_out,
                        void* workspace, size_t workspace_bytes, qt_stream_t stream);
+/* The same, and damp_out[0] (device fp32) = the damping term percdamp*mean(diag) that was added: up to the rounding of
+ * G a lower bound on lambda_min(A), which qt_cholesky_inverse_upper_bounded takes (no host read needed). */
+int qt_hessian_prepare_damp(const float* G, int K, int64_t n_samples, float percdamp,
+                            const int32_t* perm, float* A, uint8_t* dead, float* diag_out, float* damp_out,
+                            void* workspace, size_t workspace_bytes, qt_stream_t stream);
 /* diag(2/n * G) only (input to the activation-ordering argsort). */
 int qt_hessian_diag(const float* G, int K, int64_t n_samples, float* diag_out, qt_stream_t stream);
 /* a9: perm = argsort(values, descending), stable (equal values keep ascending index; NaN orders as
@@ -121,6 +126,19 @@ int qt_cholesky_inverse_upper(float* A, int K, float* U, int32_t* info, void* wo
 size_t qt_cholesky_inverse_upper_batched_workspace_bytes(int K, int n_problems);
 int qt_cholesky_inverse_upper_batched(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info,
                                       int n_problems, void* workspace, size_t workspace_bytes, qt_stream_t stream);
+
+/* Both with min_eig_lb (device fp32, one value per problem): a lower bound on lambda_min(A), e.g. half the damping
+ * term of qt_hessian_prepare_damp.  Where the block-row products run on the matrix pipe they then take TWO fp16 planes
+ * per operand and three plane products instead of three bf16 planes and six: |R| <= sqrt(max diag A)
+ * and |R^-T| <= 1/sqrt(min_eig_lb) give the per-problem power-of-two scales that keep fp16 in range, computed on the
+ * device.  Same workspace sizes.  A bound that is not positive and finite fails its problem (info = K + 1, U = I); a
+ * bound above the true lambda_min may overflow the planes.  QT_CHOL_PLANES=bf16x3|f16x2 forces a mode for A/B runs
+ * (f16x2 through the entry points without a bound is an argument error).  Deterministic; batch = single bit for bit. */
+int qt_cholesky_inverse_upper_bounded(float* A, int K, float* U, int32_t* info, const float* min_eig_lb,
+                                      void* workspace, size_t workspace_bytes, qt_stream_t stream);
+int qt_cholesky_inverse_upper_batched_bounded(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info,
+                                              int n_problems, const float* min_eig_lb, void* workspace,
+                                              size_t workspace_bytes, qt_stream_t stream);
 
 /* ---- a10  minmax observer -> calculate_qparams ----------------------------------------------
  * W[R,K] (fp32, bf16 or fp16 by w_dtype -- every w_dtype / out_dtype argument below takes the three) -> scale, zp [R, K/group_size] fp32.  group_size <= 0:
@@ -282,6 +300,14 @@ int qt_gemm3_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, fl
 int qt_gemm3_tn_f32_ex(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N,
                        int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB, int64_t bsC,
                        void* workspace, size_t workspace_bytes, qt_stream_t stream);
+
+/* Test face: the same product on two fp16 planes per operand and three plane products (the mode of
+ * qt_cholesky_inverse_upper_bounded).  bound_a / bound_b: HOST arrays, one value per problem (batch <= 32), with
+ * |A_b| <= bound_a[b] and |B_b| <= bound_b[b] elementwise. */
+int qt_gemm3_tn_f16x2(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N,
+                      int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB, int64_t bsC,
+                      const float* bound_a, const float* bound_b, void* workspace, size_t workspace_bytes,
+                      qt_stream_t stream);
 
 /* Host-only self-check of the bf16x3 block-row planner (runs without a GPU): 0 if every k chunk of every tile is
  * covered exactly once and the slab / reduction tables are consistent, else a negative code. */

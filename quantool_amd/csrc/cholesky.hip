@@ -24,6 +24,11 @@
 //                         bf16 plane copies of Y[I, :I1]                      (split3_kernel, large K only)
 // gemm3 (gemm3_tn.h) = fp32-accurate product on the bf16 MFMA from three bf16 planes per operand; sgemm
 // (sgemm_tn.h) = the f32-MFMA fmaf chain.
+// With a lower bound on lambda_min(A) (the _bounded entry points) the gemm3 products run on TWO fp16 planes per
+// operand and three plane products (G3_F16X2): the range fp16 lacks is supplied by two per-problem power-of-two scales,
+//     |R[i][j]| <= sqrt(A[j][j]) <= sqrt(max diag A)              (A = R^T R: column j of R has norm sqrt(A[j][j]))
+//     |Y[i][j]| <= ||R^-1||_2 = 1 / sqrt(lambda_min(A))           (Y = R^-T)
+// computed on the device from A's diagonal and the caller's bound before A is overwritten (chol_scales_kernel).
 #include <stdlib.h>
 #include <string.h>
 
@@ -669,6 +674,37 @@ __global__ __launch_bounds__(256) void identity_if_failed_kernel(float* __restri
         for (int j = threadIdx.x; j < K; j += blockDim.x) U[(size_t)i * K + j] = (i == j) ? 1.0f : 0.0f;
 }
 
+// Scale exponents of the two-fp16-plane products, one workgroup per problem: e[b] = eR = 3 - ceil(log2 sqrt(max diag A_b)),
+// e[nprob + b] = eY = 3 - ceil(log2(1 / sqrt(min_eig_lb[b]))), clamped to +-G3_E_MAX.  A bound that is not a positive
+// finite number cannot scale Y: the problem is flagged in info (K + 1) and ends as U = I, like a failed pivot.  A
+// diagonal that is not positive belongs to a matrix potf2 will reject; its planes may hold anything.
+__global__ __launch_bounds__(256) void chol_scales_kernel(const float* __restrict__ A, int64_t bsA, int K,
+                                                          const float* __restrict__ min_eig_lb, int32_t* __restrict__ e,
+                                                          int32_t* __restrict__ info) {
+    __shared__ float red[256];
+    const int b = blockIdx.x, nprob = gridDim.x;
+    const float* Ab = A + (size_t)b * bsA;
+    float m = 0.0f;
+    for (int i = threadIdx.x; i < K; i += 256) m = fmaxf(m, Ab[(size_t)i * K + i]);   // fmaxf drops NaNs
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        auto clampe = [](float t) { return (int)fminf(fmaxf(t, (float)-G3_E_MAX), (float)G3_E_MAX); };
+        const float d = red[0], lb = min_eig_lb[b];
+        e[b] = (d > 0.0f && d < 3.0e38f) ? clampe(3.0f - ceilf(0.5f * log2f(d))) : 0;
+        if (lb > 0.0f && lb < 3.0e38f) {
+            e[nprob + b] = clampe(3.0f - ceilf(-0.5f * log2f(lb)));
+        } else {
+            e[nprob + b] = 0;
+            info[b] = K + 1;
+        }
+    }
+}
+
 }  // namespace
 
 // bytes of ONE problem's share of the workspace (a multiple of 256), without the bf16x3 item tables (shared by a batch)
@@ -698,8 +734,19 @@ extern "C" size_t qt_cholesky_inverse_upper_workspace_bytes(int K) {
 // those of a single-problem call (tile sizes and split-K decisions come from one problem's shape), so the factors are
 // bit-identical to n separate calls; what changes is that the latency-bound panel kernels (potf2: ONE workgroup per
 // problem; trsm, the short folds) and the block-row products serve all n problems per launch.
+// min_eig_lb (device, one per problem; may be null): see the head of the file.  QT_CHOL_PLANES=bf16x3|f16x2 forces a plane
+// mode (A/B runs; read per call): bf16x3 ignores the bound, f16x2 without one is an argument error.
 static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info, int nprob, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream) {
+                    size_t workspace_bytes, hipStream_t stream, const float* min_eig_lb = nullptr) {
+    bool f16x2 = min_eig_lb != nullptr;
+    if (const char* e = getenv("QT_CHOL_PLANES")) {
+        if (strcmp(e, "bf16x3") == 0) f16x2 = false;
+        else if (strcmp(e, "f16x2") == 0) {
+            QT_CHECK_ARG(min_eig_lb, "qt_cholesky_inverse_upper: QT_CHOL_PLANES=f16x2 needs a bound on lambda_min (the _bounded entry points)");
+        } else {
+            QT_CHECK_ARG(false, "qt_cholesky_inverse_upper: QT_CHOL_PLANES=%s (bf16x3 | f16x2)", e);
+        }
+    }
     const size_t need = qt_cholesky_inverse_upper_batched_workspace_bytes(K, nprob);
     if (!workspace || workspace_bytes < need) {
         qt_set_error("qt_cholesky_inverse_upper: workspace %zu < required %zu", workspace_bytes, need);
@@ -734,6 +781,11 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
         g3_tab = (char*)qt_align_up((size_t)(ws + (size_t)nprob * prob_bytes), 256);
         QT_HIP(hipMemcpyAsync(g3_tab, g3->blob, g3->blob_bytes, hipMemcpyHostToDevice, stream));
     }
+    f16x2 = f16x2 && g3->any;
+    // two fp16 planes use the first two plane slots; the scale exponents eR[nprob], eY[nprob] sit in problem 0's third
+    int32_t* eR = f16x2 ? (int32_t*)(Rpl + 2 * plane_stride) : nullptr;
+    int32_t* eY = f16x2 ? eR + nprob : nullptr;
+    static_assert(2 * SG_MAX_BATCH * sizeof(int32_t) <= (size_t)NB * NB * 2, "the exponents fit the smallest third plane");
     // where a block-row product's C lives decides its batch stride: A (factor phase) or the workspace (T_I)
     auto g3_row = [&](const G3Step& st, const unsigned short* Bplanes, int col_a0, int col_b0, int M, int N, float* C,
                       int64_t bsC, int mode) -> int {
@@ -760,6 +812,11 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
         a.bsApl = a.bsBpl = sW * 2;       // plane copies live in the problem's workspace (bf16 elements)
         a.bsC = bsC;
         a.bsSlabs = sW;
+        if (f16x2) {
+            a.planes = G3_F16X2;
+            a.eA = eR;
+            a.eB = Bplanes == Rpl ? eR : eY;
+        }
         return qt_gemm3_launch(a, stream);
     };
     // an f32 product of the chain, for all problems: strides by where each operand lives
@@ -792,6 +849,10 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
     }));
     QT_HIP(hipMemsetAsync(info, 0, sizeof(int32_t) * nprob, stream));
     const int prio = qt_chain_prio();
+    if (f16x2) {
+        hipLaunchKernelGGL(chol_scales_kernel, dim3(nprob), dim3(256), 0, stream, (const float*)A, sA, K, min_eig_lb, eR, info);
+        QT_LAUNCH_CHECK();
+    }
 
     // ---- A = R^T R over NBO-wide outer blocks, left-looking inside one; in place.  Outer level: right-looking
     // (one k = NBO update of the trailing matrix per block) on the f32 MFMA, or -- when the bf16x3 products
@@ -847,8 +908,10 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
             // plane copies of the finished block row (columns from its diagonal block on; only entries above
             // the diagonal are ever read back)
             if (rem > 0) {
-                int rc = qt_split3_launch(A + (size_t)J0 * K + J0, K, J1 - J0, K - J0, Rpl + (size_t)J0 * K + J0, K,
-                                          plane_stride, 0, 0, 0, stream, nprob, sA, sW * 2);
+                int rc = f16x2 ? qt_split2h_launch(A + (size_t)J0 * K + J0, K, J1 - J0, K - J0, Rpl + (size_t)J0 * K + J0, K,
+                                                   plane_stride, 0, 0, 0, eR, stream, nprob, sA, sW * 2)
+                               : qt_split3_launch(A + (size_t)J0 * K + J0, K, J1 - J0, K - J0, Rpl + (size_t)J0 * K + J0, K,
+                                                  plane_stride, 0, 0, 0, stream, nprob, sA, sW * 2);
                 if (rc) return rc;
             }
         } else if (rem > 0) {
@@ -902,6 +965,9 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
         // plane copy of the finished block row of Y (zeros above the diagonal), for the later rows' products
         auto split_row = [&]() -> int {
             if (!g3->any || I1 >= K) return QT_OK;
+            if (f16x2)
+                return qt_split2h_launch(Y + (size_t)I0 * K, K, Wi, I1, Ypl + (size_t)I0 * K, K, plane_stride, 1, I0, 0, eY,
+                                         stream, nprob, sY, sW * 2);
             return qt_split3_launch(Y + (size_t)I0 * K, K, Wi, I1, Ypl + (size_t)I0 * K, K, plane_stride, 1, I0, 0, stream,
                                     nprob, sY, sW * 2);
         };
@@ -961,4 +1027,24 @@ extern "C" int qt_cholesky_inverse_upper_batched(float* A, int64_t strideA, int 
     QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
                  "qt_cholesky_inverse_upper_batched: strides must be multiples of 4 elements and >= K*K");
     return chol_run(A, strideA, K, U, strideU, info, n_problems, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+// The same with a lower bound on lambda_min(A) per problem (device, fp32; for a Gram matrix plus damp * I any value <=
+// damp, with a binade of margin for the rounding of the Gram sum): where the chain runs its block-row products on the
+// matrix pipe they take two fp16 planes and three plane products instead of three bf16 planes and six.  A bound that is
+// not positive and finite fails its problem (info = K + 1, U = I).  No host synchronisation.
+extern "C" int qt_cholesky_inverse_upper_bounded(float* A, int K, float* U, int32_t* info, const float* min_eig_lb,
+                                                 void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+    QT_CHECK_ARG(K > 0 && A && U && info && min_eig_lb, "qt_cholesky_inverse_upper_bounded: bad arguments");
+    return chol_run(A, 0, K, U, 0, info, 1, workspace, workspace_bytes, (hipStream_t)stream_, min_eig_lb);
+}
+
+extern "C" int qt_cholesky_inverse_upper_batched_bounded(float* A, int64_t strideA, int K, float* U, int64_t strideU,
+                                                         int32_t* info, int n_problems, const float* min_eig_lb,
+                                                         void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+    QT_CHECK_ARG(K > 0 && A && U && info && min_eig_lb && n_problems >= 1 && n_problems <= SG_MAX_BATCH,
+                 "qt_cholesky_inverse_upper_batched_bounded: bad arguments (1 <= n_problems <= %d)", SG_MAX_BATCH);
+    QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
+                 "qt_cholesky_inverse_upper_batched_bounded: strides must be multiples of 4 elements and >= K*K");
+    return chol_run(A, strideA, K, U, strideU, info, n_problems, workspace, workspace_bytes, (hipStream_t)stream_, min_eig_lb);
 }

@@ -40,6 +40,16 @@ struct G3Red {
 
 enum { G3_SUB = 0, G3_SET = 1, G3_ADD = 2 };   // C -= product  /  C = product  /  C += product
 
+// Plane mode.  G3_BF16X3: the three bf16 planes and six products above.  G3_F16X2: two fp16 planes per operand,
+//     hi = fp16(x * 2^e),  lo' = fp16((x * 2^e - hi) * 2^11)          (both differences exact; residual <= 2^-24 |x|)
+// and three products in the one accumulator, smallest first:  lo'_a * hi_b,  hi_a * lo'_b,  hi_a * (2^11 hi_b)  (the
+// last factor made in registers, exactly), scaled by 2^-(11 + eA + eB) in the epilogue (exact): half the MFMAs and two
+// thirds of the staged bytes.  fp16 has 5 exponent bits, so the caller must know a bound on each operand and give the
+// per-problem exponents e with |x| * 2^e < 2^4: elements down to 2^-18 of that keep 22 significant bits, smaller ones
+// keep an absolute error of 2^-25 * 2^-e (fp16 subnormals), nothing overflows.  Dropped: lo_a * lo_b <= 2^-24.
+enum { G3_BF16X3 = 0, G3_F16X2 = 1 };
+constexpr int G3_E_MAX = 40;   // |e| of a scale exponent (the epilogue's 2^-(11 + eA + eB) stays a normal float)
+
 struct G3Args {
     const unsigned short* Apl;   // plane 0 of the A operand, [rows][ld] bf16; plane q at + q * plane_stride
     const unsigned short* Bpl;
@@ -64,6 +74,11 @@ struct G3Args {
     // reads planes at Apl + b * bsApl, Bpl + b * bsBpl (elements), writes C + b * bsC and uses slabs + b * bsSlabs.
     int batch = 1;
     int64_t bsApl = 0, bsBpl = 0, bsC = 0, bsSlabs = 0;
+    // G3_F16X2: the planes are the two fp16 planes of qt_split2h_launch (plane 1 at + plane_stride) and eA / eB
+    // (device, int32[batch], |e| <= G3_E_MAX) the exponents they were split with.
+    int planes = G3_BF16X3;
+    const int32_t* eA = nullptr;
+    const int32_t* eB = nullptr;
 };
 
 // Enqueue the product (and the slab reduction when n_red > 0).  Returns qt_status.
@@ -76,6 +91,15 @@ int qt_gemm3_launch(const G3Args& a, hipStream_t stream);
 int qt_split3_launch(const float* src, int64_t ld_src, int rows, int cols, unsigned short* planes, int64_t ld_pl,
                      int64_t plane_stride, int mask_upper, int row_g0, int col_g0, hipStream_t stream, int batch = 1,
                      int64_t bs_src = 0, int64_t bs_planes = 0);
+
+// The two-plane sibling (G3_F16X2): fp16 planes hi, lo' of src * 2^e[problem] at planes, planes + plane_stride; e: device
+// int32[batch].  Same call pattern, strides and masking.
+int qt_split2h_launch(const float* src, int64_t ld_src, int rows, int cols, unsigned short* planes, int64_t ld_pl,
+                      int64_t plane_stride, int mask_upper, int row_g0, int col_g0, const int32_t* e, hipStream_t stream,
+                      int batch = 1, int64_t bs_src = 0, int64_t bs_planes = 0);
+
+// Host: the scale exponent e = 3 - ceil(log2(bound)) for an operand with |x| <= bound, clamped to +-G3_E_MAX.
+int g3_scale_exponent(float bound);
 
 // Host-side item table of a block-row product: Tm x Tn tiles over k chunks [lo, c_end) (chunks of
 // G3_CHUNK_ROWS rows), lo = 0, or with tri != 0 lo = first chunk of row 256 * tj (B is lower-triangular in

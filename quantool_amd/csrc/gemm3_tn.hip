@@ -8,7 +8,12 @@
 // walks k-chunk (64 rows) -> plane product (6) -> 4 units and stages the two panels of every product again: 12
 // stagings per chunk (hi three times, mid twice), 8 MFMAs per wave between barrier pairs.  Both sum the same products
 // in the same accumulator; the order differs (chunk -> product -> unit there, 16-row slab -> product here).
+// G3_F16X2 (gemm3_tn.h) runs a third instance on "duo-units": 16 k-rows of the two fp16 planes of both operands = 2 x
+// 16 KiB = 32 KiB, FOUR resident (128 KiB), 4 LDS-DMA per wave and duo-unit, lead 2: the plain scheme of ring_pipe.h
+// (L = R-2; instance "gemm3_kernel, f16x2") with a counted vmcnt(4).  A phase reads 12 fragments and runs the three
+// products on them: 24 MFMAs per wave between barrier pairs.
 // The epilogue applies the tile to C (C -= acc / C = acc / C += acc) or stores a slab for the ordered reduction.
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -28,6 +33,11 @@ constexpr int CH_UNITS = 6 * (CH_ROWS / UT);    // chunk loop: 24 units per chun
 constexpr int TRING = 3;                        // tri-unit loop: tri-units resident in LDS (144 KiB)
 constexpr int TRI_BYTES = 3 * UNIT_BYTES;       // planes hi, mid, lo, each the 16 KiB image of ring_pipe.h
 constexpr int TRI_DMA = 6;                      // LDS-DMA instructions per wave and tri-unit
+constexpr int DRING = 4;                        // f16x2 loop: duo-units resident in LDS (128 KiB)
+constexpr int DUO_BYTES = 2 * UNIT_BYTES;       // planes hi, lo'
+constexpr int DUO_DMA = 4;                      // LDS-DMA instructions per wave and duo-unit
+constexpr int DUO_LEAD = 2;                     // <= DRING - 2
+enum { LOOP_CHUNK = 0, LOOP_TRI = 1, LOOP_DUO = 2 };
 static_assert(CH_ROWS / UT == 4, "the phase code below recomputes the source pointers every 4 units");
 // plane (0 = hi, 1 = mid, 2 = lo) of the A / B operand in product pr, two bits each, smallest product first:
 //   pr:  0      1      2       3       4       5
@@ -51,12 +61,15 @@ struct G3Params {
     float* slabs;
     const G3Item* items;
     int64_t bsA_bytes, bsB_bytes, bsC, bsSlabs;   // problem blockIdx.y of a batch
+    const int32_t* eA;    // LOOP_DUO: scale exponents of the planes, one per problem
+    const int32_t* eB;
 };
 
-// TRI: the tri-unit loop (default); !TRI: the chunk loop (QT_G3_LOOP=chunk)
-template <int MODE, bool TRI>
+// LOOP_TRI: the tri-unit loop (default); LOOP_CHUNK: the chunk loop (QT_G3_LOOP=chunk); LOOP_DUO: two fp16 planes
+template <int MODE, int LOOP>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
-    __shared__ __attribute__((aligned(16))) char ring[TRI ? TRING * TRI_BYTES : RING * UNIT_BYTES];
+    constexpr bool TRI = LOOP == LOOP_TRI;
+    __shared__ __attribute__((aligned(16))) char ring[LOOP == LOOP_DUO ? DRING * DUO_BYTES : TRI ? TRING * TRI_BYTES : RING * UNIT_BYTES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -75,8 +88,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     const int c_hi = __builtin_amdgcn_readfirstlane(itp->c_hi);
     const int slab_idx = __builtin_amdgcn_readfirstlane(itp->slab);
     const int ti = it_tile >> 16, tj = it_tile & 0xFFFF;
-    // chunk loop: a multiple of 24 (items are >= 2 chunks: nu >= 48); tri-unit loop: a multiple of 4, >= 8
-    const int nu = (c_hi - c_lo) * (TRI ? CH_ROWS / UT : CH_UNITS);
+    // chunk loop: a multiple of 24 (items are >= 2 chunks: nu >= 48); tri-unit and f16x2 loops: a multiple of 4, >= 8
+    const int nu = (c_hi - c_lo) * (LOOP != LOOP_CHUNK ? CH_ROWS / UT : CH_UNITS);
 
     // staging geometry: as xtx_kernel (wave w fills k rows 4*(w&3)..+3 of column group w>>2; XOR swizzle of
     // the 16-B chunk index on the SOURCE address)
@@ -113,7 +126,64 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
 
-    if constexpr (TRI) {
+    if constexpr (LOOP == LOOP_DUO) {
+        // running scalar source pointers (plane hi) of the next duo-unit to issue
+        const char* runA = p.Apl + (p.rowA0 + (int64_t)c_lo * CH_ROWS) * p.ld2;
+        const char* runB = p.Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
+        auto issue2 = [&](int slot) {
+            const unsigned d = dst_wave + (unsigned)slot * DUO_BYTES;
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+                glds16_pair2(voffA, voffB, runA + pl * p.plane_bytes, runB + pl * p.plane_bytesB, d + pl * UNIT_BYTES,
+                             d + pl * UNIT_BYTES + 8192);
+            runA += ustride;
+            runB += ustrideB;
+        };
+        s16x8 fa[2][4], fb[2][2];   // [plane][tile]
+        // Phase u, both groups alike: reads of duo-unit u, issue of u+2 into the slot u-2 has left (its reads retired two
+        // barriers ago), vmcnt(4) retires u+1 with u+2 in flight (ring_pipe.h, instance "gemm3_kernel, f16x2").
+        auto phase = [&](auto slot_c, int u) {
+            constexpr int S = decltype(slot_c)::value;
+            constexpr int ISLOT = (S + DUO_LEAD) % DRING;
+            const char* base = ring + S * DUO_BYTES;
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) fa[pl][mi] = tr_load8(base + pl * UNIT_BYTES + aoff[mi]);
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) fb[pl][ni] = tr_load8(base + pl * UNIT_BYTES + boff[ni]);
+            }
+            if (u + DUO_LEAD < nu) issue2(ISLOT);
+            ring_drain_wait<DUO_DMA, DUO_LEAD>(nu - u - 2);
+            ring_sync_math([&] {
+                // 2^11 * hi_b, exact (|hi_b| < 2^4; a subnormal hi_b becomes normal): two v_pk_mul_f16 per fragment
+                s16x8 fbs[2];
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+                    fbs[ni] = __builtin_bit_cast(s16x8, __builtin_bit_cast(f16x8, fb[0][ni]) * (_Float16)2048.0f);
+                ring_mma32<true>(fa[1], fb[0], acc);   // lo'_a * hi_b
+                ring_mma32<true>(fa[0], fb[1], acc);   // hi_a * lo'_b
+                ring_mma32<true>(fa[0], fbs, acc);     // hi_a * 2^11 hi_b
+            });
+        };
+        if (nu > 0) {
+            issue2(0);
+            issue2(1);   // nu >= 8
+            wait_vmcnt<DUO_DMA*(DUO_LEAD - 1)>();
+            ring_stagger_begin(group_b);
+            for (int u = 0; u < nu; u += DRING) ring_body<DRING>(phase, u);   // nu is a multiple of 4
+            ring_stagger_end(group_b);
+        }
+        // undo the scales of the planes and the 2^11 of the products: a power of two, exact
+        const int es = -(11 + p.eA[blockIdx.y] + p.eB[blockIdx.y]);
+        const float unscale = __builtin_bit_cast(float, (unsigned)(127 + (es < -126 ? -126 : es > 127 ? 127 : es)) << 23);
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mi][ni][r] *= unscale;
+    } else if constexpr (TRI) {
         // running scalar source pointers (plane hi) of the next tri-unit to issue
         const char* runA = p.Apl + (p.rowA0 + (int64_t)c_lo * CH_ROWS) * p.ld2;
         const char* runB = p.Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
@@ -351,6 +421,38 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ s
     *(u16x4*)(dst + 2 * plane_stride) = lo;
 }
 
+// The two fp16 planes of src * 2^e (G3_F16X2).  x * 2^e is exact (no underflow: |e| <= G3_E_MAX), the residual and its
+// 2^11 are exact; hi rounds to nearest, subnormals kept.
+__global__ __launch_bounds__(256) void split2h_kernel(const float* __restrict__ src, int64_t ld_src, int cols,
+                                                      unsigned short* __restrict__ planes, int64_t ld_pl,
+                                                      int64_t plane_stride, int mask_upper, int row_g0, int col_g0,
+                                                      int64_t bs_src, int64_t bs_planes, const int32_t* __restrict__ e) {
+    const int ex = e[blockIdx.z];
+    if (blockIdx.z) {
+        src += (size_t)blockIdx.z * bs_src;
+        planes += (size_t)blockIdx.z * bs_planes;
+    }
+    const int c4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int r = blockIdx.y;
+    if (c4 >= cols) return;
+    const float scale = __builtin_bit_cast(float, (unsigned)(127 + (ex < -G3_E_MAX ? -G3_E_MAX : ex > G3_E_MAX ? G3_E_MAX : ex)) << 23);
+    f32x4 v = *(const f32x4*)(src + (size_t)r * ld_src + c4);
+    typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
+    u16x4 hi, lo;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float x = v[q] * scale;
+        if (mask_upper && col_g0 + c4 + q > row_g0 + r) x = 0.0f;
+        const _Float16 h = (_Float16)x;
+        const float r1 = x - (float)h;                      // exact
+        hi[q] = __builtin_bit_cast(unsigned short, h);
+        lo[q] = __builtin_bit_cast(unsigned short, (_Float16)(r1 * 2048.0f));
+    }
+    unsigned short* dst = planes + (size_t)r * ld_pl + c4;
+    *(u16x4*)dst = hi;
+    *(u16x4*)(dst + plane_stride) = lo;
+}
+
 }  // namespace
 
 int qt_gemm3_launch(const G3Args& a, hipStream_t stream) {
@@ -388,18 +490,23 @@ int qt_gemm3_launch(const G3Args& a, hipStream_t stream) {
     p.bsB_bytes = a.bsBpl * 2;
     p.bsC = a.bsC;
     p.bsSlabs = a.bsSlabs;
+    QT_CHECK_ARG(a.planes == G3_BF16X3 || (a.planes == G3_F16X2 && a.eA && a.eB),
+                 "qt_gemm3_launch: plane mode %d needs its scale exponents", a.planes);
+    p.eA = a.eA;
+    p.eB = a.eB;
     const dim3 grid(a.n_items, nb);
     // read per call: the tests run both loops on the same inputs in one process
     const char* loop_env = getenv("QT_G3_LOOP");
     const bool chunk_loop = loop_env && strcmp(loop_env, "chunk") == 0;
-    auto launch = [&](auto tri_c) {
-        constexpr bool TRI = decltype(tri_c)::value;
-        if (a.mode == G3_SUB) hipLaunchKernelGGL((gemm3_kernel<G3_SUB, TRI>), grid, dim3(NTHREADS), 0, stream, p);
-        else if (a.mode == G3_ADD) hipLaunchKernelGGL((gemm3_kernel<G3_ADD, TRI>), grid, dim3(NTHREADS), 0, stream, p);
-        else hipLaunchKernelGGL((gemm3_kernel<G3_SET, TRI>), grid, dim3(NTHREADS), 0, stream, p);
+    auto launch = [&](auto loop_c) {
+        constexpr int LOOP = decltype(loop_c)::value;
+        if (a.mode == G3_SUB) hipLaunchKernelGGL((gemm3_kernel<G3_SUB, LOOP>), grid, dim3(NTHREADS), 0, stream, p);
+        else if (a.mode == G3_ADD) hipLaunchKernelGGL((gemm3_kernel<G3_ADD, LOOP>), grid, dim3(NTHREADS), 0, stream, p);
+        else hipLaunchKernelGGL((gemm3_kernel<G3_SET, LOOP>), grid, dim3(NTHREADS), 0, stream, p);
     };
-    if (chunk_loop) launch(std::false_type{});
-    else launch(std::true_type{});
+    if (a.planes == G3_F16X2) launch(std::integral_constant<int, LOOP_DUO>{});
+    else if (chunk_loop) launch(std::integral_constant<int, LOOP_CHUNK>{});
+    else launch(std::integral_constant<int, LOOP_TRI>{});
     QT_LAUNCH_CHECK();
     if (a.n_red > 0) {
         hipLaunchKernelGGL(gemm3_reduce_kernel, dim3(a.n_red, 16, nb), dim3(256), 0, stream, (const float*)a.slabs, a.red,
@@ -419,6 +526,20 @@ int qt_split3_launch(const float* src, int64_t ld_src, int rows, int cols, unsig
     QT_CHECK_ARG(bs_src % 4 == 0 && bs_planes % 4 == 0, "qt_split3_launch: batch strides must be multiples of 4");
     hipLaunchKernelGGL(split3_kernel, dim3((cols / 4 + 255) / 256, rows, batch > 1 ? batch : 1), dim3(256), 0, stream, src,
                        ld_src, cols, planes, ld_pl, plane_stride, mask_upper, row_g0, col_g0, bs_src, bs_planes);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+int qt_split2h_launch(const float* src, int64_t ld_src, int rows, int cols, unsigned short* planes, int64_t ld_pl,
+                      int64_t plane_stride, int mask_upper, int row_g0, int col_g0, const int32_t* e, hipStream_t stream,
+                      int batch, int64_t bs_src, int64_t bs_planes) {
+    if (rows <= 0 || cols <= 0) return QT_OK;
+    QT_CHECK_ARG(e && cols % 4 == 0 && ld_src % 4 == 0 && ld_pl % 4 == 0 && plane_stride % 4 == 0 &&
+                     ((uintptr_t)src & 15) == 0 && ((uintptr_t)planes & 7) == 0,
+                 "qt_split2h_launch: columns / pitches must be multiples of 4 and the pointers aligned");
+    QT_CHECK_ARG(bs_src % 4 == 0 && bs_planes % 4 == 0, "qt_split2h_launch: batch strides must be multiples of 4");
+    hipLaunchKernelGGL(split2h_kernel, dim3((cols / 4 + 255) / 256, rows, batch > 1 ? batch : 1), dim3(256), 0, stream, src,
+                       ld_src, cols, planes, ld_pl, plane_stride, mask_upper, row_g0, col_g0, bs_src, bs_planes, e);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }
@@ -497,6 +618,16 @@ void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items,
     }
 }
 
+// e = 3 - ceil(log2(bound)): |x| <= bound  =>  |x| * 2^e <= 2^3, one binade under the fp16 planes' 2^4 limit
+int g3_scale_exponent(float bound) {
+    if (!(bound > 0.0f) || bound > 3.0e38f) return 0;
+    int x;
+    const float m = frexpf(bound, &x);          // bound = m * 2^x, 0.5 <= m < 1
+    const int ceil_log2 = m == 0.5f ? x - 1 : x;
+    const int e = 3 - ceil_log2;
+    return e < -G3_E_MAX ? -G3_E_MAX : e > G3_E_MAX ? G3_E_MAX : e;
+}
+
 // ---- C-ABI face (tests and micro-benchmarks; the hot path calls qt_gemm3_launch from cholesky.hip) ----
 // C (-)= A^T B with A [k][lda], B [k][ldb] fp32, k a multiple of 128.  kind 0: every tile whole (C -= A^T B);
 // kind 1: split along k into slabs (C = A^T B), as the inverse's block-row product.  Synchronous table upload.
@@ -521,7 +652,12 @@ extern "C" size_t qt_gemm3_tn_f32_workspace_bytes(int M, int N, int k) {
 // up to 8 instead of 256: the edge tiles' loads are clamped at colmax) and a batch of problems in one launch.
 static int g3_test_run(const char* who, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                        int M, int N, int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB, int64_t bsC,
-                       void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                       void* workspace, size_t workspace_bytes, hipStream_t stream, const float* bound_a = nullptr,
+                       const float* bound_b = nullptr) {
+    // bound_a / bound_b (host, one per problem: |A| <= bound_a[b], |B| <= bound_b[b]) select the two-fp16-plane mode
+    const bool f16x2 = bound_a && bound_b;
+    constexpr size_t EXP_BYTES = 256;   // eA[32], eB[32] at the end of the table area
+    QT_CHECK_ARG(!f16x2 || batch <= 32, "%s: at most 32 problems with bounds", who);
     QT_CHECK_ARG(A && B && C && M > 0 && N > 0 && k > 0 && k % 128 == 0, "%s: k=%d must be a positive multiple of 128", who, k);
     QT_CHECK_ARG(M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0, "%s: M, N, lda, ldb must be multiples of 4", who);
     QT_CHECK_ARG(batch >= 1 && bsA % 4 == 0 && bsB % 4 == 0, "%s: batch %d / strides unsupported", who, batch);
@@ -540,10 +676,23 @@ static int g3_test_run(const char* who, const float* A, int64_t lda, const float
     unsigned short* Bpl = (unsigned short*)(ws + pb);
     float* slabs = (float*)(ws + 2 * pb);
     char* tab = ws + 2 * pb + sb;   // problem 0's table serves the batch
+    int32_t* exps = (int32_t*)(tab + G3_TEST_TABLE_BYTES - EXP_BYTES);
+    if (f16x2) {
+        int32_t host_e[64] = {0};
+        for (int b = 0; b < batch; ++b) {
+            QT_CHECK_ARG(bound_a[b] > 0.0f && bound_b[b] > 0.0f, "%s: bounds must be positive", who);
+            host_e[b] = g3_scale_exponent(bound_a[b]);
+            host_e[32 + b] = g3_scale_exponent(bound_b[b]);
+        }
+        QT_HIP(hipStreamSynchronize(stream));
+        QT_HIP(hipMemcpy(exps, host_e, sizeof(host_e), hipMemcpyHostToDevice));
+    }
     for (int b = 0; b < batch; ++b) QT_HIP(hipMemsetAsync(ws + (size_t)b * per, 0, 2 * pb, stream));   // columns M.. / N.. of the planes
-    int rc = qt_split3_launch(A, lda, k, M, Apl, ldp, plane_stride, 0, 0, 0, stream, batch, bsA, (int64_t)(per / 2));
+    int rc = f16x2 ? qt_split2h_launch(A, lda, k, M, Apl, ldp, plane_stride, 0, 0, 0, exps, stream, batch, bsA, (int64_t)(per / 2))
+                   : qt_split3_launch(A, lda, k, M, Apl, ldp, plane_stride, 0, 0, 0, stream, batch, bsA, (int64_t)(per / 2));
     if (rc) return rc;
-    rc = qt_split3_launch(B, ldb, k, N, Bpl, ldp, plane_stride, 0, 0, 0, stream, batch, bsB, (int64_t)(per / 2));
+    rc = f16x2 ? qt_split2h_launch(B, ldb, k, N, Bpl, ldp, plane_stride, 0, 0, 0, exps + 32, stream, batch, bsB, (int64_t)(per / 2))
+               : qt_split3_launch(B, ldb, k, N, Bpl, ldp, plane_stride, 0, 0, 0, stream, batch, bsB, (int64_t)(per / 2));
     if (rc) return rc;
     const int Tm = (M + BT - 1) / BT, Tn = (N + BT - 1) / BT, nch = k / CH_ROWS;
     constexpr int TRI_STEP = 256 / G3_CHUNK_ROWS;
@@ -567,7 +716,7 @@ static int g3_test_run(const char* who, const float* A, int64_t lda, const float
         QT_CHECK_ARG((size_t)next * BT * BT * 4 <= sb, "%s: too many tiles for the test face", who);
     }
     const size_t ib = items.size() * sizeof(G3Item), rb = red.size() * sizeof(G3Red);
-    QT_CHECK_ARG(qt_align_up(ib, 256) + rb <= G3_TEST_TABLE_BYTES, "%s: table too large for the test face", who);
+    QT_CHECK_ARG(qt_align_up(ib, 256) + rb <= G3_TEST_TABLE_BYTES - EXP_BYTES, "%s: table too large for the test face", who);
     QT_HIP(hipStreamSynchronize(stream));
     QT_HIP(hipMemcpy(tab, items.data(), ib, hipMemcpyHostToDevice));
     if (rb) QT_HIP(hipMemcpy(tab + qt_align_up(ib, 256), red.data(), rb, hipMemcpyHostToDevice));
@@ -593,6 +742,11 @@ static int g3_test_run(const char* who, const float* A, int64_t lda, const float
     g.bsApl = g.bsBpl = (int64_t)(per / 2);
     g.bsC = bsC;
     g.bsSlabs = (int64_t)(per / 4);
+    if (f16x2) {
+        g.planes = G3_F16X2;
+        g.eA = exps;
+        g.eB = exps + 32;
+    }
     return qt_gemm3_launch(g, stream);
 }
 
@@ -609,6 +763,17 @@ extern "C" int qt_gemm3_tn_f32_ex(const float* A, int64_t lda, const float* B, i
                                   int64_t bsC, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
     return g3_test_run("qt_gemm3_tn_f32_ex", A, lda, B, ldb, C, ldc, M, N, k, kind, tri, tight, batch, bsA, bsB, bsC, workspace,
                        workspace_bytes, (hipStream_t)stream_);
+}
+
+// The same on two fp16 planes (G3_F16X2).  bound_a / bound_b: HOST arrays, one value per problem, with |A_b| <= bound_a[b]
+// and |B_b| <= bound_b[b] elementwise; a looser bound costs precision on the small elements, a violated one overflows.
+extern "C" int qt_gemm3_tn_f16x2(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
+                                 int N, int k, int kind, int tri, int tight, int batch, int64_t bsA, int64_t bsB,
+                                 int64_t bsC, const float* bound_a, const float* bound_b, void* workspace,
+                                 size_t workspace_bytes, qt_stream_t stream_) {
+    QT_CHECK_ARG(bound_a && bound_b, "qt_gemm3_tn_f16x2: bounds are required");
+    return g3_test_run("qt_gemm3_tn_f16x2", A, lda, B, ldb, C, ldc, M, N, k, kind, tri, tight, batch, bsA, bsB, bsC, workspace,
+                       workspace_bytes, (hipStream_t)stream_, bound_a, bound_b);
 }
 
 // ---- a7 for fp32 activations (an fp32 checkpoint): G += X^T X with X fp32 [n_tokens, K] --------------------------

@@ -208,10 +208,9 @@ extern "C" size_t qt_hessian_prepare_workspace_bytes(int K) {
     return 512 + (prepare_two_pass(K) ? qt_align_up((size_t)K * K * 4, 256) + 256 : 0);
 }
 
-extern "C" int qt_hessian_prepare(const float* G, int K, int64_t n_samples, float percdamp, const int32_t* perm,
-                                  float* A, uint8_t* dead, float* diag_out, void* workspace, size_t workspace_bytes,
-                                  qt_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int hessian_prepare_run(const float* G, int K, int64_t n_samples, float percdamp, const int32_t* perm, float* A,
+                               uint8_t* dead, float* diag_out, float* damp_out, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
     QT_CHECK_ARG(G && A && dead && K > 0 && n_samples > 0, "qt_hessian_prepare: bad arguments");
     const size_t need = qt_hessian_prepare_workspace_bytes(K);
     if (!workspace || workspace_bytes < need) {
@@ -223,6 +222,7 @@ extern "C" int qt_hessian_prepare(const float* G, int K, int64_t n_samples, floa
     hipLaunchKernelGGL(diag_stats_kernel, dim3(1), dim3(1024), 0, stream, G, K, c, percdamp, perm, dead, diag_out,
                        stats);
     QT_LAUNCH_CHECK();
+    if (damp_out) QT_HIP(hipMemcpyAsync(damp_out, stats, sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (prepare_two_pass(K) && (((uintptr_t)G) & 15) == 0) {
         float* S = (float*)qt_align_up((size_t)(stats + 64), 256);
         const int nb = (K + 63) / 64;
@@ -243,6 +243,23 @@ extern "C" int qt_hessian_prepare(const float* G, int K, int64_t n_samples, floa
                        (const uint8_t*)dead, (const float*)stats, A);
     QT_LAUNCH_CHECK();
     return QT_OK;
+}
+
+extern "C" int qt_hessian_prepare(const float* G, int K, int64_t n_samples, float percdamp, const int32_t* perm,
+                                  float* A, uint8_t* dead, float* diag_out, void* workspace, size_t workspace_bytes,
+                                  qt_stream_t stream_) {
+    return hessian_prepare_run(G, K, n_samples, percdamp, perm, A, dead, diag_out, nullptr, workspace, workspace_bytes,
+                               (hipStream_t)stream_);
+}
+
+// The same, and damp_out[0] (device) = the damping term that was added to the diagonal: a lower bound on lambda_min(A)
+// up to the rounding of G, for qt_cholesky_inverse_upper_bounded.
+extern "C" int qt_hessian_prepare_damp(const float* G, int K, int64_t n_samples, float percdamp, const int32_t* perm,
+                                       float* A, uint8_t* dead, float* diag_out, float* damp_out, void* workspace,
+                                       size_t workspace_bytes, qt_stream_t stream_) {
+    QT_CHECK_ARG(damp_out, "qt_hessian_prepare_damp: damp_out is required");
+    return hessian_prepare_run(G, K, n_samples, percdamp, perm, A, dead, diag_out, damp_out, workspace, workspace_bytes,
+                               (hipStream_t)stream_);
 }
 
 extern "C" int qt_hessian_diag(const float* G, int K, int64_t n_samples, float* diag_out, qt_stream_t stream_) {

@@ -26,13 +26,20 @@
 //        issue into 2u+2, beside group B's outstanding reads.)
 //   In flight at every wait: L-1 units = N*(L-1) LDS-DMA instructions per wave; never vmcnt(0) inside the loop.
 //   Past the last unit nothing is issued, and the drain ladder lowers the count with the units that still exist.
-// The three instances:
+// The instances:
 //   xtx_kernel    R 8, L 6, unit = 16 tokens (16 KiB),             N 2: vmcnt(10), 5 units = 80 KiB per CU in flight
 //   xtx16_kernel  R 5, L 3, unit = a pair of those ("double", 32 KiB), N 4: vmcnt(8), 2 doubles = 64 KiB in flight
 //   gemm3_kernel  (chunk loop, QT_G3_LOOP=chunk)  R 8, L 6, unit = 16 k-rows of one plane pair (16 KiB), N 2:
 //                 vmcnt(10), 5 units = 80 KiB in flight
 //   gemm3_kernel  R 3, unit = 16 k-rows of all three planes of both operands ("tri-unit", 48 KiB), N 6: vmcnt(6), one
 //                 tri-unit = 48 KiB in flight -- the half-phase form below
+//   gemm3_kernel, f16x2  R 4, L 2, unit = 16 k-rows of the two fp16 planes of both operands ("duo-unit", 32 KiB), N 4:
+//                 vmcnt(4), one duo-unit = 32 KiB in flight.  Four 32 KiB slots fit where three 48 KiB ones do, so L = 2
+//                 = R-2 is the plain scheme above, both groups alike, no half-phase hooks.  RAW: unit u is retired by the
+//                 vmcnt(4) of LOAD(u-1) (only u+1 stays outstanding), intervals 2u-2 / 2u-1, and first read in 2u.
+//                 WAR: unit u's reads retire in 2u+1 (A) / 2u+2 (B); its slot takes unit u+4, issued in LOAD(u+2):
+//                 intervals 2u+4 / 2u+5.  Prologue: units 0, 1 issued, vmcnt(4) retires unit 0.  Drain: nothing is
+//                 issued from phase nu-2 on, whose wait is vmcnt(0) (ring_drain_wait<4, 2>); nu is a multiple of 4.
 //
 // R = 3, HALF-PHASE ISSUE (gemm3_kernel).  Three 48 KiB tri-units are all the LDS holds, and the scheme above then
 // allows L = 1 only: its wait would be vmcnt(0) right behind the issue, with nothing in flight under the MFMAs.  What
@@ -241,17 +248,16 @@ __device__ __forceinline__ void ring_stagger_end(bool group_b) {
 }
 
 // One trip round a ring of SLOTS slots: phase(slot as an integral_constant, unit index), so that every LDS address
-// of a phase is an immediate.  8: xtx_kernel / gemm3_kernel's chunk loop, 5: xtx16_kernel, 3: gemm3_kernel.
+// of a phase is an immediate.  8: xtx_kernel / gemm3_kernel's chunk loop, 5: xtx16_kernel, 4: gemm3_kernel on two fp16
+// planes, 3: gemm3_kernel.
 template <int SLOTS, class Phase>
 __device__ __forceinline__ void ring_body(Phase&& phase, int u) {
-    static_assert(SLOTS == 3 || SLOTS == 5 || SLOTS == 8, "unrolled by hand");
+    static_assert(SLOTS == 3 || SLOTS == 4 || SLOTS == 5 || SLOTS == 8, "unrolled by hand");
     phase(std::integral_constant<int, 0>{}, u);
     phase(std::integral_constant<int, 1>{}, u + 1);
     phase(std::integral_constant<int, 2>{}, u + 2);
-    if constexpr (SLOTS >= 5) {
-        phase(std::integral_constant<int, 3>{}, u + 3);
-        phase(std::integral_constant<int, 4>{}, u + 4);
-    }
+    if constexpr (SLOTS >= 4) phase(std::integral_constant<int, 3>{}, u + 3);
+    if constexpr (SLOTS >= 5) phase(std::integral_constant<int, 4>{}, u + 4);
     if constexpr (SLOTS == 8) {
         phase(std::integral_constant<int, 5>{}, u + 5);
         phase(std::integral_constant<int, 6>{}, u + 6);

@@ -278,20 +278,26 @@ def gptq_quantize_batched(groups: Sequence[Tuple[Sequence[torch.Tensor], Hessian
     U = ubuf[:, :K * K].view(n, K, K)
     A = torch.empty((n, K, K), dtype=torch.float32, device=dev)
     perms, invs, deads = [], [], []
+    # the damping term each prepare adds, on the device: half of it bounds lambda_min(A) from below (one binade of margin
+    # for the fp32 rounding of G), which lets the factor chain run its long products on two fp16 planes
+    damps = torch.zeros(n, dtype=torch.float32, device=dev) if dampening_frac > 0 else None
     for b, (ws, acc) in enumerate(groups):
         perm = inv = None   # perm: sweep position -> original column; inv: its inverse
         if actorder is not None:
             perm, inv = ops.argsort_desc(ops.hessian_diag(acc.G, acc.n))
-        _, dead, _ = ops.hessian_prepare(acc.G, acc.n, dampening_frac, perm, A_out=A[b], scratch=ubuf[b])
+        _, dead, _ = ops.hessian_prepare(acc.G, acc.n, dampening_frac, perm, A_out=A[b], scratch=ubuf[b],
+                                         damp_out=None if damps is None else damps[b:b + 1])
         perms.append(perm)
         invs.append(inv)
         deads.append(dead)
 
     # ---- factorise all groups in one chain of launches (a8) -------------------------------------------
+    # damp == 0 means mean(diag H) == 0: every column is dead and A is the identity, whose smallest eigenvalue is 1
+    lb = None if damps is None else torch.where(damps > 0, damps * 0.5, torch.ones_like(damps))
     if n == 1:
-        _, info = ops.cholesky_inverse_upper(A[0], U_out=U[0])
+        _, info = ops.cholesky_inverse_upper(A[0], U_out=U[0], min_eig_lb=lb)
     else:
-        info = ops.cholesky_inverse_upper_batched(A, U)
+        info = ops.cholesky_inverse_upper_batched(A, U, min_eig_lb=lb)
     del A
 
     # ---- stacked fp32 working copy in sweep order, observer (a10) ------------------------------------

@@ -35,6 +35,8 @@ SIGNATURES = {
     "qt_hessian_prepare_workspace_bytes": (c_size_t, [c_int]),
     "qt_hessian_prepare": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    "qt_hessian_prepare_damp": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "qt_hessian_diag": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "qt_argsort_desc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "qt_cholesky_inverse_upper_workspace_bytes": (c_size_t, [c_int]),
@@ -42,6 +44,10 @@ SIGNATURES = {
     "qt_cholesky_inverse_upper_batched_workspace_bytes": (c_size_t, [c_int, c_int]),
     "qt_cholesky_inverse_upper_batched": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                                   c_size_t, c_void_p]),
+    "qt_cholesky_inverse_upper_bounded": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p]),
+    "qt_cholesky_inverse_upper_batched_bounded": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int,
+                                                          c_void_p, c_void_p, c_size_t, c_void_p]),
     "qt_group_minmax_qparams": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "qt_weight_gather_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
@@ -86,6 +92,9 @@ SIGNATURES = {
                                 c_void_p, c_size_t, c_void_p]),
     "qt_gemm3_tn_f32_ex": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    "qt_gemm3_tn_f16x2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     "qt_sgemm_tn_f32_workspace_bytes": (c_size_t, [c_int, c_int]),
     "qt_sgemm_tn_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),

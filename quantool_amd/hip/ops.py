@@ -228,10 +228,12 @@ def factor_view(buf: torch.Tensor, K: int) -> torch.Tensor:
 
 
 def hessian_prepare(G: torch.Tensor, n_samples: int, percdamp: float, perm: Optional[torch.Tensor] = None,
-                    A_out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+                    A_out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None,
+                    damp_out: Optional[torch.Tensor] = None):
     """Returns (A flipped+damped [K,K] fp32 upper-valid, dead uint8[K], diag fp32[K]).  ``scratch``: a contiguous
     device tensor whose bytes may be used as the workspace (e.g. ``factor_buffer``: the buffer the factor will be
-    written to afterwards); too small or absent: the cached per-stream workspace."""
+    written to afterwards); too small or absent: the cached per-stream workspace.  ``damp_out``: fp32 device tensor
+    whose first element receives the damping term that was added to the diagonal (no host read)."""
     lib = load()
     _req(G, torch.float32, "G", 2)
     K = G.shape[0]
@@ -252,14 +254,31 @@ def hessian_prepare(G: torch.Tensor, n_samples: int, percdamp: float, perm: Opti
         ws = scratch.view(torch.uint8).reshape(-1)
     else:
         ws = workspace(need, G.device, "prep")
+    if damp_out is not None:
+        _req(damp_out, torch.float32, "damp_out", damp_out.dim())
+        if damp_out.numel() < 1 or damp_out.device != G.device:
+            raise ValueError("damp_out must be a non-empty fp32 tensor on G's device")
+        check("qt_hessian_prepare_damp", lib.qt_hessian_prepare_damp(
+            G.data_ptr(), K, int(n_samples), float(percdamp), _ptr(perm), A.data_ptr(), dead.data_ptr(), diag.data_ptr(),
+            damp_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return A, dead, diag
     check("qt_hessian_prepare", lib.qt_hessian_prepare(G.data_ptr(), K, int(n_samples), float(percdamp), _ptr(perm),
                                                        A.data_ptr(), dead.data_ptr(), diag.data_ptr(), ws.data_ptr(),
                                                        ws.numel(), _stream()))
     return A, dead, diag
 
 
-def cholesky_inverse_upper(A: torch.Tensor, U_out: Optional[torch.Tensor] = None):
-    """A (flipped damped Hessian, destroyed) -> (U upper [K,K] fp32, info int32[1] device)."""
+def _min_eig_lb(lb: torch.Tensor, n: int, device) -> torch.Tensor:
+    _req(lb, torch.float32, "min_eig_lb", lb.dim())
+    if lb.numel() != n or not lb.is_contiguous() or lb.device != device:
+        raise ValueError(f"min_eig_lb must be a contiguous fp32 device tensor of {n} value(s)")
+    return lb
+
+
+def cholesky_inverse_upper(A: torch.Tensor, U_out: Optional[torch.Tensor] = None,
+                           min_eig_lb: Optional[torch.Tensor] = None):
+    """A (flipped damped Hessian, destroyed) -> (U upper [K,K] fp32, info int32[1] device).  ``min_eig_lb``: fp32 device
+    tensor of one value, a lower bound on lambda_min(A): the long block-row products then run on two fp16 planes."""
     lib = load()
     _req(A, torch.float32, "A", 2)
     K = A.shape[0]
@@ -270,6 +289,11 @@ def cholesky_inverse_upper(A: torch.Tensor, U_out: Optional[torch.Tensor] = None
         raise ValueError("U must be contiguous fp32 [K, K]")
     info = torch.zeros(1, dtype=torch.int32, device=A.device)
     ws = workspace(lib.qt_cholesky_inverse_upper_workspace_bytes(K), A.device, "chol")
+    if min_eig_lb is not None:
+        lb = _min_eig_lb(min_eig_lb, 1, A.device)
+        check("qt_cholesky_inverse_upper_bounded", lib.qt_cholesky_inverse_upper_bounded(
+            A.data_ptr(), K, U.data_ptr(), info.data_ptr(), lb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return U, info
     check("qt_cholesky_inverse_upper", lib.qt_cholesky_inverse_upper(A.data_ptr(), K, U.data_ptr(), info.data_ptr(),
                                                                      ws.data_ptr(), ws.numel(), _stream()))
     return U, info
@@ -278,10 +302,11 @@ def cholesky_inverse_upper(A: torch.Tensor, U_out: Optional[torch.Tensor] = None
 MAX_BATCH = 16      # problems per batched factorisation / groups per grouped sweep (SG_MAX_BATCH / SG_MAX_GROUPS)
 
 
-def cholesky_inverse_upper_batched(A: torch.Tensor, U: torch.Tensor):
+def cholesky_inverse_upper_batched(A: torch.Tensor, U: torch.Tensor, min_eig_lb: Optional[torch.Tensor] = None):
     """n problems of one size in every launch of the chain.  ``A``: [n, K, K] fp32 (flipped damped Hessians, destroyed)
     -- or any tensor whose [b] slices are contiguous K x K matrices at a uniform stride -- ``U`` likewise (written).
-    Returns info int32[n] (device).  Bit-identical per problem to ``cholesky_inverse_upper``."""
+    Returns info int32[n] (device).  Bit-identical per problem to ``cholesky_inverse_upper``.  ``min_eig_lb``: fp32[n]
+    on the device, as in ``cholesky_inverse_upper``."""
     lib = load()
     _req(A, torch.float32, "A", 3)
     _req(U, torch.float32, "U", 3)
@@ -293,6 +318,12 @@ def cholesky_inverse_upper_batched(A: torch.Tensor, U: torch.Tensor):
             raise ValueError(f"{name}: every [b] slice must be a contiguous K x K matrix at a stride that is a multiple of 4")
     info = torch.zeros(n, dtype=torch.int32, device=A.device)
     ws = workspace(lib.qt_cholesky_inverse_upper_batched_workspace_bytes(K, n), A.device, "chol")
+    if min_eig_lb is not None:
+        lb = _min_eig_lb(min_eig_lb, n, A.device)
+        check("qt_cholesky_inverse_upper_batched_bounded", lib.qt_cholesky_inverse_upper_batched_bounded(
+            A.data_ptr(), A.stride(0) if n > 1 else K * K, K, U.data_ptr(), U.stride(0) if n > 1 else K * K,
+            info.data_ptr(), n, lb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return info
     check("qt_cholesky_inverse_upper_batched", lib.qt_cholesky_inverse_upper_batched(
         A.data_ptr(), A.stride(0) if n > 1 else K * K, K, U.data_ptr(), U.stride(0) if n > 1 else K * K, info.data_ptr(), n,
         ws.data_ptr(), ws.numel(), _stream()))
@@ -1249,6 +1280,37 @@ def gemm3_tn_ex(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, kind: int = 0
     check("qt_gemm3_tn_f32_ex", lib.qt_gemm3_tn_f32_ex(A.data_ptr(), M, B.data_ptr(), N, C3.data_ptr(), N, M, N, k, kind,
                                                        int(tri), int(tight), n, k * M, k * N, M * N, ws.data_ptr(),
                                                        ws.numel(), _stream()))
+    return C
+
+
+def gemm3_tn_f16x2(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, bound_a, bound_b, kind: int = 0,
+                   tri: bool = False, tight: bool = False):
+    """``gemm3_tn_ex`` on two fp16 planes per operand and three plane products.  ``bound_a`` / ``bound_b``: a float, or
+    one per problem of a batch, with |A_b| <= bound_a[b] and |B_b| <= bound_b[b] elementwise (host values)."""
+    import ctypes
+
+    lib = load()
+    if A.dim() == 2:
+        A, B, C3 = A[None], B[None], C[None]
+    else:
+        C3 = C
+    _req(A, torch.float32, "A", 3)
+    _req(B, torch.float32, "B", 3)
+    _req(C3, torch.float32, "C", 3)
+    n, k, M = A.shape
+    n2, k2, N = B.shape
+    assert n == n2 and k == k2 and tuple(C3.shape) == (n, M, N)
+    # every [b] slice a contiguous matrix; the batch stride may be padded (a multiple of 4 elements)
+    for t, cols in ((A, M), (B, N), (C3, N)):
+        assert t.stride(2) == 1 and t.stride(1) == cols and (n == 1 or (t.stride(0) >= t.shape[1] * cols and t.stride(0) % 4 == 0))
+    ba = [float(bound_a)] * n if not hasattr(bound_a, "__len__") else [float(x) for x in bound_a]
+    bb = [float(bound_b)] * n if not hasattr(bound_b, "__len__") else [float(x) for x in bound_b]
+    assert len(ba) == n and len(bb) == n
+    ba_c, bb_c = (ctypes.c_float * n)(*ba), (ctypes.c_float * n)(*bb)
+    ws = workspace(n * lib.qt_gemm3_tn_f32_workspace_bytes(M, N, k), A.device, "gemm3")
+    check("qt_gemm3_tn_f16x2", lib.qt_gemm3_tn_f16x2(
+        A.data_ptr(), M, B.data_ptr(), N, C3.data_ptr(), N, M, N, k, kind, int(tri), int(tight), n, A.stride(0), B.stride(0),
+        C3.stride(0), ctypes.cast(ba_c, ctypes.c_void_p), ctypes.cast(bb_c, ctypes.c_void_p), ws.data_ptr(), ws.numel(), _stream()))
     return C
 
 

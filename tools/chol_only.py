@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Cholesky-inverse chain alone (for rocprofv3 per-kernel breakdowns)."""
+"""Cholesky-inverse chain alone (for rocprofv3 per-kernel breakdowns).  The bound on lambda_min is passed, so
+QT_CHOL_PLANES=bf16x3|f16x2 selects the plane mode of the block-row products."""
 import sys
 from pathlib import Path
 
@@ -16,11 +17,13 @@ X = torch.randn(2 * K, K, device=dev).to(torch.bfloat16)
 G = torch.zeros(K, K, device=dev)
 ops.xtx_accumulate(X, G)
 for _ in range(reps):
-    A, dead, _ = ops.hessian_prepare(G, 8, 0.01, None)
+    damp = torch.zeros(1, dtype=torch.float32, device=dev)
+    A, dead, _ = ops.hessian_prepare(G, 8, 0.01, None, damp_out=damp)
+    lb = damp * 0.5
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    U, info = ops.cholesky_inverse_upper(A)
+    U, info = ops.cholesky_inverse_upper(A, min_eig_lb=lb)
     e1.record()
     torch.cuda.synchronize()
     print(f"K={K} chol {e0.elapsed_time(e1):.2f} ms info={int(info.item())}", flush=True)
