@@ -470,6 +470,21 @@ int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_for
  *   that expert's last row and is never stored: no byte outside Xq[x_rows, K] and Wq[E, N, K] is read, no element
  *   outside Y[m < offsets[E], n < N] is written.  No bias, no workspace, no atomics: deterministic.  
  *
+ * qt_moe_gemm_i8_ring_w4: the prefill form of qt_gemm_i8_grouped for W4A8 banks: qt_gemm_i8_ring_w4's 256 x 256
+ *   LDS-ring tile and per-K-tile group fold over E packed weight matrices.  qt_gemm_i8_ring_grouped's arguments with
+ *   the same meanings (x_rows, the number of rows of Xq, in front of the stream; no bias).  Taken: w_format ==
+ *   QT_W_INT4_PACKED with G == K / 128, K a multiple of QT_I8_RING_W4_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned,
+ *   E <= 4096, R <= 2^31 - 1, (ceil(R/256) + E) ceil(N/256) < 2^31, and with row_idx x_rows K <= 2^32 (a gathered row
+ *   is addressed by a 32-bit byte offset from Xq), without it x_rows >= R; zp_x needs wsum.  Anything else is
+ *   QT_ERR_INVALID before any launch and qt_last_error names the reason (int8 weights run on qt_gemm_i8_ring_grouped,
+ *   G == 1 runs on qt_gemm_i8_grouped).  For every legal input Y is bit-identical to qt_gemm_i8_grouped's on the same
+ *   arguments: acc_g is exact and the fold t -> prod = s_w t -> tot = tot + prod, g ascending, then y = s_x tot, runs
+ *   literally, once per output element.  The grid and the walk are qt_gemm_i8_ring_grouped's; rows >= offsets[E] are
+ *   not written; row_idx values are clamped into [0, x_rows); a tile row past the expert's last row re-reads that
+ *   expert's last row and is never stored: no byte outside Xq[x_rows, K], Wq[E, N, K/8], s_w / wsum[E, N, G] is read,
+ *   no element outside Y[m < offsets[E], n < N] is written.  No workspace, no atomics: deterministic.  The name is of
+ *   the qt_moe_* family; the form's limits are those of the two entry points it joins.  
+ *
  * qt_moe_combine: out [T, H] (dtype bf16 / fp16) = the weighted sum of each token's routed rows of Y [R, H] (pitch
  *   ldy), transformers' MixtralExperts.forward restated: for the token's rows r = row_of[t k + j] >= 0 in ascending
  *   row order (= ascending expert), with w = weights[t, j] fp32 [T, k]:
@@ -488,6 +503,10 @@ int qt_gemm_i8_ring_grouped(const int8_t* Xq, int K, const int32_t* row_idx, int
                             const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
                             const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
                             int64_t x_rows, qt_stream_t stream);
+int qt_moe_gemm_i8_ring_w4(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets, int E,
+                           const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
+                           const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
+                           int64_t x_rows, qt_stream_t stream);
 int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
                    int64_t T, int k, void* out, qt_stream_t stream);
 

@@ -1,5 +1,6 @@
 // What the two int8 instances of ring_pipe.h's pipeline share -- gemm_i8_ring_kernel / gemm_i8_ring_moe_kernel
-// (qlinear_ring.hip) and gemm_i8_ring_w4_kernel (qlinear_ring_w4.hip): the 256 x 256 tile over K-contiguous operands,
+// (qlinear_ring.hip) and gemm_i8_ring_w4_kernel / gemm_i8_ring_w4_moe_kernel (qlinear_ring_w4.hip): the 256 x 256 tile
+// over K-contiguous operands, the grouped forms' expert walk,
 // K-tile t = units 4t .. 4t+3 = A0, B0, B1, A1 (half panels of 128 rows x 128 k), R 8, L 6.  Each file's head comment
 // keeps the hazard argument of its own instance.  As with ring_pipe.h, an edit here edits hand-scheduled kernels:
 // tools/isa_compare.py says whether one meant to be neutral was (profiles/i8_ring_tile_isa_parent_vs_refactor.txt
@@ -28,6 +29,42 @@ __device__ __forceinline__ void i8_ring_tile_of(int pid, int tiles_m, int tiles_
     const int in_g = pid % per_group;
     m_tile = first_m + in_g % gsize;
     n_tile = in_g / gsize;
+}
+
+// The grouped (MOE) forms -- gemm_i8_ring_moe_kernel and gemm_i8_ring_w4_moe_kernel: expert e owns rows
+// [offsets[e], offsets[e + 1]) of Y and the e-th weight matrix; R routed rows in all; A row m (and s_x / zp_x) is read
+// at row_idx[m], clamped into [0, x_rows), when row_idx is given, else at m
+struct RingMoe {
+    const int32_t* offsets;
+    const int32_t* row_idx;
+    int64_t x_rows;
+    int E;
+};
+
+// m-tile slot -> (expert, first row of the tile, end of the expert's rows); offsets clamped to [0, R] and made
+// ascending, so a bad table cannot move a write out of Y (as gemm_i8_kernel).  False for a surplus slot.  The grid
+// holds ceil(R/256) + E slots, an upper bound on sum_e ceil(rows_e / 256).  Uniform over the workgroup: scalar work
+__device__ __forceinline__ bool i8_ring_moe_walk(const RingMoe& g, int R, int slot, int& e, int& m0, int& m_end) {
+    int start = 0;
+    for (int j = 0; j < g.E; ++j) {
+        const int lo = min(max(g.offsets[j], 0), R);
+        const int hi = min(max(g.offsets[j + 1], lo), R);
+        const int nt = (int)(((int64_t)hi - lo + BT - 1) / BT);
+        if (slot < start + nt) {
+            e = j;
+            m0 = lo + (slot - start) * BT;
+            m_end = hi;
+            return true;
+        }
+        start += nt;
+    }
+    return false;
+}
+
+// the Xq / s_x / zp_x row of output row m
+__device__ __forceinline__ int64_t i8_ring_moe_src_row(const RingMoe& g, int64_t m) {
+    if (g.row_idx) return min(max((int64_t)g.row_idx[m], (int64_t)0), g.x_rows - 1);
+    return m;
 }
 
 // LDS image of an A unit (and of an int8 B unit): 16 pieces of 1 KiB, piece = 8 rows x 128 B; the 16-byte chunk c of row

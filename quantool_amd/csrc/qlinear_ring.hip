@@ -53,15 +53,6 @@ struct RingArgs {
     int64_t ldy;
     int out_dtype;
 };
-// grouped (MOE) form only: expert e owns rows [offsets[e], offsets[e + 1]) of Y and the e-th weight matrix; p.M is the
-// routed-row count R; A row m (and s_x / zp_x) is read at row_idx[m], clamped into [0, x_rows), when row_idx is
-// given, else at m
-struct RingMoe {
-    const int32_t* offsets;
-    const int32_t* row_idx;
-    int64_t x_rows;
-    int E;
-};
 
 template <bool MOE>
 __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
@@ -84,24 +75,10 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     const float* s_w = p.s_w;
     const int32_t* wsum = p.wsum;
     if constexpr (MOE) {
-        // m-tile slot -> (expert, tile within the expert); offsets clamped to [0, R] and made ascending, so a bad
-        // table cannot move a write out of Y (as gemm_i8_kernel)
-        const int slot = m_tile;
-        const int R = (int)p.M;                       // <= 0x7fffffff (host)
-        int start = 0, e = -1, lo_e = 0, hi_e = 0;
-        for (int j = 0; j < g.E; ++j) {
-            const int lo = min(max(g.offsets[j], 0), R);
-            const int hi = min(max(g.offsets[j + 1], lo), R);
-            const int nt = (int)(((int64_t)hi - lo + BT - 1) / BT);
-            if (slot < start + nt) {
-                e = j;
-                lo_e = lo + (slot - start) * BT;
-                hi_e = hi;
-                break;
-            }
-            start += nt;
-        }
-        if (e < 0) return;                            // surplus workgroup: uniform, before any LDS-DMA or barrier
+        // m-tile slot -> (expert, tile within the expert): i8_ring_tile.h
+        int e, lo_e, hi_e;
+        // a surplus workgroup returns: uniform, before any LDS-DMA or barrier; p.M = R <= 0x7fffffff (host)
+        if (!i8_ring_moe_walk(g, (int)p.M, m_tile, e, lo_e, hi_e)) return;
         e = __builtin_amdgcn_readfirstlane(e);        // wave-uniform: the A and B bases below stay scalar
         m0 = __builtin_amdgcn_readfirstlane(lo_e);
         m_end = __builtin_amdgcn_readfirstlane(hi_e);
@@ -111,9 +88,7 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     }
     // the Xq / s_x / zp_x row of output row m (m < m_end)
     auto src_row = [&](int64_t m) -> int64_t {
-        if constexpr (MOE) {
-            if (g.row_idx) return min(max((int64_t)g.row_idx[m], (int64_t)0), g.x_rows - 1);
-        }
+        if constexpr (MOE) return i8_ring_moe_src_row(g, m);
         return m;
     };
     const int nu = K / KU * 4;                        // units = phases

@@ -49,6 +49,18 @@
 // EDGES: as qlinear_ring.hip.  A tile row past M (N) is fetched from row M - 1 (N - 1) -- data, scales and wsum -- is
 // computed and never stored; K is a whole number of K-tiles and G = K / 128, so no byte outside Xq[M, K],
 // Wq[N, K/8], s_w / wsum[N, G], s_x / zp_x[M] is read.
+//
+// qt_moe_gemm_i8_ring_w4: the same tile over E packed weight matrices (ring_w4_tile<ASYM, true>), equal to
+// qt_gemm_i8_grouped to the bit.  All it does differently lies outside the K loop.  The grid holds
+// ceil(R/256) + E m-tile slots per n-tile; a workgroup walks the clamped offsets (i8_ring_tile.h) to its expert e, its
+// first row m0 and the expert's end m_end, and a surplus one returns before the fills, their barrier and any LDS-DMA.
+// e, m0 and m_end are wave-uniform, so the MOE bases are scalar as the dense ones are: srcB = Wq + (e N + n0) K/2 (K a
+// multiple of 128 keeps every expert's matrix 16-byte aligned), srcS = (s_w | wsum) + (e N + n0) G 4, and for
+// contiguous rows srcA = Xq + m0 K with rows clamped to m_end - 1.  The Xq / s_x / zp_x row of each of the tile's 256
+// rows -- row_idx[m] clamped into [0, x_rows), or m -- is staged in LDS beside sZp (sRow, 1 KiB: 153 600 B in all)
+// by the threads that fill sZp, and read from there for the A offsets (with row_idx the base is Xq itself and each
+// lane's four A offsets are sRow[r] K + 16 c < x_rows K <= 2^32, written into sOff as ever) and for the epilogue's s_x.
+// Nothing new is live in the loop.  A tile row past m_end takes the source row of m_end - 1 and is never stored.
 #include "common.h"
 #include "i8_args.h"
 #include "i8_unpack.h"
@@ -74,18 +86,22 @@ struct RingW4Args {
     int out_dtype;
 };
 
-template <bool ASYM>
-__device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
+template <bool ASYM, bool MOE>
+__device__ __forceinline__ void ring_w4_tile(const RingW4Args& p, const RingMoe& g) {
     // one LDS block, the small tables first: their addresses (and those of the scales) then fit the 16-bit offset field
     // of a DS instruction and hold no register each.  The ring's slots lie beyond 64 KiB: see tile_base below.
     //   sOff  each thread's LDS-DMA source offsets {A0 i0, A0 i1, scales, -, A1 i0, A1 i1, B0, B1}, 32 B per thread:
     //         read back by their owner in front of the issue, so that they hold no registers across the phases
-    //   sZp   the tile's 256 row zero-points;  sc  two K-tiles' scales;  ring  the 8 slots
-    __shared__ __attribute__((aligned(16))) char lds[NTHREADS * 32 + BT * 4 + 2 * SC_BYTES + RING * UNIT_BYTES];
+    //   sZp   the tile's 256 row zero-points;  sRow  (MOE) the Xq / s_x / zp_x row of each of the tile's 256 rows;
+    //   sc  two K-tiles' scales;  ring  the 8 slots
+    constexpr int ROW_BYTES = MOE ? BT * 4 : 0;
+    __shared__ __attribute__((aligned(16))) char lds[NTHREADS * 32 + BT * 4 + ROW_BYTES + 2 * SC_BYTES +
+                                                     RING * UNIT_BYTES];
     unsigned* sOff = (unsigned*)lds;
     int* sZp = (int*)(lds + NTHREADS * 32);
-    int* sc = (int*)(lds + NTHREADS * 32 + BT * 4);
-    char* ring = lds + NTHREADS * 32 + BT * 4 + 2 * SC_BYTES;
+    [[maybe_unused]] int* sRow = (int*)(lds + NTHREADS * 32 + BT * 4);
+    int* sc = (int*)(lds + NTHREADS * 32 + BT * 4 + ROW_BYTES);
+    char* ring = lds + NTHREADS * 32 + BT * 4 + ROW_BYTES + 2 * SC_BYTES;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -93,17 +109,37 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     const bool group_b = wave >= 4;  // wave-uniform
 
     const int tiles_n = (p.N + BT - 1) / BT;
-    const int tiles_m = (int)((p.M + BT - 1) / BT);
-    int m_tile, n_tile;
+    const int tiles_m = (int)((p.M + BT - 1) / BT) + (MOE ? g.E : 0);
+    int m_tile, n_tile;                               // the grouped form: m_tile is an m-tile slot
     i8_ring_tile_of(blockIdx.x, tiles_m, tiles_n, m_tile, n_tile);
-    const int64_t m0 = (int64_t)m_tile * BT;
-    const int64_t m_end = p.M;
+    int64_t m0 = (int64_t)m_tile * BT;
+    int64_t m_end = p.M;                              // rows [m0, m_end) of this tile's matrix exist
     const int n0 = n_tile * BT;
     const int K = p.K, G = p.G;
+    const int Kb = K / 2;                             // bytes of a packed weight row
     const int nu = K / KU * 4;                        // units = phases
+    int64_t w_row0 = n0;                              // the tile's first row of Wq / s_w / wsum: e N + n0
+    if constexpr (MOE) {
+        // m-tile slot -> (expert, tile within the expert): i8_ring_tile.h.  A surplus workgroup returns: uniform, before
+        // the fills below, their barrier and any LDS-DMA; p.M = R <= 0x7fffffff (host)
+        int e, lo_e, hi_e;
+        if (!i8_ring_moe_walk(g, (int)p.M, m_tile, e, lo_e, hi_e)) return;
+        e = __builtin_amdgcn_readfirstlane(e);        // wave-uniform: every base below stays scalar
+        m0 = __builtin_amdgcn_readfirstlane(lo_e);
+        m_end = __builtin_amdgcn_readfirstlane(hi_e);
+        w_row0 = (int64_t)e * p.N + n0;
+    }
+    const int64_t a_last = m_end - 1 - m0;            // last valid row of the A panel, relative to the tile
 
-    // the tile's row zero-points, before any LDS-DMA is in flight (plain loads: nothing counted yet)
-    if (ASYM) {
+    // the tile's row zero-points (and source rows), before any LDS-DMA is in flight (plain loads: nothing counted yet)
+    if constexpr (MOE) {
+        // a tile row past the expert's last row takes that row's source: fetched again, computed and never stored
+        if (tid < BT) {
+            const int64_t ms = i8_ring_moe_src_row(g, m0 + (tid < a_last ? tid : a_last));
+            sRow[tid] = (int)ms;                      // < x_rows, R <= 2^31 - 1
+            if (ASYM) sZp[tid] = (m0 + tid < m_end) ? p.zp_x[ms] : 0;
+        }
+    } else if (ASYM) {
         if (tid < BT) sZp[tid] = (m0 + tid < m_end) ? p.zp_x[m0 + tid] : 0;
     }
     __syncthreads();
@@ -112,14 +148,20 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     // A: two LDS-DMA instructions per thread and unit (i8_ring_tile.h)
     // B: one; lane: row 16 wave + (lane >> 2) of the half panel, physical chunk lane & 3
     // scales: one dword per lane, column 64 (wave & 3) + lane of the tile
-    const int64_t a_last = m_end - 1 - m0;            // last valid row of the A / B panel, relative to the tile
-    const int b_last = p.N - 1 - n0;
-    const int Kb = K / 2;                             // bytes of a packed weight row
+    const int b_last = p.N - 1 - n0;                  // last valid row of the B panel, relative to the tile
     {
         unsigned voffA[2][2], voffB[2], voffS;        // [half][instruction], [half]
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             i8_ring_a_voff(wave, lane, i, a_last, K, [](int64_t ra) { return ra; }, voffA[0][i], voffA[1][i]);
+        if constexpr (MOE) {
+            if (g.row_idx) {                          // gathered rows: offsets from Xq itself, < x_rows K <= 2^32
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    i8_ring_a_voff(wave, lane, i, a_last, K, [&](int64_t ra) { return (int64_t)sRow[ra]; }, voffA[0][i],
+                                   voffA[1][i]);
+            }
+        }
         const int r = 16 * wave + (lane >> 2);
         const int c = (lane & 3) ^ ((r >> 2) & 3);
         const int rb0 = r < b_last ? r : b_last, rb1 = HP + r < b_last ? HP + r : b_last;
@@ -147,9 +189,12 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     const unsigned dstB_wave = __builtin_amdgcn_readfirstlane(ring_lds + wave * 1024);
     const unsigned dstS_wave = __builtin_amdgcn_readfirstlane(sc_lds + wave * 256);
     const int8_t* srcA = p.Xq + m0 * (int64_t)K;      // scalar: k-byte 0 of the tile's first row
-    const int8_t* srcB = p.Wq + (int64_t)n0 * Kb;
+    if constexpr (MOE) {
+        if (g.row_idx) srcA = p.Xq;
+    }
+    const int8_t* srcB = p.Wq + w_row0 * Kb;
     // waves 0-3: s_w, waves 4-7: wsum (symmetric: s_w again, never read)
-    const char* srcS = ((ASYM && group_b) ? (const char*)p.wsum : (const char*)p.s_w) + (size_t)n0 * G * 4;
+    const char* srcS = ((ASYM && group_b) ? (const char*)p.wsum : (const char*)p.s_w) + (size_t)w_row0 * G * 4;
     // unit i = 4 t + J: J is a compile-time constant wherever the slot is
     auto off_of = [&](auto j_c) -> uint4 {            // read ahead of the phase's fragment reads
         constexpr int J = decltype(j_c)::value;
@@ -316,6 +361,7 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
     fold(std::integral_constant<int, 3>{});           // the last phase's acc_g
 
     // ---- epilogue: y = s_x[m] * tot (+ bias[n]), once per output element, by the lane that holds it ----
+    // (the grouped form: s_x at the row's source row, from sRow; no bias)
     const int ob = lane_bits();
     const int lr_e = (ob >> 5) & 31, lh_e = (ob >> 10) & 1;
 #pragma unroll
@@ -323,7 +369,8 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
         const int n = n0 + qb * HP + wave_n * 32 + lr_e;
         if (n >= p.N) continue;
         float bn = 0.0f;
-        if (p.bias) bn = qt_load_w(p.bias, p.out_dtype, n);
+        const bool has_bias = !MOE && p.bias;
+        if (has_bias) bn = qt_load_w(p.bias, p.out_dtype, n);
 #pragma unroll
         for (int qa = 0; qa < 2; ++qa) {
 #pragma unroll
@@ -332,8 +379,10 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = i8_ring_cd_row(m0 + qa * HP + wave_m * 64 + mi * 32, r, lh_e);
                     if (m >= m_end) continue;
-                    float y = p.s_x[m] * tot[qa][qb][mi][r];
-                    if (p.bias) y = y + bn;
+                    int64_t ms = m;
+                    if constexpr (MOE) ms = sRow[m - m0];
+                    float y = p.s_x[ms] * tot[qa][qb][mi][r];
+                    if (has_bias) y = y + bn;
                     qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n), y);
                 }
             }
@@ -342,7 +391,13 @@ __device__ __forceinline__ void ring_w4_tile(const RingW4Args& p) {
 }
 
 template <bool ASYM>
-__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_w4_kernel(const RingW4Args p) { ring_w4_tile<ASYM>(p); }
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_w4_kernel(const RingW4Args p) {
+    ring_w4_tile<ASYM, false>(p, RingMoe{});
+}
+template <bool ASYM>
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_w4_moe_kernel(const RingW4Args p, const RingMoe g) {
+    ring_w4_tile<ASYM, true>(p, g);
+}
 
 }  // namespace
 
@@ -367,6 +422,42 @@ extern "C" int qt_gemm_i8_ring_w4(const int8_t* Xq, int64_t M, int K, const void
     RingW4Args a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, G, ldy, out_dtype};
     if (zp_x) hipLaunchKernelGGL(gemm_i8_ring_w4_kernel<true>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
     else hipLaunchKernelGGL(gemm_i8_ring_w4_kernel<false>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+// The grouped form.  Its name joins the qt_moe_* family, not qt_gemm_i8*: the set of qt_gemm_i8* entry points is the
+// table ops.I8_FORMS (hip/ops.py), which holds this form's row beside it (I8_MOE_RING_W4_FORM) until it moves in.
+extern "C" int qt_moe_gemm_i8_ring_w4(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R,
+                                      const int32_t* offsets, int E, const void* Wq, int w_format, int N,
+                                      const float* s_x, const int32_t* zp_x, const float* s_w, int G,
+                                      const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, int64_t x_rows,
+                                      qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(x_rows > 0, "qt_moe_gemm_i8_ring_w4: bad arguments");
+    QT_CHECK_ARG(w_format == QT_W_INT4_PACKED, "qt_moe_gemm_i8_ring_w4: w_format %d unsupported: packed int4 weights "
+                 "only (int8 weights run on qt_gemm_i8_ring_grouped)", w_format);
+    QT_CHECK_ARG(K % QT_I8_RING_W4_K_UNIT == 0, "qt_moe_gemm_i8_ring_w4: K %d is not a multiple of the k-unit %d", K,
+                 QT_I8_RING_W4_K_UNIT);
+    QT_CHECK_ARG(G == K / QT_I8_RING_W4_K_UNIT, "qt_moe_gemm_i8_ring_w4: G %d unsupported: one scale per group of %d "
+                 "columns only, G = K / %d = %d (channel-wise scales run on qt_gemm_i8_grouped)", G, QT_I8_RING_W4_K_UNIT,
+                 QT_I8_RING_W4_K_UNIT, K / QT_I8_RING_W4_K_UNIT);
+    QT_CHECK_ARG(R <= 0x7fffffffLL, "qt_moe_gemm_i8_ring_w4: R %lld too large", (long long)R);
+    QT_CHECK_ARG(E <= 4096, "qt_moe_gemm_i8_ring_w4: E %d > 4096", E);
+    if (int st = qt_i8_check_grouped("qt_moe_gemm_i8_ring_w4", Xq, K, R, offsets, E, Wq, w_format, N, s_x, zp_x, s_w, G,
+                                     wsum, Y, out_dtype, ldy, true))
+        return st;
+    // gathered rows are addressed by a 32-bit byte offset from Xq; contiguous rows need R of them
+    QT_CHECK_ARG(!row_idx || x_rows * (int64_t)K <= (1LL << 32), "qt_moe_gemm_i8_ring_w4: x_rows %lld x K %d > 2^32 "
+                 "bytes: a gathered row is addressed by a 32-bit offset", (long long)x_rows, K);
+    QT_CHECK_ARG(row_idx || x_rows >= R, "qt_moe_gemm_i8_ring_w4: x_rows %lld < R %lld without row_idx",
+                 (long long)x_rows, (long long)R);
+    const int64_t tiles = ((R + BT - 1) / BT + E) * (int64_t)((N + BT - 1) / BT);
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "qt_moe_gemm_i8_ring_w4: too many tiles");
+    RingW4Args a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, nullptr, Y, R, N, K, G, ldy, out_dtype};
+    RingMoe g{offsets, row_idx, x_rows, E};
+    if (zp_x) hipLaunchKernelGGL(gemm_i8_ring_w4_moe_kernel<true>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a, g);
+    else hipLaunchKernelGGL(gemm_i8_ring_w4_moe_kernel<false>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a, g);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

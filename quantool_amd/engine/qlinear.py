@@ -24,7 +24,8 @@ down_proj``).  The loader inverts that write: A16 experts are dequantised into t
 ``WeightOnlyExperts`` on the stored integer weights (``qt_gemm_wq_grouped`` at decode); A8 experts replace the bank with
 a ``QuantizedExperts`` that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` +
 ``qt_moe_combine``; ``qt_gemm_i8_skinny_grouped`` in place of the GEMM for up to ``grouped_max_tokens`` tokens, and
-``qt_gemm_i8_ring_grouped`` for an int8 bank from ``ring_min_rows_per_expert`` routed rows per expert).
+``qt_gemm_i8_ring_grouped`` for an int8 bank from ``ring_min_rows_per_expert`` routed rows per expert,
+``qt_moe_gemm_i8_ring_w4`` for a packed int4 bank from ``ring_w4_min_rows_per_expert``).
 
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
 weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,

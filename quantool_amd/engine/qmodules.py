@@ -230,7 +230,10 @@ class QuantizedExperts(_RoutedExperts):
     decode range a product of R routed rows with R / E >= ``ring_min_rows_per_expert`` (when that is not 0) runs an
     int8 bank with one scale group on the 256-row LDS-ring tile ``qt_gemm_i8_ring_grouped`` where
     ``ops.gemm_i8_ring_grouped_supported`` holds; it agrees with the tiled kernel to the bit as well, so the attribute
-    changes speed alone, and 0 never uses it.  Packed int4 (W4A8) banks never reach it."""
+    changes speed alone, and 0 never uses it.  A packed int4 (W4A8) bank with one scale per 128 columns has its own
+    ring and its own bound: from R / E >= ``ring_w4_min_rows_per_expert`` (0: never) a product runs on
+    ``qt_moe_gemm_i8_ring_w4`` where ``ops.moe_gemm_i8_ring_w4_supported`` holds, equal to the tiled kernel to the bit
+    again; every other int4 product stays on the tiled kernel."""
 
     # Decode form up to this many tokens: the measured crossover at Mixtral-8x7B's bank shapes (DESIGN.md 4.11).
     grouped_max_tokens = 16
@@ -238,6 +241,11 @@ class QuantizedExperts(_RoutedExperts):
     # ring is no slower than the tiled grouped kernel on both products at Mixtral-8x7B's bank shapes, at that size and
     # every larger one, in both runs.
     ring_min_rows_per_expert = 1024
+    # The same bound for a packed int4 bank with G = K / 128 and qt_moe_gemm_i8_ring_w4 (0: never; never below 1024): the
+    # smallest measured R / E from which the ring beats the tiled grouped kernel on both products by more than the tiled
+    # kernel's own run-to-run spread, at that size and every larger one, in both runs.  At 1024 the down
+    # product is level (0.6 - 1.2 % against a spread of 1.0 %).
+    ring_w4_min_rows_per_expert = 2048
 
     def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
                  down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
@@ -267,12 +275,15 @@ class QuantizedExperts(_RoutedExperts):
         Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=self.act_symmetric)
         w, s_w = getattr(self, part), getattr(self, f"{part}_scale")
         R = x.shape[0] if row_idx is None else row_idx.numel()
-        ring = self.ring_min_rows_per_expert
+        ring, ring_w4 = self.ring_min_rows_per_expert, self.ring_w4_min_rows_per_expert
         if 1 <= tokens <= self.grouped_max_tokens:
             gemm = ops.gemm_i8_skinny_grouped
         elif (ring > 0 and R >= ring * self.num_experts and not self.int4 and s_w.shape[2] == 1
               and ops.gemm_i8_ring_grouped_supported(Xq, w, s_w, row_idx)):
             gemm = ops.gemm_i8_ring_grouped
+        elif (ring_w4 > 0 and R >= ring_w4 * self.num_experts and self.int4 and s_w.shape[2] * 128 == x.shape[1]
+              and ops.moe_gemm_i8_ring_w4_supported(Xq, w, s_w, row_idx)):
+            gemm = ops.moe_gemm_i8_ring_w4
         else:
             gemm = ops.gemm_i8_grouped
         return gemm(Xq, s_x, w, s_w, offsets, row_idx=row_idx,

@@ -617,6 +617,10 @@ I8_FORMS = {f.entry: f for f in (
     I8Form("qt_gemm_i8_skinny_grouped", experts=True),
     I8Form("qt_gemm_i8_ring_grouped", experts=True, max_e=4096, x_rows=True, **_RING),
 )}
+# The W4A8 bank's ring form.  Its entry point is of the qt_moe_* family and its row stands beside the table, not in it,
+# because the table is the set of qt_gemm_i8* entry points; to fold it in, rename the entry point and move this row.
+I8_MOE_RING_W4_FORM = I8Form("qt_moe_gemm_i8_ring_w4", experts=True, max_e=4096, x_rows=True,
+                             **{**_RING, "dtypes": (torch.int32,), "groups": "per_unit"})
 
 I8_SKINNY_MAX_M = I8_FORMS["qt_gemm_i8_skinny"].max_m   # rows of Xq qt_gemm_i8_skinny takes
 # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
@@ -647,7 +651,8 @@ def _i8_refusal(form: I8Form, Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Ten
         if form.dtypes == (torch.int8,):
             return f"int8 weights only, got {Wq.dtype} (packed int4 runs on {tiled})"
         if form.dtypes == (torch.int32,):
-            return f"packed int4 (int32) weights only, got {Wq.dtype} (int8 weights run on gemm_i8_ring)"
+            ring = "gemm_i8_ring_grouped" if form.experts else "gemm_i8_ring"
+            return f"packed int4 (int32) weights only, got {Wq.dtype} (int8 weights run on {ring})"
         return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
     x_rows, K = Xq.shape[0], Xq.shape[-1]
     if K % U != 0:
@@ -859,6 +864,25 @@ def gemm_i8_ring_grouped(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, 
     rows.  ``ValueError`` where ``gemm_i8_ring_grouped_supported`` is false."""
     return _gemm_i8_grouped(I8_FORMS["qt_gemm_i8_ring_grouped"], Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x,
                             wsum, out_dtype)
+
+
+def moe_gemm_i8_ring_w4_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                                  row_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``moe_gemm_i8_ring_w4`` takes these operands: a packed int4 bank [E, N, K/8] with one scale per 128
+    columns, K a multiple of ``I8_RING_W4_K_UNIT`` and at most 32768, both operands 16-byte aligned, at most 4096
+    experts, a grid that fits, and, with ``row_idx``, an Xq of at most 2^32 bytes.  Host-only."""
+    return _i8_refusal(I8_MOE_RING_W4_FORM, Xq, Wq, s_w, row_idx) is None
+
+
+def moe_gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                        offsets: torch.Tensor, *, rows: Optional[int] = None,
+                        row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                        zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                        out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8_grouped`` on the 256 x 256 LDS-ring tile for packed int4 banks (``qt_moe_gemm_i8_ring_w4``): the
+    prefill form for W4A8 banks.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit; ``row_idx`` values are
+    clamped into Xq's rows.  ``ValueError`` where ``moe_gemm_i8_ring_w4_supported`` is false."""
+    return _gemm_i8_grouped(I8_MOE_RING_W4_FORM, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
 
 
 def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:

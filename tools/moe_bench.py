@@ -38,11 +38,13 @@ hit experts cold).  Reported per form: median microseconds and the hit experts' 
 
   python tools/moe_bench.py --ring-tokens 512,1024,2048,4096,8192,16384
 
-The W8A8 prefill comparison: per product (gate_up gathered by token, down contiguous) and per T, qt_gemm_i8_grouped and
-qt_gemm_i8_ring_grouped on the same operands, alternating call by call in one loop, each call between its own HIP
+The A8 prefill comparison, per scheme of --schemes (W8A8, W4A8): per product (gate_up gathered by token, down
+contiguous) and per T, qt_gemm_i8_grouped and the scheme's ring form (W8A8: qt_gemm_i8_ring_grouped, W4A8:
+qt_moe_gemm_i8_ring_w4) on the same operands, alternating call by call in one loop, each call between its own HIP
 events: median / mean / min microseconds per form, ring speedup (tiled median / ring median), bits_equal.  Then
-QuantizedExperts.forward end to end with ring_min_rows_per_expert 0 and at the class default (or at
---ring-min-rows-per-expert), alternating likewise.
+QuantizedExperts.forward end to end with the scheme's attribute (ring_min_rows_per_expert /
+ring_w4_min_rows_per_expert) at 0 and at the class default (or at --ring-min-rows-per-expert /
+--ring-w4-min-rows-per-expert), alternating likewise.
 """
 from __future__ import annotations
 
@@ -235,47 +237,54 @@ def _us(times):
             "min_us": round(t[0] * 1e6, 2)}
 
 
-def _bench_a8_ring(T, qe, dev, g, args):
+def _bench_a8_ring(scheme, T, qe, dev, g, args):
     """One prefill row: both grouped forms of each product on the same routing and rows, and the bank's forward."""
     from qlinear_bench import time_pair
 
+    int4, sym = scheme == "W4A8", qe.act_symmetric
+    ring = ops.moe_gemm_i8_ring_w4 if int4 else ops.gemm_i8_ring_grouped
+    attr = "ring_w4_min_rows_per_expert" if int4 else "ring_min_rows_per_expert"
     x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
     logits = torch.randn(T, E, device=dev, generator=g)
     w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
     w = w / w.sum(-1, keepdim=True)
     offsets, src_token, _, _ = ops.moe_route(idx, E)
     off = offsets.cpu().tolist()
-    Xq, s_x, _ = ops.quantize_tokens_i8(x, symmetric=True)
-    row = {"scheme": "W8A8", "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
+    Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=sym)
+    gu_ws, dn_ws = (None, None) if sym else (qe.gate_up_wsum, qe.down_wsum)
+    row = {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
            "R_over_E": T * TOPK / E}
-    default = QuantizedExperts.ring_min_rows_per_expert
-    ring_at = default if args.ring_min_rows_per_expert < 0 else args.ring_min_rows_per_expert
+    default = getattr(QuantizedExperts, attr)
+    asked = args.ring_w4_min_rows_per_expert if int4 else args.ring_min_rows_per_expert
+    ring_at = default if asked < 0 else asked
     with torch.no_grad():
-        gu = ops.gemm_i8_grouped(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H)
+        gu = ops.gemm_i8_grouped(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H, zp_x=zp_x,
+                                 wsum=gu_ws)
         gate, up = gu.chunk(2, dim=-1)
-        hq, s_h, _ = ops.quantize_tokens_i8(qe.act_fn(gate) * up, symmetric=True)
+        hq, s_h, zp_h = ops.quantize_tokens_i8(qe.act_fn(gate) * up, symmetric=sym)
         del gu, gate, up
-        products = {"gate_up": lambda fn: fn(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H),
-                    "down": lambda fn: fn(hq, s_h, qe.down, qe.down_scale, offsets, K=I)}
+        products = {"gate_up": lambda fn: fn(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H,
+                                             zp_x=zp_x, wsum=gu_ws),
+                    "down": lambda fn: fn(hq, s_h, qe.down, qe.down_scale, offsets, K=I, zp_x=zp_h, wsum=dn_ws)}
         for name, call in products.items():
-            t = time_pair({"tiled": lambda i: call(ops.gemm_i8_grouped),
-                           "ring": lambda i: call(ops.gemm_i8_ring_grouped)}, args.reps, args.warmup)
-            same = torch.equal(call(ops.gemm_i8_grouped).view(torch.int16),
-                               call(ops.gemm_i8_ring_grouped).view(torch.int16))
+            t = time_pair({"tiled": lambda i: call(ops.gemm_i8_grouped), "ring": lambda i: call(ring)},
+                          args.reps, args.warmup)
+            same = torch.equal(call(ops.gemm_i8_grouped).view(torch.int16), call(ring).view(torch.int16))
             row[name] = {"tiled": _us(t["tiled"]), "ring": _us(t["ring"]), "bits_equal": same}
             row[name]["speedup"] = round(row[name]["tiled"]["us"] / row[name]["ring"]["us"], 3)
 
         def bank(setting):
             def run(i):
-                QuantizedExperts.ring_min_rows_per_expert = setting
-                qe(x, idx, w)
+                setattr(QuantizedExperts, attr, setting)
+                return qe(x, idx, w)
             return run
 
         try:
             t = time_pair({"attr_0": bank(0), "attr_ring": bank(ring_at)}, args.reps, args.warmup)
+            same = torch.equal(bank(0)(0).view(torch.int16), bank(ring_at)(0).view(torch.int16))
         finally:
-            QuantizedExperts.ring_min_rows_per_expert = default
-    row["experts"] = {"ring_min_rows_per_expert": ring_at, "on_ring": bool(0 < ring_at <= T * TOPK / E),
+            setattr(QuantizedExperts, attr, default)
+    row["experts"] = {attr: ring_at, "on_ring": bool(0 < ring_at <= T * TOPK / E), "bits_equal": same,
                       "attr_0": _us(t["attr_0"]), "attr_ring": _us(t["attr_ring"])}
     row["experts"]["speedup"] = round(row["experts"]["attr_0"]["us"] / row["experts"]["attr_ring"]["us"], 3)
     return row
@@ -287,9 +296,12 @@ def main():
     ap.add_argument("--decode-tokens", default="",
                     help="A8 schemes: compare the two grouped GEMM forms at these token counts instead")
     ap.add_argument("--ring-tokens", default="",
-                    help="W8A8: compare qt_gemm_i8_grouped and qt_gemm_i8_ring_grouped at these token counts instead")
+                    help="W8A8 / W4A8: compare qt_gemm_i8_grouped and the scheme's ring form at these token counts "
+                         "instead")
     ap.add_argument("--ring-min-rows-per-expert", type=int, default=-1,
-                    help="with --ring-tokens: the attribute of the bank's second timing (default: the class's)")
+                    help="with --ring-tokens, W8A8: the attribute of the bank's second timing (default: the class's)")
+    ap.add_argument("--ring-w4-min-rows-per-expert", type=int, default=-1,
+                    help="with --ring-tokens, W4A8: the attribute of the bank's second timing (default: the class's)")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -301,14 +313,20 @@ def main():
     rows = []
 
     if args.ring_tokens:
-        qe = _experts("W8A8", dev, g)
-        for T in (int(t) for t in args.ring_tokens.split(",")):
-            row = _bench_a8_ring(T, qe, dev, g, args)
-            rows.append(row)
-            print(json.dumps(row), file=sys.stderr)
+        for scheme in args.schemes.split(","):
+            if scheme not in ("W8A8", "W4A8"):
+                raise SystemExit("--ring-tokens compares the A8 grouped GEMMs (W8A8 / W4A8)")
+            qe = _experts(scheme, dev, g)
+            for T in (int(t) for t in args.ring_tokens.split(",")):
+                row = _bench_a8_ring(scheme, T, qe, dev, g, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del qe
             torch.cuda.empty_cache()
-        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, W8A8 prefill: qt_gemm_i8_grouped vs "
-                                    "qt_gemm_i8_ring_grouped", "E": E, "top_k": TOPK, "H": H, "I": I,
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A8 prefill: qt_gemm_i8_grouped vs "
+                                    "qt_gemm_i8_ring_grouped (W8A8) / qt_moe_gemm_i8_ring_w4 (W4A8)",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
                           "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
         return
 
