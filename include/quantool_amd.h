@@ -404,6 +404,9 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
 #define QT_I8_RING_W4_K_UNIT 128
 #define QT_I8_RING_W4_SLOTS 8
 #define QT_I8_RING_W4_LEAD 6
+#define QT_MOE_I8_WIDE_K_UNIT 128
+#define QT_MOE_I8_WIDE_TILE_ROWS 128
+#define QT_MOE_I8_WIDE_MAX_E 4096
 enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
 int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
                           int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
@@ -485,6 +488,29 @@ int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_for
  *   no element outside Y[m < offsets[E], n < N] is written.  No workspace, no atomics: deterministic.  The name is of
  *   the qt_moe_* family; the form's limits are those of the two entry points it joins.  
  *
+ * qt_moe_gemm_i8_wide: the form of qt_gemm_i8_grouped between the decode range and the rings -- batched decode,
+ *   speculative verification, short prompts: qt_gemm_i8_mid's weight-streaming 16-column tile over E weight matrices.
+ *   qt_moe_gemm_i8_ring_w4's argument list with the same meanings (x_rows, the number of rows of Xq, in front of the
+ *   stream; no bias).  Taken: both weight formats, G = 1 and G = K/128, with and without zp_x / wsum (zp_x needs wsum),
+ *   bf16 and fp16 output, any R >= 1 up to the slot bound below, any N >= 1, any ldy >= N, K a multiple of
+ *   QT_MOE_I8_WIDE_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned, E <= QT_MOE_I8_WIDE_MAX_E, and with row_idx
+ *   x_rows K <= 2^32 (a gathered row is addressed by a 32-bit byte offset from Xq), without it x_rows >= R.  Anything
+ *   else is QT_ERR_INVALID before any launch and qt_last_error names the reason.  For every legal input Y is
+ *   bit-identical to qt_gemm_i8_grouped's on the same arguments, for qt_gemm_i8_mid's reason: acc_g is an exact int32
+ *   sum whatever its order, the waves hand their acc_g over as int32 through LDS, and one thread per output element
+ *   runs the chain t_g -> tot = tot + s_w t_g -> y = s_x tot literally, g ascending from 0.0f, with one rounding to
+ *   out_dtype; no wave ever holds an fp32 partial.  A workgroup holds MT = 2, 4 or 8 m-tiles of 16 rows, chosen from R
+ *   alone (R <= 32: 2, R <= 64: 4, else 8: an expert owns at most R rows); the grid is ceil(N/16) column tiles x
+ *   (floor(R / (16 MT)) + min(E, R)) row-tile slots, an upper bound on sum_e ceil(rows_e / (16 MT)) that needs no host
+ *   read of the counts, and must not exceed 65535 slots.  A workgroup walks offsets (clamped to [0, R] and made
+ *   ascending) to its expert and its tile of up to 16 MT of that expert's rows; a surplus one exits before its first
+ *   weight load and its first barrier.  An expert's weights are read once per QT_MOE_I8_WIDE_TILE_ROWS of its rows,
+ *   and only the experts that own rows are read.  rows >= offsets[E] are not written; row_idx values are clamped into
+ *   [0, x_rows); a tile row past the expert's last row is zero in registers, a weight row past N re-reads row N - 1 of
+ *   the same expert, neither is stored: no byte outside Xq[x_rows, K], Wq[E, N, K] (int4: [E, N, K/8] words), s_w /
+ *   wsum[E, N, G], s_x / zp_x[x_rows] is read, no element outside Y[m < offsets[E], n < N] is written.  No workspace,
+ *   no atomics: deterministic, no communication between workgroups.  
+ *
  * qt_moe_combine: out [T, H] (dtype bf16 / fp16) = the weighted sum of each token's routed rows of Y [R, H] (pitch
  *   ldy), transformers' MixtralExperts.forward restated: for the token's rows r = row_of[t k + j] >= 0 in ascending
  *   row order (= ascending expert), with w = weights[t, j] fp32 [T, k]:
@@ -507,6 +533,10 @@ int qt_moe_gemm_i8_ring_w4(const int8_t* Xq, int K, const int32_t* row_idx, int6
                            const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x,
                            const float* s_w, int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy,
                            int64_t x_rows, qt_stream_t stream);
+int qt_moe_gemm_i8_wide(const int8_t* Xq, int K, const int32_t* row_idx, int64_t R, const int32_t* offsets, int E,
+                        const void* Wq, int w_format, int N, const float* s_x, const int32_t* zp_x, const float* s_w,
+                        int G, const int32_t* wsum, void* Y, int out_dtype, int64_t ldy, int64_t x_rows,
+                        qt_stream_t stream);
 int qt_moe_combine(const void* Y, int dtype, int H, int64_t ldy, const int32_t* row_of, const float* weights,
                    int64_t T, int k, void* out, qt_stream_t stream);
 

@@ -25,7 +25,9 @@ down_proj``).  The loader inverts that write: A16 experts are dequantised into t
 a ``QuantizedExperts`` that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` +
 ``qt_moe_combine``; ``qt_gemm_i8_skinny_grouped`` in place of the GEMM for up to ``grouped_max_tokens`` tokens, and
 ``qt_gemm_i8_ring_grouped`` for an int8 bank from ``ring_min_rows_per_expert`` routed rows per expert,
-``qt_moe_gemm_i8_ring_w4`` for a packed int4 bank from ``ring_w4_min_rows_per_expert``).
+``qt_moe_gemm_i8_ring_w4`` for a packed int4 bank from ``ring_w4_min_rows_per_expert``, and between the decode range and
+the rings ``qt_moe_gemm_i8_wide`` up to ``wide_max_rows_per_expert`` / ``wide_w4_max_rows_per_expert`` routed rows per
+expert for products with K >= ``wide_min_k`` and N <= ``wide_max_n``).
 
 Loading needs no GPU: every load-time step (int4 unpacking, the column permutation of actorder ``group``, the per-group
 weight sums) is integer torch work on whatever device the model is built on.  Only ``QuantizedLinear.forward``,

@@ -233,7 +233,14 @@ class QuantizedExperts(_RoutedExperts):
     changes speed alone, and 0 never uses it.  A packed int4 (W4A8) bank with one scale per 128 columns has its own
     ring and its own bound: from R / E >= ``ring_w4_min_rows_per_expert`` (0: never) a product runs on
     ``qt_moe_gemm_i8_ring_w4`` where ``ops.moe_gemm_i8_ring_w4_supported`` holds, equal to the tiled kernel to the bit
-    again; every other int4 product stays on the tiled kernel."""
+    again; every other int4 product stays on the tiled kernel.
+
+    Between the decode range and the rings a product of R routed rows with K >= ``wide_min_k`` and, when ``wide_max_n``
+    is not 0, N <= ``wide_max_n`` runs on the weight-streaming 16-column tile ``qt_moe_gemm_i8_wide`` where
+    ``ops.moe_gemm_i8_wide_supported`` holds, up to R / E <= ``wide_max_rows_per_expert`` for an int8 bank and up to
+    R / E <= ``wide_w4_max_rows_per_expert`` for a packed int4 bank (0: never; each format reads its own attribute
+    alone).  It agrees with the tiled kernel to the bit too, so these attributes change speed alone; the skinny range
+    and the two rings keep precedence, and everything else runs the tiled kernel."""
 
     # Decode form up to this many tokens: the measured crossover at Mixtral-8x7B's bank shapes (DESIGN.md 4.11).
     grouped_max_tokens = 16
@@ -246,6 +253,22 @@ class QuantizedExperts(_RoutedExperts):
     # kernel's own run-to-run spread, at that size and every larger one, in both runs.  At 1024 the down
     # product is level (0.6 - 1.2 % against a spread of 1.0 %).
     ring_w4_min_rows_per_expert = 2048
+    # qt_moe_gemm_i8_wide up to this many routed rows per expert (R / E; 0: never), for an int8 bank and for a packed
+    # int4 bank: per format and product, the largest measured R / E at which, and at every smaller measured size past the
+    # decode range, the form beat the tiled grouped kernel in both runs by more than the tiled kernel's largest
+    # run-to-run spread in those runs (Mixtral-8x7B's bank shapes, R / E = 4.25 ... 1024).  Int8: the down
+    # product wins 1.54 / 1.39 / 1.16x at R / E = 4.25 / 8 / 16 and loses from 32 (0.92x); gate_up never wins (0.88x at
+    # best).  Packed int4: down wins 2.2 / 2.2 / 1.5 / 1.3x at 4.25 / 8 / 16 / 32 and loses from 64 (0.94x); gate_up wins
+    # 1.10 / 1.07x at 4.25 / 8 and loses from 16 (0.78x).
+    wide_max_rows_per_expert = 16
+    wide_w4_max_rows_per_expert = 32
+    # Products with a smaller K stay on the tiled kernel: they are launch-bound (as QuantizedLinear.mid_min_k).
+    wide_min_k = 512
+    # Products with more output columns stay on the tiled kernel (0: no bound): every 16-column tile re-reads its
+    # activation rows.  The down product's N at the measured shapes: only down qualifies for an int8 bank, and with
+    # gate_up (N = 28672) held back the int4 bound above is down's own; what this gives up is int4 gate_up's 7 - 11 % at
+    # R / E <= 8.
+    wide_max_n = 4096
 
     def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
                  down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
@@ -276,6 +299,7 @@ class QuantizedExperts(_RoutedExperts):
         w, s_w = getattr(self, part), getattr(self, f"{part}_scale")
         R = x.shape[0] if row_idx is None else row_idx.numel()
         ring, ring_w4 = self.ring_min_rows_per_expert, self.ring_w4_min_rows_per_expert
+        wide = self.wide_w4_max_rows_per_expert if self.int4 else self.wide_max_rows_per_expert
         if 1 <= tokens <= self.grouped_max_tokens:
             gemm = ops.gemm_i8_skinny_grouped
         elif (ring > 0 and R >= ring * self.num_experts and not self.int4 and s_w.shape[2] == 1
@@ -284,6 +308,10 @@ class QuantizedExperts(_RoutedExperts):
         elif (ring_w4 > 0 and R >= ring_w4 * self.num_experts and self.int4 and s_w.shape[2] * 128 == x.shape[1]
               and ops.moe_gemm_i8_ring_w4_supported(Xq, w, s_w, row_idx)):
             gemm = ops.moe_gemm_i8_ring_w4
+        elif (wide > 0 and R <= wide * self.num_experts and x.shape[1] >= self.wide_min_k
+              and (self.wide_max_n == 0 or w.shape[1] <= self.wide_max_n)
+              and ops.moe_gemm_i8_wide_supported(Xq, w, s_w, row_idx)):
+            gemm = ops.moe_gemm_i8_wide
         else:
             gemm = ops.gemm_i8_grouped
         return gemm(Xq, s_x, w, s_w, offsets, row_idx=row_idx,

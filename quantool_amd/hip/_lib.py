@@ -127,6 +127,9 @@ SIGNATURES = {
     "qt_moe_gemm_i8_ring_w4": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64,
                                        c_int64, c_void_p]),
+    "qt_moe_gemm_i8_wide": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64,
+                                    c_int64, c_void_p]),
     "qt_moe_combine": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                c_void_p]),
     "qt_dequantize_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -604,6 +604,9 @@ class I8Form:
     x_rows: bool = False             # the entry point takes the number of rows of Xq behind ldy
     slots: Optional[int] = None      # half panels resident in LDS
     lead: Optional[int] = None       # half panels the LDS-DMA runs ahead of the MFMAs
+    # an expert form whose grid's second dimension holds R // tile_rows + min(E, R) row-tile slots (<= 65535); None:
+    # the rings' count of 256-row tiles
+    tile_rows: Optional[int] = None
 
 
 _RING = dict(dtypes=(torch.int8,), k_unit=128, groups="one", aligned16=True, slots=8, lead=6)
@@ -621,6 +624,10 @@ I8_FORMS = {f.entry: f for f in (
 # because the table is the set of qt_gemm_i8* entry points; to fold it in, rename the entry point and move this row.
 I8_MOE_RING_W4_FORM = I8Form("qt_moe_gemm_i8_ring_w4", experts=True, max_e=4096, x_rows=True,
                              **{**_RING, "dtypes": (torch.int32,), "groups": "per_unit"})
+# The bank form between the decode range and the rings: qt_gemm_i8_mid's tile over E weight matrices.  Beside the table
+# for the same reason.
+I8_MOE_WIDE_FORM = I8Form("qt_moe_gemm_i8_wide", experts=True, x_rows=True, max_e=4096, k_unit=128,
+                          groups="one_or_per_unit", aligned16=True, tile_rows=128)
 
 I8_SKINNY_MAX_M = I8_FORMS["qt_gemm_i8_skinny"].max_m   # rows of Xq qt_gemm_i8_skinny takes
 # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
@@ -634,6 +641,10 @@ I8_RING_W4_LEAD = I8_FORMS["qt_gemm_i8_ring_w4"].lead
 I8_MID_MAX_M = I8_FORMS["qt_gemm_i8_mid"].max_m         # rows of Xq qt_gemm_i8_mid takes (QT_I8_MID_MAX_M)
 I8_MID_K_UNIT = I8_FORMS["qt_gemm_i8_mid"].k_unit       # columns per k-block of qt_gemm_i8_mid: K must be a multiple
 I8_RING_GROUPED_MAX_E = I8_FORMS["qt_gemm_i8_ring_grouped"].max_e   # experts qt_gemm_i8_ring_grouped walks per workgroup
+MOE_I8_WIDE_K_UNIT = I8_MOE_WIDE_FORM.k_unit            # columns per k-block of qt_moe_gemm_i8_wide: K must be a multiple
+MOE_I8_WIDE_TILE_ROWS = I8_MOE_WIDE_FORM.tile_rows      # rows of one expert a workgroup of qt_moe_gemm_i8_wide holds at most
+MOE_I8_WIDE_MAX_E = I8_MOE_WIDE_FORM.max_e              # experts qt_moe_gemm_i8_wide walks per workgroup
+MOE_I8_WIDE_MAX_SLOTS = 65535                           # row-tile slots: the grid's second dimension
 
 
 def _i8_refusal(form: I8Form, Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
@@ -676,7 +687,13 @@ def _i8_refusal(form: I8Form, Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Ten
         if E > form.max_e:
             return f"E={E} > {form.max_e} experts"
         R = x_rows if row_idx is None else row_idx.numel()
-        if ((R + 255) // 256 + E) * ((N + 255) // 256) > 0x7fffffff:
+        if form.tile_rows is not None:
+            # up to R = 64 the entry point holds 32 or 64 rows per slot, at most 65 slots in all: the bound only bites
+            # where a slot holds tile_rows
+            slots = R // form.tile_rows + min(E, R)
+            if slots > MOE_I8_WIDE_MAX_SLOTS:
+                return f"{slots} row-tile slots (R={R}, E={E}) exceed the grid's {MOE_I8_WIDE_MAX_SLOTS}"
+        elif ((R + 255) // 256 + E) * ((N + 255) // 256) > 0x7fffffff:
             return f"too many tiles: R={R}, E={E}, N={N}"
     return None
 
@@ -883,6 +900,27 @@ def moe_gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s
     prefill form for W4A8 banks.  Same arguments; Y equals ``gemm_i8_grouped``'s to the bit; ``row_idx`` values are
     clamped into Xq's rows.  ``ValueError`` where ``moe_gemm_i8_ring_w4_supported`` is false."""
     return _gemm_i8_grouped(I8_MOE_RING_W4_FORM, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
+
+
+def moe_gemm_i8_wide_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                               row_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``moe_gemm_i8_wide`` takes these operands: an int8 or packed int4 bank with G = 1 or K/128, K a multiple
+    of ``MOE_I8_WIDE_K_UNIT`` and at most 32768, both operands 16-byte aligned, at most ``MOE_I8_WIDE_MAX_E`` experts,
+    R // ``MOE_I8_WIDE_TILE_ROWS`` + min(E, R) <= ``MOE_I8_WIDE_MAX_SLOTS`` row-tile slots, and, with ``row_idx``, an Xq
+    of at most 2^32 bytes.  Host-only."""
+    return _i8_refusal(I8_MOE_WIDE_FORM, Xq, Wq, s_w, row_idx) is None
+
+
+def moe_gemm_i8_wide(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                     offsets: torch.Tensor, *, rows: Optional[int] = None,
+                     row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                     zp_x: Optional[torch.Tensor] = None, wsum: Optional[torch.Tensor] = None,
+                     out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8_grouped`` on the weight-streaming 16-column tile (``qt_moe_gemm_i8_wide``): the bank form between the
+    decode range and the rings -- batched decode, speculative verification, short prompts.  Same arguments; Y equals
+    ``gemm_i8_grouped``'s to the bit; ``row_idx`` values are clamped into Xq's rows.  ``ValueError`` where
+    ``moe_gemm_i8_wide_supported`` is false."""
+    return _gemm_i8_grouped(I8_MOE_WIDE_FORM, Xq, s_x, Wq, s_w, offsets, rows, row_idx, K, zp_x, wsum, out_dtype)
 
 
 def moe_combine(Y: torch.Tensor, row_of: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:

@@ -36,7 +36,10 @@ B-row GEMM per Linear, and in every scheme and mode (the W4A16 ones included) ``
 and ``tokens_agree_with_dequantized`` count over all B x --new generated tokens, sequence by sequence.
 ``--pair mid`` (A8 schemes) replaces the mode pair by one that differs only in ``QuantizedLinear.mid_max_m``:
 ``a8_mid_off`` (0: rows 17 .. 128 on the tiled ``qt_gemm_i8``) against ``a8_mid`` (the class default:
-``qt_gemm_i8_mid``); everything else stays at its default in both.
+``qt_gemm_i8_mid``); everything else stays at its default in both.  ``--pair wide`` (A8 schemes, ``--model mixtral``)
+likewise differs only in ``QuantizedExperts.wide_max_rows_per_expert`` / ``wide_w4_max_rows_per_expert`` /
+``wide_max_n``: ``a8_wide_off`` (all 0: the banks' products past the decode range on the tiled ``qt_gemm_i8_grouped``)
+against ``a8_wide`` (the class defaults: ``qt_moe_gemm_i8_wide``).
 """
 from __future__ import annotations
 
@@ -181,6 +184,34 @@ def a8_mid_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) 
     result["speedup"] = round(t / k, 3)
 
 
+def a8_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """One loaded A8 sparse-MoE model decoded as ``a8_wide_off`` (``QuantizedExperts``' three wide attributes 0) and
+    ``a8_wide`` (their defaults)."""
+    from quantool_amd.engine.qlinear import QuantizedExperts
+
+    names = ("wide_max_rows_per_expert", "wide_w4_max_rows_per_expert", "wide_max_n")
+    model = load_quantized(path, device=dev)
+    defaults = {n: getattr(QuantizedExperts, n) for n in names}
+    result.update(defaults, wide_min_k=QuantizedExperts.wide_min_k, grouped_max_tokens=QuantizedExperts.grouped_max_tokens)
+    result["quantized_expert_banks"] = sum(isinstance(m, QuantizedExperts) for m in model.modules())
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, values in (("a8_wide_off", dict.fromkeys(names, 0)), ("a8_wide", defaults)):
+            for n, v in values.items():
+                setattr(QuantizedExperts, n, v)
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    for n, v in defaults.items():
+        setattr(QuantizedExperts, n, v)
+    same = [x == y for x, y in zip(tokens["a8_wide_off"], tokens["a8_wide"])]
+    result["tokens_agree"] = sum(same)
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_step"]) for m in ("a8_wide_off", "a8_wide"))
+    result["speedup"] = round(t / k, 3)
+
+
 def a8_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
     """One loaded A8 model decoded as ``a8_tiled`` (class attributes 0) and ``a8_skinny`` (their defaults)."""
     from quantool_amd.engine.qlinear import QuantizedExperts, QuantizedLinear
@@ -216,8 +247,9 @@ def main():
     ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
-    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid"],
-                    help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid")
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide"],
+                    help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
+                         "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide")
     ap.add_argument("--modes", default=None,
                     help="default: dequantized,packed (llama) / dequantized,packed,packed_experts (mixtral)")
     args = ap.parse_args()
@@ -237,7 +269,7 @@ def main():
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
               "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
     if args.scheme != "W4A16":
-        (a8_mid_modes if args.pair == "mid" else a8_modes)(path, dev, prompt, args.new, result)
+        {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes}[args.pair](path, dev, prompt, args.new, result)
         print(json.dumps(result))
         return
     tokens = {}

@@ -45,6 +45,14 @@ events: median / mean / min microseconds per form, ring speedup (tiled median / 
 QuantizedExperts.forward end to end with the scheme's attribute (ring_min_rows_per_expert /
 ring_w4_min_rows_per_expert) at 0 and at the class default (or at --ring-min-rows-per-expert /
 --ring-w4-min-rows-per-expert), alternating likewise.
+
+  python tools/moe_bench.py --wide-tokens 17,32,64,128,256,512,1024,2048,4096 [--schemes W8A8,W4A8]
+
+The A8 batched-decode comparison, per scheme: per product and per T, qt_gemm_i8_grouped and qt_moe_gemm_i8_wide on the
+same operands, alternating call by call in one loop, each call between its own HIP events: median / mean / min
+microseconds per form, wide speedup (tiled median / wide median), bits_equal.  Then QuantizedExperts.forward end to end
+with wide_max_rows_per_expert, wide_w4_max_rows_per_expert and wide_max_n all 0 and at the class defaults (or at
+--wide-max-rows-per-expert / --wide-w4-max-rows-per-expert / --wide-max-n), alternating likewise.
 """
 from __future__ import annotations
 
@@ -290,6 +298,65 @@ def _bench_a8_ring(scheme, T, qe, dev, g, args):
     return row
 
 
+WIDE_ATTRS = ("wide_max_rows_per_expert", "wide_w4_max_rows_per_expert", "wide_max_n")
+
+
+def _bench_a8_wide(scheme, T, qe, dev, g, args):
+    """One batched-decode row: the tiled and the wide form of each product on the same routing and rows, and the
+    bank's forward with the wide attributes at 0 and at the chosen values."""
+    from qlinear_bench import time_pair
+
+    int4, sym = scheme == "W4A8", qe.act_symmetric
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = w / w.sum(-1, keepdim=True)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    off = offsets.cpu().tolist()
+    Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=sym)
+    gu_ws, dn_ws = (None, None) if sym else (qe.gate_up_wsum, qe.down_wsum)
+    row = {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
+           "R_over_E": T * TOPK / E}
+    defaults = {name: getattr(QuantizedExperts, name) for name in WIDE_ATTRS}
+    chosen = {name: (defaults[name] if getattr(args, name) < 0 else getattr(args, name)) for name in WIDE_ATTRS}
+    with torch.no_grad():
+        gu = ops.gemm_i8_grouped(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H, zp_x=zp_x,
+                                 wsum=gu_ws)
+        gate, up = gu.chunk(2, dim=-1)
+        hq, s_h, zp_h = ops.quantize_tokens_i8(qe.act_fn(gate) * up, symmetric=sym)
+        del gu, gate, up
+        products = {"gate_up": lambda fn: fn(Xq, s_x, qe.gate_up, qe.gate_up_scale, offsets, row_idx=src_token, K=H,
+                                             zp_x=zp_x, wsum=gu_ws),
+                    "down": lambda fn: fn(hq, s_h, qe.down, qe.down_scale, offsets, K=I, zp_x=zp_h, wsum=dn_ws)}
+        for name, call in products.items():
+            t = time_pair({"tiled": lambda i: call(ops.gemm_i8_grouped), "wide": lambda i: call(ops.moe_gemm_i8_wide)},
+                          args.reps, args.warmup)
+            same = torch.equal(call(ops.gemm_i8_grouped).view(torch.int16),
+                               call(ops.moe_gemm_i8_wide).view(torch.int16))
+            row[name] = {"tiled": _us(t["tiled"]), "wide": _us(t["wide"]), "bits_equal": same}
+            row[name]["speedup"] = round(row[name]["tiled"]["us"] / row[name]["wide"]["us"], 3)
+
+        def bank(settings):
+            def run(i):
+                for attr, value in settings.items():
+                    setattr(QuantizedExperts, attr, value)
+                return qe(x, idx, w)
+            return run
+
+        try:
+            zero = {name: 0 for name in WIDE_ATTRS}
+            t = time_pair({"attr_0": bank(zero), "attr_wide": bank(chosen)}, args.reps, args.warmup)
+            same = torch.equal(bank(zero)(0).view(torch.int16), bank(chosen)(0).view(torch.int16))
+        finally:
+            for attr, value in defaults.items():
+                setattr(QuantizedExperts, attr, value)
+    at = chosen["wide_w4_max_rows_per_expert" if int4 else "wide_max_rows_per_expert"]
+    row["experts"] = {**chosen, "on_wide": bool(T > QuantizedExperts.grouped_max_tokens and T * TOPK / E <= at),
+                      "bits_equal": same, "attr_0": _us(t["attr_0"]), "attr_wide": _us(t["attr_wide"])}
+    row["experts"]["speedup"] = round(row["experts"]["attr_0"]["us"] / row["experts"]["attr_wide"]["us"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
@@ -302,6 +369,12 @@ def main():
                     help="with --ring-tokens, W8A8: the attribute of the bank's second timing (default: the class's)")
     ap.add_argument("--ring-w4-min-rows-per-expert", type=int, default=-1,
                     help="with --ring-tokens, W4A8: the attribute of the bank's second timing (default: the class's)")
+    ap.add_argument("--wide-tokens", default="",
+                    help="W8A8 / W4A8: compare qt_gemm_i8_grouped and qt_moe_gemm_i8_wide at these token counts instead")
+    for name in WIDE_ATTRS:
+        ap.add_argument("--" + name.replace("_", "-"), type=int, default=-1,
+                        help=f"with --wide-tokens: QuantizedExperts.{name} of the bank's second timing (default: the "
+                             "class's)")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -311,6 +384,23 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     rows = []
+
+    if args.wide_tokens:
+        for scheme in args.schemes.split(","):
+            if scheme not in ("W8A8", "W4A8"):
+                raise SystemExit("--wide-tokens compares the A8 grouped GEMMs (W8A8 / W4A8)")
+            qe = _experts(scheme, dev, g)
+            for T in (int(t) for t in args.wide_tokens.split(",")):
+                row = _bench_a8_wide(scheme, T, qe, dev, g, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del qe
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A8 batched decode: qt_gemm_i8_grouped vs qt_moe_gemm_i8_wide",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
 
     if args.ring_tokens:
         for scheme in args.schemes.split(","):
