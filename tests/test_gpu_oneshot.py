@@ -134,3 +134,64 @@ def test_gram_stream_and_group_stream_routes_give_the_single_stream_result(dev):
         torch.cuda.synchronize()
         runs.append((o.results["s.q"].weight_packed.clone(), o.results["s.q"].weight_scale.clone()))
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+def test_group_streams_reused_with_different_data(dev):
+    """Two `oneshot` calls in a row through the cached `GroupStreams` pools, with DIFFERENT weights and activations and no
+    synchronisation between them: what the streams, the allocator's recycled blocks or a workspace still hold from the
+    first call is wrong data for the second (repeating one problem, as the test above does, would not notice).  Each call
+    has a long-batch group with a SmoothQuant stage and a plain one (Gram stream, each chain on a group stream behind its
+    event) and a short-batch group (staged, group stream), and must equal its own one-stream reference bit for bit."""
+    from quantool_amd.engine.gptq_linear import HessianAccumulator, gptq_quantize_shared
+    from quantool_amd.engine.modifiers import GPTQModifier, SmoothQuantModifier
+    from quantool_amd.engine.oneshot import LinearCalibrationSet, LinearGroup, oneshot
+    from quantool_amd.engine.schemes import QuantArgs
+    from quantool_amd.engine.smoothquant import ChannelMinMax, apply_smoothing, smoothquant_scales
+    from quantool_amd.hip import ops
+
+    n_long = HessianAccumulator.DIRECT_TOKENS
+    shapes = {"s": (512, [("s.q", 64), ("s.k", 32)], [n_long], True),        # long batch + smoothing: Gram stream
+              "a": (256, [("a.up", 160)], [n_long, n_long], False),          # two long batches: Gram stream
+              "c": (256, [("c.o", 96)], [64] * 6, False)}                    # short batches: staged, group stream
+    sets, refs = [], []
+    for seed in (11, 12):
+        torch.manual_seed(seed)
+        groups, ref = [], {}
+        for gname, (K, lins, batches, smoothed) in shapes.items():
+            Xs = [torch.randn(n, K, device=dev).to(torch.bfloat16) for n in batches]
+            Ws = {n: (torch.randn(r, K, device=dev) * 0.02).to(torch.bfloat16) for n, r in lins}
+            v = {f"{gname}.norm": torch.rand(K, device=dev).to(torch.bfloat16) + 0.5} if smoothed else None
+            groups.append(LinearGroup(gname, Xs if len(Xs) > 1 else Xs[0], Ws, smooth_vectors=v, num_samples=len(batches)))
+            ws, xs = [Ws[n] for n, _ in lins], Xs
+            if smoothed:      # the SmoothQuant stage on the current stream: s from all tokens, W * s, v / s, X / s
+                stats = ChannelMinMax(K, dev)
+                for x in Xs:
+                    stats.add(x)
+                s = smoothquant_scales(stats, ws, 0.5)
+                ws, new_v = apply_smoothing(s, ws, list(v.values()))
+                xs = [ops.scale_columns(x, s, divide=True) for x in Xs]
+                ref[f"{gname}.norm"] = new_v[0].clone()
+            acc = HessianAccumulator(K, dev)
+            for x in xs:
+                acc.add(x, num_samples=1)
+            res = gptq_quantize_shared(ws, acc, QuantArgs(actorder="static"))
+            for (n, _), r in zip(lins, res):
+                ref[n] = (r.weight_packed.clone(), r.weight_scale.clone())
+        sets.append(groups)
+        refs.append(ref)
+    torch.cuda.synchronize()
+    for n in ("s.q", "s.k", "a.up", "c.o"):      # or a stale read of the other call's data could pass
+        assert not torch.equal(refs[0][n][0], refs[1][n][0]), n
+    recipe = [SmoothQuantModifier(smoothing_strength=0.5), GPTQModifier(scheme="W4A16")]
+    outs = [oneshot(model=LinearCalibrationSet(groups), recipe=recipe) for groups in sets]      # no synchronise between
+    torch.cuda.synchronize()
+    for i, (out, ref) in enumerate(zip(outs, refs)):
+        assert set(out.results) == {"s.q", "s.k", "a.up", "c.o"}
+        for n, r in out.results.items():
+            packed, scale = ref[n]
+            other = refs[1 - i][n][0]
+            assert torch.equal(r.weight_packed, packed), (
+                f"call {i}, {n}: {int((r.weight_packed != packed).sum())} of {packed.numel()} packed words differ; equals the "
+                f"other call's reference (stale read): {torch.equal(r.weight_packed, other)}")
+            assert torch.equal(r.weight_scale, scale), f"call {i}, {n}: scales differ"
+        assert torch.equal(out.smoothed["s.norm"], ref["s.norm"]), f"call {i}: smoothed norm vector differs"
