@@ -614,6 +614,40 @@ int qt_gemm_wq_grouped(const void* X, int x_dtype, int K, int64_t ldx, const int
                        const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w, int G,
                        const int8_t* zp_w, const int32_t* g_idx, void* Y, int64_t ldy, qt_stream_t stream);
 
+/* qt_moe_gemm_wq_wide: qt_gemm_wq_grouped for more than a few rows per expert -- batched decode, speculative
+ *   verification, short prompts.  The arguments and their meanings are qt_gemm_wq_grouped's, plus
+ *   x_rows, the number of rows of X.  No bias, no workspace, no atomics.
+ *   Taken: QT_W_INT4_PACKED and QT_W_INT8, G = 1 and G = K / 128, with and without zp_w, bf16 and fp16, any R >= 1 up to
+ *   the slot bound below, any N >= 1, any ldy >= N, K a multiple of QT_MOE_WQ_WIDE_K_UNIT, X, Wq and ldx * 2 multiples of
+ *   16 bytes, E <= QT_MOE_WQ_WIDE_MAX_E, x_rows * ldx * 2 + 2 K < 2^32 (a row of X is addressed by a 32-bit byte offset
+ *   from X), and without row_idx x_rows >= R.  Everything else -- g_idx != NULL, a ragged K, a misaligned operand or
+ *   pitch, a null pointer, a G that is neither 1 nor K / 128, a dtype that is not 16-bit, too many slots, the 2^32
+ *   bound -- returns QT_ERR_INVALID before any launch, and qt_last_error names the reason.
+ *   Every row of Y is bit-identical to qt_gemm_wq_grouped's row on the same arguments, and so to qt_gemm_wq_skinny with
+ *   that expert's weight on that row alone: per output element, wave w accumulates the k-blocks kb = w, w + 4, ... in
+ *   ascending order on the same MFMA with the same fragment layout, then ((c0 + c1) + c2) + c3, then one rounding;
+ *   and a row of the MFMA's output reads its own activation row only.  qt_gemm_wq_skinny's error bound and
+ *   exact-input guarantee carry over.  Deterministic: two runs give the same bits.
+ *   A workgroup holds MT tiles of 16 rows of one expert and reads that expert's weights once for all of them.  MT is
+ *   chosen on the host from R and E alone: the smallest of 1, 2, 4, 8 with 16 MT >= ceil(R / E) (8 when none is), so
+ *   that evenly routed rows put one expert in one workgroup per 16 columns; no count is read on the host.  The grid is
+ *   ceil(N/16) column tiles x (floor(R / (16 MT)) + min(E, R)) row-tile slots, an upper bound on
+ *   sum_e ceil(rows_e / (16 MT)) for any routing (per expert ceil(r/q) <= floor(r/q) + [r > 0], and
+ *   sum_e floor(r_e/q) <= floor(R/q)); that count must not exceed QT_MOE_WQ_WIDE_MAX_SLOTS = 65535.  A workgroup walks
+ *   offsets, clamped to [0, R] and made ascending, to its expert and tile; a surplus one exits before its first weight
+ *   load and its barrier; an expert with more than 16 MT rows takes several slots; only the experts that own rows
+ *   have their weights read.
+ *   row_idx values are clamped into [0, x_rows), not followed.  No byte outside X [x_rows, K] (pitch ldx),
+ *   Wq [E, N, .], s_w / zp_w [E, N, G], offsets [E + 1] and row_idx [R] is read; rows >= offsets[E] are not written,
+ *   and nothing outside Y[m < offsets[E], n < N] is. */
+int qt_moe_gemm_wq_wide(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                        const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w, int G,
+                        const int8_t* zp_w, const int32_t* g_idx, void* Y, int64_t ldy, int64_t x_rows,
+                        qt_stream_t stream);
+#define QT_MOE_WQ_WIDE_K_UNIT 128
+#define QT_MOE_WQ_WIDE_MAX_E 4096
+#define QT_MOE_WQ_WIDE_MAX_SLOTS 65535
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

@@ -153,7 +153,8 @@ def audit_m0(src: Path) -> None:
 # (round 3: wrapping gemm3_kernel's body in an item loop let LICM hoist 128 epilogue addresses -> 179 spills)
 NO_SPILL_KERNELS = ("xtx_kernel", "xtx16_kernel", "gemm3_kernel", "sgemm_ring_kernel", "quantize_tokens_kernel",
                     "gemm_i8_kernel", "gemm_i8_ring_kernel", "gemm_i8_ring_moe_kernel", "gemm_i8_mid_kernel",
-                    "gemm_i8_ring_w4_kernel", "gemm_i8_ring_w4_moe_kernel", "moe_gemm_i8_wide_kernel")
+                    "gemm_i8_ring_w4_kernel", "gemm_i8_ring_w4_moe_kernel", "moe_gemm_i8_wide_kernel",
+                    "moe_gemm_wq_wide_kernel")
 
 
 def audit_spills(src_name: str, asm_text: str) -> None:

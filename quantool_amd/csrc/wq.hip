@@ -9,7 +9,8 @@
 //                        once), dequantises it and feeds v_mfma_f32_16x16x32_{bf16,f16} with M padded to 16 (the
 //                        activations are the B operand).  Four k-blocks are in flight per wave before the first MFMA.
 //                        The 4 waves' fp32 partials are summed through LDS in wave order: no atomics.
-// qt_gemm_wq_stream      the skinny tile over up to 8 m-tiles of 16 rows (M <= 128): a k-block's weight
+// qt_gemm_wq_stream      the skinny tile over up to 8 m-tiles of 16 rows (M <= 128; the tile is stated in
+//                        wq_stream_tile.h and shared with wq_moe_wide.hip): a k-block's weight
 //                        chunk is loaded and dequantised once and multiplied with every live m-tile; each m-tile's
 //                        accumulator runs the skinny kernel's chain, so every row equals the skinny kernel's to the bit.
 // qt_gemm_wq_grouped     the same kernel over E weight matrices (MOE = true): grid (column tiles, slots), one slot per
@@ -19,68 +20,9 @@
 //
 // -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own unless written as __builtin_fmaf.
 #include "common.h"
+#include "wq_stream_tile.h"
 
 namespace {
-
-constexpr int WQ_THREADS = 256;
-constexpr int WQ_WAVES = WQ_THREADS / 64;
-constexpr int WQ_KB = 128;      // columns per k-block (= the weight group)
-constexpr int WQ_UNROLL = 4;    // k-blocks in flight per wave
-
-struct WqArgs {
-    const unsigned short* X;
-    int64_t ldx;
-    int M;
-    const void* Wq;
-    int N, K, Kw;               // Kw: int32 words per packed row (int4)
-    const float* s_w;
-    int G;
-    const int8_t* zp_w;
-    const int32_t* g_idx;
-    const unsigned short* bias;
-    unsigned short* Y;          // Y (GEMV) or W (dequantise)
-    int64_t ldy;
-    int vec;                    // 16-byte weight / activation / output accesses are aligned and in bounds
-    // grouped form only (qt_gemm_wq_grouped): M is the routed-row count R; expert e owns output rows
-    // [offsets[e], offsets[e + 1]) and weight matrix e; X row of output row m is row_idx[m] (or m when NULL)
-    const int32_t* offsets;
-    const int32_t* row_idx;
-    int E;
-};
-
-template <int DT>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    if constexpr (DT == QT_F16) {
-        const unsigned lo = __builtin_bit_cast(unsigned short, (_Float16)a);
-        const unsigned hi = __builtin_bit_cast(unsigned short, (_Float16)b);
-        return lo | (hi << 16);
-    } else {
-        const unsigned lo = __builtin_bit_cast(unsigned short, (__bf16)a);
-        const unsigned hi = __builtin_bit_cast(unsigned short, (__bf16)b);
-        return lo | (hi << 16);
-    }
-}
-
-template <int DT>
-__device__ __forceinline__ float h2f(unsigned short h) {
-    return DT == QT_F16 ? qt_f16_to_f32(h) : qt_bf16_to_f32(h);
-}
-
-// The group of column c and its scale / zero-point offset.  cz = OFF + zp: the stored level plus OFF is the unsigned
-// value u the kernels convert (u - cz = q - zp exactly).  g_idx values are clamped to [0, G).
-template <bool INT4, bool ZP, bool GIDX>
-__device__ __forceinline__ void group_params(const WqArgs& p, int64_t n, int c, float& s, float& cz) {
-    int g;
-    if constexpr (GIDX) {
-        g = p.g_idx[c];
-        g = min(max(g, 0), p.G - 1);
-    } else {
-        g = p.G == 1 ? 0 : c / WQ_KB;
-    }
-    s = p.s_w[n * p.G + g];
-    cz = INT4 ? 8.0f : 128.0f;
-    if constexpr (ZP) cz = cz + (float)p.zp_w[n * p.G + g];
-}
 
 // unsigned value u = level + OFF of column c of row n (any alignment)
 template <bool INT4>
@@ -144,63 +86,6 @@ __global__ void __launch_bounds__(WQ_THREADS) dequant_kernel(const WqArgs p, int
 }
 
 // ---- qt_gemm_wq_skinny ----------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-// a once-read 16-byte weight chunk: non-temporal load (MI355X_MICROARCH nt-weights)
-__device__ __forceinline__ uint4 ld_nt16(const void* p) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(const u32x4 a, const u32x4 b, f32x4 c) {
-    if constexpr (DT == QT_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                       0, 0, 0);
-}
-
-// The A fragment of one MFMA step: 8 consecutive weight columns, w = round_to_dtype(dequantised value).
-// Without a zero-point the value is fma(u, s, -OFF s): -OFF s is exact (OFF a power of two), so this is one rounding
-// of q s, the same value as (u - OFF) * s.  With a zero-point: (u - cz) * s, the difference exact.
-template <int DT, bool ZP>
-__device__ __forceinline__ u32x4 frag_from_u(const float (&u)[8], float s, float cz, float noff) {
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if constexpr (ZP) {
-            const float t = u[j] - cz;
-            f[j] = t * s;
-        } else {
-            f[j] = __builtin_fmaf(u[j], s, noff);
-        }
-    }
-    return (u32x4){pack2<DT>(f[0], f[1]), pack2<DT>(f[2], f[3]), pack2<DT>(f[4], f[5]), pack2<DT>(f[6], f[7])};
-}
-
-// one packed word (8 int4 columns) -> u values in column order (nibble j = column j)
-__device__ __forceinline__ void u_int4(unsigned w, float (&u)[8]) {
-    const unsigned lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        u[2 * i] = (float)((lo >> (8 * i)) & 0xffu);       // v_cvt_f32_ubyte{i}
-        u[2 * i + 1] = (float)((hi >> (8 * i)) & 0xffu);
-    }
-}
-
-// two dwords (8 int8 columns) -> u = level + 128
-__device__ __forceinline__ void u_int8(unsigned a, unsigned b, float (&u)[8]) {
-    a ^= 0x80808080u;
-    b ^= 0x80808080u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        u[i] = (float)((a >> (8 * i)) & 0xffu);
-        u[4 + i] = (float)((b >> (8 * i)) & 0xffu);
-    }
-}
-
 // MOE: the grouped form.  blockIdx.y is a slot: the walk over offsets (clamped to [0, R], so a bad table cannot move a
 // write out of Y) maps it to expert e and rows [m0, m0 + M) of that expert, M <= 16; the expert's weight, scale,
 // zero-point and g_idx rows are then the arguments of the same tile code.  Rows are independent through the MFMA (row m
@@ -351,154 +236,12 @@ __global__ void __launch_bounds__(WQ_THREADS) wq_skinny_kernel(const WqArgs args
 }
 
 // ---- qt_gemm_wq_stream ----------------------------------------------------------------------------------------------
-// The skinny tile over MT m-tiles of 16 activation rows (17 <= M <= 128 is what it is for; 1 <= M is taken): the same
-// workgroup shape, the same k-block -> wave map and the same statements for the weight chunk, the group parameters and
-// the A fragment, so accumulator t of wave w runs the chain the skinny kernel's wave w runs on rows [16 t, 16 t + 16).
-// The A fragments of a k-block are formed once and kept for every m-tile.  The B fragments (activation rows) come from
-// L2 in fragment shape, WQ_XB - 1 (k-block, m-tile) steps ahead of the MFMAs that use them.
-// One instance per tile count MT = ceil(M / 16), and a wave takes its k-blocks in batches of WQ_SB (then 4, 2, 1 for the
-// rest), so nothing in a batch is conditional: no dead k-block, no dead m-tile.  (The skinny kernel pads its last batch
-// with all-zero products instead, which leave a sum that started at +0 unchanged; the batch length is no part of the
-// summation order.)  Instances for 2 / 4 / 8 tiles with uniform branches around the dead tiles' loads and MFMAs were
-// tried first: every branch made the compiler merge the whole accumulator array, and the 8-tile instance needed 256
-// VGPRs and 200 AGPRs of copies.
-constexpr int WQ_XB = 4;        // activation fragment sets resident per wave: the one in use and WQ_XB - 1 in flight
-
-template <int V>
-struct WqInt {
-    static constexpr int value = V;
-};
-
+// wq_stream_tile.h's tile on rows [0, M) of X: one instance per tile count MT = ceil(M / 16).
 template <bool INT4, int DT, bool ZP, int MT>
 __global__ void __launch_bounds__(WQ_THREADS) wq_stream_kernel(const WqArgs p) {
-    __shared__ f32x4 red[WQ_WAVES - 1][MT][64];
-    // k-blocks in flight per wave: 32 VGPRs of weight chunks in either format
-    constexpr int WQ_SB = INT4 ? 2 * WQ_UNROLL : WQ_UNROLL;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // in an SGPR: the k-block offsets are scalar
-    const int r = lane & 15;            // A row (weight row n0 + r) and B column (activation row 16 t + r)
-    const int kq = lane >> 4;           // which 32 columns of the k-block
-    const int64_t n0 = (int64_t)blockIdx.x * 16;
-    const int64_t n = n0 + r;
-    const bool n_ok = n < p.N;
-    const int64_t nrow = n_ok ? n : 0;
-    const int nfull = p.K / WQ_KB;      // K is a multiple of WQ_KB
-    const float off = INT4 ? 8.0f : 128.0f;
-    constexpr int WV = INT4 ? 1 : 2;    // 16-byte weight chunks per lane per k-block
-    // Activations come through buffer loads: m-tile t's descriptor starts at row 16 t and ends with the last column of
-    // row min(M, 16 t + 16) - 1, so a lane whose row is >= M is out of range (ldx >= K): it gets zeros and no memory
-    // access is made for it.  The host bounds ldx, so the byte offsets fit 32 bits.
-    const int xoff = (int)(((int64_t)r * p.ldx + 32 * kq) * 2);
-
-    f32x4 acc[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-
-    // UC k-blocks kb, kb + 4, ... of this wave: every weight load issued before the first MFMA
-    auto batch = [&](const int kb, auto uc) {
-        constexpr int UC = decltype(uc)::value;
-        constexpr int STEPS = UC * MT;
-        uint4 wv[UC][WV];
-        u32x4 xv[WQ_XB][4];
-        float sc[UC], cz[UC];
-        // step i = (k-block u = i / MT, m-tile t = i % MT): its four 16-byte activation loads
-        auto load_x = [&](int i, u32x4 (&dst)[4]) {
-            const int u = i / MT, t = i % MT;
-            const int rows = min(p.M - 16 * t, 16);
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(p.X + (int64_t)(16 * t) * p.ldx), 0, (int)(((int64_t)(rows - 1) * p.ldx + p.K) * 2), 0x00020000);
-            const int soff = (kb + u * WQ_WAVES) * (WQ_KB * 2);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                dst[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xoff + 16 * s, soff, 0));
-        };
-#pragma unroll
-        for (int i = 0; i < WQ_XB - 1 && i < STEPS; ++i) load_x(i, xv[i]);
-#pragma unroll
-        for (int u = 0; u < UC; ++u) {
-            const int c0 = (kb + u * WQ_WAVES) * WQ_KB + 32 * kq;
-            if constexpr (INT4) {
-                const uint4* src = (const uint4*)((const int32_t*)p.Wq + nrow * p.Kw + c0 / 8);
-                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x88888888u, 0x88888888u, 0x88888888u,
-                                                                                 0x88888888u);
-            } else {
-                const uint4* src = (const uint4*)((const int8_t*)p.Wq + nrow * p.K + c0);
-                wv[u][0] = n_ok ? ld_nt16(src) : make_uint4(0x80808080u, 0x80808080u, 0x80808080u,
-                                                                                 0x80808080u);
-                wv[u][1] = n_ok ? ld_nt16(src + 1)
-                                : make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
-            }
-            float sv = 0.0f, czv = off;
-            if (n_ok) group_params<INT4, ZP, false>(p, nrow, c0, sv, czv);
-            sc[u] = sv;
-            cz[u] = czv;
-        }
-#pragma unroll
-        for (int u = 0; u < UC; ++u) {
-            const float s = sc[u];
-            const float noff = -(off * s);
-            const unsigned wd[8] = {wv[u][0].x, wv[u][0].y, wv[u][0].z, wv[u][0].w, wv[u][WV - 1].x,
-                                    wv[u][WV - 1].y, wv[u][WV - 1].z, wv[u][WV - 1].w};
-            u32x4 a[4];
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                float uu[8];
-                if constexpr (INT4) u_int4(wd[s4], uu);
-                else u_int8(wd[2 * s4], wd[2 * s4 + 1], uu);
-                a[s4] = frag_from_u<DT, ZP>(uu, s, cz[u], noff);
-            }
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const int i = u * MT + t;
-                if (i + WQ_XB - 1 < STEPS) load_x(i + WQ_XB - 1, xv[(i + WQ_XB - 1) % WQ_XB]);
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) acc[t] = mfma16<DT>(a[s4], xv[i % WQ_XB][s4], acc[t]);
-            }
-        }
-    };
-    int kb = wave;
-    int left = nfull > wave ? (nfull - wave + WQ_WAVES - 1) / WQ_WAVES : 0;   // this wave's k-blocks: kb, kb + 4, ...
-    for (; left >= WQ_SB; left -= WQ_SB, kb += WQ_SB * WQ_WAVES) batch(kb, WqInt<WQ_SB>{});
-    if constexpr (WQ_SB > 4) {
-        if (left & 4) {
-            batch(kb, WqInt<4>{});
-            kb += 4 * WQ_WAVES;
-        }
-    }
-    if (left & 2) {
-        batch(kb, WqInt<2>{});
-        kb += 2 * WQ_WAVES;
-    }
-    if (left & 1) batch(kb, WqInt<1>{});
-
-    // as the skinny kernel, per m-tile: y = ((w0 + w1) + w2) + w3 (+ bias), one rounding
-    if (wave > 0) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t) red[wave - 1][t][lane] = acc[t];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int64_t m = 16 * t + r;
-            f32x4 y4 = acc[t];
-#pragma unroll
-            for (int w = 0; w < WQ_WAVES - 1; ++w) {
-                const f32x4 o = red[w][t][lane];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) y4[i] = y4[i] + o[i];
-            }
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int64_t nn = n0 + 4 * kq + i;
-                if (nn >= p.N) continue;
-                float y = y4[i];
-                if (p.bias) y = y + h2f<DT>(p.bias[nn]);
-                p.Y[m * p.ldy + nn] = (unsigned short)(pack2<DT>(y, 0.0f) & 0xffffu);
-            }
-        }
-    }
+    constexpr bool MOE = false;
+    constexpr int64_t m0 = 0, x_rows = 0;
+#include "wq_stream_tile_body.h"
 }
 
 template <bool I4, int D, bool Z>

@@ -21,7 +21,8 @@ Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up
 ``<layer>.block_sparse_moe.experts.{e}.w1 / w3 / w2``, otherwise ``<layer>.mlp.experts.{e}.gate_proj / up_proj /
 down_proj``).  The loader inverts that write: A16 experts are dequantised into the fused parameters
 (``gate_up_proj[e] = cat(w1, w3)``, ``down_proj[e] = w2``), or with ``a16_experts="packed"`` replace the bank with a
-``WeightOnlyExperts`` on the stored integer weights (``qt_gemm_wq_grouped`` at decode); A8 experts replace the bank with
+``WeightOnlyExperts`` on the stored integer weights (``qt_gemm_wq_grouped`` at decode, ``qt_moe_gemm_wq_wide`` from
+``wide_min_tokens`` tokens and, with ``a16_experts_wide_tokens``, past 128); A8 experts replace the bank with
 a ``QuantizedExperts`` that runs the routed rows on the grouped int8 GEMM (``qt_moe_route`` + ``qt_gemm_i8_grouped`` +
 ``qt_moe_combine``; ``qt_gemm_i8_skinny_grouped`` in place of the GEMM for up to ``grouped_max_tokens`` tokens, and
 ``qt_gemm_i8_ring_grouped`` for an int8 bank from ``ring_min_rows_per_expert`` routed rows per expert,
@@ -265,10 +266,14 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
 
 
 A16_MODES = ("dequantized", "packed")
+# The largest ``a16_experts_wide_tokens``: the largest call size at which qt_moe_gemm_wq_wide was measured (DESIGN.md
+# 4.19).
+A16_EXPERTS_WIDE_MAX_TOKENS = 2048
 
 
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
-                   a16_experts: str = "dequantized", a16_stream_rows: int = 0) -> nn.Module:
+                   a16_experts: str = "dequantized", a16_stream_rows: int = 0,
+                   a16_experts_wide_tokens: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -280,6 +285,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``WeightOnlyLinear`` built, so inputs of 17 to that many rows run ``qt_gemm_wq_stream`` on the stored weights
     instead of dequantise + ``F.linear`` (``WeightOnlyExperts`` are not touched); it is recorded under
     ``"a16_stream_rows"``.  A8 checkpoints ignore it.
+    ``a16_experts_wide_tokens`` (0, the default, or 129 ... ``A16_EXPERTS_WIDE_MAX_TOKENS``; needs
+    ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
+    tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
+    is recorded under ``"a16_experts_wide_tokens"``.  A8 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -304,6 +313,13 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         raise ValueError(f"a16_stream_rows={a16_stream_rows!r}: expected 0 or 17 ... 128")
     if a16_stream_rows and a16 != "packed":
         raise ValueError("a16_stream_rows needs a16='packed' (dequantised Linears have no stored weights to stream)")
+    if type(a16_experts_wide_tokens) is not int or not (
+            a16_experts_wide_tokens == 0 or 129 <= a16_experts_wide_tokens <= A16_EXPERTS_WIDE_MAX_TOKENS):
+        raise ValueError(f"a16_experts_wide_tokens={a16_experts_wide_tokens!r}: expected 0 or 129 ... "
+                         f"{A16_EXPERTS_WIDE_MAX_TOKENS}")
+    if a16_experts_wide_tokens and a16_experts != "packed":
+        raise ValueError("a16_experts_wide_tokens needs a16_experts='packed' (dequantised banks have no stored weights "
+                         "to run on)")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -348,6 +364,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                          packed_experts=packed_experts)
         if new is not None:
             replaced.append(bank_name)
+            if packed_experts and a16_experts_wide_tokens:
+                new.wide_max_tokens = a16_experts_wide_tokens
             _set_submodule(model, bank_name, new)
     for name, t in quant.items():
         lin = model.get_submodule(name)
@@ -376,4 +394,5 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))
         if packed_experts:
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)
+            model._qt_checkpoint["a16_experts_wide_tokens"] = a16_experts_wide_tokens
     return model

@@ -330,6 +330,13 @@ class WeightOnlyExperts(_RoutedExperts):
     transformers forward runs on them (honouring ``config._experts_implementation``), so the output equals the dense
     bank's to the bit.  On CPU tensors ``forward`` is that bank forward on ``stored(part).dequantize``.
 
+    Inside the routed forward a product with T >= ``wide_min_tokens`` (when that is not 0) runs
+    ``qt_moe_gemm_wq_wide`` (several 16-row tiles of one expert per workgroup, the expert's weights read once for all of
+    them) where ``ops.moe_gemm_wq_wide_supported`` holds; the two kernels agree to the bit, so the attribute changes speed
+    alone.  Opt-in: with ``wide_max_tokens`` > 0, ``grouped_max_tokens`` < T <= ``wide_max_tokens`` takes the routed
+    forward on that kernel instead of the dequantise path, on a bank where both products are supported (no ``g_idx``,
+    H and I multiples of 128); its rows are bit-identical to the grouped GEMV's, not to the dense bank's.
+
     Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
     ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
     [E, H] (optional, actorder ``group``); ``down`` int32 [E, H, ceil(I/8)] or int8 [E, H, I] and its ``down_scale``,
@@ -342,6 +349,17 @@ class WeightOnlyExperts(_RoutedExperts):
     # re-reads an expert's weights once per 16 of its rows and still beats the dequantise path (2.7 ms) up to T = 192;
     # at 128 it takes 1.2 ms.
     grouped_max_tokens = 128
+    # qt_moe_gemm_wq_wide inside the routed forward from this many tokens (0: never): the smallest measured T from which
+    # the form beat the grouped GEMV on both products, in both runs and all three schemes, by more than the GEMV's own
+    # run-to-run spread (at most 1.8 %), at that size and at every larger measured size up to 128 (Mixtral-8x7B's bank
+    # shapes, E = 8, top-2).  At 96 tokens (2 m-tiles) it wins 1.21 - 1.29x and at 128 1.11 - 1.20x; at 17,
+    # 32 and 64 (1 m-tile: the GEMV's own tile) it is 0.95 - 1.05x.
+    wide_min_tokens = 96
+    # The routed forward on qt_moe_gemm_wq_wide up to this many tokens, past grouped_max_tokens.  0, the default: never
+    # -- a fused kernel cannot equal the dense bank's summation order, so it is the caller's choice
+    # (``load_quantized(..., a16_experts_wide_tokens=)``; the measurements support 384: the routed forward takes 0.47 - 0.83
+    # of the dequantise path's time at 192 - 384 tokens and 1.08 - 1.19 of it at 512).
+    wide_max_tokens = 0
 
     def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
                  down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
@@ -368,7 +386,8 @@ class WeightOnlyExperts(_RoutedExperts):
                 f"weights={'int4' if self.int4 else 'int8'}, "
                 f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
                 f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
-                f"grouped_max_tokens={self.grouped_max_tokens}")
+                f"grouped_max_tokens={self.grouped_max_tokens}, wide_min_tokens={self.wide_min_tokens}, "
+                f"wide_max_tokens={self.wide_max_tokens}")
 
     def stored(self, part: str) -> StoredWeight:
         """The ``part`` ("gate_up" / "down") buffers as they are now, as one bank weight [E, ...]."""
@@ -401,11 +420,36 @@ class WeightOnlyExperts(_RoutedExperts):
         from ..hip import ops
 
         w = self.stored(part)
-        return ops.gemm_wq_grouped(x, w.levels, w.scale, offsets, row_idx=row_idx, K=w.K, zp_w=w.zero_point,
-                                   g_idx=w.g_idx)
+        gemm = ops.gemm_wq_grouped
+        if tokens > self.grouped_max_tokens:
+            gemm = ops.moe_gemm_wq_wide         # the extended range: forward() has checked both products
+        elif self.wide_min_tokens > 0 and tokens >= self.wide_min_tokens:
+            # the attribute and T decide first: ops' wide names are read only past them
+            if ops.moe_gemm_wq_wide_supported(x, w.levels, w.scale, w.zero_point, w.g_idx, row_idx):
+                gemm = ops.moe_gemm_wq_wide
+        return gemm(x, w.levels, w.scale, offsets, row_idx=row_idx, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx)
+
+    def _wide_range(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor) -> bool:
+        """Whether both products of this call run on ``qt_moe_gemm_wq_wide``: the gate_up product on the rows of
+        ``hidden_states`` gathered by token, the down product on the R = ``top_k_index.numel()`` routed rows (a
+        stand-in of that shape on the meta device is judged: the rows themselves are a fresh contiguous tensor)."""
+        from ..hip import ops
+
+        x = _rows(hidden_states, self.hidden_dim)
+        routed = top_k_index.reshape(-1)        # its length alone is read
+        act = torch.empty((routed.numel(), self.intermediate_dim), dtype=x.dtype, device="meta")
+        for part, rows, row_idx in (("gate_up", x, routed), ("down", act, None)):
+            w = self.stored(part)
+            if not ops.moe_gemm_wq_wide_supported(rows, w.levels, w.scale, w.zero_point, w.g_idx, row_idx):
+                return False
+        return True
 
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
-        if hidden_states.is_cuda and 1 <= hidden_states.numel() // self.hidden_dim <= self.grouped_max_tokens:
+        T = hidden_states.numel() // self.hidden_dim
+        if hidden_states.is_cuda and 1 <= T <= self.grouped_max_tokens:
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        if (hidden_states.is_cuda and self.wide_max_tokens > 0 and self.grouped_max_tokens < T <= self.wide_max_tokens
+                and self._wide_range(hidden_states, top_k_index)):
             return super().forward(hidden_states, top_k_index, top_k_weights)
         dense = {"gate_up_proj": self.dense_weight("gate_up", hidden_states.dtype),
                  "down_proj": self.dense_weight("down", hidden_states.dtype)}

@@ -140,6 +140,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_gemm_wq_grouped": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "qt_moe_gemm_wq_wide": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                    c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                    c_void_p]),
 }
 
 _lib = None

@@ -1141,6 +1141,103 @@ def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offset
     return Y
 
 
+MOE_WQ_WIDE_K_UNIT = 128        # columns per k-block of qt_moe_gemm_wq_wide: K must be a multiple (QT_MOE_WQ_WIDE_K_UNIT)
+MOE_WQ_WIDE_MAX_E = 4096        # experts a workgroup of qt_moe_gemm_wq_wide walks (QT_MOE_WQ_WIDE_MAX_E)
+MOE_WQ_WIDE_MAX_SLOTS = 65535   # row-tile slots of its grid (QT_MOE_WQ_WIDE_MAX_SLOTS)
+
+
+def moe_wq_wide_mtiles(R: int, E: int) -> int:
+    """The m-tiles of 16 rows a workgroup of ``qt_moe_gemm_wq_wide`` holds for R routed rows over E experts: the
+    smallest of 1, 2, 4, 8 whose 16 MT rows hold ceil(R / E) (8 when none does), as the library chooses it."""
+    per = -(-R // E)
+    return 1 if per <= 16 else 2 if per <= 32 else 4 if per <= 64 else 8
+
+
+def _moe_wq_wide_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                         g_idx: Optional[torch.Tensor] = None, row_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_moe_gemm_wq_wide`` would refuse these operands, or None.  Host-only: touches no library, and reads
+    shapes, dtypes, strides and addresses alone, so CPU tensors are judged like device ones."""
+    U = MOE_WQ_WIDE_K_UNIT
+    if g_idx is not None:
+        return "g_idx is not taken (an actorder-group bank runs on gemm_wq_grouped or on the dequantised bank)"
+    if X.dtype not in (torch.bfloat16, torch.float16):
+        return f"X must be bf16 or fp16, got {X.dtype}"
+    if X.dim() != 2 or X.stride(1) != 1:
+        return f"X must be 2-d with unit column stride, got shape {tuple(X.shape)} strides {X.stride()}"
+    if Wq.dtype not in (torch.int8, torch.int32):
+        return f"int8 or packed int4 (int32) weights only, got {Wq.dtype}"
+    if Wq.dim() != 3:
+        return f"Wq must be a bank [E, N, .], got {tuple(Wq.shape)}"
+    x_rows, K = X.shape
+    if K == 0 or K % U != 0:
+        return f"K={K} is not a multiple of the k-unit {U}"
+    G = s_w.shape[-1] if s_w.dim() == 3 else -1
+    if G not in (1, K // U):
+        return f"G must be 1 or K / {U} = {K // U}, got s_w {tuple(s_w.shape)}"
+    ldx = X.stride(0) if x_rows > 1 else K      # one row: its pitch is never used
+    if X.data_ptr() % 16 != 0 or Wq.data_ptr() % 16 != 0 or (ldx * 2) % 16 != 0:
+        return "X, Wq and the row pitch of X must be 16-byte aligned"
+    E = Wq.shape[0]
+    if E > MOE_WQ_WIDE_MAX_E:
+        return f"E={E} experts are more than {MOE_WQ_WIDE_MAX_E}"
+    R = x_rows if row_idx is None else row_idx.numel()
+    if R < 1 or x_rows < 1:
+        return f"empty product: R={R}, X rows={x_rows}"
+    if x_rows * ldx * 2 + 2 * K >= 1 << 32:
+        return (f"x_rows={x_rows} x pitch {ldx} x 2 + 2 K reaches 2^32 bytes: a row of X is addressed by a 32-bit "
+                "offset")
+    slots = R // (16 * moe_wq_wide_mtiles(R, E)) + min(E, R)
+    if slots > MOE_WQ_WIDE_MAX_SLOTS:
+        return f"{slots} row-tile slots (R={R}, E={E}) exceed the grid's {MOE_WQ_WIDE_MAX_SLOTS}"
+    return None
+
+
+def moe_gemm_wq_wide_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                               zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                               row_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``moe_gemm_wq_wide`` takes these operands: no ``g_idx``, 16-bit X with unit column stride, an int8 or
+    packed int4 bank of at most ``MOE_WQ_WIDE_MAX_E`` experts, K a multiple of ``MOE_WQ_WIDE_K_UNIT``, G = 1 or K/128, X,
+    Wq and X's row pitch 16-byte aligned, X below 2^32 bytes, at most ``MOE_WQ_WIDE_MAX_SLOTS`` row-tile slots.
+    Host-only."""
+    return _moe_wq_wide_refusal(X, Wq, s_w, zp_w, g_idx, row_idx) is None
+
+
+def moe_gemm_wq_wide(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
+                     row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                     zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_wq_grouped`` with several tiles of 16 rows of one expert per workgroup (``qt_moe_gemm_wq_wide``): the
+    bank form for batched decode, speculative verification and short prompts.  Same arguments; every row of Y equals
+    ``gemm_wq_grouped``'s to the bit, and ``row_idx`` values are clamped into X's rows.  ``ValueError`` where
+    ``moe_gemm_wq_wide_supported`` is false, before the library is touched."""
+    why = _moe_wq_wide_refusal(X, Wq, s_w, zp_w, g_idx, row_idx)
+    if why is not None:
+        raise ValueError(f"moe_gemm_wq_wide: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    Mx, Kx = X.shape
+    if K is not None and K != Kx:
+        raise ValueError(f"K={K} but X has {Kx} columns")
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, Kx, experts=True)
+    E = Wq.shape[0]
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    _req(offsets, torch.int32, "offsets", 1)
+    if offsets.numel() != E + 1 or not offsets.is_contiguous() or offsets.device != X.device:
+        raise ValueError(f"offsets must be contiguous int32 [E + 1 = {E + 1}] on {X.device}")
+    if row_idx is not None:
+        _req(row_idx, torch.int32, "row_idx", 1)
+        if not row_idx.is_contiguous() or row_idx.device != X.device:
+            raise ValueError(f"row_idx must be contiguous int32 [R] on {X.device}")
+        R = row_idx.numel()
+    else:
+        R = Mx
+    Y = torch.empty((R, N), dtype=X.dtype, device=X.device)
+    check("qt_moe_gemm_wq_wide", lib.qt_moe_gemm_wq_wide(
+        X.data_ptr(), code, K, X.stride(0) if Mx > 1 else K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(),
+        fmt, N, s_w.data_ptr(), G, _ptr(zp_w), None, Y.data_ptr(), Y.stride(0), Mx, _stream()))
+    return Y
+
+
 # ---- a12  AWQ ------------------------------------------------------------------------------
 def _w2d(W: torch.Tensor):
     if W.dim() != 2 or not W.is_cuda or W.stride(1) != 1:

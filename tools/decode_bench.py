@@ -212,6 +212,32 @@ def a8_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict)
     result["speedup"] = round(t / k, 3)
 
 
+def a16_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, wide_min_tokens: int, result: dict) -> None:
+    """One packed A16 sparse-MoE model (``a16_experts="packed"``) decoded as ``a16_wide_off`` (``WeightOnlyExperts``'
+    ``wide_min_tokens`` = 0: the grouped GEMV) and ``a16_wide`` (``wide_min_tokens`` = the class default, or
+    --wide-min-tokens).  The two kernels agree to the bit, so the tokens must."""
+    model = load_quantized(path, device=dev, a16="packed", a16_experts="packed")
+    default = WeightOnlyExperts.wide_min_tokens
+    chosen = default if wide_min_tokens < 0 else wide_min_tokens
+    result.update(wide_min_tokens=chosen, wide_min_tokens_default=default,
+                  grouped_max_tokens=WeightOnlyExperts.grouped_max_tokens,
+                  weight_only_expert_banks=sum(isinstance(m, WeightOnlyExperts) for m in model.modules()))
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, value in (("a16_wide_off", 0), ("a16_wide", chosen)):
+            WeightOnlyExperts.wide_min_tokens = value
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    WeightOnlyExperts.wide_min_tokens = default
+    same = [x == y for x, y in zip(tokens["a16_wide_off"], tokens["a16_wide"])]
+    result["tokens_agree"] = sum(same)
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_step"]) for m in ("a16_wide_off", "a16_wide"))
+    result["speedup"] = round(t / k, 3)
+
+
 def a8_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
     """One loaded A8 model decoded as ``a8_tiled`` (class attributes 0) and ``a8_skinny`` (their defaults)."""
     from quantool_amd.engine.qlinear import QuantizedExperts, QuantizedLinear
@@ -249,7 +275,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
     ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide"],
                     help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
-                         "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide")
+                         "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; W4A16 with --model "
+                         "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide")
+    ap.add_argument("--wide-min-tokens", type=int, default=-1,
+                    help="with --scheme W4A16 --pair wide: WeightOnlyExperts.wide_min_tokens of a16_wide (default: "
+                         "the class's)")
     ap.add_argument("--modes", default=None,
                     help="default: dequantized,packed (llama) / dequantized,packed,packed_experts (mixtral)")
     args = ap.parse_args()
@@ -270,6 +300,12 @@ def main():
               "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
     if args.scheme != "W4A16":
         {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes}[args.pair](path, dev, prompt, args.new, result)
+        print(json.dumps(result))
+        return
+    if args.pair == "wide":
+        if not mixtral:
+            raise SystemExit("--scheme W4A16 --pair wide compares expert-bank kernels: it needs --model mixtral")
+        a16_wide_modes(path, dev, prompt, args.new, args.wide_min_tokens, result)
         print(json.dumps(result))
         return
     tokens = {}

@@ -2,12 +2,13 @@
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
-                                  [--a16-stream-rows N]
+                                  [--a16-stream-rows N] [--a16-experts-wide-tokens N]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
 on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed`` with it: routed-expert banks on
-``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
+``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``;
+``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
 evaluation wall times.
 """
 from __future__ import annotations
@@ -38,12 +39,16 @@ def main():
     ap.add_argument("--a16-experts", default="dequantized", choices=list(A16_MODES))
     ap.add_argument("--a16-stream-rows", type=int, default=0,
                     help="with --a16 packed: inputs of 17 to this many rows (at most 128) run qt_gemm_wq_stream")
+    ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
+                    help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
+                         "qt_moe_gemm_wq_wide instead of dequantising the banks")
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
     model = load_quantized(args.checkpoint, device=args.device,
                            dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
-                           a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows)
+                           a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
+                           a16_experts_wide_tokens=args.a16_experts_wide_tokens)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()

@@ -53,6 +53,16 @@ same operands, alternating call by call in one loop, each call between its own H
 microseconds per form, wide speedup (tiled median / wide median), bits_equal.  Then QuantizedExperts.forward end to end
 with wide_max_rows_per_expert, wide_w4_max_rows_per_expert and wide_max_n all 0 and at the class defaults (or at
 --wide-max-rows-per-expert / --wide-w4-max-rows-per-expert / --wide-max-n), alternating likewise.
+
+  python tools/moe_bench.py --schemes W4A16,W4A16_ASYM,W8A16 --a16-wide-tokens 17,32,64,96,128,192,256,384,512,768,1024,2048
+
+The A16 batched-decode comparison, per scheme and T: per product and as a pair, qt_gemm_wq_grouped and
+qt_moe_gemm_wq_wide on the same operands, alternating call by call in one loop, each call between its own HIP events,
+the two forms reading different copies of the bank in a rep and the copies rotating from rep to rep (cold weights, as
+above): median / mean / min microseconds per form, wide speedup (grouped median / wide median), bits_equal_grouped.
+Then WeightOnlyExperts.forward end to end on the path it had before the wide form (wide_min_tokens = wide_max_tokens =
+0: the grouped pair up to grouped_max_tokens, the dequantise path above) against the new path (wide_min_tokens =
+--a16-wide-min-tokens, wide_max_tokens = the largest T asked for), alternating likewise.
 """
 from __future__ import annotations
 
@@ -357,6 +367,73 @@ def _bench_a8_wide(scheme, T, qe, dev, g, args):
     return row
 
 
+def _bench_a16_wide(scheme, T, banks, dev, g, args, wide_max):
+    """One A16 batched-decode row: the grouped and the wide form of each product and of the pair on the same routing
+    and rows, and the bank's forward on the old and on the new path, cold weights."""
+    from qlinear_bench import time_pair
+
+    n = len(banks)
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = (w / w.sum(-1, keepdim=True)).to(torch.bfloat16)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    off = offsets.cpu().tolist()
+    R = T * TOPK
+    row = {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)], "R_over_E": R / E,
+           "m_tiles": ops.moe_wq_wide_mtiles(R, E), "cold_copies": n}
+    with torch.no_grad():
+        b0 = banks[0]
+        gu = ops.gemm_wq_grouped(x, b0.gate_up, b0.gate_up_scale, offsets, row_idx=src_token, K=H,
+                                 zp_w=b0.gate_up_zero_point)
+        gate, up = gu.chunk(2, dim=-1)
+        h = b0.act_fn(gate) * up
+        del gu, gate, up
+
+        def gate_up(fn, b):
+            return fn(x, b.gate_up, b.gate_up_scale, offsets, row_idx=src_token, K=H, zp_w=b.gate_up_zero_point)
+
+        def down(fn, b):
+            return fn(h, b.down, b.down_scale, offsets, K=I, zp_w=b.down_zero_point)
+
+        def pair(fn, b):
+            gate_up(fn, b)
+            return down(fn, b)
+
+        for name, call in (("gate_up", gate_up), ("down", down), ("pair", pair)):
+            t = time_pair({"grouped": lambda i: call(ops.gemm_wq_grouped, banks[i % n]),
+                           "wide": lambda i: call(ops.moe_gemm_wq_wide, banks[(i + 1) % n])}, args.reps, args.warmup)
+            row[name] = {"grouped": _us(t["grouped"]), "wide": _us(t["wide"])}
+            if name != "pair":
+                row[name]["bits_equal_grouped"] = torch.equal(call(ops.gemm_wq_grouped, b0).view(torch.int16),
+                                                              call(ops.moe_gemm_wq_wide, b0).view(torch.int16))
+            row[name]["speedup"] = round(row[name]["grouped"]["us"] / row[name]["wide"]["us"], 3)
+
+        def bank(wide_min_tokens, wide_max_tokens, shift):
+            def run(i):
+                b = banks[(i + shift) % n]
+                b.wide_min_tokens, b.wide_max_tokens = wide_min_tokens, wide_max_tokens
+                return b(x, idx, w)
+            return run
+
+        keep = [(b.wide_min_tokens, b.wide_max_tokens) for b in banks]
+        try:
+            reps = args.reps if T <= b0.grouped_max_tokens else max(3, args.reps // 2)
+            t = time_pair({"before": bank(0, 0, 0), "wide": bank(args.a16_wide_min_tokens, wide_max, 1)}, reps,
+                          min(args.warmup, 2))
+            y0, y1 = bank(0, 0, 0)(0), bank(args.a16_wide_min_tokens, wide_max, 0)(0)
+        finally:
+            for b, (lo, hi) in zip(banks, keep):
+                b.wide_min_tokens, b.wide_max_tokens = lo, hi
+    row["experts"] = {"wide_min_tokens": args.a16_wide_min_tokens, "wide_max_tokens": wide_max,
+                      "before_path": "grouped" if T <= b0.grouped_max_tokens else "dequantise",
+                      "bits_equal": torch.equal(y0.view(torch.int16), y1.view(torch.int16)),
+                      "max_abs_diff": float((y0.float() - y1.float()).abs().max()),
+                      "before": _us(t["before"]), "wide": _us(t["wide"])}
+    row["experts"]["speedup"] = round(row["experts"]["before"]["us"] / row["experts"]["wide"]["us"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
@@ -375,6 +452,11 @@ def main():
         ap.add_argument("--" + name.replace("_", "-"), type=int, default=-1,
                         help=f"with --wide-tokens: QuantizedExperts.{name} of the bank's second timing (default: the "
                              "class's)")
+    ap.add_argument("--a16-wide-tokens", default="",
+                    help="W4A16 / W4A16_ASYM / W8A16: compare qt_gemm_wq_grouped and qt_moe_gemm_wq_wide at these token "
+                         "counts instead")
+    ap.add_argument("--a16-wide-min-tokens", type=int, default=1,
+                    help="with --a16-wide-tokens: WeightOnlyExperts.wide_min_tokens of the bank's second timing")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -384,6 +466,32 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     rows = []
+
+    if args.a16_wide_tokens:
+        from transformers import MixtralConfig
+        from transformers.models.mixtral.modeling_mixtral import MixtralExperts
+
+        cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=TOPK)
+        tokens = [int(t) for t in args.a16_wide_tokens.split(",")]
+        for scheme in args.schemes.split(","):
+            if scheme not in A16:
+                raise SystemExit("--a16-wide-tokens compares the A16 grouped GEMMs (W4A16 / W4A16_ASYM / W8A16)")
+            n = 3 if scheme != "W8A16" else 2       # > 1.4 GB of bank copies in all, as the A16 rows above
+            with torch.device("meta"):
+                shells = [MixtralExperts(cfg) for _ in range(n)]
+            banks = [_wo_experts(scheme, b, dev, g) for b in shells]
+            for T in tokens:
+                row = _bench_a16_wide(scheme, T, banks, dev, g, args, max(tokens))
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del banks
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A16 batched decode: qt_gemm_wq_grouped vs "
+                                    "qt_moe_gemm_wq_wide",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
 
     if args.wide_tokens:
         for scheme in args.schemes.split(","):
