@@ -395,7 +395,33 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   activation row past M is zero in registers, a weight row past N re-reads row N - 1, neither is stored: no byte
  *   outside Xq[M, K], Wq[N, K] (int4: [N, K/8] words), s_w / wsum[N, G], s_x / zp_x[M] is read, no element outside
  *   Y[m < M, n < N] is written.  Deterministic, no atomics, no workspace, no communication between workgroups.
- *    */
+ *   
+ *
+ * qt_act_mul_quantize_i8: the glue between the two products of an MLP in one row pass -- h = act(gate) * up as torch's
+ *   two elementwise kernels leave it in a 16-bit tensor, then qt_quantize_tokens_i8 on h -- without h ever reaching
+ *   memory.  gate and up are [M, K] bf16 / fp16 (x_dtype) with unit column stride and row pitches ldg, ldu >= K; they may
+ *   be the two halves of one [M, 2K] tensor (up = gate + K, ldg = ldu = 2K) and need no alignment: 16-byte loads are
+ *   taken when both pointers, both pitches and K allow, element loads otherwise.  act: QT_ACT_SILU.  Xq, s_x, zp_x,
+ *   col_perm and symmetric mean what they mean in qt_quantize_tokens_i8, with one difference on a malformed table: an
+ *   entry of col_perm outside [0, K) is clamped into the row here (the gather reads the workgroup's own K values and
+ *   nothing else), where qt_quantize_tokens_i8 reads X at the entry as given.  H (may be NULL): when given, h is also stored
+ *   as [M, K] in x_dtype with row pitch ldh >= K, in natural column order (col_perm does not apply to it); it exists so
+ *   that the activation can be pinned bit for bit apart from the quantiser.  A null gate, up, Xq or s_x, M <= 0,
+ *   K <= 0, a pitch below K, an x_dtype that is not 16-bit, an unknown act, asymmetric activations without zp_x,
+ *   K > 32768 (the GEMMs' bound) and M > INT32_MAX are QT_ERR_INVALID before any launch, and qt_last_error names the
+ *   reason.  Fixed sequence per element, in fp32 with no contraction:
+ *     g  = (float)gate[m, k];  u = (float)up[m, k]
+ *     a  = g / (1.0f + expf(-g))              IEEE division
+ *     a' = a rounded once to x_dtype (RNE)    -- what torch's SiLU leaves in a 16-bit tensor
+ *     p  = (float)a' * u
+ *     h  = p rounded once to x_dtype (RNE)    -- what torch's multiply leaves
+ *   then exactly qt_quantize_tokens_i8's row sequence on h: min / max including 0, s, zp,
+ *   q = rint(clamp(h / s + zp, -128, 127)), Xq[m, k] = q(h[m, col_perm[k]]).
+ *   So (Xq, s_x, zp_x) equal qt_quantize_tokens_i8(F.silu(gate) * up) to the bit wherever this expf is torch's (pinned
+ *   over all 65536 patterns of both dtypes by the tests).  One workgroup per row: h is computed once,
+ *   held in LDS as 16-bit values (2 K bytes) while min / max are reduced, and quantised from there.  A row's result
+ *   depends on the row alone.  Deterministic, no atomics, no workspace.  (csrc/act_quant.hip) */
+enum qt_act { QT_ACT_SILU = 0 };
 #define QT_I8_MID_MAX_M 128
 #define QT_I8_MID_K_UNIT 128
 #define QT_I8_RING_K_UNIT 128
@@ -410,6 +436,9 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
 enum qt_weight_format { QT_W_INT8 = 0, QT_W_INT4_PACKED = 1 };
 int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t ldx, const int32_t* col_perm,
                           int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x, qt_stream_t stream);
+int qt_act_mul_quantize_i8(const void* gate, int64_t ldg, const void* up, int64_t ldu, int x_dtype, int64_t M, int K,
+                           int act, const int32_t* col_perm, int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x,
+                           void* H, int64_t ldh, qt_stream_t stream);
 int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                int out_dtype, int64_t ldy, qt_stream_t stream);
@@ -432,7 +461,8 @@ int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_for
  *   route -> quantize_tokens_i8 (all T tokens once) -> gemm_i8_grouped (gate_up, rows gathered by src_token)
  *   -> act_fn(gate) * up in torch -> quantize_tokens_i8 (routed rows) -> gemm_i8_grouped (down, contiguous) -> combine
  * Per-token quantisation is a function of the row alone, so quantising the T tokens and gathering equals gathering
- * and quantising.
+ * and quantising.  With QuantizedExperts.fused_act and a SiLU act_fn the two steps of the second line's start run as
+ * one, act_mul_quantize_i8 on the two halves of the gate_up output, to the same bits.
  *
  * qt_moe_route: top_k_index [T, k] (int32, or int64 when index_is_int64) -> offsets int32 [E + 1],
  *   src_token / src_slot int32 [T k], row_of int32 [T k] (may be NULL).  The routed rows are the entries (t, j) with

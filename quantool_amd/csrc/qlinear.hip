@@ -6,36 +6,22 @@
 //                         single LDS buffer (A and B, 144-B rows: 36 KB); each wave owns 64 x 64 = 2 x 2 MFMA tiles.
 //                         Packed int4 weights are unpacked to int8 between the global load and the LDS store.
 // (decode sizes, 1 <= M <= 16: qlinear_skinny.hip, equal to qt_gemm_i8 to the bit)
+// (SiLU(gate) * up fused into the quantiser, qt_act_mul_quantize_i8: act_quant.hip; the quantiser's constants and
+//  per-element step, shared with it: i8_quant.h)
 //
 // Numerics are the header's fixed sequence; -ffp-contract=off (csrc/build.py) keeps every multiply and add its own
 // rounding, so a torch restatement of the same steps is equal to the bit.
-#include <float.h>
-
 #include "common.h"
 #include "i8_args.h"
+#include "i8_quant.h"
 #include "i8_unpack.h"
 
 namespace {
-
-// Symmetric activation divisor: max(|min|, |max|) / ((qmax - qmin) / 2) with qmin = -128, qmax = 127, as the weight
-// observer's /7.5 for 4 bits (SURVEY A.2 calculate_qparams, recalled, not pinned against the upstream
-// source).  vLLM's own dynamic int8 path divides by 127 instead; a checkpoint's numbers are only reproduced by the
-// divisor its calibration used, so the constant has one home.
-constexpr float kActSymDivisor = 127.5f;
-constexpr float kActAsymDivisor = 255.0f;
-constexpr float kQmin = -128.0f;
-constexpr float kQmax = 127.0f;
 
 constexpr int QT_THREADS = 256;
 
 __device__ __forceinline__ float ld_x(const unsigned short* X, int dtype, size_t idx) {
     return qt_h16_to_f32(X[idx], dtype);
-}
-
-__device__ __forceinline__ int q_one(float x, float s, float zp) {
-    float v = x / s + zp;
-    v = fminf(fmaxf(v, kQmin), kQmax);
-    return (int)__builtin_rintf(v);
 }
 
 __global__ void __launch_bounds__(QT_THREADS) quantize_tokens_kernel(const unsigned short* __restrict__ X, int dtype,
@@ -87,15 +73,8 @@ __global__ void __launch_bounds__(QT_THREADS) quantize_tokens_kernel(const unsig
         mn = fminf(mn, red[0][w]);
         mx = fmaxf(mx, red[1][w]);
     }
-    float s, zp = 0.0f;
-    if (symmetric) {
-        s = fmaxf(-mn, mx) / kActSymDivisor;
-        s = fmaxf(s, FLT_EPSILON);
-    } else {
-        s = (mx - mn) / kActAsymDivisor;
-        s = fmaxf(s, FLT_EPSILON);
-        zp = fminf(fmaxf(__builtin_rintf(kQmin - mn / s), kQmin), kQmax);
-    }
+    float s, zp;
+    qt_i8_row_qparams(mn, mx, symmetric, s, zp);   // i8_quant.h: the divisor's one home
     if (tid == 0) {
         s_x[m] = s;
         if (zp_x) zp_x[m] = (int32_t)zp;
@@ -103,16 +82,7 @@ __global__ void __launch_bounds__(QT_THREADS) quantize_tokens_kernel(const unsig
 
     if (vec) {   // no col_perm, K % 8 == 0: 8 elements -> one 8-byte store
         for (int k = tid * 8; k < K; k += QT_THREADS * 8) {
-            const uint4 u = *(const uint4*)(row + k);
-            const unsigned w[4] = {u.x, u.y, u.z, u.w};
-            unsigned o[2] = {0u, 0u};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int qa = q_one(qt_h16_to_f32((unsigned short)(w[i] & 0xffffu), dtype), s, zp);
-                const int qb = q_one(qt_h16_to_f32((unsigned short)(w[i] >> 16), dtype), s, zp);
-                o[i >> 1] |= (((unsigned)qa & 0xffu) | (((unsigned)qb & 0xffu) << 8)) << (16 * (i & 1));
-            }
-            *(uint2*)(qrow + k) = make_uint2(o[0], o[1]);
+            *(uint2*)(qrow + k) = q_eight(*(const uint4*)(row + k), dtype, s, zp);
         }
     } else {
         for (int k = tid; k < K; k += QT_THREADS) {

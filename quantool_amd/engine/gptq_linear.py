@@ -30,6 +30,12 @@ class HessianAccumulator:
     token buffer ``[stage_tokens, K]`` and launches ``qt_xtx_accumulate`` once per full buffer
     (and on ``flush``, which every reader of ``G`` goes through).  Batches of ``direct_tokens`` or
     more skip the buffer.
+
+    Streams: work a caller issues through ``add`` is ordered against other streams by the caller, as any tensor
+    operation is.  The one launch the caller does not see is the flush: it runs on whatever stream is current when ``G``
+    is read, which need not be the stream ``add`` staged the tokens on.  That launch is ordered here: the flushing
+    stream first waits for the staging stream, and whatever touches ``G`` or the token buffer next on another stream
+    than the flushing one (a read of ``G``, a further ``add``, a ``reset``) first waits for the flush's Gram launch.
     """
 
     STAGE_BYTES = 1 << 30      # default token buffer: 1 GiB worth of rows, 4096..65536 tokens
@@ -46,12 +52,23 @@ class HessianAccumulator:
         self._stage: Optional[torch.Tensor] = None
         self._stage_sized = False   # the fp32 path halves stage_tokens exactly once
         self._fill = 0
+        self._staged_on = None      # stream of the staging copies not yet flushed
+        self._flushed = None        # (stream, event) of the last flush's Gram launch
 
     @property
     def G(self) -> torch.Tensor:
         """The Gram sum with every staged token folded in."""
         self.flush()
+        self._after_flush()
         return self._G
+
+    def _after_flush(self) -> None:
+        """The current stream behind the last flush's Gram launch, when that ran on another stream."""
+        if self._flushed is not None:
+            stream, event = self._flushed
+            here = torch.cuda.current_stream(self._G.device)
+            if here != stream:
+                here.wait_event(event)
 
     @G.setter
     def G(self, value: torch.Tensor) -> None:
@@ -94,8 +111,11 @@ class HessianAccumulator:
             self._stage = torch.empty((self.stage_tokens, self.K), dtype=self.dtype, device=self._G.device)
         if self._fill + t > self.stage_tokens:
             self.flush()
+        self._after_flush()             # a flush elsewhere may still be reading the buffer
         self._stage[self._fill:self._fill + t].copy_(X2)     # also the dtype conversion, if any
         self._fill += t
+        if self._G.is_cuda:
+            self._staged_on = torch.cuda.current_stream(self._G.device)
 
     def _gram(self, rows: torch.Tensor) -> None:
         # QT_XTX_LAUNCH_TOKENS=n (0 = off, the default): at most n tokens per Gram launch.  The kernel adds all tokens of
@@ -104,6 +124,7 @@ class HessianAccumulator:
         # the fp64 Gram the default is 2.5e-6 of sqrt(Hii Hjj) at K = 14336 where upstream's order gives 7e-7 (DESIGN.md
         # 2.0).  Launches of n tokens make it a two-level sum (partial sums of n, then their sum), at the price of one
         # read-modify-write of G per launch (K = 14336: 0.2 ms each).
+        self._after_flush()             # launches into G one after the other, whichever streams they are on
         limit = _launch_token_limit()
         if limit <= 0 or rows.shape[0] <= limit:
             chunks = [rows]
@@ -117,15 +138,23 @@ class HessianAccumulator:
 
     def flush(self) -> None:
         if self._fill:
+            here = torch.cuda.current_stream(self._G.device) if self._G.is_cuda else None
+            if here is not None and self._staged_on is not None and here != self._staged_on:
+                here.wait_stream(self._staged_on)        # the staging copies (and every earlier launch into G)
             self._gram(self._stage[:self._fill])
             self._fill = 0
+            self._staged_on = None
+            if here is not None:
+                self._flushed = (here, here.record_event())
 
     def release_stage(self) -> None:
         self.flush()
         self._stage = None
 
     def reset(self) -> None:
+        self._after_flush()
         self._fill = 0
+        self._staged_on = self._flushed = None
         self._G.zero_()
         self.n = 0
 

@@ -35,7 +35,11 @@ weight sums) is integer torch work on whatever device the model is built on.  On
 ``QuantizedExperts.forward``, ``WeightOnlyLinear.forward`` and ``WeightOnlyExperts.forward`` on device tensors need
 the HIP library.
 
-The four modules are defined in ``qmodules.py`` and one stored weight as a value (``StoredWeight``: the only reader of a
+With ``a8_fused_act=True`` an A8 checkpoint's MLP glue -- SiLU(gate) * up and the quantiser of the down product -- runs
+as one pass (``qt_act_mul_quantize_i8``): ``QuantizedExperts.fused_act`` in a bank, a ``QuantizedMLP`` in place of a
+Llama-style dense MLP.
+
+The modules are defined in ``qmodules.py`` and one stored weight as a value (``StoredWeight``: the only reader of a
 module's checkpoint tensors, the kernels' layout rules, ``dequantize``, the stacking of experts into a bank) in
 ``stored_weight.py``; both are re-exported here, and this file is the loader.
 """
@@ -49,7 +53,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .qmodules import QuantizedExperts, QuantizedLinear, WeightOnlyExperts, WeightOnlyLinear
+from .qmodules import QuantizedExperts, QuantizedLinear, QuantizedMLP, WeightOnlyExperts, WeightOnlyLinear
 from .serialization import load_state
 from .stored_weight import GROUP, StoredWeight, group_sums, pack_int4, unpack_int4  # noqa: F401 (re-exported)
 
@@ -273,7 +277,7 @@ A16_EXPERTS_WIDE_MAX_TOKENS = 2048
 
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
-                   a16_experts_wide_tokens: int = 0) -> nn.Module:
+                   a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -289,6 +293,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
     tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
     is recorded under ``"a16_experts_wide_tokens"``.  A8 checkpoints ignore it.
+    ``a8_fused_act`` (False, the default, or True) runs the glue between the two products of every A8 MLP as one pass,
+    ``qt_act_mul_quantize_i8``, equal to the bit to the SiLU, the multiply and the quantiser it replaces: it sets
+    ``fused_act`` on every ``QuantizedExperts`` built and puts a ``QuantizedMLP`` in place of every dense MLP for which
+    ``QuantizedMLP.eligible`` holds (a Llama-style MLP of three ``QuantizedLinear``s with SiLU); state-dict keys do not
+    move, and it is recorded under ``"a8_fused_act"``.  A16 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -320,6 +329,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if a16_experts_wide_tokens and a16_experts != "packed":
         raise ValueError("a16_experts_wide_tokens needs a16_experts='packed' (dequantised banks have no stored weights "
                          "to run on)")
+    if type(a8_fused_act) is not bool:
+        raise ValueError(f"a8_fused_act={a8_fused_act!r}: expected True or False")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -366,6 +377,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             replaced.append(bank_name)
             if packed_experts and a16_experts_wide_tokens:
                 new.wide_max_tokens = a16_experts_wide_tokens
+            if a8 and a8_fused_act:
+                new.fused_act = True
             _set_submodule(model, bank_name, new)
     for name, t in quant.items():
         lin = model.get_submodule(name)
@@ -384,10 +397,15 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             W = dequantized_weight(name, t, mdtype)
             _check_shape(f"{path}: {name}", W.shape, lin.weight.shape)
             lin.weight.data = W
+    if a8 and a8_fused_act:
+        for name, mlp in [(n, m) for n, m in model.named_modules() if QuantizedMLP.eligible(m)]:
+            _set_submodule(model, name, QuantizedMLP(mlp.gate_proj, mlp.up_proj, mlp.down_proj, mlp.act_fn))
     from .sequential import rename_module_prefix as _rename
 
     ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
+    if a8:
+        model._qt_checkpoint["a8_fused_act"] = a8_fused_act
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows

@@ -1,7 +1,8 @@
-"""The four modules ``load_quantized`` (engine/qlinear.py) installs in place of a checkpoint's quantized Linears and
-routed-expert banks.  Each keeps the checkpoint's integer weights in registered buffers; the weight-only pair hands them
-to the kernels, to ``dequantize`` and back to checkpoint tensors as one ``StoredWeight`` (engine/stored_weight.py).
-Only ``forward`` on device tensors needs the HIP library."""
+"""The modules ``load_quantized`` (engine/qlinear.py) installs in place of a checkpoint's quantized Linears,
+routed-expert banks and, on request, Llama-style MLPs of three quantized Linears (``QuantizedMLP``).  Each keeps the
+checkpoint's integer weights in registered buffers; the weight-only pair hands them to the kernels, to ``dequantize``
+and back to checkpoint tensors as one ``StoredWeight`` (engine/stored_weight.py).  Only ``forward`` on device tensors
+needs the HIP library."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -78,12 +79,19 @@ class QuantizedLinear(nn.Module):
                 f"col_perm={self.col_perm is not None}, bias={self.bias is not None}, "
                 f"ring_w4_min_m={self.ring_w4_min_m}")
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def quantize_rows(self, x: torch.Tensor):
+        """The rows of ``x`` as this Linear's GEMMs take them: (Xq int8 [M, K], s_x, zp_x or None)."""
         from ..hip import ops
 
-        Xq, s_x, zp_x = ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric,
-                                               col_perm=self.col_perm)
-        bias = None if self.bias is None else self.bias.to(x.dtype)
+        return ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric, col_perm=self.col_perm)
+
+    def gemm_rows(self, Xq: torch.Tensor, s_x: torch.Tensor, zp_x: Optional[torch.Tensor],
+                  out_dtype: torch.dtype) -> torch.Tensor:
+        """Quantised rows (``quantize_rows``, or any pass that equals it) times the weight: [M, N] in ``out_dtype``, on
+        the GEMM form the class docstring gives for M."""
+        from ..hip import ops
+
+        bias = None if self.bias is None else self.bias.to(out_dtype)
         M = Xq.shape[0]
         if 1 <= M <= min(self.skinny_max_m, ops.I8_SKINNY_MAX_M):
             gemm = ops.gemm_i8_skinny
@@ -102,10 +110,80 @@ class QuantizedLinear(nn.Module):
             gemm = ops.gemm_i8_mid
         else:
             gemm = ops.gemm_i8
-        y = gemm(
+        return gemm(
             Xq, s_x, self.weight, self.weight_scale, K=self.in_features, zp_x=zp_x,
-            wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=x.dtype)
-        return y.reshape(*x.shape[:-1], self.out_features)
+            wsum=None if zp_x is None else self.wsum, bias=bias, out_dtype=out_dtype)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        Xq, s_x, zp_x = self.quantize_rows(x)
+        return self.gemm_rows(Xq, s_x, zp_x, x.dtype).reshape(*x.shape[:-1], self.out_features)
+
+
+def is_silu(act_fn) -> bool:
+    """Whether ``act_fn`` is SiLU as ``qt_act_mul_quantize_i8`` states it: ``nn.SiLU``, ``F.silu`` or what
+    ``transformers.activations.ACT2FN["silu"]`` yields (a module whose forward is ``F.silu``)."""
+    if isinstance(act_fn, nn.SiLU) or act_fn is F.silu:
+        return True
+    try:
+        from transformers.activations import ACT2FN
+    except ImportError:
+        return False
+    ref = ACT2FN["silu"]
+    return act_fn is ref or (isinstance(ref, nn.Module) and type(act_fn) is type(ref))
+
+
+class QuantizedMLP(nn.Module):
+    """A Llama-style MLP ``down_proj(act_fn(gate_proj(x)) * up_proj(x))`` of three ``QuantizedLinear``s with the glue
+    between the products fused: ``x`` is quantised once for gate and up, and ``qt_act_mul_quantize_i8`` turns their
+    outputs into down's quantised rows in one pass (five launches, not eight).  The three GEMMs are the ones the
+    stand-alone Linears choose, and the fused pass equals torch's SiLU, its multiply and ``qt_quantize_tokens_i8`` to
+    the bit (include/quantool_amd.h), so the module changes speed alone.  Opt-in: ``load_quantized(...,
+    a8_fused_act=True)`` builds it where ``eligible`` holds.  The children keep their names, so state-dict keys do not
+    move."""
+
+    # parents whose forward is the plain down(act(gate(x)) * up(x)), by class name (transformers 5.x)
+    PLAIN_MLPS = ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP")
+
+    def __init__(self, gate_proj: QuantizedLinear, up_proj: QuantizedLinear, down_proj: QuantizedLinear, act_fn):
+        super().__init__()
+        reason = self.refusal(gate_proj, up_proj, down_proj, act_fn)
+        if reason:
+            raise ValueError(f"QuantizedMLP: {reason}")
+        self.gate_proj, self.up_proj, self.down_proj, self.act_fn = gate_proj, up_proj, down_proj, act_fn
+
+    @staticmethod
+    def refusal(gate, up, down, act_fn) -> Optional[str]:
+        """Why these four cannot run fused (None: they can)."""
+        if not all(isinstance(m, QuantizedLinear) for m in (gate, up, down)):
+            return "gate_proj, up_proj and down_proj must all be QuantizedLinears"
+        if not is_silu(act_fn):
+            return "act_fn is not SiLU"
+        if gate.in_features != up.in_features or gate.act_symmetric != up.act_symmetric:
+            return "gate_proj and up_proj differ in in_features or act_symmetric, so they cannot share quantised rows"
+        if (gate.col_perm is None) != (up.col_perm is None) or (
+                gate.col_perm is not None and not torch.equal(gate.col_perm, up.col_perm)):
+            return "gate_proj and up_proj differ in col_perm, so they cannot share quantised rows"
+        if not gate.out_features == up.out_features == down.in_features:
+            return "gate_proj / up_proj outputs are not down_proj's inputs"
+        return None
+
+    @classmethod
+    def eligible(cls, mlp: nn.Module) -> bool:
+        """Whether ``mlp`` is one of ``PLAIN_MLPS`` whose three Linears and activation can run fused."""
+        if type(mlp).__name__ not in cls.PLAIN_MLPS:
+            return False
+        parts = [getattr(mlp, n, None) for n in ("gate_proj", "up_proj", "down_proj", "act_fn")]
+        return cls.refusal(*parts) is None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from ..hip import ops
+
+        gate, up, down = self.gate_proj, self.up_proj, self.down_proj
+        Xq, s_x, zp_x = gate.quantize_rows(x)
+        g = gate.gemm_rows(Xq, s_x, zp_x, x.dtype)
+        u = up.gemm_rows(Xq, s_x, zp_x, x.dtype)
+        Hq, s_h, zp_h = ops.act_mul_quantize_i8(g, u, symmetric=down.act_symmetric, col_perm=down.col_perm)
+        return down.gemm_rows(Hq, s_h, zp_h, x.dtype).reshape(*x.shape[:-1], down.out_features)
 
 
 class WeightOnlyLinear(nn.Module):
@@ -240,7 +318,11 @@ class QuantizedExperts(_RoutedExperts):
     ``ops.moe_gemm_i8_wide_supported`` holds, up to R / E <= ``wide_max_rows_per_expert`` for an int8 bank and up to
     R / E <= ``wide_w4_max_rows_per_expert`` for a packed int4 bank (0: never; each format reads its own attribute
     alone).  It agrees with the tiled kernel to the bit too, so these attributes change speed alone; the skinny range
-    and the two rings keep precedence, and everything else runs the tiled kernel."""
+    and the two rings keep precedence, and everything else runs the tiled kernel.
+
+    Opt-in: with ``fused_act`` and a SiLU ``act_fn``, ``act_fn(gate) * up`` and the down product's quantiser run as one
+    pass, ``qt_act_mul_quantize_i8``, on the two halves of the gate_up output; the GEMM choice sees the same rows and
+    the output is the same to the bit."""
 
     # Decode form up to this many tokens: the measured crossover at Mixtral-8x7B's bank shapes (DESIGN.md 4.11).
     grouped_max_tokens = 16
@@ -269,6 +351,10 @@ class QuantizedExperts(_RoutedExperts):
     # gate_up (N = 28672) held back the int4 bound above is down's own; what this gives up is int4 gate_up's 7 - 11 % at
     # R / E <= 8.
     wide_max_n = 4096
+    # SiLU(gate) * up and the down product's quantiser in one pass, qt_act_mul_quantize_i8, when act_fn is SiLU: equal
+    # to the three passes it replaces to the bit.  Off by default: opt-in through
+    # ``load_quantized(..., a8_fused_act=True)``; any other act_fn keeps the three passes.
+    fused_act = False
 
     def __init__(self, hidden_size: int, intermediate_size: int, gate_up: torch.Tensor, gate_up_scale: torch.Tensor,
                  down: torch.Tensor, down_scale: torch.Tensor, act_fn: nn.Module, act_symmetric: bool):
@@ -296,8 +382,17 @@ class QuantizedExperts(_RoutedExperts):
         from ..hip import ops
 
         Xq, s_x, zp_x = ops.quantize_tokens_i8(x, symmetric=self.act_symmetric)
+        return self._gemm(part, Xq, s_x, zp_x, offsets, row_idx, tokens, x.dtype)
+
+    def _gemm(self, part: str, Xq: torch.Tensor, s_x: torch.Tensor, zp_x: Optional[torch.Tensor],
+              offsets: torch.Tensor, row_idx: Optional[torch.Tensor], tokens: int, out_dtype: torch.dtype):
+        """Quantised rows times the ``part`` weights, on the GEMM form the class docstring gives for ``tokens`` and
+        the R routed rows."""
+        from ..hip import ops
+
         w, s_w = getattr(self, part), getattr(self, f"{part}_scale")
-        R = x.shape[0] if row_idx is None else row_idx.numel()
+        K = Xq.shape[1]
+        R = Xq.shape[0] if row_idx is None else row_idx.numel()
         ring, ring_w4 = self.ring_min_rows_per_expert, self.ring_w4_min_rows_per_expert
         wide = self.wide_w4_max_rows_per_expert if self.int4 else self.wide_max_rows_per_expert
         if 1 <= tokens <= self.grouped_max_tokens:
@@ -305,18 +400,32 @@ class QuantizedExperts(_RoutedExperts):
         elif (ring > 0 and R >= ring * self.num_experts and not self.int4 and s_w.shape[2] == 1
               and ops.gemm_i8_ring_grouped_supported(Xq, w, s_w, row_idx)):
             gemm = ops.gemm_i8_ring_grouped
-        elif (ring_w4 > 0 and R >= ring_w4 * self.num_experts and self.int4 and s_w.shape[2] * 128 == x.shape[1]
+        elif (ring_w4 > 0 and R >= ring_w4 * self.num_experts and self.int4 and s_w.shape[2] * 128 == K
               and ops.moe_gemm_i8_ring_w4_supported(Xq, w, s_w, row_idx)):
             gemm = ops.moe_gemm_i8_ring_w4
-        elif (wide > 0 and R <= wide * self.num_experts and x.shape[1] >= self.wide_min_k
+        elif (wide > 0 and R <= wide * self.num_experts and K >= self.wide_min_k
               and (self.wide_max_n == 0 or w.shape[1] <= self.wide_max_n)
               and ops.moe_gemm_i8_wide_supported(Xq, w, s_w, row_idx)):
             gemm = ops.moe_gemm_i8_wide
         else:
             gemm = ops.gemm_i8_grouped
         return gemm(Xq, s_x, w, s_w, offsets, row_idx=row_idx,
-                    K=x.shape[1], zp_x=zp_x, wsum=None if zp_x is None else getattr(self, f"{part}_wsum"),
-                    out_dtype=x.dtype)
+                    K=K, zp_x=zp_x, wsum=None if zp_x is None else getattr(self, f"{part}_wsum"),
+                    out_dtype=out_dtype)
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        # the attribute decides first: ops' fused name is read only past it
+        if not (self.fused_act and is_silu(self.act_fn)):
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        from ..hip import ops
+
+        x = _rows(hidden_states, self.hidden_dim)
+        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
+        T, I = x.shape[0], self.intermediate_dim
+        Y = self._product("gate_up", x, offsets, src_token, T)
+        Xq, s_x, zp_x = ops.act_mul_quantize_i8(Y[:, :I], Y[:, I:], symmetric=self.act_symmetric)
+        y = self._gemm("down", Xq, s_x, zp_x, offsets, None, T, Y.dtype)
+        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
 
 
 class WeightOnlyExperts(_RoutedExperts):

@@ -104,6 +104,8 @@ SIGNATURES = {
                               c_int, c_int64, c_void_p]),
     "qt_quantize_tokens_i8": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "qt_act_mul_quantize_i8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_skinny": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,

@@ -534,6 +534,41 @@ def quantize_tokens_i8(X: torch.Tensor, symmetric: bool = True, col_perm: Option
     return Xq, s_x, zp_x
 
 
+ACTS = {"silu": 0}   # qt_act
+
+
+def act_mul_quantize_i8(gate: torch.Tensor, up: torch.Tensor, symmetric: bool = True,
+                        col_perm: Optional[torch.Tensor] = None, act: str = "silu", return_h: bool = False):
+    """``quantize_tokens_i8(act(gate) * up, symmetric, col_perm)`` in one pass (``qt_act_mul_quantize_i8``): gate and up
+    [M, K] bf16 / fp16 of one dtype (unit column stride, any row pitch each: the two halves of one [M, 2K] tensor are
+    taken as they are) -> (Xq, s_x, zp_x), and with ``return_h`` the intermediate ``act(gate) * up`` [M, K] as well."""
+    lib = load()
+    code = _x2d(gate, "gate")
+    if _x2d(up, "up") != code or up.shape != gate.shape or up.device != gate.device:
+        raise ValueError(f"gate and up must agree in shape, dtype and device, got {tuple(gate.shape)} {gate.dtype} "
+                         f"and {tuple(up.shape)} {up.dtype}")
+    if act not in ACTS:
+        raise ValueError(f"act must be one of {sorted(ACTS)}, got {act!r}")
+    M, K = gate.shape
+    if M == 0 or K == 0:
+        raise ValueError(f"gate must be non-empty, got shape {tuple(gate.shape)}")
+    if col_perm is not None:
+        _req(col_perm, torch.int32, "col_perm", 1)
+        if col_perm.numel() != K or not col_perm.is_contiguous():
+            raise ValueError(f"col_perm must be contiguous int32 [{K}]")
+    Xq = torch.empty((M, K), dtype=torch.int8, device=gate.device)
+    s_x = torch.empty(M, dtype=torch.float32, device=gate.device)
+    zp_x = None if symmetric else torch.empty(M, dtype=torch.int32, device=gate.device)
+    H = torch.empty((M, K), dtype=gate.dtype, device=gate.device) if return_h else None
+    # a one-row view may carry any stride(0): the pitch of a single row is never used, K keeps the host check quiet
+    ldg = gate.stride(0) if M > 1 else max(gate.stride(0), K)
+    ldu = up.stride(0) if M > 1 else max(up.stride(0), K)
+    check("qt_act_mul_quantize_i8", lib.qt_act_mul_quantize_i8(
+        gate.data_ptr(), ldg, up.data_ptr(), ldu, code, M, K, ACTS[act], _ptr(col_perm), int(bool(symmetric)),
+        Xq.data_ptr(), s_x.data_ptr(), _ptr(zp_x), _ptr(H), K, _stream()))
+    return (Xq, s_x, zp_x, H) if return_h else (Xq, s_x, zp_x)
+
+
 def _i8_operands(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, K: Optional[int],
                  zp_x: Optional[torch.Tensor], wsum: Optional[torch.Tensor], out_dtype, experts: bool = False):
     """Checks the operands of ``qt_gemm_i8`` -- or, with ``experts``, of ``qt_gemm_i8_grouped``: E weights stacked

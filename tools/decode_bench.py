@@ -39,7 +39,10 @@ and ``tokens_agree_with_dequantized`` count over all B x --new generated tokens,
 ``qt_gemm_i8_mid``); everything else stays at its default in both.  ``--pair wide`` (A8 schemes, ``--model mixtral``)
 likewise differs only in ``QuantizedExperts.wide_max_rows_per_expert`` / ``wide_w4_max_rows_per_expert`` /
 ``wide_max_n``: ``a8_wide_off`` (all 0: the banks' products past the decode range on the tiled ``qt_gemm_i8_grouped``)
-against ``a8_wide`` (the class defaults: ``qt_moe_gemm_i8_wide``).
+against ``a8_wide`` (the class defaults: ``qt_moe_gemm_i8_wide``).  ``--pair fused`` (A8 schemes, either model) loads
+the checkpoint twice, ``a8_fused_off`` with the default loader and ``a8_fused`` with ``a8_fused_act=True`` (every
+``QuantizedExperts`` with ``fused_act``, every dense MLP a ``QuantizedMLP``: SiLU(gate) * up and the quantiser in one
+``qt_act_mul_quantize_i8`` pass); the prompt's logits are asserted equal to the bit before anything is timed.
 """
 from __future__ import annotations
 
@@ -212,6 +215,36 @@ def a8_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict)
     result["speedup"] = round(t / k, 3)
 
 
+def a8_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """The A8 checkpoint loaded as ``a8_fused_off`` (the default loader) and as ``a8_fused`` (``a8_fused_act=True``),
+    decoded in turn."""
+    from quantool_amd.engine.qlinear import QuantizedExperts, QuantizedMLP
+
+    models = {"a8_fused_off": load_quantized(path, device=dev),
+              "a8_fused": load_quantized(path, device=dev, a8_fused_act=True)}
+    fused = models["a8_fused"]
+    result["quantized_mlps"] = sum(isinstance(m, QuantizedMLP) for m in fused.modules())
+    result["fused_expert_banks"] = sum(isinstance(m, QuantizedExperts) and m.fused_act for m in fused.modules())
+    assert result["quantized_mlps"] + result["fused_expert_banks"] > 0, "nothing in this checkpoint runs fused"
+    with torch.no_grad():
+        a, b = (m(input_ids=prompt).logits for m in models.values())
+    assert torch.equal(a.view(torch.int16), b.view(torch.int16)), "the prompt's logits differ with a8_fused_act"
+    result["logits_bits_equal"] = True
+    del a, b
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, model in models.items():
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    same = [x == y for x, y in zip(tokens["a8_fused_off"], tokens["a8_fused"])]
+    result["tokens_agree"] = sum(same)
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_step"]) for m in ("a8_fused_off", "a8_fused"))
+    result["speedup"] = round(t / k, 3)
+
+
 def a16_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, wide_min_tokens: int, result: dict) -> None:
     """One packed A16 sparse-MoE model (``a16_experts="packed"``) decoded as ``a16_wide_off`` (``WeightOnlyExperts``'
     ``wide_min_tokens`` = 0: the grouped GEMV) and ``a16_wide`` (``wide_min_tokens`` = the class default, or
@@ -273,9 +306,10 @@ def main():
     ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
-    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide"],
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused"],
                     help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
-                         "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; W4A16 with --model "
+                         "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; fused = a8_fused_off vs a8_fused "
+                         "(load_quantized(..., a8_fused_act=True)); W4A16 with --model "
                          "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide")
     ap.add_argument("--wide-min-tokens", type=int, default=-1,
                     help="with --scheme W4A16 --pair wide: WeightOnlyExperts.wide_min_tokens of a16_wide (default: "
@@ -299,7 +333,7 @@ def main():
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
               "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
     if args.scheme != "W4A16":
-        {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes}[args.pair](path, dev, prompt, args.new, result)
+        {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes, "fused": a8_fused_modes}[args.pair](path, dev, prompt, args.new, result)
         print(json.dumps(result))
         return
     if args.pair == "wide":

@@ -2,13 +2,15 @@
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
-                                  [--a16-stream-rows N] [--a16-experts-wide-tokens N]
+                                  [--a16-stream-rows N] [--a16-experts-wide-tokens N] [--a8-fused-act]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
 on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed`` with it: routed-expert banks on
 ``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``;
-``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
+``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``;
+``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
+``qt_act_mul_quantize_i8`` pass, the same perplexity to the bit).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
 evaluation wall times.
 """
 from __future__ import annotations
@@ -23,8 +25,8 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, WeightOnlyExperts, WeightOnlyLinear,  # noqa: E402
-                                         load_quantized)
+from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, QuantizedMLP, WeightOnlyExperts,  # noqa: E402
+                                         WeightOnlyLinear, load_quantized)
 from quantool_amd.evaluate import perplexity  # noqa: E402
 
 
@@ -42,13 +44,15 @@ def main():
     ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
+    ap.add_argument("--a8-fused-act", action="store_true",
+                    help="A8 checkpoints: run every MLP's and expert bank's glue as one qt_act_mul_quantize_i8 pass")
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
     model = load_quantized(args.checkpoint, device=args.device,
                            dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
-                           a16_experts_wide_tokens=args.a16_experts_wide_tokens)
+                           a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -58,6 +62,7 @@ def main():
     t2 = time.perf_counter()
     r.update({"checkpoint": str(args.checkpoint), "format": model._qt_checkpoint["format"],
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()),
+              "quantized_mlps": sum(isinstance(m, QuantizedMLP) for m in model.modules()),
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
               "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})

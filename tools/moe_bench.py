@@ -63,6 +63,14 @@ above): median / mean / min microseconds per form, wide speedup (grouped median 
 Then WeightOnlyExperts.forward end to end on the path it had before the wide form (wide_min_tokens = wide_max_tokens =
 0: the grouped pair up to grouped_max_tokens, the dequantise path above) against the new path (wide_min_tokens =
 --a16-wide-min-tokens, wide_max_tokens = the largest T asked for), alternating likewise.
+
+  python tools/moe_bench.py --fused-act [--tokens 1,16,32,128,512,2048,8192] [--schemes W8A8,W4A8]
+
+The A8 glue comparison, per scheme and T: ``act_fn(gate) * up`` in torch followed by qt_quantize_tokens_i8 (three
+launches) against qt_act_mul_quantize_i8 on the two halves of the same gate_up output, and QuantizedExperts.forward end
+to end with ``fused_act`` off and on, alternating call by call in one loop, each call between its own HIP events.  The
+unfused form runs twice in that loop ("unfused" and "unfused_again"): their ratio is the yardstick's own spread.  Both
+comparisons assert bit equality before anything is timed.
 """
 from __future__ import annotations
 
@@ -367,6 +375,55 @@ def _bench_a8_wide(scheme, T, qe, dev, g, args):
     return row
 
 
+def _bench_a8_fused(scheme, T, qe, dev, g, args):
+    """One glue row: the three passes between the bank's products against the fused pass on the same gate_up output,
+    and the bank's forward with ``fused_act`` off and on."""
+    from qlinear_bench import time_pair
+
+    sym = qe.act_symmetric
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = w / w.sum(-1, keepdim=True)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    row = {"scheme": scheme, "T": T, "R": T * TOPK}
+
+    def unfused(Y):
+        gate, up = Y.chunk(2, dim=-1)
+        return ops.quantize_tokens_i8(qe.act_fn(gate) * up, symmetric=sym)
+
+    def fused(Y):
+        return ops.act_mul_quantize_i8(Y[:, :I], Y[:, I:], symmetric=sym)
+
+    def bank(on):
+        def run(i):
+            qe.fused_act = on
+            return qe(x, idx, w)
+        return run
+
+    def ratios(t):
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        return {**{k: _us(v) for k, v in t.items()}, "speedup": round(med["unfused"] / med["fused"], 3),
+                "unfused_spread": round(abs(med["unfused"] / med["unfused_again"] - 1.0), 4)}
+
+    with torch.no_grad():
+        Y = qe._product("gate_up", x, offsets, src_token, T)
+        for a, b in zip(unfused(Y), fused(Y)):
+            assert (a is None and b is None) or torch.equal(a, b), "the fused pass differs from the three passes"
+        try:
+            assert torch.equal(bank(False)(0).view(torch.int16), bank(True)(0).view(torch.int16)), \
+                "the bank's output differs with fused_act"
+            row["bits_equal"] = True
+            row["glue"] = ratios(time_pair({"unfused": lambda i: unfused(Y), "fused": lambda i: fused(Y),
+                                            "unfused_again": lambda i: unfused(Y)}, args.reps, args.warmup))
+            del Y
+            row["experts"] = ratios(time_pair({"unfused": bank(False), "fused": bank(True),
+                                               "unfused_again": bank(False)}, args.reps, args.warmup))
+        finally:
+            qe.fused_act = False
+    return row
+
+
 def _bench_a16_wide(scheme, T, banks, dev, g, args, wide_max):
     """One A16 batched-decode row: the grouped and the wide form of each product and of the pair on the same routing
     and rows, and the bank's forward on the old and on the new path, cold weights."""
@@ -457,6 +514,9 @@ def main():
                          "counts instead")
     ap.add_argument("--a16-wide-min-tokens", type=int, default=1,
                     help="with --a16-wide-tokens: WeightOnlyExperts.wide_min_tokens of the bank's second timing")
+    ap.add_argument("--fused-act", action="store_true",
+                    help="W8A8 / W4A8: compare the three glue passes and qt_act_mul_quantize_i8, and the bank's forward "
+                         "with fused_act off and on, at --tokens (default then: 1,16,32,128,512,2048,8192)")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -489,6 +549,25 @@ def main():
             torch.cuda.empty_cache()
         print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A16 batched decode: qt_gemm_wq_grouped vs "
                                     "qt_moe_gemm_wq_wide",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
+
+    if args.fused_act:
+        tokens = args.tokens if args.tokens != ap.get_default("tokens") else "1,16,32,128,512,2048,8192"
+        for scheme in args.schemes.split(","):
+            if scheme not in ("W8A8", "W4A8"):
+                raise SystemExit("--fused-act compares the A8 banks' glue (W8A8 / W4A8)")
+            qe = _experts(scheme, dev, g)
+            for T in (int(t) for t in tokens.split(",")):
+                row = _bench_a8_fused(scheme, T, qe, dev, g, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del qe
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A8 glue: silu * up + qt_quantize_tokens_i8 vs "
+                                    "qt_act_mul_quantize_i8",
                           "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
                           "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
         return

@@ -5,6 +5,7 @@ tiled GEMM at decode sizes.
   python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
   python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
   python tools/qlinear_bench.py --ring-w4 [--ms 2048,4096,8192]   # W4A8 prefill: qt_gemm_i8 vs qt_gemm_i8_ring_w4
+  python tools/qlinear_bench.py --mlp [--ms 1,16,32,128,2048,8192]     # three Linears + glue vs QuantizedMLP
 
 Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N = 4096, K = 14336) and M: device time
 (HIP events, mean over --reps after --warmup) of the activation pass (qt_quantize_tokens_i8), the GEMM (qt_gemm_i8:
@@ -37,6 +38,14 @@ medians), with ``bits_equal`` per cell.
 the LDS-ring qt_gemm_i8_ring_w4 on the same operands, with qt_quantize_tokens_i8 and bf16 F.linear, under the "ring"
 rows' harness, at --ms (default 2048,4096,8192) on the three shapes, with ``bits_equal`` per cell and tiled / ring as
 "speedup".  ``QuantizedLinear.ring_w4_min_m`` is set from two such runs.
+
+--mlp prints only "mlp" rows: a Llama-3-8B MLP (hidden 4096, intermediate 14336) as W8A8 and W4A8, at --ms (default
+1,16,32,128,2048,8192).  "glue": ``F.silu(g) * u`` followed by qt_quantize_tokens_i8 (three launches) against
+qt_act_mul_quantize_i8 on the same gate / up outputs.  "mlp": ``down(silu(gate(x)) * up(x))`` on three
+``QuantizedLinear``s (eight launches) against ``QuantizedMLP`` on the same three (five), under the decode rows' harness
+(alternating call by call, per-call events, the Linears rotating over more than 512 MiB of copies, medians).  The unfused
+form runs twice in each loop ("unfused", "unfused_again"): their ratio is the yardstick's own spread.  Bit equality of the
+two forms is asserted before anything is timed.
 """
 from __future__ import annotations
 
@@ -270,6 +279,76 @@ def ring_w4_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+MLP_MS = "1,16,32,128,2048,8192"
+MLP_HIDDEN, MLP_INTER = 4096, 14336
+
+
+def mlp_rows(ms, reps, warmup, dev, g):
+    """Three QuantizedLinears and torch's glue against QuantizedMLP, and the glue alone, W8A8 and W4A8, cold weights."""
+    from quantool_amd.engine.qlinear import QuantizedMLP
+
+    rows = []
+    for scheme in ("W8A8", "W4A8"):
+        int4 = scheme == "W4A8"
+
+        def linear(K, N):
+            q = torch.randint(-8 if int4 else -128, 8 if int4 else 128, (N, K), device=dev, generator=g,
+                              dtype=torch.int8)
+            s = torch.rand(N, K // 128 if int4 else 1, device=dev, generator=g) * (1e-2 if int4 else 1e-3)
+            return QuantizedLinear(K, N, pack_int4(q) if int4 else q, s, act_symmetric=not int4)
+
+        first = [linear(MLP_HIDDEN, MLP_INTER), linear(MLP_HIDDEN, MLP_INTER), linear(MLP_INTER, MLP_HIDDEN)]
+        nbytes = sum(l.weight.numel() * l.weight.element_size() for l in first)
+        n_cp = max(3, -(-int(COLD_BYTES * 1.1) // nbytes))
+        sets = [first] + [[linear(l.in_features, l.out_features) for l in first] for _ in range(n_cp - 1)]
+        fused_sets = [QuantizedMLP(*ls, torch.nn.SiLU()) for ls in sets]
+
+        def ratios(t):
+            med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+            out = {k: {"us": round(med[k] * 1e6, 2), "min_us": round(min(v) * 1e6, 2)} for k, v in t.items()}
+            out["speedup"] = round(med["unfused"] / med["fused"], 3)
+            out["unfused_spread"] = round(abs(med["unfused"] / med["unfused_again"] - 1.0), 4)
+            return out
+
+        for M in ms:
+            x = torch.randn(M, MLP_HIDDEN, device=dev, generator=g).to(torch.bfloat16)
+            gate, up, down = first
+
+            def unfused(i):
+                ga, u, d = sets[i % n_cp]
+                return d(F.silu(ga(x)) * u(x))
+
+            def fused(i):
+                return fused_sets[i % n_cp](x)
+
+            with torch.no_grad():
+                gv, uv = gate(x), up(x)
+
+                def glue_unfused(i):
+                    return ops.quantize_tokens_i8(F.silu(gv) * uv, symmetric=down.act_symmetric)
+
+                def glue_fused(i):
+                    return ops.act_mul_quantize_i8(gv, uv, symmetric=down.act_symmetric)
+
+                for a, b in zip(glue_unfused(0), glue_fused(0)):
+                    assert (a is None and b is None) or torch.equal(a, b), "the fused pass differs from the three passes"
+                assert torch.equal(unfused(0).view(torch.int16), fused(0).view(torch.int16)), \
+                    "QuantizedMLP differs from the three Linears"
+                # forms that share a rep read different copies, or the later finds the earlier one's weights cached
+                row = {"scheme": scheme, "M": M, "hidden": MLP_HIDDEN, "intermediate": MLP_INTER, "cold_copies": n_cp,
+                       "bits_equal": True,
+                       "glue": ratios(time_pair({"unfused": glue_unfused, "fused": glue_fused,
+                                                 "unfused_again": glue_unfused}, reps, warmup)),
+                       "mlp": ratios(time_pair({"unfused": unfused, "fused": lambda i: fused(i + 1),
+                                                "unfused_again": lambda i: unfused(i + 2)}, reps, warmup))}
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr)
+            del x, gv, uv
+        del sets, fused_sets, first
+        torch.cuda.empty_cache()
+    return rows
+
+
 def _time(fn, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -294,11 +373,19 @@ def main():
     ap.add_argument("--mid", action="store_true", help="only the tiled-vs-mid rows (17 .. 128 rows and neighbours)")
     ap.add_argument("--mid-shapes", default=",".join(MID_SHAPES))
     ap.add_argument("--ring-w4", action="store_true", help="only the W4A8 tiled-vs-ring rows (qt_gemm_i8_ring_w4)")
+    ap.add_argument("--mlp", action="store_true",
+                    help="only the MLP rows: three QuantizedLinears + torch's glue vs QuantizedMLP (qt_act_mul_quantize_i8)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qlinear_bench needs a GPU")
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
+    if args.mlp:
+        ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else MLP_MS).split(",") if m]
+        print(json.dumps({"metric": "Llama-3-8B MLP, A8: three QuantizedLinears + silu * up vs QuantizedMLP, cold weights",
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                          "mlp": mlp_rows(ms, args.reps, args.warmup, dev, g)}))
+        return
     if args.mid:
         mid = []
         for shape in args.mid_shapes.split(","):
