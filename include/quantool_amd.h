@@ -171,7 +171,14 @@ int qt_weight_gather_qparams(const void* W, int w_dtype, int R, int K, int64_t l
  * blocksize must be 128 (upstream default) in this build.  Bit-exact against
  * oracle/gptq_oracle.c:orc_gptq_sweep for identical inputs -- including when the updates of columns
  * far to the right are applied for several blocks in one pass over W (env QT_SWEEP_BATCH, 1..8 blocks,
- * default 4, 8 from K = 8192: every block's product is still its own ascending-k chain, subtracted in block order). */
+ * default 4, 8 from K = 8192: every block's product is still its own ascending-k chain, subtracted in block order),
+ * and when a batch's block steps share a launch with the previous batch's far update (env QT_SWEEP_FUSED, default
+ * on up to 6144 rows; 0 = one launch per block).
+ * Workspace: 8 * blocksize * R floats (the blocks' errors of the longest batch) rounded up to 256 bytes, + 256.
+ * Where the shape and the environment at the time of the call allow the fused form (R and K multiples of 128,
+ * R <= 6144 or QT_SWEEP_FUSED=1) it holds two buffers of one batch each (a batch writes its own errors while the
+ * previous batch's far update still reads the other): no more than the above for batches of up to 4 blocks, twice
+ * it for 8 (K >= 8192 or QT_SWEEP_BATCH).  Under QT_SWEEP_FAR=bf16x3 the far update's planes and tile table on top. */
 size_t qt_gptq_sweep_workspace_bytes(int R, int K, int blocksize);
 int qt_gptq_sweep(float* W, int R, int K, const float* U, const float* scale_t, const float* zp_t,
                   int G, const int32_t* g_idx, int blocksize, int num_bits, int8_t* Qt,

@@ -151,7 +151,7 @@ def audit_m0(src: Path) -> None:
 
 # kernels whose inner loops are hand-scheduled around a fixed register budget: a spill there is a silent 20-30 %
 # (round 3: wrapping gemm3_kernel's body in an item loop let LICM hoist 128 epilogue addresses -> 179 spills)
-NO_SPILL_KERNELS = ("xtx_kernel", "xtx16_kernel", "gemm3_kernel", "sgemm_ring_kernel", "quantize_tokens_kernel",
+NO_SPILL_KERNELS = ("xtx_kernel", "xtx16_kernel", "gemm3_kernel", "sgemm_ring_kernel", "sweep_fused_kernel", "quantize_tokens_kernel",
                     "gemm_i8_kernel", "gemm_i8_ring_kernel", "gemm_i8_ring_moe_kernel", "gemm_i8_mid_kernel",
                     "gemm_i8_ring_w4_kernel", "gemm_i8_ring_w4_moe_kernel", "moe_gemm_i8_wide_kernel",
                     "moe_gemm_wq_wide_kernel")
@@ -175,7 +175,7 @@ def build(verbose: bool = False) -> Path:
     srcs = sources()
     with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         objs = list(ex.map(_compile, srcs))
-    for name in ("xtx.hip", "gemm3_tn.hip", "sgemm_tn.hip", "qlinear.hip", "qlinear_ring.hip", "qlinear_ring_w4.hip"):
+    for name in ("xtx.hip", "gemm3_tn.hip", "sgemm_tn.hip", "sweep.hip", "qlinear.hip", "qlinear_ring.hip", "qlinear_ring_w4.hip"):
         audit_m0(CSRC / name)
     newest = max(o.stat().st_mtime for o in objs)
     if not LIB_PATH.exists() or LIB_PATH.stat().st_mtime < newest:

@@ -10,6 +10,8 @@
 //                        "w = w - (err * u)" with two roundings (no contraction).
 //   sgemm_tn (SUB)     : W[:, i2:] -= Err1 @ U[i1:i2, i2:] as an ascending-k fmaf chain from 0
 //                        on the f32 MFMA, then one subtraction -- the oracle's fixed order.
+// Up to 6144 rows, on whole 128-tiles, a batch of blocks runs as ONE launch instead (sweep_fused_kernel below): its
+// block steps and near updates per group of rows, beside the far update of the batch before it.
 // Bit-exact against oracle/gptq_oracle.c:orc_gptq_sweep.
 #include <stdlib.h>
 
@@ -19,6 +21,7 @@
 
 #include "common.h"
 #include "gemm3_tn.h"
+#include "sgemm_ring.h"
 #include "sgemm_tn.h"
 
 #pragma clang fp contract(off)
@@ -473,6 +476,311 @@ __global__ __launch_bounds__(QTHREADS) void sweep_quad_kernel(float* __restrict_
     if (valid && p == 0) loss[row] = loss_in + s.lsum / 2.0f;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// sweep_fused_kernel: ONE launch = the whole batch b (all its 128-column blocks AND the near updates between
+// them) for every group of rows  +  the far update of batch b - 1 on the columns right of batch b.
+//
+// Rows of W are independent given U, and the far update of batch b - 1 right of batch b touches no column that
+// batch b reads or writes, so the two kinds of workgroup share nothing but the launch: no flag, no wait.  The
+// first n_row_wgs workgroups own 512 / NL rows each; the others run sgemm_ring_body over the far update's tiles.
+// Both kinds fit the ring's budget (512 threads, 128 registers, <= 80 KiB of LDS: two workgroups per CU, of
+// either kind), so the latency-bound block steps run on SIMDs whose MFMA pipe the far update keeps busy.
+//
+// A row workgroup, per block of the batch:
+//   * the 128 steps with NL lanes per row (lane (r, p) owns columns NL m + p): sweep_quad_kernel's step with a
+//     wider broadcast -- per ELEMENT the same operations in the same order (ascending source column,
+//     w = w - (err * u) with two roundings, IEEE divisions, rintf; loss in column order), so the same bits;
+//   * the near update of the batch's remaining columns for its own rows: per 32 x 32 tile one ascending-k
+//     chain from zero over the block's 128 k on v_mfma_f32_32x32x2f32, k paired (2 kk, 2 kk + 1) as in
+//     sgemm_tn's kernels, then one subtraction -- the bits of the separate MODE_SUB launch.  The error rows come
+//     from LDS (the steps leave them there), the U panel straight from global memory.
+// LDS: the U block's strict upper triangle per (step, float4 group, lane class): step c keeps only the groups
+// its lanes still update, 48 KiB (NL = 16) / 40 KiB (NL = 8) instead of 64; the block's errors [128][rows];
+// the diagonal.  66 560 B (NL = 16, 32 rows) / 74 752 B (NL = 8, 64 rows).
+template <int NL>
+struct LaneGeo {
+    static constexpr int NM = BS / NL;            // columns per lane
+    static constexpr int NK4 = NM / 4;            // float4 groups of a lane's columns
+    static constexpr int ROWS = 512 / NL;         // rows per workgroup
+    static constexpr int BLK = NL * 4;            // floats of one float4 group over the lane classes
+    static constexpr int BAND = 4 * NL;           // steps over which the first live group stays the same
+    // first float of step c: steps of band q = c / BAND keep groups q .. NK4 - 1
+    __host__ __device__ static constexpr int ut_base(int c) {
+        const int band = c / BAND, in = c % BAND;
+        return BLK * (BAND * (band * NK4 - band * (band - 1) / 2) + in * (NK4 - band));
+    }
+    static constexpr int UT_FLOATS = ut_base(BS);
+    static constexpr int ES_FLOATS = BS * ROWS;
+    static constexpr size_t LDS = (size_t)(UT_FLOATS + ES_FLOATS + 2 * BS) * sizeof(float);
+};
+static_assert(LaneGeo<16>::UT_FLOATS == 12288 && LaneGeo<8>::UT_FLOATS == 10240, "triangle layout");
+static_assert(LaneGeo<16>::LDS >= (size_t)RING_LDS_BYTES && LaneGeo<8>::LDS >= (size_t)RING_LDS_BYTES &&
+                  LaneGeo<16>::LDS <= 80 * 1024 && LaneGeo<8>::LDS <= 80 * 1024,
+              "the launch's LDS holds the ring, and two workgroups fit a CU");
+
+// every lane of a row's NL lanes gets lane P0's value: DPP row_share within 16 lanes; for 8 lanes the two halves
+// of a DPP row take their own source lane
+template <int NL, int P0>
+__device__ __forceinline__ float lane_bcast(float v, bool hi) {
+    const int x = __builtin_bit_cast(int, v);
+    if constexpr (NL == 16) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true));
+    } else {
+        static_assert(NL == 8, "8 or 16 lanes per row");
+        const int lo = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true);
+        const int up = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0 + 8, 0xF, 0xF, true);
+        return __builtin_bit_cast(float, hi ? up : lo);
+    }
+}
+
+template <int NL>
+struct LaneState {
+    float w[LaneGeo<NL>::NM], sc[LaneGeo<NL>::NM], zz[LaneGeo<NL>::NM];
+    float u[2][LaneGeo<NL>::NM], d[2];      // U values / diagonal of step C in parity C & 1: read one step ahead
+    float lsum, qv, ev, dv;
+};
+
+template <int NL, int C>
+__device__ __forceinline__ void lane_fetch(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd, int p) {
+    using G = LaneGeo<NL>;
+    if constexpr (C < BS) {
+        constexpr int band = C / G::BAND;
+        const f32x4* urow = (const f32x4*)(Ut + G::ut_base(C) + p * 4);
+#pragma unroll
+        for (int k4 = band; k4 < G::NK4; ++k4) {
+            const f32x4 t = urow[(k4 - band) * NL];
+            s.u[C & 1][4 * k4 + 0] = t[0]; s.u[C & 1][4 * k4 + 1] = t[1]; s.u[C & 1][4 * k4 + 2] = t[2]; s.u[C & 1][4 * k4 + 3] = t[3];
+        }
+        s.d[C & 1] = dd[C];
+    }
+}
+
+// quad_step with NL lanes per row
+template <int NL, int M0, int P0>
+__device__ __forceinline__ void lane_step(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
+                                          int p, bool hi, float qmin, float qmax) {
+    constexpr int NM = LaneGeo<NL>::NM;
+    constexpr int C = NL * M0 + P0;
+    lane_fetch<NL, C + 1>(s, Ut, dd, p);
+    const float* u = s.u[C & 1];
+    const float d = s.d[C & 1];
+    const float wv = s.w[M0];
+    float x = wv / s.sc[M0];
+    x = x + s.zz[M0];
+    x = fminf(fmaxf(x, qmin), qmax);
+    const float q = rintf(x);
+    const float dq = (q - s.zz[M0]) * s.sc[M0];
+    const float diff = wv - dq;
+    const float e = diff / d;
+    const bool own = p == P0;
+    s.dv = own ? diff : s.dv;
+    s.qv = own ? q : s.qv;
+    s.ev = own ? e : s.ev;
+    const float eb = lane_bcast<NL, P0>(e, hi);
+    {
+        const float pr = eb * u[M0];
+        const float t = s.w[M0] - pr;
+        s.w[M0] = p > P0 ? t : (own ? dq : s.w[M0]);
+    }
+    constexpr int MS = M0 + 1;
+    if (MS < NM && (MS & 1)) {
+        const float pr = eb * u[MS];
+        s.w[MS] = s.w[MS] - pr;
+    }
+    const f32x2 e2 = {eb, eb};
+#pragma unroll
+    for (int m = (MS + 1) & ~1; m < NM; m += 2) {
+        const f32x2 uu = {u[m], u[m + 1]};
+        const f32x2 pr = e2 * uu;
+        f32x2 wp = {s.w[m], s.w[m + 1]};
+        wp = wp - pr;
+        s.w[m] = wp[0];
+        s.w[m + 1] = wp[1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int NL, int M0, int P0>
+__device__ __forceinline__ void lane_steps(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
+                                           int p, bool hi, float qmin, float qmax) {
+    if constexpr (P0 < NL) {
+        lane_step<NL, M0, P0>(s, Ut, dd, p, hi, qmin, qmax);
+        lane_steps<NL, M0, P0 + 1>(s, Ut, dd, p, hi, qmin, qmax);
+    }
+}
+
+// the row's loss: the NL columns' terms of a macro-step added in column order, in every lane of the row alike
+template <int NL, int P0>
+__device__ __forceinline__ void lane_loss(LaneState<NL>& s, float t, bool hi) {
+    if constexpr (P0 < NL) {
+        s.lsum = s.lsum + lane_bcast<NL, P0>(t, hi);
+        lane_loss<NL, P0 + 1>(s, t, hi);
+    }
+}
+
+template <int NL, int M0>
+__device__ __forceinline__ void lane_run(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
+                                         float* __restrict__ Es, int p, bool hi, int rl, float qmin, float qmax, int row,
+                                         int R, int i1, int8_t* __restrict__ Qt, float* __restrict__ ErrB) {
+    if constexpr (M0 < LaneGeo<NL>::NM) {
+        lane_steps<NL, M0, 0>(s, Ut, dd, p, hi, qmin, qmax);
+        // every lane now holds the level, the error and the rounding residual of its own column NL M0 + p
+        const int c = NL * M0 + p;
+        lane_loss<NL, 0>(s, (s.dv * s.dv) * dd[BS + c], hi);
+        asm volatile("" : "+v"(s.lsum));     // summed here: left alone, hipcc keeps all 128 terms for one sum at the block's end (spills)
+        Qt[(size_t)(i1 + c) * R + row] = (int8_t)s.qv;
+        ErrB[(size_t)c * R + row] = s.ev;
+        Es[c * LaneGeo<NL>::ROWS + rl] = s.ev;
+        lane_run<NL, M0 + 1>(s, Ut, dd, Es, p, hi, rl, qmin, qmax, row, R, i1, Qt, ErrB);
+    }
+}
+
+struct FusedArgs {
+    float* W;
+    int R, K;
+    const float* U;
+    const float* scale_t;
+    const float* zp_t;
+    const int32_t* g_idx;
+    int b0, nblk;              // the batch: columns [b0, b0 + 128 nblk)
+    float qmin, qmax;
+    int8_t* Qt;
+    float* ErrT;               // [nblk * 128][R], this batch's buffer
+    float* loss;
+    int prio;
+    int n_row_wgs;             // the launch's first workgroups; the others walk the far update's tiles
+};
+
+template <int NL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sweep_fused_kernel(const FusedArgs f,
+                                                                                                     const SweepGroups sg,
+                                                                                                     const RingArgs far) {
+    using G = LaneGeo<NL>;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    if ((int)blockIdx.x >= f.n_row_wgs) {
+        sgemm_ring_body<true>(far, (char*)sm, f.n_row_wgs);
+        return;
+    }
+    qt_set_chain_prio(f.prio);
+    const int R = f.R, K = f.K;
+    const float* U = f.U;
+    const int32_t* g_idx = f.g_idx;
+    const int row0 = blockIdx.x * G::ROWS;
+    if (sg.n > 1) {
+        const int g = sweep_group_of(sg, row0);
+        U += (size_t)g * sg.bsU;
+        g_idx += (size_t)g * K;
+    }
+    float* Ut = sm;                          // the U block's triangle (LaneGeo::ut_base)
+    float* Es = sm + G::UT_FLOATS;           // [BS k][ROWS]: the block's errors, the near update's A operand
+    float* dd = Es + G::ES_FLOATS;           // [BS] diag, [BS] 1 / diag^2
+    float* W = f.W;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int bend = f.b0 + f.nblk * BS;
+    float lrow = (threadIdx.x & (NL - 1)) == 0 ? f.loss[row0 + threadIdx.x / NL] : 0.0f;
+
+    for (int blk = 0; blk < f.nblk; ++blk) {
+        // Every per-lane index of a block is derived from this opaque copy of the thread id: were they loop
+        // invariants, hipcc would compute the block's ~100 per-lane addresses once in front of the loop and keep
+        // them in scratch (the build refuses a private segment); recomputing them costs a few dozen integer
+        // operations per 128 steps.
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63;
+        const int p = tid & (NL - 1), rl = tid / NL;
+        const bool hi = (tid & 8) != 0;
+        const int row = row0 + rl;               // R % 128 == 0: every row exists
+        const int h = lane >> 5, l31 = lane & 31;
+        const int i1 = f.b0 + blk * BS, i2 = i1 + BS;
+        const float* ublk = U + (size_t)i1 * K + i1;
+        {   // the U block, strictly above the diagonal: 8 independent float4 loads per thread, then LDS
+            f32x4 v[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int e4 = tid + 512 * r;                      // float4 index in the 128 x 32 grid
+                const int i = e4 >> 5, jj = e4 & 31;
+                v[r] = *(const f32x4*)(ublk + (size_t)i * K + jj * 4);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int e4 = tid + 512 * r;
+                const int i = e4 >> 5, jj = e4 & 31;
+                const int m = jj / (NL / 4), pc = (jj % (NL / 4)) * 4;      // columns 4 jj + q = NL m + pc + q
+                const int k4 = m >> 2, band = i / G::BAND;
+                if (k4 >= band) {
+                    float* dst = Ut + G::ut_base(i) + (k4 - band) * G::BLK + pc * 4 + (m & 3);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) dst[q * 4] = (jj * 4 + q > i) ? v[r][q] : 0.0f;
+                }
+            }
+        }
+        if (tid < BS) {
+            const float d = ublk[(size_t)tid * K + tid];
+            dd[tid] = d;
+            dd[BS + tid] = 1.0f / (d * d);
+        }
+        LaneState<NL> s;
+        {
+            const float* wrow = W + (size_t)row * K + i1 + p;
+            const int32_t* gcol = g_idx + i1 + p;
+#pragma unroll
+            for (int m = 0; m < G::NM; ++m) {
+                s.w[m] = wrow[NL * m];
+                const int g = gcol[NL * m];
+                s.sc[m] = f.scale_t[(size_t)g * R + row];
+                s.zz[m] = f.zp_t[(size_t)g * R + row];
+            }
+        }
+        s.lsum = 0.0f;
+        s.qv = 0.0f;
+        s.ev = 0.0f;
+        s.dv = 0.0f;
+        __syncthreads();
+        lane_fetch<NL, 0>(s, Ut, dd, p);
+        lane_run<NL, 0>(s, Ut, dd, Es, p, hi, rl, f.qmin, f.qmax, row, R, i1, f.Qt, f.ErrT + (size_t)blk * BS * R);
+        {   // dequantised values back to W (upstream: W[:, i1:i2] = Q1)
+            float* wrow = W + (size_t)row * K + i1 + p;
+#pragma unroll
+            for (int m = 0; m < G::NM; ++m) wrow[NL * m] = s.w[m];
+        }
+        lrow = lrow + s.lsum / 2.0f;
+        if (blk + 1 == f.nblk) break;
+        __syncthreads();      // the block's errors are in Es; nobody reads Ut any more
+        // near update of the batch's remaining columns, this workgroup's rows: W[rows, i2:bend] -= Es^T U[i1:i2, i2:bend]
+        {
+            const int tiles_n = (bend - i2) / 32;
+            const int n_t = tiles_n * (G::ROWS / 32);
+            for (int t = wave; t < n_t; t += 8) {
+                const int tm = t / tiles_n, tn = t - tm * tiles_n;
+                const int col0 = i2 + tn * 32;
+                float* cp = W + (size_t)(row0 + tm * 32 + 4 * h) * K + col0 + l31;
+                float cin[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) cin[r] = cp[(size_t)((r & 3) + 8 * (r >> 2)) * K];
+                const float* bp = U + (size_t)(i1 + h) * K + col0 + l31;
+                const float* ap = Es + h * G::ROWS + tm * 32 + l31;
+                f32x16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+                for (int k0 = 0; k0 < BS / 2; k0 += 16) {
+                    float b[16];
+#pragma unroll
+                    for (int kk = 0; kk < 16; ++kk) b[kk] = bp[(size_t)(2 * (k0 + kk)) * K];
+#pragma unroll
+                    for (int kk = 0; kk < 16; ++kk) {
+                        const float a = ap[2 * (k0 + kk) * G::ROWS];
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[kk], acc, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) cp[(size_t)((r & 3) + 8 * (r >> 2)) * K] = cin[r] - acc[r];
+            }
+        }
+        __syncthreads();      // the next block's columns are up to date for every row of the workgroup
+    }
+    if ((threadIdx.x & (NL - 1)) == 0) f.loss[row0 + threadIdx.x / NL] = lrow;
+}
+
 }  // namespace
 
 // OPT-IN, NOT the parity contract (QT_SWEEP_FAR=bf16x3): the far update as a three-plane bf16 product (gemm3_tn.h) instead
@@ -502,9 +810,39 @@ static FarPlan far_plan(int R, int K, int blocksize) {
     return f;
 }
 
+static size_t sweep_err_bytes(int R, int blocksize) {
+    return qt_align_up((size_t)SWEEP_MAX_BATCH * blocksize * R * 4, 256);
+}
+
+// Blocks per batch: 4, 8 from K = 8192 (measurements at the batch loop in sweep_run); QT_SWEEP_BATCH forces it.
+static int sweep_batch_blocks(int K) {
+    const char* e = getenv("QT_SWEEP_BATCH");
+    const int b = e ? atoi(e) : (K >= 8192 ? 8 : 4);
+    return b < 1 ? 1 : (b > SWEEP_MAX_BATCH ? SWEEP_MAX_BATCH : b);
+}
+
+// One of the fused form's two error buffers: the errors of one batch as long as this call's batches are.  Two
+// batches of up to 4 blocks fit the room the chain of launches has always asked for (8 blocks).
+static size_t sweep_fused_err_bytes(int R, int K, int blocksize) {
+    return qt_align_up((size_t)sweep_batch_blocks(K) * blocksize * R * 4, 256);
+}
+
+// Whether a sweep of this shape may take the fused form (sweep_fused_kernel), as far as shape and environment say:
+// whole 128-tiles, the f32 far update, and up to 6144 rows unless QT_SWEEP_FUSED=1 asks for it at any height
+// (QT_SWEEP_FUSED=0: never).  Read per call; the workspace holds the second error buffer only where this holds.
+static bool sweep_fused_shape(int R, int K) {
+    const char* e = getenv("QT_SWEEP_FUSED");
+    return !(e && e[0] == '0') && (R <= 6144 || (e && e[0] == '1')) && K % BS == 0 && R % 128 == 0 &&
+           !sweep_far_bf16x3(R, K);
+}
+
 extern "C" size_t qt_gptq_sweep_workspace_bytes(int R, int K, int blocksize) {
     if (R <= 0 || blocksize <= 0) return 0;
-    size_t n = qt_align_up((size_t)SWEEP_MAX_BATCH * blocksize * R * 4, 256) + 256;  // ErrT[batch][blocksize][R]
+    // ErrT[8][blocksize][R]; the fused form needs two buffers of one batch each: a batch writes one while the far
+    // update of the batch before it, running in the same launch, still reads the other
+    size_t n = sweep_err_bytes(R, blocksize);
+    if (sweep_fused_shape(R, K) && 2 * sweep_fused_err_bytes(R, K, blocksize) > n) n = 2 * sweep_fused_err_bytes(R, K, blocksize);
+    n += 256;
     if (sweep_far_bf16x3(R, K)) {
         const FarPlan f = far_plan(R, K, blocksize);
         n += f.u_bytes + f.e_bytes + f.tab_bytes;
@@ -532,7 +870,7 @@ static int sweep_run(float* W, int R, int K, const float* U, const float* scale_
     G3Item* far_tab = nullptr;
     if (far3) {
         fp = far_plan(R, K, blocksize);
-        char* q = (char*)ErrT + qt_align_up((size_t)SWEEP_MAX_BATCH * blocksize * R * 4, 256);
+        char* q = (char*)ErrT + sweep_err_bytes(R, blocksize);      // (never beside the fused form's second error buffer)
         Upl = (unsigned short*)q;
         q += fp.u_bytes;
         Epl = (unsigned short*)q;
@@ -561,11 +899,7 @@ static int sweep_run(float* W, int R, int K, const float* U, const float* scale_
     // Batch size: 4 blocks, 8 from K = 8192 up -- a longer batch halves the far update's traffic on W again but puts
     // more near-update columns between two block kernels (K = 14336 / R = 4096: 11.74 -> 11.35 ms; K = 4096 /
     // R = 28672: 5.9 -> 6.0 ms; K = 8192: +-0.5 %, profiles/r03_sweep_batch_ab.txt).  The bits do not depend on it.  QT_SWEEP_BATCH forces it.
-    const int batch_blocks = [&] {
-        const char* e = getenv("QT_SWEEP_BATCH");
-        const int b = e ? atoi(e) : (K >= 8192 ? 8 : 4);
-        return b < 1 ? 1 : (b > SWEEP_MAX_BATCH ? SWEEP_MAX_BATCH : b);
-    }();
+    const int batch_blocks = sweep_batch_blocks(K);
     const int prio = qt_chain_prio();
     // stacked problems: an update product's B operand (rows of U) depends on the row group of the output tile
     auto set_groups = [&](SgemmArgs& g) {
@@ -603,6 +937,93 @@ static int sweep_run(float* W, int R, int K, const float* U, const float* scale_
             }
         }
         QT_HIP(hipMemcpyAsync(far_tab, host, (size_t)fp.Tm * fp.Tn_max * sizeof(G3Item), hipMemcpyHostToDevice, stream));
+    }
+    // The fused form (sweep_fused_kernel): per batch b the stream carries far_near(b - 1) -- the far update of batch
+    // b - 1 on batch b's own columns -- and then ONE launch of [batch b's block steps and near updates] beside
+    // [far_rest(b - 1): the same far update on every column right of batch b].  far_near and far_rest are a column
+    // split of the one far update: the same chains in the same order per element.  Per element the subtractions
+    // still arrive in ascending block order (far_rest(b - 1) precedes far_near(b) and far_rest(b) on the stream).
+    // ErrT is double-buffered: batch b writes buffer b & 1 while far_rest(b - 1) reads the other.
+    // QT_SWEEP_FUSED=0 (read per call) forces the chain of launches below; so do shapes off the ring's whole tiles.
+    // Unset, the fused form is taken up to 6144 rows: the row workgroups run the quantise step in all 16 (8) lanes of a
+    // row, 2.6 (1.5) times the vector work of four lanes per row.  That is free while they are a latency-bound chain on
+    // a chip the far update fills, and a loss once the rows alone fill the chip (K = 4096 / R = 28672: 5.76 ms as
+    // launches, 6.02 fused with 8 lanes, 6.90 with 16; K = 14336 / R = 4096: 11.3 -> 9.45 ms with 16, 10.2 with 8;
+    // K = 4096 / R = 6144: 2.35 -> 1.97; profiles/sweep_fused_ab.txt, sweep_fused_stage_times_*.txt).  6144 is the
+    // tallest shape measured faster; with the form taken up to 8192 rows the Llama-3-70B layer (R = 8192 at K = 8192 and
+    // 28672) ran 340 ms per step against the parent's 324 in the one run made.  QT_SWEEP_FUSED=1 takes it at any height.
+    bool fused = sweep_fused_shape(R, K) && quad && (((uintptr_t)U | (uintptr_t)ErrT) & 15) == 0 &&
+                 (sg.n <= 1 || sg.bsU % 4 == 0);
+    if (fused) {
+        SgemmArgs probe;     // the far update's shape as the ring sees it (column count and offsets are multiples of 128)
+        probe.A = ErrT; probe.lda = R;
+        probe.B = U; probe.ldb = K;
+        probe.Cin = W; probe.ldcin = K;
+        probe.Cout = W; probe.ldcout = K;
+        probe.M = R; probe.N = BS; probe.kdim = BS * batch_blocks; probe.k_mode = SG_K_FULL; probe.mode = SG_MODE_SUB;
+        probe.chain_len = BS;
+        fused = sgemm_ring_applies(probe);
+    }
+    if (fused) {
+        // Lanes per row: 16 (32 rows per workgroup: R / 32 workgroups, the shortest step); QT_SWEEP_LANES=8 selects 8
+        // (64 rows per workgroup), slower at both measured heights (above) and kept for A/B runs.
+        const char* lanes_env = getenv("QT_SWEEP_LANES");
+        const int lanes = lanes_env && atoi(lanes_env) == 8 ? 8 : 16;
+        static QtOncePerDevice lds_attr_f16, lds_attr_f8;
+        QT_HIP(lds_attr_f16.run([&] {
+            return hipFuncSetAttribute((const void*)sweep_fused_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)LaneGeo<16>::LDS);
+        }));
+        QT_HIP(lds_attr_f8.run([&] {
+            return hipFuncSetAttribute((const void*)sweep_fused_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)LaneGeo<8>::LDS);
+        }));
+        float* Err[2] = {ErrT, (float*)((char*)ErrT + sweep_fused_err_bytes(R, K, blocksize))};
+        const int span = BS * batch_blocks;
+        const int n_row_wgs = R / (512 / lanes);
+        int b = 0;
+        for (int b0 = 0; b0 < K; b0 += span, ++b) {
+            const int bend = (b0 + span < K) ? b0 + span : K;
+            RingArgs far{};
+            int far_wgs = 0;
+            if (b > 0) {
+                SgemmArgs g;
+                g.A = Err[(b - 1) & 1]; g.lda = R;
+                g.B = U + (size_t)(b0 - span) * K + b0; g.ldb = K;
+                g.Cin = W + b0; g.ldcin = K;
+                g.Cout = W + b0; g.ldcout = K;
+                g.M = R; g.N = bend - b0; g.kdim = span; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
+                g.chain_len = BS;
+                set_groups(g);
+                const int rc = qt_sgemm_tn(g, stream);       // far_near(b - 1)
+                if (rc) return rc;
+                if (bend < K) {                              // far_rest(b - 1)
+                    g.B = U + (size_t)(b0 - span) * K + bend;
+                    g.Cin = W + bend;
+                    g.Cout = W + bend;
+                    g.N = K - bend;
+                    far = sgemm_ring_args(g);
+                    // two workgroups per CU, 256 CUs: what the row workgroups leave, at least one per CU
+                    const int room = 512 - n_row_wgs > 256 ? 512 - n_row_wgs : 256;
+                    far_wgs = far.n_tiles < room ? far.n_tiles : room;
+                }
+            }
+            FusedArgs f;
+            f.W = W; f.R = R; f.K = K; f.U = U; f.scale_t = scale_t; f.zp_t = zp_t; f.g_idx = g_idx;
+            f.b0 = b0; f.nblk = (bend - b0) / BS;
+            f.qmin = qmin; f.qmax = qmax; f.Qt = Qt; f.ErrT = Err[b & 1]; f.loss = loss; f.prio = prio;
+            f.n_row_wgs = n_row_wgs;
+            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
+            if (lanes == 16)
+                hipLaunchKernelGGL(sweep_fused_kernel<16>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<16>::LDS, stream, f,
+                                   sg, far);
+            else
+                hipLaunchKernelGGL(sweep_fused_kernel<8>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<8>::LDS, stream, f,
+                                   sg, far);
+            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
+            QT_LAUNCH_CHECK();
+        }
+        return QT_OK;
     }
     for (int b0 = 0; b0 < K; b0 += BS * batch_blocks) {
         const int bend = (b0 + BS * batch_blocks < K) ? b0 + BS * batch_blocks : K;   // first column right of the batch
