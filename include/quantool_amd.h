@@ -427,7 +427,38 @@ int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, in
  *   So (Xq, s_x, zp_x) equal qt_quantize_tokens_i8(F.silu(gate) * up) to the bit wherever this expf is torch's (pinned
  *   over all 65536 patterns of both dtypes by the tests).  One workgroup per row: h is computed once,
  *   held in LDS as 16-bit values (2 K bytes) while min / max are reduced, and quantised from there.  A row's result
- *   depends on the row alone.  Deterministic, no atomics, no workspace.  (csrc/act_quant.hip) */
+ *   depends on the row alone.  Deterministic, no atomics, no workspace.  (csrc/act_quant.hip)
+ *
+ * qt_rmsnorm_quantize_i8: the glue in front of the products that share one normalised input (q/k/v, gate/up) in one row
+ *   pass -- y = weight * RMSNorm(x) as transformers' LlamaRMSNorm.forward leaves it in a 16-bit tensor, then
+ *   qt_quantize_tokens_i8 on y.  X is [M, K] bf16 / fp16 (x_dtype) with unit column stride and row pitch ldx >= K, weight
+ *   [K] in x_dtype; neither needs alignment: 16-byte loads are taken when both pointers, ldx and K allow, element
+ *   loads otherwise.  Xq, s_x, zp_x, col_perm and symmetric mean what they mean in qt_act_mul_quantize_i8, the clamp of
+ *   a malformed col_perm entry into the row included.  Y (may be NULL): when given, y is stored as [M, K] in x_dtype
+ *   with row pitch ldy >= K, in natural column order (col_perm does not apply to it); it is what the residual stream
+ *   and every consumer that does not take Xq read.  rstd (may be NULL): fp32 [M], the row's r below.  A null X, weight,
+ *   Xq or s_x, M <= 0, K <= 0, ldx < K, Y given with ldy < K, an x_dtype that is not 16-bit, asymmetric activations
+ *   without zp_x, an eps that is negative or not finite, K > 32768 (the GEMMs' bound) and M > INT32_MAX are
+ *   QT_ERR_INVALID before any launch, and qt_last_error names the reason.  Fixed sequence per row, in fp32 with no
+ *   contraction (every multiply and add its own rounding):
+ *     1. sq_k = x_k * x_k
+ *     2. lane t of 256 owns the 8-element chunks c = t (mod 256), chunk c being columns 8c ... 8c+7, and adds their
+ *        sq_k to its partial in ascending k, starting from 0.0f (the element-load path walks the same chunks)
+ *     3. the lane partials combine by the xor butterfly 32, 16, ..., 1 inside each wave of 64, then
+ *        sum = ((wave0 + wave1) + wave2) + wave3
+ *     4. mean = sum * (1.0f / (float)K);  v = mean + eps;  r = (float)(1.0 / sqrt((double)v)), the correctly rounded
+ *        fp32 value of 1 / sqrt(v), which is what torch.rsqrt returns on the device (rsqrtf, the hardware's approximation,
+ *        is 1 ulp off in about one value of ten);  rstd[m] = r
+ *     5. n_k = (x_k * r) rounded once to x_dtype (RNE);  y_k = ((float)w_k * (float)n_k) rounded once to x_dtype (RNE)
+ *        -- the normalised row is narrowed before the weight multiplies it, as LlamaRMSNorm.forward does
+ *     6. exactly qt_quantize_tokens_i8's row sequence on y: min / max including 0, s, zp,
+ *        q = rint(clamp(y / s + zp, -128, 127)), Xq[m, k] = q(y[m, col_perm[k]]).
+ *   The sum order of steps 2 and 3 depends on K alone -- not on alignment, pitch, M or the row's index -- so a row's
+ *   result depends on the row alone.  It is not torch's order: given r, Y is exactly step 5 and (Xq, s_x, zp_x) are
+ *   exactly qt_quantize_tokens_i8(Y); r itself is within (8 ceil(K/2048) + 13) 2^-24 (relative) of the exact value and
+ *   equals torch's to the bit wherever the sum of squares is exact in fp32.  One workgroup per row: the
+ *   row is held in LDS as 16-bit values (2 K bytes), x first and y in its place.  Deterministic, no atomics, no
+ *   workspace.  (csrc/rmsnorm_quant.hip) */
 enum qt_act { QT_ACT_SILU = 0 };
 #define QT_I8_MID_MAX_M 128
 #define QT_I8_MID_K_UNIT 128
@@ -446,6 +477,9 @@ int qt_quantize_tokens_i8(const void* X, int x_dtype, int64_t M, int K, int64_t 
 int qt_act_mul_quantize_i8(const void* gate, int64_t ldg, const void* up, int64_t ldu, int x_dtype, int64_t M, int K,
                            int act, const int32_t* col_perm, int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x,
                            void* H, int64_t ldh, qt_stream_t stream);
+int qt_rmsnorm_quantize_i8(const void* X, int64_t ldx, const void* weight, int x_dtype, int64_t M, int K, float eps,
+                           const int32_t* col_perm, int symmetric, int8_t* Xq, float* s_x, int32_t* zp_x,
+                           void* Y, int64_t ldy, float* rstd, qt_stream_t stream);
 int qt_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                int out_dtype, int64_t ldy, qt_stream_t stream);

@@ -1,6 +1,6 @@
 // The per-token int8 activation quantiser's constants and per-row / per-element steps (include/quantool_amd.h,
-// qt_quantize_tokens_i8), shared by the kernels that end in it: quantize_tokens_kernel (qlinear.hip) and
-// act_mul_quantize_kernel (act_quant.hip).
+// qt_quantize_tokens_i8), shared by the kernels that end in it: quantize_tokens_kernel (qlinear.hip),
+// act_mul_quantize_kernel (act_quant.hip) and rmsnorm_quantize_kernel (rmsnorm_quant.hip).
 #pragma once
 #include <float.h>
 

@@ -37,7 +37,8 @@ the HIP library.
 
 With ``a8_fused_act=True`` an A8 checkpoint's MLP glue -- SiLU(gate) * up and the quantiser of the down product -- runs
 as one pass (``qt_act_mul_quantize_i8``): ``QuantizedExperts.fused_act`` in a bank, a ``QuantizedMLP`` in place of a
-Llama-style dense MLP.
+Llama-style dense MLP.  With ``a8_fused_norm=True`` the RMSNorms in front of q/k/v and gate/up become
+``QuantizingRMSNorm``s: the norm and the quantiser its consumers share run as one pass (``qt_rmsnorm_quantize_i8``).
 
 The modules are defined in ``qmodules.py`` and one stored weight as a value (``StoredWeight``: the only reader of a
 module's checkpoint tensors, the kernels' layout rules, ``dequantize``, the stacking of experts into a bank) in
@@ -53,7 +54,8 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .qmodules import QuantizedExperts, QuantizedLinear, QuantizedMLP, WeightOnlyExperts, WeightOnlyLinear
+from .qmodules import (QuantizedExperts, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm, SharedRows,  # noqa: F401
+                       WeightOnlyExperts, WeightOnlyLinear)
 from .serialization import load_state
 from .stored_weight import GROUP, StoredWeight, group_sums, pack_int4, unpack_int4  # noqa: F401 (re-exported)
 
@@ -269,6 +271,26 @@ def _load_bank(path, bank_name: str, bank: nn.Module, experts: Dict[int, Dict[st
                              down_zero_point=down.zero_point, down_g_idx=down.g_idx)
 
 
+def _install_quantizing_norms(model: nn.Module) -> None:
+    """``a8_fused_norm``: in every decoder layer of ``QuantizingRMSNorm.PLAIN_LAYERS``, ``input_layernorm`` quantises for
+    ``self_attn.{q,k,v}_proj`` and ``post_attention_layernorm`` for ``mlp.{gate,up}_proj`` (a plain MLP, or a
+    ``QuantizedMLP``, which quantises once for both), wherever ``QuantizingRMSNorm.refusal`` is None."""
+    for name, layer in [(n, m) for n, m in model.named_modules()
+                        if type(m).__name__ in QuantizingRMSNorm.PLAIN_LAYERS]:
+        feeds = [("input_layernorm", getattr(layer, "self_attn", None), ("q_proj", "k_proj", "v_proj"))]
+        mlp = getattr(layer, "mlp", None)
+        if isinstance(mlp, QuantizedMLP) or type(mlp).__name__ in QuantizedMLP.PLAIN_MLPS:
+            feeds.append(("post_attention_layernorm", mlp, ("gate_proj", "up_proj")))
+        for norm_name, parent, names in feeds:
+            norm = getattr(layer, norm_name, None)
+            consumers = [getattr(parent, n, None) for n in names]
+            if norm is None or parent is None or QuantizingRMSNorm.refusal(norm, consumers) is not None:
+                continue
+            takes = 1 if isinstance(parent, QuantizedMLP) else len(consumers)
+            _set_submodule(model, f"{name}.{norm_name}",
+                           QuantizingRMSNorm(norm.weight, norm.variance_epsilon, consumers, takes=takes))
+
+
 A16_MODES = ("dequantized", "packed")
 # The largest ``a16_experts_wide_tokens``: the largest call size at which qt_moe_gemm_wq_wide was measured (DESIGN.md
 # 4.19).
@@ -277,7 +299,8 @@ A16_EXPERTS_WIDE_MAX_TOKENS = 2048
 
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
-                   a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False) -> nn.Module:
+                   a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
+                   a8_fused_norm: bool = False) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -298,6 +321,13 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``fused_act`` on every ``QuantizedExperts`` built and puts a ``QuantizedMLP`` in place of every dense MLP for which
     ``QuantizedMLP.eligible`` holds (a Llama-style MLP of three ``QuantizedLinear``s with SiLU); state-dict keys do not
     move, and it is recorded under ``"a8_fused_act"``.  A16 checkpoints ignore it.
+    ``a8_fused_norm`` (False, the default, or True) runs the RMSNorm in front of q/k/v and of gate/up and the quantiser
+    those Linears share as one pass, ``qt_rmsnorm_quantize_i8``: in every decoder layer of
+    ``QuantizingRMSNorm.PLAIN_LAYERS`` it puts a ``QuantizingRMSNorm`` in place of ``input_layernorm`` and (not in a
+    Mixtral layer, whose second norm feeds the router and the bank) of ``post_attention_layernorm`` wherever
+    ``QuantizingRMSNorm.refusal`` is None.  The norm's sum over K runs in the kernel's order, not torch's, so outputs may
+    differ from the default loader's in rare last bits; state-dict keys do not move, and it is recorded
+    under ``"a8_fused_norm"``.  A16 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -331,6 +361,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                          "to run on)")
     if type(a8_fused_act) is not bool:
         raise ValueError(f"a8_fused_act={a8_fused_act!r}: expected True or False")
+    if type(a8_fused_norm) is not bool:
+        raise ValueError(f"a8_fused_norm={a8_fused_norm!r}: expected True or False")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -400,12 +432,15 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if a8 and a8_fused_act:
         for name, mlp in [(n, m) for n, m in model.named_modules() if QuantizedMLP.eligible(m)]:
             _set_submodule(model, name, QuantizedMLP(mlp.gate_proj, mlp.up_proj, mlp.down_proj, mlp.act_fn))
+    if a8 and a8_fused_norm:
+        _install_quantizing_norms(model)
     from .sequential import rename_module_prefix as _rename
 
     ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
     model._qt_checkpoint = {"path": str(path), "format": fmt, "input_activations": acts, "ignore": ignore}
     if a8:
         model._qt_checkpoint["a8_fused_act"] = a8_fused_act
+        model._qt_checkpoint["a8_fused_norm"] = a8_fused_norm
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows

@@ -79,8 +79,16 @@ class QuantizedLinear(nn.Module):
                 f"col_perm={self.col_perm is not None}, bias={self.bias is not None}, "
                 f"ring_w4_min_m={self.ring_w4_min_m}")
 
+    # A ``SharedRows`` a ``QuantizingRMSNorm`` in front of this Linear fills (None, the default: nobody does).
+    rows_from = None
+
     def quantize_rows(self, x: torch.Tensor):
-        """The rows of ``x`` as this Linear's GEMMs take them: (Xq int8 [M, K], s_x, zp_x or None)."""
+        """The rows of ``x`` as this Linear's GEMMs take them: (Xq int8 [M, K], s_x, zp_x or None).  Where a norm in
+        front has quantised exactly this tensor already (``rows_from``), its rows are taken."""
+        if self.rows_from is not None:
+            rows = self.rows_from.take(x)
+            if rows is not None:
+                return rows
         from ..hip import ops
 
         return ops.quantize_tokens_i8(_rows(x, self.in_features), symmetric=self.act_symmetric, col_perm=self.col_perm)
@@ -184,6 +192,147 @@ class QuantizedMLP(nn.Module):
         u = up.gemm_rows(Xq, s_x, zp_x, x.dtype)
         Hq, s_h, zp_h = ops.act_mul_quantize_i8(g, u, symmetric=down.act_symmetric, col_perm=down.col_perm)
         return down.gemm_rows(Hq, s_h, zp_h, x.dtype).reshape(*x.shape[:-1], down.out_features)
+
+
+def _version_of(t: torch.Tensor) -> Optional[int]:
+    """``t``'s in-place write counter, or None where torch keeps none (inference tensors)."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
+
+
+class SharedRows:
+    """The hand-off between a ``QuantizingRMSNorm`` and the ``QuantizedLinear``s behind it: the tensor ``y`` the norm
+    returned, its version when it was returned, its quantised rows ``(Xq, s_x, zp_x)`` and how many consumers are
+    still to come.  ``take(x)`` gives the rows only for that very tensor, unwritten since; after the last consumer
+    every reference is dropped, so between forwards nothing is pinned."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self) -> None:
+        self.y = self.version = self.rows = None
+        self.left = 0
+
+    def put(self, y: torch.Tensor, Xq: torch.Tensor, s_x: torch.Tensor, zp_x: Optional[torch.Tensor],
+            consumers: int) -> None:
+        self.clear()
+        version = _version_of(y)
+        if version is None or consumers <= 0:      # staleness could not be seen: every consumer quantises for itself
+            return
+        self.y, self.version, self.rows, self.left = y, version, (Xq, s_x, zp_x), int(consumers)
+
+    @property
+    def holds_tensors(self) -> bool:
+        return self.y is not None or self.rows is not None
+
+    def take(self, x: torch.Tensor):
+        """``(Xq, s_x, zp_x)`` when ``x`` is the tensor the norm returned and nothing has written to it; else None."""
+        if self.y is None or x is not self.y or _version_of(x) != self.version:
+            return None
+        rows = self.rows
+        self.left -= 1
+        if self.left <= 0:
+            self.clear()
+        return rows
+
+
+class QuantizingRMSNorm(nn.Module):
+    """An RMSNorm whose output feeds only ``QuantizedLinear``s that share their quantised rows (q/k/v, or gate/up), with
+    the quantiser fused in: ``forward(x)`` runs ``qt_rmsnorm_quantize_i8`` -- one launch in place of torch's chain of
+    elementwise and reduction kernels and of the consumers' quantiser launches -- returns ``Y`` shaped like ``x`` and
+    leaves ``(Xq, s_x, zp_x)`` in the ``SharedRows`` its consumers ask first.  ``Y`` and the rows are the header's fixed
+    sequence: the five lines of ``LlamaRMSNorm.forward`` with the kernel's own order of summation over K, then exactly
+    ``qt_quantize_tokens_i8(Y)``.  Opt-in: ``load_quantized(..., a8_fused_norm=True)`` builds it where
+    ``refusal`` is None.  ``weight`` keeps its name, so state-dict keys do not move.
+
+    The installed torch sequence runs instead when ``x`` is not a 16-bit device tensor of the weight's dtype, when
+    K > ``MAX_K`` or when a gradient is required; the consumers then quantise for themselves.
+
+    ``takes``: how many ``quantize_rows`` calls follow one forward (the default: one per consumer; a ``QuantizedMLP``
+    quantises once for gate and up)."""
+
+    # norms whose forward is the five-line sequence the kernel restates, by class name (transformers 5.x)
+    PLAIN_NORMS = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm", "Qwen3RMSNorm", "MixtralRMSNorm")
+    # decoder layers whose forward hands input_layernorm's output to self_attn and post_attention_layernorm's to mlp
+    PLAIN_LAYERS = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer", "Qwen3DecoderLayer",
+                    "MixtralDecoderLayer")
+    MAX_K = 32768              # qt_rmsnorm_quantize_i8's bound
+    device_types = ("cuda",)   # where the kernel exists
+
+    def __init__(self, weight: nn.Parameter, eps: float, consumers, takes: Optional[int] = None):
+        super().__init__()
+        consumers = list(consumers)
+        if not consumers or not all(isinstance(c, QuantizedLinear) for c in consumers):
+            raise ValueError("QuantizingRMSNorm: the consumers must all be QuantizedLinears")
+        reason = self._consumers_refusal(consumers, weight.numel())
+        if reason:
+            raise ValueError(f"QuantizingRMSNorm: {reason}")
+        self.weight = weight if isinstance(weight, nn.Parameter) else nn.Parameter(weight, requires_grad=False)
+        self.variance_epsilon = float(eps)
+        self.takes = len(consumers) if takes is None else int(takes)
+        self.__dict__["_shared"] = SharedRows()
+        self.__dict__["_consumers"] = consumers      # not submodules: they keep their own names in the model
+        for c in consumers:
+            c.rows_from = self._shared
+
+    @property
+    def shared(self) -> SharedRows:
+        return self._shared
+
+    @staticmethod
+    def _consumers_refusal(consumers, K: int) -> Optional[str]:
+        first = consumers[0]
+        if first.in_features != K:
+            return "the consumers' in_features is not the norm's width"
+        for c in consumers[1:]:
+            if c.in_features != first.in_features or c.act_symmetric != first.act_symmetric:
+                return "the consumers differ in in_features or act_symmetric, so they cannot share quantised rows"
+            if (c.col_perm is None) != (first.col_perm is None) or (
+                    c.col_perm is not None and not torch.equal(c.col_perm, first.col_perm)):
+                return "the consumers differ in col_perm, so they cannot share quantised rows"
+        return None
+
+    @classmethod
+    def refusal(cls, norm: nn.Module, consumers) -> Optional[str]:
+        """Why ``norm`` cannot quantise for ``consumers`` (None: it can)."""
+        if type(norm).__name__ not in cls.PLAIN_NORMS:
+            return f"{type(norm).__name__} is not one of {cls.PLAIN_NORMS}"
+        consumers = list(consumers)
+        if not consumers or not all(isinstance(c, QuantizedLinear) for c in consumers):
+            return "the consumers must all be QuantizedLinears"
+        weight = getattr(norm, "weight", None)
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not hasattr(norm, "variance_epsilon"):
+            return "the norm has no 1-d weight or no variance_epsilon"
+        return cls._consumers_refusal(consumers, weight.numel())
+
+    def extra_repr(self) -> str:
+        return f"{tuple(self.weight.shape)}, eps={self.variance_epsilon}, consumers={len(self._consumers)}"
+
+    def _torch_forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+        input_dtype = hidden_states.dtype
+        hidden_states = hidden_states.to(torch.float32)
+        variance = hidden_states.pow(2).mean(-1, keepdim=True)
+        hidden_states = hidden_states * torch.rsqrt(variance + self.variance_epsilon)
+        return self.weight * hidden_states.to(input_dtype)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w = self.weight
+        K = w.numel()
+        if (x.device.type not in self.device_types or x.dtype not in (torch.bfloat16, torch.float16)
+                or x.dtype != w.dtype or x.device != w.device or K > self.MAX_K or x.numel() == 0
+                or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
+            self._shared.clear()
+            return self._torch_forward(x)
+        from ..hip import ops
+
+        first = self._consumers[0]
+        Y, Xq, s_x, zp_x = ops.rmsnorm_quantize_i8(_rows(x, K), w, self.variance_epsilon,
+                                                   symmetric=first.act_symmetric, col_perm=first.col_perm)
+        y = Y.reshape(x.shape)
+        self._shared.put(y, Xq, s_x, zp_x, self.takes)
+        return y
 
 
 class WeightOnlyLinear(nn.Module):

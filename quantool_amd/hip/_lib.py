@@ -106,6 +106,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "qt_act_mul_quantize_i8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "qt_rmsnorm_quantize_i8": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "qt_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_skinny": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,

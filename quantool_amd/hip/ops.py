@@ -569,6 +569,43 @@ def act_mul_quantize_i8(gate: torch.Tensor, up: torch.Tensor, symmetric: bool = 
     return (Xq, s_x, zp_x, H) if return_h else (Xq, s_x, zp_x)
 
 
+def rmsnorm_quantize_i8(X: torch.Tensor, weight: torch.Tensor, eps: float, symmetric: bool = True,
+                        col_perm: Optional[torch.Tensor] = None, return_rstd: bool = False):
+    """``Y = weight * RMSNorm(X)`` as transformers' ``LlamaRMSNorm.forward`` leaves it, and ``quantize_tokens_i8(Y,
+    symmetric, col_perm)``, in one pass (``qt_rmsnorm_quantize_i8``): X [M, K] bf16 / fp16 (unit column stride, any row
+    pitch), weight [K] of the same dtype on the same device -> (Y [M, K], Xq, s_x, zp_x), and with ``return_rstd`` the
+    rows' fp32 ``rsqrt(mean(x^2) + eps)`` [M] as well."""
+    code = _x2d(X, "X")
+    if not weight.is_cuda or weight.device != X.device:
+        raise ValueError(f"weight must be a device tensor on X's device {X.device}, got {weight.device}")
+    if weight.dtype != X.dtype:
+        raise TypeError(f"weight must be of X's dtype {X.dtype}, got {weight.dtype}")
+    M, K = X.shape
+    if M == 0 or K == 0:
+        raise ValueError(f"X must be non-empty, got shape {tuple(X.shape)}")
+    if weight.dim() != 1 or weight.numel() != K or not weight.is_contiguous():
+        raise ValueError(f"weight must be contiguous [{K}], got shape {tuple(weight.shape)}")
+    if col_perm is not None:
+        _req(col_perm, torch.int32, "col_perm", 1)
+        if col_perm.numel() != K or not col_perm.is_contiguous():
+            raise ValueError(f"col_perm must be contiguous int32 [{K}]")
+    eps = float(eps)
+    if not (eps >= 0.0 and eps != float("inf")):
+        raise ValueError(f"eps must be finite and not negative, got {eps!r}")
+    lib = load()
+    Y = torch.empty((M, K), dtype=X.dtype, device=X.device)
+    Xq = torch.empty((M, K), dtype=torch.int8, device=X.device)
+    s_x = torch.empty(M, dtype=torch.float32, device=X.device)
+    zp_x = None if symmetric else torch.empty(M, dtype=torch.int32, device=X.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=X.device) if return_rstd else None
+    # a one-row view may carry any stride(0): the pitch of a single row is never used, K keeps the host check quiet
+    ldx = X.stride(0) if M > 1 else max(X.stride(0), K)
+    check("qt_rmsnorm_quantize_i8", lib.qt_rmsnorm_quantize_i8(
+        X.data_ptr(), ldx, weight.data_ptr(), code, M, K, eps, _ptr(col_perm), int(bool(symmetric)), Xq.data_ptr(),
+        s_x.data_ptr(), _ptr(zp_x), Y.data_ptr(), K, _ptr(rstd), _stream()))
+    return (Y, Xq, s_x, zp_x, rstd) if return_rstd else (Y, Xq, s_x, zp_x)
+
+
 def _i8_operands(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, K: Optional[int],
                  zp_x: Optional[torch.Tensor], wsum: Optional[torch.Tensor], out_dtype, experts: bool = False):
     """Checks the operands of ``qt_gemm_i8`` -- or, with ``experts``, of ``qt_gemm_i8_grouped``: E weights stacked

@@ -43,6 +43,11 @@ against ``a8_wide`` (the class defaults: ``qt_moe_gemm_i8_wide``).  ``--pair fus
 the checkpoint twice, ``a8_fused_off`` with the default loader and ``a8_fused`` with ``a8_fused_act=True`` (every
 ``QuantizedExperts`` with ``fused_act``, every dense MLP a ``QuantizedMLP``: SiLU(gate) * up and the quantiser in one
 ``qt_act_mul_quantize_i8`` pass); the prompt's logits are asserted equal to the bit before anything is timed.
+``--pair norm`` (A8 schemes) loads it twice with ``a8_fused_act=True``, ``a8_norm_off`` without and ``a8_norm`` with
+``a8_fused_norm=True`` (the RMSNorms in front of q/k/v and gate/up as ``QuantizingRMSNorm``s: the norm and the
+quantiser its consumers share in one ``qt_rmsnorm_quantize_i8`` pass).  The kernel's sum over K runs in its own order,
+so nothing is asserted of the logits: how many of the prompt's differ, and by how much at most, is reported
+(``logits_differ``, ``logits_max_abs_diff``) beside ``quantizing_norms``.
 """
 from __future__ import annotations
 
@@ -245,6 +250,43 @@ def a8_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict
     result["speedup"] = round(t / k, 3)
 
 
+def a8_norm_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """The A8 checkpoint loaded with ``a8_fused_act=True`` as ``a8_norm_off`` and, with ``a8_fused_norm=True`` besides,
+    as ``a8_norm``, decoded in turn."""
+    from quantool_amd.engine.qlinear import QuantizedMLP, QuantizingRMSNorm
+
+    models = {"a8_norm_off": load_quantized(path, device=dev, a8_fused_act=True),
+              "a8_norm": load_quantized(path, device=dev, a8_fused_act=True, a8_fused_norm=True)}
+    fused = models["a8_norm"]
+    result["quantized_mlps"] = sum(isinstance(m, QuantizedMLP) for m in fused.modules())
+    result["quantizing_norms"] = sum(isinstance(m, QuantizingRMSNorm) for m in fused.modules())
+    assert result["quantizing_norms"] > 0, "no norm of this checkpoint runs fused"
+    assert not any(isinstance(m, QuantizingRMSNorm) for m in models["a8_norm_off"].modules())
+    with torch.no_grad():
+        a, b = (m(input_ids=prompt).logits.float() for m in models.values())
+    result["logits"] = a.numel()
+    result["logits_differ"] = int((a != b).sum())
+    result["logits_max_abs_diff"] = float((a - b).abs().max())
+    result["logits_max_abs"] = float(a.abs().max())
+    result["prompt_argmax_agree"] = int((a.argmax(-1) == b.argmax(-1)).sum())
+    result["prompt_positions"] = a.shape[0] * a.shape[1]
+    del a, b
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, model in models.items():
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    same = [x == y for x, y in zip(tokens["a8_norm_off"], tokens["a8_norm"])]
+    result["tokens_agree"] = sum(same)                         # a random-init model's logits are near ties
+    result["first_difference"] = same.index(False) if not all(same) else None
+    t, k = (min(result["modes"][m]["ms_per_step"]) for m in ("a8_norm_off", "a8_norm"))
+    result["speedup"] = round(t / k, 3)
+    off = result["modes"]["a8_norm_off"]["ms_per_step"]
+    result["off_spread"] = round(abs(off[0] / off[1] - 1.0), 4)
+
+
 def a16_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, wide_min_tokens: int, result: dict) -> None:
     """One packed A16 sparse-MoE model (``a16_experts="packed"``) decoded as ``a16_wide_off`` (``WeightOnlyExperts``'
     ``wide_min_tokens`` = 0: the grouped GEMV) and ``a16_wide`` (``wide_min_tokens`` = the class default, or
@@ -306,10 +348,11 @@ def main():
     ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
-    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused"],
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused", "norm"],
                     help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
                          "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; fused = a8_fused_off vs a8_fused "
-                         "(load_quantized(..., a8_fused_act=True)); W4A16 with --model "
+                         "(load_quantized(..., a8_fused_act=True)); norm = a8_norm_off vs a8_norm (a8_fused_norm=True, "
+                         "a8_fused_act=True in both); W4A16 with --model "
                          "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide")
     ap.add_argument("--wide-min-tokens", type=int, default=-1,
                     help="with --scheme W4A16 --pair wide: WeightOnlyExperts.wide_min_tokens of a16_wide (default: "
@@ -333,7 +376,8 @@ def main():
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
               "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
     if args.scheme != "W4A16":
-        {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes, "fused": a8_fused_modes}[args.pair](path, dev, prompt, args.new, result)
+        {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes, "fused": a8_fused_modes,
+         "norm": a8_norm_modes}[args.pair](path, dev, prompt, args.new, result)
         print(json.dumps(result))
         return
     if args.pair == "wide":

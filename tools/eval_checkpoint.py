@@ -3,6 +3,7 @@
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-experts-wide-tokens N] [--a8-fused-act]
+                                  [--a8-fused-norm]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
@@ -10,8 +11,10 @@ on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed``
 ``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``;
 ``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``;
 ``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
-``qt_act_mul_quantize_i8`` pass, the same perplexity to the bit).  Prints one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and
-evaluation wall times.
+``qt_act_mul_quantize_i8`` pass, the same perplexity to the bit; ``--a8-fused-norm`` on an A8 checkpoint: the RMSNorms in
+front of q/k/v and gate/up and the quantiser their consumers share in one ``qt_rmsnorm_quantize_i8`` pass each, whose sum
+over K runs in the kernel's own order, so the perplexity may move in its last digits).  Prints one JSON line: perplexity,
+mean NLL, predicted tokens, the module counts, load and evaluation wall times.
 """
 from __future__ import annotations
 
@@ -25,8 +28,8 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, QuantizedMLP, WeightOnlyExperts,  # noqa: E402
-                                         WeightOnlyLinear, load_quantized)
+from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm,  # noqa: E402
+                                         WeightOnlyExperts, WeightOnlyLinear, load_quantized)
 from quantool_amd.evaluate import perplexity  # noqa: E402
 
 
@@ -46,13 +49,17 @@ def main():
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
     ap.add_argument("--a8-fused-act", action="store_true",
                     help="A8 checkpoints: run every MLP's and expert bank's glue as one qt_act_mul_quantize_i8 pass")
+    ap.add_argument("--a8-fused-norm", action="store_true",
+                    help="A8 checkpoints: run the RMSNorm in front of q/k/v and gate/up and their shared quantiser as one "
+                         "qt_rmsnorm_quantize_i8 pass")
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
     model = load_quantized(args.checkpoint, device=args.device,
                            dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
-                           a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act)
+                           a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act,
+                           a8_fused_norm=args.a8_fused_norm)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -63,6 +70,7 @@ def main():
     r.update({"checkpoint": str(args.checkpoint), "format": model._qt_checkpoint["format"],
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()),
               "quantized_mlps": sum(isinstance(m, QuantizedMLP) for m in model.modules()),
+              "quantizing_norms": sum(isinstance(m, QuantizingRMSNorm) for m in model.modules()),
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
               "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})

@@ -6,6 +6,7 @@ tiled GEMM at decode sizes.
   python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
   python tools/qlinear_bench.py --ring-w4 [--ms 2048,4096,8192]   # W4A8 prefill: qt_gemm_i8 vs qt_gemm_i8_ring_w4
   python tools/qlinear_bench.py --mlp [--ms 1,16,32,128,2048,8192]     # three Linears + glue vs QuantizedMLP
+  python tools/qlinear_bench.py --norm [--ms 1,16,32,128,2048,8192]    # RMSNorm + 3 (2) quantisers vs one fused launch
 
 Per shape (q/k/v fused N = 6144, K = 4096; gate/up N = 28672, K = 4096; down N = 4096, K = 14336) and M: device time
 (HIP events, mean over --reps after --warmup) of the activation pass (qt_quantize_tokens_i8), the GEMM (qt_gemm_i8:
@@ -46,6 +47,15 @@ qt_act_mul_quantize_i8 on the same gate / up outputs.  "mlp": ``down(silu(gate(x
 (alternating call by call, per-call events, the Linears rotating over more than 512 MiB of copies, medians).  The unfused
 form runs twice in each loop ("unfused", "unfused_again"): their ratio is the yardstick's own spread.  Bit equality of the
 two forms is asserted before anything is timed.
+
+--norm prints only "norm" rows: the glue in front of q/k/v and of gate/up alone, at K = 4096 and --ms (default
+1,16,32,128,2048,8192), bf16, with symmetric and with asymmetric activations.  "qkv": the installed ``LlamaRMSNorm``
+followed by three qt_quantize_tokens_i8 calls on its output against one qt_rmsnorm_quantize_i8 launch; "gate_up": the
+same with two.  The --mlp rows' protocol: forms alternate call by call between their own events, the unfused form runs
+twice in each loop and the ratio of its two medians is the spread.  Before anything is timed the fused Y is compared
+with the norm's (``y_differ``: how many elements land on the other 16-bit neighbour -- the kernel's sum over K runs in its
+own order) and its rows are asserted equal to qt_quantize_tokens_i8 of its own Y; ``torch_norm_kernels``
+is the number of device kernels one call of the installed norm launches, as torch's profiler counts them.
 """
 from __future__ import annotations
 
@@ -349,6 +359,72 @@ def mlp_rows(ms, reps, warmup, dev, g):
     return rows
 
 
+NORM_K = 4096
+NORM_EPS = 1e-5
+
+
+def count_kernels(fn):
+    """How many device kernels one call of ``fn`` launches (torch's profiler), or the reason it could not be counted."""
+    try:
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA and "memcpy" not in e.name.lower()]
+        return {"count": len(names), "names": [n[:80] for n in names]}
+    except Exception as e:  # noqa: BLE001
+        return {"count": None, "reason": f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"}
+
+
+def norm_rows(ms, reps, warmup, dev, g):
+    """The installed RMSNorm + 3 (q/k/v) or 2 (gate/up) qt_quantize_tokens_i8 calls against one
+    qt_rmsnorm_quantize_i8 launch, K = 4096, bf16."""
+    from transformers.models.llama.modeling_llama import LlamaRMSNorm
+
+    K = NORM_K
+    norm = LlamaRMSNorm(K, NORM_EPS).to(dev, torch.bfloat16)
+    norm.weight.data.copy_(torch.randn(K, device=dev, generator=g) * 0.5 + 1)
+    w = norm.weight.detach()
+    rows = []
+    for M in ms:
+        x = (torch.randn(M, K, device=dev, generator=g) * 3).to(torch.bfloat16)
+        with torch.no_grad():
+            kernels = count_kernels(lambda: norm(x))
+            for symmetric in (True, False):
+                want = norm(x)
+                Y, Xq, s_x, zp_x = ops.rmsnorm_quantize_i8(x, w, NORM_EPS, symmetric=symmetric)
+                for a, b in zip((Xq, s_x, zp_x), ops.quantize_tokens_i8(Y, symmetric=symmetric)):
+                    assert (a is None and b is None) or torch.equal(a, b), "the fused rows are not the quantiser's"
+                differ = int((Y.view(torch.int16) != want.view(torch.int16)).sum())
+                row = {"M": M, "K": K, "symmetric": symmetric, "y_differ": differ, "y_elements": Y.numel(),
+                       "torch_norm_kernels": kernels["count"]}
+                for name, n in (("qkv", 3), ("gate_up", 2)):
+                    def unfused(i, n=n):
+                        y = norm(x)
+                        return [ops.quantize_tokens_i8(y, symmetric=symmetric) for _ in range(n)]
+
+                    def fused(i):
+                        return ops.rmsnorm_quantize_i8(x, w, NORM_EPS, symmetric=symmetric)
+
+                    t = time_pair({"unfused": unfused, "fused": fused, "unfused_again": unfused}, reps, warmup)
+                    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+                    out = {k: {"us": round(med[k] * 1e6, 2), "min_us": round(min(v) * 1e6, 2)} for k, v in t.items()}
+                    out["speedup"] = round(med["unfused"] / med["fused"], 3)
+                    out["unfused_spread"] = round(abs(med["unfused"] / med["unfused_again"] - 1.0), 4)
+                    out["launches"] = {"unfused": None if kernels["count"] is None else kernels["count"] + n, "fused": 1}
+                    row[name] = out
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+        if M == ms[0]:
+            print(json.dumps({"torch_norm_kernels": kernels}), file=sys.stderr)
+        del x
+    return rows, kernels
+
+
 def _time(fn, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -375,11 +451,20 @@ def main():
     ap.add_argument("--ring-w4", action="store_true", help="only the W4A8 tiled-vs-ring rows (qt_gemm_i8_ring_w4)")
     ap.add_argument("--mlp", action="store_true",
                     help="only the MLP rows: three QuantizedLinears + torch's glue vs QuantizedMLP (qt_act_mul_quantize_i8)")
+    ap.add_argument("--norm", action="store_true",
+                    help="only the norm rows: the installed RMSNorm + 3 (2) quantisers vs qt_rmsnorm_quantize_i8")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("qlinear_bench needs a GPU")
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
+    if args.norm:
+        ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else MLP_MS).split(",") if m]
+        rows, kernels = norm_rows(ms, args.reps, args.warmup, dev, g)
+        print(json.dumps({"metric": "RMSNorm + per-token int8 quantisers (3: q/k/v, 2: gate/up) vs qt_rmsnorm_quantize_i8, "
+                                    "K = 4096, bf16", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                          "torch_norm_kernels": kernels, "norm": rows}))
+        return
     if args.mlp:
         ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else MLP_MS).split(",") if m]
         print(json.dumps({"metric": "Llama-3-8B MLP, A8: three QuantizedLinears + silu * up vs QuantizedMLP, cold weights",
