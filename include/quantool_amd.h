@@ -319,6 +319,13 @@ int qt_gemm3_tn_f16x2(const float* A, int64_t lda, const float* B, int64_t ldb, 
 /* Host-only self-check of the bf16x3 block-row planner (runs without a GPU): 0 if every k chunk of every tile is
  * covered exactly once and the slab / reduction tables are consistent, else a negative code. */
 int qt_gemm3_plan_check(int Tm, int Tn, int c_end, int tri, int* n_items_out, int* n_slabs_out, int* longest_out);
+/* The same for all item tables of one qt_cholesky_inverse_upper chain of size K at the default block sizes (runs
+ * without a GPU).  merged = 0: one table per long product (QT_CHOL_MERGE=0 / order); 1: one table per block row over
+ * both of its products (QT_CHOL_MERGE=1).  min_chunks <= 0: the default threshold (QT_CHOL_G3_MIN_CHUNKS otherwise).
+ * 0 if every tile of both segments is covered exactly once over its k range by contiguous pieces of >= 2 chunks, slab
+ * ids are unique per launch and below the count the workspace is sized for, and no launch exceeds the item cap; else a
+ * negative code.  counts_out[5] (may be null): product launches, items, slabs, the workspace's slab count, table bytes. */
+int qt_chol_g3_plan_check(int K, int merged, int min_chunks, long long* counts_out);
 /* ---- A8 runtime: W8A8 / INT8 / W4A8 checkpoints on the int8 MFMA --------------------------------------
  * The inference side of the 8-bit dynamic per-token activation block these checkpoints carry
  * (config_groups.group_0.input_activations): activations are quantised per row on the fly and multiplied with the

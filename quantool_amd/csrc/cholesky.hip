@@ -22,6 +22,9 @@
 //     left of I        :  T_I = sum_{p<I0} R[p, I]^T Y[p, :I0]               (gemm3 SET / sgemm SET, k = I0)
 //                         Y[I, :I0] = -Y_II T_I = -(Y_II^T)^T T_I             (transpose + sgemm NEG, k = NBI)
 //                         bf16 plane copies of Y[I, :I1]                      (split3_kernel, large K only)
+// The two phases can also run as ONE walk over the block rows (QT_CHOL_MERGE, chol_merge_mode() below): block row J's
+// two long products have the same A operand R[:J0, J], the same k range and need only rows before J of R and Y, so
+// they fit one gemm3 launch with two output segments and one item table.
 // gemm3 (gemm3_tn.h) = fp32-accurate product on the bf16 MFMA from three bf16 planes per operand; sgemm
 // (sgemm_tn.h) = the f32-MFMA fmaf chain.
 // With a lower bound on lambda_min(A) (the _bounded entry points) the gemm3 products run on TWO fp16 planes per
@@ -75,9 +78,11 @@ struct G3Step {
 struct CholG3Plan {
     bool any = false;
     std::vector<G3Step> fac, inv;       // per outer block / per block row (n_items == 0: sgemm_tn)
+    std::vector<G3Step> row;            // merged plans: per block row, both products in one table (n_items == 0: fac / inv)
     char* blob = nullptr;               // pinned
     size_t blob_bytes = 0;
     int max_slabs = 0;
+    bool any_row = false;               // some row is merged
 };
 
 static int chol_g3_min_chunks() {   // read per call: tests switch the path on for small K
@@ -100,23 +105,43 @@ static int chol_g3_target_items(int K) {
     return K < 8192 ? 96 : 256;
 }
 
-static const CholG3Plan* chol_g3_plan(int K, int NBO, int NBI) {
-    static std::mutex m;
-    static std::map<std::tuple<int, int, int, int>, CholG3Plan*> plans;
-    const int min_chunks = chol_g3_min_chunks();
-    const int target_items = chol_g3_target_items(K);
-    std::lock_guard<std::mutex> lock(m);
-    const auto key = std::make_tuple(K, NBO, NBI, min_chunks * 1024 + target_items);
-    auto it = plans.find(key);
-    if (it != plans.end()) return it->second;
-    CholG3Plan* pl = new CholG3Plan();
-    std::vector<char> bytes;
-    auto add = [&](int Tm, int Tn, int c_end, int tri) {
+// QT_CHOL_MERGE = 0 | order | 1 (read per call).  0: two phases -- the whole factorisation, all diagonal inverses, then
+// Y row by row.  order: ONE walk over the block rows -- per row J the two long products, J's panel chain, the plane
+// copy of R's row, the inverses of J's diagonal blocks, the Y_JJ recurrence with the transpose and the NEG product, the
+// plane copy of Y's row -- with the kernels, tables and arguments of 0: every step reads only what earlier rows (and
+// earlier steps of its own) finished, so the bits are those of 0.  1: the walk with the two long products of a row,
+//     A[J, J0:] -= R[:J0, J]^T R[:J0, J0:]      and      T_J = R[:J0, J]^T Y[:J0, :J0]
+// (one A operand, one k range) as the two segments of ONE gemm3 launch with one item table (g3_plan_row2): together
+// they always cover K output columns, so each tile is cut into about half as many pieces and half the slabs are
+// written and reduced.  The walk needs the plane products and NBO == NBI; anything else, and a size at which no row
+// can be merged (chol_g3_build), runs as 0.
+enum { CHOL_TWO_PHASE = 0, CHOL_WALK = 1, CHOL_WALK_MERGED = 2 };
+static int chol_merge_mode() {
+    const char* e = getenv("QT_CHOL_MERGE");
+    if (!e) return CHOL_WALK_MERGED;
+    if (strcmp(e, "order") == 0) return CHOL_WALK;
+    return atoi(e) != 0 ? CHOL_WALK_MERGED : CHOL_TWO_PHASE;
+}
+
+// Host only: the steps and the table bytes of one (K, block sizes, thresholds).  merged: rows where BOTH products have
+// a table get one table over both segments instead (pl.row; their fac / inv entries stay empty), cut under the slab
+// budget of the separate tables so that the workspace of a size never depends on the switch.
+static void chol_g3_build(int K, int NBO, int NBI, int min_chunks, int target_items, bool merged, CholG3Plan& pl,
+                          std::vector<char>& bytes) {
+    pl = CholG3Plan();
+    bytes.clear();
+    int slab_budget = 0;
+    if (merged) {
+        CholG3Plan sep;
+        std::vector<char> sep_bytes;
+        chol_g3_build(K, NBO, NBI, min_chunks, target_items, false, sep, sep_bytes);
+        slab_budget = sep.max_slabs;
+    }
+    auto enough = [&](int Tm, int Tn, int c_end, int tri) {
+        return min_chunks > 0 && K % 8 == 0 && g3_row_chunks(Tm, Tn, c_end, tri) * G3_CHUNK_ROWS >= (long)min_chunks * 128;
+    };
+    auto store = [&](const std::vector<G3Item>& items, const std::vector<G3Red>& red) {
         G3Step st;
-        if (min_chunks <= 0 || K % 8 != 0 || g3_row_chunks(Tm, Tn, c_end, tri) * G3_CHUNK_ROWS < (long)min_chunks * 128) return st;
-        std::vector<G3Item> items;
-        std::vector<G3Red> red;
-        g3_plan_row(Tm, Tn, c_end, tri, items, red, target_items);
         st.n_items = (int)items.size();
         st.n_red = (int)red.size();
         st.item_off = qt_align_up(bytes.size(), 256);
@@ -125,20 +150,62 @@ static const CholG3Plan* chol_g3_plan(int K, int NBO, int NBI) {
         st.red_off = qt_align_up(bytes.size(), 256);
         bytes.resize(st.red_off + red.size() * sizeof(G3Red));
         if (!red.empty()) memcpy(bytes.data() + st.red_off, red.data(), red.size() * sizeof(G3Red));
-        for (const G3Red& r : red) pl->max_slabs = pl->max_slabs > r.first + r.count ? pl->max_slabs : r.first + r.count;
-        pl->any = true;
+        for (const G3Red& r : red) pl.max_slabs = pl.max_slabs > r.first + r.count ? pl.max_slabs : r.first + r.count;
+        pl.any = true;
         return st;
     };
-    for (int J0 = 0; J0 < K; J0 += NBO) {
+    auto add = [&](int Tm, int Tn, int c_end, int tri) {
+        if (!enough(Tm, Tn, c_end, tri)) return G3Step();
+        std::vector<G3Item> items;
+        std::vector<G3Red> red;
+        g3_plan_row(Tm, Tn, c_end, tri, items, red, target_items);
+        return store(items, red);
+    };
+    const bool walk = merged && NBO == NBI;
+    const int cap = target_items > 0 && target_items < 256 ? target_items : 256;   // items per launch, as g3_plan_row
+    pl.row.assign(walk ? (K + NBO - 1) / NBO : 0, G3Step());
+    std::vector<char> is_merged(pl.row.size(), 0);
+    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
         const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-        pl->fac.push_back(J0 == 0 ? G3Step() : add((J1 - J0 + 255) / 256, (K - J0 + 255) / 256, J0 / G3_CHUNK_ROWS, 0));
+        const int Tm = (J1 - J0 + 255) / 256, Tn0 = (K - J0 + 255) / 256, Tn1 = (J0 + 255) / 256, c_end = J0 / G3_CHUNK_ROWS;
+        // A row is merged only where the cap leaves every tile of the launch at least two pieces: with more tiles than
+        // half the cap the pieces become whole tiles and the launch lasts as long as the full k range (K = 28672: 224
+        // tiles per 512-row block against a cap of 256 -- one 70B bench run 340.3 -> 345.1 ms per step merged).
+        if (walk && J0 > 0 && 2 * Tm * (Tn0 + Tn1) <= cap && enough(Tm, Tn0, c_end, 0) && enough(Tm, Tn1, c_end, 1)) {
+            std::vector<G3Item> items;
+            std::vector<G3Red> red;
+            g3_plan_row2(Tm, Tn0, Tn1, c_end, items, red, target_items, slab_budget);
+            pl.row[Jb] = store(items, red);
+            is_merged[Jb] = 1;
+            pl.any_row = true;
+        }
     }
-    for (int I0 = 0; I0 < K; I0 += NBI) {
+    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
+        const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
+        const bool skip = J0 == 0 || (walk && is_merged[Jb]);
+        pl.fac.push_back(skip ? G3Step() : add((J1 - J0 + 255) / 256, (K - J0 + 255) / 256, J0 / G3_CHUNK_ROWS, 0));
+    }
+    for (int I0 = 0, Ib = 0; I0 < K; I0 += NBI, ++Ib) {
         const int I1 = (K - I0 < NBI) ? K : I0 + NBI;
-        pl->inv.push_back(I0 == 0 ? G3Step() : add((I1 - I0 + 255) / 256, (I0 + 255) / 256, I0 / G3_CHUNK_ROWS, 1));
+        const bool skip = I0 == 0 || (walk && is_merged[Ib]);
+        pl.inv.push_back(skip ? G3Step() : add((I1 - I0 + 255) / 256, (I0 + 255) / 256, I0 / G3_CHUNK_ROWS, 1));
     }
+    pl.blob_bytes = pl.any ? qt_align_up(bytes.size(), 256) : 0;
+}
+
+static const CholG3Plan* chol_g3_plan(int K, int NBO, int NBI, bool merged = false) {
+    static std::mutex m;
+    static std::map<std::tuple<int, int, int, int>, CholG3Plan*> plans;
+    const int min_chunks = chol_g3_min_chunks();
+    const int target_items = chol_g3_target_items(K);
+    std::lock_guard<std::mutex> lock(m);
+    const auto key = std::make_tuple(K, NBO, NBI, (merged ? 1 << 30 : 0) + min_chunks * 1024 + target_items);
+    auto it = plans.find(key);
+    if (it != plans.end()) return it->second;
+    CholG3Plan* pl = new CholG3Plan();
+    std::vector<char> bytes;
+    chol_g3_build(K, NBO, NBI, min_chunks, target_items, merged, *pl, bytes);
     if (pl->any) {
-        pl->blob_bytes = qt_align_up(bytes.size(), 256);
         if (hipHostMalloc((void**)&pl->blob, pl->blob_bytes, hipHostMallocDefault) != hipSuccess) {
             pl->any = false;   // no pinned memory: stay on the f32 path
             pl->blob = nullptr;
@@ -151,6 +218,7 @@ static const CholG3Plan* chol_g3_plan(int K, int NBO, int NBI) {
         pl->max_slabs = 0;
         for (G3Step& st : pl->fac) st = G3Step();
         for (G3Step& st : pl->inv) st = G3Step();
+        for (G3Step& st : pl->row) st = G3Step();
     }
     plans[key] = pl;
     return pl;
@@ -475,7 +543,8 @@ __global__ __launch_bounds__(256) void trsm_rt_kernel(const float* __restrict__ 
 //   Ydiag(b) : (R^-1)^T dense n x n at Y + (b*128)*(ldy+1) (zeros above the diagonal)
 __global__ __launch_bounds__(128) void trinv_batched_kernel(const float* __restrict__ Rd_all, int K,
                                                             float* __restrict__ Dinv_all,
-                                                            float* __restrict__ Y, int64_t ldy, int64_t bsW, int64_t bsY) {
+                                                            float* __restrict__ Y, int64_t ldy, int64_t bsW, int64_t bsY,
+                                                            int blk0) {
     if (blockIdx.y) {      // problem b of a batch
         Rd_all += (size_t)blockIdx.y * bsW;
         Dinv_all += (size_t)blockIdx.y * bsW;
@@ -484,7 +553,7 @@ __global__ __launch_bounds__(128) void trinv_batched_kernel(const float* __restr
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Rt = sm;             // [NB][LDT]  Rt[p][i] = R[i][p]
     float* Xs = sm + NB * LDT;  // [NB][LDP]
-    const int b = blockIdx.x;
+    const int b = blk0 + blockIdx.x;   // the launch covers blocks blk0 .. blk0 + gridDim.x - 1
     const int n = (K - b * NB < NB) ? K - b * NB : NB;
     const float* Rd = Rd_all + (size_t)b * RD_STRIDE;
     const int j = threadIdx.x;
@@ -549,14 +618,15 @@ __global__ __launch_bounds__(128) void trinv_batched_kernel(const float* __restr
 // Z is lower triangular: Ydiag(b) = Z, Dinv[b] = Z^T.  Wave w owns the columns 32w .. 32w + 31 of the identity.
 __global__ __launch_bounds__(256) void trinv_mfma_kernel(const float* __restrict__ Rd_all, int K,
                                                          float* __restrict__ Dinv_all,
-                                                         float* __restrict__ Y, int64_t ldy, int64_t bsW, int64_t bsY) {
+                                                         float* __restrict__ Y, int64_t ldy, int64_t bsW, int64_t bsY,
+                                                         int blk0) {
     if (blockIdx.y) {      // problem b of a batch
         Rd_all += (size_t)blockIdx.y * bsW;
         Dinv_all += (size_t)blockIdx.y * bsW;
         Y += (size_t)blockIdx.y * bsY;
     }
     extern __shared__ __attribute__((aligned(16))) float Rs[];  // [RD_STRIDE]
-    const int blk = blockIdx.x;
+    const int blk = blk0 + blockIdx.x;   // the launch covers blocks blk0 .. blk0 + gridDim.x - 1
     const int n = (K - blk * NB < NB) ? K - blk * NB : NB;
     const float* Rd = Rd_all + (size_t)blk * RD_STRIDE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -755,7 +825,18 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
     const int nblk = (K + NB - 1) / NB;
     char* ws = (char*)qt_align_up((size_t)workspace, 256);
     int NBO, NBI;
-    const CholG3Plan* g3 = chol_blocks(K, NBO, NBI);
+    const CholG3Plan* g3 = chol_blocks(K, NBO, NBI);   // sizes the workspace, whatever QT_CHOL_MERGE says
+    int merge_mode = (g3->any && NBO == NBI) ? chol_merge_mode() : CHOL_TWO_PHASE;
+    const CholG3Plan* tab = g3;                         // the tables the launches use
+    if (merge_mode == CHOL_WALK_MERGED) {
+        tab = chol_g3_plan(K, NBO, NBI, true);
+        // by construction the merged tables need no more slabs and no more table bytes than the separate ones
+        // (a size with no merged row keeps the two phases: the walk alone buys nothing)
+        if (!tab->any || !tab->any_row || tab->max_slabs > g3->max_slabs || tab->blob_bytes > g3->blob_bytes) {
+            tab = g3;
+            merge_mode = CHOL_TWO_PHASE;
+        }
+    }
     const size_t prob_bytes = chol_problem_ws_bytes(K, g3);
     const int64_t sW = (int64_t)(prob_bytes / 4);            // one problem's workspace, in floats
     const int64_t sA = nprob > 1 ? strideA : 0, sU = nprob > 1 ? strideU : 0;
@@ -779,7 +860,7 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
         q += qt_align_up((size_t)3 * K * K * 2, 256);
         g3_slabs = (float*)q;
         g3_tab = (char*)qt_align_up((size_t)(ws + (size_t)nprob * prob_bytes), 256);
-        QT_HIP(hipMemcpyAsync(g3_tab, g3->blob, g3->blob_bytes, hipMemcpyHostToDevice, stream));
+        QT_HIP(hipMemcpyAsync(g3_tab, tab->blob, tab->blob_bytes, hipMemcpyHostToDevice, stream));
     }
     f16x2 = f16x2 && g3->any;
     // two fp16 planes use the first two plane slots; the scale exponents eR[nprob], eY[nprob] sit in problem 0's third
@@ -787,8 +868,9 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
     int32_t* eY = f16x2 ? eR + nprob : nullptr;
     static_assert(2 * SG_MAX_BATCH * sizeof(int32_t) <= (size_t)NB * NB * 2, "the exponents fit the smallest third plane");
     // where a block-row product's C lives decides its batch stride: A (factor phase) or the workspace (T_I)
+    // second: the launch also carries segment 1 of a merged row, T_J = R[:J0, J]^T Y[:J0, :J0] -> TI (G3Args)
     auto g3_row = [&](const G3Step& st, const unsigned short* Bplanes, int col_a0, int col_b0, int M, int N, float* C,
-                      int64_t bsC, int mode) -> int {
+                      int64_t bsC, int mode, bool second = false) -> int {
         G3Args a;
         a.Apl = Rpl;
         a.Bpl = Bplanes;
@@ -816,6 +898,16 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
             a.planes = G3_F16X2;
             a.eA = eR;
             a.eB = Bplanes == Rpl ? eR : eY;
+        }
+        if (second) {
+            a.Bpl1 = Ypl;
+            a.colB01 = 0;
+            a.eB1 = eY;
+            a.C1 = TI;
+            a.ldc1 = K;
+            a.bsC1 = sW;
+            a.mode1 = G3_SET;
+            a.N1 = col_a0;   // J0 columns
         }
         return qt_gemm3_launch(a, stream);
     };
@@ -857,27 +949,23 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
     // ---- A = R^T R over NBO-wide outer blocks, left-looking inside one; in place.  Outer level: right-looking
     // (one k = NBO update of the trailing matrix per block) on the f32 MFMA, or -- when the bf16x3 products
     // are in use for this K -- left-looking (block row J gathers all earlier block rows in one long-k product)
-    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
-        const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-        if (g3->any && J0 > 0) {
-            // A[J, J0:] -= R[:J0, J]^T R[:J0, J0:]
-            const G3Step& st = g3->fac[Jb];
-            float* C = A + (size_t)J0 * K + J0;
-            if (st.n_items > 0) {
-                int rc = g3_row(st, Rpl, J0, J0, J1 - J0, K - J0, C, sA, G3_SUB);
-                if (rc) return rc;
-            } else {
-                SgemmArgs g;
-                g.A = A + J0; g.lda = K;
-                g.B = A + J0; g.ldb = K;
-                g.Cin = C; g.ldcin = K;
-                g.Cout = C; g.ldcout = K;
-                g.M = J1 - J0; g.N = K - J0; g.kdim = J0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-                g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
-                int rc = sgemm(g, sA, sA, sA);
-                if (rc) return rc;
-            }
-        }
+    // A[J, J0:] -= R[:J0, J]^T R[:J0, J0:]
+    auto fac_product = [&](int J0, int J1, int Jb) -> int {
+        if (!(g3->any && J0 > 0)) return QT_OK;
+        const G3Step& st = tab->fac[Jb];
+        float* C = A + (size_t)J0 * K + J0;
+        if (st.n_items > 0) return g3_row(st, Rpl, J0, J0, J1 - J0, K - J0, C, sA, G3_SUB);
+        SgemmArgs g;
+        g.A = A + J0; g.lda = K;
+        g.B = A + J0; g.ldb = K;
+        g.Cin = C; g.ldcin = K;
+        g.Cout = C; g.ldcout = K;
+        g.M = J1 - J0; g.N = K - J0; g.kdim = J0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
+        g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
+        return sgemm(g, sA, sA, sA);
+    };
+    // the panel chain of block row J, then its plane copies (or the right-looking update)
+    auto fac_panels = [&](int J0, int J1) -> int {
         for (int j0 = J0; j0 < J1; j0 += NB) {
             const int j = j0 / NB, nbj = (K - j0 < NB) ? K - j0 : NB;
             float* Ajj = A + (size_t)j0 * K + j0;
@@ -926,21 +1014,36 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
             int rc = sgemm(g, sA, sA, sA);
             if (rc) return rc;
         }
-    }
-    // ---- all diagonal-block inverses at once ----
-    {
+        return QT_OK;
+    };
+    // the inverses of the 128x128 diagonal blocks blk0 .. blk0 + n - 1
+    auto trinv = [&](int blk0, int n) -> int {
         const char* e = getenv("QT_CHOL_TRINV");   // read per call: the tests compare the two kernels in one process
         if (e && strcmp(e, "div") == 0)
-            hipLaunchKernelGGL(trinv_batched_kernel, dim3(nblk, nprob), dim3(NB), inv_lds, stream, (const float*)Rd, K, Dinv, Y,
-                               (int64_t)K, sW, sY);
+            hipLaunchKernelGGL(trinv_batched_kernel, dim3(n, nprob), dim3(NB), inv_lds, stream, (const float*)Rd, K, Dinv, Y,
+                               (int64_t)K, sW, sY, blk0);
         else
-            hipLaunchKernelGGL(trinv_mfma_kernel, dim3(nblk, nprob), dim3(256), RD_STRIDE * sizeof(float), stream,
-                               (const float*)Rd, K, Dinv, Y, (int64_t)K, sW, sY);
-    }
-    QT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(trinv_mfma_kernel, dim3(n, nprob), dim3(256), RD_STRIDE * sizeof(float), stream,
+                               (const float*)Rd, K, Dinv, Y, (int64_t)K, sW, sY, blk0);
+        QT_LAUNCH_CHECK();
+        return QT_OK;
+    };
     // ---- Y = R^-T by NBI-row block rows ----
-    for (int I0 = 0, Ib = 0; I0 < K; I0 += NBI, ++Ib) {
-        const int I1 = (K - I0 < NBI) ? K : I0 + NBI;
+    // left of the diagonal block: the K^3/3 of the inverse, one product per block row:  T_I = R[:I0, I]^T Y[:I0, :I0]
+    auto inv_product = [&](int I0, int I1, int Ib) -> int {
+        if (I0 == 0) return QT_OK;
+        if (g3->any && tab->inv[Ib].n_items > 0) return g3_row(tab->inv[Ib], Ypl, I0, 0, I1 - I0, I0, TI, sW, G3_SET);
+        SgemmArgs g;
+        g.A = A + I0; g.lda = K;
+        g.B = Y; g.ldb = K;
+        g.Cin = nullptr; g.ldcin = 0;
+        g.Cout = TI; g.ldcout = K;
+        g.M = I1 - I0; g.N = I0; g.kdim = I0; g.k_mode = SG_K_FROM_N0; g.mode = SG_MODE_SET;
+        g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
+        return sgemm(g, sA, sY, sW);
+    };
+    // the rest of block row I: Y_II, then Y[I, :I0] = -Y_II T_I from the T_I the product left in TI, then the plane copy
+    auto inv_row = [&](int I0, int I1) -> int {
         const int Wi = I1 - I0;
         // the diagonal 512-block Y_II by the 128-row recurrence (short k)
         for (int i0 = I0 + NB; i0 < I1; i0 += NB) {
@@ -971,26 +1074,7 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
             return qt_split3_launch(Y + (size_t)I0 * K, K, Wi, I1, Ypl + (size_t)I0 * K, K, plane_stride, 1, I0, 0, stream,
                                     nprob, sY, sW * 2);
         };
-        if (I0 == 0) {
-            int rc0 = split_row();
-            if (rc0) return rc0;
-            continue;
-        }
-        // left of the diagonal block: the K^3/3 of the inverse, one product per block row
-        int rc;
-        if (g3->any && g3->inv[Ib].n_items > 0) {
-            rc = g3_row(g3->inv[Ib], Ypl, I0, 0, Wi, I0, TI, sW, G3_SET);
-        } else {
-            SgemmArgs g;
-            g.A = A + I0; g.lda = K;
-            g.B = Y; g.ldb = K;
-            g.Cin = nullptr; g.ldcin = 0;
-            g.Cout = TI; g.ldcout = K;
-            g.M = Wi; g.N = I0; g.kdim = I0; g.k_mode = SG_K_FROM_N0; g.mode = SG_MODE_SET;
-            g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
-            rc = sgemm(g, sA, sY, sW);
-        }
-        if (rc) return rc;
+        if (I0 == 0) return split_row();
         hipLaunchKernelGGL(transpose_lower_block_kernel, dim3((Wi + 31) / 32, (Wi + 31) / 32, nprob), dim3(256), 0, stream,
                            (const float*)(Y + (size_t)I0 * K + I0), (int64_t)K, Wi, XT, NBO_MAX, sY, sW);
         QT_LAUNCH_CHECK();
@@ -1000,10 +1084,41 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
         t.Cin = nullptr; t.ldcin = 0;
         t.Cout = Y + (size_t)I0 * K; t.ldcout = K;
         t.M = Wi; t.N = I0; t.kdim = Wi; t.k_mode = SG_K_FULL; t.mode = SG_MODE_NEG;
-        rc = sgemm(t, sW, sW, sY);
+        int rc = sgemm(t, sW, sW, sY);
         if (rc) return rc;
-        rc = split_row();
+        return split_row();
+    };
+    if (merge_mode == CHOL_TWO_PHASE) {
+        for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
+            const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
+            int rc = fac_product(J0, J1, Jb);
+            if (!rc) rc = fac_panels(J0, J1);
+            if (rc) return rc;
+        }
+        int rc = trinv(0, nblk);   // all diagonal-block inverses at once
         if (rc) return rc;
+        for (int I0 = 0, Ib = 0; I0 < K; I0 += NBI, ++Ib) {
+            const int I1 = (K - I0 < NBI) ? K : I0 + NBI;
+            rc = inv_product(I0, I1, Ib);
+            if (!rc) rc = inv_row(I0, I1);
+            if (rc) return rc;
+        }
+    } else {
+        // one walk over the block rows (NBO == NBI): see chol_merge_mode()
+        for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
+            const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
+            int rc;
+            if (merge_mode == CHOL_WALK_MERGED && tab->row[Jb].n_items > 0) {
+                rc = g3_row(tab->row[Jb], Rpl, J0, J0, J1 - J0, K - J0, A + (size_t)J0 * K + J0, sA, G3_SUB, /*second=*/true);
+            } else {
+                rc = fac_product(J0, J1, Jb);
+                if (!rc) rc = inv_product(J0, J1, Jb);
+            }
+            if (!rc) rc = fac_panels(J0, J1);
+            if (!rc) rc = trinv(J0 / NB, (J1 - J0 + NB - 1) / NB);
+            if (!rc) rc = inv_row(J0, J1);
+            if (rc) return rc;
+        }
     }
     hipLaunchKernelGGL(flat_reverse_lower_to_upper_kernel, dim3((K + 255) / 256, K, nprob), dim3(256), 0, stream, U, K, sU);
     QT_LAUNCH_CHECK();
@@ -1047,4 +1162,99 @@ extern "C" int qt_cholesky_inverse_upper_batched_bounded(float* A, int64_t strid
     QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
                  "qt_cholesky_inverse_upper_batched_bounded: strides must be multiples of 4 elements and >= K*K");
     return chol_run(A, strideA, K, U, strideU, info, n_problems, workspace, workspace_bytes, (hipStream_t)stream_, min_eig_lb);
+}
+
+// Host-only self-check of the chain's item tables (no GPU needed; tests/test_chol_g3_plan.py) at the default block
+// sizes (512 / 512): merged = 0 the separate tables of QT_CHOL_MERGE=0 / order, 1 those of QT_CHOL_MERGE=1; min_chunks
+// <= 0: the default threshold.  Over all block rows it verifies that every tile of both segments is covered exactly once
+// over its k range (the triangular start on segment 1 / the inverse's product), that a tile's pieces are contiguous,
+// in slab order and at least 2 chunks long, that slab ids are unique per launch and below the count the workspace is
+// sized for (the separate tables'), and that no launch has more items than the cap.  counts_out[5]: product launches,
+// items, slabs (all rows), the workspace's slab count, table bytes.  Returns 0, or a negative code naming the property.
+extern "C" int qt_chol_g3_plan_check(int K, int merged, int min_chunks, long long* counts_out) {
+    if (K <= 0) return -1;
+    constexpr int NBX = 512, TRI_STEP = 256 / G3_CHUNK_ROWS;
+    if (min_chunks <= 0) min_chunks = 64;
+    const int cap = chol_g3_target_items(K);
+    CholG3Plan sep, pl;
+    std::vector<char> sep_bytes, bytes;
+    chol_g3_build(K, NBX, NBX, min_chunks, cap, false, sep, sep_bytes);
+    chol_g3_build(K, NBX, NBX, min_chunks, cap, merged != 0, pl, bytes);
+    if (pl.max_slabs > sep.max_slabs || pl.blob_bytes > sep.blob_bytes) return -2;
+    long long launches = 0, n_items = 0, n_slabs = 0;
+    // one table: segment 0 = Tm x Tn0 tiles from chunk 0 (tri0: from the tile column's own chunk), segment 1 = Tm x Tn1
+    auto check = [&](const G3Step& st, int Tm, int Tn0, int tri0, int Tn1, int c_end) -> int {
+        if (st.n_items <= 0) return 0;
+        const G3Item* items = (const G3Item*)(bytes.data() + st.item_off);
+        const G3Red* red = (const G3Red*)(bytes.data() + st.red_off);
+        if (st.n_items > cap && st.n_items > Tm * (Tn0 + Tn1)) return -3;
+        const int Tn[2] = {Tn0, Tn1};
+        auto lo_of = [&](int seg, int tj) { return (seg == 1 || tri0) ? TRI_STEP * tj : 0; };
+        std::vector<int> cover((size_t)2 * Tm * (Tn0 + Tn1 + 1) * c_end, 0);
+        auto cell = [&](int seg, int ti, int tj, int c) { return (((size_t)seg * Tm + ti) * (Tn0 + Tn1 + 1) + tj) * c_end + c; };
+        std::vector<int> owner(sep.max_slabs, -1);
+        int slabs_here = 0;
+        for (int q = 0; q < st.n_items; ++q) {
+            const G3Item& it = items[q];
+            const int seg = (it.tile & G3_SEG_BIT) ? 1 : 0, ti = it.tile >> 16, tj = it.tile & G3_TJ_MASK;
+            if (ti < 0 || ti >= Tm || tj >= Tn[seg]) return -4;
+            const int lo = lo_of(seg, tj);
+            if (it.c_lo < lo || it.c_hi > c_end || it.c_hi - it.c_lo < 2) return -5;
+            for (int c = it.c_lo; c < it.c_hi; ++c) cover[cell(seg, ti, tj, c)]++;
+            if (it.slab < 0) {
+                if (it.c_lo != lo || it.c_hi != c_end) return -6;
+            } else {
+                if (it.slab >= sep.max_slabs) return -7;
+                if (owner[it.slab] >= 0) return -8;
+                owner[it.slab] = q;
+                ++slabs_here;
+            }
+        }
+        for (int seg = 0; seg < 2; ++seg)
+            for (int ti = 0; ti < Tm; ++ti)
+                for (int tj = 0; tj < Tn[seg]; ++tj)
+                    for (int c = 0; c < c_end; ++c)
+                        if (cover[cell(seg, ti, tj, c)] != (c >= lo_of(seg, tj) ? 1 : 0)) return -9;
+        int in_red = 0;
+        for (int r = 0; r < st.n_red; ++r) {
+            const G3Red& e = red[r];
+            if (e.count < 2 || e.first < 0 || e.first + e.count > sep.max_slabs || (e.seg != 0 && e.seg != 1)) return -10;
+            const int want_tile = e.tile | (e.seg ? G3_SEG_BIT : 0);
+            int prev_hi = lo_of(e.seg, e.tile & G3_TJ_MASK);
+            for (int q = 0; q < e.count; ++q) {
+                const int o = owner[e.first + q];
+                if (o < 0 || items[o].tile != want_tile || items[o].c_lo != prev_hi) return -11;
+                prev_hi = items[o].c_hi;
+                owner[e.first + q] = -2;   // listed once
+            }
+            if (prev_hi != c_end) return -12;
+            in_red += e.count;
+        }
+        if (in_red != slabs_here) return -13;
+        ++launches;
+        n_items += st.n_items;
+        n_slabs += slabs_here;
+        return 0;
+    };
+    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBX, ++Jb) {
+        const int J1 = (K - J0 < NBX) ? K : J0 + NBX;
+        const int Tm = (J1 - J0 + 255) / 256, Tn0 = (K - J0 + 255) / 256, Tn1 = (J0 + 255) / 256, c_end = J0 / G3_CHUNK_ROWS;
+        int rc = 0;
+        if (Jb < (int)pl.row.size() && pl.row[Jb].n_items > 0) {
+            if (pl.fac[Jb].n_items > 0 || pl.inv[Jb].n_items > 0) return -14;
+            rc = check(pl.row[Jb], Tm, Tn0, 0, Tn1, c_end);
+        } else {
+            rc = check(pl.fac[Jb], Tm, Tn0, 0, 0, c_end);
+            if (!rc) rc = check(pl.inv[Jb], Tm, Tn1, 1, 0, c_end);
+        }
+        if (rc) return rc;
+    }
+    if (counts_out) {
+        counts_out[0] = launches;
+        counts_out[1] = n_items;
+        counts_out[2] = n_slabs;
+        counts_out[3] = sep.max_slabs;
+        counts_out[4] = (long long)pl.blob_bytes;
+    }
+    return 0;
 }

@@ -24,7 +24,7 @@ constexpr int G3_CHUNK_ROWS = 64;   // granularity of an item's k range
 
 // One workgroup = one item: a 256x256 output tile over k rows [64*c_lo, 64*c_hi) of the planes (>= 2 chunks).
 struct G3Item {
-    int tile;   // (ti << 16) | tj : output rows 256*ti.., columns 256*tj..
+    int tile;   // (ti << 16) | (segment << 15) | tj : output rows 256*ti.., columns 256*tj.. of the segment's C
     int c_lo;   // k range in chunks of G3_CHUNK_ROWS rows, relative to row0 of the call
     int c_hi;
     int slab;   // < 0: the item covers the tile's whole k range and applies it to C itself (C -= acc / C = acc);
@@ -35,8 +35,10 @@ struct G3Red {
     int tile;
     int first;
     int count;
-    int pad;
+    int seg;    // segment (0 / 1) whose C the tile belongs to
 };
+constexpr int G3_SEG_BIT = 1 << 15;   // in G3Item::tile (G3Red::tile carries ti and tj only)
+constexpr int G3_TJ_MASK = G3_SEG_BIT - 1;
 
 enum { G3_SUB = 0, G3_SET = 1, G3_ADD = 2 };   // C -= product  /  C = product  /  C += product
 
@@ -79,6 +81,16 @@ struct G3Args {
     int planes = G3_BF16X3;
     const int32_t* eA = nullptr;
     const int32_t* eB = nullptr;
+    // Second segment (Bpl1 != nullptr): the same launch also forms  A^T B1  into C1.  Items and reductions whose tile
+    // carries G3_SEG_BIT read B1's planes (layout, pitch and batch stride as B's) from column colB01 on and apply to
+    // C1 [M][N1] with mode1; everything on the A side, the slabs and the tables are shared.
+    const unsigned short* Bpl1 = nullptr;
+    int colB01 = 0;
+    const int32_t* eB1 = nullptr;
+    float* C1 = nullptr;
+    int64_t ldc1 = 0, bsC1 = 0;
+    int mode1 = G3_SET;
+    int N1 = 0;
 };
 
 // Enqueue the product (and the slab reduction when n_red > 0).  Returns qt_status.
@@ -107,3 +119,9 @@ int g3_scale_exponent(float bound);
 // of the 256 CUs), longest first.
 long g3_row_chunks(int Tm, int Tn, int c_end, int tri);
 void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items, std::vector<G3Red>& red, int target_items = 0);
+// One table for the two products of a block row that share the A operand and the k range: segment 0 = Tm x Tn0 tiles
+// over chunks [0, c_end), segment 1 = Tm x Tn1 tiles with the triangular start (G3_SEG_BIT set in their tile).  Same
+// rule as g3_plan_row over the union of the tiles; slab ids run across both segments.  max_slabs > 0: pieces grow
+// until the table needs no more slabs than that.
+void g3_plan_row2(int Tm, int Tn0, int Tn1, int c_end, std::vector<G3Item>& items, std::vector<G3Red>& red,
+                  int target_items = 0, int max_slabs = 0);

@@ -63,6 +63,12 @@ struct G3Params {
     int64_t bsA_bytes, bsB_bytes, bsC, bsSlabs;   // problem blockIdx.y of a batch
     const int32_t* eA;    // LOOP_DUO: scale exponents of the planes, one per problem
     const int32_t* eB;
+    // segment 1 (items with G3_SEG_BIT; gemm3_tn.h): what differs from segment 0
+    const char* Bpl1;
+    const int32_t* eB1;
+    float* C1;
+    int64_t ldc1, bsC1;
+    int colB01, N1, mode1;
 };
 
 // LOOP_TRI: the tri-unit loop (default); LOOP_CHUNK: the chunk loop (QT_G3_LOOP=chunk); LOOP_DUO: two fp16 planes
@@ -76,18 +82,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     const int wave_m = wave >> 2, wave_n = wave & 3;
     const bool group_b = wave >= 4;
 
-    if (blockIdx.y) {       // problem b of a batch of identical shapes
-        p.Apl += (size_t)blockIdx.y * p.bsA_bytes;
-        p.Bpl += (size_t)blockIdx.y * p.bsB_bytes;
-        p.C += (size_t)blockIdx.y * p.bsC;
-        p.slabs += (size_t)blockIdx.y * p.bsSlabs;
-    }
     const G3Item* itp = p.items + blockIdx.x;
     const int it_tile = __builtin_amdgcn_readfirstlane(itp->tile);
+    // the item's segment (uniform): which B planes it reads here, which C it applies to in the epilogue
+    const bool seg1 = (it_tile & G3_SEG_BIT) != 0;
+    const char* Bpl = seg1 ? p.Bpl1 : p.Bpl;
+    const int colB0 = seg1 ? p.colB01 : p.colB0;
+    if (blockIdx.y) {       // problem b of a batch of identical shapes
+        p.Apl += (size_t)blockIdx.y * p.bsA_bytes;
+        Bpl += (size_t)blockIdx.y * p.bsB_bytes;
+        p.slabs += (size_t)blockIdx.y * p.bsSlabs;
+    }
     const int c_lo = __builtin_amdgcn_readfirstlane(itp->c_lo);
     const int c_hi = __builtin_amdgcn_readfirstlane(itp->c_hi);
     const int slab_idx = __builtin_amdgcn_readfirstlane(itp->slab);
-    const int ti = it_tile >> 16, tj = it_tile & 0xFFFF;
+    const int ti = it_tile >> 16, tj = it_tile & G3_TJ_MASK;
     // chunk loop: a multiple of 24 (items are >= 2 chunks: nu >= 48); tri-unit and f16x2 loops: a multiple of 4, >= 8
     const int nu = (c_hi - c_lo) * (LOOP != LOOP_CHUNK ? CH_ROWS / UT : CH_UNITS);
 
@@ -97,7 +106,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     const int lch = (lane & 15) ^ (rsub << 2);
     const int trow = 4 * (wave & 3) + rsub;
     int colA = p.colA0 + ti * BT + (wave >> 2) * 128 + lch * 8;
-    int colB = p.colB0 + tj * BT + (wave >> 2) * 128 + lch * 8;
+    int colB = colB0 + tj * BT + (wave >> 2) * 128 + lch * 8;
     colA = colA > p.colmax - 8 ? p.colmax - 8 : colA;   // edge tiles: clamp (masked at the store)
     colB = colB > p.colmaxB - 8 ? p.colmaxB - 8 : colB;
     const unsigned voffA = (unsigned)((size_t)trow * (size_t)p.ld2 + (size_t)colA * 2);
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     if constexpr (LOOP == LOOP_DUO) {
         // running scalar source pointers (plane hi) of the next duo-unit to issue
         const char* runA = p.Apl + (p.rowA0 + (int64_t)c_lo * CH_ROWS) * p.ld2;
-        const char* runB = p.Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
+        const char* runB = Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
         auto issue2 = [&](int slot) {
             const unsigned d = dst_wave + (unsigned)slot * DUO_BYTES;
 #pragma unroll
@@ -175,7 +184,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
             ring_stagger_end(group_b);
         }
         // undo the scales of the planes and the 2^11 of the products: a power of two, exact
-        const int es = -(11 + p.eA[blockIdx.y] + p.eB[blockIdx.y]);
+        const int es = -(11 + p.eA[blockIdx.y] + (seg1 ? p.eB1 : p.eB)[blockIdx.y]);
         const float unscale = __builtin_bit_cast(float, (unsigned)(127 + (es < -126 ? -126 : es > 127 ? 127 : es)) << 23);
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
@@ -186,7 +195,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     } else if constexpr (TRI) {
         // running scalar source pointers (plane hi) of the next tri-unit to issue
         const char* runA = p.Apl + (p.rowA0 + (int64_t)c_lo * CH_ROWS) * p.ld2;
-        const char* runB = p.Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
+        const char* runB = Bpl + (p.rowB0 + (int64_t)c_lo * CH_ROWS) * p.ld2B;
         auto issue3 = [&](int slot) {
             const unsigned d = dst_wave + (unsigned)slot * TRI_BYTES;
 #pragma unroll
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
             const int64_t plA = (PA_BITS >> (2 * pr)) & 3u, plB = (PB_BITS >> (2 * pr)) & 3u;
             const int64_t row = (int64_t)(c_lo + c) * CH_ROWS + j * UT;
             a = p.Apl + plA * p.plane_bytes + (p.rowA0 + row) * p.ld2;
-            b = p.Bpl + plB * p.plane_bytesB + (p.rowB0 + row) * p.ld2B;
+            b = Bpl + plB * p.plane_bytesB + (p.rowB0 + row) * p.ld2B;
         };
         auto issue = [&](int i, int slot) {
             const char *a, *b;
@@ -312,22 +321,32 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
     // ---- epilogue ----
     const int jl = lane & 31, ih = 4 * (lane >> 5);
     if (slab_idx < 0) {
+        float* C = (seg1 ? p.C1 : p.C) + (size_t)blockIdx.y * (size_t)(seg1 ? p.bsC1 : p.bsC);
+        const int64_t ldc = seg1 ? p.ldc1 : p.ldc;
+        const int N = seg1 ? p.N1 : p.N;
+        auto apply = [&](auto mode_c) {
+            constexpr int M_ = decltype(mode_c)::value;
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
+            for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                const int gj = tj * BT + wave_n * 64 + ni * 32 + jl;
+                for (int ni = 0; ni < 2; ++ni) {
+                    const int gj = tj * BT + wave_n * 64 + ni * 32 + jl;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int gi = ti * BT + wave_m * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + ih;
-                    if (gi < p.M && gj < p.N) {
-                        float* dst = p.C + (size_t)gi * p.ldc + gj;
-                        if (MODE == G3_SUB) *dst = *dst - acc[mi][ni][r];
-                        else if (MODE == G3_ADD) *dst = *dst + acc[mi][ni][r];
-                        else *dst = acc[mi][ni][r];
+                    for (int r = 0; r < 16; ++r) {
+                        const int gi = ti * BT + wave_m * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + ih;
+                        if (gi < p.M && gj < N) {
+                            float* dst = C + (size_t)gi * ldc + gj;
+                            if (M_ == G3_SUB) *dst = *dst - acc[mi][ni][r];
+                            else if (M_ == G3_ADD) *dst = *dst + acc[mi][ni][r];
+                            else *dst = acc[mi][ni][r];
+                        }
                     }
                 }
-            }
+        };
+        const int mode = seg1 ? p.mode1 : MODE;
+        if (mode == G3_SUB) apply(std::integral_constant<int, G3_SUB>{});
+        else if (mode == G3_ADD) apply(std::integral_constant<int, G3_ADD>{});
+        else apply(std::integral_constant<int, G3_SET>{});
     } else {
         float* slab = p.slabs + (size_t)slab_idx * (size_t)(BT * BT);
 #pragma unroll
@@ -346,12 +365,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm3_kernel(G3Params p) {
 // C[tile] (-)= sum of the tile's slabs in table order (one float4 per thread per step)
 __global__ __launch_bounds__(256) void gemm3_reduce_kernel(const float* __restrict__ slabs,
                                                            const G3Red* __restrict__ red, float* C, int64_t ldc,
-                                                           int M, int N, int mode, int64_t bsSlabs, int64_t bsC) {
+                                                           int M, int N, int mode, int64_t bsSlabs, int64_t bsC,
+                                                           float* C1, int64_t ldc1, int N1, int mode1, int64_t bsC1) {
+    const G3Red t = red[blockIdx.x];
+    if (t.seg) {            // a tile of segment 1 (gemm3_tn.h): its own C, extent and mode
+        C = C1;
+        ldc = ldc1;
+        N = N1;
+        mode = mode1;
+        bsC = bsC1;
+    }
     if (blockIdx.z) {
         slabs += (size_t)blockIdx.z * bsSlabs;
         C += (size_t)blockIdx.z * bsC;
     }
-    const G3Red t = red[blockIdx.x];
     const int ti = t.tile >> 16, tj = t.tile & 0xFFFF;
     const int part = blockIdx.y;   // 16 parts of 16 rows
     const size_t tile_elems = (size_t)BT * BT;
@@ -494,6 +521,19 @@ int qt_gemm3_launch(const G3Args& a, hipStream_t stream) {
                  "qt_gemm3_launch: plane mode %d needs its scale exponents", a.planes);
     p.eA = a.eA;
     p.eB = a.eB;
+    // second segment: absent = a copy of the first (no item carries G3_SEG_BIT then)
+    const bool two = a.Bpl1 != nullptr;
+    QT_CHECK_ARG(!two || (((uintptr_t)a.Bpl1 & 15) == 0 && a.C1 && a.N1 > 0 && (a.planes != G3_F16X2 || a.eB1) &&
+                          a.mode1 >= G3_SUB && a.mode1 <= G3_ADD),
+                 "qt_gemm3_launch: second segment incomplete");
+    p.Bpl1 = two ? (const char*)a.Bpl1 : p.Bpl;
+    p.eB1 = two ? a.eB1 : a.eB;
+    p.C1 = two ? a.C1 : a.C;
+    p.ldc1 = two ? a.ldc1 : a.ldc;
+    p.bsC1 = two ? a.bsC1 : a.bsC;
+    p.colB01 = two ? a.colB01 : a.colB0;
+    p.N1 = two ? a.N1 : a.N;
+    p.mode1 = two ? a.mode1 : a.mode;
     const dim3 grid(a.n_items, nb);
     // read per call: the tests run both loops on the same inputs in one process
     const char* loop_env = getenv("QT_G3_LOOP");
@@ -510,7 +550,7 @@ int qt_gemm3_launch(const G3Args& a, hipStream_t stream) {
     QT_LAUNCH_CHECK();
     if (a.n_red > 0) {
         hipLaunchKernelGGL(gemm3_reduce_kernel, dim3(a.n_red, 16, nb), dim3(256), 0, stream, (const float*)a.slabs, a.red,
-                           a.C, a.ldc, a.M, a.N, a.mode, a.bsSlabs, a.bsC);
+                           a.C, a.ldc, a.M, a.N, a.mode, a.bsSlabs, a.bsC, p.C1, p.ldc1, p.N1, p.mode1, p.bsC1);
         QT_LAUNCH_CHECK();
     }
     return QT_OK;
@@ -553,40 +593,76 @@ long g3_row_chunks(int Tm, int Tn, int c_end, int tri) {
     return total;
 }
 
-void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items, std::vector<G3Red>& red, int target_items) {
-    constexpr int TRI_STEP = 256 / G3_CHUNK_ROWS;
+// The rule behind both planners.  tiles: (tile word of G3Item, first chunk of its k range, segment), in table order.
+namespace {
+struct G3PlanTile {
+    int tile, lo, seg;
+};
+void g3_deal_xcds(std::vector<G3Item>& items);
+void g3_plan_tiles(const std::vector<G3PlanTile>& tiles, int c_end, std::vector<G3Item>& items, std::vector<G3Red>& red,
+                   int target_items, int max_slabs) {
     items.clear();
     red.clear();
-    const long total = g3_row_chunks(Tm, Tn, c_end, tri);
+    long total = 0;
+    for (const G3PlanTile& t : tiles) total += std::max(0, c_end - t.lo);
     const int cap = target_items > 0 && target_items < NUM_CU ? target_items : NUM_CU;   // items per product (at most one round of the CUs)
     // smallest piece length (in chunks, >= 2) with which all pieces fit one round of the 256 CUs
-    auto count_items = [&](int per) {
+    auto count_items = [&](int per, long& n_slabs) {
         long n_items = 0;
-        for (int tj = 0; tj < Tn; ++tj) {
-            const int n = c_end - (tri ? TRI_STEP * tj : 0);
-            if (n > 0) n_items += (long)Tm * ((n + per - 1) / per);
+        n_slabs = 0;
+        for (const G3PlanTile& t : tiles) {
+            const int n = c_end - t.lo;
+            if (n <= 0) continue;
+            const int pieces = (n + per - 1) / per;
+            n_items += pieces;
+            if (pieces > 1) n_slabs += pieces;
         }
         return n_items;
     };
     int per = std::max(2, (int)((total + cap - 1) / cap));
-    while (count_items(per) > cap && per < c_end) ++per;   // more tiles than the cap: one item per tile
+    long n_slabs = 0;
+    // more tiles than the cap: one item per tile.  A slab budget (max_slabs > 0) lengthens the pieces the same way.
+    while ((count_items(per, n_slabs) > cap || (max_slabs > 0 && n_slabs > max_slabs)) && per < c_end) ++per;
     int next_slab = 0;
-    for (int ti = 0; ti < Tm; ++ti)
-        for (int tj = 0; tj < Tn; ++tj) {
-            const int lo = tri ? TRI_STEP * tj : 0, n = c_end - lo;
-            if (n <= 0) continue;
-            const int pieces = (n + per - 1) / per;
-            const int tile = (ti << 16) | tj;
-            if (pieces == 1) {
-                items.push_back({tile, lo, c_end, -1});
-                continue;
-            }
-            red.push_back({tile, next_slab, pieces, 0});
-            for (int s = 0; s < pieces; ++s) {
-                const int a = lo + (int)((long)n * s / pieces), b = lo + (int)((long)n * (s + 1) / pieces);
-                items.push_back({tile, a, b, next_slab++});
-            }
+    for (const G3PlanTile& t : tiles) {
+        const int lo = t.lo, n = c_end - lo;
+        if (n <= 0) continue;
+        const int pieces = (n + per - 1) / per;
+        if (pieces == 1) {
+            items.push_back({t.tile, lo, c_end, -1});
+            continue;
         }
+        red.push_back({t.tile & ~G3_SEG_BIT, next_slab, pieces, t.seg});
+        for (int s = 0; s < pieces; ++s) {
+            const int a = lo + (int)((long)n * s / pieces), b = lo + (int)((long)n * (s + 1) / pieces);
+            items.push_back({t.tile, a, b, next_slab++});
+        }
+    }
+    g3_deal_xcds(items);
+}
+}  // namespace
+
+void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items, std::vector<G3Red>& red, int target_items) {
+    constexpr int TRI_STEP = 256 / G3_CHUNK_ROWS;
+    std::vector<G3PlanTile> tiles;
+    for (int ti = 0; ti < Tm; ++ti)
+        for (int tj = 0; tj < Tn; ++tj) tiles.push_back({(ti << 16) | tj, tri ? TRI_STEP * tj : 0, 0});
+    g3_plan_tiles(tiles, c_end, items, red, target_items, 0);
+}
+
+void g3_plan_row2(int Tm, int Tn0, int Tn1, int c_end, std::vector<G3Item>& items, std::vector<G3Red>& red, int target_items,
+                  int max_slabs) {
+    constexpr int TRI_STEP = 256 / G3_CHUNK_ROWS;
+    std::vector<G3PlanTile> tiles;
+    for (int ti = 0; ti < Tm; ++ti)
+        for (int tj = 0; tj < Tn0; ++tj) tiles.push_back({(ti << 16) | tj, 0, 0});
+    for (int ti = 0; ti < Tm; ++ti)
+        for (int tj = 0; tj < Tn1; ++tj) tiles.push_back({(ti << 16) | G3_SEG_BIT | tj, TRI_STEP * tj, 1});
+    g3_plan_tiles(tiles, c_end, items, red, target_items, max_slabs);
+}
+
+namespace {
+void g3_deal_xcds(std::vector<G3Item>& items) {
     // longest items first (they all start in the first round; the order only matters beyond 256 items)
     std::stable_sort(items.begin(), items.end(),
                      [](const G3Item& x, const G3Item& y) { return (x.c_hi - x.c_lo) > (y.c_hi - y.c_lo); });
@@ -617,6 +693,7 @@ void g3_plan_row(int Tm, int Tn, int c_end, int tri, std::vector<G3Item>& items,
         items.swap(dealt);
     }
 }
+}  // namespace
 
 // e = 3 - ceil(log2(bound)): |x| <= bound  =>  |x| * 2^e <= 2^3, one binade under the fp16 planes' 2^4 limit
 int g3_scale_exponent(float bound) {

@@ -87,6 +87,7 @@ SIGNATURES = {
                            c_size_t, c_void_p]),
     "qt_gemm3_plan_check": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "qt_xtx_tile_table_check": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+    "qt_chol_g3_plan_check": (c_int, [c_int, c_int, c_int, c_void_p]),
     "qt_gemm3_tn_f32_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "qt_gemm3_tn_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                 c_void_p, c_size_t, c_void_p]),

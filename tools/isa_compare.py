@@ -7,6 +7,10 @@ Per kernel it prints one of
   PIPELINE    the text differs, but between the kernel's first and last s_barrier the instruction count is the same
               and the pipeline instructions (MFMA, LDS reads, LDS-DMA, s_waitcnt, s_barrier, s_setprio, s_sleep,
               branches) are the same sequence once register numbers are masked
+  LOOPS       neither, but every basic block that holds an MFMA -- the bodies and tails of the ring loops -- is the same
+              instruction sequence once register numbers and labels are masked: what changed lies in the prologue and
+              the epilogue (epilogue code that the scheduler places ahead of the loop's closing barrier counts into
+              the PIPELINE region and fails that test)
   DIFFERENT   anything else
 and exits 1 when a kernel is DIFFERENT or missing."""
 import re
@@ -42,6 +46,23 @@ def region(lines):
     return len(reg), [l for l in mask if l.startswith(PIPE)]
 
 
+def mfma_blocks(lines):
+    out, cur = [], []
+    for l in lines:
+        t = l.split(";")[0].strip()
+        if not t or t.startswith(".") or t.endswith(":"):
+            if t.endswith(":") and cur:
+                out.append(cur)
+                cur = []
+            continue
+        cur.append(re.sub(r"\.LBB\d+_\d+", ".L", re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", t)))
+        if t.startswith(("s_cbranch", "s_branch")):
+            out.append(cur)
+            cur = []
+    out.append(cur)
+    return [b for b in out if any(i.startswith("v_mfma") for i in b)]
+
+
 def main(a_path, b_path):
     a, b = kernels(a_path), kernels(b_path)
     bad = 0
@@ -52,9 +73,11 @@ def main(a_path, b_path):
             verdict = "IDENTICAL"
         elif region(a[k]) == region(b[k]):
             verdict = "PIPELINE"
+        elif mfma_blocks(a[k]) and mfma_blocks(a[k]) == mfma_blocks(b[k]):
+            verdict = "LOOPS"
         else:
             verdict = "DIFFERENT"
-        bad += verdict not in ("IDENTICAL", "PIPELINE")
+        bad += verdict not in ("IDENTICAL", "PIPELINE", "LOOPS")
         print(f"{verdict:10s} {k}")
     return 1 if bad else 0
 
