@@ -9,16 +9,19 @@ per column on the device, sweep.hip: "tolerance 1e-6, not part of the bit-exact 
 the shapes are chosen to reach code paths, not job sizes.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+from tests.test_gpu_sweep_fused import chain_launches, fused_launches, sweep_launches
 from tests.util import synth_activations, synth_weight
 
 pytestmark = pytest.mark.gpu
 
-SWEEP_ENV = ("QT_SWEEP_BLOCK", "QT_SWEEP_BATCH", "QT_SWEEP_FAR", "QT_SGEMM_RING", "QT_SGEMM_RING_MIN_TILES")
+SWEEP_ENV = ("QT_SWEEP_FUSED", "QT_SWEEP_LANES", "QT_SWEEP_BLOCK", "QT_SWEEP_BATCH", "QT_SWEEP_FAR", "QT_SGEMM_RING",
+             "QT_SGEMM_RING_MIN_TILES")
 
 
 @pytest.fixture(autouse=True)
@@ -167,14 +170,22 @@ def test_far_update_batch_length(ops, oracle, dev, monkeypatch, batch, K, bits, 
     _check(ops, dev, _case(oracle, 130, K, 128 if K == 1152 else -1, sym, bits))
 
 
-@pytest.mark.parametrize("batch", [3, 8])
-def test_chained_far_update_on_the_ring_kernel(ops, oracle, dev, monkeypatch, batch):
+@pytest.mark.parametrize("batch,form", [(3, "chain"), (8, "chain"), (3, "fused"), (8, "fused")],
+                         ids=["3", "8", "3-fused", "8-fused"])
+def test_chained_far_update_on_the_ring_kernel(ops, oracle, dev, monkeypatch, batch, form):
     """R = 256, K = 1152: whole 128 x 128 tiles, so with ``QT_SGEMM_RING_MIN_TILES=1`` every update product of the
-    sweep -- the chained far updates (three or eight chains) included -- is served by ``sgemm_ring_kernel``."""
+    chain of launches (``QT_SWEEP_FUSED=0``: a shape of whole tiles takes the fused form otherwise) -- the chained
+    far updates (three or eight chains) included -- is served by ``sgemm_ring_kernel``.  "fused": the same case in
+    the form the default takes, whose far update walks the same tiles inside ``sweep_fused_kernel``'s launch.  The
+    count of block-kernel launches tells which of the two ran."""
     monkeypatch.setenv("QT_SWEEP_BATCH", str(batch))
     monkeypatch.setenv("QT_SGEMM_RING", "1")
     monkeypatch.setenv("QT_SGEMM_RING_MIN_TILES", "1")
-    _check(ops, dev, _case(oracle, 256, 1152, 128, False, 8))
+    if form == "chain":
+        monkeypatch.setenv("QT_SWEEP_FUSED", "0")
+    c = _case(oracle, 256, 1152, 128, False, 8)
+    _, launches = sweep_launches(lambda: _check(ops, dev, c))
+    assert launches == (chain_launches(1152) if form == "chain" else fused_launches(1152, batch))
 
 
 # ------------------------------------------------------------------------------------ e. dead columns
@@ -208,6 +219,55 @@ def _grouped_gs(K):
     return 128 if K % 128 == 0 else 68        # 1156 = 17 * 68
 
 
+@functools.lru_cache(maxsize=2)      # the parameter that changes least often is the case's: a case is built once
+def _grouped_case(oracle, row_end, K, bits, sym):
+    """Inputs of one stacked sweep and, per group, the oracle's outputs for that group's rows alone (its own factor
+    and ``g_idx``).  At 8 bits every group's levels must reach both ends of the range."""
+    n = len(row_end)
+    gs = _grouped_gs(K)
+    row_begin = (0,) + row_end[:-1]
+    Wn = synth_weight(row_end[-1], K, seed=n + K + bits)
+    scale, zp = oracle.minmax_qparams(Wn, gs, sym, bits)
+    g_idx = np.stack([_permuted_g_idx(K, gs, 100 + g) for g in range(n)])
+    factors = [_factor(oracle, K, 1000 + g)[0] for g in range(n)]
+    qmin, qmax = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
+    want = []
+    for g in range(n):
+        r0, r1 = row_begin[g], row_end[g]
+        Qo, Wo, lo = oracle.gptq_sweep_c(Wn[r0:r1], factors[g], scale[r0:r1], zp[r0:r1], g_idx[g], 128, bits)
+        if bits == 8:
+            assert Qo.min() == qmin and Qo.max() == qmax
+        want.append((Qo, Wo, lo))
+    return dict(row_end=list(row_end), row_begin=list(row_begin), K=K, bits=bits, W=Wn, scale=scale, zp=zp, g_idx=g_idx,
+                factors=factors, want=want)
+
+
+def _check_grouped(ops, dev, c):
+    """``ops.gptq_sweep_grouped`` on the case, the factors as [K, K] slices of a wider buffer whose gaps hold NaN; each
+    group's rows of the levels, of W and of the loss against the oracle on that group alone."""
+    n, K, bits = len(c["row_end"]), c["K"], c["bits"]
+    pad = 256
+    ubuf = torch.full((n, K * K + pad), float("nan"), dtype=torch.float32, device=dev)
+    U = ubuf[:, :K * K].view(n, K, K)
+    for g in range(n):
+        U[g].copy_(torch.from_numpy(c["factors"][g]))
+    assert U.stride(0) > K * K
+    W = torch.from_numpy(c["W"].copy()).to(dev)
+    Qt, loss = ops.gptq_sweep_grouped(W, U, c["row_end"], torch.from_numpy(np.ascontiguousarray(c["scale"].T)).to(dev),
+                                      torch.from_numpy(np.ascontiguousarray(c["zp"].T)).to(dev),
+                                      torch.from_numpy(c["g_idx"]).to(dev), 128, bits)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(ubuf[:, K * K:]).all()), "the gap between two factors was written"
+    qmin, qmax = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
+    assert int(Qt.min()) >= qmin and int(Qt.max()) <= qmax
+    q, w, ls = Qt.cpu().numpy().T, W.cpu().numpy(), loss.cpu().numpy()
+    for g, (Qo, Wo, lo) in enumerate(c["want"]):
+        r0, r1 = c["row_begin"][g], c["row_end"][g]
+        assert np.array_equal(q[r0:r1], Qo), f"group {g}: {(q[r0:r1] != Qo).sum()} of {Qo.size} levels differ"
+        np.testing.assert_array_equal(w[r0:r1], Wo, err_msg=f"group {g}")
+        np.testing.assert_allclose(ls[r0:r1], lo, rtol=1e-6, err_msg=f"group {g}")
+
+
 @pytest.mark.parametrize("form", ["quad", "row"])
 @pytest.mark.parametrize("bits,sym", [(4, True), (8, False)])
 @pytest.mark.parametrize("K", [640, 1156])
@@ -219,37 +279,7 @@ def test_grouped_sweep_each_group_against_the_oracle(ops, oracle, dev, monkeypat
     levels, of W and of the loss are held to ``gptq_sweep_c`` on that group alone.  n = 16 is SG_MAX_GROUPS."""
     if form == "row":
         monkeypatch.setenv("QT_SWEEP_BLOCK", "row")
-    gs = _grouped_gs(K)
-    row_end = _grouped_rows(n)
-    row_begin = [0] + row_end[:-1]
-    R = row_end[-1]
-    Wn = synth_weight(R, K, seed=n + K + bits)
-    scale, zp = oracle.minmax_qparams(Wn, gs, sym, bits)
-    g_idx = np.stack([_permuted_g_idx(K, gs, 100 + g) for g in range(n)])
-    factors = [_factor(oracle, K, 1000 + g)[0] for g in range(n)]
-    pad = 256
-    ubuf = torch.full((n, K * K + pad), float("nan"), dtype=torch.float32, device=dev)
-    U = ubuf[:, :K * K].view(n, K, K)
-    for g in range(n):
-        U[g].copy_(torch.from_numpy(factors[g]))
-    assert U.stride(0) > K * K
-    W = torch.from_numpy(Wn.copy()).to(dev)
-    Qt, loss = ops.gptq_sweep_grouped(W, U, row_end, torch.from_numpy(np.ascontiguousarray(scale.T)).to(dev),
-                                      torch.from_numpy(np.ascontiguousarray(zp.T)).to(dev),
-                                      torch.from_numpy(g_idx).to(dev), 128, bits)
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(ubuf[:, K * K:]).all()), "the gap between two factors was written"
-    qmin, qmax = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
-    assert int(Qt.min()) >= qmin and int(Qt.max()) <= qmax
-    q, w, ls = Qt.cpu().numpy().T, W.cpu().numpy(), loss.cpu().numpy()
-    for g in range(n):
-        r0, r1 = row_begin[g], row_end[g]
-        Qo, Wo, lo = oracle.gptq_sweep_c(Wn[r0:r1], factors[g], scale[r0:r1], zp[r0:r1], g_idx[g], 128, bits)
-        if bits == 8:
-            assert Qo.min() == qmin and Qo.max() == qmax
-        assert np.array_equal(q[r0:r1], Qo), f"group {g}: {(q[r0:r1] != Qo).sum()} of {Qo.size} levels differ"
-        np.testing.assert_array_equal(w[r0:r1], Wo, err_msg=f"group {g}")
-        np.testing.assert_allclose(ls[r0:r1], lo, rtol=1e-6, err_msg=f"group {g}")
+    _check_grouped(ops, dev, _grouped_case(oracle, tuple(_grouped_rows(n)), K, bits, sym))
 
 
 def test_grouped_sweep_refuses_bad_boundaries_and_strides(ops, dev):

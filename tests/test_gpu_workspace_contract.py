@@ -262,7 +262,7 @@ def _sweep(R, K, env, branch):
         t["Qt"], t["loss"] = ops.gptq_sweep(t["W"], t["U"], t["s"], t["z"], t["g"], 128, 4)
 
     return Case(
-        f"qt_gptq_sweep R={R} K={K}{' far=bf16x3' if env else ''}", branch, make,
+        f"qt_gptq_sweep R={R} K={K}{' far=bf16x3' if env and 'QT_SWEEP_FAR' in env else ''}", branch, make,
         lambda lib, t: lib.qt_gptq_sweep_workspace_bytes(R, K, 128),
         lambda lib, t, ws, nb: lib.qt_gptq_sweep(t["W"].data_ptr(), R, K, t["U"].data_ptr(), t["s"].data_ptr(),
                                                  t["z"].data_ptr(), G, t["g"].data_ptr(), 128, 4, t["Qt"].data_ptr(),
@@ -270,7 +270,7 @@ def _sweep(R, K, env, branch):
         via_ops, ["W", "Qt", "loss"], env)
 
 
-def _sweep_grouped(R, K, row_end, branch):
+def _sweep_grouped(R, K, row_end, branch, env=None):
     n = len(row_end)
     hW, hU, hs, hg = _sweep_inputs(R, K, n, R + K + n)
     G = K // 128
@@ -290,7 +290,7 @@ def _sweep_grouped(R, K, row_end, branch):
         lambda lib, t, ws, nb: lib.qt_gptq_sweep_grouped(
             t["W"].data_ptr(), R, K, t["U"].data_ptr(), K * K, n, ctypes.cast(ends, ctypes.c_void_p), t["s"].data_ptr(),
             t["z"].data_ptr(), G, t["g"].data_ptr(), 128, 4, t["Qt"].data_ptr(), t["loss"].data_ptr(), ws, nb, _stream()),
-        via_ops, ["W", "Qt", "loss"])
+        via_ops, ["W", "Qt", "loss"], env)
 
 
 # ---------------------------------------------------------------------------------------------------------- a12: AWQ
@@ -450,7 +450,16 @@ CASES = [
     (_sgemm, (200, 136, 1000, 0, "sgemm: ragged M / N / k, split-k with Cin - acc in the reduction")),
     (_gemm3, (260, 516, 512, 0, "gemm3 test face kind 0: whole tiles, planes + item table (slab area unused)")),
     (_gemm3, (260, 516, 512, 1, "gemm3 test face kind 1: every tile cut along k into slabs")),
+    # qt_gptq_sweep_workspace_bytes again (appended: a case's id carries its index), on whole 128-tiles, where the sweep
+    # takes the fused form: two error buffers of one batch each, the second at ErrT + sweep_fused_err_bytes
+    # (FUSED_SWEEPS below holds each of these to the fused form's launch count)
+    (_sweep, (256, 1152, None, "fused sweep: two buffers of the default 4 blocks inside the classic 8-block ErrT")),
+    (_sweep, (256, 2304, {"QT_SWEEP_BATCH": "8"},
+              "fused sweep: 8-block batches, the second buffer lies beyond the classic ErrT (the size doubles)")),
+    (_sweep_grouped, (512, 768, [128, 384, 512], "fused grouped sweep: three row groups, 2-block batches, a far_rest with row groups",
+                      {"QT_SWEEP_BATCH": "2"})),
 ]
+FUSED_SWEEPS = CASES[-3:]
 
 
 def _id(entry):
@@ -466,6 +475,38 @@ def test_entry_point_stays_inside_the_workspace_it_asks_for(entry, offset, dev, 
     printed with a failure)."""
     builder, args = entry
     _run(builder(*args), dev, ops, monkeypatch, offset)
+
+
+@pytest.mark.parametrize("entry", FUSED_SWEEPS, ids=[_id(e) for e in FUSED_SWEEPS])
+def test_fused_sweep_cases_take_the_fused_form(entry, dev, ops, monkeypatch):
+    """The fused cases above are fused: through ``ops`` under their environment each makes ``ceil(K / (128 batch))``
+    block-kernel launches, not the chain's ``K / 128``."""
+    from tests.test_gpu_sweep_fused import chain_launches, default_batch, fused_launches, sweep_launches
+
+    builder, args = entry
+    case = builder(*args)
+    for k, v in case.env.items():
+        monkeypatch.setenv(k, v)
+    K = args[1]
+    batch = int(case.env.get("QT_SWEEP_BATCH", default_batch(K)))
+    t = case.make(dev)
+    _, launches = sweep_launches(lambda: case.via_ops(ops, t))
+    assert launches == fused_launches(K, batch) != chain_launches(K), launches
+
+
+def test_fused_sweep_doubles_the_workspace_only_for_8_block_batches(monkeypatch):
+    """R = 256, K = 2304: with 8-block batches the fused form asks for more than the chain of launches
+    (``QT_SWEEP_FUSED=0``), with 4-block batches for exactly as much."""
+    lib = _lib.load()
+    need = {}
+    for batch in ("4", "8"):
+        monkeypatch.setenv("QT_SWEEP_BATCH", batch)
+        monkeypatch.delenv("QT_SWEEP_FUSED", raising=False)
+        need[batch, "default"] = int(lib.qt_gptq_sweep_workspace_bytes(256, 2304, 128))
+        monkeypatch.setenv("QT_SWEEP_FUSED", "0")
+        need[batch, "chain"] = int(lib.qt_gptq_sweep_workspace_bytes(256, 2304, 128))
+    assert need["4", "default"] == need["4", "chain"] == need["8", "chain"] > 0
+    assert need["8", "default"] > need["8", "chain"]
 
 
 def test_every_size_function_has_a_case():
