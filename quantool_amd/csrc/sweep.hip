@@ -13,6 +13,15 @@
 // Up to 6144 rows, on whole 128-tiles, a batch of blocks runs as ONE launch instead (sweep_fused_kernel below): its
 // block steps and near updates per group of rows, beside the far update of the batch before it.
 // Bit-exact against oracle/gptq_oracle.c:orc_gptq_sweep.
+//
+// Three kernel forms run the 128 steps of a block, and the contract is stated once for all of them:
+//   sweep_block_kernel (QT_SWEEP_BLOCK=row)  one lane per row            quantise_weight + its own update loops
+//   sweep_quad_kernel  (chain of launches)   4 lanes per row             col_step<QuadLayout, ...>
+//   sweep_fused_kernel<16 | 8>               16 or 8 lanes per row       col_step<TriLayout<NL>, ...>
+// quantise_weight is the fp32 op sequence of one weight; col_step is the whole column step of the multi-lane forms
+// (read-ahead of U, quantise, broadcast of the owner's error, update of the lane's later columns), which differ only
+// in their broadcast (row_bcast) and in where a lane finds its U values in LDS (the two layout traits).  The host
+// side is sweep_run: the checks and the choice between sweep_run_fused and sweep_run_chain.
 #include <stdlib.h>
 
 #include <map>
@@ -45,6 +54,22 @@ __device__ __forceinline__ int sweep_group_of(const SweepGroups& sg, int row0) {
     int g = 0;
     while (g + 1 < sg.n && row0 >= sg.row_end[g]) ++g;
     return g;
+}
+
+// The quantise step of one weight, the only statement of it in this file: upstream's fp32 operations one by one, each
+// rounded on its own (no contraction) -- IEEE division (-fhip-fp32-correctly-rounded-divide-sqrt), clamp, round half
+// to even (rintf = v_rndne_f32), dequantise, and the error fed back to the later columns, diff / d with d = U[c][c].
+struct Quantised {
+    float q, dq, diff, e;   // level, dequantised value, w - dq, diff / d
+};
+__device__ __forceinline__ Quantised quantise_weight(float wv, float sc, float zz, float d, float qmin, float qmax) {
+    float x = wv / sc;
+    x = x + zz;
+    x = fminf(fmaxf(x, qmin), qmax);
+    const float q = rintf(x);
+    const float dq = (q - zz) * sc;
+    const float diff = wv - dq;
+    return {q, dq, diff, diff / d};
 }
 
 __global__ __launch_bounds__(ROWS) void sweep_block_kernel(float* __restrict__ W, int R, int K,
@@ -141,19 +166,13 @@ __global__ __launch_bounds__(ROWS) void sweep_block_kernel(float* __restrict__ W
             const int c = cb + t;
             {  // columns >= cnt of a ragged last block run as inert padding (w=0, U=0, d=1)
                 const float d = dd[c], rd2 = dd[BS + c];
-                const float wv = w[t];
-                float x = wv / sc[t];
-                x = x + zz[t];
-                x = fminf(fmaxf(x, qmin), qmax);
-                const float q = rintf(x);
-                const float dq = (q - zz[t]) * sc[t];
-                const float diff = wv - dq;
-                blk_loss = blk_loss + (diff * diff) * rd2;
-                const float e = diff / d;
+                const Quantised z = quantise_weight(w[t], sc[t], zz[t], d, qmin, qmax);
+                blk_loss = blk_loss + (z.diff * z.diff) * rd2;
+                const float e = z.e;
                 er[t] = e;
-                w[t] = dq;
+                w[t] = z.dq;
                 if (valid && c < cnt) {
-                    Qt[(size_t)(i1 + c) * R + row] = (int8_t)q;
+                    Qt[(size_t)(i1 + c) * R + row] = (int8_t)z.q;
                     ErrT[(size_t)c * R + row] = e;
                 }
                 const float* urow = Un + c * BS + cb;
@@ -229,10 +248,10 @@ __global__ __launch_bounds__(ROWS) void sweep_block_kernel(float* __restrict__ W
 // column, each step  w = w - (err * u)  with two roundings, IEEE division, round-half-even -- so the
 // outputs are bit for bit those of the row-per-lane kernel and of oracle/gptq_oracle.c:orc_gptq_sweep.
 // The per-row loss is summed in column order too (every lane of a quad carries the same running sum).
+// sweep_fused_kernel (further down) runs the same step with 16 or 8 lanes per row; the step is written once, for
+// NL lanes (col_step), right below.
 //
-// LDS: only the U block, laid out per (step c, lane class p): Up[c][p][m] = U[i1+c][i1+4m+p] for
-// 4m+p > c, else 0 (a lane reads its 32 - m0 values of a step as float4s; 36-float rows keep the four
-// classes of a quad on disjoint banks).  73 KiB per workgroup of 64 rows, so two workgroups share a CU
+// LDS: only the U block (QuadLayout).  73 KiB per workgroup of 64 rows, so two workgroups share a CU
 // with room left for a GEMM workgroup.
 constexpr int QL = 4;                 // lanes per row
 constexpr int QROWS = 64;             // rows per workgroup (128: half as many workgroups holding a CU's LDS, but the
@@ -243,77 +262,131 @@ constexpr int UP_P = QM + 4;          // floats per (c, p) row
 constexpr int UP_C = QL * UP_P;       // floats per step c
 constexpr size_t QUAD_LDS = (size_t)(BS * UP_C + 2 * BS) * sizeof(float);
 
-template <int P0>
-__device__ __forceinline__ float quad_bcast(float v) {
-    // every lane of a quad gets lane P0's value (DPP quad_perm [P0, P0, P0, P0])
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), P0 * 0x55, 0xF, 0xF, true));
+// every lane of a row's NL lanes gets lane P0's value: DPP quad_perm [P0, P0, P0, P0] within a quad, row_share within
+// 16 lanes; for 8 lanes the two halves of a DPP row take their own source lane (hi: this lane is in the upper half)
+template <int NL, int P0>
+__device__ __forceinline__ float row_bcast(float v, bool hi) {
+    const int x = __builtin_bit_cast(int, v);
+    if constexpr (NL == 4) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, P0 * 0x55, 0xF, 0xF, true));
+    } else if constexpr (NL == 16) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true));
+    } else {
+        static_assert(NL == 8, "4, 8 or 16 lanes per row");
+        const int lo = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true);
+        const int up = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0 + 8, 0xF, 0xF, true);
+        return __builtin_bit_cast(float, hi ? up : lo);
+    }
 }
 
-constexpr int QPF = 3;   // macro-steps (of 4 columns) a lane's scale / zero-point loads run ahead of their use
-
-struct QuadState {
-    float w[QM], sc[QM], zz[QM];   // sc / zz: only entries M0 .. M0 + QPF are live at macro-step M0
-    float u[2][QM], d[2];          // this lane's U values and the diagonal entry of step C in u[C & 1] / d[C & 1]: read one step ahead
+// What lane (r, p) of NL carries through a block: its BS / NL columns NL m + p of row r
+template <int NL>
+struct StepState {
+    static constexpr int NM = BS / NL;
+    float w[NM], sc[NM], zz[NM];   // sweep_quad_kernel streams sc / zz: only entries M0 .. M0 + QPF are live at macro-step M0
+    float u[2][NM], d[2];          // this lane's U values and the diagonal entry of step C in u[C & 1] / d[C & 1]: read one step ahead
     float lsum, qv, ev, dv;
 };
 
-// this lane's U values of step C (columns 4m + p, m >= C / 4) and U[C][C], from LDS into the registers of parity C & 1
-template <int C>
-__device__ __forceinline__ void quad_fetch(QuadState& s, const float* __restrict__ Up, const float* __restrict__ dd, int p) {
+// The U block in LDS.  The two layouts are all that differs between the forms' steps: where lane class p finds the
+// row of its values of step C, and at which float4 of that row the group k4 (the lane's columns 4 k4 .. 4 k4 + 3,
+// k4 >= band = C / (4 NL): the groups before it are wholly behind the step) lies.
+//
+// QuadLayout (sweep_quad_kernel): per (step c, lane class p): Up[c][p][m] = U[i1+c][i1+4m+p] for
+// 4m+p > c, else 0 (a lane reads its 32 - m0 values of a step as float4s; 36-float rows keep the four
+// classes of a quad on disjoint banks).
+struct QuadLayout {
+    static constexpr int NL = QL;
+    template <int C>
+    __device__ static __forceinline__ const f32x4* row(const float* __restrict__ Up, int p) {
+        return (const f32x4*)(Up + C * UP_C + p * UP_P);
+    }
+    static constexpr int at(int k4, int /*band*/) { return k4; }
+};
+
+// TriLayout (sweep_fused_kernel): the U block's strict upper triangle per (step, float4 group, lane class): step c
+// keeps only the groups its lanes still update, 48 KiB (NL = 16) / 40 KiB (NL = 8) instead of 64.
+template <int NL>
+struct LaneGeo {
+    static constexpr int NM = BS / NL;            // columns per lane
+    static constexpr int NK4 = NM / 4;            // float4 groups of a lane's columns
+    static constexpr int ROWS = 512 / NL;         // rows per workgroup
+    static constexpr int BLK = NL * 4;            // floats of one float4 group over the lane classes
+    static constexpr int BAND = 4 * NL;           // steps over which the first live group stays the same
+    // first float of step c: steps of band q = c / BAND keep groups q .. NK4 - 1
+    __host__ __device__ static constexpr int ut_base(int c) {
+        const int band = c / BAND, in = c % BAND;
+        return BLK * (BAND * (band * NK4 - band * (band - 1) / 2) + in * (NK4 - band));
+    }
+    static constexpr int UT_FLOATS = ut_base(BS);
+    static constexpr int ES_FLOATS = BS * ROWS;
+    static constexpr size_t LDS = (size_t)(UT_FLOATS + ES_FLOATS + 2 * BS) * sizeof(float);
+};
+static_assert(LaneGeo<16>::UT_FLOATS == 12288 && LaneGeo<8>::UT_FLOATS == 10240, "triangle layout");
+static_assert(LaneGeo<16>::LDS >= (size_t)RING_LDS_BYTES && LaneGeo<8>::LDS >= (size_t)RING_LDS_BYTES &&
+                  LaneGeo<16>::LDS <= 80 * 1024 && LaneGeo<8>::LDS <= 80 * 1024,
+              "the launch's LDS holds the ring, and two workgroups fit a CU");
+template <int NL_>
+struct TriLayout {
+    static constexpr int NL = NL_;
+    template <int C>
+    __device__ static __forceinline__ const f32x4* row(const float* __restrict__ Ut, int p) {
+        return (const f32x4*)(Ut + LaneGeo<NL>::ut_base(C) + p * 4);
+    }
+    static constexpr int at(int k4, int band) { return (k4 - band) * NL; }
+};
+
+// this lane's U values of step C (columns NL m + p, m >= C / NL) and U[C][C], from LDS into the registers of parity C & 1
+template <class L, int C>
+__device__ __forceinline__ void step_fetch(StepState<L::NL>& s, const float* __restrict__ Ub, const float* __restrict__ dd, int p) {
     if constexpr (C < BS) {
-        constexpr int M0 = C >> 2;
-        const f32x4* urow = (const f32x4*)(Up + C * UP_C + p * UP_P);
+        constexpr int band = C / (4 * L::NL);
+        const f32x4* urow = L::template row<C>(Ub, p);
 #pragma unroll
-        for (int k4 = M0 >> 2; k4 < QM / 4; ++k4) {
-            const f32x4 t = urow[k4];
+        for (int k4 = band; k4 < BS / L::NL / 4; ++k4) {
+            const f32x4 t = urow[L::at(k4, band)];
             s.u[C & 1][4 * k4 + 0] = t[0]; s.u[C & 1][4 * k4 + 1] = t[1]; s.u[C & 1][4 * k4 + 2] = t[2]; s.u[C & 1][4 * k4 + 3] = t[3];
         }
         s.d[C & 1] = dd[C];
     }
 }
 
-template <int M0, int P0>
-__device__ __forceinline__ void quad_step(QuadState& s, const float* __restrict__ Up, const float* __restrict__ dd,
-                                          int p, float qmin, float qmax) {
-    constexpr int C = 4 * M0 + P0;
+// Step C = NL M0 + P0 of a block, in every lane of the row (hi: row_bcast's, unused but for 8 lanes)
+template <class L, int M0, int P0>
+__device__ __forceinline__ void col_step(StepState<L::NL>& s, const float* __restrict__ Ub, const float* __restrict__ dd,
+                                         int p, bool hi, float qmin, float qmax) {
+    constexpr int NM = BS / L::NL;
+    constexpr int C = L::NL * M0 + P0;
     // The LDS reads of step C + 1 are issued before step C's arithmetic (a lone wave per SIMD has nothing else to cover
     // their latency with; rows beyond a ragged block's last column are zero-filled, so the read ahead is always valid)
 #if !defined(QT_SWEEP_LAB) || QT_SWEEP_LAB != 4     // lab build 4: the reads of a step at its own start, as up to round 4
-    quad_fetch<C + 1>(s, Up, dd, p);
-#else
-    quad_fetch<C>(s, Up, dd, p);
+    step_fetch<L, C + 1>(s, Ub, dd, p);
+#else                                               // (of sweep_quad_kernel only: the fused kernel has no lab builds)
+    step_fetch<L, L::NL == QL ? C : C + 1>(s, Ub, dd, p);
 #endif
     const float* u = s.u[C & 1];
-    const float d = s.d[C & 1];
     // the quantise step on this lane's own column-M0 value (final only in the owner lane)
-    const float wv = s.w[M0];
-    float x = wv / s.sc[M0];
-    x = x + s.zz[M0];
-    x = fminf(fmaxf(x, qmin), qmax);
-    const float q = rintf(x);
-    const float dq = (q - s.zz[M0]) * s.sc[M0];
-    const float diff = wv - dq;
-    const float e = diff / d;
+    const Quantised z = quantise_weight(s.w[M0], s.sc[M0], s.zz[M0], s.d[C & 1], qmin, qmax);
     const bool own = p == P0;
-    s.dv = own ? diff : s.dv;
-    s.qv = own ? q : s.qv;
-    s.ev = own ? e : s.ev;
-    const float eb = quad_bcast<P0>(e);
+    s.dv = own ? z.diff : s.dv;
+    s.qv = own ? z.q : s.qv;
+    s.ev = own ? z.e : s.ev;
+    const float eb = row_bcast<L::NL, P0>(z.e, hi);
     // column M0 of the lanes behind the owner; the owner's becomes the dequantised value; lanes before it keep theirs
     {
         const float pr = eb * u[M0];
         const float t = s.w[M0] - pr;
-        s.w[M0] = p > P0 ? t : (own ? dq : s.w[M0]);
+        s.w[M0] = p > P0 ? t : (own ? z.dq : s.w[M0]);
     }
     // every later column of this lane (two per instruction where a pair is available)
     constexpr int MS = M0 + 1;
-    if (MS < QM && (MS & 1)) {
+    if (MS < NM && (MS & 1)) {
         const float pr = eb * u[MS];
         s.w[MS] = s.w[MS] - pr;
     }
     const f32x2 e2 = {eb, eb};
 #pragma unroll
-    for (int m = (MS + 1) & ~1; m < QM; m += 2) {
+    for (int m = (MS + 1) & ~1; m < NM; m += 2) {
         const f32x2 uu = {u[m], u[m + 1]};
         const f32x2 pr = e2 * uu;
         f32x2 wp = {s.w[m], s.w[m + 1]};
@@ -324,6 +397,29 @@ __device__ __forceinline__ void quad_step(QuadState& s, const float* __restrict_
     __builtin_amdgcn_sched_barrier(0);   // keep a step's LDS reads next to their use (register pressure)
 }
 
+template <int NL, int M0, int P0>
+__device__ __forceinline__ void lane_steps(StepState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
+                                           int p, bool hi, float qmin, float qmax) {
+    if constexpr (P0 < NL) {
+        col_step<TriLayout<NL>, M0, P0>(s, Ut, dd, p, hi, qmin, qmax);
+        lane_steps<NL, M0, P0 + 1>(s, Ut, dd, p, hi, qmin, qmax);
+    }
+}
+
+// the row's loss: the NL columns' terms of a macro-step added in column order, in every lane of the row alike (the
+// row-per-lane kernel's and the oracle's order: ascending column)
+template <int NL, int P0>
+__device__ __forceinline__ void lane_loss(StepState<NL>& s, float t, bool hi) {
+    if constexpr (P0 < NL) {
+        s.lsum = s.lsum + row_bcast<NL, P0>(t, hi);
+        lane_loss<NL, P0 + 1>(s, t, hi);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// sweep_quad_kernel's own part: scales streamed ahead of the steps, ragged blocks, rows past R.
+constexpr int QPF = 3;   // macro-steps (of 4 columns) a lane's scale / zero-point loads run ahead of their use
+
 struct QuadScales {
     const float* scale_t;   // + rowc
     const float* zp_t;      // + rowc
@@ -332,7 +428,7 @@ struct QuadScales {
 };
 
 template <int M>
-__device__ __forceinline__ void quad_load_scales(QuadState& s, const QuadScales& q) {
+__device__ __forceinline__ void quad_load_scales(StepState<QL>& s, const QuadScales& q) {
 #if defined(QT_SWEEP_LAB) && QT_SWEEP_LAB == 3     // lab build 3 (timing only): no scale / zero-point loads inside the loop
     if constexpr (M >= QPF && M < QM) {
         s.sc[M] = s.sc[M - QPF];
@@ -348,25 +444,17 @@ __device__ __forceinline__ void quad_load_scales(QuadState& s, const QuadScales&
 }
 
 template <int M0>
-__device__ __forceinline__ void quad_macro_step(QuadState& s, const QuadScales& qs, const float* __restrict__ Up,
+__device__ __forceinline__ void quad_macro_step(StepState<QL>& s, const QuadScales& qs, const float* __restrict__ Up,
                                                 const float* __restrict__ dd,
                                                 int p, float qmin, float qmax, bool valid, int row, int R, int i1,
                                                 int8_t* __restrict__ Qt, float* __restrict__ ErrT) {
     quad_load_scales<M0 + QPF>(s, qs);
-    quad_step<M0, 0>(s, Up, dd, p, qmin, qmax);
-    quad_step<M0, 1>(s, Up, dd, p, qmin, qmax);
-    quad_step<M0, 2>(s, Up, dd, p, qmin, qmax);
-    quad_step<M0, 3>(s, Up, dd, p, qmin, qmax);
+    col_step<QuadLayout, M0, 0>(s, Up, dd, p, false, qmin, qmax);
+    col_step<QuadLayout, M0, 1>(s, Up, dd, p, false, qmin, qmax);
+    col_step<QuadLayout, M0, 2>(s, Up, dd, p, false, qmin, qmax);
+    col_step<QuadLayout, M0, 3>(s, Up, dd, p, false, qmin, qmax);
     // every lane now holds the level, the error and the rounding residual of its own column 4 M0 + p
-    // the row's loss: the four columns' terms added in column order, in every lane of the quad alike (the
-    // row-per-lane kernel's and the oracle's order: ascending column)
-    {
-        const float t = (s.dv * s.dv) * dd[BS + 4 * M0 + p];
-        s.lsum = s.lsum + quad_bcast<0>(t);
-        s.lsum = s.lsum + quad_bcast<1>(t);
-        s.lsum = s.lsum + quad_bcast<2>(t);
-        s.lsum = s.lsum + quad_bcast<3>(t);
-    }
+    lane_loss<QL, 0>(s, (s.dv * s.dv) * dd[BS + 4 * M0 + p], false);
 #if defined(QT_SWEEP_LAB) && QT_SWEEP_LAB == 2     // lab build 2 (timing only): no stores inside the loop
     if (valid && M0 == QM - 1) {
 #else
@@ -379,7 +467,7 @@ __device__ __forceinline__ void quad_macro_step(QuadState& s, const QuadScales& 
 }
 
 template <int M0>
-__device__ __forceinline__ void quad_run(QuadState& s, const QuadScales& qs, const float* __restrict__ Up,
+__device__ __forceinline__ void quad_run(StepState<QL>& s, const QuadScales& qs, const float* __restrict__ Up,
                                          const float* __restrict__ dd, int p,
                                          float qmin, float qmax, bool valid, int row, int R, int i1, int nm,
                                          int8_t* __restrict__ Qt, float* __restrict__ ErrT) {
@@ -439,7 +527,7 @@ __global__ __launch_bounds__(QTHREADS) void sweep_quad_kernel(float* __restrict_
         dd[tid] = d;
         dd[BS + tid] = 1.0f / (d * d);   // only the loss uses it (tolerance 1e-6, not part of the bit-exact contract)
     }
-    QuadState s;
+    StepState<QL> s;
     {
         const float* wrow = W + (size_t)rowc * K + i1 + p;
 #pragma unroll
@@ -461,7 +549,7 @@ __global__ __launch_bounds__(QTHREADS) void sweep_quad_kernel(float* __restrict_
     // consume the early loss read here, where the row's own loads are waited for anyway: its use at the end would
     // otherwise carry an s_waitcnt vmcnt(0) that also waits for every store of the write-back to be acknowledged
     asm volatile("" ::"v"(loss_in));
-    quad_fetch<0>(s, Up, dd, p);
+    step_fetch<QuadLayout, 0>(s, Up, dd, p);
 
 #if !defined(QT_SWEEP_LAB) || QT_SWEEP_LAB != 1   // lab build 1 (tools/sweep_lab.sh, timing only): prologue + epilogue alone
     quad_run<0>(s, qs, Up, dd, p, qmin, qmax, valid, row, R, i1, nm, Qt, ErrT);
@@ -494,132 +582,10 @@ __global__ __launch_bounds__(QTHREADS) void sweep_quad_kernel(float* __restrict_
 //     chain from zero over the block's 128 k on v_mfma_f32_32x32x2f32, k paired (2 kk, 2 kk + 1) as in
 //     sgemm_tn's kernels, then one subtraction -- the bits of the separate MODE_SUB launch.  The error rows come
 //     from LDS (the steps leave them there), the U panel straight from global memory.
-// LDS: the U block's strict upper triangle per (step, float4 group, lane class): step c keeps only the groups
-// its lanes still update, 48 KiB (NL = 16) / 40 KiB (NL = 8) instead of 64; the block's errors [128][rows];
+// LDS: the U block's strict upper triangle (TriLayout); the block's errors [128][rows];
 // the diagonal.  66 560 B (NL = 16, 32 rows) / 74 752 B (NL = 8, 64 rows).
-template <int NL>
-struct LaneGeo {
-    static constexpr int NM = BS / NL;            // columns per lane
-    static constexpr int NK4 = NM / 4;            // float4 groups of a lane's columns
-    static constexpr int ROWS = 512 / NL;         // rows per workgroup
-    static constexpr int BLK = NL * 4;            // floats of one float4 group over the lane classes
-    static constexpr int BAND = 4 * NL;           // steps over which the first live group stays the same
-    // first float of step c: steps of band q = c / BAND keep groups q .. NK4 - 1
-    __host__ __device__ static constexpr int ut_base(int c) {
-        const int band = c / BAND, in = c % BAND;
-        return BLK * (BAND * (band * NK4 - band * (band - 1) / 2) + in * (NK4 - band));
-    }
-    static constexpr int UT_FLOATS = ut_base(BS);
-    static constexpr int ES_FLOATS = BS * ROWS;
-    static constexpr size_t LDS = (size_t)(UT_FLOATS + ES_FLOATS + 2 * BS) * sizeof(float);
-};
-static_assert(LaneGeo<16>::UT_FLOATS == 12288 && LaneGeo<8>::UT_FLOATS == 10240, "triangle layout");
-static_assert(LaneGeo<16>::LDS >= (size_t)RING_LDS_BYTES && LaneGeo<8>::LDS >= (size_t)RING_LDS_BYTES &&
-                  LaneGeo<16>::LDS <= 80 * 1024 && LaneGeo<8>::LDS <= 80 * 1024,
-              "the launch's LDS holds the ring, and two workgroups fit a CU");
-
-// every lane of a row's NL lanes gets lane P0's value: DPP row_share within 16 lanes; for 8 lanes the two halves
-// of a DPP row take their own source lane
-template <int NL, int P0>
-__device__ __forceinline__ float lane_bcast(float v, bool hi) {
-    const int x = __builtin_bit_cast(int, v);
-    if constexpr (NL == 16) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true));
-    } else {
-        static_assert(NL == 8, "8 or 16 lanes per row");
-        const int lo = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0, 0xF, 0xF, true);
-        const int up = __builtin_amdgcn_update_dpp(0, x, 0x150 + P0 + 8, 0xF, 0xF, true);
-        return __builtin_bit_cast(float, hi ? up : lo);
-    }
-}
-
-template <int NL>
-struct LaneState {
-    float w[LaneGeo<NL>::NM], sc[LaneGeo<NL>::NM], zz[LaneGeo<NL>::NM];
-    float u[2][LaneGeo<NL>::NM], d[2];      // U values / diagonal of step C in parity C & 1: read one step ahead
-    float lsum, qv, ev, dv;
-};
-
-template <int NL, int C>
-__device__ __forceinline__ void lane_fetch(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd, int p) {
-    using G = LaneGeo<NL>;
-    if constexpr (C < BS) {
-        constexpr int band = C / G::BAND;
-        const f32x4* urow = (const f32x4*)(Ut + G::ut_base(C) + p * 4);
-#pragma unroll
-        for (int k4 = band; k4 < G::NK4; ++k4) {
-            const f32x4 t = urow[(k4 - band) * NL];
-            s.u[C & 1][4 * k4 + 0] = t[0]; s.u[C & 1][4 * k4 + 1] = t[1]; s.u[C & 1][4 * k4 + 2] = t[2]; s.u[C & 1][4 * k4 + 3] = t[3];
-        }
-        s.d[C & 1] = dd[C];
-    }
-}
-
-// quad_step with NL lanes per row
-template <int NL, int M0, int P0>
-__device__ __forceinline__ void lane_step(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
-                                          int p, bool hi, float qmin, float qmax) {
-    constexpr int NM = LaneGeo<NL>::NM;
-    constexpr int C = NL * M0 + P0;
-    lane_fetch<NL, C + 1>(s, Ut, dd, p);
-    const float* u = s.u[C & 1];
-    const float d = s.d[C & 1];
-    const float wv = s.w[M0];
-    float x = wv / s.sc[M0];
-    x = x + s.zz[M0];
-    x = fminf(fmaxf(x, qmin), qmax);
-    const float q = rintf(x);
-    const float dq = (q - s.zz[M0]) * s.sc[M0];
-    const float diff = wv - dq;
-    const float e = diff / d;
-    const bool own = p == P0;
-    s.dv = own ? diff : s.dv;
-    s.qv = own ? q : s.qv;
-    s.ev = own ? e : s.ev;
-    const float eb = lane_bcast<NL, P0>(e, hi);
-    {
-        const float pr = eb * u[M0];
-        const float t = s.w[M0] - pr;
-        s.w[M0] = p > P0 ? t : (own ? dq : s.w[M0]);
-    }
-    constexpr int MS = M0 + 1;
-    if (MS < NM && (MS & 1)) {
-        const float pr = eb * u[MS];
-        s.w[MS] = s.w[MS] - pr;
-    }
-    const f32x2 e2 = {eb, eb};
-#pragma unroll
-    for (int m = (MS + 1) & ~1; m < NM; m += 2) {
-        const f32x2 uu = {u[m], u[m + 1]};
-        const f32x2 pr = e2 * uu;
-        f32x2 wp = {s.w[m], s.w[m + 1]};
-        wp = wp - pr;
-        s.w[m] = wp[0];
-        s.w[m + 1] = wp[1];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int NL, int M0, int P0>
-__device__ __forceinline__ void lane_steps(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
-                                           int p, bool hi, float qmin, float qmax) {
-    if constexpr (P0 < NL) {
-        lane_step<NL, M0, P0>(s, Ut, dd, p, hi, qmin, qmax);
-        lane_steps<NL, M0, P0 + 1>(s, Ut, dd, p, hi, qmin, qmax);
-    }
-}
-
-// the row's loss: the NL columns' terms of a macro-step added in column order, in every lane of the row alike
-template <int NL, int P0>
-__device__ __forceinline__ void lane_loss(LaneState<NL>& s, float t, bool hi) {
-    if constexpr (P0 < NL) {
-        s.lsum = s.lsum + lane_bcast<NL, P0>(t, hi);
-        lane_loss<NL, P0 + 1>(s, t, hi);
-    }
-}
-
 template <int NL, int M0>
-__device__ __forceinline__ void lane_run(LaneState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
+__device__ __forceinline__ void lane_run(StepState<NL>& s, const float* __restrict__ Ut, const float* __restrict__ dd,
                                          float* __restrict__ Es, int p, bool hi, int rl, float qmin, float qmax, int row,
                                          int R, int i1, int8_t* __restrict__ Qt, float* __restrict__ ErrB) {
     if constexpr (M0 < LaneGeo<NL>::NM) {
@@ -719,7 +685,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             dd[tid] = d;
             dd[BS + tid] = 1.0f / (d * d);
         }
-        LaneState<NL> s;
+        StepState<NL> s;
         {
             const float* wrow = W + (size_t)row * K + i1 + p;
             const int32_t* gcol = g_idx + i1 + p;
@@ -736,7 +702,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         s.ev = 0.0f;
         s.dv = 0.0f;
         __syncthreads();
-        lane_fetch<NL, 0>(s, Ut, dd, p);
+        step_fetch<TriLayout<NL>, 0>(s, Ut, dd, p);
         lane_run<NL, 0>(s, Ut, dd, Es, p, hi, rl, f.qmin, f.qmax, row, R, i1, f.Qt, f.ErrT + (size_t)blk * BS * R);
         {   // dequantised values back to W (upstream: W[:, i1:i2] = Q1)
             float* wrow = W + (size_t)row * K + i1 + p;
@@ -850,6 +816,213 @@ extern "C" size_t qt_gptq_sweep_workspace_bytes(int R, int K, int blocksize) {
     return n;
 }
 
+// What every schedule of a sweep reads.
+struct SweepCtx {
+    float* W;
+    int R, K;
+    const float* U;
+    const float* scale_t;
+    const float* zp_t;
+    const int32_t* g_idx;
+    float qmin, qmax;
+    int8_t* Qt;
+    float* loss;
+    float* ErrT;            // the workspace, 256-byte aligned: ErrT[batch][128][R]
+    int batch_blocks;       // blocks per batch (sweep_batch_blocks)
+    int prio;
+    hipStream_t stream;
+    const SweepGroups& sg;
+};
+
+// The update product  W[:, c0:c1] -= Err^T U[k0:k0+kdim, c0:c1]  (Err: [kdim][R]) as qt_sgemm_tn and the ring take it:
+// per element one ascending-k chain, or with chain_len > 0 one chain per chain_len rows of Err, subtracted in turn.
+static SgemmArgs sweep_update_args(const SweepCtx& c, const float* Err, int k0, int kdim, int c0, int c1, int chain_len) {
+    SgemmArgs g;
+    g.A = Err; g.lda = c.R;
+    g.B = c.U + (size_t)k0 * c.K + c0; g.ldb = c.K;
+    g.Cin = c.W + c0; g.ldcin = c.K;
+    g.Cout = c.W + c0; g.ldcout = c.K;
+    g.M = c.R; g.N = c1 - c0; g.kdim = kdim; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
+    g.chain_len = chain_len;
+    // stacked problems: an update product's B operand (rows of U) depends on the row group of the output tile
+    if (c.sg.n > 1) {
+        g.n_groups = c.sg.n;
+        g.group_bsB = c.sg.bsU;
+        for (int i = 0; i < c.sg.n; ++i) g.group_m_end[i] = c.sg.row_end[i];
+    }
+    return g;
+}
+
+// A kernel's dynamic LDS beyond the default limit, asked for once per device.
+template <auto Kernel>
+static hipError_t sweep_lds_attr(size_t lds_bytes) {
+    static QtOncePerDevice once;
+    return once.run([&] {
+        return hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    });
+}
+
+// The opt-in three-plane far update (sweep_far_bf16x3): its plan and its room in the workspace behind ErrT
+// (never beside the fused form's second error buffer).
+struct Far3 {
+    FarPlan fp;
+    unsigned short *Upl, *Epl;
+    G3Item* tab;
+};
+
+static int sweep_far3_prepare(const SweepCtx& c, Far3& f) {
+    const int K = c.K;
+    const FarPlan& fp = f.fp = far_plan(c.R, K, BS);
+    char* q = (char*)c.ErrT + sweep_err_bytes(c.R, BS);
+    f.Upl = (unsigned short*)q;
+    q += fp.u_bytes;
+    f.Epl = (unsigned short*)q;
+    q += fp.e_bytes;
+    f.tab = (G3Item*)q;
+    // planes of U once (pad columns zeroed: edge tiles read them), the tile list once: column-major in tiles, so a
+    // far update over the first Tn' tile columns right of the batch is a prefix of it
+    QT_HIP(hipMemsetAsync(f.Upl, 0, fp.u_bytes, c.stream));
+    QT_HIP(hipMemsetAsync(f.Epl, 0, fp.e_bytes, c.stream));
+    int rc = qt_split3_launch(c.U, K, K, K, f.Upl, fp.ldU, (int64_t)K * fp.ldU, 0, 0, 0, c.stream);
+    if (rc) return rc;
+    static std::mutex m;
+    static std::map<std::tuple<int, int, int>, G3Item*> tabs;      // pinned, per (Tm, Tn_max, chunks)
+    const int c_end = BS * c.batch_blocks / G3_CHUNK_ROWS;
+    G3Item* host = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(m);
+        const auto key = std::make_tuple(fp.Tm, fp.Tn_max, c_end);
+        auto it = tabs.find(key);
+        if (it == tabs.end()) {
+            if (hipHostMalloc((void**)&host, fp.tab_bytes, hipHostMallocDefault) != hipSuccess) {
+                qt_set_error("qt_gptq_sweep: no pinned memory for the far update's tile table");
+                return QT_ERR_HIP;
+            }
+            int n = 0;
+            for (int tj = 0; tj < fp.Tn_max; ++tj)
+                for (int ti = 0; ti < fp.Tm; ++ti) host[n++] = {(ti << 16) | tj, 0, c_end, -1};
+            tabs[key] = host;
+        } else {
+            host = it->second;
+        }
+    }
+    QT_HIP(hipMemcpyAsync(f.tab, host, (size_t)fp.Tm * fp.Tn_max * sizeof(G3Item), hipMemcpyHostToDevice, c.stream));
+    return QT_OK;
+}
+
+// The far update of batch [b0, bend) as a three-plane product: error rows of the batch -> planes, then
+// W[:, bend:] -= E^T U[b0:bend, bend:]
+static int sweep_far3_update(const SweepCtx& c, const Far3& f, int b0, int bend) {
+    const FarPlan& fp = f.fp;
+    int rc = qt_split3_launch(c.ErrT, c.R, bend - b0, c.R, f.Epl, fp.ldE, (int64_t)fp.kmax * fp.ldE, 0, 0, 0, c.stream);
+    if (rc) return rc;
+    G3Args a;
+    a.Apl = f.Epl; a.ld = fp.ldE; a.plane_stride = (int64_t)fp.kmax * fp.ldE; a.rowA0 = 0; a.colA0 = 0; a.colmax = (int)fp.ldE;
+    a.Bpl = f.Upl; a.ldB = fp.ldU; a.plane_strideB = (int64_t)c.K * fp.ldU; a.rowB0 = b0; a.colB0 = bend; a.colmaxB = (int)fp.ldU;
+    a.M = c.R; a.N = c.K - bend; a.C = c.W + bend; a.ldc = c.K; a.mode = G3_SUB;
+    a.slabs = nullptr; a.red = nullptr; a.n_red = 0;
+    a.items = f.tab; a.n_items = fp.Tm * ((c.K - bend + 255) / 256);
+    return qt_gemm3_launch(a, c.stream);
+}
+
+// The fused form (sweep_fused_kernel): per batch b the stream carries far_near(b - 1) -- the far update of batch
+// b - 1 on batch b's own columns -- and then ONE launch of [batch b's block steps and near updates] beside
+// [far_rest(b - 1): the same far update on every column right of batch b].  far_near and far_rest are a column
+// split of the one far update: the same chains in the same order per element.  Per element the subtractions
+// still arrive in ascending block order (far_rest(b - 1) precedes far_near(b) and far_rest(b) on the stream).
+// ErrT is double-buffered: batch b writes buffer b & 1 while far_rest(b - 1) reads the other.
+static int sweep_run_fused(const SweepCtx& c) {
+    const int R = c.R, K = c.K;
+    // Lanes per row: 16 (32 rows per workgroup: R / 32 workgroups, the shortest step); QT_SWEEP_LANES=8 selects 8
+    // (64 rows per workgroup), slower at both measured heights (at the choice of form in sweep_run) and kept for A/B runs.
+    const char* lanes_env = getenv("QT_SWEEP_LANES");
+    const int lanes = lanes_env && atoi(lanes_env) == 8 ? 8 : 16;
+    QT_HIP(sweep_lds_attr<sweep_fused_kernel<16>>(LaneGeo<16>::LDS));
+    QT_HIP(sweep_lds_attr<sweep_fused_kernel<8>>(LaneGeo<8>::LDS));
+    float* Err[2] = {c.ErrT, (float*)((char*)c.ErrT + sweep_fused_err_bytes(R, K, BS))};
+    const int span = BS * c.batch_blocks;
+    const int n_row_wgs = R / (512 / lanes);
+    int b = 0;
+    for (int b0 = 0; b0 < K; b0 += span, ++b) {
+        const int bend = (b0 + span < K) ? b0 + span : K;
+        RingArgs far{};
+        int far_wgs = 0;
+        if (b > 0) {
+            const float* err_prev = Err[(b - 1) & 1];
+            // far_near(b - 1)
+            const int rc = qt_sgemm_tn(sweep_update_args(c, err_prev, b0 - span, span, b0, bend, BS), c.stream);
+            if (rc) return rc;
+            if (bend < K) {                              // far_rest(b - 1)
+                far = sgemm_ring_args(sweep_update_args(c, err_prev, b0 - span, span, bend, K, BS));
+                // two workgroups per CU, 256 CUs: what the row workgroups leave, at least one per CU
+                const int room = 512 - n_row_wgs > 256 ? 512 - n_row_wgs : 256;
+                far_wgs = far.n_tiles < room ? far.n_tiles : room;
+            }
+        }
+        FusedArgs f;
+        f.W = c.W; f.R = R; f.K = K; f.U = c.U; f.scale_t = c.scale_t; f.zp_t = c.zp_t; f.g_idx = c.g_idx;
+        f.b0 = b0; f.nblk = (bend - b0) / BS;
+        f.qmin = c.qmin; f.qmax = c.qmax; f.Qt = c.Qt; f.ErrT = Err[b & 1]; f.loss = c.loss; f.prio = c.prio;
+        f.n_row_wgs = n_row_wgs;
+        qt_prof_mark(QT_PROF_SWEEP_BLOCK, c.stream);
+        if (lanes == 16)
+            hipLaunchKernelGGL(sweep_fused_kernel<16>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<16>::LDS, c.stream, f,
+                               c.sg, far);
+        else
+            hipLaunchKernelGGL(sweep_fused_kernel<8>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<8>::LDS, c.stream, f,
+                               c.sg, far);
+        qt_prof_mark(QT_PROF_SWEEP_BLOCK, c.stream);
+        QT_LAUNCH_CHECK();
+    }
+    return QT_OK;
+}
+
+// The chain of launches: per block one block kernel (quad: four lanes per row, else a lane per row) and the near
+// update of the batch's remaining columns, per batch one far update (far3: as the opt-in three-plane product).
+// Lazy far update: the blocks of a batch update only the batch's own later columns right away
+// (k = 128, few columns); everything to the right of the batch gets the batch's chains in ONE
+// pass over W (chain_len = 128: same roundings, in the same order, as one pass per block), so
+// the read-modify-write traffic on W drops by the batch size.
+static int sweep_run_chain(const SweepCtx& c, bool quad, bool far3) {
+    const int R = c.R, K = c.K, span = BS * c.batch_blocks;
+    QT_HIP(sweep_lds_attr<sweep_block_kernel>(SWEEP_LDS));
+    QT_HIP(sweep_lds_attr<sweep_quad_kernel>(QUAD_LDS));
+    Far3 f3{};
+    if (far3) {
+        const int rc = sweep_far3_prepare(c, f3);
+        if (rc) return rc;
+    }
+    for (int b0 = 0; b0 < K; b0 += span) {
+        const int bend = (b0 + span < K) ? b0 + span : K;   // first column right of the batch
+        for (int i1 = b0; i1 < bend; i1 += BS) {
+            const int i2 = (i1 + BS < K) ? i1 + BS : K;
+            const int cnt = i2 - i1;
+            float* err_blk = c.ErrT + (size_t)(i1 - b0) * R;
+            qt_prof_mark(QT_PROF_SWEEP_BLOCK, c.stream);
+            if (quad)
+                hipLaunchKernelGGL(sweep_quad_kernel, dim3((R + QROWS - 1) / QROWS), dim3(QTHREADS), QUAD_LDS, c.stream, c.W,
+                                   R, K, c.U, c.scale_t, c.zp_t, c.g_idx, i1, cnt, c.qmin, c.qmax, c.Qt, err_blk, c.loss,
+                                   c.prio, c.sg);
+            else
+                hipLaunchKernelGGL(sweep_block_kernel, dim3((R + ROWS - 1) / ROWS), dim3(ROWS), SWEEP_LDS, c.stream, c.W, R,
+                                   K, c.U, c.scale_t, c.zp_t, c.g_idx, i1, cnt, c.qmin, c.qmax, c.Qt, err_blk, c.loss,
+                                   c.prio, c.sg);
+            qt_prof_mark(QT_PROF_SWEEP_BLOCK, c.stream);
+            QT_LAUNCH_CHECK();
+            if (i2 < bend) {   // near update: the rest of this batch
+                const int rc = qt_sgemm_tn(sweep_update_args(c, err_blk, i1, cnt, i2, bend, 0), c.stream);
+                if (rc) return rc;
+            }
+        }
+        if (bend == K) break;
+        // far update: every chain of the batch, one pass
+        const int rc = far3 && bend - b0 == span ? sweep_far3_update(c, f3, b0, bend)
+                                                 : qt_sgemm_tn(sweep_update_args(c, c.ErrT, b0, bend - b0, bend, K, BS), c.stream);
+        if (rc) return rc;
+    }
+    return QT_OK;
+}
+
 static int sweep_run(float* W, int R, int K, const float* U, const float* scale_t, const float* zp_t, int G,
                      const int32_t* g_idx, int blocksize, int num_bits, int8_t* Qt, float* loss, void* workspace,
                      size_t workspace_bytes, hipStream_t stream, const SweepGroups& sg) {
@@ -865,86 +1038,17 @@ static int sweep_run(float* W, int R, int K, const float* U, const float* scale_
     }
     float* ErrT = (float*)qt_align_up((size_t)workspace, 256);
     const bool far3 = sweep_far_bf16x3(R, K) && sg.n <= 1;      // the opt-in three-plane far update: single problem only
-    FarPlan fp{};
-    unsigned short *Upl = nullptr, *Epl = nullptr;
-    G3Item* far_tab = nullptr;
-    if (far3) {
-        fp = far_plan(R, K, blocksize);
-        char* q = (char*)ErrT + sweep_err_bytes(R, blocksize);      // (never beside the fused form's second error buffer)
-        Upl = (unsigned short*)q;
-        q += fp.u_bytes;
-        Epl = (unsigned short*)q;
-        q += fp.e_bytes;
-        far_tab = (G3Item*)q;
-    }
     const float qmin = -(float)(1 << (num_bits - 1)), qmax = (float)((1 << (num_bits - 1)) - 1);
-    static QtOncePerDevice lds_attr;
-    QT_HIP(lds_attr.run([&] {
-        return hipFuncSetAttribute((const void*)sweep_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)SWEEP_LDS);
-    }));
-    static QtOncePerDevice lds_attr_q;
-    QT_HIP(lds_attr_q.run([&] {
-        return hipFuncSetAttribute((const void*)sweep_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)QUAD_LDS);
-    }));
     // QT_SWEEP_BLOCK=row: the row-per-lane block kernel (the round-1/2 form; A/B and cross-check); default: four lanes per row
     const char* blk_env = getenv("QT_SWEEP_BLOCK");
     const bool quad = !(blk_env && blk_env[0] == 'r');
     QT_HIP(hipMemsetAsync(loss, 0, (size_t)R * 4, stream));
-    // Lazy far update: the blocks of a batch update only the batch's own later columns right away
-    // (k = 128, few columns); everything to the right of the batch gets the batch's chains in ONE
-    // pass over W (chain_len = 128: same roundings, in the same order, as one pass per block), so
-    // the read-modify-write traffic on W drops by the batch size.
     // Batch size: 4 blocks, 8 from K = 8192 up -- a longer batch halves the far update's traffic on W again but puts
     // more near-update columns between two block kernels (K = 14336 / R = 4096: 11.74 -> 11.35 ms; K = 4096 /
     // R = 28672: 5.9 -> 6.0 ms; K = 8192: +-0.5 %, profiles/r03_sweep_batch_ab.txt).  The bits do not depend on it.  QT_SWEEP_BATCH forces it.
-    const int batch_blocks = sweep_batch_blocks(K);
-    const int prio = qt_chain_prio();
-    // stacked problems: an update product's B operand (rows of U) depends on the row group of the output tile
-    auto set_groups = [&](SgemmArgs& g) {
-        if (sg.n <= 1) return;
-        g.n_groups = sg.n;
-        g.group_bsB = sg.bsU;
-        for (int i = 0; i < sg.n; ++i) g.group_m_end[i] = sg.row_end[i];
-    };
-    if (far3) {
-        // planes of U once (pad columns zeroed: edge tiles read them), the tile list once: column-major in tiles, so a
-        // far update over the first Tn' tile columns right of the batch is a prefix of it
-        QT_HIP(hipMemsetAsync(Upl, 0, fp.u_bytes, stream));
-        QT_HIP(hipMemsetAsync(Epl, 0, fp.e_bytes, stream));
-        int rc = qt_split3_launch(U, K, K, K, Upl, fp.ldU, (int64_t)K * fp.ldU, 0, 0, 0, stream);
-        if (rc) return rc;
-        static std::mutex m;
-        static std::map<std::tuple<int, int, int>, G3Item*> tabs;      // pinned, per (Tm, Tn_max, chunks)
-        const int c_end = BS * batch_blocks / G3_CHUNK_ROWS;
-        G3Item* host = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(m);
-            const auto key = std::make_tuple(fp.Tm, fp.Tn_max, c_end);
-            auto it = tabs.find(key);
-            if (it == tabs.end()) {
-                if (hipHostMalloc((void**)&host, fp.tab_bytes, hipHostMallocDefault) != hipSuccess) {
-                    qt_set_error("qt_gptq_sweep: no pinned memory for the far update's tile table");
-                    return QT_ERR_HIP;
-                }
-                int n = 0;
-                for (int tj = 0; tj < fp.Tn_max; ++tj)
-                    for (int ti = 0; ti < fp.Tm; ++ti) host[n++] = {(ti << 16) | tj, 0, c_end, -1};
-                tabs[key] = host;
-            } else {
-                host = it->second;
-            }
-        }
-        QT_HIP(hipMemcpyAsync(far_tab, host, (size_t)fp.Tm * fp.Tn_max * sizeof(G3Item), hipMemcpyHostToDevice, stream));
-    }
-    // The fused form (sweep_fused_kernel): per batch b the stream carries far_near(b - 1) -- the far update of batch
-    // b - 1 on batch b's own columns -- and then ONE launch of [batch b's block steps and near updates] beside
-    // [far_rest(b - 1): the same far update on every column right of batch b].  far_near and far_rest are a column
-    // split of the one far update: the same chains in the same order per element.  Per element the subtractions
-    // still arrive in ascending block order (far_rest(b - 1) precedes far_near(b) and far_rest(b) on the stream).
-    // ErrT is double-buffered: batch b writes buffer b & 1 while far_rest(b - 1) reads the other.
-    // QT_SWEEP_FUSED=0 (read per call) forces the chain of launches below; so do shapes off the ring's whole tiles.
+    const SweepCtx c = {W, R, K, U, scale_t, zp_t, g_idx, qmin, qmax, Qt, loss, ErrT, sweep_batch_blocks(K), qt_chain_prio(),
+                        stream, sg};
+    // The choice of form.  QT_SWEEP_FUSED=0 (read per call) forces the chain of launches; so do shapes off the ring's whole tiles.
     // Unset, the fused form is taken up to 6144 rows: the row workgroups run the quantise step in all 16 (8) lanes of a
     // row, 2.6 (1.5) times the vector work of four lanes per row.  That is free while they are a latency-bound chain on
     // a chip the far update fills, and a loss once the rows alone fill the chip (K = 4096 / R = 28672: 5.76 ms as
@@ -952,132 +1056,11 @@ static int sweep_run(float* W, int R, int K, const float* U, const float* scale_
     // K = 4096 / R = 6144: 2.35 -> 1.97; profiles/sweep_fused_ab.txt, sweep_fused_stage_times_*.txt).  6144 is the
     // tallest shape measured faster; with the form taken up to 8192 rows the Llama-3-70B layer (R = 8192 at K = 8192 and
     // 28672) ran 340 ms per step against the parent's 324 in the one run made.  QT_SWEEP_FUSED=1 takes it at any height.
-    bool fused = sweep_fused_shape(R, K) && quad && (((uintptr_t)U | (uintptr_t)ErrT) & 15) == 0 &&
-                 (sg.n <= 1 || sg.bsU % 4 == 0);
-    if (fused) {
-        SgemmArgs probe;     // the far update's shape as the ring sees it (column count and offsets are multiples of 128)
-        probe.A = ErrT; probe.lda = R;
-        probe.B = U; probe.ldb = K;
-        probe.Cin = W; probe.ldcin = K;
-        probe.Cout = W; probe.ldcout = K;
-        probe.M = R; probe.N = BS; probe.kdim = BS * batch_blocks; probe.k_mode = SG_K_FULL; probe.mode = SG_MODE_SUB;
-        probe.chain_len = BS;
-        fused = sgemm_ring_applies(probe);
-    }
-    if (fused) {
-        // Lanes per row: 16 (32 rows per workgroup: R / 32 workgroups, the shortest step); QT_SWEEP_LANES=8 selects 8
-        // (64 rows per workgroup), slower at both measured heights (above) and kept for A/B runs.
-        const char* lanes_env = getenv("QT_SWEEP_LANES");
-        const int lanes = lanes_env && atoi(lanes_env) == 8 ? 8 : 16;
-        static QtOncePerDevice lds_attr_f16, lds_attr_f8;
-        QT_HIP(lds_attr_f16.run([&] {
-            return hipFuncSetAttribute((const void*)sweep_fused_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)LaneGeo<16>::LDS);
-        }));
-        QT_HIP(lds_attr_f8.run([&] {
-            return hipFuncSetAttribute((const void*)sweep_fused_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)LaneGeo<8>::LDS);
-        }));
-        float* Err[2] = {ErrT, (float*)((char*)ErrT + sweep_fused_err_bytes(R, K, blocksize))};
-        const int span = BS * batch_blocks;
-        const int n_row_wgs = R / (512 / lanes);
-        int b = 0;
-        for (int b0 = 0; b0 < K; b0 += span, ++b) {
-            const int bend = (b0 + span < K) ? b0 + span : K;
-            RingArgs far{};
-            int far_wgs = 0;
-            if (b > 0) {
-                SgemmArgs g;
-                g.A = Err[(b - 1) & 1]; g.lda = R;
-                g.B = U + (size_t)(b0 - span) * K + b0; g.ldb = K;
-                g.Cin = W + b0; g.ldcin = K;
-                g.Cout = W + b0; g.ldcout = K;
-                g.M = R; g.N = bend - b0; g.kdim = span; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-                g.chain_len = BS;
-                set_groups(g);
-                const int rc = qt_sgemm_tn(g, stream);       // far_near(b - 1)
-                if (rc) return rc;
-                if (bend < K) {                              // far_rest(b - 1)
-                    g.B = U + (size_t)(b0 - span) * K + bend;
-                    g.Cin = W + bend;
-                    g.Cout = W + bend;
-                    g.N = K - bend;
-                    far = sgemm_ring_args(g);
-                    // two workgroups per CU, 256 CUs: what the row workgroups leave, at least one per CU
-                    const int room = 512 - n_row_wgs > 256 ? 512 - n_row_wgs : 256;
-                    far_wgs = far.n_tiles < room ? far.n_tiles : room;
-                }
-            }
-            FusedArgs f;
-            f.W = W; f.R = R; f.K = K; f.U = U; f.scale_t = scale_t; f.zp_t = zp_t; f.g_idx = g_idx;
-            f.b0 = b0; f.nblk = (bend - b0) / BS;
-            f.qmin = qmin; f.qmax = qmax; f.Qt = Qt; f.ErrT = Err[b & 1]; f.loss = loss; f.prio = prio;
-            f.n_row_wgs = n_row_wgs;
-            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
-            if (lanes == 16)
-                hipLaunchKernelGGL(sweep_fused_kernel<16>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<16>::LDS, stream, f,
-                                   sg, far);
-            else
-                hipLaunchKernelGGL(sweep_fused_kernel<8>, dim3(n_row_wgs + far_wgs), dim3(512), LaneGeo<8>::LDS, stream, f,
-                                   sg, far);
-            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
-            QT_LAUNCH_CHECK();
-        }
-        return QT_OK;
-    }
-    for (int b0 = 0; b0 < K; b0 += BS * batch_blocks) {
-        const int bend = (b0 + BS * batch_blocks < K) ? b0 + BS * batch_blocks : K;   // first column right of the batch
-        for (int i1 = b0; i1 < bend; i1 += BS) {
-            const int i2 = (i1 + BS < K) ? i1 + BS : K;
-            const int cnt = i2 - i1;
-            float* err_blk = ErrT + (size_t)(i1 - b0) * R;
-            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
-            if (quad)
-                hipLaunchKernelGGL(sweep_quad_kernel, dim3((R + QROWS - 1) / QROWS), dim3(QTHREADS), QUAD_LDS, stream, W,
-                                   R, K, U, scale_t, zp_t, g_idx, i1, cnt, qmin, qmax, Qt, err_blk, loss, prio, sg);
-            else
-                hipLaunchKernelGGL(sweep_block_kernel, dim3((R + ROWS - 1) / ROWS), dim3(ROWS), SWEEP_LDS, stream, W, R,
-                                   K, U, scale_t, zp_t, g_idx, i1, cnt, qmin, qmax, Qt, err_blk, loss, prio, sg);
-            qt_prof_mark(QT_PROF_SWEEP_BLOCK, stream);
-            QT_LAUNCH_CHECK();
-            if (i2 < bend) {   // near update: the rest of this batch
-                SgemmArgs g;
-                g.A = err_blk; g.lda = R;
-                g.B = U + (size_t)i1 * K + i2; g.ldb = K;
-                g.Cin = W + i2; g.ldcin = K;
-                g.Cout = W + i2; g.ldcout = K;
-                g.M = R; g.N = bend - i2; g.kdim = cnt; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-                set_groups(g);
-                const int rc = qt_sgemm_tn(g, stream);
-                if (rc) return rc;
-            }
-        }
-        if (bend < K && far3 && bend - b0 == BS * batch_blocks) {
-            // far update as a three-plane product: error rows of the batch -> planes, then W[:, bend:] -= E^T U[b0:bend, bend:]
-            int rc = qt_split3_launch(ErrT, R, bend - b0, R, Epl, fp.ldE, (int64_t)fp.kmax * fp.ldE, 0, 0, 0, stream);
-            if (rc) return rc;
-            G3Args a;
-            a.Apl = Epl; a.ld = fp.ldE; a.plane_stride = (int64_t)fp.kmax * fp.ldE; a.rowA0 = 0; a.colA0 = 0; a.colmax = (int)fp.ldE;
-            a.Bpl = Upl; a.ldB = fp.ldU; a.plane_strideB = (int64_t)K * fp.ldU; a.rowB0 = b0; a.colB0 = bend; a.colmaxB = (int)fp.ldU;
-            a.M = R; a.N = K - bend; a.C = W + bend; a.ldc = K; a.mode = G3_SUB;
-            a.slabs = nullptr; a.red = nullptr; a.n_red = 0;
-            a.items = far_tab; a.n_items = fp.Tm * ((K - bend + 255) / 256);
-            rc = qt_gemm3_launch(a, stream);
-            if (rc) return rc;
-        } else if (bend < K) {        // far update: every chain of the batch, one pass
-            SgemmArgs g;
-            g.A = ErrT; g.lda = R;
-            g.B = U + (size_t)b0 * K + bend; g.ldb = K;
-            g.Cin = W + bend; g.ldcin = K;
-            g.Cout = W + bend; g.ldcout = K;
-            g.M = R; g.N = K - bend; g.kdim = bend - b0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-            g.chain_len = BS;
-            set_groups(g);
-            const int rc = qt_sgemm_tn(g, stream);
-            if (rc) return rc;
-        }
-    }
-    return QT_OK;
+    const bool fused = sweep_fused_shape(R, K) && quad && (((uintptr_t)U | (uintptr_t)ErrT) & 15) == 0 &&
+                       (sg.n <= 1 || sg.bsU % 4 == 0) &&
+                       // the far update's shape as the ring sees it (column count and offsets are multiples of 128)
+                       sgemm_ring_applies(sweep_update_args(c, ErrT, 0, BS * c.batch_blocks, 0, BS, BS));
+    return fused ? sweep_run_fused(c) : sweep_run_chain(c, quad, far3);
 }
 
 extern "C" int qt_gptq_sweep(float* W, int R, int K, const float* U, const float* scale_t, const float* zp_t, int G,

@@ -1,5 +1,5 @@
 """The fused sweep (``sweep_fused_kernel``, csrc/sweep.hip) against ``oracle/gptq_oracle.c``: its own quantise step
-(``lane_step``, 8 or 16 lanes per row), its own near update and the far update that shares its launch
+(``col_step`` on ``TriLayout``, 8 or 16 lanes per row), its own near update and the far update that shares its launch
 (``sgemm_ring_body<true>``), over what the entry points accept on whole 128-tiles -- the shapes the default takes the
 fused form at.  ``test_gpu_sweep_matrix.py`` sits off whole tiles and holds the chain of launches to the same oracle.
 
