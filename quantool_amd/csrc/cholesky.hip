@@ -6,7 +6,8 @@
 // Ut = J R^T J upper, so Hd^-1 = (Ut^-1)^T (Ut^-1) and, by uniqueness of the Cholesky factor,
 //     U = Ut^-1 = J R^-T J = flat-reverse(Y),   Y = R^-T (lower).
 // Cost 2/3 K^3 flops (vs 4/3 K^3) and every block recurrence below is a k-major "TN" product.  Two block
-// sizes: NB = 128 for the latency-bound panel kernels, NBO / NBI = 256 for everything that carries the K^3.
+// sizes: NB = 128 for the latency-bound panel kernels, NBO / NBI for everything that carries the K^3 (chol_blocks: 512
+// where the plane products are live, 256 on the f32 chain).
 //   potrf over NBO-wide outer blocks J, left-looking inside one (all in place in A):
 //     block row j of J :  A[j, j:] -= sum_{p in J, p<j} R[p, j]^T R[p, j:]   (sgemm SUB, k <= NBO - 128)
 //                         R_jj = chol(A_jj), 32x32 inverses                   (potf2_kernel)
@@ -32,6 +33,9 @@
 //     |R[i][j]| <= sqrt(A[j][j]) <= sqrt(max diag A)              (A = R^T R: column j of R has norm sqrt(A[j][j]))
 //     |Y[i][j]| <= ||R^-1||_2 = 1 / sqrt(lambda_min(A))           (Y = R^-T)
 // computed on the device from A's diagonal and the caller's bound before A is overwritten (chol_scales_kernel).
+// Host side, behind the kernels: CholLayout (chol_layout.h) is the one statement of a problem's workspace, CholCtx what
+// every step reads, chol_sgemm_args / g3_row the two product builders, fac_product ... inv_row the steps above, and
+// chol_run_two_phase / chol_run_walk the two orders in which chol_run enqueues them.
 #include <stdlib.h>
 #include <string.h>
 
@@ -39,14 +43,14 @@
 #include <tuple>
 #include <vector>
 
+#include "chol_layout.h"
 #include "common.h"
 #include "gemm3_tn.h"
 #include "sgemm_tn.h"
 
 namespace {
 
-constexpr int NB = 128;
-constexpr int NBO_MAX = 1024; // workspace is sized for the widest outer block
+static_assert(CHOL_CHUNK_ROWS == G3_CHUNK_ROWS, "chol_layout.h counts k chunks as gemm3_tn.h cuts them");
 // Outer block of the factorisation / block-row height of the inverse (multiples of 128).  QT_CHOL_NBO /
 // QT_CHOL_NBI force them (A/B runs); otherwise 256 on the f32 chain (measured at K = 14336 / 4096: 128: 40.5 /
 // 4.30 ms, 256: 35.3 / 4.04, 512: 36.4 / 4.05, 1024: 38.5 / 4.40) and 512 where the bf16x3 products are in
@@ -163,32 +167,29 @@ static void chol_g3_build(int K, int NBO, int NBI, int min_chunks, int target_it
     };
     const bool walk = merged && NBO == NBI;
     const int cap = target_items > 0 && target_items < 256 ? target_items : 256;   // items per launch, as g3_plan_row
-    pl.row.assign(walk ? (K + NBO - 1) / NBO : 0, G3Step());
+    pl.row.assign(walk ? BlockRow::count(K, NBO) : 0, G3Step());
     std::vector<char> is_merged(pl.row.size(), 0);
-    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
-        const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-        const int Tm = (J1 - J0 + 255) / 256, Tn0 = (K - J0 + 255) / 256, Tn1 = (J0 + 255) / 256, c_end = J0 / G3_CHUNK_ROWS;
+    for (BlockRow J(K, NBO); J; ++J) {
+        const int Tm = J.Tm(), Tn0 = J.Tn0(), Tn1 = J.Tn1(), c_end = J.c_end();
         // A row is merged only where the cap leaves every tile of the launch at least two pieces: with more tiles than
         // half the cap the pieces become whole tiles and the launch lasts as long as the full k range (K = 28672: 224
         // tiles per 512-row block against a cap of 256 -- one 70B bench run 340.3 -> 345.1 ms per step merged).
-        if (walk && J0 > 0 && 2 * Tm * (Tn0 + Tn1) <= cap && enough(Tm, Tn0, c_end, 0) && enough(Tm, Tn1, c_end, 1)) {
+        if (walk && J.J0 > 0 && 2 * Tm * (Tn0 + Tn1) <= cap && enough(Tm, Tn0, c_end, 0) && enough(Tm, Tn1, c_end, 1)) {
             std::vector<G3Item> items;
             std::vector<G3Red> red;
             g3_plan_row2(Tm, Tn0, Tn1, c_end, items, red, target_items, slab_budget);
-            pl.row[Jb] = store(items, red);
-            is_merged[Jb] = 1;
+            pl.row[J.Jb] = store(items, red);
+            is_merged[J.Jb] = 1;
             pl.any_row = true;
         }
     }
-    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
-        const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-        const bool skip = J0 == 0 || (walk && is_merged[Jb]);
-        pl.fac.push_back(skip ? G3Step() : add((J1 - J0 + 255) / 256, (K - J0 + 255) / 256, J0 / G3_CHUNK_ROWS, 0));
+    for (BlockRow J(K, NBO); J; ++J) {
+        const bool skip = J.J0 == 0 || (walk && is_merged[J.Jb]);
+        pl.fac.push_back(skip ? G3Step() : add(J.Tm(), J.Tn0(), J.c_end(), 0));
     }
-    for (int I0 = 0, Ib = 0; I0 < K; I0 += NBI, ++Ib) {
-        const int I1 = (K - I0 < NBI) ? K : I0 + NBI;
-        const bool skip = I0 == 0 || (walk && is_merged[Ib]);
-        pl.inv.push_back(skip ? G3Step() : add((I1 - I0 + 255) / 256, (I0 + 255) / 256, I0 / G3_CHUNK_ROWS, 1));
+    for (BlockRow I(K, NBI); I; ++I) {
+        const bool skip = I.J0 == 0 || (walk && is_merged[I.Jb]);
+        pl.inv.push_back(skip ? G3Step() : add(I.Tm(), I.Tn1(), I.c_end(), 1));
     }
     pl.blob_bytes = pl.any ? qt_align_up(bytes.size(), 256) : 0;
 }
@@ -223,10 +224,6 @@ static const CholG3Plan* chol_g3_plan(int K, int NBO, int NBI, bool merged = fal
     plans[key] = pl;
     return pl;
 }
-static size_t chol_g3_ws_bytes(const CholG3Plan* pl, int K) {
-    if (!pl->any) return 0;
-    return 2 * qt_align_up((size_t)3 * K * K * 2, 256) + (size_t)pl->max_slabs * 256 * 256 * 4 + pl->blob_bytes + 256;
-}
 
 // block sizes and item tables of one call
 static const CholG3Plan* chol_blocks(int K, int& NBO, int& NBI) {
@@ -247,7 +244,6 @@ constexpr int LDP = NB + 1;  // padded LDS leading dimension
 // column is held as four 32-entry arrays: the 32 steps inside a sub-block are unrolled (static
 // indices) and the sub-block loop stays a run-time loop with wave-uniform guards.
 constexpr int LDT = NB + 4;  // LDS leading dimension with 16-byte aligned rows
-constexpr int RD_STRIDE = NB * NB + 4 * 32 * 32;  // dense R block + four 32x32 sub-block inverses
 
 #define QT_SEL4(kb, v0, v1, v2, v3) ((kb) == 0 ? (v0) : (kb) == 1 ? (v1) : (kb) == 2 ? (v2) : (v3))
 
@@ -777,37 +773,52 @@ __global__ __launch_bounds__(256) void chol_scales_kernel(const float* __restric
 
 }  // namespace
 
-// bytes of ONE problem's share of the workspace (a multiple of 256), without the bf16x3 item tables (shared by a batch)
-static size_t chol_problem_ws_bytes(int K, const CholG3Plan* g3) {
-    const size_t nb = (K + NB - 1) / NB;
-    // T panel [128, K] + T_I panel [512, K] + X_II [512, 512] + Rd, Dinv [nb][128*128] each + split-K slabs
-    // (a split product writes splits * M * N floats with splits <= 2048 workgroups / tiles: <= 2048 * 128 * 128)
-    const size_t split = (size_t)2048 * NB * NB * 4 + (size_t)NBO_MAX * K * 4;
-    size_t n = (size_t)NB * K * 4 + (size_t)NBO_MAX * K * 4 + (size_t)NBO_MAX * NBO_MAX * 4 + nb * (NB * NB + RD_STRIDE) * 4 + split + 256;
-    if (g3->any) n += 2 * qt_align_up((size_t)3 * K * K * 2, 256) + (size_t)g3->max_slabs * 256 * 256 * 4 + 256;
-    return qt_align_up(n, 256);
-}
+// ---- host side: workspace, context, the steps, the two schedules ----------------------------
+
+// ONE problem's share of the workspace as the plan g3 sizes it; a batch's is CholLayout::batch_bytes
+static CholLayout chol_layout(int K, const CholG3Plan* g3) { return CholLayout(K, g3->any, g3->max_slabs); }
 
 extern "C" size_t qt_cholesky_inverse_upper_batched_workspace_bytes(int K, int n_problems) {
     if (K <= 0 || n_problems <= 0) return 0;
     int nbo_, nbi_;
     const CholG3Plan* g3 = chol_blocks(K, nbo_, nbi_);
-    return (size_t)n_problems * chol_problem_ws_bytes(K, g3) + g3->blob_bytes + 512;
+    return chol_layout(K, g3).batch_bytes(n_problems, g3->blob_bytes);
 }
 
 extern "C" size_t qt_cholesky_inverse_upper_workspace_bytes(int K) {
     return qt_cholesky_inverse_upper_batched_workspace_bytes(K, 1);
 }
 
-// n problems of one size K in every launch of the chain: problem b's matrices at A + b * strideA, U + b * strideU
-// (elements), its pivot flag at info[b].  Per problem the kernels, their launch shapes and the order of every sum are
-// those of a single-problem call (tile sizes and split-K decisions come from one problem's shape), so the factors are
-// bit-identical to n separate calls; what changes is that the latency-bound panel kernels (potf2: ONE workgroup per
-// problem; trsm, the short folds) and the block-row products serve all n problems per launch.
+constexpr size_t INV_LDS = (size_t)(NB * LDT + NB * LDP) * sizeof(float);
+constexpr size_t POTF2_LDS = (size_t)(NB * LDA + 4 * 32 * 32) * sizeof(float);
+constexpr size_t RD_LDS = RD_STRIDE * sizeof(float);   // trsm_rt_kernel, trinv_mfma_kernel: one Rd block
+
+// What every step of one call reads.  n problems of one size K in every launch of the chain: problem b's matrices at
+// A + b * sA, Y + b * sY (elements), its share of the workspace at + b * sW, its pivot flag at info[b].
+struct CholCtx {
+    float *A, *Y;              // A: the input, R in place; Y = U: R^-T (lower) until the closing reversal
+    int K, nprob, NBO, NBI;
+    int64_t sA, sY, sW;        // batch strides in floats (sA, sY: 0 for one problem; sW: one problem's workspace)
+    float *T, *TI, *XT, *Rd, *Dinv, *split_ws;   // CholLayout's regions in problem 0's share
+    size_t split_ws_bytes;
+    // bf16x3 products: plane copies of R and Y, slabs (per problem), item tables (one copy for the batch)
+    unsigned short *Rpl, *Ypl;
+    int64_t plane_stride;
+    float* g3_slabs;
+    char* g3_tab;
+    const CholG3Plan* g3;      // sizes the workspace, whatever QT_CHOL_MERGE says
+    const CholG3Plan* tab;     // the tables the launches use
+    int planes;                // G3_BF16X3 | G3_F16X2
+    int merge_mode;            // CHOL_TWO_PHASE | CHOL_WALK | CHOL_WALK_MERGED
+    int32_t *info, *eR, *eY;   // eR, eY (G3_F16X2): the scale exponents, [nprob] each
+    int prio;
+    hipStream_t stream;
+};
+
+// The plane mode and the schedule of one call, from the arguments and the environment (read per call).
 // min_eig_lb (device, one per problem; may be null): see the head of the file.  QT_CHOL_PLANES=bf16x3|f16x2 forces a plane
-// mode (A/B runs; read per call): bf16x3 ignores the bound, f16x2 without one is an argument error.
-static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info, int nprob, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream, const float* min_eig_lb = nullptr) {
+// mode (A/B runs): bf16x3 ignores the bound, f16x2 without one is an argument error.
+static int chol_resolve(CholCtx& c, const float* min_eig_lb) {
     bool f16x2 = min_eig_lb != nullptr;
     if (const char* e = getenv("QT_CHOL_PLANES")) {
         if (strcmp(e, "bf16x3") == 0) f16x2 = false;
@@ -817,314 +828,298 @@ static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU,
             QT_CHECK_ARG(false, "qt_cholesky_inverse_upper: QT_CHOL_PLANES=%s (bf16x3 | f16x2)", e);
         }
     }
-    const size_t need = qt_cholesky_inverse_upper_batched_workspace_bytes(K, nprob);
+    c.g3 = chol_blocks(c.K, c.NBO, c.NBI);
+    c.planes = (f16x2 && c.g3->any) ? G3_F16X2 : G3_BF16X3;
+    c.merge_mode = (c.g3->any && c.NBO == c.NBI) ? chol_merge_mode() : CHOL_TWO_PHASE;
+    c.tab = c.g3;
+    if (c.merge_mode == CHOL_WALK_MERGED) {
+        c.tab = chol_g3_plan(c.K, c.NBO, c.NBI, true);
+        // by construction the merged tables need no more slabs and no more table bytes than the separate ones
+        // (a size with no merged row keeps the two phases: the walk alone buys nothing)
+        if (!c.tab->any || !c.tab->any_row || c.tab->max_slabs > c.g3->max_slabs || c.tab->blob_bytes > c.g3->blob_bytes) {
+            c.tab = c.g3;
+            c.merge_mode = CHOL_TWO_PHASE;
+        }
+    }
+    return QT_OK;
+}
+
+// Where an operand of a chain product lives decides its batch stride: in the matrix A (R, in place), in the matrix Y
+// (= U), or in the problem's share of the workspace (T, T_I, X_II, Dinv).
+enum CholHome { IN_A, IN_Y, IN_WS };
+struct CholOperand { float* p; int64_t ld; CholHome home; };
+static int64_t chol_stride(const CholCtx& c, CholHome h) { return h == IN_A ? c.sA : h == IN_Y ? c.sY : c.sW; }
+
+// An f32 product of the chain, for all problems:  C (mode) A^T B  with A [kdim][M], B [kdim][N].  SG_MODE_SUB works in
+// place on C; SET and NEG only write it.  offer_split: the product may take the split-K slabs -- the two long block-row
+// products alone (fac_product, inv_product): a split changes the order of a sum, so the offer is part of the bits.
+static SgemmArgs chol_sgemm_args(const CholCtx& c, CholOperand A, CholOperand B, CholOperand C, int M, int N, int kdim,
+                                 int k_mode, int mode, bool offer_split) {
+    SgemmArgs g;
+    g.A = A.p; g.lda = A.ld;
+    g.B = B.p; g.ldb = B.ld;
+    g.Cin = mode == SG_MODE_SUB ? C.p : nullptr; g.ldcin = mode == SG_MODE_SUB ? C.ld : 0;
+    g.Cout = C.p; g.ldcout = C.ld;
+    g.M = M; g.N = N; g.kdim = kdim; g.k_mode = k_mode; g.mode = mode;
+    g.split_ws = offer_split ? c.split_ws : nullptr; g.split_ws_bytes = offer_split ? c.split_ws_bytes : 0;
+    g.batch = c.nprob;
+    g.bsA = chol_stride(c, A.home); g.bsB = chol_stride(c, B.home); g.bsCin = g.bsCout = chol_stride(c, C.home);
+    g.bs_split = c.sW;
+    return g;
+}
+
+// A block-row product on the plane copies:  C[M][N] (mode) R[:k, col_a0:]^T B[:k, col_b0:]  with the items of st.
+// second: the launch also carries segment 1 of a merged row, T_J = R[:J0, J]^T Y[:J0, :J0] -> TI (G3Args)
+static int g3_row(const CholCtx& c, const G3Step& st, const unsigned short* Bplanes, int col_a0, int col_b0, int M, int N,
+                  float* C, CholHome c_home, int mode, bool second = false) {
+    G3Args a;
+    a.Apl = c.Rpl; a.Bpl = Bplanes; a.plane_stride = c.plane_stride; a.ld = c.K;
+    a.rowA0 = a.rowB0 = 0; a.colA0 = col_a0; a.colB0 = col_b0; a.colmax = c.K;
+    a.M = M; a.N = N; a.C = C; a.ldc = c.K; a.mode = mode;
+    a.slabs = c.g3_slabs;
+    a.items = (const G3Item*)(c.g3_tab + st.item_off); a.n_items = st.n_items;
+    a.red = (const G3Red*)(c.g3_tab + st.red_off); a.n_red = st.n_red;
+    a.batch = c.nprob;
+    a.bsApl = a.bsBpl = c.sW * 2;       // plane copies live in the problem's workspace (bf16 elements)
+    a.bsC = chol_stride(c, c_home); a.bsSlabs = c.sW;
+    if (c.planes == G3_F16X2) {
+        a.planes = G3_F16X2; a.eA = c.eR; a.eB = Bplanes == c.Rpl ? c.eR : c.eY;
+    }
+    if (second) {
+        a.Bpl1 = c.Ypl; a.colB01 = 0; a.eB1 = c.eY;
+        a.C1 = c.TI; a.ldc1 = c.K; a.bsC1 = c.sW; a.mode1 = G3_SET;
+        a.N1 = col_a0;   // J0 columns
+    }
+    return qt_gemm3_launch(a, c.stream);
+}
+
+// ---- A = R^T R over NBO-wide outer blocks, left-looking inside one; in place.  Outer level: right-looking
+// (one k = NBO update of the trailing matrix per block) on the f32 MFMA, or -- when the bf16x3 products
+// are in use for this K -- left-looking (block row J gathers all earlier block rows in one long-k product)
+// A[J, J0:] -= R[:J0, J]^T R[:J0, J0:]
+static int fac_product(const CholCtx& c, const BlockRow& J) {
+    if (!(c.g3->any && J.J0 > 0)) return QT_OK;
+    const int K = c.K, J0 = J.J0;
+    const G3Step& st = c.tab->fac[J.Jb];
+    float* C = c.A + (size_t)J0 * K + J0;
+    if (st.n_items > 0) return g3_row(c, st, c.Rpl, J0, J0, J.rows(), K - J0, C, IN_A, G3_SUB);
+    const CholOperand RJ = {c.A + J0, K, IN_A};   // R[:J0, J0:]
+    return qt_sgemm_tn(chol_sgemm_args(c, RJ, RJ, {C, K, IN_A}, J.rows(), K - J0, J0, SG_K_FULL, SG_MODE_SUB, true), c.stream);
+}
+
+// the panel chain of block row J, then its plane copies (or the right-looking update)
+static int fac_panels(const CholCtx& c, const BlockRow& J) {
+    const int K = c.K, J0 = J.J0, J1 = J.J1, nprob = c.nprob;
+    float* A = c.A;
+    for (int j0 = J0; j0 < J1; j0 += NB) {
+        const int j = j0 / NB, nbj = (K - j0 < NB) ? K - j0 : NB;
+        float* Ajj = A + (size_t)j0 * K + j0;
+        if (j0 > J0) {
+            // rows J0..j0 of this outer block are final: fold them into block row j
+            const CholOperand Rj = {A + (size_t)J0 * K + j0, K, IN_A};
+            int rc = qt_sgemm_tn(chol_sgemm_args(c, Rj, Rj, {Ajj, K, IN_A}, nbj, K - j0, j0 - J0, SG_K_FULL, SG_MODE_SUB, false),
+                                 c.stream);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(potf2_kernel, dim3(nprob), dim3(POTF2_THREADS), POTF2_LDS, c.stream, (const float*)Ajj, (int64_t)K, nbj,
+                           Ajj, (int64_t)K, c.Rd + (size_t)j * RD_STRIDE, c.info, j0, c.prio, c.sA, c.sW);
+        QT_LAUNCH_CHECK();
+        const int rest = K - j0 - nbj;
+        if (rest > 0) {
+            hipLaunchKernelGGL(trsm_rt_kernel, dim3((rest + 127) / 128, nprob), dim3(256), RD_LDS, c.stream,
+                               (const float*)(c.Rd + (size_t)j * RD_STRIDE), nbj, (const float*)(Ajj + nbj), (int64_t)K,
+                               Ajj + nbj, (int64_t)K, rest, c.prio, c.sW, c.sA);
+            QT_LAUNCH_CHECK();
+        }
+    }
+    const int rem = K - J1;
+    if (c.g3->any) {
+        // plane copies of the finished block row (columns from its diagonal block on; only entries above
+        // the diagonal are ever read back)
+        if (rem > 0) {
+            float* RJ = A + (size_t)J0 * K + J0;
+            unsigned short* pl = c.Rpl + (size_t)J0 * K + J0;
+            int rc = c.planes == G3_F16X2
+                         ? qt_split2h_launch(RJ, K, J1 - J0, K - J0, pl, K, c.plane_stride, 0, 0, 0, c.eR, c.stream, nprob, c.sA, c.sW * 2)
+                         : qt_split3_launch(RJ, K, J1 - J0, K - J0, pl, K, c.plane_stride, 0, 0, 0, c.stream, nprob, c.sA, c.sW * 2);
+            if (rc) return rc;
+        }
+    } else if (rem > 0) {
+        // the K^3/3 of the factorisation: one SYRK-shaped update per outer block, upper tiles only
+        const CholOperand RJ = {A + (size_t)J0 * K + J1, K, IN_A};
+        SgemmArgs g = chol_sgemm_args(c, RJ, RJ, {A + (size_t)J1 * K + J1, K, IN_A}, rem, rem, J1 - J0, SG_K_FULL, SG_MODE_SUB, false);
+        g.upper_only = 1;
+        int rc = qt_sgemm_tn(g, c.stream);
+        if (rc) return rc;
+    }
+    return QT_OK;
+}
+
+// the inverses of the 128x128 diagonal blocks blk0 .. blk0 + n - 1
+static int trinv(const CholCtx& c, int blk0, int n) {
+    const char* e = getenv("QT_CHOL_TRINV");   // read per call: the tests compare the two kernels in one process
+    if (e && strcmp(e, "div") == 0)
+        hipLaunchKernelGGL(trinv_batched_kernel, dim3(n, c.nprob), dim3(NB), INV_LDS, c.stream, (const float*)c.Rd, c.K, c.Dinv,
+                           c.Y, (int64_t)c.K, c.sW, c.sY, blk0);
+    else
+        hipLaunchKernelGGL(trinv_mfma_kernel, dim3(n, c.nprob), dim3(256), RD_LDS, c.stream, (const float*)c.Rd, c.K, c.Dinv,
+                           c.Y, (int64_t)c.K, c.sW, c.sY, blk0);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+// ---- Y = R^-T by NBI-row block rows ----
+// left of the diagonal block: the K^3/3 of the inverse, one product per block row:  T_I = R[:I0, I]^T Y[:I0, :I0]
+static int inv_product(const CholCtx& c, const BlockRow& I) {
+    const int K = c.K, I0 = I.J0;
+    if (I0 == 0) return QT_OK;
+    if (c.g3->any && c.tab->inv[I.Jb].n_items > 0) return g3_row(c, c.tab->inv[I.Jb], c.Ypl, I0, 0, I.rows(), I0, c.TI, IN_WS, G3_SET);
+    return qt_sgemm_tn(chol_sgemm_args(c, {c.A + I0, K, IN_A}, {c.Y, K, IN_Y}, {c.TI, K, IN_WS}, I.rows(), I0, I0, SG_K_FROM_N0,
+                                       SG_MODE_SET, true),
+                       c.stream);
+}
+
+// plane copy of the finished block row of Y (zeros above the diagonal), for the later rows' products
+static int split_row(const CholCtx& c, const BlockRow& I) {
+    const int K = c.K, I0 = I.J0;
+    if (!c.g3->any || I.J1 >= K) return QT_OK;
+    if (c.planes == G3_F16X2)
+        return qt_split2h_launch(c.Y + (size_t)I0 * K, K, I.rows(), I.J1, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.eY,
+                                 c.stream, c.nprob, c.sY, c.sW * 2);
+    return qt_split3_launch(c.Y + (size_t)I0 * K, K, I.rows(), I.J1, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.stream,
+                            c.nprob, c.sY, c.sW * 2);
+}
+
+// the rest of block row I: Y_II, then Y[I, :I0] = -Y_II T_I from the T_I the product left in TI, then the plane copy
+static int inv_row(const CholCtx& c, const BlockRow& I) {
+    const int K = c.K, I0 = I.J0, I1 = I.J1, Wi = I.rows();
+    float* Y = c.Y;
+    // the diagonal 512-block Y_II by the 128-row recurrence (short k)
+    for (int i0 = I0 + NB; i0 < I1; i0 += NB) {
+        const int i = i0 / NB, nbi = (K - i0 < NB) ? K - i0 : NB;
+        const CholOperand Yi = {Y + (size_t)i0 * K + I0, K, IN_Y}, Tp = {c.T, K, IN_WS};
+        int rc = qt_sgemm_tn(chol_sgemm_args(c, {c.A + (size_t)I0 * K + i0, K, IN_A}, {Y + (size_t)I0 * K + I0, K, IN_Y}, Tp, nbi,
+                                             i0 - I0, i0 - I0, SG_K_FROM_N0, SG_MODE_SET, false),
+                             c.stream);
+        if (rc) return rc;
+        rc = qt_sgemm_tn(chol_sgemm_args(c, {c.Dinv + (size_t)i * NB * NB, NB, IN_WS}, Tp, Yi, nbi, i0 - I0, nbi, SG_K_FULL,
+                                         SG_MODE_NEG, false),
+                         c.stream);
+        if (rc) return rc;
+    }
+    if (I0 == 0) return split_row(c, I);
+    hipLaunchKernelGGL(transpose_lower_block_kernel, dim3((Wi + 31) / 32, (Wi + 31) / 32, c.nprob), dim3(256), 0, c.stream,
+                       (const float*)(Y + (size_t)I0 * K + I0), (int64_t)K, Wi, c.XT, NBO_MAX, c.sY, c.sW);
+    QT_LAUNCH_CHECK();
+    int rc = qt_sgemm_tn(chol_sgemm_args(c, {c.XT, NBO_MAX, IN_WS}, {c.TI, K, IN_WS}, {Y + (size_t)I0 * K, K, IN_Y}, Wi, I0, Wi,
+                                         SG_K_FULL, SG_MODE_NEG, false),
+                         c.stream);
+    if (rc) return rc;
+    return split_row(c, I);
+}
+
+// QT_CHOL_MERGE=0: the whole factorisation, all diagonal-block inverses at once, then Y row by row
+static int chol_run_two_phase(const CholCtx& c) {
+    for (BlockRow J(c.K, c.NBO); J; ++J) {
+        int rc = fac_product(c, J);
+        if (!rc) rc = fac_panels(c, J);
+        if (rc) return rc;
+    }
+    int rc = trinv(c, 0, (c.K + NB - 1) / NB);
+    if (rc) return rc;
+    for (BlockRow I(c.K, c.NBI); I; ++I) {
+        rc = inv_product(c, I);
+        if (!rc) rc = inv_row(c, I);
+        if (rc) return rc;
+    }
+    return QT_OK;
+}
+
+// one walk over the block rows (NBO == NBI): see chol_merge_mode()
+static int chol_run_walk(const CholCtx& c) {
+    for (BlockRow J(c.K, c.NBO); J; ++J) {
+        int rc;
+        if (c.merge_mode == CHOL_WALK_MERGED && c.tab->row[J.Jb].n_items > 0) {
+            rc = g3_row(c, c.tab->row[J.Jb], c.Rpl, J.J0, J.J0, J.rows(), c.K - J.J0, c.A + (size_t)J.J0 * c.K + J.J0, IN_A, G3_SUB,
+                        /*second=*/true);
+        } else {
+            rc = fac_product(c, J);
+            if (!rc) rc = inv_product(c, J);
+        }
+        if (!rc) rc = fac_panels(c, J);
+        if (!rc) rc = trinv(c, J.J0 / NB, (J.rows() + NB - 1) / NB);
+        if (!rc) rc = inv_row(c, J);
+        if (rc) return rc;
+    }
+    return QT_OK;
+}
+
+// the panel kernels' dynamic LDS beyond the default limit, asked for once per device
+static hipError_t chol_lds_attrs() {
+    static QtOncePerDevice lds_attr;
+    return lds_attr.run([] {
+        const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+        hipError_t e = hipFuncSetAttribute((const void*)potf2_kernel, attr, (int)POTF2_LDS);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)trsm_rt_kernel, attr, (int)RD_LDS);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)trinv_batched_kernel, attr, (int)INV_LDS);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)trinv_mfma_kernel, attr, (int)RD_LDS);
+        return e;
+    });
+}
+
+// n problems of one size K in every launch of the chain: problem b's matrices at A + b * strideA, U + b * strideU
+// (elements), its pivot flag at info[b].  Per problem the kernels, their launch shapes and the order of every sum are
+// those of a single-problem call (tile sizes and split-K decisions come from one problem's shape), so the factors are
+// bit-identical to n separate calls; what changes is that the latency-bound panel kernels (potf2: ONE workgroup per
+// problem; trsm, the short folds) and the block-row products serve all n problems per launch.
+static int chol_run(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info, int nprob, void* workspace,
+                    size_t workspace_bytes, hipStream_t stream, const float* min_eig_lb = nullptr) {
+    CholCtx c = {};
+    c.A = A; c.Y = U; c.K = K; c.nprob = nprob; c.info = info; c.stream = stream;
+    if (int rc = chol_resolve(c, min_eig_lb)) return rc;
+    const CholLayout L = chol_layout(K, c.g3);
+    const size_t need = L.batch_bytes(nprob, c.g3->blob_bytes);
     if (!workspace || workspace_bytes < need) {
         qt_set_error("qt_cholesky_inverse_upper: workspace %zu < required %zu", workspace_bytes, need);
         return QT_ERR_WORKSPACE;
     }
-    const int nblk = (K + NB - 1) / NB;
     char* ws = (char*)qt_align_up((size_t)workspace, 256);
-    int NBO, NBI;
-    const CholG3Plan* g3 = chol_blocks(K, NBO, NBI);   // sizes the workspace, whatever QT_CHOL_MERGE says
-    int merge_mode = (g3->any && NBO == NBI) ? chol_merge_mode() : CHOL_TWO_PHASE;
-    const CholG3Plan* tab = g3;                         // the tables the launches use
-    if (merge_mode == CHOL_WALK_MERGED) {
-        tab = chol_g3_plan(K, NBO, NBI, true);
-        // by construction the merged tables need no more slabs and no more table bytes than the separate ones
-        // (a size with no merged row keeps the two phases: the walk alone buys nothing)
-        if (!tab->any || !tab->any_row || tab->max_slabs > g3->max_slabs || tab->blob_bytes > g3->blob_bytes) {
-            tab = g3;
-            merge_mode = CHOL_TWO_PHASE;
-        }
+    c.sW = (int64_t)(L.bytes() / 4); c.sA = nprob > 1 ? strideA : 0; c.sY = nprob > 1 ? strideU : 0;
+    c.T = (float*)(ws + L.T); c.TI = (float*)(ws + L.TI); c.XT = (float*)(ws + L.XT);
+    c.Rd = (float*)(ws + L.Rd); c.Dinv = (float*)(ws + L.Dinv);
+    c.split_ws = (float*)(ws + L.split); c.split_ws_bytes = L.split_bytes;
+    c.plane_stride = (int64_t)K * K;
+    if (c.g3->any) {
+        c.Rpl = (unsigned short*)(ws + L.Rpl); c.Ypl = (unsigned short*)(ws + L.Ypl);
+        c.g3_slabs = (float*)(ws + L.slabs); c.g3_tab = ws + L.tables(nprob);
+        QT_HIP(hipMemcpyAsync(c.g3_tab, c.tab->blob, c.tab->blob_bytes, hipMemcpyHostToDevice, stream));
     }
-    const size_t prob_bytes = chol_problem_ws_bytes(K, g3);
-    const int64_t sW = (int64_t)(prob_bytes / 4);            // one problem's workspace, in floats
-    const int64_t sA = nprob > 1 ? strideA : 0, sU = nprob > 1 ? strideU : 0;
-    float* T = (float*)ws;
-    float* TI = T + (size_t)NB * K;
-    float* XT = TI + (size_t)NBO_MAX * K;
-    float* Rd = XT + (size_t)NBO_MAX * NBO_MAX;
-    float* Dinv = Rd + (size_t)nblk * RD_STRIDE;
-    float* split_ws = Dinv + (size_t)nblk * NB * NB;
-    const size_t split_ws_bytes = (size_t)2048 * NB * NB * 4 + (size_t)NBO_MAX * K * 4;
-    // bf16x3 products: plane copies of R and Y, slabs (per problem), item tables (one copy for the batch)
-    unsigned short *Rpl = nullptr, *Ypl = nullptr;
-    float* g3_slabs = nullptr;
-    char* g3_tab = nullptr;
-    const int64_t plane_stride = (int64_t)K * K;
-    if (g3->any) {
-        char* q = (char*)qt_align_up((size_t)((char*)split_ws + split_ws_bytes), 256);
-        Rpl = (unsigned short*)q;
-        q += qt_align_up((size_t)3 * K * K * 2, 256);
-        Ypl = (unsigned short*)q;
-        q += qt_align_up((size_t)3 * K * K * 2, 256);
-        g3_slabs = (float*)q;
-        g3_tab = (char*)qt_align_up((size_t)(ws + (size_t)nprob * prob_bytes), 256);
-        QT_HIP(hipMemcpyAsync(g3_tab, tab->blob, tab->blob_bytes, hipMemcpyHostToDevice, stream));
-    }
-    f16x2 = f16x2 && g3->any;
     // two fp16 planes use the first two plane slots; the scale exponents eR[nprob], eY[nprob] sit in problem 0's third
-    int32_t* eR = f16x2 ? (int32_t*)(Rpl + 2 * plane_stride) : nullptr;
-    int32_t* eY = f16x2 ? eR + nprob : nullptr;
     static_assert(2 * SG_MAX_BATCH * sizeof(int32_t) <= (size_t)NB * NB * 2, "the exponents fit the smallest third plane");
-    // where a block-row product's C lives decides its batch stride: A (factor phase) or the workspace (T_I)
-    // second: the launch also carries segment 1 of a merged row, T_J = R[:J0, J]^T Y[:J0, :J0] -> TI (G3Args)
-    auto g3_row = [&](const G3Step& st, const unsigned short* Bplanes, int col_a0, int col_b0, int M, int N, float* C,
-                      int64_t bsC, int mode, bool second = false) -> int {
-        G3Args a;
-        a.Apl = Rpl;
-        a.Bpl = Bplanes;
-        a.plane_stride = plane_stride;
-        a.ld = K;
-        a.rowA0 = a.rowB0 = 0;
-        a.colA0 = col_a0;
-        a.colB0 = col_b0;
-        a.colmax = K;
-        a.M = M;
-        a.N = N;
-        a.C = C;
-        a.ldc = K;
-        a.mode = mode;
-        a.slabs = g3_slabs;
-        a.items = (const G3Item*)(g3_tab + st.item_off);
-        a.n_items = st.n_items;
-        a.red = (const G3Red*)(g3_tab + st.red_off);
-        a.n_red = st.n_red;
-        a.batch = nprob;
-        a.bsApl = a.bsBpl = sW * 2;       // plane copies live in the problem's workspace (bf16 elements)
-        a.bsC = bsC;
-        a.bsSlabs = sW;
-        if (f16x2) {
-            a.planes = G3_F16X2;
-            a.eA = eR;
-            a.eB = Bplanes == Rpl ? eR : eY;
-        }
-        if (second) {
-            a.Bpl1 = Ypl;
-            a.colB01 = 0;
-            a.eB1 = eY;
-            a.C1 = TI;
-            a.ldc1 = K;
-            a.bsC1 = sW;
-            a.mode1 = G3_SET;
-            a.N1 = col_a0;   // J0 columns
-        }
-        return qt_gemm3_launch(a, stream);
-    };
-    // an f32 product of the chain, for all problems: strides by where each operand lives
-    auto sgemm = [&](SgemmArgs& g, int64_t bsA_, int64_t bsB_, int64_t bsC_) -> int {
-        g.batch = nprob;
-        g.bsA = bsA_;
-        g.bsB = bsB_;
-        g.bsCin = g.bsCout = bsC_;
-        g.bs_split = sW;
-        return qt_sgemm_tn(g, stream);
-    };
-    float* Y = U;
-    const int64_t sY = sU;
-    const size_t inv_lds = (size_t)(NB * LDT + NB * LDP) * sizeof(float);
-    const size_t potf2_lds = (size_t)(NB * LDA + 4 * 32 * 32) * sizeof(float);
-    static QtOncePerDevice lds_attr;
-    QT_HIP(lds_attr.run([&] {
-        hipError_t e = hipFuncSetAttribute((const void*)potf2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)potf2_lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)trsm_rt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(RD_STRIDE * sizeof(float)));
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)trinv_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)inv_lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)trinv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(RD_STRIDE * sizeof(float)));
-        return e;
-    }));
+    c.eR = c.planes == G3_F16X2 ? (int32_t*)(c.Rpl + 2 * c.plane_stride) : nullptr;
+    c.eY = c.planes == G3_F16X2 ? c.eR + nprob : nullptr;
+    QT_HIP(chol_lds_attrs());
     QT_HIP(hipMemsetAsync(info, 0, sizeof(int32_t) * nprob, stream));
-    const int prio = qt_chain_prio();
-    if (f16x2) {
-        hipLaunchKernelGGL(chol_scales_kernel, dim3(nprob), dim3(256), 0, stream, (const float*)A, sA, K, min_eig_lb, eR, info);
+    c.prio = qt_chain_prio();
+    if (c.planes == G3_F16X2) {
+        hipLaunchKernelGGL(chol_scales_kernel, dim3(nprob), dim3(256), 0, stream, (const float*)A, c.sA, K, min_eig_lb, c.eR, info);
         QT_LAUNCH_CHECK();
     }
-
-    // ---- A = R^T R over NBO-wide outer blocks, left-looking inside one; in place.  Outer level: right-looking
-    // (one k = NBO update of the trailing matrix per block) on the f32 MFMA, or -- when the bf16x3 products
-    // are in use for this K -- left-looking (block row J gathers all earlier block rows in one long-k product)
-    // A[J, J0:] -= R[:J0, J]^T R[:J0, J0:]
-    auto fac_product = [&](int J0, int J1, int Jb) -> int {
-        if (!(g3->any && J0 > 0)) return QT_OK;
-        const G3Step& st = tab->fac[Jb];
-        float* C = A + (size_t)J0 * K + J0;
-        if (st.n_items > 0) return g3_row(st, Rpl, J0, J0, J1 - J0, K - J0, C, sA, G3_SUB);
-        SgemmArgs g;
-        g.A = A + J0; g.lda = K;
-        g.B = A + J0; g.ldb = K;
-        g.Cin = C; g.ldcin = K;
-        g.Cout = C; g.ldcout = K;
-        g.M = J1 - J0; g.N = K - J0; g.kdim = J0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-        g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
-        return sgemm(g, sA, sA, sA);
-    };
-    // the panel chain of block row J, then its plane copies (or the right-looking update)
-    auto fac_panels = [&](int J0, int J1) -> int {
-        for (int j0 = J0; j0 < J1; j0 += NB) {
-            const int j = j0 / NB, nbj = (K - j0 < NB) ? K - j0 : NB;
-            float* Ajj = A + (size_t)j0 * K + j0;
-            if (j0 > J0) {
-                // rows J0..j0 of this outer block are final: fold them into block row j
-                SgemmArgs g;
-                g.A = A + (size_t)J0 * K + j0; g.lda = K;
-                g.B = A + (size_t)J0 * K + j0; g.ldb = K;
-                g.Cin = Ajj; g.ldcin = K;
-                g.Cout = Ajj; g.ldcout = K;
-                g.M = nbj; g.N = K - j0; g.kdim = j0 - J0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-                int rc = sgemm(g, sA, sA, sA);
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(potf2_kernel, dim3(nprob), dim3(POTF2_THREADS), potf2_lds, stream, (const float*)Ajj, (int64_t)K, nbj,
-                               Ajj, (int64_t)K, Rd + (size_t)j * RD_STRIDE, info, j0, prio, sA, sW);
-            QT_LAUNCH_CHECK();
-            const int rest = K - j0 - nbj;
-            if (rest > 0) {
-                hipLaunchKernelGGL(trsm_rt_kernel, dim3((rest + 127) / 128, nprob), dim3(256), RD_STRIDE * sizeof(float),
-                                   stream, (const float*)(Rd + (size_t)j * RD_STRIDE), nbj, (const float*)(Ajj + nbj),
-                                   (int64_t)K, Ajj + nbj, (int64_t)K, rest, prio, sW, sA);
-                QT_LAUNCH_CHECK();
-            }
-        }
-        const int rem = K - J1;
-        if (g3->any) {
-            // plane copies of the finished block row (columns from its diagonal block on; only entries above
-            // the diagonal are ever read back)
-            if (rem > 0) {
-                int rc = f16x2 ? qt_split2h_launch(A + (size_t)J0 * K + J0, K, J1 - J0, K - J0, Rpl + (size_t)J0 * K + J0, K,
-                                                   plane_stride, 0, 0, 0, eR, stream, nprob, sA, sW * 2)
-                               : qt_split3_launch(A + (size_t)J0 * K + J0, K, J1 - J0, K - J0, Rpl + (size_t)J0 * K + J0, K,
-                                                  plane_stride, 0, 0, 0, stream, nprob, sA, sW * 2);
-                if (rc) return rc;
-            }
-        } else if (rem > 0) {
-            // the K^3/3 of the factorisation: one SYRK-shaped update per outer block, upper tiles only
-            SgemmArgs g;
-            g.A = A + (size_t)J0 * K + J1; g.lda = K;
-            g.B = A + (size_t)J0 * K + J1; g.ldb = K;
-            g.Cin = A + (size_t)J1 * K + J1; g.ldcin = K;
-            g.Cout = A + (size_t)J1 * K + J1; g.ldcout = K;
-            g.M = rem; g.N = rem; g.kdim = J1 - J0; g.k_mode = SG_K_FULL; g.mode = SG_MODE_SUB;
-            g.upper_only = 1;
-            int rc = sgemm(g, sA, sA, sA);
-            if (rc) return rc;
-        }
-        return QT_OK;
-    };
-    // the inverses of the 128x128 diagonal blocks blk0 .. blk0 + n - 1
-    auto trinv = [&](int blk0, int n) -> int {
-        const char* e = getenv("QT_CHOL_TRINV");   // read per call: the tests compare the two kernels in one process
-        if (e && strcmp(e, "div") == 0)
-            hipLaunchKernelGGL(trinv_batched_kernel, dim3(n, nprob), dim3(NB), inv_lds, stream, (const float*)Rd, K, Dinv, Y,
-                               (int64_t)K, sW, sY, blk0);
-        else
-            hipLaunchKernelGGL(trinv_mfma_kernel, dim3(n, nprob), dim3(256), RD_STRIDE * sizeof(float), stream,
-                               (const float*)Rd, K, Dinv, Y, (int64_t)K, sW, sY, blk0);
-        QT_LAUNCH_CHECK();
-        return QT_OK;
-    };
-    // ---- Y = R^-T by NBI-row block rows ----
-    // left of the diagonal block: the K^3/3 of the inverse, one product per block row:  T_I = R[:I0, I]^T Y[:I0, :I0]
-    auto inv_product = [&](int I0, int I1, int Ib) -> int {
-        if (I0 == 0) return QT_OK;
-        if (g3->any && tab->inv[Ib].n_items > 0) return g3_row(tab->inv[Ib], Ypl, I0, 0, I1 - I0, I0, TI, sW, G3_SET);
-        SgemmArgs g;
-        g.A = A + I0; g.lda = K;
-        g.B = Y; g.ldb = K;
-        g.Cin = nullptr; g.ldcin = 0;
-        g.Cout = TI; g.ldcout = K;
-        g.M = I1 - I0; g.N = I0; g.kdim = I0; g.k_mode = SG_K_FROM_N0; g.mode = SG_MODE_SET;
-        g.split_ws = split_ws; g.split_ws_bytes = split_ws_bytes;
-        return sgemm(g, sA, sY, sW);
-    };
-    // the rest of block row I: Y_II, then Y[I, :I0] = -Y_II T_I from the T_I the product left in TI, then the plane copy
-    auto inv_row = [&](int I0, int I1) -> int {
-        const int Wi = I1 - I0;
-        // the diagonal 512-block Y_II by the 128-row recurrence (short k)
-        for (int i0 = I0 + NB; i0 < I1; i0 += NB) {
-            const int i = i0 / NB, nbi = (K - i0 < NB) ? K - i0 : NB;
-            SgemmArgs g;
-            g.A = A + (size_t)I0 * K + i0; g.lda = K;
-            g.B = Y + (size_t)I0 * K + I0; g.ldb = K;
-            g.Cin = nullptr; g.ldcin = 0;
-            g.Cout = T; g.ldcout = K;
-            g.M = nbi; g.N = i0 - I0; g.kdim = i0 - I0; g.k_mode = SG_K_FROM_N0; g.mode = SG_MODE_SET;
-            int rc = sgemm(g, sA, sY, sW);
-            if (rc) return rc;
-            SgemmArgs t;
-            t.A = Dinv + (size_t)i * NB * NB; t.lda = NB;
-            t.B = T; t.ldb = K;
-            t.Cin = nullptr; t.ldcin = 0;
-            t.Cout = Y + (size_t)i0 * K + I0; t.ldcout = K;
-            t.M = nbi; t.N = i0 - I0; t.kdim = nbi; t.k_mode = SG_K_FULL; t.mode = SG_MODE_NEG;
-            rc = sgemm(t, sW, sW, sY);
-            if (rc) return rc;
-        }
-        // plane copy of the finished block row of Y (zeros above the diagonal), for the later rows' products
-        auto split_row = [&]() -> int {
-            if (!g3->any || I1 >= K) return QT_OK;
-            if (f16x2)
-                return qt_split2h_launch(Y + (size_t)I0 * K, K, Wi, I1, Ypl + (size_t)I0 * K, K, plane_stride, 1, I0, 0, eY,
-                                         stream, nprob, sY, sW * 2);
-            return qt_split3_launch(Y + (size_t)I0 * K, K, Wi, I1, Ypl + (size_t)I0 * K, K, plane_stride, 1, I0, 0, stream,
-                                    nprob, sY, sW * 2);
-        };
-        if (I0 == 0) return split_row();
-        hipLaunchKernelGGL(transpose_lower_block_kernel, dim3((Wi + 31) / 32, (Wi + 31) / 32, nprob), dim3(256), 0, stream,
-                           (const float*)(Y + (size_t)I0 * K + I0), (int64_t)K, Wi, XT, NBO_MAX, sY, sW);
-        QT_LAUNCH_CHECK();
-        SgemmArgs t;
-        t.A = XT; t.lda = NBO_MAX;
-        t.B = TI; t.ldb = K;
-        t.Cin = nullptr; t.ldcin = 0;
-        t.Cout = Y + (size_t)I0 * K; t.ldcout = K;
-        t.M = Wi; t.N = I0; t.kdim = Wi; t.k_mode = SG_K_FULL; t.mode = SG_MODE_NEG;
-        int rc = sgemm(t, sW, sW, sY);
-        if (rc) return rc;
-        return split_row();
-    };
-    if (merge_mode == CHOL_TWO_PHASE) {
-        for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
-            const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-            int rc = fac_product(J0, J1, Jb);
-            if (!rc) rc = fac_panels(J0, J1);
-            if (rc) return rc;
-        }
-        int rc = trinv(0, nblk);   // all diagonal-block inverses at once
-        if (rc) return rc;
-        for (int I0 = 0, Ib = 0; I0 < K; I0 += NBI, ++Ib) {
-            const int I1 = (K - I0 < NBI) ? K : I0 + NBI;
-            rc = inv_product(I0, I1, Ib);
-            if (!rc) rc = inv_row(I0, I1);
-            if (rc) return rc;
-        }
-    } else {
-        // one walk over the block rows (NBO == NBI): see chol_merge_mode()
-        for (int J0 = 0, Jb = 0; J0 < K; J0 += NBO, ++Jb) {
-            const int J1 = (K - J0 < NBO) ? K : J0 + NBO;
-            int rc;
-            if (merge_mode == CHOL_WALK_MERGED && tab->row[Jb].n_items > 0) {
-                rc = g3_row(tab->row[Jb], Rpl, J0, J0, J1 - J0, K - J0, A + (size_t)J0 * K + J0, sA, G3_SUB, /*second=*/true);
-            } else {
-                rc = fac_product(J0, J1, Jb);
-                if (!rc) rc = inv_product(J0, J1, Jb);
-            }
-            if (!rc) rc = fac_panels(J0, J1);
-            if (!rc) rc = trinv(J0 / NB, (J1 - J0 + NB - 1) / NB);
-            if (!rc) rc = inv_row(J0, J1);
-            if (rc) return rc;
-        }
-    }
-    hipLaunchKernelGGL(flat_reverse_lower_to_upper_kernel, dim3((K + 255) / 256, K, nprob), dim3(256), 0, stream, U, K, sU);
+    if (int rc = c.merge_mode == CHOL_TWO_PHASE ? chol_run_two_phase(c) : chol_run_walk(c)) return rc;
+    hipLaunchKernelGGL(flat_reverse_lower_to_upper_kernel, dim3((K + 255) / 256, K, nprob), dim3(256), 0, stream, U, K, c.sY);
     QT_LAUNCH_CHECK();
     hipLaunchKernelGGL(identity_if_failed_kernel, dim3(K < 1024 ? K : 1024, 1, nprob), dim3(256), 0, stream, U, K,
-                       (const int32_t*)info, sU);
+                       (const int32_t*)info, c.sY);
     QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+// The batched entry points' argument checks (fn: the entry point, for the message; ptrs: its pointers are all there).
+static int chol_check_batch(const char* fn, bool ptrs, int K, int n_problems, int64_t strideA, int64_t strideU) {
+    QT_CHECK_ARG(K > 0 && ptrs && n_problems >= 1 && n_problems <= SG_MAX_BATCH, "%s: bad arguments (1 <= n_problems <= %d)", fn,
+                 SG_MAX_BATCH);
+    QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
+                 "%s: strides must be multiples of 4 elements and >= K*K", fn);
     return QT_OK;
 }
 
@@ -1137,10 +1132,7 @@ extern "C" int qt_cholesky_inverse_upper(float* A, int K, float* U, int32_t* inf
 extern "C" int qt_cholesky_inverse_upper_batched(float* A, int64_t strideA, int K, float* U, int64_t strideU, int32_t* info,
                                                  int n_problems, void* workspace, size_t workspace_bytes,
                                                  qt_stream_t stream_) {
-    QT_CHECK_ARG(K > 0 && A && U && info && n_problems >= 1 && n_problems <= SG_MAX_BATCH,
-                 "qt_cholesky_inverse_upper_batched: bad arguments (1 <= n_problems <= %d)", SG_MAX_BATCH);
-    QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
-                 "qt_cholesky_inverse_upper_batched: strides must be multiples of 4 elements and >= K*K");
+    if (int rc = chol_check_batch("qt_cholesky_inverse_upper_batched", A && U && info, K, n_problems, strideA, strideU)) return rc;
     return chol_run(A, strideA, K, U, strideU, info, n_problems, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
@@ -1157,10 +1149,9 @@ extern "C" int qt_cholesky_inverse_upper_bounded(float* A, int K, float* U, int3
 extern "C" int qt_cholesky_inverse_upper_batched_bounded(float* A, int64_t strideA, int K, float* U, int64_t strideU,
                                                          int32_t* info, int n_problems, const float* min_eig_lb,
                                                          void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
-    QT_CHECK_ARG(K > 0 && A && U && info && min_eig_lb && n_problems >= 1 && n_problems <= SG_MAX_BATCH,
-                 "qt_cholesky_inverse_upper_batched_bounded: bad arguments (1 <= n_problems <= %d)", SG_MAX_BATCH);
-    QT_CHECK_ARG(n_problems == 1 || (strideA >= (int64_t)K * K && strideU >= (int64_t)K * K && strideA % 4 == 0 && strideU % 4 == 0),
-                 "qt_cholesky_inverse_upper_batched_bounded: strides must be multiples of 4 elements and >= K*K");
+    if (int rc = chol_check_batch("qt_cholesky_inverse_upper_batched_bounded", A && U && info && min_eig_lb, K, n_problems,
+                                  strideA, strideU))
+        return rc;
     return chol_run(A, strideA, K, U, strideU, info, n_problems, workspace, workspace_bytes, (hipStream_t)stream_, min_eig_lb);
 }
 
@@ -1236,9 +1227,8 @@ extern "C" int qt_chol_g3_plan_check(int K, int merged, int min_chunks, long lon
         n_slabs += slabs_here;
         return 0;
     };
-    for (int J0 = 0, Jb = 0; J0 < K; J0 += NBX, ++Jb) {
-        const int J1 = (K - J0 < NBX) ? K : J0 + NBX;
-        const int Tm = (J1 - J0 + 255) / 256, Tn0 = (K - J0 + 255) / 256, Tn1 = (J0 + 255) / 256, c_end = J0 / G3_CHUNK_ROWS;
+    for (BlockRow J(K, NBX); J; ++J) {
+        const int Jb = J.Jb, Tm = J.Tm(), Tn0 = J.Tn0(), Tn1 = J.Tn1(), c_end = J.c_end();
         int rc = 0;
         if (Jb < (int)pl.row.size() && pl.row[Jb].n_items > 0) {
             if (pl.fac[Jb].n_items > 0 || pl.inv[Jb].n_items > 0) return -14;

@@ -417,7 +417,7 @@ CASES = [
     (_prepare, (2040, "prepare: one pass below the threshold (512 bytes of statistics only)")),
     (_prepare, (2048, "prepare: two passes at the threshold K = 2048 (K * K * 4 bytes for the symmetric copy)")),
     (_prepare, (2048, "prepare: QT_PREPARE_TWO_PASS=0 keeps the one-pass size at K = 2048", {"QT_PREPARE_TWO_PASS": "0"})),
-    # chol_problem_ws_bytes (cholesky.hip)
+    # CholLayout (chol_layout.h, cholesky.hip)
     (_chol, (1000, F32_CHAIN, "chain: f32 products only (no plane copies), ragged K = 1000")),
     (_chol, (1000, BF16X3_CHAIN, "chain: bf16x3 block-row products forced at small K (plane copies, slabs, item tables), K = 1000")),
     (_chol, (384, F32_CHAIN, "chain: f32, K of three 128-blocks, two outer blocks")),

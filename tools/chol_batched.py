@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """n equal-size factorisations: n single-problem chains one after another vs ONE batched chain (same stream).
 usage: chol_batched.py K n [reps]"""
+import hashlib
 import sys
 from pathlib import Path
 
@@ -21,7 +22,7 @@ Ab = torch.empty((n, K, K), dtype=torch.float32, device=dev)
 Ub = torch.empty((n, K, K), dtype=torch.float32, device=dev)
 
 
-def timed(fn):
+def timed(what, fn):
     best = 1e9
     for _ in range(reps + 1):          # first repetition: workspace allocation, item tables
         for b in range(n):
@@ -29,21 +30,23 @@ def timed(fn):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        fn()
+        info = fn()
         e1.record()
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1))
+        # for comparing two libraries (lab_run.py, QT_LAB_SO): the factors' bytes
+        print(f"K={K} n={n} {what} {e0.elapsed_time(e1):.2f} ms U sha256={hashlib.sha256(Ub.cpu().numpy()).hexdigest()} "
+              f"info={torch.cat(info).tolist() if isinstance(info, list) else info.tolist()}", flush=True)
     return best
 
 
 def singles():
-    for b in range(n):
-        ops.cholesky_inverse_upper(Ab[b], U_out=Ub[b])
+    return [ops.cholesky_inverse_upper(Ab[b], U_out=Ub[b])[1] for b in range(n)]
 
 
-t1 = timed(singles)
+t1 = timed("singles", singles)
 U1 = Ub.clone()
-t2 = timed(lambda: ops.cholesky_inverse_upper_batched(Ab, Ub))
+t2 = timed("batched", lambda: ops.cholesky_inverse_upper_batched(Ab, Ub))
 same = torch.equal(U1, Ub)
 print(f"K={K} n={n}: {n} single chains {t1:.2f} ms ({t1 / n:.2f} each) | one batched chain {t2:.2f} ms ({t2 / n:.2f} per problem) | "
       f"x{t1 / t2:.2f} | bit-identical: {same}")

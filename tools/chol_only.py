@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Cholesky-inverse chain alone (for rocprofv3 per-kernel breakdowns).  The bound on lambda_min is passed, so
 QT_CHOL_PLANES=bf16x3|f16x2 selects the plane mode of the block-row products."""
+import hashlib
 import sys
 from pathlib import Path
 
@@ -27,3 +28,5 @@ for _ in range(reps):
     e1.record()
     torch.cuda.synchronize()
     print(f"K={K} chol {e0.elapsed_time(e1):.2f} ms info={int(info.item())}", flush=True)
+    # for comparing two libraries (lab_run.py, QT_LAB_SO): the factor's bytes
+    print(f"K={K} U sha256={hashlib.sha256(U.cpu().numpy()).hexdigest()} info={info.tolist()}", flush=True)
