@@ -60,6 +60,34 @@ size_t qt_xtx_workspace_bytes(int64_t n_tokens, int K);
 int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
                       void* workspace, size_t workspace_bytes, qt_stream_t stream);
 
+/* Several Gram sums of ONE K and ONE 16-bit dtype in one launch: problem p computes
+ * G[p][K,K] (lower triangle incl. diagonal tiles) += X[p]^T X[p] for X[p] [n_tokens[p], K] with pitch ldx[p].
+ * X and G are HOST arrays of device pointers; n_problems is 1..16; the token counts may differ.  A problem with 0
+ * tokens contributes nothing and its G (and its X, ldx) is not touched; a batch without tokens launches nothing.
+ * Alignment and range rules per problem are those of qt_xtx_accumulate; no two problems may share a G.  A problem
+ * whose token count is no multiple of 64 needs ldx[p] == K (the kernel reads an item with one pitch, and the staged
+ * zero-padded tail tile has pitch K): otherwise QT_ERR_INVALID -- send that problem through qt_xtx_accumulate.
+ * Deterministic, no atomics: a (problem, tile) pair is either summed by one work item over all of the problem's
+ * token tiles and added into G from the epilogue, or by several items over disjoint token ranges whose fp32 slabs a
+ * table-driven reduction adds in ascending token order.  Which of the two, and the ranges, is a pure function of
+ * (n_tokens[], K) -- never of data or pointers -- and qt_xtx_batched_plan returns exactly the table the launch uses.
+ * A batch with one non-empty problem is handed to qt_xtx_accumulate: bit-identical to it.  In a larger batch a
+ * problem's bits may differ from its single launch (the fp32 partial sums group differently); they depend on the
+ * other problems' SIZES only, never on their data.  Precision: a pair summed by one item is ONE fp32 chain over all of
+ * the problem's tokens, so its rounding error grows with the square root of the token count (measured against the fp64
+ * Gram, K = 4096: 4.9e-6 of sqrt(G_ii G_jj) at 65 536 tokens, 1.07e-5 at 196 608, where the single launch's two-level
+ * sum stays below 1e-6).
+ * qt_xtx_batched_plan (host-only, needs no device): rows of 6 ints -- problem, ti, tj, first token tile (of 64),
+ * token tiles, slab index or -1 for an item added into G -- in launch order; writes min(*n_items, max_items) rows
+ * (items may be NULL to ask for the counts alone).  The workspace the launch needs is a property of that plan (its
+ * slabs, one staged tail tile per ragged problem, its tables), so the same call returns it in *workspace_bytes: there
+ * is no separate size function, and every out pointer may be NULL.  0 bytes for a batch without tokens. */
+int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, const int64_t* n_tokens, const int64_t* ldx, int K,
+                              float* const* G, int n_problems, void* workspace, size_t workspace_bytes,
+                              qt_stream_t stream);
+int qt_xtx_batched_plan(const int64_t* n_tokens, int n_problems, int K, int32_t* items, int max_items, int* n_items,
+                        int* n_slabs, size_t* workspace_bytes);
+
 /* The same accumulation for fp32 activations X [n_tokens, K] (an fp32 checkpoint: upstream's `inp.float()` is
  * then an fp32 Gram product).  fp32-accurate on the bf16 MFMA: the tokens are split into three
  * bf16 planes (residual <= 2^-27 |x|) and the six plane products of weight >= 2^-16 are summed in one fp32

@@ -21,6 +21,7 @@
 // the 32 resident on one XCD form a 4x8 block of tiles and all 256 of a round form a 16x16 block
 // walking the tokens together: a panel missed by one XCD's L2 is in the Infinity Cache for the rest.
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <map>
@@ -60,7 +61,41 @@ struct XtxParams {
     double* dot_partials;
     int batch_items;          // DOT: work items per problem (the grid holds n_batch problems back to back) ...
     int64_t x_batch_bytes;    // ... whose X matrices lie this many bytes apart
+    // BATCHED variant of xtx16_kernel (qt_xtx_accumulate_batched): X, tail, ldx, n_tt, has_tail and G above are unused;
+    // every workgroup reads its item and its problem from these device tables instead
+    const struct XtxBItem* b_items;   // [grid] in logical order
+    const struct XtxBProb* b_probs;   // [n_problems]
 };
+
+// Records of the batched launch (device tables in the caller's workspace, built by xtx_batched_plan on the host)
+struct XtxBItem {       // 32 B: one workgroup's work
+    int prob;           // index into the problem table
+    int tile;           // (ti << 16) | tj
+    int tt0, cnt;       // token tiles [tt0, tt0 + cnt) of the problem
+    int slab;           // fp32 slab it writes, or -1: the only item of (prob, tile), added into G
+    int pad[3];
+};
+struct XtxBProb {       // 64 B: one problem of the batch
+    const void* X;
+    const void* tail;   // its zero-padded [64, K] staging of the ragged last token tile, or null
+    float* G;
+    int64_t ldx;
+    int n_tt, has_tail;
+    int64_t pad[3];
+};
+struct XtxBRed {        // 32 B: one slabbed (problem, tile): slabs slab0 + c * stride, c = 0 .. n_chunks-1 in token order
+    int prob, tile, slab0, n_chunks, stride;
+    int pad[3];
+};
+static_assert(sizeof(XtxBItem) == 32 && sizeof(XtxBProb) == 64 && sizeof(XtxBRed) == 32, "table records");
+
+// a value every lane holds alike, kept in a scalar register whatever load the compiler chose for it
+__device__ __forceinline__ int xtx_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t xtx_uni64(uint64_t v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
 
 // Workgroup -> logical item.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share one; speed only, never
 // correctness).  Within each round of 256 consecutive blocks, the 32 blocks of one XCD take 32 consecutive logical
@@ -357,8 +392,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
 constexpr int RING16 = 10;          // units
 constexpr int DBL_BYTES = 2 * UNIT_BYTES;
 
-template <bool F16, bool DOT = false>
+//
+// BATCHED (qt_xtx_accumulate_batched): several problems of one K in one launch.  The workgroup's item (problem, tile,
+// token tiles, slab) and its problem (X, tail, G, pitch) come from two device tables, read once with wave-uniform
+// loads into locals; nothing in the by-value argument struct is indexed or modified.  No throttle.
+template <bool F16, bool DOT = false, bool BATCHED = false>
 __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
+    static_assert(!(DOT && BATCHED), "the fused product has its own batch form");
     constexpr int ND = 5;       // doubles resident in LDS
     constexpr int LEAD = 3;     // double d+LEAD is issued in phase d  (LEAD <= ND-2)
     __shared__ __attribute__((aligned(16))) char ring[RING16 * UNIT_BYTES];
@@ -377,12 +417,31 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
         logical -= prob * p.batch_items;
         Xb += (size_t)prob * (size_t)p.x_batch_bytes;
     }
-    int tt0, cnt, slab_idx;
-    const int tt_packed = xtx_item(p, logical, tt0, cnt, slab_idx);
+    int tt0, cnt, slab_idx, tt_packed;
+    const void* tailp = p.tail;
+    float* Gp = p.G;
+    int64_t ldx = p.ldx;
+    int n_tt = p.n_tt, has_tail = p.has_tail;
+    if (BATCHED) {
+        const XtxBItem* it = p.b_items + logical;
+        const XtxBProb* pr = p.b_probs + xtx_uni(it->prob);
+        tt_packed = xtx_uni(it->tile);
+        tt0 = xtx_uni(it->tt0);
+        cnt = xtx_uni(it->cnt);
+        slab_idx = xtx_uni(it->slab);
+        Xb = (const char*)xtx_uni64((uint64_t)pr->X);
+        tailp = (const void*)xtx_uni64((uint64_t)pr->tail);
+        Gp = (float*)xtx_uni64((uint64_t)pr->G);
+        ldx = (int64_t)xtx_uni64((uint64_t)pr->ldx);
+        n_tt = xtx_uni(pr->n_tt);
+        has_tail = xtx_uni(pr->has_tail);
+    } else {
+        tt_packed = xtx_item(p, logical, tt0, cnt, slab_idx);
+    }
     const int ti = tt_packed >> 16, tj = tt_packed & 0xFFFF;
     const int nd = cnt * (BKT / (2 * UT));  // doubles of this item (2 per 64-token tile)
     const int K = p.K;
-    const size_t ld2 = (size_t)p.ldx * 2;
+    const size_t ld2 = (size_t)ldx * 2;
 
     // staging: as xtx_kernel, with token-row bit 3 folded into the chunk swizzle
     const int rsub = lane >> 4;
@@ -398,11 +457,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
     const unsigned ring_lds = (unsigned)(size_t)(QT_LDS char*)ring;
     const unsigned dst_wave = __builtin_amdgcn_readfirstlane(ring_lds + (wave >> 2) * 4096 + (wave & 3) * 1024);
 
-    const bool ends_in_tail = p.has_tail && (tt0 + cnt == p.n_tt);
+    const bool ends_in_tail = has_tail && (tt0 + cnt == n_tt);
     const int d_tail = ends_in_tail ? nd - 2 : 0x7fffffff;             // first double taken from the staging
     const size_t ustride = (size_t)UT * ld2;
     auto dbl_src = [&](int d) -> const char* {
-        return d >= d_tail ? (const char*)p.tail + (size_t)(d - d_tail) * 2 * ustride
+        return d >= d_tail ? (const char*)tailp + (size_t)(d - d_tail) * 2 * ustride
                            : Xb + ((size_t)tt0 * BKT + (size_t)d * 2 * UT) * ld2;
     };
     const char* run_src = Xb + (size_t)tt0 * BKT * ld2;
@@ -525,7 +584,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
                 for (int r = 0; r < 4; ++r) {
                     const int gi = ti * BT + wave_m * 128 + ai * 16 + ih + r;
                     if (gi < K && gj < K) {
-                        float* dst = p.G + (size_t)gi * K + gj;
+                        float* dst = Gp + (size_t)gi * K + gj;
                         *dst = *dst + acc[ai][bj][r];
                     }
                 }
@@ -955,6 +1014,316 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
         return launch(ptp, pt);
     }
     return launch(p, pl);
+}
+
+// ---- several Gram sums of one K in one launch ---------------------------------------------------------
+namespace {
+
+// xtx_reduce_kernel driven by a table: G[prob][tile] += sum_c slab[slab0 + c * stride], ascending c = ascending tokens
+__global__ __launch_bounds__(256) void xtx_reduce_batched_kernel(const float* __restrict__ slabs,
+                                                                 const XtxBRed* __restrict__ reds,
+                                                                 const XtxBProb* __restrict__ probs, int K) {
+    const XtxBRed* rd = reds + blockIdx.x;
+    const int tt_packed = xtx_uni(rd->tile), slab0 = xtx_uni(rd->slab0), n_chunks = xtx_uni(rd->n_chunks),
+              stride = xtx_uni(rd->stride);
+    float* G = (float*)xtx_uni64((uint64_t)probs[xtx_uni(rd->prob)].G);
+    const int ti = tt_packed >> 16, tj = tt_packed & 0xFFFF;
+    const int part = blockIdx.y;  // 16 parts of 16 rows
+    const size_t tile_elems = (size_t)BT * BT;
+    for (int e = threadIdx.x; e < 16 * (BT / 4); e += blockDim.x) {
+        const int i_loc = part * 16 + e / (BT / 4);
+        const int j_loc = (e % (BT / 4)) * 4;
+        const int gi = ti * BT + i_loc, gj = tj * BT + j_loc;
+        if (gi >= K || gj >= K) continue;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < n_chunks; ++c) {
+            const f32x4 v = *(const f32x4*)(slabs + ((size_t)slab0 + (size_t)c * stride) * tile_elems +
+                                            (size_t)i_loc * BT + j_loc);
+            s += v;
+        }
+        float* dst = G + (size_t)gi * K + gj;
+        if (gj + 3 < K) {
+            f32x4 o = *(f32x4*)dst;
+            o += s;
+            *(f32x4*)dst = o;
+        } else {
+            for (int c = 0; c < 4 && gj + c < K; ++c) dst[c] += s[c];
+        }
+    }
+}
+
+constexpr int XTX_BATCH_MAX = 16;
+constexpr int XTX_MIN_CHUNK = 4;     // token tiles: no problem is cut into chunks shorter than this
+
+struct XtxBPlan {
+    int single = -1;                 // >= 0: the only problem with tokens -- the launch delegates to qt_xtx_accumulate
+    std::vector<XtxBItem> items;     // logical order
+    std::vector<XtxBRed> reds;
+    int n_slabs = 0, n_ragged = 0;
+    int tail_slot[XTX_BATCH_MAX];    // which staged tail tile a ragged problem owns, or -1
+    size_t slab_bytes = 0, tail_bytes = 0, tail_stride = 0, tab_bytes = 0;
+    size_t item_off = 0, prob_off = 0, red_off = 0;     // byte offsets inside the table blob
+    size_t need = 0;                 // workspace bytes, the 256 of alignment slack included
+};
+
+// chunks a problem of n_tt token tiles is cut into for chunk length L: none shorter than XTX_MIN_CHUNK
+int xtx_chunks_for(int n_tt, int L) { return std::max(1, std::min((n_tt + L - 1) / L, n_tt / XTX_MIN_CHUNK)); }
+
+// The planner: a pure function of (n_tokens[], K) (and of QT_XTX_ORDER, as the single plan is).  Both
+// qt_xtx_batched_plan and qt_xtx_accumulate_batched go through it.
+//
+// One problem with tokens: xtx_plan's own items (the launch hands that problem to qt_xtx_accumulate).
+// Otherwise: the (problem, tile) pairs, longest problem first and a problem's tiles in table order, so that the 32
+// items an XCD takes share a problem and panels.  As in xtx_plan, whole rounds of 256 pairs are DIRECT items (all of
+// the problem's tokens, added into G); no direct item may be longer than the whole launch's ideal makespan (work /
+// 256), a longer one is cut to that length.  The pairs after the last whole round -- the shortest problems' -- are cut
+// with ONE chunk length L, picked by xtx_plan's rounds-times-length cost; a problem no longer than L stays one
+// (direct) item.  Slabs are capped at 1 GiB.  Within a problem the items go chunk by chunk, tiles inside a chunk.
+int xtx_batched_plan(const int64_t* n_tokens, int n_problems, int K, XtxBPlan& pl) {
+    const int nt = (K + BT - 1) / BT;
+    const int n_tiles = nt * (nt + 1) / 2;
+    std::vector<int> tab;
+    xtx_tile_order(nt, tab);
+    if ((int)tab.size() != n_tiles) return QT_ERR_INVALID;
+    std::vector<int> act;
+    int n_tt[XTX_BATCH_MAX];
+    for (int p = 0; p < n_problems; ++p) {
+        n_tt[p] = (int)((n_tokens[p] + BKT - 1) / BKT);
+        pl.tail_slot[p] = -1;
+        if (n_tokens[p] > 0) act.push_back(p);
+        if (n_tokens[p] % BKT != 0) pl.tail_slot[p] = pl.n_ragged++;
+    }
+    if (act.empty()) return QT_OK;
+    auto emit = [&](int p, int c, int t_lo, int t_hi) {   // tiles [t_lo, t_hi) of the table, c chunks of problem p
+        if (t_lo >= t_hi) return;
+        const int base_cnt = n_tt[p] / c, rem = n_tt[p] % c, width = t_hi - t_lo;
+        const int slab_base = pl.n_slabs;
+        for (int ch = 0; ch < c; ++ch)
+            for (int t = t_lo; t < t_hi; ++t) {
+                XtxBItem it = {};
+                it.prob = p;
+                it.tile = tab[t];
+                it.tt0 = ch * base_cnt + std::min(ch, rem);
+                it.cnt = base_cnt + (ch < rem ? 1 : 0);
+                it.slab = c > 1 ? pl.n_slabs++ : -1;
+                pl.items.push_back(it);
+            }
+        if (c > 1)
+            for (int t = t_lo; t < t_hi; ++t) {
+                XtxBRed rd = {};
+                rd.prob = p;
+                rd.tile = tab[t];
+                rd.slab0 = slab_base + (t - t_lo);
+                rd.n_chunks = c;
+                rd.stride = width;
+                pl.reds.push_back(rd);
+            }
+    };
+    if (act.size() == 1) {
+        const int p = act[0];
+        pl.single = p;
+        const XtxPlan sp = xtx_plan(n_tokens[p], K);
+        emit(p, 1, 0, sp.n_direct);
+        emit(p, sp.s2, sp.n_direct, sp.n_direct + sp.n_rem);
+    } else {
+        std::stable_sort(act.begin(), act.end(), [&](int a, int b) { return n_tt[a] > n_tt[b]; });
+        const int64_t n_pairs = (int64_t)act.size() * n_tiles;
+        const int64_t n_whole = n_pairs / NUM_CU * NUM_CU;      // pairs [0, n_whole): direct rounds
+        int64_t work = 0;
+        for (int p : act) work += (int64_t)n_tiles * n_tt[p];
+        const int l_cap = (int)std::max<int64_t>(XTX_MIN_CHUNK, (work + NUM_CU - 1) / NUM_CU);
+        // tiles of the problem of rank a that lie in the direct rounds
+        auto whole_of = [&](size_t a) {
+            return (int)std::max<int64_t>(0, std::min<int64_t>(n_tiles, n_whole - (int64_t)a * n_tiles));
+        };
+        int64_t slabs_whole = 0;
+        for (size_t a = 0; a < act.size(); ++a) {
+            const int c = xtx_chunks_for(n_tt[act[a]], l_cap);
+            if (c > 1) slabs_whole += (int64_t)c * whole_of(a);
+        }
+        // chunk length of the remainder: S = 1 is "every pair one item"
+        const int64_t slab_cap = ((int64_t)1 << 30) / ((int64_t)BT * BT * 4);
+        int max_rem = 0;
+        for (size_t a = 0; a < act.size(); ++a)
+            if (whole_of(a) < n_tiles) max_rem = std::max(max_rem, n_tt[act[a]]);
+        int best_L = std::max(max_rem, 1);
+        double best_cost = 0.0;
+        for (int S = 1; S <= 64 && max_rem > 0; ++S) {
+            const int L = (max_rem + S - 1) / S;
+            if (S > 1 && L < XTX_MIN_CHUNK) break;
+            int64_t n_items = 0, n_slabs = 0;
+            int longest = 0;
+            for (size_t a = 0; a < act.size(); ++a) {
+                const int r = n_tiles - whole_of(a);
+                if (r == 0) continue;
+                const int c = xtx_chunks_for(n_tt[act[a]], L);
+                n_items += (int64_t)c * r;
+                if (c > 1) n_slabs += (int64_t)c * r;
+                longest = std::max(longest, (n_tt[act[a]] + c - 1) / c);
+            }
+            if (slabs_whole + n_slabs > slab_cap) break;
+            const double cost = (double)((n_items + NUM_CU - 1) / NUM_CU) * longest;
+            if (S == 1 || cost < best_cost * 0.97) {
+                best_cost = cost;
+                best_L = L;
+            }
+        }
+        if (slabs_whole > slab_cap) return QT_ERR_UNSUPPORTED;   // cannot happen below 16 problems (fewer than 512 slabs)
+        for (size_t a = 0; a < act.size(); ++a)
+            emit(act[a], xtx_chunks_for(n_tt[act[a]], l_cap), 0, whole_of(a));
+        for (size_t a = 0; a < act.size(); ++a)
+            emit(act[a], xtx_chunks_for(n_tt[act[a]], best_L), whole_of(a), n_tiles);
+    }
+    pl.slab_bytes = (size_t)pl.n_slabs * BT * BT * 4;
+    pl.tail_stride = qt_align_up((size_t)BKT * K * 2, 256);
+    pl.tail_bytes = (size_t)pl.n_ragged * pl.tail_stride;
+    pl.item_off = 0;
+    pl.prob_off = pl.item_off + pl.items.size() * sizeof(XtxBItem);
+    pl.red_off = pl.prob_off + (size_t)n_problems * sizeof(XtxBProb);
+    pl.tab_bytes = qt_align_up(pl.red_off + pl.reds.size() * sizeof(XtxBRed), 256);
+    pl.need = pl.single >= 0 ? qt_xtx_workspace_bytes(n_tokens[pl.single], K)
+                             : pl.slab_bytes + pl.tail_bytes + pl.tab_bytes + 256;
+    return QT_OK;
+}
+
+int xtx_batched_args_ok(const char* fn, const int64_t* n_tokens, int n_problems, int K) {
+    QT_CHECK_ARG(n_problems >= 1 && n_problems <= XTX_BATCH_MAX, "%s: n_problems=%d must be 1..%d", fn, n_problems,
+                 XTX_BATCH_MAX);
+    QT_CHECK_ARG(n_tokens != nullptr, "%s: null n_tokens", fn);
+    QT_CHECK_ARG(K > 0 && K % 8 == 0, "%s: K=%d must be a positive multiple of 8", fn, K);
+    for (int p = 0; p < n_problems; ++p) {
+        QT_CHECK_ARG(n_tokens[p] >= 0, "%s: n_tokens[%d] < 0", fn, p);
+        QT_CHECK_ARG(n_tokens[p] < ((int64_t)1 << 36), "%s: n_tokens[%d] too large", fn, p);
+    }
+    return QT_OK;
+}
+
+}  // namespace
+
+extern "C" int qt_xtx_batched_plan(const int64_t* n_tokens, int n_problems, int K, int32_t* items, int max_items,
+                                   int* n_items, int* n_slabs, size_t* workspace_bytes) {
+    if (n_items) *n_items = 0;
+    if (n_slabs) *n_slabs = 0;
+    if (workspace_bytes) *workspace_bytes = 0;
+    const int rc = xtx_batched_args_ok("qt_xtx_batched_plan", n_tokens, n_problems, K);
+    if (rc != QT_OK) return rc;
+    XtxBPlan pl;
+    const int prc = xtx_batched_plan(n_tokens, n_problems, K, pl);
+    if (prc != QT_OK) {
+        qt_set_error("qt_xtx_batched_plan: no plan for K=%d", K);
+        return prc;
+    }
+    if (n_items) *n_items = (int)pl.items.size();
+    if (n_slabs) *n_slabs = pl.n_slabs;
+    if (workspace_bytes) *workspace_bytes = pl.need;      // what qt_xtx_accumulate_batched checks its workspace against
+    for (int i = 0; items && i < max_items && i < (int)pl.items.size(); ++i) {
+        const XtxBItem& it = pl.items[i];
+        int32_t* row = items + (size_t)i * 6;
+        row[0] = it.prob;
+        row[1] = it.tile >> 16;
+        row[2] = it.tile & 0xFFFF;
+        row[3] = it.tt0;
+        row[4] = it.cnt;
+        row[5] = it.slab;
+    }
+    return QT_OK;
+}
+
+extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, const int64_t* n_tokens, const int64_t* ldx,
+                                         int K, float* const* G, int n_problems, void* workspace, size_t workspace_bytes,
+                                         qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* fn = "qt_xtx_accumulate_batched";
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "%s: x_dtype %d must be QT_BF16 or QT_F16", fn, x_dtype);
+    const int arc = xtx_batched_args_ok(fn, n_tokens, n_problems, K);
+    if (arc != QT_OK) return arc;
+    QT_CHECK_ARG(X && G && ldx, "%s: null array", fn);
+    for (int p = 0; p < n_problems; ++p) {
+        if (n_tokens[p] == 0) continue;
+        QT_CHECK_ARG(X[p] && G[p], "%s: null pointer in problem %d", fn, p);
+        QT_CHECK_ARG(ldx[p] >= K && ldx[p] % 8 == 0, "%s: ldx[%d]=%lld must be >= K and a multiple of 8", fn, p,
+                     (long long)ldx[p]);
+        QT_CHECK_ARG(((uintptr_t)X[p] & 15) == 0 && ((uintptr_t)G[p] & 15) == 0,
+                     "%s: X[%d] and G[%d] must be 16-byte aligned", fn, p, p);
+        QT_CHECK_ARG((uint64_t)ldx[p] * 2 * UT + (uint64_t)K * 2 < ((uint64_t)1 << 32), "%s: ldx[%d] too large", fn, p);
+        // an item is read with ONE pitch, and the staged tail tile has pitch K
+        QT_CHECK_ARG(n_tokens[p] % BKT == 0 || ldx[p] == K,
+                     "%s: problem %d has a ragged token count (%lld %% 64 != 0) and ldx=%lld != K=%d; "
+                     "send it through qt_xtx_accumulate", fn, p, (long long)n_tokens[p], (long long)ldx[p], K);
+        for (int q = 0; q < p; ++q)
+            QT_CHECK_ARG(n_tokens[q] == 0 || G[q] != G[p], "%s: problems %d and %d share one G", fn, q, p);
+    }
+    XtxBPlan pl;
+    const int prc = xtx_batched_plan(n_tokens, n_problems, K, pl);
+    if (prc != QT_OK) {
+        qt_set_error("%s: no plan for K=%d", fn, K);
+        return prc;
+    }
+    if (pl.items.empty()) return QT_OK;
+    if (workspace_bytes < pl.need || !workspace) {
+        qt_set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, pl.need);
+        return QT_ERR_WORKSPACE;
+    }
+    if (pl.single >= 0) {
+        const int p = pl.single;
+        return qt_xtx_accumulate(X[p], x_dtype, n_tokens[p], K, ldx[p], G[p], workspace, workspace_bytes, stream_);
+    }
+    char* ws = (char*)qt_align_up((size_t)workspace, 256);
+    float* slabs = (float*)ws;
+    char* tails = ws + pl.slab_bytes;
+    char* tabs = tails + pl.tail_bytes;
+    // the tables: built in pageable host memory of this call and uploaded by ONE copy.  A pageable source is staged by
+    // the runtime before hipMemcpyAsync returns, so this call's vector may die and no later call can rewrite what an
+    // earlier copy still reads (the hazard of a pinned buffer reused across calls).
+    std::vector<char> blob(pl.tab_bytes, 0);
+    memcpy(blob.data() + pl.item_off, pl.items.data(), pl.items.size() * sizeof(XtxBItem));
+    XtxBProb* probs = (XtxBProb*)(blob.data() + pl.prob_off);
+    for (int p = 0; p < n_problems; ++p) {
+        XtxBProb& r = probs[p];
+        r.X = n_tokens[p] ? X[p] : nullptr;
+        r.G = n_tokens[p] ? G[p] : nullptr;
+        r.ldx = n_tokens[p] ? ldx[p] : K;
+        r.n_tt = (int)((n_tokens[p] + BKT - 1) / BKT);
+        r.has_tail = pl.tail_slot[p] >= 0;
+        r.tail = r.has_tail ? tails + (size_t)pl.tail_slot[p] * pl.tail_stride : nullptr;
+    }
+    if (!pl.reds.empty()) memcpy(blob.data() + pl.red_off, pl.reds.data(), pl.reds.size() * sizeof(XtxBRed));
+    QT_HIP(hipMemcpyAsync(tabs, blob.data(), pl.tab_bytes, hipMemcpyHostToDevice, stream));
+    if (pl.n_ragged > 0) {
+        QT_HIP(hipMemsetAsync(tails, 0, pl.tail_bytes, stream));
+        for (int p = 0; p < n_problems; ++p) {
+            if (pl.tail_slot[p] < 0) continue;
+            const int64_t full = n_tokens[p] / BKT * BKT;
+            QT_HIP(hipMemcpyAsync(tails + (size_t)pl.tail_slot[p] * pl.tail_stride,
+                                  (const char*)X[p] + (size_t)full * K * 2, (size_t)(n_tokens[p] - full) * K * 2,
+                                  hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    XtxParams q = {};
+    q.K = K;
+    q.slabs = slabs;
+    {
+        const char* e = getenv("QT_XTX_MAP");
+        q.map_mode = e ? atoi(e) : 0;
+    }
+    q.thr_win = 128;
+    q.thr_nap = 127;
+    q.thr_chk = 32;
+    q.batch_items = 1;
+    q.b_items = (const XtxBItem*)(tabs + pl.item_off);
+    q.b_probs = (const XtxBProb*)(tabs + pl.prob_off);
+    const int grid = (int)pl.items.size();
+    qt_prof_mark(QT_PROF_XTX, stream);
+    if (x_dtype == QT_F16) hipLaunchKernelGGL((xtx16_kernel<true, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
+    else hipLaunchKernelGGL((xtx16_kernel<false, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
+    qt_prof_mark(QT_PROF_XTX, stream);
+    QT_LAUNCH_CHECK();
+    if (!pl.reds.empty()) {
+        hipLaunchKernelGGL(xtx_reduce_batched_kernel, dim3((unsigned)pl.reds.size(), 16), dim3(256), 0, stream,
+                           (const float*)slabs, (const XtxBRed*)(tabs + pl.red_off), q.b_probs, K);
+        QT_LAUNCH_CHECK();
+    }
+    return QT_OK;
 }
 
 // ---- internal: loss = scale * <H, X^T X>_F without materialising X^T X (awq.hip) -----------------------------

@@ -147,6 +147,51 @@ class HessianAccumulator:
             if here is not None:
                 self._flushed = (here, here.record_event())
 
+    @staticmethod
+    def flush_many(accs) -> None:
+        """``flush()`` for every accumulator of ``accs``.  With ``QT_XTX_BATCHED=1`` (read per call; default ``0``)
+        those that share ``(K, 16-bit dtype, device)`` and hold staged tokens are folded in by ONE batched Gram launch
+        over their staging buffers (``ops.xtx_accumulate_batched``; runs of at most 16).  Everything else is flushed
+        alone, exactly as ``flush()`` does it: fp32 accumulators, the only member of its group, and any group with a
+        member whose flush ``QT_XTX_LAUNCH_TOKENS`` would split.  Off, this is the loop ``for acc in accs:
+        acc.flush()``.
+
+        Streams, as the class docstring promises for ``flush``: the flushing (current) stream first waits for every
+        member's staging stream and for every member's earlier flush, and every member then records ``(stream, event)``
+        of the shared launch in ``_flushed``."""
+        accs = list(accs)
+        groups: dict = {}
+        if batched_flush_enabled():
+            limit = _launch_token_limit()
+            for acc in accs:
+                # anything else that can flush() (a stand-in with the accumulator's contract) is flushed alone
+                if isinstance(acc, HessianAccumulator) and acc._fill and acc.dtype in (torch.bfloat16, torch.float16):
+                    groups.setdefault((acc.K, acc.dtype, acc._G.device), []).append(acc)
+            groups = {k: g for k, g in groups.items()
+                      if len(g) > 1 and not (limit > 0 and any(a._fill > limit for a in g))}
+        together = {id(a) for g in groups.values() for a in g}
+        for acc in accs:
+            if id(acc) not in together:
+                acc.flush()
+        for (_, _, device), group in groups.items():
+            here = torch.cuda.current_stream(device) if device.type == "cuda" else None
+            for b0 in range(0, len(group), ops.XTX_BATCH_MAX):
+                run = group[b0:b0 + ops.XTX_BATCH_MAX]
+                if len(run) == 1:
+                    run[0].flush()
+                    continue
+                for acc in run:
+                    if here is not None and acc._staged_on is not None and here != acc._staged_on:
+                        here.wait_stream(acc._staged_on)
+                    acc._after_flush()
+                ops.xtx_accumulate_batched([acc._stage[:acc._fill] for acc in run], [acc._G for acc in run])
+                event = here.record_event() if here is not None else None
+                for acc in run:
+                    acc._fill = 0
+                    acc._staged_on = None
+                    if here is not None:
+                        acc._flushed = (here, event)
+
     def release_stage(self) -> None:
         self.flush()
         self._stage = None
@@ -157,6 +202,17 @@ class HessianAccumulator:
         self._staged_on = self._flushed = None
         self._G.zero_()
         self.n = 0
+
+
+flush_accumulators = HessianAccumulator.flush_many      # the sequential driver's name for it
+
+
+def batched_flush_enabled() -> bool:
+    """``QT_XTX_BATCHED=1``: ``HessianAccumulator.flush_many`` folds accumulators of equal K in by one batched Gram
+    launch.  Off by default: a batched problem's fp32 sums group differently from its single launch."""
+    import os
+
+    return os.environ.get("QT_XTX_BATCHED", "0") == "1"
 
 
 def _launch_token_limit() -> int:

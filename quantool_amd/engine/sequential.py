@@ -19,7 +19,7 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from .gptq_linear import HessianAccumulator, batch_chains_enabled, batchable, gptq_quantize_batched
+from .gptq_linear import HessianAccumulator, batch_chains_enabled, batchable, flush_accumulators, gptq_quantize_batched
 from .modifiers import GPTQModifier, select_modifiers
 from .streams import GroupStreams
 
@@ -686,8 +686,7 @@ def _calibrate_layer(layer: nn.Module, linears: Dict[str, nn.Module], cache: Lis
             pass
     for hk in hooks:
         hk.remove()
-    for acc in accs.values():
-        acc.flush()
+    flush_accumulators(accs.values())       # HessianAccumulator.flush_many
     return leaders, accs
 
 

@@ -147,6 +147,86 @@ def xtx_accumulate(X: torch.Tensor, G: torch.Tensor) -> None:
                                                      ws.numel(), _stream()))
 
 
+XTX_BATCH_MAX = 16      # problems per qt_xtx_accumulate_batched call
+
+
+def xtx_batched_plan(n_tokens, K: int):
+    """The item table ``qt_xtx_accumulate_batched`` would launch for these token counts (host only, no device):
+    ``(items, n_slabs)``, ``items`` a list of ``(problem, ti, tj, first token tile, token tiles, slab or -1)``."""
+    import ctypes
+
+    lib = load()
+    n = len(n_tokens)
+    counts = (ctypes.c_int64 * n)(*[int(t) for t in n_tokens])
+    n_items, n_slabs = ctypes.c_int(0), ctypes.c_int(0)
+    check("qt_xtx_batched_plan", lib.qt_xtx_batched_plan(counts, n, K, None, 0, ctypes.byref(n_items),
+                                                         ctypes.byref(n_slabs), None))
+    rows = (ctypes.c_int32 * (6 * max(1, n_items.value)))()
+    check("qt_xtx_batched_plan", lib.qt_xtx_batched_plan(counts, n, K, rows, n_items.value, ctypes.byref(n_items),
+                                                         ctypes.byref(n_slabs), None))
+    return [tuple(rows[6 * i:6 * i + 6]) for i in range(n_items.value)], n_slabs.value
+
+
+def xtx_batched_workspace_bytes(n_tokens, K: int) -> int:
+    """Workspace bytes ``qt_xtx_accumulate_batched`` needs for these token counts: a property of its plan, returned by
+    ``qt_xtx_batched_plan`` (host only)."""
+    import ctypes
+
+    n = len(n_tokens)
+    counts = (ctypes.c_int64 * n)(*[int(t) for t in n_tokens])
+    need = ctypes.c_size_t(0)
+    check("qt_xtx_batched_plan", load().qt_xtx_batched_plan(counts, n, K, None, 0, None, None, ctypes.byref(need)))
+    return int(need.value)
+
+
+def xtx_accumulate_batched(Xs, Gs) -> None:
+    """``Gs[p]`` [K, K] fp32 (lower triangle) += ``Xs[p]``^T ``Xs[p]`` for every p, in one launch per 16 problems.
+    One K, one 16-bit dtype and one device for the whole list; the token counts may differ.  Empty inputs are dropped;
+    a strided input with a ragged token count (which the batched entry point refuses) goes through
+    ``xtx_accumulate``.  Bits: see ``qt_xtx_accumulate_batched`` in the header."""
+    import ctypes
+
+    lib = load()
+    Xs, Gs = list(Xs), list(Gs)
+    if len(Xs) != len(Gs):
+        raise ValueError(f"{len(Xs)} inputs for {len(Gs)} Gram matrices")
+    if not Xs:
+        return
+    xdt = _act16(Xs[0], "Xs[0]")
+    K = Gs[0].shape[0]
+    batch = []
+    for i, (X, G) in enumerate(zip(Xs, Gs)):
+        if _act16(X, f"Xs[{i}]") != xdt:
+            raise TypeError(f"Xs[{i}] is {X.dtype}, Xs[0] is {Xs[0].dtype}: one dtype per batch")
+        _req(G, torch.float32, f"Gs[{i}]", 2)
+        if tuple(G.shape) != (K, K) or not G.is_contiguous():
+            raise ValueError(f"Gs[{i}] must be contiguous [{K}, {K}], got {tuple(G.shape)}")
+        if X.shape[-1] != K:
+            raise ValueError(f"Xs[{i}] last dim {X.shape[-1]} != K {K}")
+        if X.device != Xs[0].device or G.device != Xs[0].device:
+            raise ValueError(f"problem {i} is not on {Xs[0].device}: one device per batch")
+        if any(G.data_ptr() == g.data_ptr() for _, g in batch):
+            raise ValueError(f"Gs[{i}] is also an earlier problem's Gram matrix")
+        X2 = _rows16(X.reshape(-1, K))
+        n = X2.shape[0]
+        if n == 0:
+            continue
+        if n % 64 and n > 1 and X2.stride(0) != K:
+            xtx_accumulate(X2, G)           # ragged and strided: two launches of the single entry point
+            continue
+        batch.append((X2, G))
+    for b0 in range(0, len(batch), XTX_BATCH_MAX):
+        part = batch[b0:b0 + XTX_BATCH_MAX]
+        m = len(part)
+        counts = (ctypes.c_int64 * m)(*[x.shape[0] for x, _ in part])
+        pitches = (ctypes.c_int64 * m)(*[x.stride(0) if x.shape[0] > 1 else K for x, _ in part])
+        xp = (ctypes.c_void_p * m)(*[x.data_ptr() for x, _ in part])
+        gp = (ctypes.c_void_p * m)(*[g.data_ptr() for _, g in part])
+        ws = workspace(xtx_batched_workspace_bytes([x.shape[0] for x, _ in part], K), Xs[0].device, "xtx_batched")
+        check("qt_xtx_accumulate_batched", lib.qt_xtx_accumulate_batched(xp, xdt, counts, pitches, K, gp, m, ws.data_ptr(),
+                                                                         ws.numel(), _stream()))
+
+
 def xtx_accumulate_f32(X: torch.Tensor, G: torch.Tensor) -> None:
     """G[K,K] fp32 (lower triangle) += X^T X for fp32 X[..., K]: the fp32-accurate three-plane product (an fp32
     checkpoint's activations, which upstream accumulates as `inp.float()`)."""
