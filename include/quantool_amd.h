@@ -754,11 +754,50 @@ int qt_moe_gemm_wq_wide(const void* X, int x_dtype, int K, int64_t ldx, const in
 #define QT_MOE_WQ_WIDE_MAX_E 4096
 #define QT_MOE_WQ_WIDE_MAX_SLOTS 65535
 
+/* ---- evaluation: the LM head and its cross-entropy, logits never stored ------------------------------------------
+ * qt_lm_head_nll: for every row m of H [M, K] (the final hidden states, row pitch ldh) and W [V, K] (the LM-head
+ *   weight, row pitch ldw), both bf16 or both fp16 (dtype), with x[m, v] = sum_k H[m, k] W[v, k] in an fp32
+ *   accumulator:
+ *     lse[m]    = log sum_v exp(x[m, v])
+ *     tgt[m]    = x[m, targets[m]], the fp32 accumulator of the target column, to the bit
+ *     argmax[m] = the lowest v of maximal x[m, v]
+ *     nll[m]    = lse[m] - tgt[m]
+ *   targets is [M] int32 (target_bytes 4) or int64 (target_bytes 8).  targets[m] < 0 (the ignore index): nll[m] = 0 and
+ *   tgt[m] = 0; lse[m] and argmax[m] are still written.  targets[m] >= V: nll[m] and tgt[m] are NaN -- the host cannot
+ *   see device targets without a sync, so the kernel says it.  The [M, V] logits are never written: a 256 x 256 tile
+ *   of them lives in the accumulators of one workgroup (the LDS-ring pipeline over K, v_mfma_f32_32x32x16_bf16 / _f16),
+ *   whose epilogue masks columns >= V to -inf and leaves one record {max, sum of exp(x - max), argmax} per row and
+ *   vocabulary tile in the workspace; a second kernel merges a row's records.
+ *   Contract: the k order of one accumulator is fixed (ascending 64-element K-tiles, four MFMA k-steps each), and so
+ *   is the tree that combines a row's columns: the lane's two columns (c, c + 128 of the tile), the 32 lanes by the
+ *   xor steps 16, 8, 4, 2, 1, the four column waves in ascending order, the vocabulary tiles in ascending order, each
+ *   by m = max(m1, m2), s = s1 exp(m1 - m) + s2 exp(m2 - m) with the lower columns first, ties of the maximum going
+ *   to the lower index; lse = m + logf(s).  Row m's four outputs depend only on H[m, :], W, V, K and targets[m] -- not
+ *   on M, the row's index, the pitches or the alignment of H.  Deterministic, no atomics.
+ *   Workspace: qt_lm_head_nll_workspace_size(M, V) = 16 M ceil(V / 256) bytes of records + 4 M bytes of target
+ *   logits, 16-byte aligned; a short, NULL or misaligned workspace is QT_ERR_WORKSPACE with nothing launched.
+ *   M = 0 returns QT_OK and touches nothing.  QT_ERR_INVALID before any launch, with qt_last_error naming the argument:
+ *   a dtype that is not bf16 or fp16 (fp32 operands are not taken); K not a multiple of QT_LM_HEAD_K_UNIT = 128,
+ *   below QT_LM_HEAD_MIN_K = 128 (the smallest K the ring's prologue and drain take: one trip round its eight slots)
+ *   or above QT_LM_HEAD_MAX_K = 32768; ldh < K or ldw < K; a pitch that is not a multiple of 8 elements or exceeds 2^22
+ *   elements, or a base of H or W that is not 16-byte aligned; V < 1; M < 0 or M > INT32_MAX; a target_bytes that is
+ *   neither 4 nor 8; a NULL H, W, targets, nll, lse, tgt or argmax.  Tile rows past M and vocabulary rows past V are
+ *   fetched clamped (row M - 1, row V - 1), computed and never stored: no byte outside H [M, K], W [V, K] and
+ *   targets [M] is read, nothing outside the four outputs [M] and the workspace is written.
+ *   (csrc/lm_head_nll.hip) */
+#define QT_LM_HEAD_K_UNIT 128
+#define QT_LM_HEAD_MIN_K 128
+#define QT_LM_HEAD_MAX_K 32768
+size_t qt_lm_head_nll_workspace_size(int64_t M, int V);
+int qt_lm_head_nll(const void* H, int64_t ldh, const void* W, int64_t ldw, int dtype, int64_t M, int K, int V,
+                   const void* targets, int target_bytes, float* nll, float* lse, float* tgt, int32_t* argmax,
+                   void* workspace, size_t workspace_bytes, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch
  * count since the last read, and resets the slot. */
-enum qt_prof_kernel { QT_PROF_XTX = 0, QT_PROF_SWEEP_BLOCK = 1, QT_PROF_NUM_KERNELS = 2 };
+enum qt_prof_kernel { QT_PROF_XTX = 0, QT_PROF_SWEEP_BLOCK = 1, QT_PROF_LM_HEAD_NLL = 2, QT_PROF_NUM_KERNELS = 3 };
 int qt_profile_enable(int on);
 int qt_profile_read(int kernel_id, double* total_ms, int64_t* launches);
 

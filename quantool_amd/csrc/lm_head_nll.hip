@@ -1,0 +1,388 @@
+// qt_lm_head_nll: the LM head and its cross-entropy in one pass -- per-token NLL, log-sum-exp, target logit and argmax
+// of H[M, K] x W[V, K]^T with the [M, V] logits never stored (include/quantool_amd.h).  Two kernels:
+// lm_head_nll_kernel (a 256 x 256 logit tile per 8-wave workgroup, the reduction streamed through the LDS-DMA ring of
+// ring_pipe.h, a softmax epilogue on the fp32 accumulators that leaves one {max, sum, argmax} record per row and
+// vocabulary tile) and lm_head_reduce_kernel (one thread per row merges the row's records in ascending tile order).
+//
+// THE INSTANCE.  Both operands are 16-bit and K-contiguous (H rows, W rows), the operand layout of gemm_i8_ring_kernel
+// (qlinear_ring.hip), so the unit order, the swizzle and the tile walk are i8_ring_tile.h's: a unit is a HALF PANEL of
+// 128 rows x 128 k-bytes = 64 elements of k = 16 KiB, one cache line per row and fetch, two LDS-DMA instructions per
+// wave.  K-tile t (elements [64 t, 64 t + 64)) is the four units 4t .. 4t+3 = A0, B0, B1, A1 (rows 0-127 / 128-255 of
+// the tile's H and W panels), and its four phases are the quadrants A0 x B0, A0 x B1, A1 x B0, A1 x B1 of the logit
+// tile over that k-range: per wave (2 (M) x 4 (N) waves per quadrant, 64 x 32 logits each) 2 x 1 MFMA tiles x 4 k-steps
+// = 8 v_mfma_f32_32x32x16_bf16 / _f16.  A fragment (lane l: row l & 31 of its MFMA tile, the 8 elements at k-step s,
+// half l >> 5) is the 16-byte chunk 2 s + (l >> 5) of its row: byte for byte the fragment of the int8 instance, so the
+// LDS image and the read geometry are the same.  Fragments stay in registers across the phases that share them: phase
+// 4t reads A0 and B0, 4t+1 B1, 4t+2 A1, 4t+3 nothing.
+//   R 8 slots (slot = unit % 8: two K-tiles), L 6 (unit u+6 is issued in phase u), N 2 per wave.
+//   K is a multiple of 128 elements, so the unit count nu = K / 16 is a multiple of 8, at least 8: every trip round the
+//   ring is whole, and the last trip is the one that issues nothing past nu (the drain ladder).
+//   RAW: unit i is first read in phase i - 1 at the earliest (B0, B1, A1; A0 in phase i), so the counted wait of phase
+//        u leaves only units u+3 .. u+6 in flight: vmcnt(2 * 4 = 8), and unit u+2 is read one phase after the wait
+//        that retired it.  The prologue issues units 0 .. 5 and waits vmcnt(8): units 0 and 1 have landed in front of
+//        the stagger's first barrier.  In the last trip the wait is ring_drain_wait<2, 5>(nu - u - 3): exactly the
+//        units behind u+2 that exist stay in flight, and the last three phases wait vmcnt(0).
+//   WAR: unit i is last read in phase i at the latest (its reads retire at the lgkmcnt(0) that opens MATH(i)), and its
+//        slot is re-filled by unit i+8, issued in phase i+2: ring_pipe.h's case L = R - 2.
+//   THE EPILOGUE re-uses the first 13 KiB of the ring (targets, per-N-wave partial records).  It starts behind
+//        ring_stagger_end (every wave has passed its last MATH, whose lgkmcnt(0) retired its last fragment read, and
+//        has waited vmcnt(0) for its own LDS-DMA) and one more workgroup barrier: no read of a unit and no DMA write
+//        into the ring is outstanding in any wave when the first epilogue store to LDS is issued.
+// A tile row past M is fetched from row M - 1 and a vocabulary row past V from row V - 1: the source row is clamped, the
+// value is computed, columns >= V are masked to -inf and rows >= M are never stored.  K is a whole number of K-tiles,
+// so no byte outside H[M, K] (pitch ldh) and W[V, K] (pitch ldw) is read.
+//
+// THE ROW'S SEQUENCE (what the header states).  One fp32 accumulator per logit: K-tiles in ascending k, four MFMA
+// k-steps each.  The tile's 256 columns of a row are held by 4 N-waves x 32 lanes x 2 quadrant halves; records
+// {m, s, i} (maximum, sum of exp(x - m), lowest column of the maximum) combine by
+//     merge(lo, hi): m = max(lo.m, hi.m); e = expf(-|lo.m - hi.m|);
+//                    s = lo.s * (lo.m >= hi.m ? 1 : e) + hi.s * (hi.m >= lo.m ? 1 : e);
+//                    i = the index of the larger m, the smaller index when they are equal
+// first the lane's two columns (c, c + 128), then across the 32 lanes by the xor steps 16, 8, 4, 2, 1 (lo = the lane
+// whose bit is clear), then the four N-waves in ascending order through LDS, then the vocabulary tiles in ascending
+// order in the reduce kernel.  Nothing in that tree depends on the row's place in its tile or on the tile's place in
+// the grid.  No atomics: every record and every target logit has exactly one writer.
+#include <math.h>
+
+#include "common.h"
+#include "i8_ring_tile.h"
+
+namespace {
+
+constexpr int LMH_MIN_K = 128, LMH_MAX_K = 32768;
+constexpr int64_t LMH_MAX_PITCH = 1 << 22;            // elements: a tile row's byte offset stays below 2^32
+static_assert(QT_LM_HEAD_K_UNIT == LMH_MIN_K && QT_LM_HEAD_MIN_K == LMH_MIN_K && QT_LM_HEAD_MAX_K == LMH_MAX_K,
+              "header constants");
+
+struct NllArgs {
+    const char* H;
+    const char* W;
+    const void* targets;
+    float4* rec;          // [tiles_n][M]: {max, sum, argmax (int bits), 0}
+    float* tgt_ws;        // [M]: the accumulator at the target's column
+    int64_t M;
+    int64_t ldh, ldw;     // elements
+    int V, K;
+    int tgt64;
+};
+
+struct Rec {
+    float m, s;
+    int i;
+};
+
+__device__ __forceinline__ Rec rec_merge(const Rec& lo, const Rec& hi) {
+    Rec o;
+    o.m = fmaxf(lo.m, hi.m);
+    const float e = expf(-fabsf(lo.m - hi.m));        // NaN only where both are -inf, and then it is not selected
+    const float wl = lo.m >= hi.m ? 1.0f : e;
+    const float wh = hi.m >= lo.m ? 1.0f : e;
+    const float tl = lo.s * wl;
+    const float th = hi.s * wh;
+    o.s = tl + th;
+    o.i = hi.m > lo.m ? hi.i : (lo.m > hi.m ? lo.i : min(lo.i, hi.i));
+    return o;
+}
+
+__device__ __forceinline__ int64_t load_target(const void* targets, int tgt64, int64_t m) {
+    return tgt64 ? ((const int64_t*)targets)[m] : (int64_t)((const int32_t*)targets)[m];
+}
+
+// One reduce-scatter step over the lane bit X: N rows in, N / 2 out.  The lane whose bit is set keeps the upper half.
+template <int N, int X>
+__device__ __forceinline__ void rec_scatter_step(Rec (&v)[16], int lane) {
+    const bool hb = (lane & X) != 0;
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const Rec keep = hb ? v[j + N / 2] : v[j];
+        const Rec send = hb ? v[j] : v[j + N / 2];
+        Rec got;
+        got.m = __shfl_xor(send.m, X);
+        got.s = __shfl_xor(send.s, X);
+        got.i = __shfl_xor(send.i, X);
+        v[j] = hb ? rec_merge(got, keep) : rec_merge(keep, got);
+    }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(NTHREADS, 2) void lm_head_nll_kernel(const NllArgs p) {
+    __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_m = wave >> 2, wave_n = wave & 3;
+    const bool group_b = wave >= 4;  // wave-uniform
+
+    const int tiles_n = (p.V + BT - 1) / BT;
+    const int tiles_m = (int)((p.M + BT - 1) / BT);
+    int m_tile, n_tile;
+    i8_ring_tile_of(blockIdx.x, tiles_m, tiles_n, m_tile, n_tile);
+    const int64_t m0 = (int64_t)m_tile * BT;
+    const int n0 = n_tile * BT;
+    const int nu = p.K / 64 * 4;                      // units = phases; a multiple of 8 (host: K % 128 == 0)
+
+    // ---- staging geometry: two LDS-DMA instructions per thread per unit (pieces 2 wave, 2 wave + 1) ----
+    const int64_t a_last = p.M - 1 - m0;              // last valid row of the H / W panel, relative to the tile
+    const int b_last = p.V - 1 - n0;
+    const size_t pitch_a = (size_t)p.ldh * 2, pitch_b = (size_t)p.ldw * 2;   // bytes
+    unsigned voff[4][2];                              // [A0, B0, B1, A1][instruction]
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = 16 * wave + 8 * i + (lane >> 3);                   // row of the half panel
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const int64_t ra0 = r < a_last ? r : a_last, ra1 = HP + r < a_last ? HP + r : a_last;   // clamped: a valid row
+        const int rb0 = r < b_last ? r : b_last, rb1 = HP + r < b_last ? HP + r : b_last;
+        voff[0][i] = (unsigned)((size_t)ra0 * pitch_a + 16 * c);         // < 256 * 2^23 (host: pitch <= 2^22 elements)
+        voff[1][i] = (unsigned)((size_t)rb0 * pitch_b + 16 * c);
+        voff[2][i] = (unsigned)((size_t)rb1 * pitch_b + 16 * c);
+        voff[3][i] = (unsigned)((size_t)ra1 * pitch_a + 16 * c);
+    }
+    const unsigned ring_lds = (unsigned)(size_t)(QT_LDS char*)ring;
+    const unsigned dst_wave = __builtin_amdgcn_readfirstlane(ring_lds + wave * 2048);  // wave-uniform
+    const char* srcA = p.H + (size_t)m0 * pitch_a;    // scalar: k-byte 0 of the tile's first row
+    const char* srcB = p.W + (size_t)n0 * pitch_b;
+    // unit i = 4 t + J: J is a compile-time constant wherever the slot is
+    auto issue = [&](auto j_c, int t, int slot) {
+        constexpr int J = decltype(j_c)::value;
+        const unsigned d = dst_wave + (unsigned)slot * UNIT_BYTES;
+        glds16_pair(voff[J][0], voff[J][1], ((J == 0 || J == 3) ? srcA : srcB) + (size_t)t * KU, d, d + 1024);
+    };
+
+    // ---- fragment read geometry (per lane), byte offsets inside a unit ----
+    const int lr = lane & 31, lh = lane >> 5;
+    auto frag_off = [&](int r, int s) {               // row r of the half panel, k-step s
+        const int x = (r >> 1) & 7;
+        return (r >> 3) * 1024 + (r & 7) * 128 + 16 * ((2 * s + lh) ^ x);
+    };
+    int aoff[2][4], boff[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) aoff[mi][s] = frag_off(wave_m * 64 + mi * 32 + lr, s);
+        boff[s] = frag_off(wave_n * 32 + lr, s);
+    }
+
+    f32x16 acc[2][2][2];                              // [A half][B half][mi]
+#pragma unroll
+    for (int qa = 0; qa < 2; ++qa)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) acc[qa][qb][mi] = (f32x16){};
+
+    // ---- the pipeline (ring_pipe.h): R 8, L 6, unit = a half panel, 2 LDS-DMA per wave and unit ----
+    i32x4 fa[2][4], fb[2][4];                         // A: [mi][k-step], B: [half][k-step]
+    // waits of ring_pipe.h one unit earlier: lead LEAD - 1 in its terms (units u+3 .. u+LEAD may stay in flight)
+    auto drain_wait = [&](int u) { ring_drain_wait<2, LEAD - 1>(nu - u - 3); };
+    auto phase = [&](auto slot_c, auto steady_c, int u) {
+        constexpr int S = decltype(slot_c)::value;
+        constexpr bool STEADY = decltype(steady_c)::value;
+        constexpr int Q = S & 3, QA = Q >> 1, QB = Q & 1;
+        constexpr int ISLOT = (S + LEAD) & (RING - 1);
+        // ---- LOAD: the K-tile's units sit in slots (S & 4) + {0: A0, 1: B0, 2: B1, 3: A1} ----
+        const char* tile = ring + (S & 4) * UNIT_BYTES;
+        if constexpr (Q == 0 || Q == 2) {
+            const char* base = tile + (Q == 0 ? 0 : 3) * UNIT_BYTES;
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi) fa[mi][s] = *(const i32x4*)(base + aoff[mi][s]);
+        }
+        if constexpr (Q == 0 || Q == 1) {
+            const char* base = tile + (1 + QB) * UNIT_BYTES;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) fb[QB][s] = *(const i32x4*)(base + boff[s]);
+        }
+        if (STEADY || u + LEAD < nu) {
+            issue(std::integral_constant<int, (S + LEAD) & 3>{}, (u + LEAD) >> 2, ISLOT);
+            wait_vmcnt<2 * (LEAD - 2)>();   // everything up to unit u+2 has landed; 4 units stay in flight
+        } else {
+            drain_wait(u);
+        }
+        // ---- MATH ----
+        ring_sync_math([&] {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+                    acc[QA][QB][mi] = mfma16<F16>(__builtin_bit_cast(s16x8, fa[mi][s]),
+                                                  __builtin_bit_cast(s16x8, fb[QB][s]), acc[QA][QB][mi]);
+        });
+    };
+
+    // prologue: units 0..LEAD-1 in flight (nu >= 8), units 0 and 1 landed
+    issue(std::integral_constant<int, 0>{}, 0, 0);
+    issue(std::integral_constant<int, 1>{}, 0, 1);
+    issue(std::integral_constant<int, 2>{}, 0, 2);
+    issue(std::integral_constant<int, 3>{}, 0, 3);
+    issue(std::integral_constant<int, 0>{}, 1, 4);
+    issue(std::integral_constant<int, 1>{}, 1, 5);
+    wait_vmcnt<2 * (LEAD - 2)>();
+    ring_stagger_begin(group_b);
+
+    int u = 0;
+    for (; u + 8 + LEAD <= nu; u += 8)   // every phase issues a unit that exists
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, std::true_type{}, uu); }, u);
+    for (; u + 8 <= nu; u += 8)          // the last trip: the drain ladder
+        ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, std::false_type{}, uu); }, u);
+    ring_stagger_end(group_b);
+    __syncthreads();                     // the ring is free: see THE EPILOGUE above
+
+    // ---- epilogue: targets -> LDS; per wave and row a record over its 64 columns; 4 N-waves -> one record ----
+    int* tgt_s = (int*)ring;                          // [256]: the row's target if it is a column of V, else -1
+    float* part_m = (float*)(ring + 1024);            // [4 N-waves][256 rows]
+    float* part_s = part_m + 4 * BT;
+    int* part_i = (int*)(part_s + 4 * BT);
+    if (tid < BT) {
+        const int64_t m = m0 + tid;
+        int t = -1;
+        if (m < p.M) {
+            const int64_t tv = load_target(p.targets, p.tgt64, m);
+            if (tv >= 0 && tv < p.V) t = (int)tv;
+        }
+        tgt_s[tid] = t;
+    }
+    __syncthreads();
+    const int col0 = wave_n * 32 + lr;                // the lane's columns of the tile: col0 and col0 + 128
+    const bool ok0 = n0 + col0 < p.V, ok1 = n0 + HP + col0 < p.V;
+    const float ninf = -INFINITY;
+#pragma unroll
+    for (int qa = 0; qa < 2; ++qa) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int first = qa * HP + wave_m * 64 + mi * 32;
+            Rec v[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (int)i8_ring_cd_row(first, r, lh);
+                const float a0 = acc[qa][0][mi][r], a1 = acc[qa][1][mi][r];
+                const int d = tgt_s[row] - n0;        // rows >= M hold -1: no column matches
+                if ((unsigned)d < (unsigned)BT && (d & (HP - 1)) == col0) p.tgt_ws[m0 + row] = (d >> 7) ? a1 : a0;
+                const Rec lo{ok0 ? a0 : ninf, ok0 ? 1.0f : 0.0f, col0};
+                const Rec hi{ok1 ? a1 : ninf, ok1 ? 1.0f : 0.0f, col0 + HP};
+                v[r] = rec_merge(lo, hi);
+            }
+            rec_scatter_step<16, 16>(v, lane);
+            rec_scatter_step<8, 8>(v, lane);
+            rec_scatter_step<4, 4>(v, lane);
+            rec_scatter_step<2, 2>(v, lane);
+            {   // xor 1: both lanes of the pair end with the row's record
+                Rec got;
+                got.m = __shfl_xor(v[0].m, 1);
+                got.s = __shfl_xor(v[0].s, 1);
+                got.i = __shfl_xor(v[0].i, 1);
+                v[0] = (lane & 1) ? rec_merge(got, v[0]) : rec_merge(v[0], got);
+            }
+            if ((lane & 1) == 0) {                    // the lane pair holds accumulator row r = lr >> 1
+                const int row = (int)i8_ring_cd_row(first, lr >> 1, lh);
+                part_m[wave_n * BT + row] = v[0].m;
+                part_s[wave_n * BT + row] = v[0].s;
+                part_i[wave_n * BT + row] = v[0].i;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < BT && m0 + tid < p.M) {
+        Rec o{part_m[tid], part_s[tid], part_i[tid]};
+#pragma unroll
+        for (int w = 1; w < 4; ++w) o = rec_merge(o, Rec{part_m[w * BT + tid], part_s[w * BT + tid], part_i[w * BT + tid]});
+        p.rec[(int64_t)n_tile * p.M + m0 + tid] = make_float4(o.m, o.s, __int_as_float(n0 + o.i), 0.0f);
+    }
+}
+
+constexpr int RED_THREADS = 256;
+
+__global__ __launch_bounds__(RED_THREADS) void lm_head_reduce_kernel(const float4* rec, const float* tgt_ws,
+                                                                      const void* targets, int tgt64, int64_t M, int V,
+                                                                      int tiles_n, float* nll, float* lse, float* tgt,
+                                                                      int32_t* argmax) {
+    const int64_t m = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const float4 q0 = rec[m];
+    Rec o{q0.x, q0.y, __float_as_int(q0.z)};
+    for (int t = 1; t < tiles_n; ++t) {
+        const float4 q = rec[(int64_t)t * M + m];
+        o = rec_merge(o, Rec{q.x, q.y, __float_as_int(q.z)});
+    }
+    const float l = o.m + logf(o.s);
+    const int64_t tv = load_target(targets, tgt64, m);
+    float tl, nl;
+    if (tv < 0) {
+        tl = 0.0f;
+        nl = 0.0f;
+    } else if (tv >= V) {
+        tl = __int_as_float(0x7fc00000);
+        nl = tl;
+    } else {
+        tl = tgt_ws[m];
+        nl = l - tl;
+    }
+    lse[m] = l;
+    tgt[m] = tl;
+    argmax[m] = o.i;
+    nll[m] = nl;
+}
+
+}  // namespace
+
+extern "C" size_t qt_lm_head_nll_workspace_size(int64_t M, int V) {
+    if (M <= 0 || V < 1) return 0;
+    const size_t tiles_n = ((size_t)V + BT - 1) / BT;
+    return (size_t)M * tiles_n * sizeof(float4) + (size_t)M * sizeof(float);
+}
+
+extern "C" int qt_lm_head_nll(const void* H, int64_t ldh, const void* W, int64_t ldw, int dtype, int64_t M, int K, int V,
+                              const void* targets, int target_bytes, float* nll, float* lse, float* tgt,
+                              int32_t* argmax, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* fn = "qt_lm_head_nll";
+    QT_CHECK_ARG(H, "%s: H is null", fn);
+    QT_CHECK_ARG(W, "%s: W is null", fn);
+    QT_CHECK_ARG(targets, "%s: targets is null", fn);
+    QT_CHECK_ARG(nll, "%s: nll is null", fn);
+    QT_CHECK_ARG(lse, "%s: lse is null", fn);
+    QT_CHECK_ARG(tgt, "%s: tgt is null", fn);
+    QT_CHECK_ARG(argmax, "%s: argmax is null", fn);
+    QT_CHECK_ARG(qt_dtype_is16(dtype), "%s: dtype %d must be bf16 or fp16 (fp32 operands are not taken)", fn, dtype);
+    QT_CHECK_ARG(target_bytes == 4 || target_bytes == 8, "%s: target_bytes %d must be 4 (int32) or 8 (int64)", fn,
+                 target_bytes);
+    QT_CHECK_ARG(M >= 0, "%s: M %lld is negative", fn, (long long)M);
+    QT_CHECK_ARG(M <= 0x7fffffffLL, "%s: M %lld too large", fn, (long long)M);
+    QT_CHECK_ARG(V >= 1, "%s: V %d must be at least 1", fn, V);
+    QT_CHECK_ARG(K >= LMH_MIN_K, "%s: K %d is below %d, the smallest K the ring's prologue and drain take", fn, K,
+                 LMH_MIN_K);
+    QT_CHECK_ARG(K <= LMH_MAX_K, "%s: K %d exceeds %d", fn, K, LMH_MAX_K);
+    QT_CHECK_ARG(K % LMH_MIN_K == 0, "%s: K %d is not a multiple of %d", fn, K, LMH_MIN_K);
+    QT_CHECK_ARG(ldh >= K, "%s: ldh %lld is below K %d", fn, (long long)ldh, K);
+    QT_CHECK_ARG(ldw >= K, "%s: ldw %lld is below K %d", fn, (long long)ldw, K);
+    QT_CHECK_ARG(ldh % 8 == 0 && ldh <= LMH_MAX_PITCH, "%s: ldh %lld must be a multiple of 8 elements (16 bytes) and at "
+                 "most %lld", fn, (long long)ldh, (long long)LMH_MAX_PITCH);
+    QT_CHECK_ARG(ldw % 8 == 0 && ldw <= LMH_MAX_PITCH, "%s: ldw %lld must be a multiple of 8 elements (16 bytes) and at "
+                 "most %lld", fn, (long long)ldw, (long long)LMH_MAX_PITCH);
+    QT_CHECK_ARG(((uintptr_t)H & 15) == 0, "%s: H is not 16-byte aligned", fn);
+    QT_CHECK_ARG(((uintptr_t)W & 15) == 0, "%s: W is not 16-byte aligned", fn);
+    if (M == 0) return QT_OK;
+    const int tiles_n = (V + BT - 1) / BT;
+    const int64_t tiles = ((M + BT - 1) / BT) * (int64_t)tiles_n;
+    QT_CHECK_ARG(tiles <= 0x7fffffffLL, "%s: too many tiles (M %lld, V %d)", fn, (long long)M, V);
+    const size_t need = qt_lm_head_nll_workspace_size(M, V);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+        qt_set_error("%s: workspace of %zu bytes needed (16-byte aligned), got %zu at %p", fn, need, workspace_bytes,
+                     workspace);
+        return QT_ERR_WORKSPACE;
+    }
+    float4* rec = (float4*)workspace;
+    float* tgt_ws = (float*)(rec + (size_t)M * tiles_n);
+    NllArgs a{(const char*)H, (const char*)W, targets, rec, tgt_ws, M, ldh, ldw, V, K, target_bytes == 8};
+    qt_prof_mark(QT_PROF_LM_HEAD_NLL, stream);
+    if (dtype == QT_F16)
+        hipLaunchKernelGGL(lm_head_nll_kernel<true>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
+    else
+        hipLaunchKernelGGL(lm_head_nll_kernel<false>, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a);
+    QT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lm_head_reduce_kernel, dim3((unsigned)((M + RED_THREADS - 1) / RED_THREADS)), dim3(RED_THREADS), 0,
+                       stream, rec, tgt_ws, targets, a.tgt64, M, V, tiles_n, nll, lse, tgt, argmax);
+    QT_LAUNCH_CHECK();
+    qt_prof_mark(QT_PROF_LM_HEAD_NLL, stream);
+    return QT_OK;
+}

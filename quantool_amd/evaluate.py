@@ -61,17 +61,81 @@ def nll_sum(logits: torch.Tensor, targets: torch.Tensor, chunk_rows: int = 1024)
     return float(tot)
 
 
+HEADS = ("logits", "fused")
+IGNORE_INDEX = -100
+
+
+def fused_head_parts(model):
+    """(decoder, LM-head weight) of a model whose head ``ops.lm_head_nll`` can stand in for, or ``ValueError`` naming
+    why it cannot: the decoder is ``model.base_model`` (its output is the final norm's), the head a bias-free
+    ``nn.Linear`` with a 16-bit weight on a GPU, applied to the hidden states as they are (no logit soft-capping)."""
+    why = "head=\"fused\" is not available for this model: "
+    base = getattr(model, "base_model", None)
+    if base is None or base is model:
+        raise ValueError(why + "it has no base_model (the decoder with its final norm) apart from itself")
+    head = model.get_output_embeddings() if hasattr(model, "get_output_embeddings") else None
+    if head is None:
+        raise ValueError(why + "it has no output embedding (get_output_embeddings())")
+    if type(head) is not torch.nn.Linear:
+        raise ValueError(why + f"its head is a {type(head).__name__}, not a plain nn.Linear")
+    if head.bias is not None:
+        raise ValueError(why + "its head has a bias")
+    config = getattr(model, "config", None)
+    for name in ("final_logit_softcapping", "logit_softcapping", "logits_soft_cap"):
+        if getattr(config, name, None):
+            raise ValueError(why + f"its config sets logit soft-capping ({name}={getattr(config, name)})")
+    W = head.weight
+    if W.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(why + f"its head weight is {W.dtype}, not bf16 or fp16")
+    from .hip import ops
+
+    if not ops.lm_head_k_supported(W.shape[1]):
+        raise ValueError(why + f"its hidden size {W.shape[1]} is outside the kernel's range (a multiple of "
+                         f"{ops.LM_HEAD_K_UNIT} in [{ops.LM_HEAD_MIN_K}, {ops.LM_HEAD_MAX_K}])")
+    if not W.is_cuda:
+        raise ValueError(why + f"its head weight is on {W.device}, not on a GPU")
+    return base, W
+
+
+def _fused_batch(base, W, ids: torch.Tensor):
+    """(sum of NLL in fp64, positions whose argmax is the target) of one batch through ``ops.lm_head_nll``.  Every row
+    of the [B, T, K] hidden states goes to the kernel as it lies in memory (a view, no copy of the [:, :-1] rows); the
+    last position of each sequence, which predicts nothing, carries the ignore index and contributes 0."""
+    from .hip import ops
+
+    out = base(input_ids=ids)
+    hs = out.last_hidden_state if hasattr(out, "last_hidden_state") else out[0]
+    if not hs.is_cuda or hs.dtype != W.dtype:
+        raise ValueError(f"head=\"fused\" is not available for this model: its hidden states are {hs.dtype} on "
+                         f"{hs.device}, the head weight {W.dtype} on {W.device}")
+    B, T, K = hs.shape
+    if not hs.is_contiguous():                 # a decoder that returns a transposed or sliced tensor: [B, T, K] rows once
+        hs = hs.contiguous()
+    tg = torch.full((B, T), IGNORE_INDEX, dtype=torch.int64, device=hs.device)
+    tg[:, :-1] = ids[:, 1:]
+    tg = tg.view(-1)
+    nll, _, argmax = ops.lm_head_nll(hs.view(B * T, K), W, tg)
+    return float(nll.double().sum()), int(((argmax == tg) & (tg >= 0)).sum())
+
+
 @torch.no_grad()
 def perplexity(model, input_ids=None, *, batch_size: int = 8, device=None, chunk_rows: int = 1024,
                tokenizer=None, dataset=None, num_samples: int = 512, max_seq_length: int = 2048,
-               text_column: str = "text", dtype: Optional[torch.dtype] = None) -> dict:
+               text_column: str = "text", dtype: Optional[torch.dtype] = None, head: str = "logits") -> dict:
     """exp(sum NLL / predicted tokens) over the next-token predictions of every sequence.
 
     ``model``: an ``nn.Module`` (returns logits, or an object with ``.logits``) or a checkpoint directory, which goes
     through ``load_quantized``.  ``input_ids``: a [B, T] tensor or a list of 1-d tensors (sequences of equal length
     share a forward, up to ``batch_size``).  Text instead: ``dataset`` (rows, a ``datasets.Dataset`` or a local
     .json / .jsonl file) with a ``tokenizer``, through the calibration front-end (``build_batches``; nothing is
-    fetched -- a dataset id is refused).  Returns ``{"perplexity", "nll", "tokens"}`` (``nll`` is the mean)."""
+    fetched -- a dataset id is refused).  Returns ``{"perplexity", "nll", "tokens"}`` (``nll`` is the mean).
+
+    ``head="fused"``: the decoder (``model.base_model``) runs alone and ``ops.lm_head_nll`` takes its hidden states and
+    the LM-head weight: the [B, T, V] logits are never formed and every logit stays in fp32.  ``ValueError`` when the
+    model is not eligible (``fused_head_parts``).  The result then also carries ``"head"`` and ``"top1"``, the share of
+    positions whose argmax is the target."""
+    if head not in HEADS:
+        raise ValueError(f"head must be one of {HEADS}, got {head!r}")
     if isinstance(model, (str, Path)):
         from .engine.qlinear import load_quantized
 
@@ -90,6 +154,16 @@ def perplexity(model, input_ids=None, *, batch_size: int = 8, device=None, chunk
         raise ValueError("no sequence has two or more tokens: nothing to predict")
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
+    if head == "fused":
+        base, W = fused_head_parts(model)
+        total, hits, n = 0.0, 0, 0
+        for ids in _batches(seqs, batch_size):
+            ids = ids.to(W.device)
+            t, h = _fused_batch(base, W, ids)
+            total, hits = total + t, hits + h
+            n += ids.shape[0] * (ids.shape[1] - 1)
+        nll = total / n
+        return {"perplexity": math.exp(nll), "nll": nll, "tokens": n, "head": head, "top1": hits / n}
     total, n = 0.0, 0
     for ids in _batches(seqs, batch_size):
         ids = ids.to(device)

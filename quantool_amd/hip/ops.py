@@ -1643,3 +1643,64 @@ def sgemm_tn(A: torch.Tensor, B: torch.Tensor, Cin: Optional[torch.Tensor] = Non
         out.data_ptr(), out.stride(0), M, N, k, int(skip_zero_k), mode, int(allow_split_k),
         ws.data_ptr() if allow_split_k else None, ws.numel() if allow_split_k else 0, _stream()))
     return out
+
+
+# ---- evaluation: LM head + cross-entropy, logits never stored ---------------------------------
+LM_HEAD_K_UNIT = 128        # include/quantool_amd.h: QT_LM_HEAD_K_UNIT / _MIN_K / _MAX_K / the pitch bound
+LM_HEAD_MIN_K = 128
+LM_HEAD_MAX_K = 32768
+LM_HEAD_MAX_PITCH = 1 << 22
+
+
+def lm_head_k_supported(K: int) -> bool:
+    """Whether ``qt_lm_head_nll`` takes a hidden size of K."""
+    return LM_HEAD_MIN_K <= K <= LM_HEAD_MAX_K and K % LM_HEAD_K_UNIT == 0
+
+
+def lm_head_nll(H: torch.Tensor, W: torch.Tensor, targets: torch.Tensor, return_target_logit: bool = False):
+    """Per-row cross-entropy of the LM head without the logits (``qt_lm_head_nll``): H [M, K] and W [V, K], both bf16
+    or both fp16 (unit column stride, any 16-byte-aligned row pitch), targets [M] int32 / int64 -> (nll fp32 [M], lse
+    fp32 [M], argmax int32 [M]); with ``return_target_logit`` the fp32 target logit [M] as a fourth.  A negative target
+    is ignored (nll 0), a target >= V gives NaN."""
+    code = _x2d(H, "H")
+    if not W.is_cuda or W.device != H.device:
+        raise ValueError(f"W must be a device tensor on H's device {H.device}, got {W.device}")
+    if W.dtype != H.dtype:
+        raise TypeError(f"W must be of H's dtype {H.dtype}, got {W.dtype}")
+    if W.dim() != 2 or W.stride(1) != 1:
+        raise ValueError(f"W must be 2-d [V, K] with unit column stride, got shape {tuple(W.shape)} strides {W.stride()}")
+    M, K = H.shape
+    V = W.shape[0]
+    if W.shape[1] != K:
+        raise ValueError(f"W must be [V, {K}], got {tuple(W.shape)}")
+    if V < 1:
+        raise ValueError("W must have at least one row")
+    if not lm_head_k_supported(K):
+        raise ValueError(f"K {K} unsupported: a multiple of {LM_HEAD_K_UNIT} in [{LM_HEAD_MIN_K}, {LM_HEAD_MAX_K}] only")
+    if not targets.is_cuda or targets.device != H.device:
+        raise ValueError(f"targets must be a device tensor on H's device {H.device}, got {targets.device}")
+    if targets.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"targets must be torch.int32 or torch.int64, got {targets.dtype}")
+    if targets.dim() != 1 or targets.numel() != M or not targets.is_contiguous():
+        raise ValueError(f"targets must be contiguous [{M}], got shape {tuple(targets.shape)}")
+    # a one-row matrix may carry any stride(0): the pitch of a single row is never used, K keeps the host check quiet
+    ldh = H.stride(0) if M > 1 else K
+    ldw = W.stride(0) if V > 1 else K
+    for name, t, ld in (("H", H, ldh), ("W", W, ldw)):
+        if ld < K or ld % 8 or ld > LM_HEAD_MAX_PITCH:
+            raise ValueError(f"{name}: row pitch {ld} must be a multiple of 8 elements in [{K}, {LM_HEAD_MAX_PITCH}]")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name} must start on a 16-byte boundary")
+    lib = load()
+    dev = H.device
+    nll = torch.empty(M, dtype=torch.float32, device=dev)
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    tgt = torch.empty(M, dtype=torch.float32, device=dev)
+    argmax = torch.empty(M, dtype=torch.int32, device=dev)
+    if M == 0:
+        return (nll, lse, argmax, tgt) if return_target_logit else (nll, lse, argmax)
+    ws = workspace(lib.qt_lm_head_nll_workspace_size(M, V), dev, "lm_head_nll")
+    check("qt_lm_head_nll", lib.qt_lm_head_nll(
+        H.data_ptr(), ldh, W.data_ptr(), ldw, code, M, K, V, targets.data_ptr(), targets.element_size(), nll.data_ptr(),
+        lse.data_ptr(), tgt.data_ptr(), argmax.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return (nll, lse, argmax, tgt) if return_target_logit else (nll, lse, argmax)

@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--a8-fused-norm", action="store_true",
                     help="A8 checkpoints: run the RMSNorm in front of q/k/v and gate/up and their shared quantiser as one "
                          "qt_rmsnorm_quantize_i8 pass")
+    ap.add_argument("--head", default="logits", choices=["logits", "fused"],
+                    help="fused: the LM head and its cross-entropy run as one qt_lm_head_nll pass, no [B, T, V] logits")
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
@@ -63,9 +65,12 @@ def main():
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
-    r = perplexity(model, ids, batch_size=args.batch_size)
+    if args.device.startswith("cuda"):
+        torch.cuda.reset_peak_memory_stats()
+    r = perplexity(model, ids, batch_size=args.batch_size, head=args.head)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
+        r["eval_peak_bytes"] = torch.cuda.max_memory_allocated()
     t2 = time.perf_counter()
     r.update({"checkpoint": str(args.checkpoint), "format": model._qt_checkpoint["format"],
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()),
@@ -73,7 +78,7 @@ def main():
               "quantizing_norms": sum(isinstance(m, QuantizingRMSNorm) for m in model.modules()),
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
-              "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
+              "head": args.head, "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
     print(json.dumps(r))
 
 
