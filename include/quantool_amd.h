@@ -793,6 +793,47 @@ int qt_lm_head_nll(const void* H, int64_t ldh, const void* W, int64_t ldw, int d
                    const void* targets, int target_bytes, float* nll, float* lse, float* tgt, int32_t* argmax,
                    void* workspace, size_t workspace_bytes, qt_stream_t stream);
 
+/* qt_lm_head_kl: the distance of two models that share one LM-head weight, per token and with neither [M, V] logit
+ *   matrix written.  For every row m of Hp [M, K] (the original model's final hidden states, row pitch ldhp), Hq [M, K]
+ *   (the quantised model's, row pitch ldhq) and W [V, K] (row pitch ldw), all bf16 or all fp16 (dtype), with
+ *   a[m, v] = sum_k Hp[m, k] W[v, k] and b[m, v] = sum_k Hq[m, k] W[v, k] in fp32 accumulators, P = softmax(a[m, :]) and
+ *   Q = softmax(b[m, :]):
+ *     lse_p[m] = log sum_v exp(a[m, v]),  lse_q[m] = log sum_v exp(b[m, v])
+ *     kl[m]    = KL(P || Q) = sum_v P[v] (a[m, v] - b[m, v]) - lse_p[m] + lse_q[m]
+ *              = t / s_a - lse_p[m] + lse_q[m],  t = sum_v exp(a[m, v] - max_a) (a[m, v] - b[m, v]),
+ *                s_a = sum_v exp(a[m, v] - max_a).  kl[m] is not clamped at 0: it is exactly 0 where Hp[m, :] and
+ *                Hq[m, :] are equal, and rounding may leave a negative value of the size of an fp32 ulp of the lse.
+ *     argmax_p[m], argmax_q[m] = the lowest v of maximal a[m, v], of maximal b[m, v]
+ *     nll_p[m] = lse_p[m] - a[m, targets[m]],  nll_q[m] = lse_q[m] - b[m, targets[m]]
+ *   targets as in qt_lm_head_nll: targets[m] < 0 (the ignore index) gives nll_p[m] = nll_q[m] = 0, targets[m] >= V gives
+ *   NaN in both; kl, both lse and both argmax are still written.
+ *   One workgroup holds 128 token rows x 256 vocabulary columns of a AND b in its accumulators: the K-tile's four
+ *   half-panel units are Hp rows, two halves of W rows, Hq rows (the same 128 token rows), so a[m, v] and b[m, v] lie
+ *   in one lane and a[m, v] - b[m, v] is formed in fp32 from the accumulators -- never from rounded logits.
+ *   Contract: a and b are qt_lm_head_nll's accumulators of (Hp, W) and (Hq, W), and {lse_p, argmax_p, nll_p} and
+ *   {lse_q, argmax_q, nll_q} are its outputs for them, to the bit: the same k order, the same records {m, s, i} and
+ *   the same merge order -- the lane's two columns (c, c + 128 of the tile), the 32 lanes by the xor steps 16, 8, 4, 2,
+ *   1, the four column waves in ascending order, the vocabulary tiles in ascending order.  The P record carries t as a
+ *   fourth field: an element is {a, 1, v, a - b}, a masked column (>= V) {-inf, 0, v, 0}, and t merges with the weights
+ *   of s: t = t1 exp(m1 - m) + t2 exp(m2 - m).  Row m's seven outputs depend only on Hp[m, :], Hq[m, :], W, V, K and
+ *   targets[m] -- not on M, the row's index, the pitches or the alignment of Hp and Hq.  Deterministic, no atomics.
+ *   Workspace: qt_lm_head_kl_workspace_size(M, V) = 32 M ceil(V / 256) bytes of records + 8 M bytes of target logits,
+ *   16-byte aligned; a short, NULL or misaligned workspace is QT_ERR_WORKSPACE with nothing launched.
+ *   M = 0 returns QT_OK and touches nothing.  QT_ERR_INVALID before any launch, with qt_last_error naming the argument:
+ *   the refusals of qt_lm_head_nll, for both hidden-state operands -- a dtype that is not bf16 or fp16 (fp32 operands
+ *   are not taken); K not a multiple of QT_LM_HEAD_K_UNIT, below QT_LM_HEAD_MIN_K or above QT_LM_HEAD_MAX_K; ldhp < K,
+ *   ldhq < K or ldw < K; a pitch that is not a multiple of 8 elements or exceeds 2^22 elements, or a base of Hp, Hq or W
+ *   that is not 16-byte aligned; V < 1; M < 0 or M > INT32_MAX; a target_bytes that is neither 4 nor 8; a NULL Hp, Hq,
+ *   W, targets, kl, nll_p, nll_q, lse_p, lse_q, argmax_p or argmax_q.  Tile rows past M and vocabulary rows past V are
+ *   fetched clamped (row M - 1 on each side, row V - 1), computed and never stored: no byte outside Hp [M, K],
+ *   Hq [M, K], W [V, K] and targets [M] is read, nothing outside the seven outputs [M] and the workspace is written.
+ *   (csrc/lm_head_kl.hip) */
+size_t qt_lm_head_kl_workspace_size(int64_t M, int V);
+int qt_lm_head_kl(const void* Hp, int64_t ldhp, const void* Hq, int64_t ldhq, const void* W, int64_t ldw, int dtype,
+                  int64_t M, int K, int V, const void* targets, int target_bytes, float* kl, float* nll_p, float* nll_q,
+                  float* lse_p, float* lse_q, int32_t* argmax_p, int32_t* argmax_q, void* workspace,
+                  size_t workspace_bytes, qt_stream_t stream);
+
 /* ---- measurement aid (bench.py roofline leg; not part of the reference surface) -------------
  * When enabled, HIP events are recorded on the launch stream immediately around the named
  * kernel; qt_profile_read synchronises them, returns the summed device time and the launch

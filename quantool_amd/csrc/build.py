@@ -123,7 +123,7 @@ def _resources(src: Path, stderr: str) -> str:
 
 
 def audit_m0(src: Path) -> None:
-    """xtx.hip, gemm3_tn.hip, sgemm_tn.hip, qlinear_ring.hip, qlinear_ring_w4.hip and lm_head_nll.hip write M0 from inline asm without restoring it (the LDS-DMA destination).  That is only
+    """xtx.hip, gemm3_tn.hip, sgemm_tn.hip, qlinear_ring.hip, qlinear_ring_w4.hip, lm_head_nll.hip and lm_head_kl.hip write M0 from inline asm without restoring it (the LDS-DMA destination).  That is only
     sound while hipcc itself never touches M0 in that translation unit, so the device ISA is checked:
     every line that names m0 must sit inside an ;;#ASMSTART ... ;;#ASMEND block."""
     stamp = OBJ_DIR / (src.stem + ".m0audit")
@@ -154,7 +154,7 @@ def audit_m0(src: Path) -> None:
 NO_SPILL_KERNELS = ("xtx_kernel", "xtx16_kernel", "gemm3_kernel", "sgemm_ring_kernel", "sweep_fused_kernel", "quantize_tokens_kernel",
                     "gemm_i8_kernel", "gemm_i8_ring_kernel", "gemm_i8_ring_moe_kernel", "gemm_i8_mid_kernel",
                     "gemm_i8_ring_w4_kernel", "gemm_i8_ring_w4_moe_kernel", "moe_gemm_i8_wide_kernel",
-                    "moe_gemm_wq_wide_kernel", "lm_head_nll_kernel")
+                    "moe_gemm_wq_wide_kernel", "lm_head_nll_kernel", "lm_head_kl_kernel")
 
 
 def audit_spills(src_name: str, asm_text: str) -> None:
@@ -176,7 +176,7 @@ def build(verbose: bool = False) -> Path:
     with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         objs = list(ex.map(_compile, srcs))
     for name in ("xtx.hip", "gemm3_tn.hip", "sgemm_tn.hip", "sweep.hip", "qlinear.hip", "qlinear_ring.hip", "qlinear_ring_w4.hip",
-                 "lm_head_nll.hip"):
+                 "lm_head_nll.hip", "lm_head_kl.hip"):
         audit_m0(CSRC / name)
     newest = max(o.stat().st_mtime for o in objs)
     if not LIB_PATH.exists() or LIB_PATH.stat().st_mtime < newest:

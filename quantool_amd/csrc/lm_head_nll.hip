@@ -41,18 +41,15 @@
 // first the lane's two columns (c, c + 128), then across the 32 lanes by the xor steps 16, 8, 4, 2, 1 (lo = the lane
 // whose bit is clear), then the four N-waves in ascending order through LDS, then the vocabulary tiles in ascending
 // order in the reduce kernel.  Nothing in that tree depends on the row's place in its tile or on the tile's place in
-// the grid.  No atomics: every record and every target logit has exactly one writer.
+// the grid.  No atomics: every record and every target logit has exactly one writer.  The record, its merge and the
+// scatter step are lm_head_rec.h's, shared with lm_head_kl.hip.
 #include <math.h>
 
 #include "common.h"
 #include "i8_ring_tile.h"
+#include "lm_head_rec.h"
 
 namespace {
-
-constexpr int LMH_MIN_K = 128, LMH_MAX_K = 32768;
-constexpr int64_t LMH_MAX_PITCH = 1 << 22;            // elements: a tile row's byte offset stays below 2^32
-static_assert(QT_LM_HEAD_K_UNIT == LMH_MIN_K && QT_LM_HEAD_MIN_K == LMH_MIN_K && QT_LM_HEAD_MAX_K == LMH_MAX_K,
-              "header constants");
 
 struct NllArgs {
     const char* H;
@@ -65,44 +62,6 @@ struct NllArgs {
     int V, K;
     int tgt64;
 };
-
-struct Rec {
-    float m, s;
-    int i;
-};
-
-__device__ __forceinline__ Rec rec_merge(const Rec& lo, const Rec& hi) {
-    Rec o;
-    o.m = fmaxf(lo.m, hi.m);
-    const float e = expf(-fabsf(lo.m - hi.m));        // NaN only where both are -inf, and then it is not selected
-    const float wl = lo.m >= hi.m ? 1.0f : e;
-    const float wh = hi.m >= lo.m ? 1.0f : e;
-    const float tl = lo.s * wl;
-    const float th = hi.s * wh;
-    o.s = tl + th;
-    o.i = hi.m > lo.m ? hi.i : (lo.m > hi.m ? lo.i : min(lo.i, hi.i));
-    return o;
-}
-
-__device__ __forceinline__ int64_t load_target(const void* targets, int tgt64, int64_t m) {
-    return tgt64 ? ((const int64_t*)targets)[m] : (int64_t)((const int32_t*)targets)[m];
-}
-
-// One reduce-scatter step over the lane bit X: N rows in, N / 2 out.  The lane whose bit is set keeps the upper half.
-template <int N, int X>
-__device__ __forceinline__ void rec_scatter_step(Rec (&v)[16], int lane) {
-    const bool hb = (lane & X) != 0;
-#pragma unroll
-    for (int j = 0; j < N / 2; ++j) {
-        const Rec keep = hb ? v[j + N / 2] : v[j];
-        const Rec send = hb ? v[j] : v[j + N / 2];
-        Rec got;
-        got.m = __shfl_xor(send.m, X);
-        got.s = __shfl_xor(send.s, X);
-        got.i = __shfl_xor(send.i, X);
-        v[j] = hb ? rec_merge(got, keep) : rec_merge(keep, got);
-    }
-}
 
 template <bool F16>
 __global__ __launch_bounds__(NTHREADS, 2) void lm_head_nll_kernel(const NllArgs p) {
@@ -266,13 +225,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void lm_head_nll_kernel(const NllArgs 
             rec_scatter_step<8, 8>(v, lane);
             rec_scatter_step<4, 4>(v, lane);
             rec_scatter_step<2, 2>(v, lane);
-            {   // xor 1: both lanes of the pair end with the row's record
-                Rec got;
-                got.m = __shfl_xor(v[0].m, 1);
-                got.s = __shfl_xor(v[0].s, 1);
-                got.i = __shfl_xor(v[0].i, 1);
-                v[0] = (lane & 1) ? rec_merge(got, v[0]) : rec_merge(v[0], got);
-            }
+            v[0] = rec_pair_step(v[0], lane);         // xor 1: both lanes of the pair end with the row's record
             if ((lane & 1) == 0) {                    // the lane pair holds accumulator row r = lr >> 1
                 const int row = (int)i8_ring_cd_row(first, lr >> 1, lh);
                 part_m[wave_n * BT + row] = v[0].m;
@@ -286,7 +239,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void lm_head_nll_kernel(const NllArgs 
         Rec o{part_m[tid], part_s[tid], part_i[tid]};
 #pragma unroll
         for (int w = 1; w < 4; ++w) o = rec_merge(o, Rec{part_m[w * BT + tid], part_s[w * BT + tid], part_i[w * BT + tid]});
-        p.rec[(int64_t)n_tile * p.M + m0 + tid] = make_float4(o.m, o.s, __int_as_float(n0 + o.i), 0.0f);
+        p.rec[(int64_t)n_tile * p.M + m0 + tid] = rec_pack(o, n0);
     }
 }
 
@@ -298,12 +251,8 @@ __global__ __launch_bounds__(RED_THREADS) void lm_head_reduce_kernel(const float
                                                                       int32_t* argmax) {
     const int64_t m = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x;
     if (m >= M) return;
-    const float4 q0 = rec[m];
-    Rec o{q0.x, q0.y, __float_as_int(q0.z)};
-    for (int t = 1; t < tiles_n; ++t) {
-        const float4 q = rec[(int64_t)t * M + m];
-        o = rec_merge(o, Rec{q.x, q.y, __float_as_int(q.z)});
-    }
+    Rec o = rec_unpack(rec[m]);
+    for (int t = 1; t < tiles_n; ++t) o = rec_merge(o, rec_unpack(rec[(int64_t)t * M + m]));
     const float l = o.m + logf(o.s);
     const int64_t tv = load_target(targets, tgt64, m);
     float tl, nl;

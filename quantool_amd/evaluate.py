@@ -1,8 +1,9 @@
-"""Perplexity of a model or a saved checkpoint on token sequences.
+"""Perplexity of a model or a saved checkpoint on token sequences, and its divergence from the model it came from.
 
 The reference declares an evaluation step and enables it by default (``src/quantool/args/quantization_args.py:63-80``:
 ``enable_evaluation=True``, ``metrics=["perplexity"]``) but never runs one (``cli.py:413`` is commented out).  This is
-that step for the checkpoints this backend writes: ``perplexity(path_or_model, input_ids)``.
+that step for the checkpoints this backend writes: ``perplexity(path_or_model, input_ids)``, and
+``divergence(reference, path_or_model, input_ids)`` for the per-token KL and top-1 agreement of the two models.
 """
 from __future__ import annotations
 
@@ -173,3 +174,112 @@ def perplexity(model, input_ids=None, *, batch_size: int = 8, device=None, chunk
         del logits
     nll = total / n
     return {"perplexity": math.exp(nll), "nll": nll, "tokens": n}
+
+
+def load_side(side, device, dtype):
+    """A module as it is; a directory through ``load_quantized`` when its config.json carries a quantization_config,
+    else as a dense checkpoint through transformers with ``local_files_only=True`` (nothing is fetched)."""
+    if not isinstance(side, (str, Path)):
+        return side
+    import json
+
+    path = Path(side)
+    cfg_file = path / "config.json"
+    if not cfg_file.is_file():
+        raise ValueError(f"{path}: not a local checkpoint directory (no config.json); nothing is fetched")
+    if json.loads(cfg_file.read_text()).get("quantization_config"):
+        from .engine.qlinear import load_quantized
+
+        return load_quantized(path, device=device or "cuda", dtype=dtype)
+    from transformers import AutoModelForCausalLM
+
+    model = AutoModelForCausalLM.from_pretrained(str(path), local_files_only=True, dtype=dtype or "auto")
+    return model.to(device or "cuda").eval()
+
+
+def _hidden(base, ids, W):
+    out = base(input_ids=ids)
+    hs = out.last_hidden_state if hasattr(out, "last_hidden_state") else out[0]
+    if not hs.is_cuda or hs.dtype != W.dtype:
+        raise ValueError(f"divergence is not available for this pair: hidden states are {hs.dtype} on {hs.device}, "
+                         f"the head weight {W.dtype} on {W.device}")
+    return hs if hs.is_contiguous() else hs.contiguous()
+
+
+DIVERGENCE_KEYS = ("tokens", "kl", "kl_max", "top1_agree", "nll_ref", "nll", "perplexity_ref", "perplexity", "top1_ref",
+                   "top1")
+
+
+@torch.no_grad()
+def divergence(reference, model, input_ids=None, *, batch_size: int = 8, device=None,
+               dtype: Optional[torch.dtype] = None, tokenizer=None, dataset=None, num_samples: int = 512,
+               max_seq_length: int = 2048, text_column: str = "text") -> dict:
+    """How far ``model`` (the quantised side, Q) moved from ``reference`` (the original, P) on the same tokens: the
+    per-token KL(P || Q) and the top-1 agreement, beside both perplexities.
+
+    Either side is an ``nn.Module`` or a local directory: one whose config.json has a ``quantization_config`` goes
+    through ``load_quantized``, a dense one through transformers' ``from_pretrained(local_files_only=True)``.
+    ``input_ids`` / ``dataset`` + ``tokenizer`` as in ``perplexity``.  Both decoders run on the same ids, and
+    ``ops.lm_head_kl`` takes the two [B * T, K] hidden states and the one head weight: no logits are formed, and
+    a - b is taken between fp32 accumulators.  The last position of each sequence carries the ignore index and is
+    left out of every statistic, so the positions are exactly ``perplexity``'s.
+
+    Eligible: both sides pass ``fused_head_parts`` and their head weights have one shape and dtype and are
+    ``torch.equal``; anything else is a ``ValueError`` naming the reason.  Returns ``{"tokens", "kl" (mean), "kl_max",
+    "top1_agree", "nll_ref", "nll", "perplexity_ref", "perplexity", "top1_ref", "top1"}``; sums are kept in fp64."""
+    reference = load_side(reference, device, dtype)
+    model = load_side(model, device, dtype)
+    try:
+        base_p, W = fused_head_parts(reference)
+    except ValueError as e:
+        raise ValueError(f"divergence: the reference: {e}") from None
+    try:
+        base_q, Wq = fused_head_parts(model)
+    except ValueError as e:
+        raise ValueError(f"divergence: the model: {e}") from None
+    why = "the two models' LM heads differ: one head weight is what the kernel takes"
+    if W.shape != Wq.shape or W.dtype != Wq.dtype:
+        raise ValueError(f"divergence: {why} (reference {tuple(W.shape)} {W.dtype}, model {tuple(Wq.shape)} {Wq.dtype})")
+    if W.device != Wq.device:
+        raise ValueError(f"divergence: the two models are on different devices ({W.device}, {Wq.device})")
+    if W.data_ptr() != Wq.data_ptr() and not torch.equal(W, Wq):
+        raise ValueError(f"divergence: {why} (the weights are not equal)")
+    if input_ids is None:
+        if dataset is None:
+            raise ValueError("pass input_ids, or dataset= with tokenizer=")
+        from .engine.sequential import build_batches
+
+        input_ids = build_batches(dataset, tokenizer, num_samples, max_seq_length, False, 0, text_column)
+    seqs = [s for s in _sequences(input_ids) if s.numel() >= 2]
+    if not seqs:
+        raise ValueError("no sequence has two or more tokens: nothing to predict")
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    from .hip import ops
+
+    dev = W.device
+    sums = torch.zeros(3, dtype=torch.float64, device=dev)         # kl, nll_ref, nll
+    hits = torch.zeros(3, dtype=torch.int64, device=dev)           # agree, top1_ref, top1
+    kl_max = torch.full((), -math.inf, dtype=torch.float32, device=dev)
+    n = 0
+    for ids in _batches(seqs, batch_size):
+        ids = ids.to(dev)
+        hp = _hidden(base_p, ids, W)
+        hq = _hidden(base_q, ids, W)
+        B, T, K = hp.shape
+        if hq.shape != hp.shape:
+            raise ValueError(f"divergence: hidden states of {tuple(hp.shape)} and {tuple(hq.shape)}")
+        tg = torch.full((B, T), IGNORE_INDEX, dtype=torch.int64, device=dev)
+        tg[:, :-1] = ids[:, 1:]
+        tg = tg.view(-1)
+        r = ops.lm_head_kl(hp.view(B * T, K), hq.view(B * T, K), W, tg)
+        keep = tg >= 0
+        sums += torch.stack([r.kl[keep].double().sum(), r.nll_p.double().sum(), r.nll_q.double().sum()])
+        hits += torch.stack([((r.argmax_p == r.argmax_q) & keep).sum(), ((r.argmax_p == tg) & keep).sum(),
+                             ((r.argmax_q == tg) & keep).sum()])
+        kl_max = torch.maximum(kl_max, r.kl[keep].max())
+        n += B * (T - 1)
+    kl, nll_ref, nll = (float(x) / n for x in sums)
+    agree, top1_ref, top1 = (int(x) / n for x in hits)
+    return {"tokens": n, "kl": kl, "kl_max": float(kl_max), "top1_agree": agree, "nll_ref": nll_ref, "nll": nll,
+            "perplexity_ref": math.exp(nll_ref), "perplexity": math.exp(nll), "top1_ref": top1_ref, "top1": top1}

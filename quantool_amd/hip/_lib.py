@@ -154,6 +154,10 @@ SIGNATURES = {
     "qt_lm_head_nll_workspace_size": (c_size_t, [c_int64, c_int]),
     "qt_lm_head_nll": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "qt_lm_head_kl_workspace_size": (c_size_t, [c_int64, c_int]),
+    "qt_lm_head_kl": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int,
+                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

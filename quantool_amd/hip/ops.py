@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import logging
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional
 
@@ -1657,19 +1658,27 @@ def lm_head_k_supported(K: int) -> bool:
     return LM_HEAD_MIN_K <= K <= LM_HEAD_MAX_K and K % LM_HEAD_K_UNIT == 0
 
 
-def lm_head_nll(H: torch.Tensor, W: torch.Tensor, targets: torch.Tensor, return_target_logit: bool = False):
-    """Per-row cross-entropy of the LM head without the logits (``qt_lm_head_nll``): H [M, K] and W [V, K], both bf16
-    or both fp16 (unit column stride, any 16-byte-aligned row pitch), targets [M] int32 / int64 -> (nll fp32 [M], lse
-    fp32 [M], argmax int32 [M]); with ``return_target_logit`` the fp32 target logit [M] as a fourth.  A negative target
-    is ignored (nll 0), a target >= V gives NaN."""
-    code = _x2d(H, "H")
+def _lm_head_operands(hidden, W: torch.Tensor, targets: torch.Tensor):
+    """The checks that ``qt_lm_head_nll`` and ``qt_lm_head_kl`` share, made before the library is touched.  ``hidden``:
+    (name, tensor) of each hidden-state operand; the first sets device, dtype and shape for the rest.  Returns
+    (dtype code, M, K, V, the hidden operands' pitches, W's pitch)."""
+    name0, H = hidden[0]
+    code = _x2d(H, name0)
+    M, K = H.shape
+    for name, X in hidden[1:]:
+        _x2d(X, name)
+        if X.device != H.device:
+            raise ValueError(f"{name} must be a device tensor on {name0}'s device {H.device}, got {X.device}")
+        if X.dtype != H.dtype:
+            raise TypeError(f"{name} must be of {name0}'s dtype {H.dtype}, got {X.dtype}")
+        if X.shape != H.shape:
+            raise ValueError(f"{name} must be of {name0}'s shape {tuple(H.shape)}, got {tuple(X.shape)}")
     if not W.is_cuda or W.device != H.device:
-        raise ValueError(f"W must be a device tensor on H's device {H.device}, got {W.device}")
+        raise ValueError(f"W must be a device tensor on {name0}'s device {H.device}, got {W.device}")
     if W.dtype != H.dtype:
-        raise TypeError(f"W must be of H's dtype {H.dtype}, got {W.dtype}")
+        raise TypeError(f"W must be of {name0}'s dtype {H.dtype}, got {W.dtype}")
     if W.dim() != 2 or W.stride(1) != 1:
         raise ValueError(f"W must be 2-d [V, K] with unit column stride, got shape {tuple(W.shape)} strides {W.stride()}")
-    M, K = H.shape
     V = W.shape[0]
     if W.shape[1] != K:
         raise ValueError(f"W must be [V, {K}], got {tuple(W.shape)}")
@@ -1678,19 +1687,28 @@ def lm_head_nll(H: torch.Tensor, W: torch.Tensor, targets: torch.Tensor, return_
     if not lm_head_k_supported(K):
         raise ValueError(f"K {K} unsupported: a multiple of {LM_HEAD_K_UNIT} in [{LM_HEAD_MIN_K}, {LM_HEAD_MAX_K}] only")
     if not targets.is_cuda or targets.device != H.device:
-        raise ValueError(f"targets must be a device tensor on H's device {H.device}, got {targets.device}")
+        raise ValueError(f"targets must be a device tensor on {name0}'s device {H.device}, got {targets.device}")
     if targets.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"targets must be torch.int32 or torch.int64, got {targets.dtype}")
     if targets.dim() != 1 or targets.numel() != M or not targets.is_contiguous():
         raise ValueError(f"targets must be contiguous [{M}], got shape {tuple(targets.shape)}")
     # a one-row matrix may carry any stride(0): the pitch of a single row is never used, K keeps the host check quiet
-    ldh = H.stride(0) if M > 1 else K
+    ldhs = [X.stride(0) if M > 1 else K for _, X in hidden]
     ldw = W.stride(0) if V > 1 else K
-    for name, t, ld in (("H", H, ldh), ("W", W, ldw)):
+    for name, t, ld in [(n, X, l) for (n, X), l in zip(hidden, ldhs)] + [("W", W, ldw)]:
         if ld < K or ld % 8 or ld > LM_HEAD_MAX_PITCH:
             raise ValueError(f"{name}: row pitch {ld} must be a multiple of 8 elements in [{K}, {LM_HEAD_MAX_PITCH}]")
         if t.data_ptr() % 16:
             raise ValueError(f"{name} must start on a 16-byte boundary")
+    return code, M, K, V, ldhs, ldw
+
+
+def lm_head_nll(H: torch.Tensor, W: torch.Tensor, targets: torch.Tensor, return_target_logit: bool = False):
+    """Per-row cross-entropy of the LM head without the logits (``qt_lm_head_nll``): H [M, K] and W [V, K], both bf16
+    or both fp16 (unit column stride, any 16-byte-aligned row pitch), targets [M] int32 / int64 -> (nll fp32 [M], lse
+    fp32 [M], argmax int32 [M]); with ``return_target_logit`` the fp32 target logit [M] as a fourth.  A negative target
+    is ignored (nll 0), a target >= V gives NaN."""
+    code, M, K, V, (ldh,), ldw = _lm_head_operands((("H", H),), W, targets)
     lib = load()
     dev = H.device
     nll = torch.empty(M, dtype=torch.float32, device=dev)
@@ -1704,3 +1722,30 @@ def lm_head_nll(H: torch.Tensor, W: torch.Tensor, targets: torch.Tensor, return_
         H.data_ptr(), ldh, W.data_ptr(), ldw, code, M, K, V, targets.data_ptr(), targets.element_size(), nll.data_ptr(),
         lse.data_ptr(), tgt.data_ptr(), argmax.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return (nll, lse, argmax, tgt) if return_target_logit else (nll, lse, argmax)
+
+
+LmHeadKl = namedtuple("LmHeadKl", "kl nll_p nll_q lse_p lse_q argmax_p argmax_q")
+
+
+def lm_head_kl(Hp: torch.Tensor, Hq: torch.Tensor, W: torch.Tensor, targets: Optional[torch.Tensor] = None) -> LmHeadKl:
+    """Per-row KL(P || Q) of two models that share the head weight W, without either logit matrix (``qt_lm_head_kl``):
+    Hp, Hq [M, K] (the original's and the quantised model's hidden states) and W [V, K], all bf16 or all fp16 (unit
+    column stride, any 16-byte-aligned row pitch, Hp's and Hq's may differ), targets [M] int32 / int64 or None (every
+    row ignored) -> ``(kl, nll_p, nll_q, lse_p, lse_q, argmax_p, argmax_q)``, fp32 [M] and int32 [M].  Each side's lse,
+    argmax and nll are ``lm_head_nll``'s for that side, to the bit; ``kl`` is not clamped at 0."""
+    if targets is None:
+        _x2d(Hp, "Hp")
+        targets = torch.full((Hp.shape[0],), -100, dtype=torch.int64, device=Hp.device)
+    code, M, K, V, (ldhp, ldhq), ldw = _lm_head_operands((("Hp", Hp), ("Hq", Hq)), W, targets)
+    lib = load()
+    dev = Hp.device
+    f = [torch.empty(M, dtype=torch.float32, device=dev) for _ in range(5)]
+    am = [torch.empty(M, dtype=torch.int32, device=dev) for _ in range(2)]
+    out = LmHeadKl(*f, *am)
+    if M == 0:
+        return out
+    ws = workspace(lib.qt_lm_head_kl_workspace_size(M, V), dev, "lm_head_kl")
+    check("qt_lm_head_kl", lib.qt_lm_head_kl(
+        Hp.data_ptr(), ldhp, Hq.data_ptr(), ldhq, W.data_ptr(), ldw, code, M, K, V, targets.data_ptr(),
+        targets.element_size(), *(t.data_ptr() for t in out), ws.data_ptr(), ws.numel(), _stream()))
+    return out

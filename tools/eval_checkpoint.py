@@ -3,7 +3,7 @@
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-experts-wide-tokens N] [--a8-fused-act]
-                                  [--a8-fused-norm]
+                                  [--a8-fused-norm] [--head logits|fused] [--against REF]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
@@ -13,8 +13,11 @@ on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed``
 ``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
 ``qt_act_mul_quantize_i8`` pass, the same perplexity to the bit; ``--a8-fused-norm`` on an A8 checkpoint: the RMSNorms in
 front of q/k/v and gate/up and the quantiser their consumers share in one ``qt_rmsnorm_quantize_i8`` pass each, whose sum
-over K runs in the kernel's own order, so the perplexity may move in its last digits).  Prints one JSON line: perplexity,
-mean NLL, predicted tokens, the module counts, load and evaluation wall times.
+over K runs in the kernel's own order, so the perplexity may move in its last digits).  ``--against REF`` (the original
+model: a dense checkpoint directory, or a quantised one) adds ``"divergence"``: what ``evaluate.divergence(REF,
+checkpoint)`` returns on the same tokens -- the mean and maximum per-token KL(REF || checkpoint), the top-1 agreement and
+both perplexities through one ``qt_lm_head_kl`` pass per batch -- with its wall time and peak allocated memory.  Prints
+one JSON line: perplexity, mean NLL, predicted tokens, the module counts, load and evaluation wall times.
 """
 from __future__ import annotations
 
@@ -30,7 +33,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm,  # noqa: E402
                                          WeightOnlyExperts, WeightOnlyLinear, load_quantized)
-from quantool_amd.evaluate import perplexity  # noqa: E402
+from quantool_amd.evaluate import divergence, load_side, perplexity  # noqa: E402
 
 
 def main():
@@ -54,6 +57,8 @@ def main():
                          "qt_rmsnorm_quantize_i8 pass")
     ap.add_argument("--head", default="logits", choices=["logits", "fused"],
                     help="fused: the LM head and its cross-entropy run as one qt_lm_head_nll pass, no [B, T, V] logits")
+    ap.add_argument("--against", default=None, metavar="REF",
+                    help="the original model's directory: adds evaluate.divergence(REF, checkpoint) on the same tokens")
     args = ap.parse_args()
     ids = torch.load(args.tokens)
     t0 = time.perf_counter()
@@ -79,6 +84,20 @@ def main():
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
               "head": args.head, "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
+    if args.against:
+        t3 = time.perf_counter()
+        ref = load_side(args.against, args.device, getattr(torch, args.dtype) if args.dtype else None)
+        if args.device.startswith("cuda"):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+        t4 = time.perf_counter()
+        d = divergence(ref, model, ids, batch_size=args.batch_size)
+        if args.device.startswith("cuda"):
+            torch.cuda.synchronize()
+            d["eval_peak_bytes"] = torch.cuda.max_memory_allocated()
+        d.update({"against": str(args.against), "load_s": round(t4 - t3, 3),
+                  "eval_s": round(time.perf_counter() - t4, 3)})
+        r["divergence"] = d
     print(json.dumps(r))
 
 
