@@ -439,6 +439,35 @@ int qt_chol_g3_plan_check(int K, int merged, int min_chunks, long long* counts_o
  *   Y[m < M, n < N] is written.  Deterministic, no atomics, no workspace, no communication between workgroups.
  *   
  *
+ * qt_splitk_gemm_i8: the short-prompt form of qt_gemm_i8 for W8A8 / INT8, a few tiles of rows over a long reduction:
+ *   qt_gemm_i8_ring's 256 x 256 tile over a k-range, plus a reduce pass.  qt_gemm_i8's arguments with the same
+ *   meanings, followed by splits, workspace and workspace_size.  Taken: w_format == QT_W_INT8 with G == 1, K a multiple
+ *   of QT_SPLITK_I8_K_UNIT, K <= 32768, Xq, Wq and the workspace 16-byte aligned, bf16 and fp16 output, with and without
+ *   zp_x / wsum and bias, any M >= 1, any N >= 1, any ldy >= N, and a split count S >= 2 out of qt_splitk_gemm_i8_plan.
+ *   Everything else -- packed int4, G > 1, a ragged K, a misaligned operand, a null workspace, S == 1 (that is
+ *   qt_gemm_i8_ring), S > K / QT_SPLITK_I8_K_UNIT or > QT_SPLITK_I8_MAX_SPLITS, a workspace smaller than the plan's
+ *   (the message names the size needed) -- is QT_ERR_INVALID before any launch, and qt_last_error names the reason.
+ *   For every legal input Y is bit-identical to qt_gemm_i8's on the same arguments: acc is an exact int32 sum in any
+ *   order, so S partial sums over disjoint k-ranges, added in int32, are acc; the chain t -> tot = 0.0f + s_w t -> y
+ *   above then runs literally, once per output element.  Two launches on the caller's stream.  (1) A workgroup is
+ *   (tile, split): split s owns the K-tiles (QT_SPLITK_I8_K_UNIT k-bytes each) [t0(s), t1(s)) that
+ *   qt_splitk_gemm_i8_range deals -- contiguous, sizes differing by at most one -- and stores its int32 accumulators,
+ *   unchanged, into slab s of the workspace: int32 [S][Mp][Np] row-major, Mp = 256 ceil(M/256), Np = 256 ceil(N/256).
+ *   Tile rows and columns past M or N are computed from the clamped source rows, as in qt_gemm_i8_ring, and land in
+ *   the slab's padding, which nothing ever reads.  (2) The reduce pass reads the S slabs at m < M, n < N only, adds
+ *   them in int32 and runs the epilogue.  The workspace need not be initialised.  No byte outside Xq[M, K], Wq[N, K]
+ *   is read, no element outside Y[m < M, n < N] and no byte past workspace_size is written.  Deterministic, no
+ *   atomics, no communication between workgroups inside a launch: a row's result depends on the row, the weight and
+ *   the epilogue inputs alone.  
+ * qt_splitk_gemm_i8_plan: host-only, no device needed: the split count and the workspace size for (M, N, K) on a
+ *   device of `cus` compute units.  splits_requested == 0: tiles = ceil(M/256) ceil(N/256), kt = K / QT_SPLITK_I8_K_UNIT,
+ *   S = clamp(cus / tiles, 1, min(max(kt / QT_SPLITK_I8_MIN_K_TILES, 1), QT_SPLITK_I8_MAX_SPLITS)) -- about one
+ *   workgroup per compute unit, and no split shorter than QT_SPLITK_I8_MIN_K_TILES K-tiles (two trips round the ring;
+ *   the measured rule).  splits_requested >= 1: that S, refused (QT_ERR_INVALID) above min(K / QT_SPLITK_I8_K_UNIT,
+ *   QT_SPLITK_I8_MAX_SPLITS).  *workspace_size = S Mp Np 4 bytes (also for S == 1, which qt_splitk_gemm_i8 refuses).
+ * qt_splitk_gemm_i8_range: host-only: the K-tiles [*t0, *t1) of split s out of `splits` over k_tiles K-tiles:
+ *   t0 = s q + min(s, r) with q = k_tiles / splits, r = k_tiles % splits; the first r splits hold q + 1.
+ *
  * qt_act_mul_quantize_i8: the glue between the two products of an MLP in one row pass -- h = act(gate) * up as torch's
  *   two elementwise kernels leave it in a 16-bit tensor, then qt_quantize_tokens_i8 on h -- without h ever reaching
  *   memory.  gate and up are [M, K] bf16 / fp16 (x_dtype) with unit column stride and row pitches ldg, ldu >= K; they may
@@ -503,6 +532,9 @@ enum qt_act { QT_ACT_SILU = 0 };
 #define QT_I8_RING_W4_K_UNIT 128
 #define QT_I8_RING_W4_SLOTS 8
 #define QT_I8_RING_W4_LEAD 6
+#define QT_SPLITK_I8_K_UNIT 128
+#define QT_SPLITK_I8_MAX_SPLITS 32
+#define QT_SPLITK_I8_MIN_K_TILES 4
 #define QT_MOE_I8_WIDE_K_UNIT 128
 #define QT_MOE_I8_WIDE_TILE_ROWS 128
 #define QT_MOE_I8_WIDE_MAX_E 4096
@@ -530,6 +562,13 @@ int qt_gemm_i8_ring_w4(const int8_t* Xq, int64_t M, int K, const void* Wq, int w
 int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                    const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                    int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_splitk_gemm_i8_plan(int64_t M, int N, int K, int cus, int splits_requested, int* splits,
+                           size_t* workspace_size);
+int qt_splitk_gemm_i8_range(int k_tiles, int splits, int s, int* t0, int* t1);
+int qt_splitk_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                      const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                      int out_dtype, int64_t ldy, int splits, void* workspace, size_t workspace_size,
+                      qt_stream_t stream);
 
 /* ---- Routed experts: W8A8 / INT8 / W4A8 sparse-MoE banks on the same int8 GEMM ------------------------------
  * The A8 expert forward (engine/qlinear.py QuantizedExperts) restates transformers' MixtralExperts.forward with the

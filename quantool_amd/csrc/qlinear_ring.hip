@@ -33,6 +33,15 @@
 // row are wave-uniform, so the B base (expert e's matrix) and, for contiguous rows, the A base stay scalar.  With row_idx
 // the A base is Xq itself and each lane's 32-bit offset is row_idx[m] K + 16 c (the host refuses x_rows K > 2^32; the
 // index is clamped into [0, x_rows)).  A tile row past the expert's last row re-reads that expert's last row.
+//
+// qt_splitk_gemm_i8: the same tile over a k-range (ring_tile<false, true>), for 129-2047 rows over a long reduction,
+// where the whole-K ring has 16-64 tiles for 256 CUs.  A workgroup is (tile, split): split s owns
+// K-tiles [t0(s), t1(s)) (splitk_range), its fetches start at k-byte 128 t0 and it runs 4 (t1 - t0) units.  A split of
+// one K-tile is nu = 4 < LEAD: the prologue and the drain ladder take it as they take K = 128.  Nothing else of the
+// pipeline knows about the split.  In place of the epilogue the accumulators go, unchanged, into slab s of an int32
+// [S][Mp][Np] workspace, the tile's padding included; gemm_i8_splitk_reduce_kernel adds the S slabs in int32 at m < M,
+// n < N and runs the epilogue once.  The int32 sum is exact in any order, so Y is qt_gemm_i8's to the bit.  Two
+// launches, no atomics, no communication between workgroups inside a launch.
 #include "common.h"
 #include "i8_args.h"
 #include "i8_ring_tile.h"
@@ -54,8 +63,24 @@ struct RingArgs {
     int out_dtype;
 };
 
-template <bool MOE>
-__device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
+// The split-K mode (qt_splitk_gemm_i8): a workgroup is (tile, split) = (blockIdx.x, blockIdx.y) and stores its int32
+// accumulators into slab blockIdx.y of int32 [splits][Mp][Np] instead of running the epilogue
+struct RingSplit {
+    int32_t* slab;
+    int64_t Mp, Np;                                   // 256 ceil(M/256), 256 ceil(N/256)
+    int splits;
+};
+
+// K-tiles [t0, t1) of split s out of S over kt K-tiles: contiguous, the first kt % S splits hold one more
+__host__ __device__ __forceinline__ void splitk_range(int kt, int S, int s, int& t0, int& t1) {
+    const int q = kt / S, r = kt % S;
+    t0 = s * q + (s < r ? s : r);
+    t1 = t0 + q + (s < r ? 1 : 0);
+}
+
+template <bool MOE, bool SPLIT = false>
+__device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g, const RingSplit& sk = RingSplit{}) {
+    static_assert(!(MOE && SPLIT), "the split mode is dense");
     __shared__ __attribute__((aligned(16))) char ring[RING * UNIT_BYTES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -91,7 +116,13 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
         if constexpr (MOE) return i8_ring_moe_src_row(g, m);
         return m;
     };
-    const int nu = K / KU * 4;                        // units = phases
+    int kt0 = 0, kt = K / KU;                         // K-tiles [kt0, kt0 + kt) are this workgroup's
+    if constexpr (SPLIT) {
+        int t1;
+        splitk_range(K / KU, sk.splits, (int)blockIdx.y, kt0, t1);
+        kt = t1 - kt0;                                // >= 1: the host refuses splits > K / KU
+    }
+    const int nu = kt * 4;                            // units = phases
 
     // ---- staging geometry: two LDS-DMA instructions per thread per unit (pieces 2 wave, 2 wave + 1) ----
     // lane: row lane >> 3 of its piece, physical chunk lane & 7; the logical chunk goes into the source address
@@ -113,6 +144,10 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     const unsigned dst_wave = __builtin_amdgcn_readfirstlane(ring_lds + wave * 2048);  // wave-uniform
     const int8_t* srcA = p.Xq + m0 * (int64_t)K;      // scalar: k-byte 0 of the tile's first row
     const int8_t* srcB = Wq + (int64_t)n0 * K;
+    if constexpr (SPLIT) {                            // k-byte 128 kt0 of both panels: issue() counts K-tiles from here
+        srcA += (size_t)kt0 * KU;
+        srcB += (size_t)kt0 * KU;
+    }
     if constexpr (MOE) {
         if (g.row_idx) {                              // gathered rows: offsets from Xq itself, < x_rows K <= 2^32
             srcA = p.Xq;
@@ -218,6 +253,24 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
     }
     ring_stagger_end(group_b);
 
+    if constexpr (SPLIT) {
+        // ---- the partial sums, unchanged, into this split's slab: the whole tile, padding included (rows past M and
+        // columns past N come from the clamped source rows and are never read).  m0 + 255 < Mp and n0 + 255 < Np, so
+        // no store needs a bounds test.  A wave-store is two runs of 32 lanes x 4 B = two 128-byte lines ----
+        int32_t* slab = sk.slab + ((int64_t)blockIdx.y * sk.Mp + m0) * sk.Np + n0;   // scalar
+#pragma unroll
+        for (int qa = 0; qa < 2; ++qa)
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t row = i8_ring_cd_row(qa * HP + wave_m * 64 + mi * 32, r, lh);
+                        slab[row * sk.Np + (qb * HP + wave_n * 32 + lr)] = acc[qa][qb][mi][r];
+                    }
+        return;
+    }
     // ---- epilogue: qt_gemm_i8's sequence, once per output element, by the lane that holds it ----
     const bool asym = p.zp_x != nullptr;
 #pragma unroll
@@ -254,6 +307,62 @@ __device__ __forceinline__ void ring_tile(const RingArgs& p, const RingMoe& g) {
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_kernel(const RingArgs p) { ring_tile<false>(p, RingMoe{}); }
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_ring_moe_kernel(const RingArgs p, const RingMoe g) {
     ring_tile<true>(p, g);
+}
+// grid (tiles, splits): the tile's partial sum over its split's K-tiles -> slab blockIdx.y
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_i8_splitk_partial_kernel(const RingArgs p, const RingSplit sk) {
+    ring_tile<false, true>(p, RingMoe{}, sk);
+}
+
+// The second launch of qt_splitk_gemm_i8: for m < M, n < N the int32 sum of the S slabs, then qt_gemm_i8's epilogue
+// (the one above, statement for statement).  A thread owns four consecutive columns of one row: one 16-byte load per
+// slab (Np is a multiple of 256 and the slab base is 16-byte aligned); the last quad of a row with N % 4 != 0 is read
+// element by element, so no padded element is ever read.  grid (ceil(ceil(N/4) / 256), min(M, 65535)): rows stride
+// by gridDim.y.  The sum is integer: no partial is ever converted before it is complete.
+constexpr int REDUCE_THREADS = 256;
+__global__ __launch_bounds__(REDUCE_THREADS) void gemm_i8_splitk_reduce_kernel(const RingArgs p, const RingSplit sk) {
+    const int n = 4 * (int)(blockIdx.x * REDUCE_THREADS + threadIdx.x);
+    if (n >= p.N) return;
+    const int cnt = p.N - n;                          // columns of this quad that exist: 4 or more is a whole quad
+    const bool asym = p.zp_x != nullptr;
+    const bool has_bias = p.bias != nullptr;
+    const int64_t stride = sk.Mp * sk.Np;
+    float sw[4], bn[4];
+    int ws[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int nj = j < cnt ? n + j : n;
+        sw[j] = p.s_w[nj];
+        ws[j] = asym ? p.wsum[nj] : 0;
+        bn[j] = has_bias ? qt_load_w(p.bias, p.out_dtype, nj) : 0.0f;
+    }
+    for (int64_t m = blockIdx.y; m < p.M; m += gridDim.y) {
+        const int32_t* src = sk.slab + m * sk.Np + n;
+        i32x4 a = (i32x4){};
+        if (cnt >= 4) {
+#pragma unroll 4
+            for (int s = 0; s < sk.splits; ++s) a += *(const i32x4*)(src + s * stride);
+        } else {
+            for (int s = 0; s < sk.splits; ++s) {
+                const int32_t* e = src + s * stride;
+                a[0] += e[0];
+                if (cnt > 1) a[1] += e[1];
+                if (cnt > 2) a[2] += e[2];
+            }
+        }
+        const int zp = asym ? p.zp_x[m] : 0;
+        const float sx = p.s_x[m];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= cnt) break;
+            int acc = a[j];
+            if (asym) acc = acc - zp * ws[j];
+            const float prod = sw[j] * (float)acc;
+            const float tv = 0.0f + prod;
+            float y = sx * tv;
+            if (has_bias) y = y + bn[j];
+            qt_store_w(p.Y, p.out_dtype, (size_t)(m * p.ldy + n + j), y);
+        }
+    }
 }
 
 }  // namespace
@@ -308,6 +417,83 @@ extern "C" int qt_gemm_i8_ring_grouped(const int8_t* Xq, int K, const int32_t* r
     RingArgs a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, nullptr, Y, R, N, K, ldy, out_dtype};
     RingMoe g{offsets, row_idx, x_rows, E};
     hipLaunchKernelGGL(gemm_i8_ring_moe_kernel, dim3((unsigned)tiles), dim3(NTHREADS), 0, stream, a, g);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+extern "C" int qt_splitk_gemm_i8_range(int k_tiles, int splits, int s, int* t0, int* t1) {
+    QT_CHECK_ARG(t0 && t1 && k_tiles > 0 && splits > 0 && splits <= k_tiles && s >= 0 && s < splits,
+                 "qt_splitk_gemm_i8_range: bad arguments");
+    splitk_range(k_tiles, splits, s, *t0, *t1);
+    return QT_OK;
+}
+
+extern "C" int qt_splitk_gemm_i8_plan(int64_t M, int N, int K, int cus, int splits_requested, int* splits,
+                                      size_t* workspace_size) {
+    static_assert(QT_SPLITK_I8_K_UNIT == KU, "header constants");
+    QT_CHECK_ARG(splits && workspace_size && M > 0 && N > 0 && K > 0 && splits_requested >= 0,
+                 "qt_splitk_gemm_i8_plan: bad arguments");
+    QT_CHECK_ARG(splits_requested > 0 || cus > 0, "qt_splitk_gemm_i8_plan: cus %d: the rule needs the device's compute "
+                 "unit count", cus);
+    QT_CHECK_ARG(K % QT_SPLITK_I8_K_UNIT == 0, "qt_splitk_gemm_i8_plan: K %d is not a multiple of the k-unit %d", K,
+                 QT_SPLITK_I8_K_UNIT);
+    QT_CHECK_ARG(K <= 32768, "qt_splitk_gemm_i8_plan: K %d > 32768 (the int32 accumulator bound)", K);
+    const int64_t tiles_m = (M + BT - 1) / BT, tiles_n = ((int64_t)N + BT - 1) / BT;
+    QT_CHECK_ARG(tiles_m <= 0x7fffffffLL / tiles_n, "qt_splitk_gemm_i8_plan: too many tiles");
+    const int64_t tiles = tiles_m * tiles_n;
+    const int kt = K / QT_SPLITK_I8_K_UNIT;
+    const int cap = kt < QT_SPLITK_I8_MAX_SPLITS ? kt : QT_SPLITK_I8_MAX_SPLITS;
+    int S;
+    if (splits_requested == 0) {
+        // about one workgroup per compute unit: S tiles' worth of workgroups fill the device once; and no split
+        // shorter than QT_SPLITK_I8_MIN_K_TILES K-tiles: below that the slabs cost more than the splits save (4.24)
+        const int64_t want = cus / tiles;
+        const int longest = kt / QT_SPLITK_I8_MIN_K_TILES < cap ? kt / QT_SPLITK_I8_MIN_K_TILES : cap;
+        S = (int)(want < 1 || longest < 1 ? 1 : want > longest ? longest : want);
+    } else {
+        QT_CHECK_ARG(splits_requested <= kt, "qt_splitk_gemm_i8_plan: splits %d > K / %d = %d: a split owns at least "
+                     "one K-tile", splits_requested, QT_SPLITK_I8_K_UNIT, kt);
+        QT_CHECK_ARG(splits_requested <= QT_SPLITK_I8_MAX_SPLITS, "qt_splitk_gemm_i8_plan: splits %d > "
+                     "QT_SPLITK_I8_MAX_SPLITS = %d", splits_requested, QT_SPLITK_I8_MAX_SPLITS);
+        S = splits_requested;
+    }
+    *splits = S;
+    *workspace_size = (size_t)S * (size_t)(tiles_m * BT) * (size_t)(tiles_n * BT) * sizeof(int32_t);   // < 2^53
+    return QT_OK;
+}
+
+extern "C" int qt_splitk_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N,
+                                 const float* s_x, const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum,
+                                 const void* bias, void* Y, int out_dtype, int64_t ldy, int splits, void* workspace,
+                                 size_t workspace_size, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    QT_CHECK_ARG(w_format == QT_W_INT8, "qt_splitk_gemm_i8: w_format %d unsupported: int8 weights only (packed int4 "
+                 "runs on qt_gemm_i8)", w_format);
+    QT_CHECK_ARG(G == 1, "qt_splitk_gemm_i8: G %d unsupported: one scale group per row only (grouped scales run on "
+                 "qt_gemm_i8)", G);
+    QT_CHECK_ARG(K % QT_SPLITK_I8_K_UNIT == 0, "qt_splitk_gemm_i8: K %d is not a multiple of the k-unit %d", K,
+                 QT_SPLITK_I8_K_UNIT);
+    if (int st = qt_i8_check_dense("qt_splitk_gemm_i8", Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype,
+                                   ldy, true))
+        return st;
+    QT_CHECK_ARG(splits >= 1, "qt_splitk_gemm_i8: splits %d: take the count from qt_splitk_gemm_i8_plan", splits);
+    QT_CHECK_ARG(splits != 1, "qt_splitk_gemm_i8: splits 1 is qt_gemm_i8_ring (the same tile, no slab)");
+    QT_CHECK_ARG(workspace, "qt_splitk_gemm_i8: workspace is null");
+    QT_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "qt_splitk_gemm_i8: workspace is not 16-byte aligned");
+    int S = 0;
+    size_t need = 0;
+    if (int st = qt_splitk_gemm_i8_plan(M, N, K, 0, splits, &S, &need)) return st;
+    QT_CHECK_ARG(workspace_size >= need, "qt_splitk_gemm_i8: workspace_size %zu < %zu needed (S %d x Mp x Np x 4)",
+                 workspace_size, need, S);
+    const int64_t tiles_m = (M + BT - 1) / BT, tiles_n = ((int64_t)N + BT - 1) / BT;
+    RingArgs a{Xq, (const int8_t*)Wq, s_x, zp_x, s_w, wsum, bias, Y, M, N, K, ldy, out_dtype};
+    RingSplit sk{(int32_t*)workspace, tiles_m * BT, tiles_n * BT, S};
+    hipLaunchKernelGGL(gemm_i8_splitk_partial_kernel, dim3((unsigned)(tiles_m * tiles_n), (unsigned)S), dim3(NTHREADS), 0,
+                       stream, a, sk);
+    QT_LAUNCH_CHECK();
+    const int64_t quads = ((int64_t)N + 3) / 4;
+    const dim3 rgrid((unsigned)((quads + REDUCE_THREADS - 1) / REDUCE_THREADS), (unsigned)(M < 65535 ? M : 65535));
+    hipLaunchKernelGGL(gemm_i8_splitk_reduce_kernel, rgrid, dim3(REDUCE_THREADS), 0, stream, a, sk);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }

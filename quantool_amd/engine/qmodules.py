@@ -38,7 +38,11 @@ class QuantizedLinear(nn.Module):
     again, and 0 never uses it.
     Between the two, ``skinny_max_m`` < M <= ``mid_max_m`` runs the weight-streaming ``qt_gemm_i8_mid`` (both weight
     formats, bit-identical too) on a Linear with ``in_features`` >= ``mid_min_k`` and, when ``mid_max_n`` is not 0,
-    ``out_features`` <= ``mid_max_n``, where ``ops.gemm_i8_mid_supported`` holds; ``mid_max_m`` = 0 never uses it."""
+    ``out_features`` <= ``mid_max_n``, where ``ops.gemm_i8_mid_supported`` holds; ``mid_max_m`` = 0 never uses it.
+    Below the ring, ``splitk_min_m`` <= M < ``ring_min_m`` (or any M >= ``splitk_min_m`` when ``ring_min_m`` is 0) runs an
+    int8 weight with one scale group and ``in_features`` >= ``splitk_min_k`` on the ring's tile over S k-ranges plus an
+    int32 reduce pass, ``qt_splitk_gemm_i8``, where ``ops.splitk_gemm_i8_supported`` holds: bit-identical again, and
+    ``splitk_min_m`` = 0 never uses it."""
 
     # Decode GEMV up to this many rows: the measured crossover (DESIGN.md 4.11).
     skinny_max_m = 16
@@ -57,6 +61,14 @@ class QuantizedLinear(nn.Module):
     mid_max_m = 128
     mid_max_n = 6144
     mid_min_k = 512
+    # Split-K GEMM from this many rows up to the ring (0: never) and from this many input features: the loosest measured
+    # values for which every admitted (shape, M) cell is no slower than the tiled kernel in both runs.
+    # K = 14336 (down) and 28672 (70B's down) win at every M from 129 to 2047: 1.56 - 2.85x and 1.50 - 3.17x.  K = 4096
+    # does not qualify: q/k/v wins everywhere (1.05 - 1.58x) and o up to 1536 rows (1.02 - 1.97x), but o at 2047 rows
+    # loses (0.96 / 0.97x) and gate/up ties or loses at 129, 320, 384 and 640 rows (0.97 - 1.00x in one run or both);
+    # there is no bound on M from above or on N that would keep them out, so they stay on the tiled kernel.
+    splitk_min_m = 129
+    splitk_min_k = 14336
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -116,6 +128,11 @@ class QuantizedLinear(nn.Module):
               and ops.gemm_i8_mid_supported(Xq, self.weight, self.weight_scale)):
             # the attributes and the two sizes decide first: ops' mid names are read only past them
             gemm = ops.gemm_i8_mid
+        elif (self.splitk_min_m > 0 and M >= self.splitk_min_m and (self.ring_min_m == 0 or M < self.ring_min_m)
+              and not self.int4 and self.weight_scale.shape[1] == 1 and self.in_features >= self.splitk_min_k
+              and ops.splitk_gemm_i8_supported(Xq, self.weight, self.weight_scale)):
+            # the attributes and the sizes decide first: ops' splitk names are read only past them
+            gemm = ops.splitk_gemm_i8
         else:
             gemm = ops.gemm_i8
         return gemm(

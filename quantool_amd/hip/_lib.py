@@ -122,6 +122,11 @@ SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_mid": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "qt_splitk_gemm_i8_plan": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "qt_splitk_gemm_i8_range": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
+    # qt_gemm_i8's arguments, then splits, workspace, workspace_size in front of the stream
+    "qt_splitk_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "qt_gemm_i8_skinny_grouped": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64,
                                           c_void_p]),

@@ -6,6 +6,7 @@ assumption the kernels make is asserted on the host first).  No arithmetic happe
 """
 from __future__ import annotations
 
+import ctypes
 import logging
 import os
 from collections import namedtuple
@@ -15,7 +16,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import QT_BF16, QT_F16, QT_F32, check, load
+from ._lib import QT_BF16, QT_F16, QT_F32, HipBackendError, check, load
 
 _WS_CACHE: dict = {}
 
@@ -781,6 +782,9 @@ I8_MOE_RING_W4_FORM = I8Form("qt_moe_gemm_i8_ring_w4", experts=True, max_e=4096,
 # for the same reason.
 I8_MOE_WIDE_FORM = I8Form("qt_moe_gemm_i8_wide", experts=True, x_rows=True, max_e=4096, k_unit=128,
                           groups="one_or_per_unit", aligned16=True, tile_rows=128)
+# The short-prompt form: qt_gemm_i8_ring's tile over a k-range plus a reduce pass; it takes what the dense ring takes.
+# Beside the table for the same reason (its entry point carries a split count and a workspace behind ldy).
+I8_SPLITK_FORM = I8Form("qt_splitk_gemm_i8", **_RING)
 
 I8_SKINNY_MAX_M = I8_FORMS["qt_gemm_i8_skinny"].max_m   # rows of Xq qt_gemm_i8_skinny takes
 # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
@@ -798,6 +802,9 @@ MOE_I8_WIDE_K_UNIT = I8_MOE_WIDE_FORM.k_unit            # columns per k-block of
 MOE_I8_WIDE_TILE_ROWS = I8_MOE_WIDE_FORM.tile_rows      # rows of one expert a workgroup of qt_moe_gemm_i8_wide holds at most
 MOE_I8_WIDE_MAX_E = I8_MOE_WIDE_FORM.max_e              # experts qt_moe_gemm_i8_wide walks per workgroup
 MOE_I8_WIDE_MAX_SLOTS = 65535                           # row-tile slots: the grid's second dimension
+SPLITK_I8_K_UNIT = I8_SPLITK_FORM.k_unit                # k-bytes per K-tile of qt_splitk_gemm_i8 (QT_SPLITK_I8_K_UNIT)
+SPLITK_I8_MAX_SPLITS = 32                               # slabs its reduce pass adds at most (QT_SPLITK_I8_MAX_SPLITS)
+SPLITK_I8_MIN_K_TILES = 4                               # K-tiles of the shortest split the rule deals (QT_SPLITK_I8_MIN_K_TILES)
 
 
 def _i8_refusal(form: I8Form, Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
@@ -934,6 +941,71 @@ def gemm_i8_mid(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torc
     speculative verification, short prompts.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where
     ``gemm_i8_mid_supported`` is false."""
     return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_mid"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
+
+
+def splitk_gemm_i8_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
+    """Whether ``splitk_gemm_i8`` takes these operands: what ``gemm_i8_ring`` takes -- an int8 weight with one scale
+    group, K a multiple of ``SPLITK_I8_K_UNIT`` and at most 32768, both operands 16-byte aligned.  Host-only."""
+    return _i8_refusal(I8_SPLITK_FORM, Xq, Wq, s_w) is None
+
+
+def splitk_gemm_i8_plan(M: int, N: int, K: int, cus: Optional[int] = None, splits: int = 0):
+    """(S, workspace bytes) of ``qt_splitk_gemm_i8_plan``: with ``splits`` = 0 the rule
+    S = clamp(cus / (ceil(M/256) ceil(N/256)), 1, min(max(K/128 / SPLITK_I8_MIN_K_TILES, 1), SPLITK_I8_MAX_SPLITS)),
+    else that S (up to min(K/128, SPLITK_I8_MAX_SPLITS)) or ``ValueError``; the
+    size is S * Mp * Np * 4.  ``cus`` None: the current device's compute units.  The rule itself needs no device."""
+    if cus is None:
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    S, size = ctypes.c_int(0), ctypes.c_size_t(0)
+    try:
+        check("qt_splitk_gemm_i8_plan", load().qt_splitk_gemm_i8_plan(
+            M, N, K, cus, splits, ctypes.addressof(S), ctypes.addressof(size)))
+    except HipBackendError as e:
+        if e.status == _lib.QT_ERR_INVALID:
+            raise ValueError(str(e)) from None
+        raise
+    return S.value, size.value
+
+
+def splitk_ranges(K: int, splits: int):
+    """The K-tile ranges [(t0, t1), ...] ``qt_splitk_gemm_i8_range`` deals to ``splits`` splits of a reduction of K."""
+    lib, out = load(), []
+    t0, t1 = ctypes.c_int(0), ctypes.c_int(0)
+    for s in range(splits):
+        check("qt_splitk_gemm_i8_range", lib.qt_splitk_gemm_i8_range(
+            K // SPLITK_I8_K_UNIT, splits, s, ctypes.addressof(t0), ctypes.addressof(t1)))
+        out.append((t0.value, t1.value))
+    return out
+
+
+def splitk_gemm_i8(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                   K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                   wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                   out_dtype=torch.bfloat16, splits: int = 0) -> torch.Tensor:
+    """``gemm_i8`` on the ring tile over S k-ranges plus an int32 reduce pass (``qt_splitk_gemm_i8``): the short-prompt
+    form for W8A8 / INT8, a few tiles of rows over a long reduction.  Same arguments; Y equals ``gemm_i8``'s to the bit.
+    ``splits`` = 0 takes S from ``splitk_gemm_i8_plan``; where that gives S = 1 the call is ``gemm_i8_ring`` (the same
+    tile, no slab).  ``ValueError`` where ``splitk_gemm_i8_supported`` is false or ``splits`` exceeds K / 128."""
+    form = I8_SPLITK_FORM
+    why = _i8_refusal(form, Xq, Wq, s_w)
+    if why is not None:
+        raise ValueError(f"{form.entry[3:]}: {why}")
+    lib = load()
+    fmt, N, K, G = _i8_operands(Xq, s_x, Wq, s_w, K, zp_x, wsum, out_dtype)
+    M = Xq.shape[0]
+    S, size = splitk_gemm_i8_plan(M, N, K, splits=splits)
+    if S == 1:
+        return gemm_i8_ring(Xq, s_x, Wq, s_w, K=K, zp_x=zp_x, wsum=wsum, bias=bias, out_dtype=out_dtype)
+    if bias is not None:
+        _req(bias, out_dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in the output dtype")
+    ws = workspace(size, Xq.device, tag="splitk_gemm_i8")
+    Y = torch.empty((M, N), dtype=out_dtype, device=Xq.device)
+    check(form.entry, lib.qt_splitk_gemm_i8(
+        Xq.data_ptr(), M, K, Wq.data_ptr(), fmt, N, s_x.data_ptr(), _ptr(zp_x), s_w.data_ptr(), G, _ptr(wsum),
+        _ptr(bias), Y.data_ptr(), _dtype_code(Y), Y.stride(0), S, ws.data_ptr(), size, _stream()))
+    return Y
 
 
 def moe_route(top_k_index: torch.Tensor, num_experts: int):

@@ -2,11 +2,13 @@
 or ring_w4_min_m for W4A8).
 
   python tools/ppl_bench.py <dir> [--layers 8] [--batch 8] [--seq 2048] [--scheme W8A8|W4A8] [--ring-min-m M]
+  python tools/ppl_bench.py <dir> --layers 8 --batch 1 --seq 512 --splitk-min-m      # the split-K form at a short prompt
 
 The checkpoint is the random-init Llama-3-8B-shaped RTN model of tools/decode_bench.py in that scheme (written to <dir>
 when it is not there yet).  One loaded model runs ``perplexity`` over --batch x --seq random tokens as ``tiled`` (the
 attribute at 0) and ``ring`` (the class default, or --ring-min-m: the way to time a ring that ships turned off), each
-twice after one warm-up pass; wall seconds with the device synchronised.  The Linears agree to the bit, so the perplexities must be equal as floats.  Prints one JSON line.
+twice after one warm-up pass; wall seconds with the device synchronised.  With --splitk-min-m [M] the attribute that is
+switched is ``splitk_min_m`` instead (W8A8; 0 against the class default or M; the second mode is still called "ring").  The Linears agree to the bit, so the perplexities must be equal as floats.  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -35,6 +37,9 @@ def main():
     ap.add_argument("--seq", type=int, default=2048)
     ap.add_argument("--scheme", default="W8A8", choices=["W8A8", "W4A8"])
     ap.add_argument("--ring-min-m", type=int, default=None, help="the 'ring' mode's attribute value (default: the class's)")
+    ap.add_argument("--splitk-min-m", type=int, nargs="?", const=-1, default=None,
+                    help="switch splitk_min_m (0 vs the class default, or vs M) instead of the ring's attribute")
+    ap.add_argument("--splitk-min-k", type=int, default=None, help="with --splitk-min-m: splitk_min_k for both modes")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppl_bench needs a GPU")
@@ -47,8 +52,14 @@ def main():
     attr = "ring_min_m" if args.scheme == "W8A8" else "ring_w4_min_m"
     default = getattr(QuantizedLinear, attr)
     ring = default if args.ring_min_m is None else args.ring_min_m
+    if args.splitk_min_m is not None:
+        attr, default = "splitk_min_m", QuantizedLinear.splitk_min_m
+        ring = default if args.splitk_min_m < 0 else args.splitk_min_m
+        if args.splitk_min_k is not None:
+            QuantizedLinear.splitk_min_k = args.splitk_min_k
     result = {"metric": f"evaluate.perplexity wall seconds, {args.scheme}, {attr} = 0 vs {ring}", "layers": args.layers,
-              "tokens": args.batch * args.seq, attr: ring, "class_default": default,
+              "tokens": args.batch * args.seq, "seq": args.seq, attr: ring, "class_default": default,
+              "splitk_min_k": QuantizedLinear.splitk_min_k,
               "device": torch.cuda.get_device_name(0),
               "quantized_linears": sum(isinstance(m, QuantizedLinear) for m in model.modules()), "modes": {}}
     try:

@@ -5,6 +5,7 @@ tiled GEMM at decode sizes.
   python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
   python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
   python tools/qlinear_bench.py --ring-w4 [--ms 2048,4096,8192]   # W4A8 prefill: qt_gemm_i8 vs qt_gemm_i8_ring_w4
+  python tools/qlinear_bench.py --splitk [--splits 4]  # 129 .. 2047 rows: qt_gemm_i8 vs qt_gemm_i8_ring vs qt_splitk_gemm_i8
   python tools/qlinear_bench.py --mlp [--ms 1,16,32,128,2048,8192]     # three Linears + glue vs QuantizedMLP
   python tools/qlinear_bench.py --norm [--ms 1,16,32,128,2048,8192]    # RMSNorm + 3 (2) quantisers vs one fused launch
 
@@ -39,6 +40,15 @@ medians), with ``bits_equal`` per cell.
 the LDS-ring qt_gemm_i8_ring_w4 on the same operands, with qt_quantize_tokens_i8 and bf16 F.linear, under the "ring"
 rows' harness, at --ms (default 2048,4096,8192) on the three shapes, with ``bits_equal`` per cell and tiled / ring as
 "speedup".  ``QuantizedLinear.ring_w4_min_m`` is set from two such runs.
+
+--splitk prints only "splitk" rows (W8A8, symmetric activations) at M = 129, 192, 256, 320, 384, 512, 640, 768, 1024, 1536,
+2047 (``--ms`` picks others) on q/k/v, o (4096 x 4096), gate/up, down and Llama-3-70B's down (8192 x 28672; ``--shapes``
+picks among them): the tiled qt_gemm_i8 (the yardstick), the whole-K ring qt_gemm_i8_ring, qt_splitk_gemm_i8 at the
+rule's S (``--splits S`` forces another; a cell where S exceeds K / 128 is skipped), bf16 F.linear and torch._int_mm,
+under the "ring" rows' harness (alternating call by call, per-call events, weights rotating over more than 512 MiB of
+copies, medians), with ``bits_equal`` per cell, tiled / split-K as "speedup", and "reduce_share": the reduce kernel's
+part of the two launches' device time, as torch's profiler reports them.  ``QuantizedLinear.splitk_min_m`` /
+``splitk_min_k`` are set from two such runs.
 
 --mlp prints only "mlp" rows: a Llama-3-8B MLP (hidden 4096, intermediate 14336) as W8A8 and W4A8, at --ms (default
 1,16,32,128,2048,8192).  "glue": ``F.silu(g) * u`` followed by qt_quantize_tokens_i8 (three launches) against
@@ -241,6 +251,85 @@ def ring_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+def kernel_shares(fn, calls=5):
+    """{kernel name: device microseconds per call} over ``calls`` calls of ``fn`` (torch's profiler), or the reason."""
+    try:
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.events():
+            if e.device_type == DeviceType.CUDA and "memcpy" not in e.name.lower():
+                out[e.name] = out.get(e.name, 0.0) + e.device_time / calls
+        return out
+    except Exception as e:  # noqa: BLE001
+        return {"reason": f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"}
+
+
+def splitk_rows(shape, N, K, ms, splits, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_gemm_i8_ring vs qt_splitk_gemm_i8 at short-prompt sizes, W8A8 (int8 channel-wise, symmetric
+    activations), beside bf16 F.linear and torch._int_mm: the "ring" rows' harness."""
+    rows = []
+    q = torch.randint(-128, 128, (N, K), device=dev, generator=g, dtype=torch.int8)
+    s_w = torch.rand(N, 1, device=dev, generator=g) * 1e-3
+    n_cp = max(3, -(-int(COLD_BYTES * 1.1) // q.numel()))
+    cps = [q.clone() for _ in range(n_cp)]
+    cps_t = [c.t() for c in cps]
+    n_bf = max(2, -(-int(COLD_BYTES * 1.1) // (2 * q.numel())))
+    bfs = [(torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16) for _ in range(n_bf)]
+    del q
+    for M in ms:
+        S, ws_bytes = ops.splitk_gemm_i8_plan(M, N, K)
+        if splits:
+            if splits > min(K // ops.SPLITK_I8_K_UNIT, ops.SPLITK_I8_MAX_SPLITS):
+                continue
+            S, ws_bytes = ops.splitk_gemm_i8_plan(M, N, K, splits=splits)
+        X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        Xq, s_x, _ = ops.quantize_tokens_i8(X, symmetric=True)
+        # kernels that share a rep read different copies, or the second finds the first's weights cached
+        fns = {"gemm_i8": lambda i: ops.gemm_i8(Xq, s_x, cps[i % n_cp], s_w),
+               "gemm_i8_ring": lambda i: ops.gemm_i8_ring(Xq, s_x, cps[(i + 1) % n_cp], s_w),
+               "splitk_gemm_i8": lambda i: ops.splitk_gemm_i8(Xq, s_x, cps[(i + 2) % n_cp], s_w, splits=S),
+               "bf16_linear": lambda i: F.linear(X, bfs[i % n_bf])}
+        try:
+            torch._int_mm(Xq, cps_t[0])
+            fns["torch_int_mm"] = lambda i: torch._int_mm(Xq, cps_t[i % n_cp])
+        except Exception:  # noqa: BLE001  (the prefill rows report the reason)
+            pass
+        t = time_pair(fns, reps, warmup)
+        want = fns["gemm_i8"](0).view(torch.int16)
+        same = torch.equal(want, fns["splitk_gemm_i8"](0).view(torch.int16))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        row = {"shape": shape, "scheme": "W8A8", "M": M, "N": N, "K": K, "splits": S, "workspace_bytes": ws_bytes,
+               "cold_copies": n_cp, "bits_equal": same,
+               "us": {k: round(v * 1e6, 2) for k, v in med.items()},
+               "min_us": {k: round(min(v) * 1e6, 2) for k, v in t.items()},
+               "speedup": round(med["gemm_i8"] / med["splitk_gemm_i8"], 3),
+               "ring_over_splitk": round(med["gemm_i8_ring"] / med["splitk_gemm_i8"], 3),
+               "bf16_over_splitk": round(med["bf16_linear"] / med["splitk_gemm_i8"], 3)}
+        if "torch_int_mm" in med:
+            row["splitk_over_int_mm"] = round(med["splitk_gemm_i8"] / med["torch_int_mm"], 3)
+        if S > 1:
+            k = kernel_shares(lambda: fns["splitk_gemm_i8"](0))
+            red = [v for n, v in k.items() if "splitk_reduce" in n]
+            par = [v for n, v in k.items() if "splitk_partial" in n]
+            row["reduce_share"] = (round(red[0] / (red[0] + par[0]), 3) if red and par else k.get("reason", sorted(k)))
+            if red and par:
+                row["kernel_us"] = {"partial": round(par[0], 2), "reduce": round(red[0], 2)}
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr)
+        del X, Xq
+    del cps, cps_t, bfs
+    torch.cuda.empty_cache()
+    return rows
+
+
 def ring_w4_rows(shape, N, K, ms, reps, warmup, dev, g):
     """qt_gemm_i8 vs qt_gemm_i8_ring_w4 at prefill sizes, W4A8 (packed int4 g128, asymmetric activations), beside the
     activation pass and bf16 F.linear."""
@@ -289,6 +378,8 @@ def ring_w4_rows(shape, N, K, ms, reps, warmup, dev, g):
     return rows
 
 
+SPLITK_MS = "129,192,256,320,384,512,640,768,1024,1536,2047"
+SPLITK_SHAPES = {**SHAPES, "o": (4096, 4096), "down_70b": (8192, 28672)}
 MLP_MS = "1,16,32,128,2048,8192"
 MLP_HIDDEN, MLP_INTER = 4096, 14336
 
@@ -449,6 +540,9 @@ def main():
     ap.add_argument("--mid", action="store_true", help="only the tiled-vs-mid rows (17 .. 128 rows and neighbours)")
     ap.add_argument("--mid-shapes", default=",".join(MID_SHAPES))
     ap.add_argument("--ring-w4", action="store_true", help="only the W4A8 tiled-vs-ring rows (qt_gemm_i8_ring_w4)")
+    ap.add_argument("--splitk", action="store_true",
+                    help="only the tiled-vs-ring-vs-split-K rows (qt_splitk_gemm_i8) at 129 .. 2047 rows")
+    ap.add_argument("--splits", type=int, default=0, help="with --splitk: this S instead of the rule's")
     ap.add_argument("--mlp", action="store_true",
                     help="only the MLP rows: three QuantizedLinears + torch's glue vs QuantizedMLP (qt_act_mul_quantize_i8)")
     ap.add_argument("--norm", action="store_true",
@@ -478,6 +572,18 @@ def main():
             mid += mid_rows(shape, N, K, MID_MS, args.reps, args.warmup, dev, g)
         print(json.dumps({"metric": "qt_gemm_i8 vs qt_gemm_i8_mid, 17 .. 128 rows, cold weights", "hbm_peak": HBM_PEAK,
                           "device": torch.cuda.get_device_name(0), "reps": args.reps, "mid": mid}))
+        return
+    if args.splitk:
+        ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else SPLITK_MS).split(",") if m]
+        shapes = args.shapes if args.shapes != ap.get_default("shapes") else "qkv,o,gate_up,down,down_70b"
+        sk = []
+        for shape in shapes.split(","):
+            N, K = SPLITK_SHAPES[shape]
+            sk += splitk_rows(shape, N, K, ms, args.splits, args.reps, args.warmup, dev, g)
+        print(json.dumps({"metric": "qt_gemm_i8 vs qt_gemm_i8_ring vs qt_splitk_gemm_i8, W8A8, 129 .. 2047 rows, cold "
+                                    "weights", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                          "cus": torch.cuda.get_device_properties(0).multi_processor_count,
+                          "splits_forced": args.splits, "splitk": sk}))
         return
     if args.ring_w4:
         ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else "2048,4096,8192").split(",") if m]
