@@ -935,8 +935,9 @@ static int fac_panels(const CholCtx& c, const BlockRow& J) {
     const int rem = K - J1;
     if (c.g3->any) {
         // plane copies of the finished block row (columns from its diagonal block on; only entries above
-        // the diagonal are ever read back)
-        if (rem > 0) {
+        // the diagonal are ever read back).  The factorisation never reads the last block row's; the inverse does
+        // where one of its block rows starts inside it (QT_CHOL_NBI not a multiple of QT_CHOL_NBO): T_I takes R[:I0, I].
+        if (rem > 0 || (K - 1) / c.NBI * c.NBI > J0) {
             float* RJ = A + (size_t)J0 * K + J0;
             unsigned short* pl = c.Rpl + (size_t)J0 * K + J0;
             int rc = c.planes == G3_F16X2
@@ -983,10 +984,13 @@ static int inv_product(const CholCtx& c, const BlockRow& I) {
 static int split_row(const CholCtx& c, const BlockRow& I) {
     const int K = c.K, I0 = I.J0;
     if (!c.g3->any || I.J1 >= K) return QT_OK;
+    // up to the end of the row's last 256-column tile: a later product starts tile column tj's k range at row 256 tj
+    // and reads whole tile columns, so a row that ends inside one (QT_CHOL_NBI = 128) owes it the zeros above the diagonal
+    const int tile_end = (I.J1 + CHOL_TILE - 1) / CHOL_TILE * CHOL_TILE, cols = tile_end < K ? tile_end : K;
     if (c.planes == G3_F16X2)
-        return qt_split2h_launch(c.Y + (size_t)I0 * K, K, I.rows(), I.J1, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.eY,
+        return qt_split2h_launch(c.Y + (size_t)I0 * K, K, I.rows(), cols, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.eY,
                                  c.stream, c.nprob, c.sY, c.sW * 2);
-    return qt_split3_launch(c.Y + (size_t)I0 * K, K, I.rows(), I.J1, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.stream,
+    return qt_split3_launch(c.Y + (size_t)I0 * K, K, I.rows(), cols, c.Ypl + (size_t)I0 * K, K, c.plane_stride, 1, I0, 0, c.stream,
                             c.nprob, c.sY, c.sW * 2);
 }
 

@@ -9,7 +9,10 @@ were added, and a kernel must reproduce the integer reference bit for bit.  This
 * ``assert_exactly_summable``: the guard every case calls on its own inputs before it launches;
 * ``assert_exact``: the comparator (elementwise equality, a report that names the first wrong entry and its tile);
 * restatements of the two plane splits of csrc/gemm3_tn.hip and of the token plan of csrc/xtx.hip;
-* ``fake_xtx``: a numpy Gram sum that walks that plan, with switchable mutations, for the comparator's self-tests.
+* ``fake_xtx``: a numpy Gram sum that walks that plan, with switchable mutations, for the comparator's self-tests;
+* for the Cholesky chain (csrc/cholesky.hip): ``factorable_spd`` -- matrices whose factor, inverse factor and every
+  intermediate are short dyadic numbers --, their guard ``assert_exactly_factorable``, ``with_zero_pivot``,
+  ``min_eig_lb`` and ``fake_chol_chain``, a numpy fp32 blocked chain with switchable mutations.
 """
 import numpy as np
 import torch
@@ -269,3 +272,174 @@ def fake_xtx(X, G0, mutation=None):
                 acc += np.outer(Xa[64], Xb[64])
         G[r, c] += acc
     return G.astype(np.float32), where
+
+
+# ------------------------------------------------------------------------- exactly factorable matrices (Cholesky chain)
+# A symmetric positive definite matrix whose Cholesky factor, inverse factor and every intermediate of the blocked chain
+# of csrc/cholesky.hip are short dyadic numbers: the chain then has ONE correct answer to the bit, whatever the block
+# sizes, the order of a sum, the split of a k range or the arithmetic (fp32 fmaf chain, three bf16 planes, two fp16
+# planes) -- a wrong output is a term that is missing, doubled or misplaced, never rounding.
+CHOL_NB = 128         # panel block of the chain (NB in csrc/chol_layout.h)
+
+
+def factorable_spd(K, seed, n_factors, density, exps=(-1, 0, 1)):
+    """-> (A, R, Y) in fp64 with A = R^T R, R upper triangular, Y = R^-T (lower).
+    R = D (I + N_1) ... (I + N_f): N_i is zero but for the block [:cut_i, cut_i:], which holds {-1, 0, +1} at `density`
+    (distinct seeded cuts in [8, K - 8)), so N_i^2 = 0 and (I + N_i)^-1 = I - N_i; D = diag(2^e), e drawn from `exps`
+    (the pivots of A are 4^e).  Rinv = (I - N_f) ... (I - N_1) D^-1 is formed by the same products: no solve.
+    R[r][c], r < c, can be non-zero only where a cut lies in (r, c]: the cuts are therefore drawn one from each of
+    n_factors equal strata of [8, K - 8) and applied in a seeded order, so that with a stratum of at most 128 every
+    diagonal block of the chain has off-diagonal entries and every 128 k-rows of a product carry terms.
+    The chain's contract (flat reversal of Y): U[i][j] = Y[K-1-i][K-1-j], strict lower triangle zero -- `chol_expected`."""
+    assert K >= 18 and 1 <= n_factors <= K - 16
+    rng = np.random.default_rng(seed)
+    edges = np.linspace(8, K - 8, n_factors + 1).astype(np.int64)
+    cuts = rng.permutation(np.array([rng.integers(edges[i], edges[i + 1]) for i in range(n_factors)]))
+    d = np.exp2(rng.choice(np.asarray(exps, dtype=np.float64), size=K))
+    R = np.diag(d)
+    Rinv = np.diag(1.0 / d)
+    for cut in cuts:
+        blk = rng.choice([-1.0, 1.0], size=(cut, K - cut)) * (rng.random((cut, K - cut)) < density)
+        R[:, cut:] += R[:, :cut] @ blk                       # R (I + N)
+        Rinv[:cut, :] -= blk @ Rinv[cut:, :]                 # (I - N) Rinv
+    return R.T @ R, R, np.ascontiguousarray(Rinv.T)
+
+
+# K -> (n_factors, density) of the cases the tests use (seed = K; the batches also K + 1, K + 2): R is 11-25 % dense in
+# its triangle, every diagonal 128-block has off-diagonal entries, and every bound of chol_exact_bounds keeps more
+# than 4x headroom below 2^24 (tests/test_exact_inputs.py checks each)
+CHOL_CASES = {129: (4, 0.1), 333: (8, 0.04), 640: (12, 0.015), 1000: (12, 0.012), 1536: (12, 0.008)}
+
+
+def chol_case(K, seed=None, exps=(-1, 0, 1)):
+    """factorable_spd at the parameters of CHOL_CASES, seed K unless given."""
+    return factorable_spd(K, K if seed is None else seed, *CHOL_CASES[K], exps=exps)
+
+
+def chol_expected(Y):
+    """What ``qt_cholesky_inverse_upper`` must return for A = R^T R: U[i][j] = Y[K-1-i][K-1-j] (upper, zeros below)."""
+    return np.ascontiguousarray(np.asarray(Y)[::-1, ::-1])
+
+
+def min_eig_lb(A):
+    """A valid ``min_eig_lb`` argument of the bounded entry points: half of fp64 eigvalsh(A)[0]."""
+    return 0.5 * float(np.linalg.eigvalsh(np.asarray(A, dtype=np.float64))[0])
+
+
+def with_zero_pivot(A, R, j, factor=1):
+    """A - factor * R[j][j]^2 e_j e_j^T: pivot j of the factorisation is exactly 0 (factor 1) or -R[j][j]^2 (factor 2);
+    every earlier pivot and every earlier row of R is unchanged."""
+    B = np.array(A, dtype=np.float64)
+    B[j, j] -= factor * R[j, j] ** 2
+    return B
+
+
+def chol_scale_exponent(bound):
+    """The device's g3 scale exponent of a bound on |x|: 3 - ceil(log2(bound)) (chol_scales_kernel forms it from log2f)."""
+    return int(3 - np.ceil(np.log2(float(bound))))
+
+
+def _single_f16_plane(x, e):
+    """x * 2^e is an fp16 value (split2h_kernel: hi == xs, lo' == 0) for every entry."""
+    xs = np.asarray(x, dtype=np.float32) * np.float32(2.0 ** e)
+    hi = xs.astype(np.float16).astype(np.float32)
+    lo = ((xs - hi) * np.float32(2048.0)).astype(np.float16).astype(np.float32)
+    return bool(np.array_equal(hi, xs)) and not lo.any()
+
+
+def chol_exact_bounds(A, R, Y):
+    """The largest sum |terms| of each family of sums the chain forms, in units of that family's least significant bit
+    (R in halves, Rinv in quarters, A in quarters).  With P = |A| + |R|^T |R| (the factorisation's own sums):
+      fac    4 max P                       A[i][j] - sum_p R[p][i] R[p][j]: potf2 (iii), trsm_rt's updates, the folds,
+                                           both long products of the factor
+      solve  16 max(|Rinv|^T P)            X^T B: potf2 (ii), trsm_rt's Z_b -- a 32-row inverse times a partial sum of A
+      inv3   32 max(|Rinv| |R| |Rinv|)     Dinv^T T, Y_II T_I (the NEG products), trinv_mfma's X_b^T (I - R^T Z)
+      inv2   8 max(|R|^T |Rinv|^T)         T = R^T Y (both recurrences, the long product of the inverse), potf2 (i)'s
+                                           I - R^T Z, trinv_mfma's updates
+      inv2r  8 max(|R| |Rinv|)             trinv_batched_kernel (QT_CHOL_TRINV=div): x_i -= R[i][p] x_p sums over R's rows
+    -> dict name -> value; each must stay below 2^24."""
+    aA, aR, aRi = np.abs(A), np.abs(R), np.abs(Y).T
+    P = aA + aR.T @ aR
+    return dict(fac=4.0 * P.max(), solve=16.0 * (aRi.T @ P).max(), inv3=32.0 * (aRi @ aR @ aRi).max(),
+                inv2=8.0 * (aR.T @ aRi.T).max(), inv2r=8.0 * (aR @ aRi).max())
+
+
+def assert_exactly_factorable(A, R, Y):
+    """The precondition of every exact Cholesky case (a violation is a bug of the test, as with assert_exactly_summable):
+    R Rinv == I exactly; A, R and Y survive fp32; every entry of R and Y is a single plane of both splits (bf16x3: mid
+    = lo = 0; f16x2: lo' = 0 at the exponent the bound yields and at one less -- the device forms the exponent with
+    log2f + ceilf and may land one lower at an exact power of four); every bound of chol_exact_bounds is below 2^24, so
+    every partial sum of the factorisation, the panel solves and the inverse recurrences is exact in fp32 in any order.
+    -> the bounds."""
+    A, R, Y = (np.asarray(x, dtype=np.float64) for x in (A, R, Y))
+    K = A.shape[0]
+    assert np.array_equal(R, np.triu(R)) and np.array_equal(Y, np.tril(Y))
+    assert np.array_equal(R @ Y.T, np.eye(K)), "R Rinv != I"
+    assert np.array_equal(R.T @ R, A), "A != R^T R"
+    for name, x in (("A", A), ("R", R), ("Y", Y)):
+        assert np.array_equal(x.astype(np.float32).astype(np.float64), x), f"{name} does not survive fp32"
+    assert np.array_equal(R * 2, np.rint(R * 2)) and np.array_equal(Y * 4, np.rint(Y * 4)), "R in halves, Y in quarters"
+    for name, x, bound in (("R", R, np.sqrt(np.diag(A).max())), ("Y", Y, 1.0 / np.sqrt(min_eig_lb(A)))):
+        hi, mid, lo = split_bf16x3(x)
+        assert np.array_equal(hi.astype(np.float64), x) and not mid.any() and not lo.any(), f"{name}: not one bf16 plane"
+        assert np.abs(x).max() <= bound, f"{name}: the bound the scale exponent comes from does not hold"
+        e = chol_scale_exponent(bound)
+        assert _single_f16_plane(x, e) and _single_f16_plane(x, e - 1), f"{name}: not one fp16 plane at 2^{e} / 2^{e - 1}"
+    bounds = chol_exact_bounds(A, R, Y)
+    for name, v in bounds.items():
+        assert v < 2.0 ** 24, f"{name}: sum|terms| = {v} lsb is not below 2^24"
+    return bounds
+
+
+def fake_chol_chain(A, mutation=None, nb=CHOL_NB):
+    """A plain fp32 numpy restatement of the chain, left-looking by `nb`-row blocks: per block row j the product
+    A[j, j:] -= R[:j0, j]^T R[:j0, j:], the diagonal block's factor, the panel solve with the block's inverse; then
+    Y = R^-T block row by block row -- T = R[:i0, i]^T Y[:i0, :i0] with every `nb`-wide tile column's k range starting at
+    its own first row (Y is lower triangular), Y[i, :i0] = -Dinv_i^T T -- and the flat reversal.  Only A's upper triangle
+    is read.  `mutation` breaks it the way an indexing bug would:
+      "drop_chunk"   the factor's product of the LAST block row leaves out the 64 k-rows [64, 128);
+      "late_k"       tile column 0 of the inverse's product of the LAST block row starts its k range one block late.
+    -> (U float32 [K, K], info)."""
+    A = np.triu(np.asarray(A, dtype=np.float32))
+    K = A.shape[0]
+    R = np.zeros((K, K), dtype=np.float32)
+    Dinv = {}
+    starts = list(range(0, K, nb))
+    for j0 in starts:
+        j1 = min(K, j0 + nb)
+        S = A[j0:j1, j0:].copy()
+        if j0 > 0:
+            keep = np.ones(j0, dtype=bool)
+            if mutation == "drop_chunk" and j0 == starts[-1]:
+                keep[64:128] = False
+            S -= R[:j0, j0:j1][keep].T @ R[:j0, j0:][keep]
+        n = j1 - j0
+        Rjj = np.zeros((n, n), dtype=np.float32)
+        D = S[:, :n].copy()
+        for c in range(n):                                   # right-looking, one row per step (potf2's step c)
+            piv = D[c, c]
+            if not piv > 0:
+                return np.eye(K, dtype=np.float32), j0 + c + 1
+            Rjj[c, c:] = D[c, c:] / np.sqrt(piv)
+            D[c + 1:, c + 1:] -= np.outer(Rjj[c, c + 1:], Rjj[c, c + 1:])
+        X = np.eye(n, dtype=np.float32)                      # X = Rjj^-1 by back substitution, column by column
+        for p in range(n - 1, -1, -1):
+            X[p, :] /= Rjj[p, p]
+            X[:p, :] -= np.outer(Rjj[:p, p], X[p, :])
+        Dinv[j0] = X
+        R[j0:j1, j0:j1] = Rjj
+        R[j0:j1, j1:] = X.T @ S[:, n:]
+    Y = np.zeros((K, K), dtype=np.float32)
+    for i0 in starts:
+        i1 = min(K, i0 + nb)
+        Y[i0:i1, i0:i1] = Dinv[i0].T
+        if i0 == 0:
+            continue
+        T = np.zeros((i1 - i0, i0), dtype=np.float32)
+        for c0 in range(0, i0, nb):
+            k0 = c0
+            if mutation == "late_k" and i0 == starts[-1] and c0 == 0:
+                k0 = nb
+            T[:, c0:c0 + nb] = R[k0:i0, i0:i1].T @ Y[k0:i0, c0:c0 + nb]
+        Y[i0:i1, :i0] = -(Dinv[i0].T @ T)
+    return np.ascontiguousarray(Y[::-1, ::-1]), 0

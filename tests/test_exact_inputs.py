@@ -1,5 +1,7 @@
 """CPU self-tests of tests/exact_inputs.py: the generators give what they promise, the guard refuses inputs whose
-partial sums could round, and the comparator flags each mutation of a numpy Gram sum at the right tile."""
+partial sums could round, and the comparator flags each mutation of a numpy Gram sum at the right tile; the exactly
+factorable matrices keep their identities and their guard, and a numpy fp32 blocked Cholesky chain gives their reference
+to the bit unless a k-chunk or a tile column's first block is left out."""
 import numpy as np
 import pytest
 import torch
@@ -171,3 +173,103 @@ def test_skipped_last_slab_chunk_is_flagged_in_its_tile_only(gram_case):
         _check(G, gram_case)
     assert where == (2, 2) and e.value.tiles == [(2, 2)]
     assert e.value.first[0] >= 512 and e.value.first[1] >= 512
+
+
+# ---- exactly factorable matrices (tests/test_gpu_chol_exact.py) ------------------------------------------------------
+CHOL_SEEDS = [(K, K) for K in ex.CHOL_CASES] + [(K, K + b) for K in (640, 1536) for b in (1, 2)]     # the batches' seeds
+
+
+@pytest.mark.parametrize("K,seed", CHOL_SEEDS)
+def test_factorable_spd_identities_and_guard(K, seed):
+    A, R, Y = ex.chol_case(K, seed)
+    bounds = ex.assert_exactly_factorable(A, R, Y)
+    print(f"\n[factorable] K={K} seed={seed}: " + ", ".join(f"{k} {v:.3g}" for k, v in bounds.items())
+          + f" (limit {2.0 ** 24:.3g}); max|R| {np.abs(R).max()}, max|Y| {np.abs(Y).max()}, max|A| {np.abs(A).max()}")
+    assert max(bounds.values()) * 4 < 2.0 ** 24                                    # headroom, not a near miss
+    assert set(np.unique(np.diag(R))) <= {0.5, 1.0, 2.0} and len(np.unique(np.diag(R))) == 3
+    assert np.array_equal(np.linalg.cholesky(A).T, R)                              # fp64 LAPACK agrees, exactly
+    U = ex.chol_expected(Y)
+    assert np.array_equal(U, np.triu(U)) and np.array_equal(U[0, 0], Y[K - 1, K - 1]) and np.array_equal(U[0, K - 1], Y[K - 1, 0])
+    # no zero factor hides a dropped term: the triangle is well filled and every diagonal 128-block but a last block
+    # of one row has off-diagonal entries
+    assert np.count_nonzero(R) >= 0.1 * K * (K + 1) / 2 and np.count_nonzero(Y) >= 0.1 * K * (K + 1) / 2
+    for b0 in range(0, K - 1, ex.CHOL_NB):
+        assert np.count_nonzero(np.triu(R[b0:b0 + ex.CHOL_NB, b0:b0 + ex.CHOL_NB], 1)) > 0, b0
+    lb = ex.min_eig_lb(A)
+    assert 0 < lb < np.linalg.eigvalsh(A)[0]
+
+
+def test_factorable_guard_trips_on_a_case_that_is_too_dense():
+    A, R, Y = ex.factorable_spd(640, 1, 12, 0.2)
+    assert np.array_equal(R @ Y.T, np.eye(640))                                    # still an exact inverse pair ...
+    with pytest.raises(AssertionError):
+        ex.assert_exactly_factorable(A, R, Y)                                      # ... whose sums no longer fit fp32
+    A, R, Y = ex.chol_case(333)
+    with pytest.raises(AssertionError, match="R Rinv"):
+        ex.assert_exactly_factorable(A, R, np.tril(Y + np.eye(333)))
+    R3 = R.copy()
+    R3[0, 1] = 1.0 + 2.0 ** -9                                                     # two bf16 planes
+    with pytest.raises(AssertionError):
+        ex.assert_exactly_factorable(R3.T @ R3, R3, np.linalg.inv(R3).T)
+
+
+@pytest.fixture(scope="module", params=[333, 640])
+def chol_case(request):
+    A, R, Y = ex.chol_case(request.param)
+    ex.assert_exactly_factorable(A, R, Y)
+    return A, R, ex.chol_expected(Y)
+
+
+def test_fp32_blocked_chain_gives_the_reference_to_the_bit(chol_case):
+    A, R, want = chol_case
+    poisoned = A.copy()
+    poisoned[np.tril_indices(A.shape[0], -1)] = np.nan
+    U, info = ex.fake_chol_chain(poisoned)
+    assert info == 0 and U.dtype == np.float32
+    ex.assert_exact(U, want, what="fake chain")
+    U64, _ = ex.fake_chol_chain(A, nb=64)                                          # ... whatever the blocking
+    ex.assert_exact(U64, want, what="fake chain, 64-row blocks")
+
+
+def test_chain_with_a_k_chunk_left_out_is_flagged(chol_case):
+    """64 k-rows missing from the factor's product of the last block row: its rows of R, hence of Y, hence the FIRST rows
+    of U are wrong, and nothing else."""
+    A, R, want = chol_case
+    K = A.shape[0]
+    last = (K - 1) // ex.CHOL_NB * ex.CHOL_NB
+    U, info = ex.fake_chol_chain(A, "drop_chunk")
+    assert info == 0
+    with pytest.raises(ex.ExactMismatch) as e:
+        ex.assert_exact(U, want, what="fake chain, chunk dropped")
+    bad_rows = np.flatnonzero((U.astype(np.float64) != want).any(axis=1))
+    assert e.value.count > 0 and e.value.tile[0] == 0 and bad_rows.max() < K - last
+
+
+def test_chain_with_a_tile_column_started_one_block_late_is_flagged(chol_case):
+    """The inverse's product of the last block row skips the first 128 k-rows of tile column 0: Y[last rows, :128], i.e.
+    the first rows and last 128 columns of U, and nothing else."""
+    A, R, want = chol_case
+    K = A.shape[0]
+    last = (K - 1) // ex.CHOL_NB * ex.CHOL_NB
+    U, info = ex.fake_chol_chain(A, "late_k")
+    assert info == 0
+    with pytest.raises(ex.ExactMismatch) as e:
+        ex.assert_exact(U, want, what="fake chain, late k")
+    bad = np.argwhere(U.astype(np.float64) != want)
+    assert e.value.count == len(bad) > 0
+    assert bad[:, 0].max() < K - last and bad[:, 1].min() >= K - ex.CHOL_NB
+    assert e.value.tile[0] == 0 and e.value.tile[1] >= (K - ex.CHOL_NB) // ex.TILE
+
+
+@pytest.mark.parametrize("factor", [1, 2])
+def test_zero_and_negative_pivots_are_placed_exactly(chol_case, factor):
+    A, R, _ = chol_case
+    K = A.shape[0]
+    for j in (0, 31, 32, 127, 128, K - 70, K - 1):
+        B = ex.with_zero_pivot(A, R, j, factor)
+        assert np.array_equal(np.delete(B.ravel(), j * K + j), np.delete(A.ravel(), j * K + j))
+        U, info = ex.fake_chol_chain(B)
+        assert info == j + 1 and np.array_equal(U, np.eye(K, dtype=np.float32))
+        # the pivot itself: exactly 0 / -R[j][j]^2 in fp64, with the rows before it those of R
+        piv = B[j, j] - R[:j, j] @ R[:j, j]
+        assert piv == -(factor - 1) * R[j, j] ** 2
