@@ -88,6 +88,23 @@ int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, const int64_t* 
 int qt_xtx_batched_plan(const int64_t* n_tokens, int n_problems, int K, int32_t* items, int max_items, int* n_items,
                         int* n_slabs, size_t* workspace_bytes);
 
+/* The two calls above with a bound on the length of every fp32 accumulator chain INSIDE the launch.  chain_tokens is 0
+ * (no bound: exactly the unchained call, its kernels and its bits) or a positive multiple of 640; anything else is
+ * QT_ERR_INVALID, checked before every other argument.  Every chain_tokens tokens of its work item (counted from the
+ * item's own first token) a workgroup runs its epilogue, zeroes its accumulators and goes on: an item that owns its
+ * tile adds into G, an item of a split tile stores into its private slab the first time and adds into it afterwards.
+ * So a tile with one owner ends as (((G + p1) + p2) + ...), p_i the fp32 MFMA sum over span i: bit for bit what
+ * qt_xtx_accumulate computes for that tile when called on the chain_tokens-token slices one after the other.  Rounding
+ * error then grows with sqrt(chain_tokens) + sqrt(spans) instead of sqrt(tokens) (figures: DESIGN 4.1).
+ * Same plans, same workspace (qt_xtx_workspace_bytes / qt_xtx_batched_plan) and same determinism as the unchained
+ * calls; no atomics.  With a ragged token count and ldx != K (two launches) the bound applies to the first launch; the
+ * second holds 64 token rows. */
+int qt_xtx_accumulate_chained(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
+                              int64_t chain_tokens, void* workspace, size_t workspace_bytes, qt_stream_t stream);
+int qt_xtx_accumulate_batched_chained(const void* const* X, int x_dtype, const int64_t* n_tokens, const int64_t* ldx,
+                                      int K, float* const* G, int n_problems, int64_t chain_tokens, void* workspace,
+                                      size_t workspace_bytes, qt_stream_t stream);
+
 /* The same accumulation for fp32 activations X [n_tokens, K] (an fp32 checkpoint: upstream's `inp.float()` is
  * then an fp32 Gram product).  fp32-accurate on the bf16 MFMA: the tokens are split into three
  * bf16 planes (residual <= 2^-27 |x|) and the six plane products of weight >= 2^-16 are summed in one fp32

@@ -26,6 +26,20 @@
 //        issue into 2u+2, beside group B's outstanding reads.)
 //   In flight at every wait: L-1 units = N*(L-1) LDS-DMA instructions per wave; never vmcnt(0) inside the loop.
 //   Past the last unit nothing is issued, and the drain ladder lowers the count with the units that still exist.
+// MID-LOOP FLUSH (the CHAIN forms of xtx_kernel / xtx16_kernel).  Between phase u-1 and phase u, where u is a multiple
+// of the ring (slot numbers stay immediates), a wave may run plain global loads and stores of its own -- the epilogue's
+// read-modify-write of G or of its slab -- provided it ends them with vmcnt(0).  Nothing above is disturbed:
+//   - the flush holds no barrier, so the intervals keep their numbers and both groups their barrier counts; it only
+//     lengthens the interval it stands in (2u for group A, 2u+1 for group B).  WAR is an argument about interval
+//     numbers alone (issue in LOAD, reads retired at the lgkmcnt(0) of MATH) and the flush issues no LDS-DMA.
+//   - RAW: unit u was retired by the counted wait of LOAD(u-1), in front of the barriers of phase u-1, as always.  The
+//     compiler's own vmcnt waits inside the flush count only the flush's loads; the counter is in order, so they wait
+//     for the older LDS-DMA too -- MORE than the ring needs, which is safe: the hazard argument is about minimum waits.
+//   - the counted wait of LOAD(u) assumes that the N*(L-1) youngest outstanding operations are the ring's.  Stores of
+//     the flush still in flight would be counted in their place (stores and loads share vmcnt on gfx9 and need not
+//     retire in order against each other), hence the closing vmcnt(0): behind it nothing is outstanding, units
+//     u+1 .. u+L-1 have landed early, and the following waits are satisfied sooner than they ask.
+//   The cost is one short bubble per flush: the L-1 units in flight are waited for at once, with no MFMA under them.
 // The instances:
 //   xtx_kernel    R 8, L 6, unit = 16 tokens (16 KiB),             N 2: vmcnt(10), 5 units = 80 KiB per CU in flight
 //   xtx16_kernel  R 5, L 3, unit = a pair of those ("double", 32 KiB), N 4: vmcnt(8), 2 doubles = 64 KiB in flight

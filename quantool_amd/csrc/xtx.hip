@@ -55,6 +55,9 @@ struct XtxParams {
     int thr_win;         // throttle: units a workgroup may lead the slowest started member by
     int thr_nap;         // throttle: s_sleep argument of one nap (x64 cycles)
     int thr_chk;         // throttle: units between two progress checks (a power of two, 8..256; 32 by default)
+    // CHAIN instantiations only (qt_xtx_accumulate*_chained): no fp32 accumulator chain is longer than this many tokens,
+    // a positive multiple of CHAIN_STEP, counted from the item's own first token
+    int chain_tokens;
     // DOT variant of xtx16_kernel (qt_xtx_frobenius): instead of storing its tile, every item writes
     // <H tile, its partial tile> (lower triangle, off-diagonal entries twice) to dot_partials[item]
     const float* H;
@@ -66,6 +69,12 @@ struct XtxParams {
     const struct XtxBItem* b_items;   // [grid] in logical order
     const struct XtxBProb* b_probs;   // [n_problems]
 };
+// chain_tokens fills what was padding: no member moved, and the kernels that do not read it kept their text
+static_assert(sizeof(XtxParams) == 160, "a new member of XtxParams moves the hidden kernel arguments behind it");
+
+// A flush may stand only between whole ring bodies: 8 units (128 tokens) in xtx_kernel, 5 doubles (160 tokens) in
+// xtx16_kernel.  A bound that is a multiple of both cuts the chains of both shapes at the same tokens.
+constexpr int CHAIN_STEP = 640;
 
 // Records of the batched launch (device tables in the caller's workspace, built by xtx_batched_plan on the host)
 struct XtxBItem {       // 32 B: one workgroup's work
@@ -144,8 +153,14 @@ __device__ __forceinline__ int xtx_item(const XtxParams& p, int logical, int& tt
 // units ahead of the slowest STARTED, unfinished member sleeps a bounded while (its other waves wait
 // at the phase barrier).  No workgroup ever waits FOR another: no spin, no dependence on residency.
 
-template <bool WRAP, bool F16, bool THROTTLE>
+//
+// CHAIN (qt_xtx_accumulate_chained): every p.chain_tokens tokens of its item, between two ring bodies, the
+// workgroup runs the epilogue -- a direct item adds its accumulators into G, a slab item stores (first time) or adds
+// them into its own slab -- zeroes them and goes on, so no fp32 chain is longer than that.  Each tile (each slab) has
+// one owner, so this needs no atomics; the flush adds no barrier and ends in vmcnt(0) (ring_pipe.h, MID-LOOP FLUSH).
+template <bool WRAP, bool F16, bool THROTTLE, bool CHAIN = false>
 __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
+    static_assert(!(WRAP && CHAIN), "the ablation has no chained form");
     constexpr int LEAD = 6;     // unit u+LEAD is issued in phase u  (LEAD <= RING-2: hazard analysis in ring_pipe.h)
     // ONE LDS object: the ring (+ 1 KiB of scratch for the throttle's progress snapshot).
     // Unit image: [4 channel groups: A-lo, A-hi, B-lo, B-hi][16 tokens][256 B].
@@ -312,6 +327,69 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
         if (THROTTLE && throttled && (u & (p.thr_chk - 1)) == 0) throttle_step(u);
         ring_body<8>([&](auto slot_c, int uu) { phase(slot_c, steady_c, uu); }, u);
     };
+    // CHAIN: the epilogue as a flush.  Plain C++ like the epilogue below; the row / column of the lane pass through an
+    // empty asm so that none of the 128 addresses is loop-invariant (hoisted out of the ring loop they would spill).
+    bool slab_started = false;                                      // wave-uniform: this item's slab holds a partial sum
+    [[maybe_unused]] auto chain_flush = [&](bool last) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        int row0 = wave_m * 128 + 4 * (lane >> 5), col0 = wave_n * 64 + (lane & 31);
+        asm volatile("" : "+v"(row0), "+v"(col0));
+        if (slab_idx < 0) {
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    const int gj = tj * BT + col0 + ni * 32;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int gi = ti * BT + row0 + mi * 32 + (r & 3) + 8 * (r >> 2);
+                        if (gi < K && gj < K) {
+                            float* dst = p.G + (size_t)gi * K + gj;
+                            *dst = *dst + acc[mi][ni][r];
+                        }
+                    }
+                }
+        } else {
+            float* slab = p.slabs + (size_t)slab_idx * (size_t)(BT * BT) + row0 * BT + col0;
+            if (slab_started) {
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            float* dst = slab + (mi * 32 + (r & 3) + 8 * (r >> 2)) * BT + ni * 32;
+                            *dst = *dst + acc[mi][ni][r];
+                        }
+            } else {
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            slab[(mi * 32 + (r & 3) + 8 * (r >> 2)) * BT + ni * 32] = acc[mi][ni][r];
+            }
+            slab_started = true;
+        }
+        if (last) return;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
+        // the ring's counted waits assume that only its own LDS-DMA is outstanding: retire the flush's loads and stores
+        wait_vmcnt<0>();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int next_cut = CHAIN ? p.chain_tokens / UT : 0x7fffffff;        // in units; a multiple of 8 (CHAIN_STEP)
+    auto chain_cut = [&](int u) __attribute__((always_inline)) {                                   // u < nu: tokens follow the cut
+        if (CHAIN && u == next_cut) {
+            chain_flush(false);
+            next_cut += p.chain_tokens / UT;
+        }
+    };
 
     if (nu > 0) {
         // prologue: units 0..LEAD-1 in flight, unit 0 landed
@@ -326,9 +404,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
         const int steady_end = (nu < i_tail ? nu : i_tail);
         run_src += (size_t)LEAD * ustride;
         int u = 0;
-        for (; u + 8 + LEAD <= steady_end; u += 8) body8(std::true_type{}, u);
-        for (; u + 8 <= nu; u += 8) body8(std::false_type{}, u);
+        for (; u + 8 + LEAD <= steady_end; u += 8) {
+            if constexpr (CHAIN) chain_cut(u);
+            body8(std::true_type{}, u);
+        }
+        for (; u + 8 <= nu; u += 8) {
+            if constexpr (CHAIN) chain_cut(u);
+            body8(std::false_type{}, u);
+        }
         if (u < nu) {  // nu is a multiple of 4: one half body left
+            if constexpr (CHAIN) chain_cut(u);
             phase(std::integral_constant<int, 0>{}, std::false_type{}, u);
             phase(std::integral_constant<int, 1>{}, std::false_type{}, u + 1);
             phase(std::integral_constant<int, 2>{}, std::false_type{}, u + 2);
@@ -343,6 +428,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx_kernel(XtxParams p) {
     }
 
     // ---- epilogue ----------------------------------------------------------------------------
+    if constexpr (CHAIN) {      // what is left since the last cut, by the same code as the cuts
+        chain_flush(true);
+        return;
+    }
     const int jl = lane & 31, ih = 4 * (lane >> 5);
     if (slab_idx < 0) {
         // the only workgroup of this tile in this launch: G += acc (launches on a stream are ordered)
@@ -396,9 +485,13 @@ constexpr int DBL_BYTES = 2 * UNIT_BYTES;
 // BATCHED (qt_xtx_accumulate_batched): several problems of one K in one launch.  The workgroup's item (problem, tile,
 // token tiles, slab) and its problem (X, tail, G, pitch) come from two device tables, read once with wave-uniform
 // loads into locals; nothing in the by-value argument struct is indexed or modified.  No throttle.
-template <bool F16, bool DOT = false, bool BATCHED = false>
+//
+// CHAIN: as in xtx_kernel, a flush every p.chain_tokens tokens of the item (between two trips round the ring); plain and
+// BATCHED forms only.
+template <bool F16, bool DOT = false, bool BATCHED = false, bool CHAIN = false>
 __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
     static_assert(!(DOT && BATCHED), "the fused product has its own batch form");
+    static_assert(!(DOT && CHAIN), "the fused product stores no tile: nothing to flush");
     constexpr int ND = 5;       // doubles resident in LDS
     constexpr int LEAD = 3;     // double d+LEAD is issued in phase d  (LEAD <= ND-2)
     __shared__ __attribute__((aligned(16))) char ring[RING16 * UNIT_BYTES];
@@ -515,6 +608,66 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
         }
         ring_sync_math([&] { ring_mma16<F16>(fa, fb, acc); });
     };
+    // CHAIN: the epilogue as a flush (see xtx_kernel)
+    bool slab_started = false;
+    [[maybe_unused]] auto chain_flush = [&](bool last) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        int row0 = wave_m * 128 + 4 * (lane >> 4), col0 = wave_n * 64 + (lane & 15);
+        asm volatile("" : "+v"(row0), "+v"(col0));
+        if (slab_idx < 0) {
+#pragma unroll
+            for (int ai = 0; ai < 8; ++ai)
+#pragma unroll
+                for (int bj = 0; bj < 4; ++bj) {
+                    const int gj = tj * BT + col0 + bj * 16;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int gi = ti * BT + row0 + ai * 16 + r;
+                        if (gi < K && gj < K) {
+                            float* dst = Gp + (size_t)gi * K + gj;
+                            *dst = *dst + acc[ai][bj][r];
+                        }
+                    }
+                }
+        } else {
+            float* slab = p.slabs + (size_t)slab_idx * (size_t)(BT * BT) + row0 * BT + col0;
+            if (slab_started) {
+#pragma unroll
+                for (int ai = 0; ai < 8; ++ai)
+#pragma unroll
+                    for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float* dst = slab + (ai * 16 + r) * BT + bj * 16;
+                            *dst = *dst + acc[ai][bj][r];
+                        }
+            } else {
+#pragma unroll
+                for (int ai = 0; ai < 8; ++ai)
+#pragma unroll
+                    for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) slab[(ai * 16 + r) * BT + bj * 16] = acc[ai][bj][r];
+            }
+            slab_started = true;
+        }
+        if (last) return;
+#pragma unroll
+        for (int ai = 0; ai < 8; ++ai)
+#pragma unroll
+            for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[ai][bj][r] = 0.0f;
+        wait_vmcnt<0>();        // the ring's counted waits assume that only its own LDS-DMA is outstanding
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int next_cut = CHAIN ? p.chain_tokens / (2 * UT) : 0x7fffffff;  // in doubles; a multiple of ND (CHAIN_STEP)
+    auto chain_cut = [&](int d) __attribute__((always_inline)) {                                   // d < nd: tokens follow the cut
+        if (CHAIN && d == next_cut) {
+            chain_flush(false);
+            next_cut += p.chain_tokens / (2 * UT);
+        }
+    };
 
     if (nd > 0) {
 #pragma unroll
@@ -527,10 +680,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
         const int steady_end = (nd < d_tail ? nd : d_tail);
         run_src += (size_t)LEAD * 2 * ustride;
         int d = 0;
-        for (; d + ND + LEAD <= steady_end; d += ND)
+        for (; d + ND + LEAD <= steady_end; d += ND) {
+            if constexpr (CHAIN) chain_cut(d);
             ring_body<ND>([&](auto slot_c, int dd) { phase(slot_c, std::true_type{}, dd); }, d);
+        }
         // d is a multiple of 5 here: the remaining phases take slots 0, 1, 2, ... in turn
         for (; d < nd; d += ND) {
+            if constexpr (CHAIN) chain_cut(d);
             phase(std::integral_constant<int, 0>{}, std::false_type{}, d);
             if (d + 1 < nd) phase(std::integral_constant<int, 1>{}, std::false_type{}, d + 1);
             if (d + 2 < nd) phase(std::integral_constant<int, 2>{}, std::false_type{}, d + 2);
@@ -572,6 +728,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void xtx16_kernel(XtxParams p) {
             for (int w = 1; w < 8; ++w) t += red[w];
             p.dot_partials[item_global] = t;
         }
+        return;
+    }
+    if constexpr (CHAIN) {      // what is left since the last cut, by the same code as the cuts
+        chain_flush(true);
         return;
     }
     if (slab_idx < 0) {
@@ -855,22 +1015,30 @@ extern "C" size_t qt_xtx_workspace_bytes(int64_t n_tokens, int K) {
     return pl.slab_bytes + pl.tail_bytes + pl.tab_bytes + pl.prog_bytes + 256;
 }
 
-extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
-                                 void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
+// chain_tokens of the *_chained entry points: 0 (no bound: today's kernels) or a positive multiple of CHAIN_STEP
+static int xtx_chain_arg_ok(const char* fn, int64_t chain_tokens) {
+    QT_CHECK_ARG(chain_tokens >= 0 && chain_tokens % CHAIN_STEP == 0 && chain_tokens <= 0x7fffffff / 2,
+                 "%s: chain_tokens=%lld must be 0 or a positive multiple of %d", fn, (long long)chain_tokens, CHAIN_STEP);
+    return QT_OK;
+}
+
+// qt_xtx_accumulate (chain_tokens = 0) and qt_xtx_accumulate_chained: one body, `fn` names the caller in messages
+static int xtx_accumulate_impl(const char* fn, const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
+                               int chain_tokens, void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "qt_xtx_accumulate: x_dtype %d must be QT_BF16 or QT_F16", x_dtype);
-    QT_CHECK_ARG(K > 0 && K % 8 == 0, "qt_xtx_accumulate: K=%d must be a positive multiple of 8", K);
-    QT_CHECK_ARG(ldx >= K && ldx % 8 == 0, "qt_xtx_accumulate: ldx=%lld must be >= K and a multiple of 8", (long long)ldx);
-    QT_CHECK_ARG(n_tokens >= 0, "qt_xtx_accumulate: n_tokens < 0");
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "%s: x_dtype %d must be QT_BF16 or QT_F16", fn, x_dtype);
+    QT_CHECK_ARG(K > 0 && K % 8 == 0, "%s: K=%d must be a positive multiple of 8", fn, K);
+    QT_CHECK_ARG(ldx >= K && ldx % 8 == 0, "%s: ldx=%lld must be >= K and a multiple of 8", fn, (long long)ldx);
+    QT_CHECK_ARG(n_tokens >= 0, "%s: n_tokens < 0", fn);
     if (n_tokens == 0) return QT_OK;
-    QT_CHECK_ARG(X && G, "qt_xtx_accumulate: null pointer");
-    QT_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)G & 15) == 0, "qt_xtx_accumulate: X and G must be 16-byte aligned");
+    QT_CHECK_ARG(X && G, "%s: null pointer", fn);
+    QT_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)G & 15) == 0, "%s: X and G must be 16-byte aligned", fn);
     // per-lane source offsets are 32-bit: 16 token rows of one unit must span < 4 GiB
-    QT_CHECK_ARG((uint64_t)ldx * 2 * UT + (uint64_t)K * 2 < ((uint64_t)1 << 32), "qt_xtx_accumulate: ldx too large");
+    QT_CHECK_ARG((uint64_t)ldx * 2 * UT + (uint64_t)K * 2 < ((uint64_t)1 << 32), "%s: ldx too large", fn);
     XtxPlan pl = xtx_plan(n_tokens, K);
     const size_t need = pl.slab_bytes + pl.tail_bytes + pl.tab_bytes + pl.prog_bytes + 256;
     if (workspace_bytes < need || !workspace) {
-        qt_set_error("qt_xtx_accumulate: workspace %zu < required %zu", workspace_bytes, need);
+        qt_set_error("%s: workspace %zu < required %zu", fn, workspace_bytes, need);
         return QT_ERR_WORKSPACE;
     }
     char* ws = (char*)qt_align_up((size_t)workspace, 256);
@@ -879,7 +1047,7 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
     int* tile_tab = (int*)(ws + pl.slab_bytes + pl.tail_bytes);
     const int* host_tab = xtx_host_table(K, pl.n_tiles);
     if (!host_tab) {
-        qt_set_error("qt_xtx_accumulate: could not build the tile table for K=%d", K);
+        qt_set_error("%s: could not build the tile table for K=%d", fn, K);
         return QT_ERR_HIP;
     }
     QT_HIP(hipMemcpyAsync(tile_tab, host_tab, (size_t)pl.n_tiles * 4, hipMemcpyHostToDevice, stream));
@@ -911,6 +1079,9 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
     p.dot_partials = nullptr;
     p.batch_items = 1;
     p.x_batch_bytes = 0;
+    p.b_items = nullptr;
+    p.b_probs = nullptr;
+    p.chain_tokens = 0;
     p.wrap_units = 0;
 #ifdef QT_XTX_ABLATION   // lab builds only (tools/xtx_wrap_sweep.sh): the shipped library has no way into xtx_kernel<true>
     {
@@ -928,18 +1099,19 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
     const char* thr_env = getenv("QT_XTX_THROTTLE");
     const bool throttle_on = thr_env ? atoi(thr_env) != 0 : true;
     unsigned* progress_ws = (unsigned*)(ws + pl.slab_bytes + pl.tail_bytes + pl.tab_bytes);
-    auto launch = [&](const XtxParams& q, const XtxPlan& ql) -> int {
+    auto launch = [&](const XtxParams& q, const XtxPlan& ql, int chain) -> int {
         const int grid = ql.n_direct + ql.n_rem * ql.s2;
         qt_prof_mark(QT_PROF_XTX, stream);
         // the throttle pays where several rounds of long items stream more than the Infinity Cache holds
         XtxParams qq = q;
+        qq.chain_tokens = chain;
         // (measured: K = 14336, 6 rounds, 5.6 GB of X: +3...4 %; K = 8192, 2 rounds: -1 %)
         const bool thr = throttle_on && ql.n_direct >= 4 * NUM_CU && q.n_tt >= 512 &&
                          (size_t)q.n_tt * BKT * (size_t)q.K * 2 > ((size_t)1 << 30);
         if (thr) {
             const size_t rounds = (size_t)(ql.n_direct + NUM_CU - 1) / NUM_CU;
             if (hipMemsetAsync(progress_ws, 0, rounds * 256 * sizeof(unsigned), stream) != hipSuccess) {
-                qt_set_error("qt_xtx_accumulate: hipMemsetAsync(progress) failed");
+                qt_set_error("%s: hipMemsetAsync(progress) failed", fn);
                 return QT_ERR_HIP;
             }
             qq.progress = progress_ws;
@@ -957,7 +1129,18 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
         // QT_XTX_SHAPE=16|32 forces one (same-process A/B: tools/xtx_lab.py)
         const char* she = getenv("QT_XTX_SHAPE");
         const bool shape16 = she ? atoi(she) == 16 : !thr;
-        if (shape16 && q.wrap_units == 0) {
+        if (chain > 0) {
+            // the CHAIN instantiations of the same choice of shape and throttle (never the ablation's kernel)
+            const bool f16 = x_dtype == QT_F16;
+            if (shape16) {
+                qq.progress = nullptr;
+                if (f16) hipLaunchKernelGGL((xtx16_kernel<true, false, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+                else hipLaunchKernelGGL((xtx16_kernel<false, false, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+            } else if (thr && f16) hipLaunchKernelGGL((xtx_kernel<false, true, true, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+            else if (thr) hipLaunchKernelGGL((xtx_kernel<false, false, true, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+            else if (f16) hipLaunchKernelGGL((xtx_kernel<false, true, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+            else hipLaunchKernelGGL((xtx_kernel<false, false, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
+        } else if (shape16 && q.wrap_units == 0) {
             qq.progress = nullptr;
             if (x_dtype == QT_F16) hipLaunchKernelGGL((xtx16_kernel<true>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
             else hipLaunchKernelGGL((xtx16_kernel<false>), dim3(grid), dim3(NTHREADS), 0, stream, qq);
@@ -996,7 +1179,7 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
             pfp.n_direct = pf.n_direct;
             pfp.n_rem = pf.n_rem;
             pfp.s2 = pf.s2;
-            const int rc = launch(pfp, pf);
+            const int rc = launch(pfp, pf, chain_tokens);
             if (rc != QT_OK) return rc;
         }
         XtxPlan pt = xtx_plan(BKT, K);
@@ -1011,9 +1194,23 @@ extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, i
         ptp.n_direct = pt.n_direct;
         ptp.n_rem = 0;
         ptp.s2 = 1;
-        return launch(ptp, pt);
+        return launch(ptp, pt, 0);      // one token tile: nothing to cut
     }
-    return launch(p, pl);
+    return launch(p, pl, chain_tokens);
+}
+
+extern "C" int qt_xtx_accumulate(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
+                                 void* workspace, size_t workspace_bytes, qt_stream_t stream) {
+    return xtx_accumulate_impl("qt_xtx_accumulate", X, x_dtype, n_tokens, K, ldx, G, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int qt_xtx_accumulate_chained(const void* X, int x_dtype, int64_t n_tokens, int K, int64_t ldx, float* G,
+                                         int64_t chain_tokens, void* workspace, size_t workspace_bytes,
+                                         qt_stream_t stream) {
+    const char* fn = "qt_xtx_accumulate_chained";
+    const int crc = xtx_chain_arg_ok(fn, chain_tokens);
+    if (crc != QT_OK) return crc;
+    return xtx_accumulate_impl(fn, X, x_dtype, n_tokens, K, ldx, G, (int)chain_tokens, workspace, workspace_bytes, stream);
 }
 
 // ---- several Gram sums of one K in one launch ---------------------------------------------------------
@@ -1229,11 +1426,11 @@ extern "C" int qt_xtx_batched_plan(const int64_t* n_tokens, int n_problems, int 
     return QT_OK;
 }
 
-extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, const int64_t* n_tokens, const int64_t* ldx,
-                                         int K, float* const* G, int n_problems, void* workspace, size_t workspace_bytes,
-                                         qt_stream_t stream_) {
+// qt_xtx_accumulate_batched (chain_tokens = 0) and qt_xtx_accumulate_batched_chained: one body
+static int xtx_accumulate_batched_impl(const char* fn, const void* const* X, int x_dtype, const int64_t* n_tokens,
+                                       const int64_t* ldx, int K, float* const* G, int n_problems, int chain_tokens,
+                                       void* workspace, size_t workspace_bytes, qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const char* fn = "qt_xtx_accumulate_batched";
     QT_CHECK_ARG(qt_dtype_is16(x_dtype), "%s: x_dtype %d must be QT_BF16 or QT_F16", fn, x_dtype);
     const int arc = xtx_batched_args_ok(fn, n_tokens, n_problems, K);
     if (arc != QT_OK) return arc;
@@ -1266,7 +1463,8 @@ extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, cons
     }
     if (pl.single >= 0) {
         const int p = pl.single;
-        return qt_xtx_accumulate(X[p], x_dtype, n_tokens[p], K, ldx[p], G[p], workspace, workspace_bytes, stream_);
+        return xtx_accumulate_impl(fn, X[p], x_dtype, n_tokens[p], K, ldx[p], G[p], chain_tokens, workspace,
+                                   workspace_bytes, stream_);
     }
     char* ws = (char*)qt_align_up((size_t)workspace, 256);
     float* slabs = (float*)ws;
@@ -1312,9 +1510,14 @@ extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, cons
     q.batch_items = 1;
     q.b_items = (const XtxBItem*)(tabs + pl.item_off);
     q.b_probs = (const XtxBProb*)(tabs + pl.prob_off);
+    q.chain_tokens = chain_tokens;
     const int grid = (int)pl.items.size();
     qt_prof_mark(QT_PROF_XTX, stream);
-    if (x_dtype == QT_F16) hipLaunchKernelGGL((xtx16_kernel<true, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
+    if (chain_tokens > 0 && x_dtype == QT_F16)
+        hipLaunchKernelGGL((xtx16_kernel<true, false, true, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
+    else if (chain_tokens > 0)
+        hipLaunchKernelGGL((xtx16_kernel<false, false, true, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
+    else if (x_dtype == QT_F16) hipLaunchKernelGGL((xtx16_kernel<true, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
     else hipLaunchKernelGGL((xtx16_kernel<false, false, true>), dim3(grid), dim3(NTHREADS), 0, stream, q);
     qt_prof_mark(QT_PROF_XTX, stream);
     QT_LAUNCH_CHECK();
@@ -1324,6 +1527,24 @@ extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, cons
         QT_LAUNCH_CHECK();
     }
     return QT_OK;
+}
+
+extern "C" int qt_xtx_accumulate_batched(const void* const* X, int x_dtype, const int64_t* n_tokens, const int64_t* ldx,
+                                         int K, float* const* G, int n_problems, void* workspace, size_t workspace_bytes,
+                                         qt_stream_t stream) {
+    return xtx_accumulate_batched_impl("qt_xtx_accumulate_batched", X, x_dtype, n_tokens, ldx, K, G, n_problems, 0,
+                                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int qt_xtx_accumulate_batched_chained(const void* const* X, int x_dtype, const int64_t* n_tokens,
+                                                 const int64_t* ldx, int K, float* const* G, int n_problems,
+                                                 int64_t chain_tokens, void* workspace, size_t workspace_bytes,
+                                                 qt_stream_t stream) {
+    const char* fn = "qt_xtx_accumulate_batched_chained";
+    const int crc = xtx_chain_arg_ok(fn, chain_tokens);
+    if (crc != QT_OK) return crc;
+    return xtx_accumulate_batched_impl(fn, X, x_dtype, n_tokens, ldx, K, G, n_problems, (int)chain_tokens, workspace,
+                                       workspace_bytes, stream);
 }
 
 // ---- internal: loss = scale * <H, X^T X>_F without materialising X^T X (awq.hip) -----------------------------
@@ -1420,6 +1641,9 @@ int qt_xtx_frobenius(const void* X, int x_dtype, int64_t n_tokens, int K, int64_
     p.dot_partials = partials;
     p.batch_items = items;
     p.x_batch_bytes = x_batch_stride * 2;
+    p.b_items = nullptr;
+    p.b_probs = nullptr;
+    p.chain_tokens = 0;
     const int grid = items * n_batch;
     qt_prof_mark(QT_PROF_XTX, stream);
     if (x_dtype == QT_F16) hipLaunchKernelGGL((xtx16_kernel<true, true>), dim3(grid), dim3(NTHREADS), 0, stream, p);

@@ -124,8 +124,13 @@ class HessianAccumulator:
         # the fp64 Gram the default is 2.5e-6 of sqrt(Hii Hjj) at K = 14336 where upstream's order gives 7e-7 (DESIGN.md
         # 2.0).  Launches of n tokens make it a two-level sum (partial sums of n, then their sum), at the price of one
         # read-modify-write of G per launch (K = 14336: 0.2 ms each).
+        # QT_XTX_CHAIN_TOKENS=n (0 = off, the default; rounded down to a multiple of 640): the same bound INSIDE a launch
+        # -- the kernel folds its accumulators into G every n tokens and starts again (ops.xtx_accumulate(chain_tokens=n),
+        # DESIGN.md 4.1): no extra launches, no pipeline drain.  16-bit rows only.  With both knobs set the launches are
+        # split first and each launch is chained.
         self._after_flush()             # launches into G one after the other, whichever streams they are on
         limit = _launch_token_limit()
+        chain = _chain_token_limit()
         if limit <= 0 or rows.shape[0] <= limit:
             chunks = [rows]
         else:
@@ -133,6 +138,8 @@ class HessianAccumulator:
         for part in chunks:
             if part.dtype == torch.float32:
                 ops.xtx_accumulate_f32(part, self._G)
+            elif chain > 0:
+                ops.xtx_accumulate(part, self._G, chain_tokens=chain)
             else:
                 ops.xtx_accumulate(part, self._G)
 
@@ -154,7 +161,7 @@ class HessianAccumulator:
         over their staging buffers (``ops.xtx_accumulate_batched``; runs of at most 16).  Everything else is flushed
         alone, exactly as ``flush()`` does it: fp32 accumulators, the only member of its group, and any group with a
         member whose flush ``QT_XTX_LAUNCH_TOKENS`` would split.  Off, this is the loop ``for acc in accs:
-        acc.flush()``.
+        acc.flush()``.  ``QT_XTX_CHAIN_TOKENS`` goes to the batched launch as it goes to the single ones.
 
         Streams, as the class docstring promises for ``flush``: the flushing (current) stream first waits for every
         member's staging stream and for every member's earlier flush, and every member then records ``(stream, event)``
@@ -184,7 +191,12 @@ class HessianAccumulator:
                     if here is not None and acc._staged_on is not None and here != acc._staged_on:
                         here.wait_stream(acc._staged_on)
                     acc._after_flush()
-                ops.xtx_accumulate_batched([acc._stage[:acc._fill] for acc in run], [acc._G for acc in run])
+                chain = _chain_token_limit()
+                if chain > 0:
+                    ops.xtx_accumulate_batched([acc._stage[:acc._fill] for acc in run], [acc._G for acc in run],
+                                               chain_tokens=chain)
+                else:
+                    ops.xtx_accumulate_batched([acc._stage[:acc._fill] for acc in run], [acc._G for acc in run])
                 event = here.record_event() if here is not None else None
                 for acc in run:
                     acc._fill = 0
@@ -220,6 +232,17 @@ def _launch_token_limit() -> int:
 
     try:
         return max(0, int(os.environ.get("QT_XTX_LAUNCH_TOKENS", "0") or 0)) // 64 * 64
+    except ValueError:
+        return 0
+
+
+def _chain_token_limit() -> int:
+    """``QT_XTX_CHAIN_TOKENS``: the bound on an fp32 accumulator chain inside a Gram launch, rounded down to a multiple
+    of 640 tokens; unset, unreadable or below 640: 0 (off)."""
+    import os
+
+    try:
+        return max(0, int(os.environ.get("QT_XTX_CHAIN_TOKENS", "0") or 0)) // 640 * 640
     except ValueError:
         return 0
 

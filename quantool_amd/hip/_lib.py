@@ -30,6 +30,10 @@ SIGNATURES = {
     "qt_xtx_accumulate_batched": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                           c_void_p]),
     "qt_xtx_batched_plan": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "qt_xtx_accumulate_chained": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
+                                          c_void_p]),
+    "qt_xtx_accumulate_batched_chained": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
+                                                  c_void_p, c_size_t, c_void_p]),
     "qt_xtx_accumulate_f32_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "qt_xtx_accumulate_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "qt_act_stats_workspace_bytes": (c_size_t, [c_int64, c_int]),

@@ -128,9 +128,24 @@ def release_workspaces() -> None:
 
 
 # ---- a7 -----------------------------------------------------------------------------------
-def xtx_accumulate(X: torch.Tensor, G: torch.Tensor) -> None:
-    """G[K,K] fp32 (lower triangle) += X^T X for X[..., K] bf16 / fp16 (leading dims flattened)."""
+XTX_CHAIN_STEP = 640    # chain_tokens is 0 or a positive multiple of this (one cut grid for both MFMA shapes)
+
+
+def _chain_arg(chain_tokens) -> int:
+    chain = int(chain_tokens)
+    if chain < 0 or chain % XTX_CHAIN_STEP:
+        raise ValueError(f"chain_tokens={chain_tokens!r} must be 0 or a positive multiple of {XTX_CHAIN_STEP}")
+    return chain
+
+
+def xtx_accumulate(X: torch.Tensor, G: torch.Tensor, chain_tokens: int = 0) -> None:
+    """G[K,K] fp32 (lower triangle) += X^T X for X[..., K] bf16 / fp16 (leading dims flattened).
+
+    ``chain_tokens`` > 0 (a multiple of 640): no fp32 accumulator chain inside the launch covers more than that many
+    tokens -- the workgroups fold their accumulators into G (or their slab) at every cut and start again
+    (``qt_xtx_accumulate_chained``).  0: the plain call."""
     lib = load()
+    chain = _chain_arg(chain_tokens)
     xdt = _act16(X, "X")
     _req(G, torch.float32, "G", 2)
     K = G.shape[0]
@@ -145,6 +160,10 @@ def xtx_accumulate(X: torch.Tensor, G: torch.Tensor) -> None:
     ldx = X2.stride(0) if n > 1 else K
     nbytes = lib.qt_xtx_workspace_bytes(n, K)
     ws = workspace(nbytes, X.device, "xtx")
+    if chain:
+        check("qt_xtx_accumulate_chained", lib.qt_xtx_accumulate_chained(X2.data_ptr(), xdt, n, K, ldx, G.data_ptr(), chain,
+                                                                         ws.data_ptr(), ws.numel(), _stream()))
+        return
     check("qt_xtx_accumulate", lib.qt_xtx_accumulate(X2.data_ptr(), xdt, n, K, ldx, G.data_ptr(), ws.data_ptr(),
                                                      ws.numel(), _stream()))
 
@@ -181,14 +200,16 @@ def xtx_batched_workspace_bytes(n_tokens, K: int) -> int:
     return int(need.value)
 
 
-def xtx_accumulate_batched(Xs, Gs) -> None:
+def xtx_accumulate_batched(Xs, Gs, chain_tokens: int = 0) -> None:
     """``Gs[p]`` [K, K] fp32 (lower triangle) += ``Xs[p]``^T ``Xs[p]`` for every p, in one launch per 16 problems.
     One K, one 16-bit dtype and one device for the whole list; the token counts may differ.  Empty inputs are dropped;
     a strided input with a ragged token count (which the batched entry point refuses) goes through
-    ``xtx_accumulate``.  Bits: see ``qt_xtx_accumulate_batched`` in the header."""
+    ``xtx_accumulate``.  Bits: see ``qt_xtx_accumulate_batched`` in the header.  ``chain_tokens`` as in
+    ``xtx_accumulate``, counted from each work item's own first token (``qt_xtx_accumulate_batched_chained``)."""
     import ctypes
 
     lib = load()
+    chain = _chain_arg(chain_tokens)
     Xs, Gs = list(Xs), list(Gs)
     if len(Xs) != len(Gs):
         raise ValueError(f"{len(Xs)} inputs for {len(Gs)} Gram matrices")
@@ -214,7 +235,7 @@ def xtx_accumulate_batched(Xs, Gs) -> None:
         if n == 0:
             continue
         if n % 64 and n > 1 and X2.stride(0) != K:
-            xtx_accumulate(X2, G)           # ragged and strided: two launches of the single entry point
+            xtx_accumulate(X2, G, chain)    # ragged and strided: two launches of the single entry point
             continue
         batch.append((X2, G))
     for b0 in range(0, len(batch), XTX_BATCH_MAX):
@@ -225,6 +246,11 @@ def xtx_accumulate_batched(Xs, Gs) -> None:
         xp = (ctypes.c_void_p * m)(*[x.data_ptr() for x, _ in part])
         gp = (ctypes.c_void_p * m)(*[g.data_ptr() for _, g in part])
         ws = workspace(xtx_batched_workspace_bytes([x.shape[0] for x, _ in part], K), Xs[0].device, "xtx_batched")
+        if chain:
+            check("qt_xtx_accumulate_batched_chained",
+                  lib.qt_xtx_accumulate_batched_chained(xp, xdt, counts, pitches, K, gp, m, chain, ws.data_ptr(), ws.numel(),
+                                                        _stream()))
+            continue
         check("qt_xtx_accumulate_batched", lib.qt_xtx_accumulate_batched(xp, xdt, counts, pitches, K, gp, m, ws.data_ptr(),
                                                                          ws.numel(), _stream()))
 
