@@ -316,7 +316,8 @@ int qt_smoothquant_scales(const float* cmin, const float* cmax, const float* wma
  * allow_split_k != 0 lets latency-bound shapes split k over workgroups (ordered slab reduction:
  * deterministic, but no longer the single ascending chain -- the sweep never allows it).  The workspace is read
  * only with allow_split_k != 0, and is then required in full (QT_ERR_WORKSPACE otherwise: whether k is split must
- * follow from the shape alone); with allow_split_k == 0 it may be NULL. */
+ * follow from the shape alone); with allow_split_k == 0 it may be NULL.  kdim == 0 is the empty sum (Cout = Cin, 0,
+ * -0): A and B are not read and may be NULL. */
 size_t qt_sgemm_tn_f32_workspace_bytes(int M, int N);
 int qt_sgemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Cin,
                     int64_t ldcin, float* Cout, int64_t ldcout, int M, int N, int kdim, int skip_zero_k,

@@ -219,6 +219,78 @@ int orc_potrf_lower_f32(float* A, int K) {
     return 0;
 }
 
+/* ---- the fp32 TN GEMM building block (qt_sgemm_tn_f32), every output element --------
+ * acc[m][n] = fmaf(A[kk][m], B[kk][n], acc) for kk ascending from 0, acc starting at 0.0f:
+ * the order the contract above fixes wherever upstream leaves it to BLAS.  A[k, M] and
+ * B[k, N] are row-major with pitches lda / ldb (elements).
+ * bounds == NULL: one chain over [0, k).  Otherwise bounds[0] = 0 < ... < bounds[n_chunks] = k
+ * (n_chunks >= 1): every chunk [bounds[c], bounds[c + 1]) is a chain from 0.0f and the chunk
+ * sums are added by plain binary32 '+' in ascending c starting from 0.0f -- the sequence of
+ * the split-K reduction (csrc/sgemm_tn.hip: splitk_reduce_kernel).
+ * The mode comes last, as ONE binary32 operation: 0: Cin - v, 1: v, 2: -v.  Cin is read only
+ * in mode 0 and may be Cout (each element is read before it is written).
+ * variant 0 is the oracle.  1 (descending kk inside each chunk) and 2 (acc + a * b, two
+ * roundings) are the WRONG orders: tests/test_sgemm_oracle.py uses them to show that its
+ * inputs tell the orders apart.
+ */
+static void sgemm_tn_chain(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Cin,
+                           int64_t ldcin, float* Cout, int64_t ldcout, int M, int N, int k, int mode,
+                           const int32_t* bounds, int n_chunks, int variant) {
+    const int32_t whole[2] = {0, k};
+    const int chunked = bounds != NULL;
+    if (!chunked) {
+        bounds = whole;
+        n_chunks = 1;
+    }
+#pragma omp parallel
+    {
+        float* acc = (float*)malloc(sizeof(float) * (size_t)N * 2);
+        float* sum = acc + N;
+#pragma omp for schedule(dynamic, 4)
+        for (int m = 0; m < M; ++m) {
+            for (int n = 0; n < N; ++n) sum[n] = 0.0f;
+            for (int c = 0; c < n_chunks; ++c) {
+                const int k0 = bounds[c], k1 = bounds[c + 1];
+                for (int n = 0; n < N; ++n) acc[n] = 0.0f;
+                for (int s = k0; s < k1; ++s) {
+                    const int kk = variant == 1 ? k1 - 1 - (s - k0) : s;
+                    const float a = A[(int64_t)kk * lda + m];
+                    const float* b = B + (int64_t)kk * ldb;
+                    if (variant == 2)
+                        for (int n = 0; n < N; ++n) acc[n] = acc[n] + a * b[n];
+                    else
+                        for (int n = 0; n < N; ++n) acc[n] = fmaf(a, b[n], acc[n]);
+                }
+                if (chunked)
+                    for (int n = 0; n < N; ++n) sum[n] = sum[n] + acc[n];
+            }
+            const float* v = chunked ? sum : acc;
+            float* out = Cout + (int64_t)m * ldcout;
+            if (mode == 0) {
+                const float* cin = Cin + (int64_t)m * ldcin;
+                for (int n = 0; n < N; ++n) out[n] = cin[n] - v[n];
+            } else if (mode == 1) {
+                for (int n = 0; n < N; ++n) out[n] = v[n];
+            } else {
+                for (int n = 0; n < N; ++n) out[n] = -v[n];
+            }
+        }
+        free(acc);
+    }
+}
+
+void orc_sgemm_tn_chain(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Cin, int64_t ldcin,
+                        float* Cout, int64_t ldcout, int M, int N, int k, int mode, const int32_t* bounds,
+                        int n_chunks) {
+    sgemm_tn_chain(A, lda, B, ldb, Cin, ldcin, Cout, ldcout, M, N, k, mode, bounds, n_chunks, 0);
+}
+
+void orc_sgemm_tn_wrong_order(const float* A, int64_t lda, const float* B, int64_t ldb, const float* Cin,
+                              int64_t ldcin, float* Cout, int64_t ldcout, int M, int N, int k, int mode,
+                              const int32_t* bounds, int n_chunks, int variant) {
+    sgemm_tn_chain(A, lda, B, ldb, Cin, ldcin, Cout, ldcout, M, N, k, mode, bounds, n_chunks, variant);
+}
+
 void orc_set_num_threads(int n) {
 #ifdef _OPENMP
     if (n > 0) omp_set_num_threads(n);

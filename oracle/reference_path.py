@@ -294,6 +294,54 @@ def gptq_sweep_numpy(W, U, scale, zp, g_idx, blocksize=128, num_bits=4):
 
 
 # ---------------------------------------------------------------------------------------------
+# the fp32 TN GEMM building block (qt_sgemm_tn_f32): every output element as the fmaf chain
+# ---------------------------------------------------------------------------------------------
+def _pitched_f32(a: np.ndarray, name: str) -> int:
+    """Row pitch in elements of a 2-d float32 array whose rows are contiguous (a column slice of a wider matrix is)."""
+    assert a.dtype == np.float32 and a.ndim == 2, f"{name}: 2-d float32"
+    if a.shape[0] == 0:          # no row is read (k = 0)
+        return a.shape[1]
+    assert a.shape[1] <= 1 or a.strides[1] == 4, f"{name}: rows must be contiguous"
+    assert a.strides[0] % 4 == 0 and a.strides[0] >= 4 * a.shape[1], f"{name}: row stride {a.strides[0]} bytes"
+    return a.strides[0] // 4
+
+
+def sgemm_tn_chain(A, B, Cin=None, mode=1, chunks=None, out=None, variant=0):
+    """``orc_sgemm_tn_chain``: per output element ``acc = fmaf(A[kk][m], B[kk][n], acc)`` for kk ascending from 0, then
+    mode 0: ``Cin - acc``, 1: ``acc``, 2: ``-acc``.  A [k, M], B [k, N] float32 with contiguous rows at any pitch.
+    ``chunks``: boundaries ``[0, ..., k]``; every chunk is a chain from 0 and the chunk sums are added by fp32 ``+`` in
+    ascending order from 0.0 (the split-K reduction's sequence).  ``out`` (default: a new [M, N] array) may be a column
+    slice of a wider matrix and may be ``Cin`` itself.  ``variant`` 1 / 2 are the wrong orders (descending k / unfused
+    multiply-add) that tests/test_sgemm_oracle.py holds the inputs against; everything else passes 0."""
+    k, M = A.shape
+    k2, N = B.shape
+    assert k == k2 and M > 0 and N > 0 and mode in (0, 1, 2)
+    lda, ldb = _pitched_f32(A, "A"), _pitched_f32(B, "B")
+    if out is None:
+        out = np.empty((M, N), np.float32)
+    assert out.shape == (M, N) and out.flags.writeable
+    ldcout = _pitched_f32(out, "out")
+    ldcin = 0
+    if mode == 0:
+        assert Cin is not None and Cin.shape == (M, N), "mode 0 needs Cin [M, N]"
+        ldcin = _pitched_f32(Cin, "Cin")
+    bounds, n_chunks = None, 0
+    if chunks is not None:
+        bounds = np.ascontiguousarray(chunks, dtype=np.int32)
+        n_chunks = len(bounds) - 1
+        assert n_chunks >= 1 and bounds[0] == 0 and bounds[-1] == k and (np.diff(bounds) > 0).all(), list(bounds)
+    args = [_p(A), ctypes.c_int64(lda), _p(B), ctypes.c_int64(ldb), _p(Cin) if mode == 0 else None,
+            ctypes.c_int64(ldcin), _p(out), ctypes.c_int64(ldcout), M, N, k, mode,
+            _p(bounds) if bounds is not None else None, n_chunks]
+    if variant == 0:
+        lib().orc_sgemm_tn_chain(*args)
+    else:
+        assert variant in (1, 2)
+        lib().orc_sgemm_tn_wrong_order(*args, variant)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # a9 + a8 + a10 + a11 glued: quantize_weight                                [SURVEY A.2]
 # ---------------------------------------------------------------------------------------------
 def quantize_weight(W, H, *, group_size=128, symmetric=True, num_bits=4, blocksize=128,

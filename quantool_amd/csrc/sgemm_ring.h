@@ -10,7 +10,8 @@
 //     previous tile's stores have just released) and is not needed before its first chain ends.
 // Wave -> output mapping, MFMA shape and k order are those of sgemm_tn_kernel<128, 128, MODE_SUB, *, 8>:
 // per output element the same ascending-k fmaf chain(s) from 0 and the same subtraction(s), so the results
-// are bit-identical (tests/test_gpu_sgemm.py compares the two kernels bit for bit).
+// are bit-identical (tests/test_gpu_sgemm.py compares the two kernels bit for bit; tests/test_gpu_sgemm_chain.py holds
+// every output of both to the CPU chain, oracle/gptq_oracle.c: orc_sgemm_tn_chain).
 // Requirements: MODE_SUB, k_mode FULL, M % 128 == 0 and N % 128 == 0 (whole tiles only: no edge predicates
 // anywhere), kdim % 32 == 0, kdim >= 64, chain_len % 32 == 0, lda / ldb % 4 == 0, A / B 16-byte aligned,
 // 16 * ld * 4 < 2^32, 32 * ldc * 4 < 2^31.  512 threads, 128 registers (amdgpu_waves_per_eu(4, 4)), 64 KiB of LDS.

@@ -482,7 +482,8 @@ extern "C" int qt_sgemm_tn_f32(const float* A, int64_t lda, const float* B, int6
                                int mode, int allow_split_k, void* workspace, size_t workspace_bytes,
                                qt_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    QT_CHECK_ARG(A && B && Cout && M > 0 && N > 0 && kdim >= 0, "qt_sgemm_tn_f32: bad arguments");
+    // kdim == 0 is the empty sum (Cin, zeros, -zeros): no k row is read, and a caller's empty operands have no address
+    QT_CHECK_ARG(Cout && M > 0 && N > 0 && kdim >= 0 && (kdim == 0 || (A && B)), "qt_sgemm_tn_f32: bad arguments");
     QT_CHECK_ARG(mode == SG_MODE_SUB || mode == SG_MODE_SET || mode == SG_MODE_NEG, "qt_sgemm_tn_f32: mode %d", mode);
     QT_CHECK_ARG(mode != SG_MODE_SUB || Cin, "qt_sgemm_tn_f32: MODE_SUB needs Cin");
     SgemmArgs g;

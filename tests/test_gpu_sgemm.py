@@ -1,5 +1,6 @@
 """The fp32 TN GEMM building block: modes, edges, split-K, the structural-zero skip, and the
-property the parity contract rests on -- its accumulation IS an ascending-k fmaf chain."""
+property the parity contract rests on -- its accumulation IS an ascending-k fmaf chain.
+The whole-matrix comparison with the CPU chain, on every path of qt_sgemm_tn, is tests/test_gpu_sgemm_chain.py."""
 import ctypes
 
 import numpy as np
