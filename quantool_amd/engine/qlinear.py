@@ -14,7 +14,8 @@ Linear either
 * with ``a16="packed"``, a ``WeightOnlyLinear`` that keeps the stored integer weights on the device: decode-sized inputs
   (M <= ``skinny_max_m`` rows) run the GEMV ``qt_gemm_wq_skinny``, larger ones dequantise the weight into a transient
   buffer (``qt_dequantize_weight``, bit-identical to the dequantised ``nn.Linear``) and call ``F.linear``; with
-  ``a16_stream_rows`` inputs of 17 to that many rows run the weight-streaming ``qt_gemm_wq_stream`` instead.
+  ``a16_stream_rows`` inputs of 17 to that many rows run the weight-streaming ``qt_gemm_wq_stream`` instead, and with
+  ``a16_panel_rows`` inputs above those up to that many rows run ``qt_gemm_wq_panel``.
 
 Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up_proj [E, 2I, H]`` / ``down_proj
 [E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
@@ -295,12 +296,14 @@ A16_MODES = ("dequantized", "packed")
 # The largest ``a16_experts_wide_tokens``: the largest call size at which qt_moe_gemm_wq_wide was measured (DESIGN.md
 # 4.19).
 A16_EXPERTS_WIDE_MAX_TOKENS = 2048
+# The largest ``a16_panel_rows``: the rows qt_gemm_wq_panel takes (ops.WQ_PANEL_MAX_M).
+A16_PANEL_MAX_ROWS = 512
 
 
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
-                   a8_fused_norm: bool = False) -> nn.Module:
+                   a8_fused_norm: bool = False, a16_panel_rows: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -312,6 +315,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``WeightOnlyLinear`` built, so inputs of 17 to that many rows run ``qt_gemm_wq_stream`` on the stored weights
     instead of dequantise + ``F.linear`` (``WeightOnlyExperts`` are not touched); it is recorded under
     ``"a16_stream_rows"``.  A8 checkpoints ignore it.
+    ``a16_panel_rows`` (0, the default, or 17 ... 512, above ``a16_stream_rows``; needs ``a16="packed"``) sets
+    ``panel_max_m`` on every ``WeightOnlyLinear`` built, so inputs of more than max(16, ``a16_stream_rows``) rows up to
+    that many run ``qt_gemm_wq_panel`` on the stored weights, on the Linears inside the module's measured size bounds;
+    it is recorded under ``"a16_panel_rows"``.  A8 checkpoints ignore it.
     ``a16_experts_wide_tokens`` (0, the default, or 129 ... ``A16_EXPERTS_WIDE_MAX_TOKENS``; needs
     ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
     tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
@@ -352,6 +359,12 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         raise ValueError(f"a16_stream_rows={a16_stream_rows!r}: expected 0 or 17 ... 128")
     if a16_stream_rows and a16 != "packed":
         raise ValueError("a16_stream_rows needs a16='packed' (dequantised Linears have no stored weights to stream)")
+    if type(a16_panel_rows) is not int or not (
+            a16_panel_rows == 0 or max(17, a16_stream_rows + 1) <= a16_panel_rows <= A16_PANEL_MAX_ROWS):
+        raise ValueError(f"a16_panel_rows={a16_panel_rows!r}: expected 0 or {max(17, a16_stream_rows + 1)} ... "
+                         f"{A16_PANEL_MAX_ROWS}")
+    if a16_panel_rows and a16 != "packed":
+        raise ValueError("a16_panel_rows needs a16='packed' (dequantised Linears have no stored weights to run on)")
     if type(a16_experts_wide_tokens) is not int or not (
             a16_experts_wide_tokens == 0 or 129 <= a16_experts_wide_tokens <= A16_EXPERTS_WIDE_MAX_TOKENS):
         raise ValueError(f"a16_experts_wide_tokens={a16_experts_wide_tokens!r}: expected 0 or 129 ... "
@@ -424,6 +437,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             _check_shape(f"{path}: {name}", (new.out_features, new.in_features), lin.weight.shape)
             if not a8 and a16_stream_rows:
                 new.stream_max_m = a16_stream_rows
+            if not a8 and a16_panel_rows:
+                new.panel_max_m = a16_panel_rows
             _set_submodule(model, name, new)
         else:
             W = dequantized_weight(name, t, mdtype)
@@ -444,6 +459,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows
+        model._qt_checkpoint["a16_panel_rows"] = a16_panel_rows
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))
         if packed_experts:
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)

@@ -364,7 +364,10 @@ class WeightOnlyLinear(nn.Module):
     Opt-in: with ``stream_max_m`` > 0, ``skinny_max_m`` < M <= ``stream_max_m`` runs ``qt_gemm_wq_stream`` (the weights
     read once as well; every row bit-identical to the skinny kernel's, not to ``F.linear``'s) on a Linear with
     ``in_features`` >= ``stream_min_k`` and, when ``stream_max_n`` is not 0, ``out_features`` <= ``stream_max_n``, where
-    ``ops.gemm_wq_stream_supported`` holds (no ``g_idx``, K a multiple of 128, aligned rows).
+    ``ops.gemm_wq_stream_supported`` holds (no ``g_idx``, K a multiple of 128, aligned rows).  With ``panel_max_m`` > 0,
+    max(``skinny_max_m``, ``stream_max_m``) < M <= ``panel_max_m`` runs ``qt_gemm_wq_panel`` (the same bits per row) on a
+    Linear with ``in_features`` >= ``panel_min_k``, ``out_features`` >= ``panel_min_n`` and, when ``panel_max_n`` is
+    not 0, <= ``panel_max_n``, where ``ops.gemm_wq_panel_supported`` holds.
 
     Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
     ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
@@ -381,6 +384,16 @@ class WeightOnlyLinear(nn.Module):
     stream_max_m = 0
     stream_max_n = 28672
     stream_min_k = 512
+    # LDS-panel GEMM (``qt_gemm_wq_panel``) above max(skinny_max_m, stream_max_m) rows, up to this many.  0, the default:
+    # never, for the reason given for ``stream_max_m`` (``load_quantized(..., a16_panel_rows=)``).  Used only when it is
+    # not 0: from this many input and output features and, when ``panel_max_n`` is not 0, up to that many output
+    # features -- the bounds within which no measured cell loses to dequantise + F.linear up to 96 rows, the value the
+    # tables support for ``a16_panel_rows`` (q/k/v, gate / up and gate_up of Llama-3-8B; at N = 4096 the
+    # grid is 64 workgroups and 48 and 64 rows lose, at N = 1024 every row count does; no K below 4096 was measured).
+    panel_max_m = 0
+    panel_min_k = 4096
+    panel_min_n = 6144
+    panel_max_n = 28672
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
@@ -415,7 +428,8 @@ class WeightOnlyLinear(nn.Module):
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
-                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}")
+                f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}, "
+                f"panel_max_m={self.panel_max_m}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         bias = None if self.bias is None else self.bias.to(x.dtype)
@@ -434,6 +448,13 @@ class WeightOnlyLinear(nn.Module):
             x2 = _rows(x, w.K)
             if ops.gemm_wq_stream_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
                 y = ops.gemm_wq_stream(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
+                return y.reshape(*x.shape[:-1], w.N)
+        if (self.panel_max_m > 0 and max(self.skinny_max_m, self.stream_max_m) < M <= self.panel_max_m
+                and w.K >= self.panel_min_k and w.N >= self.panel_min_n
+                and (self.panel_max_n == 0 or w.N <= self.panel_max_n) and M <= ops.WQ_PANEL_MAX_M):
+            x2 = _rows(x, w.K)
+            if ops.gemm_wq_panel_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
+                y = ops.gemm_wq_panel(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
                 return y.reshape(*x.shape[:-1], w.N)
         W = ops.dequantize_weight(w.levels, w.scale, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx, dtype=x.dtype)
         return F.linear(x, W, bias)

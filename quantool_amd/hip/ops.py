@@ -1355,6 +1355,58 @@ def gemm_wq_stream(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w
     return Y
 
 
+WQ_PANEL_MAX_M = 512     # rows of X qt_gemm_wq_panel takes (QT_WQ_PANEL_MAX_M)
+WQ_PANEL_K_UNIT = 128    # columns per k-block of qt_gemm_wq_panel: K must be a multiple (QT_WQ_PANEL_K_UNIT)
+WQ_PANEL_MAX_LDX = 1 << 24   # largest row pitch of X in elements (QT_WQ_PANEL_MAX_LDX)
+
+
+def _wq_panel_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                      g_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_gemm_wq_panel`` would refuse these operands whatever the number of rows, or None: the rules of
+    ``_wq_stream_refusal`` with the panel kernel's pitch bound.  Host-only."""
+    why = _wq_stream_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is None and X.stride(0) > WQ_PANEL_MAX_LDX:
+        why = f"the row pitch of X, {X.stride(0)} elements, is above {WQ_PANEL_MAX_LDX}"
+    return why
+
+
+def gemm_wq_panel_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                            zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_wq_panel`` takes these operands at 1 to ``WQ_PANEL_MAX_M`` rows: no ``g_idx``, 16-bit X with unit
+    column stride, K a multiple of ``WQ_PANEL_K_UNIT``, G = 1 or K/128, X, Wq and X's row pitch 16-byte aligned.
+    Host-only."""
+    return _wq_panel_refusal(X, Wq, s_w, zp_w, g_idx) is None
+
+
+def gemm_wq_panel(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w: Optional[torch.Tensor] = None,
+                  g_idx: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_wq_skinny`` for 1 <= M <= ``WQ_PANEL_MAX_M`` rows (``qt_gemm_wq_panel``): the activations go through LDS in
+    whole rows and serve four column tiles, so it carries on where ``gemm_wq_stream`` turns.  Same arguments; every row
+    of Y equals ``gemm_wq_skinny`` of that row to the bit.  ``ValueError`` where ``gemm_wq_panel_supported`` is false or
+    M is out of range, before the library is touched."""
+    M = X.shape[0] if X.dim() == 2 else -1
+    why = _wq_panel_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is None and not 1 <= M <= WQ_PANEL_MAX_M:
+        why = f"1 <= M <= {WQ_PANEL_MAX_M} rows only, got X {tuple(X.shape)}"
+    if why is not None:
+        raise ValueError(f"gemm_wq_panel: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    if bias is not None:
+        _req(bias, X.dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+    Y = torch.empty((M, N), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_panel", lib.qt_gemm_wq_panel(
+        X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), _ptr(g_idx),
+        _ptr(bias), Y.data_ptr(), Y.stride(0), _stream()))
+    return Y
+
+
 def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
                     row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
                     zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:

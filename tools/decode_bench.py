@@ -16,7 +16,7 @@ the write and the three loads short).  Every expert's gate / up / down and the a
 way and written per expert through ``expert_bank_checkpoint_names`` (``block_sparse_moe.experts.{e}.w1 / w3 / w2``).
 ``--scheme W4A16 --batch B --modes packed,packed_stream`` compares the packed runtime with and without
 ``a16_stream_rows=128`` (B rows per decode-step GEMM: ``qt_gemm_wq_stream`` against dequantise + ``F.linear``), each mode
-decoded twice.
+decoded twice; ``--modes packed,packed_panel`` does the same with ``a16_panel_rows=512`` (``qt_gemm_wq_panel``).
 
 Modes ``dequantized``, ``packed`` (``a16="packed"``: the banks stay dense bf16) and ``packed_experts`` (``a16="packed",
 a16_experts="packed"``: ``WeightOnlyExperts``); each mode also reports the resident bytes of the expert banks.
@@ -393,6 +393,8 @@ def main():
             model = load_quantized(path, device=dev, a16="packed", a16_experts="packed")
         elif mode == "packed_stream":                            # 17 - 128 rows on qt_gemm_wq_stream
             model = load_quantized(path, device=dev, a16="packed", a16_stream_rows=128)
+        elif mode == "packed_panel":                             # 17 - 512 rows on qt_gemm_wq_panel
+            model = load_quantized(path, device=dev, a16="packed", a16_panel_rows=512)
         else:
             model = load_quantized(path, device=dev, a16=mode)
         lin_bytes = bank_bytes = 0
@@ -409,7 +411,7 @@ def main():
         torch.cuda.reset_peak_memory_stats()
         toks, per_tok = decode(model, prompt, args.new)
         steps = [round(per_tok * 1e3, 3)]
-        if "packed_stream" in modes:                             # each mode twice: the second pass is the spread
+        if "packed_stream" in modes or "packed_panel" in modes:  # each mode twice: the second pass is the spread
             toks2, per_tok2 = decode(model, prompt, args.new)
             assert toks2 == toks, f"{mode}: two runs gave different tokens"
             steps.append(round(per_tok2 * 1e3, 3))
@@ -421,11 +423,12 @@ def main():
             "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules())}
         tokens[mode] = toks
         del model
-    if not mixtral and set(tokens) == {"packed", "packed_stream"}:
-        same = [x == y for x, y in zip(tokens["packed"], tokens["packed_stream"])]
+    fused = next((m for m in ("packed_stream", "packed_panel") if set(tokens) == {"packed", m}), None)
+    if not mixtral and fused:
+        same = [x == y for x, y in zip(tokens["packed"], tokens[fused])]
         result["tokens_agree"] = sum(same)                       # not expected on a random-init model
         result["first_difference"] = same.index(False) if not all(same) else None
-        p, k = (min(result["modes"][m]["ms_per_step"]) for m in ("packed", "packed_stream"))
+        p, k = (min(result["modes"][m]["ms_per_step"]) for m in ("packed", fused))
         result["speedup"] = round(p / k, 3)
     if not mixtral and set(tokens) == set(A16_MODES):
         a, b = tokens.values()

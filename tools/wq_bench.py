@@ -19,6 +19,12 @@ The 17 - 128 row range: per shape (q/k/v, o, k/v, gate/up, gate
 call in one loop, each call between its own HIP events, the weights rotating over more than 512 MiB of copies; median
 us.  ``bits_equal_skinny`` says whether every 16-row slice of the kernel's output equals the skinny kernel's bits;
 ``skinny16_us`` is the skinny kernel at M = 16 on the same weights, so the step at row 17 shows.
+
+  python tools/wq_bench.py --panel [--panel-ms 48,64,96,128,192,256,384,512] [--reps 30] [--warmup 5]
+
+The 33 - 512 row range, by the same method: per shape (q/k/v, o, k/v, gate/up, gate or up alone, down),
+scheme and M, ``ops.gemm_wq_panel`` against the dequantise + ``F.linear`` pair and, up to 128 rows,
+``ops.gemm_wq_stream``, all alternating in one loop.
 """
 from __future__ import annotations
 
@@ -83,6 +89,70 @@ def _alternate(fns, reps, warmup):
     return [_median_us(e) for e in ev]
 
 
+def _cold_weights(N, K, scheme, dev, g):
+    """One random weight of ``scheme`` (levels, scales, zero-points), its packed bytes, and copies of it totalling more
+    than 512 MiB for the calls to rotate over."""
+    bits, asym = SCHEMES[scheme]
+    lo, hi = (-8, 8) if bits == 4 else (-128, 128)
+    q = torch.randint(lo, hi, (N, K), device=dev, generator=g, dtype=torch.int8)
+    Wq0 = pack_int4(q) if bits == 4 else q
+    del q
+    s0 = (torch.rand(N, K // 128 if bits == 4 else 1, device=dev, generator=g) * 0.01 + 1e-3)
+    z0 = torch.randint(-8, 8, s0.shape, device=dev, generator=g, dtype=torch.int8) if asym else None
+    qbytes = Wq0.numel() * Wq0.element_size() + s0.numel() * 4 + (z0.numel() if asym else 0)
+    cps = [(Wq0.clone(), s0.clone(), None if z0 is None else z0.clone()) for _ in range(_copies(qbytes))]
+    return Wq0, s0, z0, qbytes, cps
+
+
+PANEL_SHAPES = ("qkv", "o", "kv", "gate_up", "gate", "down")
+
+
+def panel_main(args):
+    """--panel: ``ops.gemm_wq_panel`` against the dequantise + ``F.linear`` pair (and ``ops.gemm_wq_stream`` up to its 128
+    rows), --stream's method."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    names = [k for k in args.shapes.split(",") if k] if args.shapes != ",".join(SHAPES) else list(PANEL_SHAPES)
+    ms = [int(m) for m in args.panel_ms.split(",") if m]
+    rows = []
+    for shape in names:
+        N, K = STREAM_SHAPES[shape]
+        for scheme in args.schemes.split(","):
+            Wq0, s0, z0, qbytes, cps = _cold_weights(N, K, scheme, dev, g)
+            n_cp = len(cps)
+
+            def pair(i, X):
+                Wq, s, z = cps[i % n_cp]
+                return F.linear(X, ops.dequantize_weight(Wq, s, K=K, zp_w=z, dtype=X.dtype))
+
+            def kernel(op, i, X):
+                Wq, s, z = cps[i % n_cp]
+                return op(X, Wq, s, zp_w=z)
+
+            row = {"shape": shape, "N": N, "K": K, "scheme": scheme, "packed_mb": round(qbytes / 1e6, 2),
+                   "cold_copies": n_cp, "panel": {}}
+            for M in ms:
+                X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+                Y = kernel(ops.gemm_wq_panel, 0, X)
+                same = all(torch.equal(Y[i:i + 16].view(torch.int16),
+                                       ops.gemm_wq_skinny(X[i:i + 16], Wq0, s0, zp_w=z0).view(torch.int16))
+                           for i in range(0, M, 16))
+                fns = [lambda i: pair(i, X), lambda i: kernel(ops.gemm_wq_panel, i, X)]
+                if M <= ops.WQ_STREAM_MAX_M:
+                    fns.append(lambda i: kernel(ops.gemm_wq_stream, i, X))
+                ts = _alternate(fns, args.reps, args.warmup)
+                cell = {"pair_us": ts[0], "panel_us": ts[1], "speedup": round(ts[0] / ts[1], 2),
+                        "panel_tbs": round(qbytes / ts[1] / 1e6, 3), "bits_equal_skinny": bool(same)}
+                if len(ts) > 2:
+                    cell["stream_us"] = ts[2]
+                row["panel"][M] = cell
+            rows.append(row)
+            del cps
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "wq_bench --panel", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                      "warmup": args.warmup, "rows": rows}))
+
+
 def stream_main(args):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -91,18 +161,9 @@ def stream_main(args):
     rows = []
     for shape in names:
         N, K = STREAM_SHAPES[shape]
-        G = K // 128
         for scheme in args.schemes.split(","):
-            bits, asym = SCHEMES[scheme]
-            lo, hi = (-8, 8) if bits == 4 else (-128, 128)
-            q = torch.randint(lo, hi, (N, K), device=dev, generator=g, dtype=torch.int8)
-            Wq0 = pack_int4(q) if bits == 4 else q
-            del q
-            s0 = (torch.rand(N, G if bits == 4 else 1, device=dev, generator=g) * 0.01 + 1e-3)
-            z0 = torch.randint(-8, 8, s0.shape, device=dev, generator=g, dtype=torch.int8) if asym else None
-            qbytes = Wq0.numel() * Wq0.element_size() + s0.numel() * 4 + (z0.numel() if asym else 0)
-            n_cp = _copies(qbytes)
-            cps = [(Wq0.clone(), s0.clone(), None if z0 is None else z0.clone()) for _ in range(n_cp)]
+            Wq0, s0, z0, qbytes, cps = _cold_weights(N, K, scheme, dev, g)
+            n_cp = len(cps)
 
             def pair(i, X):
                 Wq, s, z = cps[i % n_cp]
@@ -138,6 +199,9 @@ def main():
     ap.add_argument("--stream", action="store_true", help="the 17 - 128 row range: qt_gemm_wq_stream against "
                     "dequantise + F.linear")
     ap.add_argument("--stream-ms", default="17,32,48,64,96,128")
+    ap.add_argument("--panel", action="store_true", help="the 33 - 512 row range: qt_gemm_wq_panel against "
+                    "dequantise + F.linear and, up to 128 rows, qt_gemm_wq_stream")
+    ap.add_argument("--panel-ms", default="48,64,96,128,192,256,384,512")
     ap.add_argument("--skinny-ms", default="1,2,4,8,16")
     ap.add_argument("--large-ms", default="4096,8192")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -150,6 +214,8 @@ def main():
         raise SystemExit("wq_bench needs a GPU")
     if args.stream:
         return stream_main(args)
+    if args.panel:
+        return panel_main(args)
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     shapes = {k: SHAPES[k] for k in args.shapes.split(",") if k}
