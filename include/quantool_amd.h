@@ -208,7 +208,25 @@ int qt_weight_gather_qparams(const void* W, int w_dtype, int R, int K, int64_t l
                              const uint8_t* dead, int group_size, int symmetric, int num_bits, float* W_f32, float* scale,
                              float* zp, float* scale_t, float* zp_t, int64_t ld_t, qt_stream_t stream);
 
-/* ---- a11  the column sweep of quantize_weight -----------------------------------------------
+/* The same launch with the MSE observer (upstream's `mse`) in place of min/max.  Per group, with
+ * mn / mx the minimum and maximum over the group's ORIGINAL columns: candidate i has (s_i, z_i) =
+ * calculate_qparams(shrink[i] * mn, shrink[i] * mx), the arithmetic of the min/max entries above, and the fp32 error
+ * err_i = sum_k |(rint(clamp(w_k / s_i + z_i, qmin, qmax)) - z_i) * s_i - w_k| ^ norm; scale / zp (and scale_t / zp_t,
+ * laid out as above) receive the first candidate whose error is strictly below every earlier one, idx[R, G] (may be
+ * NULL) its index.  EVERY group sees all n_steps candidates (upstream stops the whole tensor after 5 steps without
+ * an improvement anywhere).  shrink: n_steps HOST floats (1 <= n_steps <= 32, each positive and finite), copied into
+ * the launch; norm positive and finite.  Upstream's defaults: 20 steps of 1 - i / 100, norm 2.4; with shrink[0] = 1
+ * candidate 0 is the min/max observer.
+ * W_f32, perm and dead are optional TOGETHER: all three NULL gives the observer alone (perm or dead without W_f32 is
+ * an argument error).  group_size: a multiple of 32 that divides K, or <= 0 for channel-wise; num_bits 2..8.  A row
+ * must fit the LDS as above; groups wider than 128 columns reduce through 544 more bytes of it (so K <= 81648 16-bit
+ * or 40824 fp32 elements there).  No workspace, no atomics, deterministic. */
+int qt_weight_gather_qparams_mse(const void* W, int w_dtype, int R, int K, int64_t ldw, const int32_t* perm,
+                                 const uint8_t* dead, int group_size, int symmetric, int num_bits, int n_steps,
+                                 const float* shrink, float norm, float* W_f32, float* scale, float* zp, float* scale_t,
+                                 float* zp_t, int64_t ld_t, int8_t* idx, qt_stream_t stream);
+
+/* ---- a11 the column sweep of quantize_weight -----------------------------------------------
  * W[R,K] fp32 in sweep order (updated in place: error-compensated, then dequantised values),
  * U[K,K] upper factor, scale_t/zp_t [G,R] fp32 (group-major, see qt_group_minmax_qparams),
  * g_idx[K] int32 = group of each sweep position.

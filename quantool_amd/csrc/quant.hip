@@ -3,6 +3,7 @@
 // All HBM-bound single passes; one wave per (row, group) with wavefront shuffles for the
 // group-wise min/max reduction.
 #include "common.h"
+#include "qparams.h"
 
 namespace {
 
@@ -35,21 +36,8 @@ __global__ __launch_bounds__(64) void qparams_kernel(const void* __restrict__ W,
     mn = wave_min(mn);
     mx = wave_max(mx);
     if (lane == 0) {
-        mn = fminf(mn, 0.0f);
-        mx = fmaxf(mx, 0.0f);
         float s, z;
-        const float eps = 1.1920928955078125e-07f;
-        if (symmetric) {
-            const float amax = fmaxf(fabsf(mn), fabsf(mx));
-            s = amax / ((qmax - qmin) / 2.0f);
-            s = fmaxf(s, eps);
-            z = 0.0f;
-        } else {
-            s = (mx - mn) / (qmax - qmin);
-            s = fmaxf(s, eps);
-            z = qmin - mn / s;
-            z = fminf(fmaxf(rintf(z), qmin), qmax);
-        }
+        qt_calculate_qparams(mn, mx, symmetric, qmin, qmax, s, z);
         scale[(size_t)r * G + g] = s;
         zp[(size_t)r * G + g] = z;
         if (scale_t) scale_t[(size_t)g * R + r] = s;
@@ -108,21 +96,8 @@ __global__ __launch_bounds__(256) void gather_qparams_kernel(const T* __restrict
         mn = wave_min(mn);
         mx = wave_max(mx);
         if (lane == 0) {
-            mn = fminf(mn, 0.0f);
-            mx = fmaxf(mx, 0.0f);
             float s, z;
-            const float eps = 1.1920928955078125e-07f;
-            if (symmetric) {
-                const float amax = fmaxf(fabsf(mn), fabsf(mx));
-                s = amax / ((qmax - qmin) / 2.0f);
-                s = fmaxf(s, eps);
-                z = 0.0f;
-            } else {
-                s = (mx - mn) / (qmax - qmin);
-                s = fmaxf(s, eps);
-                z = qmin - mn / s;
-                z = fminf(fmaxf(rintf(z), qmin), qmax);
-            }
+            qt_calculate_qparams(mn, mx, symmetric, qmin, qmax, s, z);
             scale[(size_t)r * G + g] = s;
             zp[(size_t)r * G + g] = z;
             if (scale_t) scale_t[(size_t)g * ld_t + r] = s;
@@ -257,11 +232,6 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int8_t* __restrict__
 }
 
 }  // namespace
-
-static inline void qt_range(int num_bits, float* qmin, float* qmax) {
-    *qmin = -(float)(1 << (num_bits - 1));
-    *qmax = (float)((1 << (num_bits - 1)) - 1);
-}
 
 extern "C" int qt_group_minmax_qparams(const void* W, int w_dtype, int R, int K, int64_t ldw, int group_size,
                                        int symmetric, int num_bits, float* scale, float* zp, float* scale_t,

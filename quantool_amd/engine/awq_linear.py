@@ -14,7 +14,7 @@ from typing import Iterable, List, Optional, Sequence
 import torch
 
 from ..hip import ops
-from .gptq_linear import _on_device
+from .gptq_linear import _on_device, weight_observer
 from .schemes import QuantArgs
 
 
@@ -148,10 +148,11 @@ def search_losses(weights: Sequence[torch.Tensor], scales: torch.Tensor, G: torc
 
 def rtn_finalize(ws: torch.Tensor, qargs: QuantArgs, s: Optional[torch.Tensor] = None,
                  best: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None) -> AWQResult:
-    """Standard observer (/7.5) + round-to-nearest + pack of an already smoothed weight ``ws``."""
+    """Standard observer (/7.5; ``qargs.observer == "mse"``: the shrink-grid search) + round-to-nearest + pack of an
+    already smoothed weight ``ws``."""
     R, K = ws.shape
     gs = qargs.kernel_group_size
-    scale, zp, _, _ = ops.group_minmax_qparams(ws, gs, qargs.symmetric, qargs.num_bits)
+    scale, zp, _, _ = weight_observer(qargs)(ws, gs, qargs.symmetric, qargs.num_bits)
     Qt = ops.rtn_quantize(ws, scale, zp, gs, qargs.num_bits)
     packed = ops.pack_int4(Qt) if qargs.num_bits == 4 else None
     sdt = ws.dtype if ws.dtype in (torch.bfloat16, torch.float16) else torch.float32

@@ -293,6 +293,12 @@ def _normalize_actorder(actorder) -> Optional[str]:
     raise ValueError(f"unknown actorder {actorder!r} (expected None, 'static'/'weight' or 'group')")
 
 
+def weight_observer(qargs: QuantArgs):
+    """The observer-only op ``qargs.observer`` names: ``"mse"`` is the shrink-grid search (``ops.group_mse_qparams``,
+    DESIGN.md 4.26); every other value is the min/max observer, as before the field was read."""
+    return ops.group_mse_qparams if qargs.observer == "mse" else ops.group_minmax_qparams
+
+
 def gptq_quantize_shared(weights: Sequence[torch.Tensor], acc: HessianAccumulator, qargs: QuantArgs, *,
                          block_size: int = 128, dampening_frac: float = 0.01,
                          scale_dtype: Optional[torch.dtype] = None,
@@ -420,7 +426,7 @@ def gptq_quantize_batched(groups: Sequence[Tuple[Sequence[torch.Tensor], Hessian
                 ops.weight_gather_f32(w if w.stride(1) == 1 else w.contiguous(), perms[b], deads[b], out=Wf[r0:r0 + r])
                 r0 += r
             g_sweeps.append(g_orig)
-        scale, zp, scale_t, zp_t = ops.group_minmax_qparams(Wf, gs, qargs.symmetric, qargs.num_bits)
+        scale, zp, scale_t, zp_t = weight_observer(qargs)(Wf, gs, qargs.symmetric, qargs.num_bits)
     else:
         # qparams on the ORIGINAL matrix (before permutation / dead-column zeroing) and the working copy in sweep order
         # from ONE read of every weight; the group-major tables the sweep reads are written in place (a Linear's rows
@@ -429,14 +435,16 @@ def gptq_quantize_batched(groups: Sequence[Tuple[Sequence[torch.Tensor], Hessian
         zp = torch.empty((R, G), dtype=torch.float32, device=dev)
         scale_t = torch.empty((G, R), dtype=torch.float32, device=dev)
         zp_t = torch.empty((G, R), dtype=torch.float32, device=dev)
+        mse = qargs.observer == "mse"       # its op refuses a row that does not fit the LDS: no two-pass form
+        gather_qparams = ops.weight_gather_qparams_mse if mse else ops.weight_gather_qparams
         for b, (ws, acc) in enumerate(groups):
             r0 = row_begin[b]
             for w, r in zip(ws, rows[b]):
                 w = w if w.stride(1) == 1 else w.contiguous()
-                if K * w.element_size() <= 160 * 1024:          # a row fits the LDS: one pass
-                    ops.weight_gather_qparams(w, perms[b], deads[b], gs, qargs.symmetric, qargs.num_bits, out=Wf[r0:r0 + r],
-                                              scale=scale[r0:r0 + r], zp=zp[r0:r0 + r], scale_t=scale_t[:, r0:r0 + r],
-                                              zp_t=zp_t[:, r0:r0 + r])
+                if mse or K * w.element_size() <= 160 * 1024:   # a row fits the LDS: one pass
+                    gather_qparams(w, perms[b], deads[b], gs, qargs.symmetric, qargs.num_bits, out=Wf[r0:r0 + r],
+                                   scale=scale[r0:r0 + r], zp=zp[r0:r0 + r], scale_t=scale_t[:, r0:r0 + r],
+                                   zp_t=zp_t[:, r0:r0 + r])
                 else:                                           # (in_features beyond 81 920: the two passes of rounds 1-3)
                     ops.weight_gather_f32(w, perms[b], deads[b], out=Wf[r0:r0 + r])
                     s_, z_, st_, zt_ = ops.group_minmax_qparams(w, gs, qargs.symmetric, qargs.num_bits)

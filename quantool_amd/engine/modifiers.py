@@ -46,6 +46,7 @@ class GPTQModifier:
     sequential_targets: Optional[Union[str, List[str]]] = None
     actorder: Optional[str] = "static"   # upstream default since 0.8 (recalled)
     offload_hessians: bool = False
+    observer: Optional[str] = None       # None: the preset's ("minmax"); "mse": the shrink-grid search
 
     def __post_init__(self):
         self.targets = _as_list(self.targets)
@@ -60,7 +61,7 @@ class GPTQModifier:
 
         # activation ordering only applies to group-wise weights (upstream ignores it otherwise)
         ao = self.actorder if w.strategy == "group" else None
-        return replace(w, actorder=ao)
+        return replace(w, actorder=ao, observer=w.observer if self.observer is None else self.observer)
 
     def wants(self, name: str, module) -> bool:
         if match_target(name, module, self.ignore) or name.split(".")[-1] in self.ignore:

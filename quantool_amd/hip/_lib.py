@@ -61,6 +61,10 @@ SIGNATURES = {
                                      c_void_p]),
     "qt_weight_gather_qparams": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # qt_weight_gather_qparams' arguments with n_steps, shrink (host floats), norm after num_bits and idx before the stream
+    "qt_weight_gather_qparams_mse": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int,
+                                             c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_void_p, c_void_p]),
     "qt_gptq_sweep_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "qt_gptq_sweep": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

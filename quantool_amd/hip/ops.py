@@ -480,13 +480,9 @@ def weight_gather_f32(W: torch.Tensor, perm: Optional[torch.Tensor] = None, dead
     return out
 
 
-def weight_gather_qparams(W: torch.Tensor, perm: Optional[torch.Tensor], dead: Optional[torch.Tensor], group_size: int,
-                          symmetric: bool, num_bits: int, out: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor,
-                          scale_t: Optional[torch.Tensor] = None, zp_t: Optional[torch.Tensor] = None) -> None:
-    """``group_minmax_qparams(W)`` and ``weight_gather_f32(W, perm, dead)`` in one read of W.  ``out`` fp32 [R, K],
-    ``scale`` / ``zp`` fp32 [R, G] contiguous; ``scale_t`` / ``zp_t``: [G, R] views with unit column stride (a column
-    range of a table spanning more rows is fine: the row stride is passed on)."""
-    lib = load()
+def _gather_qparams_args(W, perm, dead, group_size, out, scale, zp, scale_t, zp_t):
+    """The argument checks of ``weight_gather_qparams`` and its MSE twin (where ``out``, ``perm`` and ``dead`` may be
+    absent together); returns (R, K, ld_t)."""
     if W.dim() != 2 or not W.is_cuda or W.stride(1) != 1:
         raise ValueError("W must be a 2-d device tensor with unit column stride")
     R, K = W.shape
@@ -495,6 +491,8 @@ def weight_gather_qparams(W: torch.Tensor, perm: Optional[torch.Tensor], dead: O
         raise ValueError(f"K={K} not divisible by group_size={gs}")
     G = K // gs
     for name, t, shape in (("out", out, (R, K)), ("scale", scale, (R, G)), ("zp", zp, (R, G))):
+        if t is None and name == "out":
+            continue
         _req(t, torch.float32, name, 2)
         if tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous {shape}")
@@ -510,9 +508,93 @@ def weight_gather_qparams(W: torch.Tensor, perm: Optional[torch.Tensor], dead: O
             _req(t, dt, name, 1)
             if t.numel() != K or not t.is_contiguous():
                 raise ValueError(f"{name} must be contiguous [K]")
+    return R, K, ld_t
+
+
+def weight_gather_qparams(W: torch.Tensor, perm: Optional[torch.Tensor], dead: Optional[torch.Tensor], group_size: int,
+                          symmetric: bool, num_bits: int, out: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor,
+                          scale_t: Optional[torch.Tensor] = None, zp_t: Optional[torch.Tensor] = None) -> None:
+    """``group_minmax_qparams(W)`` and ``weight_gather_f32(W, perm, dead)`` in one read of W.  ``out`` fp32 [R, K],
+    ``scale`` / ``zp`` fp32 [R, G] contiguous; ``scale_t`` / ``zp_t``: [G, R] views with unit column stride (a column
+    range of a table spanning more rows is fine: the row stride is passed on)."""
+    lib = load()
+    if out is None:
+        raise ValueError("out must be contiguous fp32 [R, K]")
+    R, K, ld_t = _gather_qparams_args(W, perm, dead, group_size, out, scale, zp, scale_t, zp_t)
     check("qt_weight_gather_qparams", lib.qt_weight_gather_qparams(
         W.data_ptr(), _dtype_code(W), R, K, W.stride(0), _ptr(perm), _ptr(dead), group_size, int(bool(symmetric)), num_bits,
         out.data_ptr(), scale.data_ptr(), zp.data_ptr(), _ptr(scale_t), _ptr(zp_t), ld_t, _stream()))
+
+
+MSE_MAX_STEPS = 32          # candidates per group qt_weight_gather_qparams_mse takes
+MSE_ROW_BYTES = 160 * 1024  # a row of W must fit the LDS ...
+MSE_WIDE_BYTES = 544        # ... next to this much reduction space where a group is wider than 128 columns
+
+
+def mse_shrink_grid(n_steps: int = 20) -> list:
+    """Upstream's grid of the ``mse`` observer (maxshrink 0.2, grid 100): ``1 - i / 100`` for the first ``n_steps`` i,
+    evaluated in double; the C ABI rounds each to fp32.  Candidate 0 is the min/max range itself."""
+    return [1.0 - i / 100.0 for i in range(n_steps)]
+
+
+def mse_row_fits(K: int, element_size: int, group_size: int) -> bool:
+    """Whether a row of ``K`` elements fits ``qt_weight_gather_qparams_mse`` (include/quantool_amd.h)."""
+    gs = K if group_size <= 0 else group_size
+    return (K * element_size + 15) // 16 * 16 + (MSE_WIDE_BYTES if gs > 128 else 0) <= MSE_ROW_BYTES
+
+
+def weight_gather_qparams_mse(W: torch.Tensor, perm: Optional[torch.Tensor], dead: Optional[torch.Tensor],
+                              group_size: int, symmetric: bool, num_bits: int, out: Optional[torch.Tensor],
+                              scale: torch.Tensor, zp: torch.Tensor, scale_t: Optional[torch.Tensor] = None,
+                              zp_t: Optional[torch.Tensor] = None, *, idx: Optional[torch.Tensor] = None,
+                              n_steps: int = 20, shrink=None, norm: float = 2.4) -> None:
+    """``weight_gather_qparams`` with the MSE observer: per group the candidate ranges ``shrink[i] * (min, max)`` go
+    through ``calculate_qparams`` and the first one with the least ``sum |Q(w) - w| ** norm`` is written (DESIGN.md
+    4.26); ``idx`` (int8 [R, G]) receives its index.  ``out=None`` (then ``perm`` and ``dead`` must be None too) gives
+    the observer alone.  Checked here, before the library is touched: everything the C ABI refuses."""
+    if not 1 <= int(n_steps) <= MSE_MAX_STEPS:
+        raise ValueError(f"n_steps={n_steps} outside 1..{MSE_MAX_STEPS}")
+    grid = mse_shrink_grid(n_steps) if shrink is None else [float(p) for p in shrink]
+    if len(grid) != n_steps or not all(0.0 < p < float("inf") for p in grid):
+        raise ValueError(f"shrink must hold n_steps={n_steps} positive finite factors, got {grid}")
+    if not 0.0 < float(norm) < float("inf"):
+        raise ValueError(f"norm={norm} must be positive and finite")
+    if not 2 <= int(num_bits) <= 8:
+        raise ValueError(f"num_bits={num_bits} outside 2..8")
+    if group_size > 0 and group_size % 32:
+        raise ValueError(f"group_size={group_size} must be a multiple of 32 (or <= 0: channel-wise)")
+    if out is None and (perm is not None or dead is not None):
+        raise ValueError("perm / dead need out (the observer alone takes all three None)")
+    R, K, ld_t = _gather_qparams_args(W, perm, dead, group_size, out, scale, zp, scale_t, zp_t)
+    if out is not None and out.data_ptr() % 16:
+        raise ValueError("out (W_f32) must be 16-byte aligned")
+    if not mse_row_fits(K, W.element_size(), group_size):
+        raise ValueError(f"a row of {K} {W.dtype} elements does not fit the LDS")
+    if idx is not None:
+        _req(idx, torch.int8, "idx", 2)
+        if tuple(idx.shape) != tuple(scale.shape) or not idx.is_contiguous():
+            raise ValueError(f"idx must be contiguous {tuple(scale.shape)}")
+    lib = load()
+    check("qt_weight_gather_qparams_mse", lib.qt_weight_gather_qparams_mse(
+        W.data_ptr(), _dtype_code(W), R, K, W.stride(0), _ptr(perm), _ptr(dead), group_size, int(bool(symmetric)),
+        int(num_bits), int(n_steps), (ctypes.c_float * n_steps)(*grid), float(norm), _ptr(out), scale.data_ptr(),
+        zp.data_ptr(), _ptr(scale_t), _ptr(zp_t), ld_t, _ptr(idx), _stream()))
+
+
+def group_mse_qparams(W: torch.Tensor, group_size: int, symmetric: bool = True, num_bits: int = 4, **search):
+    """The MSE observer alone, with ``group_minmax_qparams``' result: (scale[R,G], zp[R,G], scale_t[G,R], zp_t[G,R])
+    fp32.  ``search``: ``idx`` / ``n_steps`` / ``shrink`` / ``norm`` of ``weight_gather_qparams_mse``."""
+    if W.dim() != 2:
+        raise ValueError("W must be a 2-d device tensor with unit column stride")
+    R, K = W.shape
+    gs = K if group_size <= 0 else group_size
+    if K % gs:
+        raise ValueError(f"K={K} not divisible by group_size={gs}")
+    G = K // gs
+    scale, zp = (torch.empty((R, G), dtype=torch.float32, device=W.device) for _ in range(2))
+    scale_t, zp_t = (torch.empty((G, R), dtype=torch.float32, device=W.device) for _ in range(2))
+    weight_gather_qparams_mse(W, None, None, group_size, symmetric, num_bits, None, scale, zp, scale_t, zp_t, **search)
+    return scale, zp, scale_t, zp_t
 
 
 # ---- a11 ----------------------------------------------------------------------------------
