@@ -802,6 +802,68 @@ int qt_gemm_wq_panel(const void* X, int x_dtype, int M, int K, int64_t ldx, cons
 #define QT_WQ_PANEL_K_UNIT 128
 #define QT_WQ_PANEL_MAX_LDX 16777216 /* 2^24 elements: a block of 64 rows is addressed by 32-bit byte offsets below 2^31 */
 
+/* One weight of the fused decode forms below: Wq, w_format, N, s_w, G, zp_w and g_idx with the meanings of the A16 block
+ * above (K is the call's), and where the form has them bias [N] in x_dtype or NULL and the output Y [M, N] in x_dtype
+ * with row pitch ldy. */
+typedef struct qt_wq_weight {
+    const void* Wq;
+    int w_format;
+    int N;
+    const float* s_w;
+    int G;
+    const int8_t* zp_w;
+    const int32_t* g_idx;
+    const void* bias;
+    void* Y;
+    int64_t ldy;
+} qt_wq_weight;
+#define QT_WQ_FUSED_MAX_M 16
+#define QT_WQ_FUSED_K_UNIT 128
+#define QT_WQ_MULTI_MAX 4
+
+/* qt_gemm_wq_skinny_multi: qt_gemm_wq_skinny on 1 <= count <= QT_WQ_MULTI_MAX weights that read one X, in one launch
+ *   (q/k/v of an attention block at decode).  weights is a host array; every entry keeps its own
+ *   buffers, bias and output, nothing is concatenated or moved.  Taken: 1 <= M <= QT_WQ_FUSED_MAX_M, QT_W_INT4_PACKED
+ *   and QT_W_INT8, G = 1 and G = K / 128, with and without zp_w, with and without bias per weight, bf16 and fp16, any
+ *   N >= 1 per weight, ldy >= N, ldx >= K, K a multiple of QT_WQ_FUSED_K_UNIT, and X, every Wq and ldx * 2 multiples of
+ *   16 bytes (the skinny kernel's 16-byte path).  All weights share K, one format, one G and zero-points on all or on
+ *   none.  Everything else -- g_idx != NULL, a ragged K, M = 0 or M > 16, weights that differ in format, G or
+ *   zero-point presence, a misaligned operand or pitch, a null pointer, a dtype that is not 16-bit, count out of range
+ *   -- returns QT_ERR_INVALID before any launch, and qt_last_error names the reason.
+ *   Output i is bit-identical to qt_gemm_wq_skinny on weight i with the same X: the grid's x dimension is
+ *   sum_i ceil(N_i / 16) column tiles, a workgroup finds its weight in a by-value table of tile starts and runs the
+ *   skinny kernel's 16-byte loop on it -- wave w the k-blocks kb = w, w + 4, ... in ascending order on the same MFMA
+ *   with the same fragment layout, then ((c0 + c1) + c2) + c3, the bias, one rounding.  qt_gemm_wq_skinny's error bound
+ *   and exact-input guarantee carry over.  Deterministic, no atomics, no workspace.  No byte outside X [M, K] (pitch
+ *   ldx), each Wq, s_w / zp_w [N, G] and bias [N] is read; nothing outside each Y[m < M, n < N] is written. */
+int qt_gemm_wq_skinny_multi(const void* X, int x_dtype, int M, int K, int64_t ldx, const qt_wq_weight* weights,
+                            int count, qt_stream_t stream);
+
+/* qt_gemm_wq_skinny_act_mul: the two GEMVs of a gated MLP and the glue between them in one launch --
+ *   H [M, I] = act(X Wg^T) * (X Wu^T) in x_dtype with row pitch ldh >= I, I = gate->N = up->N, act: QT_ACT_SILU
+ *   (DESIGN.md 4.27).  Taken and refused: qt_gemm_wq_skinny_multi's conditions on X and on both weights; gate and up
+ *   must agree in format, N, G and zero-point presence, and carry no bias and no Y (H is the one output).
+ *   H is bit-identical to F.silu(qt_gemm_wq_skinny(X, Wg)) * qt_gemm_wq_skinny(X, Wu) as torch computes it on the device:
+ *   a workgroup owns 16 columns n of the gate weight and the same 16 columns of the up weight; wave w takes the k-blocks
+ *   kb = w, w + 4, ... in ascending order, loads its activation fragment once per k-block and feeds it to two MFMA
+ *   chains with one fp32 accumulator each, each chain the skinny kernel's on that weight; both go through LDS as
+ *   ((c0 + c1) + c2) + c3; then, per element,
+ *     g = round_to_dtype(acc_g);  u = round_to_dtype(acc_u)        -- the two skinny outputs
+ *     h = qt_act_mul_quantize_i8's sequence a, a', p, h on (g, u)  -- one statement of it serves both (csrc/h16_act.h)
+ *   Deterministic, no atomics, no workspace, no bias.  No byte outside X [M, K] (pitch ldx), the two Wq and their
+ *   s_w / zp_w [I, G] is read; nothing outside H[m < M, n < I] is written.  (csrc/wq_fused.hip) */
+int qt_gemm_wq_skinny_act_mul(const void* X, int x_dtype, int M, int K, int64_t ldx, const qt_wq_weight* gate,
+                              const qt_wq_weight* up, int act, void* H, int64_t ldh, qt_stream_t stream);
+
+/* qt_rmsnorm: qt_rmsnorm_quantize_i8 without its quantiser, for readers of Y alone (the A16 runtime):
+ *   steps 1 to 5 of that sequence word for word -- the same chunk walk, butterfly and wave order, the same fp64
+ *   1 / sqrt, the same two roundings of step 5 -- so Y [M, K] (required, row pitch ldy >= K) and rstd [M] (may be NULL)
+ *   are bit-identical to what qt_rmsnorm_quantize_i8 writes for the same X, weight and eps.  A null X, weight or Y,
+ *   M <= 0, K <= 0, K > 32768, a pitch below K, an x_dtype that is not 16-bit, an eps that is negative or not finite
+ *   are QT_ERR_INVALID before any launch.  One workgroup per row, no atomics, no workspace.  (csrc/rmsnorm_quant.hip) */
+int qt_rmsnorm(const void* X, int64_t ldx, const void* weight, int x_dtype, int64_t M, int K, float eps, void* Y,
+               int64_t ldy, float* rstd, qt_stream_t stream);
+
 /* qt_gemm_wq_grouped: qt_gemm_wq_skinny over E weight matrices at once, for routed-expert banks (engine/qlinear.py
  *   WeightOnlyExperts).  Y [R, N] in x_dtype (pitch ldy): expert e owns output rows
  *   [offsets[e], offsets[e + 1]) (offsets int32 [E + 1], on the device, ascending, offsets[E] <= R; rows past

@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "h16_act.h"
 #include "i8_quant.h"
 
 namespace {
@@ -21,27 +22,7 @@ constexpr int AQ_MAX_K = 32768;                                   // the GEMMs' 
 constexpr int AQ_RED_BYTES = 2 * (AQ_THREADS / 64) * 4;           // min / max of each wave
 constexpr int AQ_MAX_LDS = AQ_MAX_K * 2 + AQ_RED_BYTES;
 
-// fp32 -> the bits of x_dtype, one rounding to nearest even
-template <bool F16>
-__device__ __forceinline__ unsigned short to_h16(float v) {
-    if (F16) return __builtin_bit_cast(unsigned short, (_Float16)v);
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-}
-template <bool F16>
-__device__ __forceinline__ float from_h16(unsigned short b) {
-    return F16 ? qt_f16_to_f32(b) : qt_bf16_to_f32(b);
-}
-
-// h = round(round(silu(g)) * u): torch's SiLU kernel leaves a 16-bit tensor, its multiply another
-template <bool F16>
-__device__ __forceinline__ unsigned short silu_mul(unsigned short gb, unsigned short ub) {
-    const float g = from_h16<F16>(gb);
-    const float u = from_h16<F16>(ub);
-    const float a = g / (1.0f + expf(-g));
-    const float ar = from_h16<F16>(to_h16<F16>(a));
-    const float p = ar * u;
-    return to_h16<F16>(p);
-}
+// to_h16 / from_h16 and h = silu_mul(g, u) are h16_act.h's, shared with wq_fused.hip.
 
 // VEC_IN: gate and up rows take 16-byte loads (K % 8 == 0, both pointers 16-byte aligned, both pitches % 8 == 0).
 // vec_out: Xq rows take 8-byte stores and there is no col_perm;  h_vec: H rows take 16-byte stores.

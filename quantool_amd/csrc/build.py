@@ -48,6 +48,9 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "wq_panel.hip": _NO_PACKED_FP32,
     "observer_mse.hip": _NO_PACKED_FP32,
+    "wq_fused.hip": _NO_PACKED_FP32,
+    # since qt_rmsnorm's instances joined it: Y must be the quantising instances' Y bit for bit, on every device
+    "rmsnorm_quant.hip": _NO_PACKED_FP32,
 }
 
 # lab builds: extra flags (e.g. QT_EXTRA_HIPCC_FLAGS=-DQT_XTX_ABLATION for tools/xtx_wrap_sweep.sh); part of the stamp

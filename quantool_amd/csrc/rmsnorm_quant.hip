@@ -9,6 +9,9 @@
 // K allow; no atomics, no workspace, a row's result depends on nothing but the row: the element-load instances walk
 // the same 8-element chunks in the same order as the 16-byte ones, so the sum of squares has one order.
 //
+// qt_rmsnorm is the same kernel without the quantiser (QUANT = false): passes 1 and 2 alone, for the A16 runtime, whose
+// Linears read Y itself.  Y and rstd are the bits qt_rmsnorm_quantize_i8 writes.
+//
 // Numerics are the header's fixed sequence; -ffp-contract=off (csrc/build.py) keeps every multiply and add its own
 // rounding.  The quantiser's constants and per-element step are qlinear.hip's own (i8_quant.h).
 #include <math.h>
@@ -49,8 +52,10 @@ __device__ __forceinline__ unsigned short norm_mul(unsigned short xb, unsigned s
 
 // VEC_IN: x rows and the weight take 16-byte loads (K % 8 == 0, both pointers 16-byte aligned, ldx % 8 == 0).
 // vec_out: Xq rows take 8-byte stores and there is no col_perm;  y_vec: Y rows take 16-byte stores.
-template <bool F16, bool VEC_IN>
-__global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
+// QUANT = false is qt_rmsnorm's form: passes 1 and 2 alone, Y required, nothing of the quantiser read or written.
+// The row pass is stated once here; the two kernels below are its two instances.
+template <bool F16, bool VEC_IN, bool QUANT>
+__device__ __forceinline__ void rmsnorm_row(
     const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ weight, int K, float eps,
     const int32_t* __restrict__ col_perm, int symmetric, int vec_out, int8_t* __restrict__ Xq, float* __restrict__ s_x,
     int32_t* __restrict__ zp_x, unsigned short* __restrict__ Y, int64_t ldy, int y_vec, float* __restrict__ rstd) {
@@ -60,7 +65,7 @@ __global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
     const int64_t m = blockIdx.x;
     const unsigned short* xrow = X + m * ldx;
     unsigned short* yout = Y ? Y + m * ldy : nullptr;
-    int8_t* qrow = Xq + m * (int64_t)K;
+    int8_t* qrow = QUANT ? Xq + m * (int64_t)K : nullptr;
     const int tid = threadIdx.x;
     constexpr int dtype = F16 ? QT_F16 : QT_BF16;
 
@@ -116,13 +121,15 @@ __global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
             for (int i = 0; i < 4; ++i) {
                 const unsigned short lo = norm_mul<F16>((unsigned short)(xw[i] & 0xffffu), (unsigned short)(ww[i] & 0xffffu), r);
                 const unsigned short hi = norm_mul<F16>((unsigned short)(xw[i] >> 16), (unsigned short)(ww[i] >> 16), r);
-                const float a = from_h16<F16>(lo), b = from_h16<F16>(hi);
-                mn = fminf(mn, fminf(a, b));
-                mx = fmaxf(mx, fmaxf(a, b));
+                if constexpr (QUANT) {
+                    const float a = from_h16<F16>(lo), b = from_h16<F16>(hi);
+                    mn = fminf(mn, fminf(a, b));
+                    mx = fmaxf(mx, fmaxf(a, b));
+                }
                 yw[i] = (unsigned)lo | ((unsigned)hi << 16);
             }
             const uint4 y4 = make_uint4(yw[0], yw[1], yw[2], yw[3]);
-            *(uint4*)(row + k) = y4;
+            if constexpr (QUANT) *(uint4*)(row + k) = y4;
             if (yout) {
                 if (y_vec) {
                     *(uint4*)(yout + k) = y4;
@@ -140,14 +147,17 @@ __global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
             const int n = min(8, K - k0);
             for (int i = 0; i < n; ++i) {
                 const unsigned short yb = norm_mul<F16>(row[k0 + i], weight[k0 + i], r);
-                const float a = from_h16<F16>(yb);
-                mn = fminf(mn, a);
-                mx = fmaxf(mx, a);
-                row[k0 + i] = yb;
+                if constexpr (QUANT) {
+                    const float a = from_h16<F16>(yb);
+                    mn = fminf(mn, a);
+                    mx = fmaxf(mx, a);
+                    row[k0 + i] = yb;
+                }
                 if (yout) yout[k0 + i] = yb;
             }
         }
     }
+    if constexpr (!QUANT) return;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         mn = fminf(mn, __shfl_xor(mn, off));
@@ -185,6 +195,23 @@ __global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
 }
 
 template <bool F16, bool VEC_IN>
+__global__ void __launch_bounds__(RQ_THREADS) rmsnorm_quantize_kernel(
+    const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ weight, int K, float eps,
+    const int32_t* __restrict__ col_perm, int symmetric, int vec_out, int8_t* __restrict__ Xq, float* __restrict__ s_x,
+    int32_t* __restrict__ zp_x, unsigned short* __restrict__ Y, int64_t ldy, int y_vec, float* __restrict__ rstd) {
+    rmsnorm_row<F16, VEC_IN, true>(X, ldx, weight, K, eps, col_perm, symmetric, vec_out, Xq, s_x, zp_x, Y, ldy, y_vec,
+                                   rstd);
+}
+
+template <bool F16, bool VEC_IN>
+__global__ void __launch_bounds__(RQ_THREADS) rmsnorm_kernel(
+    const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ weight, int K, float eps,
+    unsigned short* __restrict__ Y, int64_t ldy, int y_vec, float* __restrict__ rstd) {
+    rmsnorm_row<F16, VEC_IN, false>(X, ldx, weight, K, eps, nullptr, 1, 0, nullptr, nullptr, nullptr, Y, ldy, y_vec,
+                                    rstd);
+}
+
+template <bool F16, bool VEC_IN>
 int launch(int64_t M, size_t lds, hipStream_t stream, const unsigned short* X, int64_t ldx, const unsigned short* weight,
            int K, float eps, const int32_t* col_perm, int symmetric, int vec_out, int8_t* Xq, float* s_x, int32_t* zp_x,
            unsigned short* Y, int64_t ldy, int y_vec, float* rstd) {
@@ -195,6 +222,20 @@ int launch(int64_t M, size_t lds, hipStream_t stream, const unsigned short* X, i
     }));
     hipLaunchKernelGGL((rmsnorm_quantize_kernel<F16, VEC_IN>), dim3((unsigned)M), dim3(RQ_THREADS), lds, stream, X, ldx,
                        weight, K, eps, col_perm, symmetric, vec_out, Xq, s_x, zp_x, Y, ldy, y_vec, rstd);
+    QT_LAUNCH_CHECK();
+    return QT_OK;
+}
+
+template <bool F16, bool VEC_IN>
+int launch_y(int64_t M, size_t lds, hipStream_t stream, const unsigned short* X, int64_t ldx, const unsigned short* weight,
+             int K, float eps, unsigned short* Y, int64_t ldy, int y_vec, float* rstd) {
+    static QtOncePerDevice lds_attr;   // as launch()
+    QT_HIP(lds_attr.run([&] {
+        return hipFuncSetAttribute((const void*)rmsnorm_kernel<F16, VEC_IN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   RQ_MAX_LDS);
+    }));
+    hipLaunchKernelGGL((rmsnorm_kernel<F16, VEC_IN>), dim3((unsigned)M), dim3(RQ_THREADS), lds, stream, X, ldx, weight, K,
+                       eps, Y, ldy, y_vec, rstd);
     QT_LAUNCH_CHECK();
     return QT_OK;
 }
@@ -234,4 +275,34 @@ extern "C" int qt_rmsnorm_quantize_i8(const void* X, int64_t ldx, const void* we
     }
     if (vec_in) return launch<false, true>(M, lds, stream, x, ldx, w, K, eps, col_perm, symmetric, vec_out, Xq, s_x, zp, y, ldy, y_vec, rstd);
     return launch<false, false>(M, lds, stream, x, ldx, w, K, eps, col_perm, symmetric, vec_out, Xq, s_x, zp, y, ldy, y_vec, rstd);
+}
+
+extern "C" int qt_rmsnorm(const void* X, int64_t ldx, const void* weight, int x_dtype, int64_t M, int K, float eps, void* Y,
+                          int64_t ldy, float* rstd, qt_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* fn = "qt_rmsnorm";
+    QT_CHECK_ARG(X, "%s: X is null", fn);
+    QT_CHECK_ARG(weight, "%s: weight is null", fn);
+    QT_CHECK_ARG(Y, "%s: Y is null", fn);
+    QT_CHECK_ARG(M > 0, "%s: M %lld must be positive", fn, (long long)M);
+    QT_CHECK_ARG(K > 0, "%s: K %d must be positive", fn, K);
+    QT_CHECK_ARG(K <= RQ_MAX_K, "%s: K %d exceeds %d, qt_rmsnorm_quantize_i8's bound", fn, K, RQ_MAX_K);
+    QT_CHECK_ARG(M <= 0x7fffffffLL, "%s: M %lld too large", fn, (long long)M);
+    QT_CHECK_ARG(ldx >= K, "%s: ldx %lld is below K %d", fn, (long long)ldx, K);
+    QT_CHECK_ARG(ldy >= K, "%s: ldy %lld is below K %d", fn, (long long)ldy, K);
+    QT_CHECK_ARG(qt_dtype_is16(x_dtype), "%s: x_dtype %d must be bf16 or fp16", fn, x_dtype);
+    QT_CHECK_ARG(eps >= 0.0f && isfinite(eps), "%s: eps %g must be finite and not negative", fn, (double)eps);
+
+    const bool vec_in = K % 8 == 0 && ldx % 8 == 0 && (((uintptr_t)X | (uintptr_t)weight) & 15) == 0;
+    const int y_vec = ldy % 8 == 0 && ((uintptr_t)Y & 15) == 0;
+    const size_t lds = (size_t)((K + 7) / 8) * 16 + RQ_RED_BYTES;
+    const unsigned short* x = (const unsigned short*)X;
+    const unsigned short* w = (const unsigned short*)weight;
+    unsigned short* y = (unsigned short*)Y;
+    if (x_dtype == QT_F16) {
+        if (vec_in) return launch_y<true, true>(M, lds, stream, x, ldx, w, K, eps, y, ldy, y_vec, rstd);
+        return launch_y<true, false>(M, lds, stream, x, ldx, w, K, eps, y, ldy, y_vec, rstd);
+    }
+    if (vec_in) return launch_y<false, true>(M, lds, stream, x, ldx, w, K, eps, y, ldy, y_vec, rstd);
+    return launch_y<false, false>(M, lds, stream, x, ldx, w, K, eps, y, ldy, y_vec, rstd);
 }

@@ -40,6 +40,10 @@ With ``a8_fused_act=True`` an A8 checkpoint's MLP glue -- SiLU(gate) * up and th
 as one pass (``qt_act_mul_quantize_i8``): ``QuantizedExperts.fused_act`` in a bank, a ``QuantizedMLP`` in place of a
 Llama-style dense MLP.  With ``a8_fused_norm=True`` the RMSNorms in front of q/k/v and gate/up become
 ``QuantizingRMSNorm``s: the norm and the quantiser its consumers share run as one pass (``qt_rmsnorm_quantize_i8``).
+The packed A16 runtime has the same pair: with ``a16_fused_act=True`` a Llama-style MLP of three ``WeightOnlyLinear``s
+becomes a ``WeightOnlyMLP`` (gate, up, SiLU and the multiply in one launch at decode size,
+``qt_gemm_wq_skinny_act_mul``) and q/k/v share one launch (``SharedOutputs``, ``qt_gemm_wq_skinny_multi``); with
+``a16_fused_norm=True`` the decoder layers' RMSNorms become ``WeightOnlyRMSNorm``s (``qt_rmsnorm``).
 
 The modules are defined in ``qmodules.py`` and one stored weight as a value (``StoredWeight``: the only reader of a
 module's checkpoint tensors, the kernels' layout rules, ``dequantize``, the stacking of experts into a bank) in
@@ -55,8 +59,8 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .qmodules import (QuantizedExperts, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm, SharedRows,  # noqa: F401
-                       WeightOnlyExperts, WeightOnlyLinear)
+from .qmodules import (QuantizedExperts, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm, SharedOutputs,  # noqa: F401
+                       SharedRows, WeightOnlyExperts, WeightOnlyLinear, WeightOnlyMLP, WeightOnlyRMSNorm)
 from .serialization import load_state
 from .stored_weight import GROUP, StoredWeight, group_sums, pack_int4, unpack_int4  # noqa: F401 (re-exported)
 
@@ -292,6 +296,29 @@ def _install_quantizing_norms(model: nn.Module) -> None:
                            QuantizingRMSNorm(norm.weight, norm.variance_epsilon, consumers, takes=takes))
 
 
+def _install_a16_fused_act(model: nn.Module) -> None:
+    """``a16_fused_act``: a ``WeightOnlyMLP`` in place of every MLP for which ``WeightOnlyMLP.eligible`` holds, and one
+    ``SharedOutputs`` over ``q_proj`` / ``k_proj`` / ``v_proj`` of every module that has the three as
+    ``WeightOnlyLinear``s that can share a launch."""
+    for name, mlp in [(n, m) for n, m in model.named_modules() if WeightOnlyMLP.eligible(m)]:
+        _set_submodule(model, name, WeightOnlyMLP(mlp.gate_proj, mlp.up_proj, mlp.down_proj, mlp.act_fn))
+    for attn in list(model.modules()):
+        members = [getattr(attn, n, None) for n in ("q_proj", "k_proj", "v_proj")]
+        if all(m is not None for m in members) and SharedOutputs.refusal(members) is None:
+            SharedOutputs(members)
+
+
+def _install_weight_only_norms(model: nn.Module) -> None:
+    """``a16_fused_norm``: in every decoder layer of ``WeightOnlyRMSNorm.PLAIN_LAYERS``, ``input_layernorm`` and
+    ``post_attention_layernorm`` become ``WeightOnlyRMSNorm``s wherever ``WeightOnlyRMSNorm.refusal`` is None."""
+    for name, layer in [(n, m) for n, m in model.named_modules()
+                        if type(m).__name__ in WeightOnlyRMSNorm.PLAIN_LAYERS]:
+        for norm_name in ("input_layernorm", "post_attention_layernorm"):
+            norm = getattr(layer, norm_name, None)
+            if norm is not None and WeightOnlyRMSNorm.refusal(norm) is None:
+                _set_submodule(model, f"{name}.{norm_name}", WeightOnlyRMSNorm(norm.weight, norm.variance_epsilon))
+
+
 A16_MODES = ("dequantized", "packed")
 # The largest ``a16_experts_wide_tokens``: the largest call size at which qt_moe_gemm_wq_wide was measured (DESIGN.md
 # 4.19).
@@ -303,7 +330,8 @@ A16_PANEL_MAX_ROWS = 512
 def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16: str = "dequantized",
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
-                   a8_fused_norm: bool = False, a16_panel_rows: int = 0) -> nn.Module:
+                   a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
+                   a16_fused_norm: bool = False) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -335,6 +363,17 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``QuantizingRMSNorm.refusal`` is None.  The norm's sum over K runs in the kernel's order, not torch's, so outputs may
     differ from the default loader's in rare last bits; state-dict keys do not move, and it is recorded
     under ``"a8_fused_norm"``.  A16 checkpoints ignore it.
+    ``a16_fused_act`` (False, the default, or True; needs ``a16="packed"``) puts a ``WeightOnlyMLP`` in place of every
+    dense MLP for which ``WeightOnlyMLP.eligible`` holds, so inputs of 1 to 16 rows run gate, up, SiLU and the multiply
+    as one launch, ``qt_gemm_wq_skinny_act_mul``, and ties ``q_proj`` / ``k_proj`` / ``v_proj`` of every attention block
+    into a ``SharedOutputs``, so the three GEMVs of such an input run as one launch, ``qt_gemm_wq_skinny_multi``.  Both
+    equal the launches they replace to the bit: the flag changes speed alone.  State-dict keys do not move, and it is
+    recorded under ``"a16_fused_act"``.  ``WeightOnlyExperts`` are not touched; A8 checkpoints ignore it.
+    ``a16_fused_norm`` (False, the default, or True; needs ``a16="packed"``) puts a ``WeightOnlyRMSNorm`` in place of
+    ``input_layernorm`` and ``post_attention_layernorm`` in every decoder layer of ``WeightOnlyRMSNorm.PLAIN_LAYERS``
+    wherever ``WeightOnlyRMSNorm.refusal`` is None: one launch, ``qt_rmsnorm``.  It changes bits exactly as
+    ``a8_fused_norm`` does (the kernel's order of summation over K); state-dict keys do not move, and it
+    is recorded under ``"a16_fused_norm"``.  A8 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -376,6 +415,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         raise ValueError(f"a8_fused_act={a8_fused_act!r}: expected True or False")
     if type(a8_fused_norm) is not bool:
         raise ValueError(f"a8_fused_norm={a8_fused_norm!r}: expected True or False")
+    for flag, value in (("a16_fused_act", a16_fused_act), ("a16_fused_norm", a16_fused_norm)):
+        if type(value) is not bool:
+            raise ValueError(f"{flag}={value!r}: expected True or False")
+        if value and a16 != "packed":
+            raise ValueError(f"{flag} needs a16='packed' (dequantised Linears and their norms run on torch's kernels)")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -449,6 +493,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             _set_submodule(model, name, QuantizedMLP(mlp.gate_proj, mlp.up_proj, mlp.down_proj, mlp.act_fn))
     if a8 and a8_fused_norm:
         _install_quantizing_norms(model)
+    if not a8 and a16_fused_act:
+        _install_a16_fused_act(model)
+    if not a8 and a16_fused_norm:
+        _install_weight_only_norms(model)
     from .sequential import rename_module_prefix as _rename
 
     ignore = [_rename(n, inverse) for n in qcfg.get("ignore") or []]
@@ -460,6 +508,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows
         model._qt_checkpoint["a16_panel_rows"] = a16_panel_rows
+        model._qt_checkpoint["a16_fused_act"] = a16_fused_act
+        model._qt_checkpoint["a16_fused_norm"] = a16_fused_norm
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))
         if packed_experts:
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)

@@ -431,6 +431,9 @@ class WeightOnlyLinear(nn.Module):
                 f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}, "
                 f"panel_max_m={self.panel_max_m}")
 
+    # A ``SharedOutputs`` this Linear is a member of (None, the default: it computes for itself).
+    outputs_from = None
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         bias = None if self.bias is None else self.bias.to(x.dtype)
         w = self.stored
@@ -440,6 +443,10 @@ class WeightOnlyLinear(nn.Module):
 
         M = x.numel() // w.K
         if 1 <= M <= min(self.skinny_max_m, ops.SKINNY_MAX_M):
+            if self.outputs_from is not None:
+                y = self.outputs_from.take(self, x)
+                if y is not None:
+                    return y
             y = ops.gemm_wq_skinny(_rows(x, w.K), w.levels, w.scale, zp_w=w.zero_point, g_idx=w.g_idx, bias=bias)
             return y.reshape(*x.shape[:-1], w.N)
         if (self.stream_max_m > 0 and self.skinny_max_m < M <= self.stream_max_m and w.K >= self.stream_min_k
@@ -458,6 +465,204 @@ class WeightOnlyLinear(nn.Module):
                 return y.reshape(*x.shape[:-1], w.N)
         W = ops.dequantize_weight(w.levels, w.scale, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx, dtype=x.dtype)
         return F.linear(x, W, bias)
+
+
+def _kernel_weight(m: WeightOnlyLinear):
+    w = m.stored
+    return w.levels, w.scale, w.zero_point, w.g_idx
+
+
+class SharedOutputs:
+    """The hand-off between the ``WeightOnlyLinear``s that read one tensor (an attention block's q/k/v): the first
+    member to see a tensor at decode size runs ``qt_gemm_wq_skinny_multi`` for all of them -- one launch, every member
+    on its own buffers, each output equal to the member's own GEMV to the bit -- keeps its output and leaves the
+    others' here with the tensor and its version.  ``take(member, x)`` hands a kept output over only for that very
+    tensor, unwritten since; after the last member every reference is dropped, so between forwards nothing is pinned.
+    Where the launch does not apply (``refusal`` at run time: rows, alignment, a tensor without a version counter)
+    ``take`` gives None and the member computes for itself.  Opt-in: ``load_quantized(..., a16_fused_act=True)``."""
+
+    # The one launch up to this many rows (at most ops.WQ_FUSED_MAX_M).  0: never -- on Llama-3-8B's q/k/v the launch with
+    # its host-side table took 1.03 - 1.27 times the three GEMV calls' time at 8 and 16 rows (W4A16 and W8A16) and 1.05
+    # times at one row of W8A16, so no measured row count is free of a losing cell (DESIGN.md 4.27).  The kernel and the
+    # hand-off stand; a caller who sets this to 16 gets them.
+    max_m = 0
+
+    def __init__(self, members):
+        members = list(members)
+        reason = self.refusal(members)
+        if reason:
+            raise ValueError(f"SharedOutputs: {reason}")
+        self.members = members
+        self.clear()
+        for m in members:
+            m.outputs_from = self
+
+    @staticmethod
+    def refusal(members) -> Optional[str]:
+        """Why these modules cannot share a launch whatever the input (None: they can)."""
+        members = list(members)
+        if not 2 <= len(members) <= 4 or not all(isinstance(m, WeightOnlyLinear) for m in members):
+            return "the members must be two to four WeightOnlyLinears"
+        first = members[0]
+        for m in members:
+            if m.g_idx is not None:
+                return "a member carries g_idx"
+            if (m.in_features != first.in_features or m.int4 != first.int4
+                    or m.weight_scale.shape[1] != first.weight_scale.shape[1]
+                    or (m.weight_zero_point is None) != (first.weight_zero_point is None)):
+                return "the members differ in in_features, format, groups or zero-point presence"
+        return None
+
+    def clear(self) -> None:
+        self.x = self.version = None
+        self.out = {}
+
+    @property
+    def holds_tensors(self) -> bool:
+        return self.x is not None or bool(self.out)
+
+    def _run(self, x: torch.Tensor):
+        from ..hip import ops
+
+        members = self.members
+        K = members[0].in_features
+        M = x.numel() // K
+        if not 1 <= M <= min(self.max_m, ops.WQ_FUSED_MAX_M, *(m.skinny_max_m for m in members)):
+            return None
+        x2 = _rows(x, K)
+        ws = [_kernel_weight(m) for m in members]
+        if any(w[0].device != x.device for w in ws) or not ops.gemm_wq_fused_supported(x2, ws):
+            return None
+        ys = ops.gemm_wq_skinny_multi(x2, [(*w[:3], None if m.bias is None else m.bias.to(x.dtype))
+                                           for w, m in zip(ws, members)])
+        return [y.reshape(*x.shape[:-1], m.out_features) for y, m in zip(ys, members)]
+
+    def take(self, member: WeightOnlyLinear, x: torch.Tensor) -> Optional[torch.Tensor]:
+        """``member``'s output for ``x``: kept from the launch another member ran on this very tensor, or out of a
+        launch of its own for all members; None where ``member`` has to compute for itself."""
+        if self.x is not None and x is self.x and _version_of(x) == self.version:
+            y = self.out.pop(id(member), None)
+            if y is not None:
+                if not self.out:
+                    self.clear()
+                return y
+        self.clear()
+        version = _version_of(x)
+        if version is None:          # staleness could not be seen
+            return None
+        ys = self._run(x)
+        if ys is None:
+            return None
+        own = None
+        for m, y in zip(self.members, ys):
+            if m is member:
+                own = y
+            else:
+                self.out[id(m)] = y
+        self.x, self.version = x, version
+        return own
+
+
+class WeightOnlyMLP(nn.Module):
+    """A Llama-style MLP ``down_proj(act_fn(gate_proj(x)) * up_proj(x))`` of three ``WeightOnlyLinear``s.  At decode
+    size -- 1 <= M <= ``fused_max_m`` rows on the device, where ``ops.gemm_wq_fused_supported`` holds for gate and up --
+    the two GEMVs, SiLU and the multiply run as one launch, ``qt_gemm_wq_skinny_act_mul``, equal to the bit to the
+    four it replaces (include/quantool_amd.h), so the module changes speed alone.  Anything else runs the three
+    children's own ``forward``, so their stream / panel settings still apply above 16 rows.  Opt-in:
+    ``load_quantized(..., a16="packed", a16_fused_act=True)`` builds it where ``eligible`` holds.  The children keep
+    their names, so state-dict keys do not move."""
+
+    PLAIN_MLPS = QuantizedMLP.PLAIN_MLPS
+    # The one launch up to this many rows (at most ops.WQ_FUSED_MAX_M): on Llama-3-8B's gate / up it took 0.66 - 0.83
+    # of the four launches' time at 1, 8 and 16 rows, W4A16 and W8A16; no measured cell loses (DESIGN.md 4.27).
+    fused_max_m = 16
+
+    def __init__(self, gate_proj: WeightOnlyLinear, up_proj: WeightOnlyLinear, down_proj: WeightOnlyLinear, act_fn):
+        super().__init__()
+        reason = self.refusal(gate_proj, up_proj, down_proj, act_fn)
+        if reason:
+            raise ValueError(f"WeightOnlyMLP: {reason}")
+        self.gate_proj, self.up_proj, self.down_proj, self.act_fn = gate_proj, up_proj, down_proj, act_fn
+
+    @staticmethod
+    def refusal(gate, up, down, act_fn) -> Optional[str]:
+        """Why these four cannot run fused (None: they can)."""
+        if not all(isinstance(m, WeightOnlyLinear) for m in (gate, up, down)):
+            return "gate_proj, up_proj and down_proj must all be WeightOnlyLinears"
+        if not is_silu(act_fn):
+            return "act_fn is not SiLU"
+        if gate.in_features != up.in_features or not gate.out_features == up.out_features == down.in_features:
+            return "gate_proj / up_proj differ in features, or their outputs are not down_proj's inputs"
+        if gate.bias is not None or up.bias is not None:
+            return "gate_proj or up_proj has a bias"
+        return SharedOutputs.refusal((gate, up))
+
+    @classmethod
+    def eligible(cls, mlp: nn.Module) -> bool:
+        """Whether ``mlp`` is one of ``PLAIN_MLPS`` whose three Linears and activation can run fused."""
+        if type(mlp).__name__ not in cls.PLAIN_MLPS:
+            return False
+        parts = [getattr(mlp, n, None) for n in ("gate_proj", "up_proj", "down_proj", "act_fn")]
+        return cls.refusal(*parts) is None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up, down = self.gate_proj, self.up_proj, self.down_proj
+        K = gate.in_features
+        M = x.numel() // K
+        if x.is_cuda and 1 <= M <= min(self.fused_max_m, gate.skinny_max_m, up.skinny_max_m):
+            from ..hip import ops
+
+            x2 = _rows(x, K)
+            wg, wu = _kernel_weight(gate), _kernel_weight(up)
+            if M <= ops.WQ_FUSED_MAX_M and wg[0].device == x.device and ops.gemm_wq_fused_supported(x2, (wg, wu)):
+                h = ops.gemm_wq_skinny_act_mul(x2, wg[:3], wu[:3])
+                return down(h.reshape(*x.shape[:-1], gate.out_features))
+        return down(self.act_fn(gate(x)) * up(x))
+
+
+class WeightOnlyRMSNorm(nn.Module):
+    """An RMSNorm of an A16 model as one launch: ``forward(x)`` runs ``qt_rmsnorm`` in place of torch's chain of
+    elementwise and reduction kernels and returns ``Y`` shaped like ``x``.  ``Y`` is ``qt_rmsnorm_quantize_i8``'s ``Y``
+    to the bit -- the five lines of ``LlamaRMSNorm.forward`` with the kernel's own order of summation over K (DESIGN.md
+    4.21) -- and any reader may use it: there is no hand-off.  Opt-in: ``load_quantized(..., a16="packed",
+    a16_fused_norm=True)`` builds it where ``refusal`` is None.  ``weight`` keeps its name, so state-dict keys do not
+    move.  The installed torch sequence runs instead exactly where ``QuantizingRMSNorm`` runs it."""
+
+    PLAIN_NORMS = QuantizingRMSNorm.PLAIN_NORMS
+    PLAIN_LAYERS = QuantizingRMSNorm.PLAIN_LAYERS
+    MAX_K = QuantizingRMSNorm.MAX_K
+    device_types = ("cuda",)   # where the kernel exists
+
+    def __init__(self, weight: nn.Parameter, eps: float):
+        super().__init__()
+        self.weight = weight if isinstance(weight, nn.Parameter) else nn.Parameter(weight, requires_grad=False)
+        self.variance_epsilon = float(eps)
+
+    @classmethod
+    def refusal(cls, norm: nn.Module) -> Optional[str]:
+        """Why ``norm`` cannot run on the kernel (None: it can)."""
+        if type(norm).__name__ not in cls.PLAIN_NORMS:
+            return f"{type(norm).__name__} is not one of {cls.PLAIN_NORMS}"
+        weight = getattr(norm, "weight", None)
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or not hasattr(norm, "variance_epsilon"):
+            return "the norm has no 1-d weight or no variance_epsilon"
+        return None
+
+    def extra_repr(self) -> str:
+        return f"{tuple(self.weight.shape)}, eps={self.variance_epsilon}"
+
+    _torch_forward = QuantizingRMSNorm._torch_forward
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w = self.weight
+        K = w.numel()
+        if (x.device.type not in self.device_types or x.dtype not in (torch.bfloat16, torch.float16)
+                or x.dtype != w.dtype or x.device != w.device or K > self.MAX_K or x.numel() == 0
+                or (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
+            return self._torch_forward(x)
+        from ..hip import ops
+
+        return ops.rmsnorm(_rows(x, K), w, self.variance_epsilon).reshape(x.shape)
 
 
 class _RoutedExperts(nn.Module):

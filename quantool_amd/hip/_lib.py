@@ -161,6 +161,12 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_gemm_wq_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # weights: a host array of WqWeight (qt_wq_weight)
+    "qt_gemm_wq_skinny_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p]),
+    "qt_gemm_wq_skinny_act_mul": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_int64, c_void_p]),
+    "qt_rmsnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int64, c_void_p,
+                           c_void_p]),
     "qt_gemm_wq_grouped": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_moe_gemm_wq_wide": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
@@ -174,6 +180,15 @@ SIGNATURES = {
                               c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_size_t, c_void_p]),
 }
+
+
+
+class WqWeight(ctypes.Structure):
+    """``qt_wq_weight``: one weight of ``qt_gemm_wq_skinny_multi`` / ``qt_gemm_wq_skinny_act_mul``."""
+
+    _fields_ = [("Wq", c_void_p), ("w_format", c_int), ("N", c_int), ("s_w", c_void_p), ("G", c_int),
+                ("zp_w", c_void_p), ("g_idx", c_void_p), ("bias", c_void_p), ("Y", c_void_p), ("ldy", c_int64)]
+
 
 _lib = None
 

@@ -1489,6 +1489,136 @@ def gemm_wq_panel(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w:
     return Y
 
 
+WQ_FUSED_MAX_M = 16      # rows of X the fused decode forms take (QT_WQ_FUSED_MAX_M)
+WQ_FUSED_K_UNIT = 128    # K must be a multiple (QT_WQ_FUSED_K_UNIT)
+WQ_MULTI_MAX = 4         # weights of one qt_gemm_wq_skinny_multi launch (QT_WQ_MULTI_MAX)
+
+
+def _wq_fused_refusal(X: torch.Tensor, weights) -> Optional[str]:
+    """Why ``qt_gemm_wq_skinny_multi`` / ``qt_gemm_wq_skinny_act_mul`` would refuse X and these weights -- (Wq, s_w,
+    zp_w, g_idx) each -- or None.  Host-only, as ``_wq_stream_refusal``, whose rules hold for every weight."""
+    if not 1 <= len(weights) <= WQ_MULTI_MAX:
+        return f"1 <= count <= {WQ_MULTI_MAX} weights, got {len(weights)}"
+    Wq0, s0, zp0, _ = weights[0]
+    for i, (Wq, s_w, zp_w, g_idx) in enumerate(weights):
+        if g_idx is not None:
+            return f"weight {i}: g_idx is not taken (actorder group runs on qt_gemm_wq_skinny)"
+        why = _wq_stream_refusal(X, Wq, s_w, zp_w, None)
+        if why is not None:
+            return f"weight {i}: {why}"
+        if Wq.dtype != Wq0.dtype or s_w.shape[-1] != s0.shape[-1] or (zp_w is None) != (zp0 is None):
+            return f"weight {i} differs from weight 0 in format, G or zero-point presence"
+    if not 1 <= X.shape[0] <= WQ_FUSED_MAX_M:
+        return f"1 <= M <= {WQ_FUSED_MAX_M} rows only, got X {tuple(X.shape)}"
+    return None
+
+
+def gemm_wq_fused_supported(X: torch.Tensor, weights) -> bool:
+    """Whether ``gemm_wq_skinny_multi`` (and, for two weights of equal N, ``gemm_wq_skinny_act_mul``) takes X and
+    ``weights``, a sequence of (Wq, s_w, zp_w, g_idx): 1 to 16 rows, no ``g_idx``, 16-bit X with unit column stride, K a
+    multiple of 128, G = 1 or K/128, X, every Wq and X's row pitch 16-byte aligned, and one format, one G and
+    zero-points on all weights or on none.  Host-only."""
+    return _wq_fused_refusal(X, weights) is None
+
+
+def _wq_weight_table(X: torch.Tensor, entries):
+    """``entries`` -- (Wq, s_w, zp_w, bias or None, Y or None) each -- checked against X and laid out as the host array
+    of ``qt_wq_weight`` the two fused entry points read; returns (array, [N, ...])."""
+    K = X.shape[1]
+    table = (_lib.WqWeight * len(entries))()
+    Ns = []
+    for slot, (Wq, s_w, zp_w, bias, Y) in zip(table, entries):
+        fmt, N, _, G = _wq_weight(Wq, s_w, zp_w, None, K)
+        if Wq.device != X.device:
+            raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+        if bias is not None:
+            _req(bias, X.dtype, "bias", 1)
+            if bias.numel() != N or not bias.is_contiguous():
+                raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+        slot.Wq, slot.w_format, slot.N, slot.s_w, slot.G = Wq.data_ptr(), fmt, N, s_w.data_ptr(), G
+        slot.zp_w, slot.g_idx, slot.bias = _ptr(zp_w), None, _ptr(bias)
+        slot.Y, slot.ldy = _ptr(Y), (0 if Y is None else Y.stride(0))
+        Ns.append(N)
+    return table, Ns
+
+
+def gemm_wq_skinny_multi(X: torch.Tensor, weights) -> list:
+    """``gemm_wq_skinny`` on up to ``WQ_MULTI_MAX`` weights that read one X, in one launch
+    (``qt_gemm_wq_skinny_multi``): q/k/v of an attention block at decode.  ``weights`` is a sequence of (Wq, s_w, zp_w,
+    bias) with ``gemm_wq_skinny``'s meanings (zp_w and bias may be None); returns [Y_i [M, N_i]], each bit-identical to
+    ``gemm_wq_skinny`` on weight i.  ``ValueError`` where ``gemm_wq_fused_supported`` is false, before the library is
+    touched."""
+    weights = [tuple(w) for w in weights]
+    why = _wq_fused_refusal(X, [(Wq, s_w, zp_w, None) for Wq, s_w, zp_w, _ in weights])
+    if why is not None:
+        raise ValueError(f"gemm_wq_skinny_multi: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    Ns = [w[0].shape[0] for w in weights]
+    # one allocation, sliced: the kernel takes any pitch, and the allocator is asked once per launch
+    flat = torch.empty(M * sum(Ns), dtype=X.dtype, device=X.device)
+    Ys, at = [], 0
+    for N in Ns:
+        Ys.append(flat[at:at + M * N].view(M, N))
+        at += M * N
+    table, _ = _wq_weight_table(X, [(Wq, s_w, zp_w, bias, Y) for (Wq, s_w, zp_w, bias), Y in zip(weights, Ys)])
+    check("qt_gemm_wq_skinny_multi", lib.qt_gemm_wq_skinny_multi(
+        X.data_ptr(), code, M, K, X.stride(0), table, len(weights), _stream()))
+    return Ys
+
+
+def gemm_wq_skinny_act_mul(X: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
+    """H [M, I] = act(X . wg^T) * (X . wu^T) in X's dtype in one launch (``qt_gemm_wq_skinny_act_mul``): ``gate`` and
+    ``up`` are (Wq, s_w, zp_w) of equal N = I, format, G and zero-point presence.  Bit-identical to ``F.silu(
+    gemm_wq_skinny(X, *gate)) * gemm_wq_skinny(X, *up)`` on the device.  ``ValueError`` where
+    ``gemm_wq_fused_supported`` is false, before the library is touched."""
+    gate, up = tuple(gate), tuple(up)
+    why = _wq_fused_refusal(X, [(*gate, None), (*up, None)])
+    if why is None and gate[0].shape[0] != up[0].shape[0]:
+        why = f"gate has {gate[0].shape[0]} rows, up {up[0].shape[0]}"
+    if why is None and act not in ACTS:
+        why = f"act must be one of {sorted(ACTS)}, got {act!r}"
+    if why is not None:
+        raise ValueError(f"gemm_wq_skinny_act_mul: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    table, (I, _) = _wq_weight_table(X, [(*gate, None, None), (*up, None, None)])
+    H = torch.empty((M, I), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_skinny_act_mul", lib.qt_gemm_wq_skinny_act_mul(
+        X.data_ptr(), code, M, K, X.stride(0), ctypes.byref(table[0]), ctypes.byref(table[1]), ACTS[act], H.data_ptr(),
+        H.stride(0), _stream()))
+    return H
+
+
+def rmsnorm(X: torch.Tensor, weight: torch.Tensor, eps: float, return_rstd: bool = False):
+    """``Y = weight * RMSNorm(X)`` alone (``qt_rmsnorm``): the Y, and with ``return_rstd`` the rstd, of
+    ``rmsnorm_quantize_i8`` to the bit, with nothing quantised.  X [M, K] bf16 / fp16 (unit column stride, any row
+    pitch), weight [K] of the same dtype on the same device."""
+    code = _x2d(X, "X")
+    if not weight.is_cuda or weight.device != X.device:
+        raise ValueError(f"weight must be a device tensor on X's device {X.device}, got {weight.device}")
+    if weight.dtype != X.dtype:
+        raise TypeError(f"weight must be of X's dtype {X.dtype}, got {weight.dtype}")
+    M, K = X.shape
+    if M == 0 or K == 0:
+        raise ValueError(f"X must be non-empty, got shape {tuple(X.shape)}")
+    if weight.dim() != 1 or weight.numel() != K or not weight.is_contiguous():
+        raise ValueError(f"weight must be contiguous [{K}], got shape {tuple(weight.shape)}")
+    eps = float(eps)
+    if not (eps >= 0.0 and eps != float("inf")):
+        raise ValueError(f"eps must be finite and not negative, got {eps!r}")
+    lib = load()
+    Y = torch.empty((M, K), dtype=X.dtype, device=X.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=X.device) if return_rstd else None
+    # a one-row view may carry any stride(0): the pitch of a single row is never used, K keeps the host check quiet
+    ldx = X.stride(0) if M > 1 else max(X.stride(0), K)
+    check("qt_rmsnorm", lib.qt_rmsnorm(X.data_ptr(), ldx, weight.data_ptr(), code, M, K, eps, Y.data_ptr(), K,
+                                       _ptr(rstd), _stream()))
+    return (Y, rstd) if return_rstd else Y
+
+
 def gemm_wq_grouped(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
                     row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
                     zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -48,6 +48,8 @@ the checkpoint twice, ``a8_fused_off`` with the default loader and ``a8_fused`` 
 quantiser its consumers share in one ``qt_rmsnorm_quantize_i8`` pass).  The kernel's sum over K runs in its own order,
 so nothing is asserted of the logits: how many of the prompt's differ, and by how much at most, is reported
 (``logits_differ``, ``logits_max_abs_diff``) beside ``quantizing_norms``.
+``--pair a16_fused`` / ``a16_norm`` / ``a16_both`` (W4A16 / W8A16, llama) load the checkpoint with ``a16="packed"`` as
+``a16_off`` and with ``a16_fused_act``, ``a16_fused_norm`` or each alone and both, decoded in turn, twice.
 """
 from __future__ import annotations
 
@@ -75,7 +77,7 @@ def _rtn(W: torch.Tensor, scheme: str = "W4A16"):
     int8 levels [N, K] and one scale per row."""
     W = W.float()
     N, K = W.shape
-    if scheme == "W8A8":
+    if scheme in ("W8A8", "W8A16"):
         s = (W.abs().amax(-1, keepdim=True) / 127.5).clamp(min=1e-8).to(torch.bfloat16)
         return torch.round(W / s.float()).clamp(-128, 127).to(torch.int8).cpu(), s.cpu()
     s = (W.reshape(N, K // 128, 128).abs().amax(-1) / 7.5).clamp(min=1e-8).to(torch.bfloat16)
@@ -85,7 +87,7 @@ def _rtn(W: torch.Tensor, scheme: str = "W4A16"):
 
 def _leaves(state: dict, pre: str, W: torch.Tensor, scheme: str) -> None:
     q, s = _rtn(W, scheme)
-    state[f"{pre}.weight" if scheme == "W8A8" else f"{pre}.weight_packed"], state[f"{pre}.weight_scale"] = q, s
+    state[f"{pre}.weight" if scheme in ("W8A8", "W8A16") else f"{pre}.weight_packed"], state[f"{pre}.weight_scale"] = q, s
     state[f"{pre}.weight_shape"] = torch.tensor(list(W.shape))
 
 
@@ -287,6 +289,50 @@ def a8_norm_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict)
     result["off_spread"] = round(abs(off[0] / off[1] - 1.0), 4)
 
 
+A16_FUSED_PAIRS = {"a16_fused": {"a16_fused": {"a16_fused_act": True}},
+                   "a16_norm": {"a16_norm": {"a16_fused_norm": True}},
+                   "a16_both": {"a16_fused": {"a16_fused_act": True}, "a16_norm": {"a16_fused_norm": True},
+                                "a16_both": {"a16_fused_act": True, "a16_fused_norm": True}}}
+
+
+def a16_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, pair: str, result: dict) -> None:
+    """The A16 checkpoint loaded with ``a16="packed"`` as ``a16_off`` and with the flags of ``pair`` (``a16_fused``:
+    ``a16_fused_act``; ``a16_norm``: ``a16_fused_norm``; ``a16_both``: each alone and the two together), decoded in turn,
+    reported as ``--pair fused`` / ``--pair norm`` report the A8 flags."""
+    from quantool_amd.engine.qlinear import WeightOnlyMLP, WeightOnlyRMSNorm
+
+    models = {"a16_off": load_quantized(path, device=dev, a16="packed")}
+    for mode, flags in A16_FUSED_PAIRS[pair].items():
+        models[mode] = load_quantized(path, device=dev, a16="packed", **flags)
+    last = list(models.values())[-1]
+    result["weight_only_mlps"] = sum(isinstance(m, WeightOnlyMLP) for m in last.modules())
+    result["weight_only_norms"] = sum(isinstance(m, WeightOnlyRMSNorm) for m in last.modules())
+    assert result["weight_only_mlps"] + result["weight_only_norms"] > 0, "nothing in this checkpoint runs fused"
+    if "a16_fused" in models:
+        with torch.no_grad():
+            a, b = (models[m](input_ids=prompt[:, :1]).logits for m in ("a16_off", "a16_fused"))
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16)), "a decode step's logits differ with a16_fused_act"
+        result["logits_bits_equal"] = True
+        del a, b
+    tokens = {}
+    for rep in range(2):                                       # every mode twice: the second pass is the spread
+        for mode, model in models.items():
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    off = result["modes"]["a16_off"]["ms_per_step"]
+    result["off_spread"] = round(abs(off[0] / off[1] - 1.0), 4)
+    for mode in (m for m in models if m != "a16_off"):
+        same = [x == y for x, y in zip(tokens["a16_off"], tokens[mode])]
+        r = result["modes"][mode]
+        r["tokens_agree"] = sum(same)                          # a16_fused_norm: a random-init model's logits are near ties
+        r["first_difference"] = same.index(False) if not all(same) else None
+        r["speedup"] = [round(o / k, 3) for o, k in zip(off, r["ms_per_step"])]     # pass by pass
+    if len(models) == 2:
+        result.update({k: r[k] for k in ("tokens_agree", "first_difference")}, speedup=round(min(off) / min(r["ms_per_step"]), 3))
+
+
 def a16_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, wide_min_tokens: int, result: dict) -> None:
     """One packed A16 sparse-MoE model (``a16_experts="packed"``) decoded as ``a16_wide_off`` (``WeightOnlyExperts``'
     ``wide_min_tokens`` = 0: the grouped GEMV) and ``a16_wide`` (``wide_min_tokens`` = the class default, or
@@ -345,15 +391,17 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--model", default="llama", choices=["llama", "mixtral"])
-    ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A8", "W4A8"],
+    ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
-    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused", "norm"],
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused", "norm", *A16_FUSED_PAIRS],
                     help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
                          "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; fused = a8_fused_off vs a8_fused "
                          "(load_quantized(..., a8_fused_act=True)); norm = a8_norm_off vs a8_norm (a8_fused_norm=True, "
                          "a8_fused_act=True in both); W4A16 with --model "
-                         "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide")
+                         "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide; W4A16 / "
+                         "W8A16: a16_fused = a16_off (a16='packed') vs a16_fused (a16_fused_act=True); a16_norm = a16_off "
+                         "vs a16_norm (a16_fused_norm=True); a16_both = a16_off vs each flag alone and the two together")
     ap.add_argument("--wide-min-tokens", type=int, default=-1,
                     help="with --scheme W4A16 --pair wide: WeightOnlyExperts.wide_min_tokens of a16_wide (default: "
                          "the class's)")
@@ -375,7 +423,13 @@ def main():
     prompt = torch.randint(0, vocab, (args.batch, args.prompt), generator=torch.Generator().manual_seed(0)).to(dev)
     result = {"tool": "decode_bench", "model": args.model, "checkpoint": str(path), "prompt": args.prompt,
               "new": args.new, "batch": args.batch, "scheme": args.scheme, "layers": args.layers, "modes": {}}
-    if args.scheme != "W4A16":
+    if args.pair in A16_FUSED_PAIRS:
+        if args.scheme not in ("W4A16", "W8A16") or mixtral:
+            raise SystemExit(f"--pair {args.pair} compares the packed A16 runtime's dense modules: W4A16 / W8A16, llama")
+        a16_fused_modes(path, dev, prompt, args.new, args.pair, result)
+        print(json.dumps(result))
+        return
+    if args.scheme not in ("W4A16", "W8A16"):
         {"mid": a8_mid_modes, "wide": a8_wide_modes, "skinny": a8_modes, "fused": a8_fused_modes,
          "norm": a8_norm_modes}[args.pair](path, dev, prompt, args.new, result)
         print(json.dumps(result))

@@ -3,7 +3,7 @@
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-panel-rows N] [--a16-experts-wide-tokens N]
-                                  [--a8-fused-act]
+                                  [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
                                   [--a8-fused-norm] [--head logits|fused] [--against REF]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
@@ -12,6 +12,8 @@ on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed``
 ``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``; ``--a16-panel-rows N`` with it: inputs
 above those, up to N rows, on ``qt_gemm_wq_panel``;
 ``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``;
+``--a16-fused-act`` / ``--a16-fused-norm`` with ``--a16 packed``: ``load_quantized``'s flags of those names -- the first
+changes inputs of 1 to 16 rows alone and no bit, the second moves the perplexity as ``--a8-fused-norm`` does;
 ``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
 ``qt_act_mul_quantize_i8`` pass, the same perplexity to the bit; ``--a8-fused-norm`` on an A8 checkpoint: the RMSNorms in
 front of q/k/v and gate/up and the quantiser their consumers share in one ``qt_rmsnorm_quantize_i8`` pass each, whose sum
@@ -34,7 +36,8 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from quantool_amd.engine.qlinear import (A16_MODES, QuantizedLinear, QuantizedMLP, QuantizingRMSNorm,  # noqa: E402
-                                         WeightOnlyExperts, WeightOnlyLinear, load_quantized)
+                                         WeightOnlyExperts, WeightOnlyLinear, WeightOnlyMLP, WeightOnlyRMSNorm,
+                                         load_quantized)
 from quantool_amd.evaluate import divergence, load_side, perplexity  # noqa: E402
 
 
@@ -55,6 +58,10 @@ def main():
     ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
+    ap.add_argument("--a16-fused-act", action="store_true",
+                    help="with --a16 packed: WeightOnlyMLPs and shared q/k/v launches (inputs of 1 to 16 rows)")
+    ap.add_argument("--a16-fused-norm", action="store_true",
+                    help="with --a16 packed: the decoder layers' RMSNorms as one qt_rmsnorm launch each")
     ap.add_argument("--a8-fused-act", action="store_true",
                     help="A8 checkpoints: run every MLP's and expert bank's glue as one qt_act_mul_quantize_i8 pass")
     ap.add_argument("--a8-fused-norm", action="store_true",
@@ -72,7 +79,8 @@ def main():
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
                            a16_panel_rows=args.a16_panel_rows,
                            a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act,
-                           a8_fused_norm=args.a8_fused_norm)
+                           a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
+                           a16_fused_norm=args.a16_fused_norm)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -89,6 +97,8 @@ def main():
               "quantizing_norms": sum(isinstance(m, QuantizingRMSNorm) for m in model.modules()),
               "weight_only_linears": sum(isinstance(m, WeightOnlyLinear) for m in model.modules()),
               "weight_only_expert_banks": sum(isinstance(m, WeightOnlyExperts) for m in model.modules()),
+              "weight_only_mlps": sum(isinstance(m, WeightOnlyMLP) for m in model.modules()),
+              "weight_only_norms": sum(isinstance(m, WeightOnlyRMSNorm) for m in model.modules()),
               "head": args.head, "load_s": round(t1 - t0, 3), "eval_s": round(t2 - t1, 3)})
     if args.against:
         t3 = time.perf_counter()

@@ -153,6 +153,49 @@ def panel_main(args):
                       "warmup": args.warmup, "rows": rows}))
 
 
+def fused_main(args):
+    """--fused: the two fused decode forms against the launches they replace, --stream's method.  ``act_mul``:
+    ``ops.gemm_wq_skinny_act_mul`` on gate and up [14336, 4096] against two ``ops.gemm_wq_skinny`` calls, ``F.silu`` and
+    the multiply; ``qkv``: ``ops.gemm_wq_skinny_multi`` on q [4096, 4096], k and v [1024, 4096] against three
+    ``ops.gemm_wq_skinny`` calls.  Cold weights, device time between events that enclose all launches of a form."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    K = 4096
+    cells = {"act_mul": (14336, 14336), "qkv": (4096, 1024, 1024)}
+    rows = []
+    for scheme in args.schemes.split(","):
+        for name, Ns in cells.items():
+            ws = [_cold_weights(N, K, scheme, dev, g) for N in Ns]
+            qbytes = sum(w[3] for w in ws)
+            n_cp = min(len(w[4]) for w in ws)
+            row = {"cell": name, "N": list(Ns), "K": K, "scheme": scheme, "packed_mb": round(qbytes / 1e6, 2),
+                   "cold_copies": n_cp, "fused": {}}
+
+            def unfused(i, X):
+                ys = [ops.gemm_wq_skinny(X, *w[4][i % n_cp][:2], zp_w=w[4][i % n_cp][2]) for w in ws]
+                return F.silu(ys[0]) * ys[1] if name == "act_mul" else ys
+
+            def fused(i, X):
+                cp = [w[4][i % n_cp] for w in ws]
+                if name == "act_mul":
+                    return ops.gemm_wq_skinny_act_mul(X, *cp)
+                return ops.gemm_wq_skinny_multi(X, [(*c, None) for c in cp])
+
+            for M in [int(m) for m in args.fused_ms.split(",") if m]:
+                X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+                a, b = unfused(0, X), fused(0, X)
+                same = all(torch.equal(x.view(torch.int16), y.view(torch.int16))
+                           for x, y in zip(*(([a], [b]) if name == "act_mul" else (a, b))))
+                ts = _alternate([lambda i: unfused(i, X), lambda i: fused(i, X)], args.reps, args.warmup)
+                row["fused"][M] = {"unfused_us": ts[0], "fused_us": ts[1], "speedup": round(ts[0] / ts[1], 2),
+                                   "fused_tbs": round(qbytes / ts[1] / 1e6, 3), "bits_equal": bool(same)}
+            rows.append(row)
+            del ws
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "wq_bench --fused", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                      "warmup": args.warmup, "rows": rows}))
+
+
 def stream_main(args):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -202,6 +245,9 @@ def main():
     ap.add_argument("--panel", action="store_true", help="the 33 - 512 row range: qt_gemm_wq_panel against "
                     "dequantise + F.linear and, up to 128 rows, qt_gemm_wq_stream")
     ap.add_argument("--panel-ms", default="48,64,96,128,192,256,384,512")
+    ap.add_argument("--fused", action="store_true", help="the fused decode forms (qt_gemm_wq_skinny_act_mul, "
+                    "qt_gemm_wq_skinny_multi) against the skinny launches and torch glue they replace")
+    ap.add_argument("--fused-ms", default="1,8,16")
     ap.add_argument("--skinny-ms", default="1,2,4,8,16")
     ap.add_argument("--large-ms", default="4096,8192")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -212,6 +258,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wq_bench needs a GPU")
+    if args.fused:
+        return fused_main(args)
     if args.stream:
         return stream_main(args)
     if args.panel:
