@@ -458,6 +458,24 @@ int qt_chol_g3_plan_check(int K, int merged, int min_chunks, long long* counts_o
  *   s_x / zp_x[M] is read, no element outside Y[m < M, n < N] is written.  Deterministic, no atomics, no workspace.
  *   
  *
+ * qt_w4_short_gemm_i8: the short-prompt form of qt_gemm_i8 for W4A8, between qt_gemm_i8_mid's rows and
+ *   qt_gemm_i8_ring_w4's.  qt_gemm_i8's arguments with the same meanings.  Taken: what qt_gemm_i8_ring_w4 takes --
+ *   w_format == QT_W_INT4_PACKED with G == K / 128, K a multiple of QT_I8_W4_SHORT_K_UNIT, K <= 32768, Xq and Wq 16-byte
+ *   aligned, with and without zp_x / wsum and bias, bf16 and fp16 output, any M >= 1, any N >= 1, any ldy >= N.
+ *   Everything else -- int8 weights, channel-wise scales (G == 1 with K > 128), a ragged K, K > 32768, a misaligned
+ *   operand, a 32-bit output, zp_x without wsum -- is QT_ERR_INVALID before any launch, and qt_last_error names the
+ *   reason.  For every legal input Y is bit-identical to qt_gemm_i8's on the same arguments: a K-tile is exactly one
+ *   weight group, so the int32 result of its four MFMA k-steps is the complete acc_g, and the chain t_g -> tot = tot +
+ *   s_w t_g -> y above runs literally, once per output element and group, g ascending, in the lane that holds the
+ *   element (two elements per packed fp32 multiply or add where the compiler forms one, each rounded on its own, never
+ *   fused).  wsum must be what its name says (|wsum[n, g]| <= 128 * 8).  A workgroup of 4 waves owns a 128 x 128 tile,
+ *   two workgroups share a compute unit; a K-tile (A 16 KiB, packed B 8 KiB, its s_w and wsum 1 KiB) reaches one of
+ *   QT_I8_W4_SHORT_SLOTS LDS slots by LDS-DMA, QT_I8_W4_SHORT_LEAD K-tiles ahead of the MFMAs, under counted waits;
+ *   the fold of one accumulator set runs beside the MFMAs that fill the other (csrc/qlinear_w4_short.hip).  A tile row
+ *   past M or N re-reads row M - 1 or N - 1 and is never stored: no byte outside Xq[M, K], Wq[N, K/8], s_w /
+ *   wsum[N, G], s_x / zp_x[M] is read, no element outside Y[m < M, n < N] is written.  Deterministic, no atomics, no
+ *   workspace.  
+ *
  * qt_gemm_i8_mid: the form of qt_gemm_i8 for a few tiles of rows, 1 <= M <= QT_I8_MID_MAX_M.  qt_gemm_i8's arguments
  *   with the same meanings.  Taken: both weight formats, G = 1 and G = K/128, with and without zp_x / wsum and bias, bf16
  *   and fp16 output, any N >= 1, any ldy >= N, K a multiple of QT_I8_MID_K_UNIT, K <= 32768, Xq and Wq 16-byte aligned.
@@ -568,6 +586,9 @@ enum qt_act { QT_ACT_SILU = 0 };
 #define QT_I8_RING_W4_K_UNIT 128
 #define QT_I8_RING_W4_SLOTS 8
 #define QT_I8_RING_W4_LEAD 6
+#define QT_I8_W4_SHORT_K_UNIT 128
+#define QT_I8_W4_SHORT_SLOTS 3
+#define QT_I8_W4_SHORT_LEAD 2
 #define QT_SPLITK_I8_K_UNIT 128
 #define QT_SPLITK_I8_MAX_SPLITS 32
 #define QT_SPLITK_I8_MIN_K_TILES 4
@@ -595,6 +616,9 @@ int qt_gemm_i8_ring(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_fo
 int qt_gemm_i8_ring_w4(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                        const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                        int out_dtype, int64_t ldy, qt_stream_t stream);
+int qt_w4_short_gemm_i8(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
+                        const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
+                        int out_dtype, int64_t ldy, qt_stream_t stream);
 int qt_gemm_i8_mid(const int8_t* Xq, int64_t M, int K, const void* Wq, int w_format, int N, const float* s_x,
                    const int32_t* zp_x, const float* s_w, int G, const int32_t* wsum, const void* bias, void* Y,
                    int out_dtype, int64_t ldy, qt_stream_t stream);

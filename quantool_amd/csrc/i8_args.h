@@ -27,6 +27,20 @@ static inline int qt_i8_check_dense(const char* name, const void* Xq, int64_t M,
                               w_format, zp_x, G, wsum, out_dtype, aligned16);
 }
 
+// qt_gemm_i8's arguments narrowed to a packed int4 weight with one scale per group of 128 columns, K a whole number of
+// groups, Xq and Wq 16-byte aligned (qt_w4_short_gemm_i8); `i8_form` is the entry point an int8 weight runs on
+static inline int qt_i8_check_packed_g128(const char* name, const char* i8_form, const void* Xq, int64_t M, int K,
+                                          const void* Wq, int w_format, int N, const void* s_x, const void* zp_x,
+                                          const void* s_w, int G, const void* wsum, const void* Y, int out_dtype,
+                                          int64_t ldy) {
+    QT_CHECK_ARG(w_format == QT_W_INT4_PACKED, "%s: w_format %d unsupported: packed int4 weights only (int8 weights run "
+                 "on %s)", name, w_format, i8_form);
+    QT_CHECK_ARG(K % 128 == 0, "%s: K %d is not a multiple of the k-unit 128", name, K);
+    QT_CHECK_ARG(G == K / 128, "%s: G %d unsupported: one scale per group of 128 columns only, G = K / 128 = %d "
+                 "(channel-wise scales run on qt_gemm_i8)", name, G, K / 128);
+    return qt_i8_check_dense(name, Xq, M, K, Wq, w_format, N, s_x, zp_x, s_w, G, wsum, Y, out_dtype, ldy, true);
+}
+
 // qt_gemm_i8_grouped's arguments
 static inline int qt_i8_check_grouped(const char* name, const void* Xq, int K, int64_t R, const void* offsets, int E,
                                       const void* Wq, int w_format, int N, const void* s_x, const void* zp_x,

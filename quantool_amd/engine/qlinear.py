@@ -331,7 +331,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
                    a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
-                   a16_fused_norm: bool = False) -> nn.Module:
+                   a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -374,6 +374,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     wherever ``WeightOnlyRMSNorm.refusal`` is None: one launch, ``qt_rmsnorm``.  It changes bits exactly as
     ``a8_fused_norm`` does (the kernel's order of summation over K); state-dict keys do not move, and it
     is recorded under ``"a16_fused_norm"``.  A8 checkpoints ignore it.
+    ``a8_w4_short_min_m`` (0, the default, or 129 and more) sets ``w4_short_min_m`` on every ``QuantizedLinear`` built,
+    so calls of that many rows up to ``ring_w4_min_m`` run a packed int4 g128 weight on ``qt_w4_short_gemm_i8``, equal to
+    the tiled kernel to the bit: the value changes speed alone.  When not 0 it is recorded under
+    ``"a8_w4_short_min_m"``.  A16 checkpoints ignore it.
 
     Routed-expert banks written per expert (``sequential.expert_bank_checkpoint_names``) are mapped back to the fused
     bank of the model built from ``config.json`` (undoing the Mixtral ``block_sparse_moe`` rename of every tensor and of
@@ -415,6 +419,9 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         raise ValueError(f"a8_fused_act={a8_fused_act!r}: expected True or False")
     if type(a8_fused_norm) is not bool:
         raise ValueError(f"a8_fused_norm={a8_fused_norm!r}: expected True or False")
+    if type(a8_w4_short_min_m) is not int or not (a8_w4_short_min_m == 0 or a8_w4_short_min_m >= 129):
+        raise ValueError(f"a8_w4_short_min_m={a8_w4_short_min_m!r}: expected 0 or 129 and more (up to 128 rows run on "
+                         "the skinny and mid kernels)")
     for flag, value in (("a16_fused_act", a16_fused_act), ("a16_fused_norm", a16_fused_norm)):
         if type(value) is not bool:
             raise ValueError(f"{flag}={value!r}: expected True or False")
@@ -479,6 +486,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             new = (quantized_linear_from_tensors(name, t, act_symmetric, bias=bias) if a8
                    else weight_only_linear_from_tensors(name, t, bias=bias))
             _check_shape(f"{path}: {name}", (new.out_features, new.in_features), lin.weight.shape)
+            if a8 and a8_w4_short_min_m:
+                new.w4_short_min_m = a8_w4_short_min_m
             if not a8 and a16_stream_rows:
                 new.stream_max_m = a16_stream_rows
             if not a8 and a16_panel_rows:
@@ -504,6 +513,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if a8:
         model._qt_checkpoint["a8_fused_act"] = a8_fused_act
         model._qt_checkpoint["a8_fused_norm"] = a8_fused_norm
+        if a8_w4_short_min_m:
+            model._qt_checkpoint["a8_w4_short_min_m"] = a8_w4_short_min_m
     if not a8 and a16 == "packed":
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows

@@ -42,7 +42,11 @@ class QuantizedLinear(nn.Module):
     Below the ring, ``splitk_min_m`` <= M < ``ring_min_m`` (or any M >= ``splitk_min_m`` when ``ring_min_m`` is 0) runs an
     int8 weight with one scale group and ``in_features`` >= ``splitk_min_k`` on the ring's tile over S k-ranges plus an
     int32 reduce pass, ``qt_splitk_gemm_i8``, where ``ops.splitk_gemm_i8_supported`` holds: bit-identical again, and
-    ``splitk_min_m`` = 0 never uses it."""
+    ``splitk_min_m`` = 0 never uses it.
+    Below the w4 ring, ``w4_short_min_m`` <= M < ``ring_w4_min_m`` (or any M >= ``w4_short_min_m`` when ``ring_w4_min_m``
+    is 0) runs a packed int4 weight with one scale per 128 columns and ``in_features`` >= ``w4_short_min_k`` on the
+    128 x 128-tile LDS ring ``qt_w4_short_gemm_i8``, where ``ops.gemm_i8_w4_short_supported`` holds: bit-identical again,
+    and ``w4_short_min_m`` = 0, the default, never uses it."""
 
     # Decode GEMV up to this many rows: the measured crossover (DESIGN.md 4.11).
     skinny_max_m = 16
@@ -69,6 +73,11 @@ class QuantizedLinear(nn.Module):
     # there is no bound on M from above or on N that would keep them out, so they stay on the tiled kernel.
     splitk_min_m = 129
     splitk_min_k = 14336
+    # The 128 x 128-tile ring for packed int4 weights from this many rows up to the w4 ring (0: never) and from this many
+    # input features.  Off unless asked for (load_quantized(a8_w4_short_min_m=...)); DESIGN.md 4.28 has the measured
+    # table and the values it recommends.
+    w4_short_min_m = 0
+    w4_short_min_k = 128
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  act_symmetric: bool, col_perm: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -89,7 +98,7 @@ class QuantizedLinear(nn.Module):
                 f"weights={'int4 g128' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"act={'sym' if self.act_symmetric else 'asym'} int8 per-token, "
                 f"col_perm={self.col_perm is not None}, bias={self.bias is not None}, "
-                f"ring_w4_min_m={self.ring_w4_min_m}")
+                f"ring_w4_min_m={self.ring_w4_min_m}, w4_short_min_m={self.w4_short_min_m}")
 
     # A ``SharedRows`` a ``QuantizingRMSNorm`` in front of this Linear fills (None, the default: nobody does).
     rows_from = None
@@ -128,6 +137,12 @@ class QuantizedLinear(nn.Module):
               and ops.gemm_i8_mid_supported(Xq, self.weight, self.weight_scale)):
             # the attributes and the two sizes decide first: ops' mid names are read only past them
             gemm = ops.gemm_i8_mid
+        elif (self.w4_short_min_m > 0 and M >= self.w4_short_min_m
+              and (self.ring_w4_min_m == 0 or M < self.ring_w4_min_m) and self.int4
+              and self.weight_scale.shape[1] * 128 == self.in_features and self.in_features >= self.w4_short_min_k
+              and ops.gemm_i8_w4_short_supported(Xq, self.weight, self.weight_scale)):
+            # the attribute and M decide first: ops' w4_short names are read only past them
+            gemm = ops.gemm_i8_w4_short
         elif (self.splitk_min_m > 0 and M >= self.splitk_min_m and (self.ring_min_m == 0 or M < self.ring_min_m)
               and not self.int4 and self.weight_scale.shape[1] == 1 and self.in_features >= self.splitk_min_k
               and ops.splitk_gemm_i8_supported(Xq, self.weight, self.weight_scale)):

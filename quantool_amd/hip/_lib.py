@@ -130,6 +130,8 @@ SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_gemm_i8_mid": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "qt_w4_short_gemm_i8": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "qt_splitk_gemm_i8_plan": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "qt_splitk_gemm_i8_range": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     # qt_gemm_i8's arguments, then splits, workspace, workspace_size in front of the stream

@@ -893,6 +893,10 @@ I8_MOE_WIDE_FORM = I8Form("qt_moe_gemm_i8_wide", experts=True, x_rows=True, max_
 # The short-prompt form: qt_gemm_i8_ring's tile over a k-range plus a reduce pass; it takes what the dense ring takes.
 # Beside the table for the same reason (its entry point carries a split count and a workspace behind ldy).
 I8_SPLITK_FORM = I8Form("qt_splitk_gemm_i8", **_RING)
+# The W4A8 form between the mid kernel's rows and the w4 ring's: a 128 x 128 tile, two workgroups per CU, three K-tiles
+# of LDS.  It takes what the w4 ring takes.  Beside the table for the same reason (an entry point of its own family).
+I8_W4_SHORT_FORM = I8Form("qt_w4_short_gemm_i8", dtypes=(torch.int32,), k_unit=128, groups="per_unit", aligned16=True,
+                          slots=3, lead=2)
 
 I8_SKINNY_MAX_M = I8_FORMS["qt_gemm_i8_skinny"].max_m   # rows of Xq qt_gemm_i8_skinny takes
 # k-bytes qt_gemm_i8_ring fetches per row at a time (QT_I8_RING_K_UNIT): K must be a multiple
@@ -910,6 +914,9 @@ MOE_I8_WIDE_K_UNIT = I8_MOE_WIDE_FORM.k_unit            # columns per k-block of
 MOE_I8_WIDE_TILE_ROWS = I8_MOE_WIDE_FORM.tile_rows      # rows of one expert a workgroup of qt_moe_gemm_i8_wide holds at most
 MOE_I8_WIDE_MAX_E = I8_MOE_WIDE_FORM.max_e              # experts qt_moe_gemm_i8_wide walks per workgroup
 MOE_I8_WIDE_MAX_SLOTS = 65535                           # row-tile slots: the grid's second dimension
+I8_W4_SHORT_K_UNIT = I8_W4_SHORT_FORM.k_unit            # k per K-tile of qt_w4_short_gemm_i8 = the weight group: K a multiple
+I8_W4_SHORT_SLOTS = I8_W4_SHORT_FORM.slots              # K-tiles (A 16 KiB, packed B 8 KiB, scales 1 KiB) resident in LDS
+I8_W4_SHORT_LEAD = I8_W4_SHORT_FORM.lead                # K-tiles the LDS-DMA runs ahead of the MFMAs
 SPLITK_I8_K_UNIT = I8_SPLITK_FORM.k_unit                # k-bytes per K-tile of qt_splitk_gemm_i8 (QT_SPLITK_I8_K_UNIT)
 SPLITK_I8_MAX_SPLITS = 32                               # slabs its reduce pass adds at most (QT_SPLITK_I8_MAX_SPLITS)
 SPLITK_I8_MIN_K_TILES = 4                               # K-tiles of the shortest split the rule deals (QT_SPLITK_I8_MIN_K_TILES)
@@ -1033,6 +1040,23 @@ def gemm_i8_ring_w4(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: 
     for W4A8.  Same arguments; Y equals ``gemm_i8``'s to the bit.  ``ValueError`` where ``gemm_i8_ring_w4_supported``
     is false."""
     return _gemm_i8_dense(I8_FORMS["qt_gemm_i8_ring_w4"], Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
+
+
+def gemm_i8_w4_short_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:
+    """Whether ``gemm_i8_w4_short`` takes these operands: what ``gemm_i8_ring_w4`` takes -- a packed int4 weight with one
+    scale per 128 columns, K a multiple of ``I8_W4_SHORT_K_UNIT`` and at most 32768, both operands 16-byte aligned.
+    Host-only."""
+    return _i8_refusal(I8_W4_SHORT_FORM, Xq, Wq, s_w) is None
+
+
+def gemm_i8_w4_short(Xq: torch.Tensor, s_x: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *,
+                     K: Optional[int] = None, zp_x: Optional[torch.Tensor] = None,
+                     wsum: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                     out_dtype=torch.bfloat16) -> torch.Tensor:
+    """``gemm_i8`` on the 128 x 128-tile LDS-ring kernel for packed int4 weights (``qt_w4_short_gemm_i8``): the form for
+    W4A8 between ``gemm_i8_mid``'s rows and ``gemm_i8_ring_w4``'s.  Same arguments; Y equals ``gemm_i8``'s to the bit.
+    ``ValueError`` where ``gemm_i8_w4_short_supported`` is false."""
+    return _gemm_i8_dense(I8_W4_SHORT_FORM, Xq, s_x, Wq, s_w, K, zp_x, wsum, bias, out_dtype)
 
 
 def gemm_i8_mid_supported(Xq: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor) -> bool:

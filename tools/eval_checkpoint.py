@@ -4,7 +4,7 @@
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-panel-rows N] [--a16-experts-wide-tokens N]
                                   [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
-                                  [--a8-fused-norm] [--head logits|fused] [--against REF]
+                                  [--a8-fused-norm] [--a8-w4-short-min-m M] [--head logits|fused] [--against REF]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--a8-fused-norm", action="store_true",
                     help="A8 checkpoints: run the RMSNorm in front of q/k/v and gate/up and their shared quantiser as one "
                          "qt_rmsnorm_quantize_i8 pass")
+    ap.add_argument("--a8-w4-short-min-m", type=int, default=0, metavar="M",
+                    help="A8 checkpoints: run packed int4 g128 Linears on qt_w4_short_gemm_i8 from M rows (0: never) up to "
+                         "the w4 ring's rows; the same perplexity to the bit")
     ap.add_argument("--head", default="logits", choices=["logits", "fused"],
                     help="fused: the LM head and its cross-entropy run as one qt_lm_head_nll pass, no [B, T, V] logits")
     ap.add_argument("--against", default=None, metavar="REF",
@@ -80,7 +83,7 @@ def main():
                            a16_panel_rows=args.a16_panel_rows,
                            a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act,
                            a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
-                           a16_fused_norm=args.a16_fused_norm)
+                           a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()

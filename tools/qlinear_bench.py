@@ -5,6 +5,7 @@ tiled GEMM at decode sizes.
   python tools/qlinear_bench.py --ms 1,8,16            # decode: qt_gemm_i8 vs qt_gemm_i8_skinny
   python tools/qlinear_bench.py --mid [--reps 30]      # 17 .. 128 rows: qt_gemm_i8 vs qt_gemm_i8_mid
   python tools/qlinear_bench.py --ring-w4 [--ms 2048,4096,8192]   # W4A8 prefill: qt_gemm_i8 vs qt_gemm_i8_ring_w4
+  python tools/qlinear_bench.py --w4-short [--ms 129,256,...]     # W4A8, 129 .. 4096 rows: qt_gemm_i8 vs qt_w4_short_gemm_i8
   python tools/qlinear_bench.py --splitk [--splits 4]  # 129 .. 2047 rows: qt_gemm_i8 vs qt_gemm_i8_ring vs qt_splitk_gemm_i8
   python tools/qlinear_bench.py --mlp [--ms 1,16,32,128,2048,8192]     # three Linears + glue vs QuantizedMLP
   python tools/qlinear_bench.py --norm [--ms 1,16,32,128,2048,8192]    # RMSNorm + 3 (2) quantisers vs one fused launch
@@ -379,7 +380,52 @@ def ring_w4_rows(shape, N, K, ms, reps, warmup, dev, g):
 
 
 SPLITK_MS = "129,192,256,320,384,512,640,768,1024,1536,2047"
+def w4_short_rows(shape, N, K, ms, reps, warmup, dev, g):
+    """qt_gemm_i8 vs qt_w4_short_gemm_i8 (and, from 2048 rows, qt_gemm_i8_ring_w4) on W4A8 operands (packed int4 g128,
+    asymmetric activations): the kernels alternate in one loop, each on its own cold copy of the weight."""
+    rows = []
+    G = K // 128
+    q = torch.randint(-8, 8, (N, K), device=dev, generator=g, dtype=torch.int8)
+    W0, s0, ws0 = pack_int4(q), torch.rand(N, G, device=dev, generator=g) * 1e-2, group_sums(q, G)
+    del q
+    nbytes = W0.numel() * 4 + s0.numel() * 4 + ws0.numel() * 4
+    n_cp = max(4, -(-int(COLD_BYTES * 1.1) // nbytes))
+    cps = [(W0.clone(), s0.clone(), ws0.clone()) for _ in range(n_cp)]
+    for M in ms:
+        X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        Xq, s_x, zp_x = ops.quantize_tokens_i8(X, symmetric=False)
+
+        def call(fn, shift):
+            def run(i):
+                W, s, ws = cps[(i + shift) % n_cp]
+                return fn(Xq, s_x, W, s, K=K, zp_x=zp_x, wsum=ws)
+            return run
+
+        fns = {"gemm_i8": call(ops.gemm_i8, 0), "gemm_i8_w4_short": call(ops.gemm_i8_w4_short, 1)}
+        if M >= 2048:
+            fns["gemm_i8_ring_w4"] = call(ops.gemm_i8_ring_w4, 2)
+        t = time_pair(fns, reps, warmup)
+        same = torch.equal(fns["gemm_i8"](0).view(torch.int16), call(ops.gemm_i8_w4_short, 0)(0).view(torch.int16))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        ops_n = 2.0 * M * N * K
+        row = {"shape": shape, "scheme": "W4A8", "M": M, "N": N, "K": K, "cold_copies": n_cp, "bits_equal": same,
+               "us": {k: round(v * 1e6, 2) for k, v in med.items()},
+               "min_us": {k: round(min(v) * 1e6, 2) for k, v in t.items()},
+               "tops": {k: round(ops_n / v / 1e12, 1) for k, v in med.items()},
+               "speedup": round(med["gemm_i8"] / med["gemm_i8_w4_short"], 3)}
+        if "gemm_i8_ring_w4" in med:
+            row["ring_w4_over_short"] = round(med["gemm_i8_ring_w4"] / med["gemm_i8_w4_short"], 3)
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr)
+        del X, Xq
+    del cps
+    torch.cuda.empty_cache()
+    return rows
+
+
 SPLITK_SHAPES = {**SHAPES, "o": (4096, 4096), "down_70b": (8192, 28672)}
+W4_SHORT_SHAPES = {**SHAPES, "o": (4096, 4096), "kv": (1024, 4096)}
+W4_SHORT_MS = "129,256,512,1024,2048,4096"
 MLP_MS = "1,16,32,128,2048,8192"
 MLP_HIDDEN, MLP_INTER = 4096, 14336
 
@@ -540,6 +586,8 @@ def main():
     ap.add_argument("--mid", action="store_true", help="only the tiled-vs-mid rows (17 .. 128 rows and neighbours)")
     ap.add_argument("--mid-shapes", default=",".join(MID_SHAPES))
     ap.add_argument("--ring-w4", action="store_true", help="only the W4A8 tiled-vs-ring rows (qt_gemm_i8_ring_w4)")
+    ap.add_argument("--w4-short", action="store_true",
+                    help="only the W4A8 tiled-vs-short(-vs-ring) rows (qt_w4_short_gemm_i8) at 129 .. 4096 rows")
     ap.add_argument("--splitk", action="store_true",
                     help="only the tiled-vs-ring-vs-split-K rows (qt_splitk_gemm_i8) at 129 .. 2047 rows")
     ap.add_argument("--splits", type=int, default=0, help="with --splitk: this S instead of the rule's")
@@ -584,6 +632,17 @@ def main():
                                     "weights", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                           "cus": torch.cuda.get_device_properties(0).multi_processor_count,
                           "splits_forced": args.splits, "splitk": sk}))
+        return
+    if args.w4_short:
+        ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else W4_SHORT_MS).split(",") if m]
+        shapes = args.shapes if args.shapes != ap.get_default("shapes") else ",".join(W4_SHORT_SHAPES)
+        rows = []
+        for shape in shapes.split(","):
+            N, K = W4_SHORT_SHAPES[shape]
+            rows += w4_short_rows(shape, N, K, ms, args.reps, args.warmup, dev, g)
+        print(json.dumps({"metric": "qt_gemm_i8 vs qt_w4_short_gemm_i8 (vs qt_gemm_i8_ring_w4 from 2048 rows), W4A8, "
+                                    "129 .. 4096 rows, cold weights", "device": torch.cuda.get_device_name(0),
+                          "reps": args.reps, "w4_short": rows}))
         return
     if args.ring_w4:
         ms = [int(m) for m in (args.ms if args.ms != ap.get_default("ms") else "2048,4096,8192").split(",") if m]
