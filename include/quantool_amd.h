@@ -826,6 +826,31 @@ int qt_gemm_wq_panel(const void* X, int x_dtype, int M, int K, int64_t ldx, cons
 #define QT_WQ_PANEL_K_UNIT 128
 #define QT_WQ_PANEL_MAX_LDX 16777216 /* 2^24 elements: a block of 64 rows is addressed by 32-bit byte offsets below 2^31 */
 
+/* qt_gemm_wq_tile: the tiled GEMM on the packed weights, for the rows above the three kernels before it (prompts of a
+ *   few hundred to a few thousand tokens, perplexity at short sequence lengths, long speculative batches; DESIGN.md
+ *   4.29).  The arguments and the weight definition are qt_gemm_wq_skinny's.  Taken: QT_W_INT4_PACKED and QT_W_INT8,
+ *   G = 1 and G = K / 128, with and without zp_w and bias, bf16 and fp16, any M >= 1 and N >= 1 with
+ *   ceil(M / 128) ceil(N / 128) < 2^31, ldy >= N, K <= ldx <= QT_WQ_TILE_MAX_LDX, K a multiple of QT_WQ_TILE_K_UNIT, and
+ *   X, Wq and ldx * 2 multiples of 16 bytes.  Everything else -- g_idx != NULL (actorder group runs on
+ *   qt_dequantize_weight + a dense GEMM), a ragged K, M = 0, a misaligned operand or pitch, a null pointer, a G that is
+ *   neither 1 nor K / 128, a dtype that is not 16-bit -- returns QT_ERR_INVALID before any launch, and qt_last_error
+ *   names the reason.
+ *   Its numerics are its own, NOT the skinny kernel's bits and not F.linear's.  The MFMA's weight operand is
+ *   w = round_to_dtype((q - zp) s), the value qt_dequantize_weight stores (the sign of a zero may differ).  A workgroup
+ *   of 4 waves owns a 128 x 128 tile of Y on v_mfma_f32_32x32x16_{bf16,f16}; output (m, n) is one fp32 accumulator over
+ *   the K-tiles of 64 columns in ascending order and, within each, the four k-steps of 16 columns in ascending order;
+ *   then the bias is added in fp32, then one rounding to x_dtype.  No atomics, no workspace, no split of K: two runs
+ *   give the same bits; row m of Y depends on row m of X alone, not on M or on the row's place in a tile; inputs whose
+ *   partial sums are all exact give round_to_dtype of the exact sum; otherwise
+ *   |y - y_exact| <= ulp_dtype(y) / 2 + K 2^-24 sum_k |x w|.  The packed weights are read once per tile of 128 rows and
+ *   no dense weight is written.  No byte outside X [M, K] (pitch ldx), Wq, s_w / zp_w [N, G] and bias [N] is read;
+ *   nothing outside Y[m < M, n < N] is written. */
+int qt_gemm_wq_tile(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format, int N,
+                    const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
+                    int64_t ldy, qt_stream_t stream);
+#define QT_WQ_TILE_K_UNIT 128
+#define QT_WQ_TILE_MAX_LDX 8388608 /* 2^23 elements: a tile of 128 rows is addressed by 32-bit byte offsets below 2^31 */
+
 /* One weight of the fused decode forms below: Wq, w_format, N, s_w, G, zp_w and g_idx with the meanings of the A16 block
  * above (K is the call's), and where the form has them bias [N] in x_dtype or NULL and the output Y [M, N] in x_dtype
  * with row pitch ldy. */

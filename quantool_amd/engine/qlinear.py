@@ -15,7 +15,8 @@ Linear either
   (M <= ``skinny_max_m`` rows) run the GEMV ``qt_gemm_wq_skinny``, larger ones dequantise the weight into a transient
   buffer (``qt_dequantize_weight``, bit-identical to the dequantised ``nn.Linear``) and call ``F.linear``; with
   ``a16_stream_rows`` inputs of 17 to that many rows run the weight-streaming ``qt_gemm_wq_stream`` instead, and with
-  ``a16_panel_rows`` inputs above those up to that many rows run ``qt_gemm_wq_panel``.
+  ``a16_panel_rows`` inputs above those up to that many rows run ``qt_gemm_wq_panel``, with ``a16_tile_rows`` what is
+  left up to that many rows runs ``qt_gemm_wq_tile``.
 
 Routed-expert banks (transformers >= 5 fuses them: ``<layer>.mlp.experts.gate_up_proj [E, 2I, H]`` / ``down_proj
 [E, H, I]``) are written per expert by ``sequential.expert_bank_checkpoint_names`` (Mixtral:
@@ -331,7 +332,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
                    a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
-                   a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0) -> nn.Module:
+                   a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0, a16_tile_rows: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -347,6 +348,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``panel_max_m`` on every ``WeightOnlyLinear`` built, so inputs of more than max(16, ``a16_stream_rows``) rows up to
     that many run ``qt_gemm_wq_panel`` on the stored weights, on the Linears inside the module's measured size bounds;
     it is recorded under ``"a16_panel_rows"``.  A8 checkpoints ignore it.
+    ``a16_tile_rows`` (0, the default, or a value above ``a16_panel_rows``, ``a16_stream_rows`` and 16; needs
+    ``a16="packed"``) sets ``tile_max_m`` on every ``WeightOnlyLinear`` built, so inputs of up to that many rows that the
+    kernels above do not take run ``qt_gemm_wq_tile`` on the stored weights instead of dequantise + ``F.linear``:
+    deterministic, but in a summation order of its own.  It is recorded under ``"a16_tile_rows"``.  A8
+    checkpoints ignore it.
     ``a16_experts_wide_tokens`` (0, the default, or 129 ... ``A16_EXPERTS_WIDE_MAX_TOKENS``; needs
     ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
     tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
@@ -408,6 +414,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                          f"{A16_PANEL_MAX_ROWS}")
     if a16_panel_rows and a16 != "packed":
         raise ValueError("a16_panel_rows needs a16='packed' (dequantised Linears have no stored weights to run on)")
+    tile_floor = max(16, a16_stream_rows, a16_panel_rows) + 1
+    if type(a16_tile_rows) is not int or not (a16_tile_rows == 0 or a16_tile_rows >= tile_floor):
+        raise ValueError(f"a16_tile_rows={a16_tile_rows!r}: expected 0 or {tile_floor} and more")
+    if a16_tile_rows and a16 != "packed":
+        raise ValueError("a16_tile_rows needs a16='packed' (dequantised Linears have no stored weights to run on)")
     if type(a16_experts_wide_tokens) is not int or not (
             a16_experts_wide_tokens == 0 or 129 <= a16_experts_wide_tokens <= A16_EXPERTS_WIDE_MAX_TOKENS):
         raise ValueError(f"a16_experts_wide_tokens={a16_experts_wide_tokens!r}: expected 0 or 129 ... "
@@ -492,6 +503,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                 new.stream_max_m = a16_stream_rows
             if not a8 and a16_panel_rows:
                 new.panel_max_m = a16_panel_rows
+            if not a8 and a16_tile_rows:
+                new.tile_max_m = a16_tile_rows
             _set_submodule(model, name, new)
         else:
             W = dequantized_weight(name, t, mdtype)
@@ -519,6 +532,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         model._qt_checkpoint["a16"] = "packed"
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows
         model._qt_checkpoint["a16_panel_rows"] = a16_panel_rows
+        model._qt_checkpoint["a16_tile_rows"] = a16_tile_rows
         model._qt_checkpoint["a16_fused_act"] = a16_fused_act
         model._qt_checkpoint["a16_fused_norm"] = a16_fused_norm
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))

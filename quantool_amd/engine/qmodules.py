@@ -382,7 +382,10 @@ class WeightOnlyLinear(nn.Module):
     ``ops.gemm_wq_stream_supported`` holds (no ``g_idx``, K a multiple of 128, aligned rows).  With ``panel_max_m`` > 0,
     max(``skinny_max_m``, ``stream_max_m``) < M <= ``panel_max_m`` runs ``qt_gemm_wq_panel`` (the same bits per row) on a
     Linear with ``in_features`` >= ``panel_min_k``, ``out_features`` >= ``panel_min_n`` and, when ``panel_max_n`` is
-    not 0, <= ``panel_max_n``, where ``ops.gemm_wq_panel_supported`` holds.
+    not 0, <= ``panel_max_n``, where ``ops.gemm_wq_panel_supported`` holds.  With ``tile_max_m`` > 0, what those branches
+    left of max(``skinny_max_m``, ``stream_max_m``) < M <= ``tile_max_m`` runs ``qt_gemm_wq_tile`` (deterministic, a
+    row's bits independent of M, but a summation order of its own) on a Linear inside ``tile_min_k`` / ``tile_min_n`` /
+    ``tile_max_n``, where ``ops.gemm_wq_tile_supported`` holds.
 
     Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
     ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
@@ -409,6 +412,17 @@ class WeightOnlyLinear(nn.Module):
     panel_min_k = 4096
     panel_min_n = 6144
     panel_max_n = 28672
+    # Tiled GEMM (``qt_gemm_wq_tile``) above the rows the branches before it took, up to this many.  0, the default: never
+    # -- its summation order is its own, neither F.linear's nor the skinny kernel's
+    # (``load_quantized(..., a16_tile_rows=)``).  Used only when it is not 0: from this many input and output features
+    # and, when ``tile_max_n`` is not 0, up to that many output features -- the only bounds within which no measured cell
+    # loses to the path before it beyond the run-to-run spread, and then only from 129 to 256 rows (gate /
+    # up and gate_up of Llama-3-8B; q/k/v, o, k/v and down lose at every row count, everything loses from 384 rows).
+    # What the kernel saves everywhere is the transient dense weight.
+    tile_max_m = 0
+    tile_min_k = 4096
+    tile_min_n = 14336
+    tile_max_n = 28672
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
@@ -444,7 +458,7 @@ class WeightOnlyLinear(nn.Module):
                 f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
                 f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}, "
-                f"panel_max_m={self.panel_max_m}")
+                f"panel_max_m={self.panel_max_m}, tile_max_m={self.tile_max_m}")
 
     # A ``SharedOutputs`` this Linear is a member of (None, the default: it computes for itself).
     outputs_from = None
@@ -477,6 +491,14 @@ class WeightOnlyLinear(nn.Module):
             x2 = _rows(x, w.K)
             if ops.gemm_wq_panel_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
                 y = ops.gemm_wq_panel(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
+                return y.reshape(*x.shape[:-1], w.N)
+        # whatever the branches above left: a Linear outside the panel's size bounds comes here from 17 rows up
+        if (self.tile_max_m > 0 and max(self.skinny_max_m, self.stream_max_m) < M <= self.tile_max_m
+                and w.K >= self.tile_min_k and w.N >= self.tile_min_n
+                and (self.tile_max_n == 0 or w.N <= self.tile_max_n)):
+            x2 = _rows(x, w.K)
+            if ops.gemm_wq_tile_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
+                y = ops.gemm_wq_tile(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
                 return y.reshape(*x.shape[:-1], w.N)
         W = ops.dequantize_weight(w.levels, w.scale, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx, dtype=x.dtype)
         return F.linear(x, W, bias)

@@ -163,6 +163,8 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "qt_gemm_wq_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "qt_gemm_wq_tile": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     # weights: a host array of WqWeight (qt_wq_weight)
     "qt_gemm_wq_skinny_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p]),
     "qt_gemm_wq_skinny_act_mul": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,

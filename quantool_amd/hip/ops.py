@@ -1513,6 +1513,68 @@ def gemm_wq_panel(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, *, zp_w:
     return Y
 
 
+WQ_TILE_K_UNIT = 128     # K must be a multiple: two K-tiles of 64 columns per weight group (QT_WQ_TILE_K_UNIT)
+WQ_TILE_MAX_LDX = 1 << 23    # largest row pitch of X in elements (QT_WQ_TILE_MAX_LDX)
+WQ_TILE_ROWS = 128       # edge of the output tile of qt_gemm_wq_tile; ceil(M / 128) ceil(N / 128) stays below 2^31
+
+
+def _wq_tile_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                     g_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_gemm_wq_tile`` would refuse these operands, or None: the rules of ``_wq_stream_refusal`` with the tile
+    kernel's pitch bound, at least one row, and a tile count below 2^31.  Host-only."""
+    why = _wq_stream_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is None and X.stride(0) > WQ_TILE_MAX_LDX:
+        why = f"the row pitch of X, {X.stride(0)} elements, is above {WQ_TILE_MAX_LDX}"
+    if why is None and X.shape[0] < 1:
+        why = f"M >= 1 rows only, got X {tuple(X.shape)}"
+    T = WQ_TILE_ROWS
+    if why is None and ((X.shape[0] + T - 1) // T) * ((Wq.shape[0] + T - 1) // T) >= 1 << 31:
+        why = f"ceil(M / {T}) * ceil(N / {T}) tiles must stay below 2^31"
+    return why
+
+
+def gemm_wq_tile_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                           zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_wq_tile`` takes these operands: at least one row, no ``g_idx``, 16-bit X with unit column stride
+    and a row pitch of at most ``WQ_TILE_MAX_LDX``, K a multiple of ``WQ_TILE_K_UNIT``, G = 1 or K/128, X, Wq and X's
+    row pitch 16-byte aligned.  Host-only."""
+    return _wq_tile_refusal(X, Wq, s_w, zp_w, g_idx) is None
+
+
+def gemm_wq_tile(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *,
+                 g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y = X W^T (+ bias) on the packed weights for any M >= 1 (``qt_gemm_wq_tile``): a 128 x 128 MFMA tile per
+    workgroup, the weights dequantised on chip, no dense weight written.  Its numerics are its own: one fp32 accumulator
+    per output over K ascending on w = round_to_dtype((q - zp) s), then the bias, then one rounding -- deterministic, a
+    row's bits independent of M, within the skinny kernel's error bound, but not bit-equal to the other ``gemm_wq_*``
+    kernels or to ``F.linear``.  ``out``: a caller-owned [M, N] view in X's dtype with unit column stride (any row
+    pitch).  ``g_idx`` is accepted only to be refused.  ``ValueError`` where ``gemm_wq_tile_supported`` is false, before
+    the library is touched."""
+    why = _wq_tile_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is not None:
+        raise ValueError(f"gemm_wq_tile: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    if bias is not None:
+        _req(bias, X.dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+    if out is None:
+        out = torch.empty((M, N), dtype=X.dtype, device=X.device)
+    elif (out.shape != (M, N) or out.dtype != X.dtype or out.device != X.device or out.stride(1) != 1
+          or out.stride(0) < N):
+        raise ValueError(f"out must be [{M}, {N}] {X.dtype} on {X.device} with unit column stride and a row pitch >= N")
+    check("qt_gemm_wq_tile", lib.qt_gemm_wq_tile(
+        X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), None,
+        _ptr(bias), out.data_ptr(), out.stride(0), _stream()))
+    return out
+
+
 WQ_FUSED_MAX_M = 16      # rows of X the fused decode forms take (QT_WQ_FUSED_MAX_M)
 WQ_FUSED_K_UNIT = 128    # K must be a multiple (QT_WQ_FUSED_K_UNIT)
 WQ_MULTI_MAX = 4         # weights of one qt_gemm_wq_skinny_multi launch (QT_WQ_MULTI_MAX)

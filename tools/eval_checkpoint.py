@@ -2,7 +2,8 @@
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
-                                  [--a16-stream-rows N] [--a16-panel-rows N] [--a16-experts-wide-tokens N]
+                                  [--a16-stream-rows N] [--a16-panel-rows N] [--a16-tile-rows N]
+                                  [--a16-experts-wide-tokens N]
                                   [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
                                   [--a8-fused-norm] [--a8-w4-short-min-m M] [--head logits|fused] [--against REF]
 
@@ -10,7 +11,8 @@
 on the int8 kernels (activations quantised per token), A16 checkpoints on their dequantised weights (``--a16 packed``:
 on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed`` with it: routed-expert banks on
 ``WeightOnlyExperts``; ``--a16-stream-rows N`` with it: inputs of 17 to N rows on ``qt_gemm_wq_stream``; ``--a16-panel-rows N`` with it: inputs
-above those, up to N rows, on ``qt_gemm_wq_panel``;
+above those, up to N rows, on ``qt_gemm_wq_panel``; ``--a16-tile-rows N`` with it: what those leave, up to N rows, on
+``qt_gemm_wq_tile``;
 ``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``;
 ``--a16-fused-act`` / ``--a16-fused-norm`` with ``--a16 packed``: ``load_quantized``'s flags of those names -- the first
 changes inputs of 1 to 16 rows alone and no bit, the second moves the perplexity as ``--a8-fused-norm`` does;
@@ -55,6 +57,9 @@ def main():
     ap.add_argument("--a16-panel-rows", type=int, default=0,
                     help="with --a16 packed: inputs above 16 (or --a16-stream-rows) rows up to this many (at most 512) "
                          "run qt_gemm_wq_panel")
+    ap.add_argument("--a16-tile-rows", type=int, default=0,
+                    help="with --a16 packed: inputs of up to this many rows that the kernels above leave run "
+                         "qt_gemm_wq_tile (a summation order of its own: the perplexity may move in its last digits)")
     ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
@@ -80,7 +85,7 @@ def main():
     model = load_quantized(args.checkpoint, device=args.device,
                            dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
-                           a16_panel_rows=args.a16_panel_rows,
+                           a16_panel_rows=args.a16_panel_rows, a16_tile_rows=args.a16_tile_rows,
                            a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act,
                            a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
                            a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m)

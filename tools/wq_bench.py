@@ -25,6 +25,12 @@ us.  ``bits_equal_skinny`` says whether every 16-row slice of the kernel's outpu
 The 33 - 512 row range, by the same method: per shape (q/k/v, o, k/v, gate/up, gate or up alone, down),
 scheme and M, ``ops.gemm_wq_panel`` against the dequantise + ``F.linear`` pair and, up to 128 rows,
 ``ops.gemm_wq_stream``, all alternating in one loop.
+
+  python tools/wq_bench.py --tile [--tile-ms 48,96,129,192,256,384,512,768,1024,2048,4096] [--reps 30] [--warmup 5]
+
+48 rows and up, by the same method: ``ops.gemm_wq_tile`` against the dequantise + ``F.linear`` pair and,
+on the shapes and rows a ``WeightOnlyLinear`` would give it, ``ops.gemm_wq_panel``; ``pair_peak_mb`` / ``tile_peak_mb``
+are one call's peak allocation above the operands.
 """
 from __future__ import annotations
 
@@ -153,6 +159,63 @@ def panel_main(args):
                       "warmup": args.warmup, "rows": rows}))
 
 
+def _peak_above(fn, X):
+    """Peak allocated bytes of one call of ``fn`` above what is allocated before it (the operands)."""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn(0, X)
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def tile_main(args):
+    """--tile: ``ops.gemm_wq_tile`` against the dequantise + ``F.linear`` pair and, where ``WeightOnlyLinear``'s panel
+    bounds hold (M <= 512, its N / K range), ``ops.gemm_wq_panel``: --stream's method, plus the peak allocation of pair
+    and kernel above the operands."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    names = [k for k in args.shapes.split(",") if k] if args.shapes != ",".join(SHAPES) else list(PANEL_SHAPES)
+    ms = [int(m) for m in args.tile_ms.split(",") if m]
+    L = WeightOnlyLinear
+    rows = []
+    for shape in names:
+        N, K = STREAM_SHAPES[shape]
+        panel_shape = K >= L.panel_min_k and N >= L.panel_min_n and (L.panel_max_n == 0 or N <= L.panel_max_n)
+        for scheme in args.schemes.split(","):
+            Wq0, s0, z0, qbytes, cps = _cold_weights(N, K, scheme, dev, g)
+            n_cp = len(cps)
+
+            def pair(i, X):
+                Wq, s, z = cps[i % n_cp]
+                return F.linear(X, ops.dequantize_weight(Wq, s, K=K, zp_w=z, dtype=X.dtype))
+
+            def kernel(op, i, X):
+                Wq, s, z = cps[i % n_cp]
+                return op(X, Wq, s, zp_w=z)
+
+            row = {"shape": shape, "N": N, "K": K, "scheme": scheme, "packed_mb": round(qbytes / 1e6, 2),
+                   "cold_copies": n_cp, "tile": {}}
+            for M in ms:
+                X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+                fns = [lambda i: pair(i, X), lambda i: kernel(ops.gemm_wq_tile, i, X)]
+                if panel_shape and M <= ops.WQ_PANEL_MAX_M:
+                    fns.append(lambda i: kernel(ops.gemm_wq_panel, i, X))
+                ts = _alternate(fns, args.reps, args.warmup)
+                cell = {"pair_us": ts[0], "tile_us": ts[1], "speedup": round(ts[0] / ts[1], 2),
+                        "tile_tflops": round(2.0 * M * N * K / ts[1] / 1e6, 1),
+                        "pair_peak_mb": round(_peak_above(pair, X) / 1e6, 2),
+                        "tile_peak_mb": round(_peak_above(lambda i, x: kernel(ops.gemm_wq_tile, i, x), X) / 1e6, 2)}
+                if len(ts) > 2:
+                    cell["panel_us"] = ts[2]
+                row["tile"][M] = cell
+            rows.append(row)
+            del cps
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "wq_bench --tile", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                      "warmup": args.warmup, "rows": rows}))
+
+
 def fused_main(args):
     """--fused: the two fused decode forms against the launches they replace, --stream's method.  ``act_mul``:
     ``ops.gemm_wq_skinny_act_mul`` on gate and up [14336, 4096] against two ``ops.gemm_wq_skinny`` calls, ``F.silu`` and
@@ -245,6 +308,9 @@ def main():
     ap.add_argument("--panel", action="store_true", help="the 33 - 512 row range: qt_gemm_wq_panel against "
                     "dequantise + F.linear and, up to 128 rows, qt_gemm_wq_stream")
     ap.add_argument("--panel-ms", default="48,64,96,128,192,256,384,512")
+    ap.add_argument("--tile", action="store_true", help="48 rows and up: qt_gemm_wq_tile against dequantise + F.linear "
+                    "and, where the module would take it, qt_gemm_wq_panel")
+    ap.add_argument("--tile-ms", default="48,96,129,192,256,384,512,768,1024,2048,4096")
     ap.add_argument("--fused", action="store_true", help="the fused decode forms (qt_gemm_wq_skinny_act_mul, "
                     "qt_gemm_wq_skinny_multi) against the skinny launches and torch glue they replace")
     ap.add_argument("--fused-ms", default="1,8,16")
@@ -264,6 +330,8 @@ def main():
         return stream_main(args)
     if args.panel:
         return panel_main(args)
+    if args.tile:
+        return tile_main(args)
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     shapes = {k: SHAPES[k] for k in args.shapes.split(",") if k}
