@@ -965,6 +965,43 @@ int qt_moe_gemm_wq_wide(const void* X, int x_dtype, int K, int64_t ldx, const in
 #define QT_MOE_WQ_WIDE_MAX_E 4096
 #define QT_MOE_WQ_WIDE_MAX_SLOTS 65535
 
+/* qt_moe_gemm_wq_tile: the bank form for prompts and evaluation batches -- qt_gemm_wq_tile's 128 x 128 MFMA tile over E
+ *   weight matrices and routed, gathered rows.  The signature and the meanings are
+ *   qt_moe_gemm_wq_wide's, argument for argument: Y [R, N] in routed order, expert e owns rows
+ *   [offsets[e], offsets[e + 1]) and weight matrix e, row_idx[r] is the row of X behind routed row r (NULL: the identity,
+ *   which needs x_rows >= R).  No bias, no workspace, no atomics, no split of K.
+ *   Taken: QT_W_INT4_PACKED and QT_W_INT8, G = 1 and G = K / 128, with and without zp_w, bf16 and fp16, any N >= 1, any
+ *   R >= 1 inside the tile bound below, any ldy >= N, K a multiple of QT_MOE_WQ_TILE_K_UNIT, X, Wq and ldx * 2 multiples
+ *   of 16 bytes, E <= QT_MOE_WQ_TILE_MAX_E, x_rows * ldx * 2 + 2 K < 2^32 (a gathered row is addressed by a 32-bit byte
+ *   offset from X).  Everything else -- g_idx != NULL, a ragged K, a misaligned operand or pitch, a null pointer, a G
+ *   that is neither 1 nor K / 128, a dtype that is not 16-bit, too many tiles, the 2^32 bound, E out of range -- returns
+ *   QT_ERR_INVALID before any launch, and qt_last_error names the reason.
+ *   Row r of Y, owned by expert e, is bit-identical to the row qt_gemm_wq_tile gives for the activation row
+ *   X[row_idx[r]] against expert e's weight, scales and zero-points, without bias: one fp32 accumulator per output over
+ *   the K-tiles of 64 columns in ascending order and, within each, the four k-steps in ascending order, the weight
+ *   operand round_to_dtype((q - zp) s), one rounding at the end; qt_gemm_wq_tile's rows depend on neither M nor the
+ *   row's place in a tile, and the two kernels share the statements.  Its error bound and exact-input guarantee carry
+ *   over.  The output is NOT bit-equal to qt_gemm_wq_grouped's or qt_moe_gemm_wq_wide's, nor to the dense bank's.
+ *   Deterministic: two runs give the same bits.
+ *   A slot is one tile of up to 128 routed rows of one expert.  The grid is 1-D over
+ *   (floor(R / 128) + min(E, R)) slots x ceil(N / 128) column tiles -- the slot count bounds the tiles of any routing and
+ *   comes from R and E alone, so no count is read on the host -- and must not exceed QT_MOE_WQ_TILE_MAX_TILES.  A band
+ *   of 8 consecutive slots walks the column tiles together, so that an XCD's L2 keeps one slot's gathered rows.  A
+ *   workgroup walks offsets, clamped to [0, R] and made ascending, to its expert, first row and live rows; a surplus
+ *   one exits before its first load and its first barrier; only the experts that own rows have their weights read.
+ *   The gathered rows go from X to LDS by the DMA lanes' own offsets: no gathered copy of X and no dense weight is
+ *   written.
+ *   row_idx values are clamped into [0, x_rows), not followed.  No byte outside X [x_rows, K] (pitch ldx),
+ *   Wq [E, N, .], s_w / zp_w [E, N, G], offsets [E + 1] and row_idx [R] is read; rows >= offsets[E] are not written,
+ *   and nothing outside Y[m < offsets[E], n < N] is.  (csrc/wq_moe_tile.hip) */
+int qt_moe_gemm_wq_tile(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                        const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w, int G,
+                        const int8_t* zp_w, const int32_t* g_idx, void* Y, int64_t ldy, int64_t x_rows,
+                        qt_stream_t stream);
+#define QT_MOE_WQ_TILE_K_UNIT 128
+#define QT_MOE_WQ_TILE_MAX_E 4096
+#define QT_MOE_WQ_TILE_MAX_TILES 2147483647 /* slots x column tiles: the 1-D grid */
+
 /* ---- evaluation: the LM head and its cross-entropy, logits never stored ------------------------------------------
  * qt_lm_head_nll: for every row m of H [M, K] (the final hidden states, row pitch ldh) and W [V, K] (the LM-head
  *   weight, row pitch ldw), both bf16 or both fp16 (dtype), with x[m, v] = sum_k H[m, k] W[v, k] in an fp32

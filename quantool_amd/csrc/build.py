@@ -51,6 +51,8 @@ SOURCE_FLAGS = {
     "wq_fused.hip": _NO_PACKED_FP32,
     # its dequantise statements must give qt_dequantize_weight's values element for element
     "wq_tile.hip": _NO_PACKED_FP32,
+    # the same statements (wq_tile_body.h): its rows must be qt_gemm_wq_tile's bit for bit
+    "wq_moe_tile.hip": _NO_PACKED_FP32,
     # since qt_rmsnorm's instances joined it: Y must be the quantising instances' Y bit for bit, on every device
     "rmsnorm_quant.hip": _NO_PACKED_FP32,
 }
@@ -140,7 +142,7 @@ def _resources(src: Path, stderr: str) -> str:
 
 
 def audit_m0(src: Path) -> None:
-    """xtx.hip, gemm3_tn.hip, sgemm_tn.hip, qlinear_ring.hip, qlinear_ring_w4.hip, qlinear_w4_short.hip, wq_tile.hip, lm_head_nll.hip and lm_head_kl.hip write M0 from inline asm without restoring it (the LDS-DMA destination).  That is only
+    """xtx.hip, gemm3_tn.hip, sgemm_tn.hip, qlinear_ring.hip, qlinear_ring_w4.hip, qlinear_w4_short.hip, wq_tile.hip, wq_moe_tile.hip, lm_head_nll.hip and lm_head_kl.hip write M0 from inline asm without restoring it (the LDS-DMA destination).  That is only
     sound while hipcc itself never touches M0 in that translation unit, so the device ISA is checked:
     every line that names m0 must sit inside an ;;#ASMSTART ... ;;#ASMEND block."""
     stamp = OBJ_DIR / (src.stem + ".m0audit")
@@ -200,7 +202,8 @@ def build(verbose: bool = False) -> Path:
         objs = list(ex.map(_compile, srcs))
     # (observer_mse.hip writes no M0: it is here for the spill audit that follows the M0 one)
     for name in ("xtx.hip", "gemm3_tn.hip", "sgemm_tn.hip", "sweep.hip", "qlinear.hip", "qlinear_ring.hip", "qlinear_ring_w4.hip",
-                 "qlinear_w4_short.hip", "wq_tile.hip", "lm_head_nll.hip", "lm_head_kl.hip", "observer_mse.hip"):
+                 "qlinear_w4_short.hip", "wq_tile.hip", "wq_moe_tile.hip", "lm_head_nll.hip", "lm_head_kl.hip",
+                 "observer_mse.hip"):
         audit_m0(CSRC / name)
     newest = max(o.stat().st_mtime for o in objs)
     if not LIB_PATH.exists() or LIB_PATH.stat().st_mtime < newest:

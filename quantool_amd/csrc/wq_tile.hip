@@ -69,239 +69,24 @@
 // host keeps ldx <= QT_WQ_TILE_MAX_LDX, so 128 rows of X span less than 2^31 bytes, and the number of tiles below 2^31.
 // The kernel is in csrc/build.py's spill and M0 audits.
 //
-// -ffp-contract=off (csrc/build.py): every multiply and add below rounds on its own.
-#include "common.h"
-#include "i8_ring_tile.h"
-#include "wq_stream_tile.h"
+// The statements are wq_tile_body.h, shared as text with moe_gemm_wq_tile_kernel (wq_moe_tile.hip; wq_tile.h says why).
+// -ffp-contract=off (csrc/build.py): every multiply and add there rounds on its own.
+#include "wq_tile.h"
 
 namespace {
 
-constexpr int TT = 128;                      // output tile edge
-constexpr int TKU = 64;                      // columns per K-tile: half a weight group
-constexpr int TSLOTS = 3;                    // units resident in LDS
-constexpr int TLEAD = 2;                     // unit t + TLEAD is issued in phase t
-constexpr int TTHREADS = 256;                // 4 waves: 2 (M) x 2 (N), 64 x 64 outputs per wave
-constexpr int TX_BYTES = TT * TKU * 2;       // 16 KiB: the X tile, and one weight image
-constexpr int TS_BYTES = 2 * TT * 4;         // 128 scales, 128 zero-points as dwords
 static_assert(QT_WQ_TILE_K_UNIT == 2 * TKU && QT_WQ_TILE_K_UNIT == WQ_KB, "two K-tiles per weight group");
-static_assert(TLEAD <= TSLOTS - 1, "WAR: see the head comment");
 static_assert((int64_t)TT * QT_WQ_TILE_MAX_LDX * 2 <= (1LL << 31), "tile offsets fit 31 bits");
-
-// One sign-extended byte per lane into a dword of LDS (64 x 4 B per wave-instruction): the gather of a column of the
-// int8 zero-point table, whose entries no dword load can address.  ring_pipe.h's glds4_one with the byte opcode;
-// counted in vmcnt like every other LDS-DMA.
-__device__ __forceinline__ void glds1_one(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile(
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_sbyte %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_dst)
-        : "memory");
-}
-
-template <int DT>
-__device__ __forceinline__ f32x16 tile_mfma(const u32x4 a, const u32x4 b, f32x16 c) {
-    if constexpr (DT == QT_F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0,
-                                                      0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                       0, 0, 0);
-}
-
-// byte offset of the 16-byte chunk c of row r in the X tile / weight image
-__device__ __forceinline__ int tile_img(int r, int c) {
-    return (r >> 3) * 1024 + (r & 7) * 128 + 16 * (c ^ ((r >> 1) & 7));
-}
 
 template <bool INT4, int DT, bool ZP>
 __global__ void __launch_bounds__(TTHREADS) wq_tile_kernel(const WqArgs p) {
-    constexpr int W_BYTES = TT * TKU / (INT4 ? 2 : 1);          // packed panel of a K-tile: 4 / 8 KiB
-    constexpr int WI = INT4 ? 1 : 2;                            // its LDS-DMA instructions per wave
-    constexpr int NI = 4 + WI + 1;                              // LDS-DMA instructions per wave and unit
-    constexpr int SLOT_BYTES = TX_BYTES + W_BYTES + TS_BYTES;
-    __shared__ __attribute__((aligned(16))) char lds[TSLOTS * SLOT_BYTES + 2 * TX_BYTES];
-    char* ring = lds;
-    char* img = lds + TSLOTS * SLOT_BYTES;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave_m = wave >> 1, wave_n = wave & 1;
     const int tiles_n = (p.N + TT - 1) / TT, tiles_m = (p.M + TT - 1) / TT;
     int m_tile, n_tile;
     i8_ring_tile_of(blockIdx.x, tiles_m, tiles_n, m_tile, n_tile);     // a band of m-tiles walks the n-tiles together
     const int m0 = m_tile * TT, n0 = n_tile * TT;
-    const int nt = p.K / TKU;                                   // K-tiles = phases, >= 2
-    const int a_last = p.M - 1 - m0, b_last = p.N - 1 - n0;     // last valid row of each operand, relative to the tile
-    const int wrow_b = p.K / (INT4 ? 2 : 1);                    // bytes of a packed weight row
-
-    // ---- staging geometry: this lane's source byte offsets, relative to the K-tile's first byte in the tile's row 0 ----
-    unsigned voffX[4], voffW, voffS;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {                               // row 32 wave + 8 i + (lane >> 3), physical chunk lane & 7
-        const int r = 32 * wave + 8 * i + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        voffX[i] = (unsigned)((int64_t)min(r, a_last) * p.ldx * 2 + 16 * c);
-    }
-    const int drow = 32 * wave + (lane >> 1);                   // the weight row this lane fetches and dequantises
-    voffW = (unsigned)((int64_t)min(drow, b_last) * wrow_b + 16 * (lane & 1));     // int8: + 32 for the second piece
-    const int scol = 64 * wave_n + lane;                        // the weight row whose scale / zero-point this lane fetches
-    const bool zp_wave = ZP && wave_m;                          // waves 2, 3: the zero-points
-    voffS = (unsigned)((int64_t)min(scol, b_last) * p.G * (zp_wave ? 1 : 4));
-    const unsigned ring_lds = (unsigned)(size_t)(QT_LDS char*)ring;
-    const unsigned dstX = __builtin_amdgcn_readfirstlane(ring_lds + wave * 4096);
-    const unsigned dstW = __builtin_amdgcn_readfirstlane(ring_lds + TX_BYTES + wave * (1024 * WI));
-    const unsigned dstS = __builtin_amdgcn_readfirstlane(ring_lds + TX_BYTES + W_BYTES + wave_m * 512 + wave_n * 256);
-    const char* srcX = (const char*)(p.X + (int64_t)m0 * p.ldx);
-    const char* srcW = (const char*)p.Wq + (int64_t)n0 * wrow_b;
-    const char* srcS = zp_wave ? (const char*)p.zp_w + (int64_t)n0 * p.G : (const char*)p.s_w + (int64_t)n0 * p.G * 4;
-    // unit u into `slot`: the X tile of K-tile u (none for u = -1) and the packed panel of K-tile min(u + 1, nt - 1)
-    auto issue = [&](int u, int slot) {
-        const unsigned off = (unsigned)slot * SLOT_BYTES;
-        if (u >= 0) {
-            const char* x = srcX + (size_t)u * (TKU * 2);
-            glds16_pair(voffX[0], voffX[1], x, dstX + off, dstX + off + 1024);
-            glds16_pair(voffX[2], voffX[3], x, dstX + off + 2048, dstX + off + 3072);
-        }
-        const int tw = min(u + 1, nt - 1);
-        const char* w = srcW + (size_t)tw * (W_BYTES / TT);
-        if constexpr (INT4) glds16_one(voffW, w, dstW + off);
-        else glds16_pair(voffW, voffW + 32, w, dstW + off, dstW + off + 1024);
-        const int g = p.G == 1 ? 0 : tw >> 1;
-        if (zp_wave) glds1_one(voffS, srcS + g, dstS + off);
-        else glds4_one(voffS, srcS + (size_t)g * 4, dstS + off);
-    };
-
-    // ---- fragment read geometry (per lane), byte offsets inside the X tile / the image ----
-    const int lr = lane & 31, lh = lane >> 5;
-    int xoff[4], woff[4];                                       // k-step s: chunk 2 s + lh; rows + 32: 4 pieces further
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        xoff[s] = tile_img(64 * wave_m + lr, 2 * s + lh);
-        woff[s] = tile_img(64 * wave_n + lr, 2 * s + lh);
-    }
-    // ---- dequantise geometry: the lane's packed bytes, its scale, and where its four chunks go ----
-    const int poff = TX_BYTES + wave * (1024 * WI) + 16 * lane; // int8: the second piece 1 KiB further
-    const int soff = TX_BYTES + W_BYTES + 4 * drow;
-    const bool drow_ok = drow <= b_last;
-    const float off_u = INT4 ? 8.0f : 128.0f;
-    int doff[4];                                                // chunk j of the lane's 32 weights
-#pragma unroll
-    for (int j = 0; j < 4; ++j)                                 // int4: columns 32 (lane & 1) + 8 j; int8: 16 ((lane & 1) + 2 (j >> 1)) + 8 (j & 1)
-        doff[j] = tile_img(drow, INT4 ? 4 * (lane & 1) + j : 2 * ((lane & 1) + 2 * (j >> 1)) + (j & 1));
-
-    unsigned pk[4 * WI];                                        // the lane's packed words of the K-tile being dequantised
-    float dsc, dcz;
-    auto load_packed = [&](const char* base) {
-#pragma unroll
-        for (int i = 0; i < WI; ++i) {
-            const u32x4 v = *(const u32x4*)(base + poff + 1024 * i);
-            pk[4 * i] = v.x, pk[4 * i + 1] = v.y, pk[4 * i + 2] = v.z, pk[4 * i + 3] = v.w;
-        }
-        const float s = *(const float*)(base + soff);
-        dsc = drow_ok ? s : 0.0f;
-        dcz = off_u;
-        if constexpr (ZP) dcz = off_u + (float)(int)(signed char)(*(const int*)(base + soff + TT * 4) & 0xff);
-    };
-    // chunk j: 8 weights -> w = round_to_dtype((u - cz) s), 16 bytes into the image
-    auto dequant_chunk = [&](int j, char* image) {
-        float u[8];
-        if constexpr (INT4) u_int4(pk[j], u);
-        else u_int8(pk[2 * j], pk[2 * j + 1], u);
-        float f[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float d = u[i] - dcz;
-            f[i] = d * dsc;
-        }
-        *(u32x4*)(image + doff[j]) =
-            (u32x4){pack2<DT>(f[0], f[1]), pack2<DT>(f[2], f[3]), pack2<DT>(f[4], f[5]), pack2<DT>(f[6], f[7])};
-    };
-
-    f32x16 acc[2][2];                                           // [nj][mi]: D rows = columns n, D columns = rows m
-#pragma unroll
-    for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nj][mi][r] = 0.0f;
-
-    // slot = t % 3 and ib = t & 1 are scalars carried beside t: one copy of the phase
-    auto phase = [&](int t, int slot, int ib) {
-        if (t + 1 < nt) wait_vmcnt<NI>();                       // unit t has landed; unit t + 1 stays in flight
-        else wait_vmcnt<0>();                                   // drain: the last unit
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");                          // no LDS access moves in front of the barrier
-        if (t + TLEAD < nt) issue(t + TLEAD, slot == 0 ? TLEAD : slot - 1);     // (slot + 2) % 3
-        const char* base = ring + slot * SLOT_BYTES;
-        const char* wimg = img + ib * TX_BYTES;
-        char* dimg = img + (ib ^ 1) * TX_BYTES;
-        u32x4 fx[2][4], fw[2][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                fw[h][s] = *(const u32x4*)(wimg + woff[s] + h * 4096);
-                fx[h][s] = *(const u32x4*)(base + xoff[s] + h * 4096);
-            }
-        load_packed(base);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) acc[nj][mi] = tile_mfma<DT>(fw[nj][s], fx[mi][s], acc[nj][mi]);
-            dequant_chunk(s, dimg);
-        }
-    };
-
-    issue(-1, TSLOTS - 1);
-    issue(0, 0);
-    issue(1, 1);
-    wait_vmcnt<2 * NI>();                                       // unit -1 has landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    load_packed(ring + (TSLOTS - 1) * SLOT_BYTES);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dequant_chunk(j, img);
-    for (int t = 0, slot = 0; t < nt; ++t, slot = slot == TSLOTS - 1 ? 0 : slot + 1) phase(t, slot, t & 1);
-
-    // ---- epilogue: y = acc (+ bias[n]), one rounding; element 4 j + i of (nj, mi) is column n + i of row m ----
-    const bool has_bias = p.bias != nullptr;
-#pragma unroll
-    for (int nj = 0; nj < 2; ++nj) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int nn = n0 + 64 * wave_n + 32 * nj + 8 * j + 4 * lh;
-            if (nn >= p.N) continue;
-            float b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) b[i] = (has_bias && nn + i < p.N) ? h2f<DT>(p.bias[nn + i]) : 0.0f;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                const int64_t m = (int64_t)m0 + 64 * wave_m + 32 * mi + lr;
-                if (m >= p.M) continue;
-                float y[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    y[i] = acc[nj][mi][4 * j + i];
-                    if (has_bias) y[i] = y[i] + b[i];
-                }
-                unsigned short* dst = p.Y + m * p.ldy + nn;
-                if (p.vec && nn + 3 < p.N) {                    // vec: Y and its pitch are 8-byte aligned
-                    *(uint2*)dst = make_uint2(pack2<DT>(y[0], y[1]), pack2<DT>(y[2], y[3]));
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (nn + i < p.N) dst[i] = (unsigned short)(pack2<DT>(y[i], 0.0f) & 0xffffu);
-                }
-            }
-        }
-    }
+    constexpr bool MOE = false;
+    constexpr int64_t row0 = 0, x_rows = 0;                     // the grouped form's names: not read
+#include "wq_tile_body.h"
 }
 
 }  // namespace

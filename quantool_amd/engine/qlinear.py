@@ -324,6 +324,9 @@ A16_MODES = ("dequantized", "packed")
 # The largest ``a16_experts_wide_tokens``: the largest call size at which qt_moe_gemm_wq_wide was measured (DESIGN.md
 # 4.19).
 A16_EXPERTS_WIDE_MAX_TOKENS = 2048
+# The largest ``a16_experts_tile_tokens``: the largest call size at which qt_moe_gemm_wq_tile was measured (DESIGN.md
+# 4.30).
+A16_EXPERTS_TILE_MAX_TOKENS = 4096
 # The largest ``a16_panel_rows``: the rows qt_gemm_wq_panel takes (ops.WQ_PANEL_MAX_M).
 A16_PANEL_MAX_ROWS = 512
 
@@ -332,7 +335,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                    a16_experts: str = "dequantized", a16_stream_rows: int = 0,
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
                    a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
-                   a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0, a16_tile_rows: int = 0) -> nn.Module:
+                   a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0, a16_tile_rows: int = 0,
+                   a16_experts_tile_tokens: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -357,6 +361,12 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
     tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
     is recorded under ``"a16_experts_wide_tokens"``.  A8 checkpoints ignore it.
+    ``a16_experts_tile_tokens`` (0, the default, or 129 ... ``A16_EXPERTS_TILE_MAX_TOKENS``, above
+    ``a16_experts_wide_tokens``; needs ``a16_experts="packed"``) sets ``tile_max_tokens`` on every ``WeightOnlyExperts``
+    built, so calls past the grouped and wide ranges up to that many tokens -- prompts, ``perplexity`` / ``divergence``
+    batches -- route their rows and run ``qt_moe_gemm_wq_tile`` on the stored weights instead of dequantising both banks:
+    deterministic, but in a summation order of its own.  It is recorded under
+    ``"a16_experts_tile_tokens"``.  A8 checkpoints ignore it.
     ``a8_fused_act`` (False, the default, or True) runs the glue between the two products of every A8 MLP as one pass,
     ``qt_act_mul_quantize_i8``, equal to the bit to the SiLU, the multiply and the quantiser it replaces: it sets
     ``fused_act`` on every ``QuantizedExperts`` built and puts a ``QuantizedMLP`` in place of every dense MLP for which
@@ -426,6 +436,14 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     if a16_experts_wide_tokens and a16_experts != "packed":
         raise ValueError("a16_experts_wide_tokens needs a16_experts='packed' (dequantised banks have no stored weights "
                          "to run on)")
+    experts_tile_floor = max(128, a16_experts_wide_tokens) + 1
+    if type(a16_experts_tile_tokens) is not int or not (
+            a16_experts_tile_tokens == 0 or experts_tile_floor <= a16_experts_tile_tokens <= A16_EXPERTS_TILE_MAX_TOKENS):
+        raise ValueError(f"a16_experts_tile_tokens={a16_experts_tile_tokens!r}: expected 0 or {experts_tile_floor} ... "
+                         f"{A16_EXPERTS_TILE_MAX_TOKENS}")
+    if a16_experts_tile_tokens and a16_experts != "packed":
+        raise ValueError("a16_experts_tile_tokens needs a16_experts='packed' (dequantised banks have no stored weights "
+                         "to run on)")
     if type(a8_fused_act) is not bool:
         raise ValueError(f"a8_fused_act={a8_fused_act!r}: expected True or False")
     if type(a8_fused_norm) is not bool:
@@ -484,6 +502,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             replaced.append(bank_name)
             if packed_experts and a16_experts_wide_tokens:
                 new.wide_max_tokens = a16_experts_wide_tokens
+            if packed_experts and a16_experts_tile_tokens:
+                new.tile_max_tokens = a16_experts_tile_tokens
             if a8 and a8_fused_act:
                 new.fused_act = True
             _set_submodule(model, bank_name, new)
@@ -539,4 +559,5 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         if packed_experts:
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)
             model._qt_checkpoint["a16_experts_wide_tokens"] = a16_experts_wide_tokens
+            model._qt_checkpoint["a16_experts_tile_tokens"] = a16_experts_tile_tokens
     return model

@@ -874,6 +874,11 @@ class WeightOnlyExperts(_RoutedExperts):
     alone.  Opt-in: with ``wide_max_tokens`` > 0, ``grouped_max_tokens`` < T <= ``wide_max_tokens`` takes the routed
     forward on that kernel instead of the dequantise path, on a bank where both products are supported (no ``g_idx``,
     H and I multiples of 128); its rows are bit-identical to the grouped GEMV's, not to the dense bank's.
+    Opt-in as well: with ``tile_max_tokens`` > 0, max(``grouped_max_tokens``, ``wide_max_tokens``) < T <=
+    ``tile_max_tokens`` takes the routed forward with both products on ``qt_moe_gemm_wq_tile`` (the dense tiled GEMM's
+    128 x 128 MFMA tile over the bank and the routed rows, which it gathers itself) where
+    ``ops.moe_gemm_wq_tile_supported`` holds for both: prompts and evaluation batches then allocate no dense bank.  Its
+    rows are ``qt_gemm_wq_tile``'s to the bit, in a summation order of its own.
 
     Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
     ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
@@ -898,6 +903,10 @@ class WeightOnlyExperts(_RoutedExperts):
     # (``load_quantized(..., a16_experts_wide_tokens=)``; the measurements support 384: the routed forward takes 0.47 - 0.83
     # of the dequantise path's time at 192 - 384 tokens and 1.08 - 1.19 of it at 512).
     wide_max_tokens = 0
+    # The routed forward on qt_moe_gemm_wq_tile up to this many tokens, past the two ranges above.  0, the default: never
+    # -- the same caller's choice, for the same reason (``load_quantized(..., a16_experts_tile_tokens=)``; what was
+    # measured is in DESIGN.md 4.30).
+    tile_max_tokens = 0
 
     def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
                  down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
@@ -925,7 +934,7 @@ class WeightOnlyExperts(_RoutedExperts):
                 f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
                 f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
                 f"grouped_max_tokens={self.grouped_max_tokens}, wide_min_tokens={self.wide_min_tokens}, "
-                f"wide_max_tokens={self.wide_max_tokens}")
+                f"wide_max_tokens={self.wide_max_tokens}, tile_max_tokens={self.tile_max_tokens}")
 
     def stored(self, part: str) -> StoredWeight:
         """The ``part`` ("gate_up" / "down") buffers as they are now, as one bank weight [E, ...]."""
@@ -959,7 +968,9 @@ class WeightOnlyExperts(_RoutedExperts):
 
         w = self.stored(part)
         gemm = ops.gemm_wq_grouped
-        if tokens > self.grouped_max_tokens:
+        if tokens > max(self.grouped_max_tokens, self.wide_max_tokens):
+            gemm = ops.moe_gemm_wq_tile         # the tile range: forward() has checked both products
+        elif tokens > self.grouped_max_tokens:
             gemm = ops.moe_gemm_wq_wide         # the extended range: forward() has checked both products
         elif self.wide_min_tokens > 0 and tokens >= self.wide_min_tokens:
             # the attribute and T decide first: ops' wide names are read only past them
@@ -967,18 +978,20 @@ class WeightOnlyExperts(_RoutedExperts):
                 gemm = ops.moe_gemm_wq_wide
         return gemm(x, w.levels, w.scale, offsets, row_idx=row_idx, K=w.K, zp_w=w.zero_point, g_idx=w.g_idx)
 
-    def _wide_range(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor) -> bool:
-        """Whether both products of this call run on ``qt_moe_gemm_wq_wide``: the gate_up product on the rows of
-        ``hidden_states`` gathered by token, the down product on the R = ``top_k_index.numel()`` routed rows (a
-        stand-in of that shape on the meta device is judged: the rows themselves are a fresh contiguous tensor)."""
+    def _both_supported(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, form: str) -> bool:
+        """Whether both products of this call run on ``qt_moe_gemm_wq_wide`` (``form`` "tile": on
+        ``qt_moe_gemm_wq_tile``): the gate_up product on the rows of ``hidden_states`` gathered by token, the down
+        product on the R = ``top_k_index.numel()`` routed rows (a stand-in of that shape on the meta device is judged:
+        the rows themselves are a fresh contiguous tensor)."""
         from ..hip import ops
 
+        supported = ops.moe_gemm_wq_tile_supported if form == "tile" else ops.moe_gemm_wq_wide_supported
         x = _rows(hidden_states, self.hidden_dim)
         routed = top_k_index.reshape(-1)        # its length alone is read
         act = torch.empty((routed.numel(), self.intermediate_dim), dtype=x.dtype, device="meta")
         for part, rows, row_idx in (("gate_up", x, routed), ("down", act, None)):
             w = self.stored(part)
-            if not ops.moe_gemm_wq_wide_supported(rows, w.levels, w.scale, w.zero_point, w.g_idx, row_idx):
+            if not supported(rows, w.levels, w.scale, w.zero_point, w.g_idx, row_idx):
                 return False
         return True
 
@@ -987,7 +1000,12 @@ class WeightOnlyExperts(_RoutedExperts):
         if hidden_states.is_cuda and 1 <= T <= self.grouped_max_tokens:
             return super().forward(hidden_states, top_k_index, top_k_weights)
         if (hidden_states.is_cuda and self.wide_max_tokens > 0 and self.grouped_max_tokens < T <= self.wide_max_tokens
-                and self._wide_range(hidden_states, top_k_index)):
+                and self._both_supported(hidden_states, top_k_index, "wide")):
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        # the attribute decides first: with 0 the tile names of ops are not read
+        if (hidden_states.is_cuda and self.tile_max_tokens > 0
+                and max(self.grouped_max_tokens, self.wide_max_tokens) < T <= self.tile_max_tokens
+                and self._both_supported(hidden_states, top_k_index, "tile")):
             return super().forward(hidden_states, top_k_index, top_k_weights)
         dense = {"gate_up_proj": self.dense_weight("gate_up", hidden_states.dtype),
                  "down_proj": self.dense_weight("down", hidden_states.dtype)}

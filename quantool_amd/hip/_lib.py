@@ -176,6 +176,9 @@ SIGNATURES = {
     "qt_moe_gemm_wq_wide": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                     c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                     c_void_p]),
+    "qt_moe_gemm_wq_tile": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                    c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                    c_void_p]),
     "qt_lm_head_nll_workspace_size": (c_size_t, [c_int64, c_int]),
     "qt_lm_head_nll": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -3,7 +3,7 @@
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-panel-rows N] [--a16-tile-rows N]
-                                  [--a16-experts-wide-tokens N]
+                                  [--a16-experts-wide-tokens N] [--a16-experts-tile-tokens N]
                                   [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
                                   [--a8-fused-norm] [--a8-w4-short-min-m M] [--head logits|fused] [--against REF]
 
@@ -14,6 +14,9 @@ on ``WeightOnlyLinear``s that keep the integer weights; ``--a16-experts packed``
 above those, up to N rows, on ``qt_gemm_wq_panel``; ``--a16-tile-rows N`` with it: what those leave, up to N rows, on
 ``qt_gemm_wq_tile``;
 ``--a16-experts-wide-tokens N`` with ``--a16-experts packed``: calls of 129 to N tokens on ``qt_moe_gemm_wq_wide``;
+``--a16-experts-tile-tokens N`` with ``--a16-experts packed``: calls above that (or above 128) up to N tokens on
+``qt_moe_gemm_wq_tile``, no dense bank allocated (a summation order of its own: the perplexity may move in its last
+digits);
 ``--a16-fused-act`` / ``--a16-fused-norm`` with ``--a16 packed``: ``load_quantized``'s flags of those names -- the first
 changes inputs of 1 to 16 rows alone and no bit, the second moves the perplexity as ``--a8-fused-norm`` does;
 ``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
@@ -63,6 +66,9 @@ def main():
     ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
+    ap.add_argument("--a16-experts-tile-tokens", type=int, default=0,
+                    help="with --a16-experts packed: calls past the grouped and wide ranges up to this many tokens route "
+                         "their rows and run qt_moe_gemm_wq_tile instead of dequantising the banks")
     ap.add_argument("--a16-fused-act", action="store_true",
                     help="with --a16 packed: WeightOnlyMLPs and shared q/k/v launches (inputs of 1 to 16 rows)")
     ap.add_argument("--a16-fused-norm", action="store_true",
@@ -86,7 +92,8 @@ def main():
                            dtype=getattr(torch, args.dtype) if args.dtype else None, a16=args.a16,
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
                            a16_panel_rows=args.a16_panel_rows, a16_tile_rows=args.a16_tile_rows,
-                           a16_experts_wide_tokens=args.a16_experts_wide_tokens, a8_fused_act=args.a8_fused_act,
+                           a16_experts_wide_tokens=args.a16_experts_wide_tokens,
+                           a16_experts_tile_tokens=args.a16_experts_tile_tokens, a8_fused_act=args.a8_fused_act,
                            a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
                            a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m)
     if args.device.startswith("cuda"):

@@ -64,6 +64,15 @@ Then WeightOnlyExperts.forward end to end on the path it had before the wide for
 0: the grouped pair up to grouped_max_tokens, the dequantise path above) against the new path (wide_min_tokens =
 --a16-wide-min-tokens, wide_max_tokens = the largest T asked for), alternating likewise.
 
+  python tools/moe_bench.py --schemes W4A16,W4A16_ASYM,W8A16 --a16-tile-tokens 512,1024,2048,4096
+
+The A16 prompt-size comparison, per scheme and T: WeightOnlyExperts.forward on the dequantise path (tile_max_tokens = 0:
+both banks dequantised, the transformers bank forward in torch) against the routed forward on qt_moe_gemm_wq_tile
+(tile_max_tokens = T), alternating call by call in one loop over rotating copies of the bank, the dequantise path twice
+("dequantise" and "dequantise_again": their ratio is the yardstick's own spread); the peak allocated memory of one
+forward of either path above what was allocated before it (peak_bytes_*); and the two products of the new path alone
+with their TFLOP/s.
+
   python tools/moe_bench.py --fused-act [--tokens 1,16,32,128,512,2048,8192] [--schemes W8A8,W4A8]
 
 The A8 glue comparison, per scheme and T: ``act_fn(gate) * up`` in torch followed by qt_quantize_tokens_i8 (three
@@ -491,6 +500,73 @@ def _bench_a16_wide(scheme, T, banks, dev, g, args, wide_max):
     return row
 
 
+def _bench_a16_tile(scheme, T, banks, dev, g, args):
+    """One A16 prompt-size row: the bank's forward on the dequantise path and on qt_moe_gemm_wq_tile, alternated (the
+    dequantise path twice: its own run-to-run spread), the two products of the new path alone, and the peak allocated
+    memory of one forward above what is allocated before it (operands and banks), cold weights."""
+    from qlinear_bench import time_pair
+
+    n = len(banks)
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = (w / w.sum(-1, keepdim=True)).to(torch.bfloat16)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    off = offsets.cpu().tolist()
+    row = {"scheme": scheme, "T": T, "rows_per_expert": [off[e + 1] - off[e] for e in range(E)],
+           "slots": T * TOPK // ops.MOE_WQ_TILE_ROWS + min(E, T * TOPK), "cold_copies": n}
+
+    def bank(tile_max_tokens, shift):
+        def run(i):
+            b = banks[(i + shift) % n]
+            b.tile_max_tokens = tile_max_tokens
+            return b(x, idx, w)
+        return run
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        y = fn(0)
+        torch.cuda.synchronize()
+        del y
+        return torch.cuda.max_memory_allocated() - base
+
+    with torch.no_grad():
+        try:
+            t = time_pair({"dequantise": bank(0, 0), "tile": bank(T, 1), "dequantise_again": bank(0, 2)}, args.reps,
+                          min(args.warmup, 2))
+            y0, y1 = bank(0, 0)(0), bank(T, 0)(0)
+            row["experts"] = {k: _us(v) for k, v in t.items()}
+            row["experts"].update(
+                speedup=round(row["experts"]["dequantise"]["us"] / row["experts"]["tile"]["us"], 3),
+                dequantise_spread=round(abs(row["experts"]["dequantise"]["us"] /
+                                            row["experts"]["dequantise_again"]["us"] - 1.0), 4),
+                max_abs_diff=float((y0.float() - y1.float()).abs().max()), out_scale=float(y0.float().abs().max()),
+                peak_bytes_dequantise=peak(bank(0, 0)), peak_bytes_tile=peak(bank(T, 0)))
+            del y0, y1
+        finally:
+            for b in banks:
+                b.__dict__.pop("tile_max_tokens", None)
+        b0 = banks[0]
+        gu = ops.moe_gemm_wq_tile(x, b0.gate_up, b0.gate_up_scale, offsets, row_idx=src_token, K=H,
+                                  zp_w=b0.gate_up_zero_point)
+        gate, up = gu.chunk(2, dim=-1)
+        h = b0.act_fn(gate) * up
+        del gu, gate, up
+        t = time_pair({"gate_up": lambda i: ops.moe_gemm_wq_tile(
+                           x, banks[i % n].gate_up, banks[i % n].gate_up_scale, offsets, row_idx=src_token, K=H,
+                           zp_w=banks[i % n].gate_up_zero_point),
+                       "down": lambda i: ops.moe_gemm_wq_tile(
+                           h, banks[i % n].down, banks[i % n].down_scale, offsets, K=I,
+                           zp_w=banks[i % n].down_zero_point)}, args.reps, args.warmup)
+        flops = {"gate_up": 2.0 * T * TOPK * 2 * I * H, "down": 2.0 * T * TOPK * H * I}
+        for name in ("gate_up", "down"):
+            row[name] = _us(t[name])
+            row[name]["tflops"] = round(flops[name] / row[name]["us"] * 1e-6, 1)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", default="2048,8192")
@@ -514,6 +590,10 @@ def main():
                          "counts instead")
     ap.add_argument("--a16-wide-min-tokens", type=int, default=1,
                     help="with --a16-wide-tokens: WeightOnlyExperts.wide_min_tokens of the bank's second timing")
+    ap.add_argument("--a16-tile-tokens", default="",
+                    help="W4A16 / W4A16_ASYM / W8A16: compare WeightOnlyExperts.forward on the dequantise path and on "
+                         "qt_moe_gemm_wq_tile (tile_max_tokens) at these token counts instead, with the peak memory of "
+                         "both")
     ap.add_argument("--fused-act", action="store_true",
                     help="W8A8 / W4A8: compare the three glue passes and qt_act_mul_quantize_i8, and the bank's forward "
                          "with fused_act off and on, at --tokens (default then: 1,16,32,128,512,2048,8192)")
@@ -526,6 +606,31 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     rows = []
+
+    if args.a16_tile_tokens:
+        from transformers import MixtralConfig
+        from transformers.models.mixtral.modeling_mixtral import MixtralExperts
+
+        cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=TOPK)
+        for scheme in args.schemes.split(","):
+            if scheme not in A16:
+                raise SystemExit("--a16-tile-tokens compares the A16 banks' forwards (W4A16 / W4A16_ASYM / W8A16)")
+            n = 3 if scheme != "W8A16" else 2       # > 1.4 GB of bank copies in all, as the A16 rows above
+            with torch.device("meta"):
+                shells = [MixtralExperts(cfg) for _ in range(n)]
+            banks = [_wo_experts(scheme, b, dev, g) for b in shells]
+            for T in (int(t) for t in args.a16_tile_tokens.split(",")):
+                row = _bench_a16_tile(scheme, T, banks, dev, g, args)
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del banks
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A16 prompt sizes: dequantise + bank forward vs "
+                                    "qt_moe_gemm_wq_tile",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
 
     if args.a16_wide_tokens:
         from transformers import MixtralConfig
