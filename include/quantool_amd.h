@@ -965,6 +965,37 @@ int qt_moe_gemm_wq_wide(const void* X, int x_dtype, int K, int64_t ldx, const in
 #define QT_MOE_WQ_WIDE_MAX_E 4096
 #define QT_MOE_WQ_WIDE_MAX_SLOTS 65535
 
+/* qt_gemm_wq_grouped_act_mul / qt_moe_gemm_wq_wide_act_mul: H [R, N] = SiLU(x Wg_e^T) * (x Wu_e^T) in x_dtype (pitch
+ *   ldh >= N) straight from a routed-expert bank gate_up, in one launch (engine/qmodules.py WeightOnlyExperts with
+ *   fused_act).  The arguments and their meanings are qt_moe_gemm_wq_wide's, argument for argument,
+ *   except that N is the intermediate size I: the bank holds 2 N rows per expert -- Wq [E, 2 N, ceil(K/8)] packed int4
+ *   or [E, 2 N, K] int8, s_w fp32 [E, 2 N, G], zp_w int8 [E, 2 N, G] or NULL; rows [0, N) of an expert are gate, rows
+ *   [N, 2 N) up -- and the one output is H.  No bias, no workspace, no atomics.
+ *   Taken and refused: exactly what qt_moe_gemm_wq_wide takes and refuses, for both entry points (g_idx != NULL, a K
+ *   that is no multiple of 128, a G that is neither 1 nor K / 128, a misaligned X, Wq or pitch, the 2^32 bound, too
+ *   many slots, a null pointer, N < 1 return QT_ERR_INVALID before any launch; qt_last_error names the entry point and
+ *   the reason).
+ *   Row m of H, owned by expert e, is bit-identical to SiLU(g) * u as torch evaluates it on the two halves g = Y[m, :N],
+ *   u = Y[m, N:] of qt_gemm_wq_grouped's output Y [R, 2 N] on the same arguments: each half's element runs
+ *   qt_gemm_wq_grouped's chain (wave w the k-blocks w, w + 4, ... ascending, then ((c0 + c1) + c2) + c3, one rounding
+ *   to x_dtype), and the activation is qt_act_mul_quantize_i8's SiLU and product on 16-bit values.  A gate or up row
+ *   past N is never read (level 0 stands in): a column tile that crosses N sees neither the first up rows nor the next
+ *   expert's gate rows.  Deterministic.
+ *   qt_gemm_wq_grouped_act_mul is the decode form: one slot per 16 rows of one expert, grid ceil(N/16) x
+ *   (floor(R/16) + min(E, R)).  qt_moe_gemm_wq_wide_act_mul holds MT tiles of 16 rows of one expert per workgroup and
+ *   forms the expert's gate and up fragments once for all of them; MT and the slot count are qt_moe_gemm_wq_wide's,
+ *   from R and E alone.  Both bound the slots by QT_MOE_WQ_WIDE_MAX_SLOTS, walk offsets clamped to [0, R], clamp
+ *   row_idx values into [0, x_rows), read nothing outside X, the bank, offsets and row_idx, and write nothing outside
+ *   H[m < offsets[E], n < N].  (csrc/wq_moe_fused.hip) */
+int qt_gemm_wq_grouped_act_mul(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                               const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w,
+                               int G, const int8_t* zp_w, const int32_t* g_idx, void* H, int64_t ldh, int64_t x_rows,
+                               qt_stream_t stream);
+int qt_moe_gemm_wq_wide_act_mul(const void* X, int x_dtype, int K, int64_t ldx, const int32_t* row_idx, int64_t R,
+                                const int32_t* offsets, int E, const void* Wq, int w_format, int N, const float* s_w,
+                                int G, const int8_t* zp_w, const int32_t* g_idx, void* H, int64_t ldh, int64_t x_rows,
+                                qt_stream_t stream);
+
 /* qt_moe_gemm_wq_tile: the bank form for prompts and evaluation batches -- qt_gemm_wq_tile's 128 x 128 MFMA tile over E
  *   weight matrices and routed, gathered rows.  The signature and the meanings are
  *   qt_moe_gemm_wq_wide's, argument for argument: Y [R, N] in routed order, expert e owns rows

@@ -49,6 +49,8 @@ SOURCE_FLAGS = {
     "wq_panel.hip": _NO_PACKED_FP32,
     "observer_mse.hip": _NO_PACKED_FP32,
     "wq_fused.hip": _NO_PACKED_FP32,
+    # the same tile (wq_fused_tile.h) and the same reason: its halves must be qt_gemm_wq_grouped's bit for bit
+    "wq_moe_fused.hip": _NO_PACKED_FP32,
     # its dequantise statements must give qt_dequantize_weight's values element for element
     "wq_tile.hip": _NO_PACKED_FP32,
     # the same statements (wq_tile_body.h): its rows must be qt_gemm_wq_tile's bit for bit

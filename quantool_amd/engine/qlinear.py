@@ -336,7 +336,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
                    a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
                    a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0, a16_tile_rows: int = 0,
-                   a16_experts_tile_tokens: int = 0) -> nn.Module:
+                   a16_experts_tile_tokens: int = 0, a16_experts_fused_act: bool = False) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -367,6 +367,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     batches -- route their rows and run ``qt_moe_gemm_wq_tile`` on the stored weights instead of dequantising both banks:
     deterministic, but in a summation order of its own.  It is recorded under
     ``"a16_experts_tile_tokens"``.  A8 checkpoints ignore it.
+    ``a16_experts_fused_act`` (False, the default, or True; needs ``a16="packed"`` and ``a16_experts="packed"``) sets
+    ``fused_act`` on every ``WeightOnlyExperts`` built, so a routed forward on the grouped or the wide kernel runs the
+    gate_up product, SiLU and the multiply as one launch (``qt_gemm_wq_grouped_act_mul`` /
+    ``qt_moe_gemm_wq_wide_act_mul``), equal to the bit to the launches it replaces: the flag changes speed alone
+    (DESIGN.md 4.31).  It is recorded under ``"a16_experts_fused_act"``.  A8 checkpoints ignore it.
     ``a8_fused_act`` (False, the default, or True) runs the glue between the two products of every A8 MLP as one pass,
     ``qt_act_mul_quantize_i8``, equal to the bit to the SiLU, the multiply and the quantiser it replaces: it sets
     ``fused_act`` on every ``QuantizedExperts`` built and puts a ``QuantizedMLP`` in place of every dense MLP for which
@@ -456,6 +461,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             raise ValueError(f"{flag}={value!r}: expected True or False")
         if value and a16 != "packed":
             raise ValueError(f"{flag} needs a16='packed' (dequantised Linears and their norms run on torch's kernels)")
+    if type(a16_experts_fused_act) is not bool:
+        raise ValueError(f"a16_experts_fused_act={a16_experts_fused_act!r}: expected True or False")
+    if a16_experts_fused_act and (a16 != "packed" or a16_experts != "packed"):
+        raise ValueError("a16_experts_fused_act needs a16='packed' and a16_experts='packed' (dequantised banks run "
+                         "their own forward)")
     path = Path(path)
     cfg, qcfg = _read_config(path)
     fmt = str(qcfg.get("format", ""))
@@ -504,6 +514,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                 new.wide_max_tokens = a16_experts_wide_tokens
             if packed_experts and a16_experts_tile_tokens:
                 new.tile_max_tokens = a16_experts_tile_tokens
+            if packed_experts and a16_experts_fused_act:
+                new.fused_act = True
             if a8 and a8_fused_act:
                 new.fused_act = True
             _set_submodule(model, bank_name, new)
@@ -560,4 +572,5 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
             model._qt_checkpoint["packed_expert_banks"] = sorted(replaced)
             model._qt_checkpoint["a16_experts_wide_tokens"] = a16_experts_wide_tokens
             model._qt_checkpoint["a16_experts_tile_tokens"] = a16_experts_tile_tokens
+            model._qt_checkpoint["a16_experts_fused_act"] = a16_experts_fused_act
     return model

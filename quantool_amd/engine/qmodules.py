@@ -879,6 +879,10 @@ class WeightOnlyExperts(_RoutedExperts):
     128 x 128 MFMA tile over the bank and the routed rows, which it gathers itself) where
     ``ops.moe_gemm_wq_tile_supported`` holds for both: prompts and evaluation batches then allocate no dense bank.  Its
     rows are ``qt_gemm_wq_tile``'s to the bit, in a summation order of its own.
+    Opt-in: with ``fused_act`` and a SiLU ``act_fn``, a routed forward on the grouped or the wide kernel runs the gate_up
+    product and ``act_fn(gate) * up`` as one launch (``qt_gemm_wq_grouped_act_mul``, or ``qt_moe_gemm_wq_wide_act_mul``
+    where the product would have run the wide kernel) where ``ops.moe_gemm_wq_act_mul_supported`` holds; the output is
+    the same to the bit.
 
     Buffers: ``gate_up`` packed int4 int32 [E, 2I, ceil(H/8)] or int8 [E, 2I, H] (rows [0, I) gate, [I, 2I) up),
     ``gate_up_scale`` fp32 [E, 2I, G], ``gate_up_zero_point`` int8 [E, 2I, G] (optional), ``gate_up_g_idx`` int32
@@ -907,6 +911,12 @@ class WeightOnlyExperts(_RoutedExperts):
     # -- the same caller's choice, for the same reason (``load_quantized(..., a16_experts_tile_tokens=)``; what was
     # measured is in DESIGN.md 4.30).
     tile_max_tokens = 0
+    # The gate_up product and SiLU(gate) * up as one launch inside the routed forward on the grouped or the wide kernel
+    # (qt_gemm_wq_grouped_act_mul / qt_moe_gemm_wq_wide_act_mul), when act_fn is SiLU and
+    # ops.moe_gemm_wq_act_mul_supported holds for the gate_up bank: equal to the passes it replaces to the bit
+    # (DESIGN.md 4.31).  Off by default: opt-in through ``load_quantized(..., a16_experts_fused_act=True)``; the tile
+    # range, the dequantise path and any other act_fn are untouched.
+    fused_act = False
 
     def __init__(self, bank: nn.Module, gate_up: torch.Tensor, gate_up_scale: torch.Tensor, down: torch.Tensor,
                  down_scale: torch.Tensor, *, gate_up_zero_point: Optional[torch.Tensor] = None,
@@ -934,7 +944,8 @@ class WeightOnlyExperts(_RoutedExperts):
                 f"groups=({self.gate_up_scale.shape[2]}, {self.down_scale.shape[2]}), "
                 f"zero_point={self.gate_up_zero_point is not None}, g_idx={self.gate_up_g_idx is not None}, "
                 f"grouped_max_tokens={self.grouped_max_tokens}, wide_min_tokens={self.wide_min_tokens}, "
-                f"wide_max_tokens={self.wide_max_tokens}, tile_max_tokens={self.tile_max_tokens}")
+                f"wide_max_tokens={self.wide_max_tokens}, tile_max_tokens={self.tile_max_tokens}, "
+                f"fused_act={self.fused_act}")
 
     def stored(self, part: str) -> StoredWeight:
         """The ``part`` ("gate_up" / "down") buffers as they are now, as one bank weight [E, ...]."""
@@ -995,13 +1006,35 @@ class WeightOnlyExperts(_RoutedExperts):
                 return False
         return True
 
+    def _routed(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
+        """The routed forward on the grouped or the wide kernel: ``_RoutedExperts.forward``, or with ``fused_act`` the
+        same with the gate_up product and ``act_fn(gate) * up`` as one call."""
+        # the attribute decides first: with False the fused names of ops are not read
+        if not (self.fused_act and is_silu(self.act_fn)):
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        from ..hip import ops
+
+        x = _rows(hidden_states, self.hidden_dim)
+        T = x.shape[0]
+        w = self.stored("gate_up")
+        # top_k_index stands in for src_token: the routed row count alone is read
+        if not ops.moe_gemm_wq_act_mul_supported(x, w.levels, w.scale, w.zero_point, w.g_idx, top_k_index.reshape(-1)):
+            return super().forward(hidden_states, top_k_index, top_k_weights)
+        offsets, src_token, _, row_of = ops.moe_route(top_k_index, self.num_experts)
+        # the wide form where _product would pick qt_moe_gemm_wq_wide (which takes whatever the fused forms take)
+        wide = T > self.grouped_max_tokens or (self.wide_min_tokens > 0 and T >= self.wide_min_tokens)
+        fused = ops.moe_gemm_wq_wide_act_mul if wide else ops.gemm_wq_grouped_act_mul
+        h = fused(x, w.levels, w.scale, offsets, row_idx=src_token, K=w.K, zp_w=w.zero_point)
+        y = self._product("down", h, offsets, None, T)
+        return ops.moe_combine(y, row_of, top_k_weights).reshape(hidden_states.shape)
+
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor):
         T = hidden_states.numel() // self.hidden_dim
         if hidden_states.is_cuda and 1 <= T <= self.grouped_max_tokens:
-            return super().forward(hidden_states, top_k_index, top_k_weights)
+            return self._routed(hidden_states, top_k_index, top_k_weights)
         if (hidden_states.is_cuda and self.wide_max_tokens > 0 and self.grouped_max_tokens < T <= self.wide_max_tokens
                 and self._both_supported(hidden_states, top_k_index, "wide")):
-            return super().forward(hidden_states, top_k_index, top_k_weights)
+            return self._routed(hidden_states, top_k_index, top_k_weights)
         # the attribute decides first: with 0 the tile names of ops are not read
         if (hidden_states.is_cuda and self.tile_max_tokens > 0
                 and max(self.grouped_max_tokens, self.wide_max_tokens) < T <= self.tile_max_tokens

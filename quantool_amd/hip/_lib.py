@@ -176,6 +176,12 @@ SIGNATURES = {
     "qt_moe_gemm_wq_wide": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                     c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                     c_void_p]),
+    "qt_gemm_wq_grouped_act_mul": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int,
+                                           c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int64, c_int64, c_void_p]),
+    "qt_moe_gemm_wq_wide_act_mul": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int,
+                                            c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_int64, c_int64, c_void_p]),
     "qt_moe_gemm_wq_tile": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                     c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                     c_void_p]),

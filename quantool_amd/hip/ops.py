@@ -1839,6 +1839,90 @@ def moe_gemm_wq_wide(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offse
     return Y
 
 
+def _moe_wq_act_mul_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                            g_idx: Optional[torch.Tensor] = None, row_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_gemm_wq_grouped_act_mul`` / ``qt_moe_gemm_wq_wide_act_mul`` would refuse a gate_up bank [E, 2I, .], or
+    None: ``qt_moe_gemm_wq_wide``'s rules, an even row count, and the decode form's 16-row slots inside the grid as
+    well as the wide form's.  Host-only."""
+    if g_idx is not None:
+        return "g_idx is not taken (an actorder group runs on gemm_wq_grouped, the activation in a pass of its own)"
+    why = _moe_wq_wide_refusal(X, Wq, s_w, zp_w, g_idx, row_idx)
+    if why is not None:
+        return why
+    E, N2 = Wq.shape[0], Wq.shape[1]
+    if N2 < 2 or N2 % 2 != 0:
+        return f"a gate_up bank holds 2 I rows per expert (gate, then up), got {N2}"
+    R = X.shape[0] if row_idx is None else row_idx.numel()
+    if R // 16 + min(E, R) > MOE_WQ_WIDE_MAX_SLOTS:
+        return f"{R // 16 + min(E, R)} 16-row slots (R={R}, E={E}) exceed the grid's {MOE_WQ_WIDE_MAX_SLOTS}"
+    return None
+
+
+def moe_gemm_wq_act_mul_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                                  zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                                  row_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_wq_grouped_act_mul`` and ``moe_gemm_wq_wide_act_mul`` take X and the gate_up bank ``Wq``
+    [E, 2I, .]: ``moe_gemm_wq_wide_supported``'s conditions, an even number of rows per expert and at most
+    ``MOE_WQ_WIDE_MAX_SLOTS`` 16-row slots.  Host-only."""
+    return _moe_wq_act_mul_refusal(X, Wq, s_w, zp_w, g_idx, row_idx) is None
+
+
+def _moe_wq_act_mul(name: str, X, Wq, s_w, offsets, row_idx, K, zp_w, g_idx, act) -> torch.Tensor:
+    why = _moe_wq_act_mul_refusal(X, Wq, s_w, zp_w, g_idx, row_idx)
+    if why is None and act not in ACTS:
+        why = f"act must be one of {sorted(ACTS)}, got {act!r}"
+    if why is not None:
+        raise ValueError(f"{name}: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    Mx, Kx = X.shape
+    if K is not None and K != Kx:
+        raise ValueError(f"K={K} but X has {Kx} columns")
+    fmt, N2, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, Kx, experts=True)
+    E = Wq.shape[0]
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    _req(offsets, torch.int32, "offsets", 1)
+    if offsets.numel() != E + 1 or not offsets.is_contiguous() or offsets.device != X.device:
+        raise ValueError(f"offsets must be contiguous int32 [E + 1 = {E + 1}] on {X.device}")
+    if row_idx is not None:
+        _req(row_idx, torch.int32, "row_idx", 1)
+        if not row_idx.is_contiguous() or row_idx.device != X.device:
+            raise ValueError(f"row_idx must be contiguous int32 [R] on {X.device}")
+        R = row_idx.numel()
+    else:
+        R = Mx
+    I = N2 // 2
+    H = torch.empty((R, I), dtype=X.dtype, device=X.device)
+    check(f"qt_{name}", getattr(lib, f"qt_{name}")(
+        X.data_ptr(), code, K, X.stride(0) if Mx > 1 else K, _ptr(row_idx), R, offsets.data_ptr(), E, Wq.data_ptr(),
+        fmt, I, s_w.data_ptr(), G, _ptr(zp_w), None, H.data_ptr(), H.stride(0), Mx, _stream()))
+    return H
+
+
+def gemm_wq_grouped_act_mul(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
+                            row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                            zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                            act: str = "silu") -> torch.Tensor:
+    """H [R, I] = act(g) * u in X's dtype in one launch (``qt_gemm_wq_grouped_act_mul``), g and u the two halves of
+    ``gemm_wq_grouped(X, Wq, ...)`` on the gate_up bank ``Wq`` [E, 2I, .] (rows [0, I) of an expert gate, [I, 2I) up):
+    the decode form, 16 rows of one expert per workgroup.  ``gemm_wq_grouped``'s arguments; bit-identical to
+    ``F.silu(Y[:, :I]) * Y[:, I:]`` of its output on the device, and ``row_idx`` values are clamped into X's rows.
+    ``g_idx`` is accepted only to be refused.  ``ValueError`` where ``moe_gemm_wq_act_mul_supported`` is false, before
+    the library is touched."""
+    return _moe_wq_act_mul("gemm_wq_grouped_act_mul", X, Wq, s_w, offsets, row_idx, K, zp_w, g_idx, act)
+
+
+def moe_gemm_wq_wide_act_mul(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, offsets: torch.Tensor, *,
+                             row_idx: Optional[torch.Tensor] = None, K: Optional[int] = None,
+                             zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
+                             act: str = "silu") -> torch.Tensor:
+    """``gemm_wq_grouped_act_mul`` with several tiles of 16 rows of one expert per workgroup
+    (``qt_moe_gemm_wq_wide_act_mul``): the batched-decode form, ``moe_wq_wide_mtiles(R, E)`` tiles as
+    ``moe_gemm_wq_wide`` holds.  Same arguments, the same H to the bit."""
+    return _moe_wq_act_mul("moe_gemm_wq_wide_act_mul", X, Wq, s_w, offsets, row_idx, K, zp_w, g_idx, act)
+
+
 MOE_WQ_TILE_K_UNIT = 128            # K must be a multiple: two K-tiles of 64 columns per group (QT_MOE_WQ_TILE_K_UNIT)
 MOE_WQ_TILE_MAX_E = 4096            # experts a workgroup of qt_moe_gemm_wq_tile walks (QT_MOE_WQ_TILE_MAX_E)
 MOE_WQ_TILE_MAX_TILES = (1 << 31) - 1   # slots x column tiles of its 1-D grid (QT_MOE_WQ_TILE_MAX_TILES)

@@ -50,6 +50,9 @@ so nothing is asserted of the logits: how many of the prompt's differ, and by ho
 (``logits_differ``, ``logits_max_abs_diff``) beside ``quantizing_norms``.
 ``--pair a16_fused`` / ``a16_norm`` / ``a16_both`` (W4A16 / W8A16, llama) load the checkpoint with ``a16="packed"`` as
 ``a16_off`` and with ``a16_fused_act``, ``a16_fused_norm`` or each alone and both, decoded in turn, twice.
+``--pair a16_experts_fused`` (W4A16 / W8A16, ``--model mixtral``) loads the checkpoint with packed expert banks as
+``a16_experts_off`` and with ``a16_experts_fused_act=True`` as ``a16_experts_fused``: one decode step's
+logits must agree to the bit, and the tokens.
 """
 from __future__ import annotations
 
@@ -333,6 +336,35 @@ def a16_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, pair: str, 
         result.update({k: r[k] for k in ("tokens_agree", "first_difference")}, speedup=round(min(off) / min(r["ms_per_step"]), 3))
 
 
+def a16_experts_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict) -> None:
+    """A packed A16 sparse-MoE checkpoint (``a16="packed"``, ``a16_experts="packed"``) loaded as ``a16_experts_off`` and,
+    with ``a16_experts_fused_act=True``, as ``a16_experts_fused``, decoded in turn, twice.  The fused
+    launches equal what they replace to the bit, so one decode step's logits must, and the tokens."""
+    kw = dict(device=dev, a16="packed", a16_experts="packed")
+    models = {"a16_experts_off": load_quantized(path, **kw),
+              "a16_experts_fused": load_quantized(path, a16_experts_fused_act=True, **kw)}
+    banks = [m for m in models["a16_experts_fused"].modules() if isinstance(m, WeightOnlyExperts)]
+    result["weight_only_expert_banks"] = len(banks)
+    assert banks and all(b.fused_act for b in banks), "no packed expert bank in this checkpoint"
+    with torch.no_grad():
+        a, b = (m(input_ids=prompt[:, :1]).logits for m in models.values())
+    assert torch.equal(a.view(torch.int16), b.view(torch.int16)), \
+        "a decode step's logits differ with a16_experts_fused_act"
+    result["logits_bits_equal"] = True
+    del a, b
+    tokens = {}
+    for rep in range(2):                                       # both modes twice: the second pass is the spread
+        for mode, model in models.items():
+            decode(model, prompt[:, :8], 4)                    # warm-up: kernels, allocator
+            toks, per_tok = decode(model, prompt, new)
+            result["modes"].setdefault(mode, {"ms_per_step": []})["ms_per_step"].append(round(per_tok * 1e3, 3))
+            assert tokens.setdefault(mode, toks) == toks, f"{mode}: two runs gave different tokens"
+    assert tokens["a16_experts_off"] == tokens["a16_experts_fused"], "the tokens differ with a16_experts_fused_act"
+    off, on = (result["modes"][m]["ms_per_step"] for m in models)
+    result["off_spread"] = round(abs(off[0] / off[1] - 1.0), 4)
+    result["speedup"] = round(min(off) / min(on), 3)
+
+
 def a16_wide_modes(path: Path, dev, prompt: torch.Tensor, new: int, wide_min_tokens: int, result: dict) -> None:
     """One packed A16 sparse-MoE model (``a16_experts="packed"``) decoded as ``a16_wide_off`` (``WeightOnlyExperts``'
     ``wide_min_tokens`` = 0: the grouped GEMV) and ``a16_wide`` (``wide_min_tokens`` = the class default, or
@@ -394,14 +426,17 @@ def main():
     ap.add_argument("--scheme", default="W4A16", choices=["W4A16", "W8A16", "W8A8", "W4A8"],
                     help="W8A8 / W4A8: an A8 checkpoint, decoded as a8_tiled and a8_skinny")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded at once (rows of every decode-step GEMM)")
-    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused", "norm", *A16_FUSED_PAIRS],
+    ap.add_argument("--pair", default="skinny", choices=["skinny", "mid", "wide", "fused", "norm", *A16_FUSED_PAIRS,
+                                                         "a16_experts_fused"],
                     help="A8 schemes: skinny = a8_tiled vs a8_skinny; mid = a8_mid_off (mid_max_m = 0) vs a8_mid; "
                          "wide = a8_wide_off (QuantizedExperts' wide attributes 0) vs a8_wide; fused = a8_fused_off vs a8_fused "
                          "(load_quantized(..., a8_fused_act=True)); norm = a8_norm_off vs a8_norm (a8_fused_norm=True, "
                          "a8_fused_act=True in both); W4A16 with --model "
                          "mixtral: wide = a16_wide_off (WeightOnlyExperts.wide_min_tokens = 0) vs a16_wide; W4A16 / "
                          "W8A16: a16_fused = a16_off (a16='packed') vs a16_fused (a16_fused_act=True); a16_norm = a16_off "
-                         "vs a16_norm (a16_fused_norm=True); a16_both = a16_off vs each flag alone and the two together")
+                         "vs a16_norm (a16_fused_norm=True); a16_both = a16_off vs each flag alone and the two together; "
+                         "W4A16 / W8A16 with --model mixtral: a16_experts_fused = a16_experts_off (packed banks) vs "
+                         "a16_experts_fused (a16_experts_fused_act=True)")
     ap.add_argument("--wide-min-tokens", type=int, default=-1,
                     help="with --scheme W4A16 --pair wide: WeightOnlyExperts.wide_min_tokens of a16_wide (default: "
                          "the class's)")
@@ -427,6 +462,12 @@ def main():
         if args.scheme not in ("W4A16", "W8A16") or mixtral:
             raise SystemExit(f"--pair {args.pair} compares the packed A16 runtime's dense modules: W4A16 / W8A16, llama")
         a16_fused_modes(path, dev, prompt, args.new, args.pair, result)
+        print(json.dumps(result))
+        return
+    if args.pair == "a16_experts_fused":
+        if args.scheme not in ("W4A16", "W8A16") or not mixtral:
+            raise SystemExit("--pair a16_experts_fused compares packed A16 expert banks: W4A16 / W8A16, --model mixtral")
+        a16_experts_fused_modes(path, dev, prompt, args.new, result)
         print(json.dumps(result))
         return
     if args.scheme not in ("W4A16", "W8A16"):

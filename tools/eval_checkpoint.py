@@ -4,7 +4,7 @@
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
                                   [--a16-stream-rows N] [--a16-panel-rows N] [--a16-tile-rows N]
                                   [--a16-experts-wide-tokens N] [--a16-experts-tile-tokens N]
-                                  [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
+                                  [--a16-experts-fused-act] [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
                                   [--a8-fused-norm] [--a8-w4-short-min-m M] [--head logits|fused] [--against REF]
 
 ``ids.pt`` holds a [B, T] integer tensor or a list of 1-d tensors (``torch.save``).  W8A8 / INT8 / W4A8 checkpoints run
@@ -17,6 +17,8 @@ above those, up to N rows, on ``qt_gemm_wq_panel``; ``--a16-tile-rows N`` with i
 ``--a16-experts-tile-tokens N`` with ``--a16-experts packed``: calls above that (or above 128) up to N tokens on
 ``qt_moe_gemm_wq_tile``, no dense bank allocated (a summation order of its own: the perplexity may move in its last
 digits);
+``--a16-experts-fused-act`` with ``--a16-experts packed``: the banks' gate_up product and SiLU(gate) * up as one launch in
+calls of up to 128 tokens (and the wide range), the same perplexity to the bit;
 ``--a16-fused-act`` / ``--a16-fused-norm`` with ``--a16 packed``: ``load_quantized``'s flags of those names -- the first
 changes inputs of 1 to 16 rows alone and no bit, the second moves the perplexity as ``--a8-fused-norm`` does;
 ``--a8-fused-act`` on an A8 checkpoint: SiLU(gate) * up and the quantiser of the down product in one
@@ -69,6 +71,9 @@ def main():
     ap.add_argument("--a16-experts-tile-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls past the grouped and wide ranges up to this many tokens route "
                          "their rows and run qt_moe_gemm_wq_tile instead of dequantising the banks")
+    ap.add_argument("--a16-experts-fused-act", action="store_true",
+                    help="with --a16-experts packed: the banks' gate_up product, SiLU and the multiply as one launch "
+                         "(qt_gemm_wq_grouped_act_mul / qt_moe_gemm_wq_wide_act_mul)")
     ap.add_argument("--a16-fused-act", action="store_true",
                     help="with --a16 packed: WeightOnlyMLPs and shared q/k/v launches (inputs of 1 to 16 rows)")
     ap.add_argument("--a16-fused-norm", action="store_true",
@@ -93,7 +98,8 @@ def main():
                            a16_experts=args.a16_experts, a16_stream_rows=args.a16_stream_rows,
                            a16_panel_rows=args.a16_panel_rows, a16_tile_rows=args.a16_tile_rows,
                            a16_experts_wide_tokens=args.a16_experts_wide_tokens,
-                           a16_experts_tile_tokens=args.a16_experts_tile_tokens, a8_fused_act=args.a8_fused_act,
+                           a16_experts_tile_tokens=args.a16_experts_tile_tokens,
+                           a16_experts_fused_act=args.a16_experts_fused_act, a8_fused_act=args.a8_fused_act,
                            a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
                            a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m)
     if args.device.startswith("cuda"):

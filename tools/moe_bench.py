@@ -80,6 +80,13 @@ launches) against qt_act_mul_quantize_i8 on the two halves of the same gate_up o
 to end with ``fused_act`` off and on, alternating call by call in one loop, each call between its own HIP events.  The
 unfused form runs twice in that loop ("unfused" and "unfused_again"): their ratio is the yardstick's own spread.  Both
 comparisons assert bit equality before anything is timed.
+
+  python tools/moe_bench.py --a16-fused-act [--tokens 1,8,16,32,64,96,128,192,384] --schemes W4A16,W4A16_ASYM,W8A16
+
+The A16 glue comparison, per scheme and T: the gate_up product followed by ``act_fn(gate) * up`` in torch against the one
+launch of qt_gemm_wq_grouped_act_mul (qt_moe_gemm_wq_wide_act_mul where the bank would run the wide kernel), and
+WeightOnlyExperts.forward end to end with ``fused_act`` off and on (past 128 tokens with wide_max_tokens = the largest T
+asked for), alternating as above over three rotating copies of the bank, bit equality asserted first.
 """
 from __future__ import annotations
 
@@ -500,6 +507,68 @@ def _bench_a16_wide(scheme, T, banks, dev, g, args, wide_max):
     return row
 
 
+def _bench_a16_fused(scheme, T, banks, dev, g, args, wide_max):
+    """One A16 fused-glue row: WeightOnlyExperts.forward with ``fused_act`` off and on (and off again: the yardstick's
+    own spread), alternating call by call over rotating copies of the bank (cold weights), after the two outputs were
+    held to bit equality; and the gate_up product + SiLU * up in torch against the one fused launch alone."""
+    from qlinear_bench import time_pair
+
+    n = len(banks)
+    x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
+    logits = torch.randn(T, E, device=dev, generator=g)
+    w, idx = torch.topk(torch.softmax(logits, -1), TOPK, dim=-1)
+    w = (w / w.sum(-1, keepdim=True)).to(torch.bfloat16)
+    offsets, src_token, _, _ = ops.moe_route(idx, E)
+    b0 = banks[0]
+    wide = T > b0.grouped_max_tokens or 0 < b0.wide_min_tokens <= T
+    row = {"scheme": scheme, "T": T, "R": T * TOPK, "form": "wide" if wide else "grouped", "cold_copies": n,
+           "m_tiles": ops.moe_wq_wide_mtiles(T * TOPK, E) if wide else 1}
+    gemm, fused_gemm = ((ops.moe_gemm_wq_wide, ops.moe_gemm_wq_wide_act_mul) if wide
+                        else (ops.gemm_wq_grouped, ops.gemm_wq_grouped_act_mul))
+
+    def glue(fused, shift):
+        def run(i):
+            b = banks[(i + shift) % n]
+            kw = dict(row_idx=src_token, K=H, zp_w=b.gate_up_zero_point)
+            if fused:
+                return fused_gemm(x, b.gate_up, b.gate_up_scale, offsets, **kw)
+            gate, up = gemm(x, b.gate_up, b.gate_up_scale, offsets, **kw).chunk(2, dim=-1)
+            return b.act_fn(gate) * up
+        return run
+
+    def bank(on, shift):
+        def run(i):
+            b = banks[(i + shift) % n]
+            b.fused_act = on
+            return b(x, idx, w)
+        return run
+
+    def ratios(t):
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        return {**{k: _us(v) for k, v in t.items()}, "speedup": round(med["unfused"] / med["fused"], 3),
+                "unfused_spread": round(abs(med["unfused"] / med["unfused_again"] - 1.0), 4)}
+
+    keep = [b.wide_max_tokens for b in banks]
+    with torch.no_grad():
+        try:
+            for b in banks:
+                b.wide_max_tokens = wide_max
+            assert torch.equal(glue(False, 0)(0).view(torch.int16), glue(True, 0)(0).view(torch.int16)), \
+                "the fused launch differs from the product and the glue"
+            assert torch.equal(bank(False, 0)(0).view(torch.int16), bank(True, 0)(0).view(torch.int16)), \
+                "the bank's output differs with fused_act"
+            row["bits_equal"] = True
+            row["glue"] = ratios(time_pair({"unfused": glue(False, 0), "fused": glue(True, 1),
+                                            "unfused_again": glue(False, 2)}, args.reps, args.warmup))
+            row["experts"] = ratios(time_pair({"unfused": bank(False, 0), "fused": bank(True, 1),
+                                               "unfused_again": bank(False, 2)}, args.reps, args.warmup))
+        finally:
+            for b, hi in zip(banks, keep):
+                b.wide_max_tokens = hi
+                b.fused_act = False
+    return row
+
+
 def _bench_a16_tile(scheme, T, banks, dev, g, args):
     """One A16 prompt-size row: the bank's forward on the dequantise path and on qt_moe_gemm_wq_tile, alternated (the
     dequantise path twice: its own run-to-run spread), the two products of the new path alone, and the peak allocated
@@ -597,6 +666,10 @@ def main():
     ap.add_argument("--fused-act", action="store_true",
                     help="W8A8 / W4A8: compare the three glue passes and qt_act_mul_quantize_i8, and the bank's forward "
                          "with fused_act off and on, at --tokens (default then: 1,16,32,128,512,2048,8192)")
+    ap.add_argument("--a16-fused-act", action="store_true",
+                    help="W4A16 / W4A16_ASYM / W8A16: compare WeightOnlyExperts.forward with fused_act off and on, and the "
+                         "gate_up product + glue against the fused launch, at --tokens (default then: "
+                         "1,8,16,32,64,96,128,192,384; past 128 on the wide_max_tokens range)")
     ap.add_argument("--schemes", default="W4A8,W8A8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -628,6 +701,32 @@ def main():
             torch.cuda.empty_cache()
         print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A16 prompt sizes: dequantise + bank forward vs "
                                     "qt_moe_gemm_wq_tile",
+                          "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
+                          "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
+        return
+
+    if args.a16_fused_act:
+        from transformers import MixtralConfig
+        from transformers.models.mixtral.modeling_mixtral import MixtralExperts
+
+        cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=TOPK)
+        default = args.tokens == ap.get_default("tokens")
+        tokens = [int(t) for t in ("1,8,16,32,64,96,128,192,384" if default else args.tokens).split(",")]
+        for scheme in args.schemes.split(","):
+            if scheme not in A16:
+                raise SystemExit("--a16-fused-act compares the A16 banks' glue (W4A16 / W4A16_ASYM / W8A16)")
+            with torch.device("meta"):
+                shells = [MixtralExperts(cfg) for _ in range(3)]    # unfused, fused, unfused_again: a copy each
+            banks = [_wo_experts(scheme, b, dev, g) for b in shells]
+            for T in tokens:
+                row = _bench_a16_fused(scheme, T, banks, dev, g, args, max(tokens))
+                rows.append(row)
+                print(json.dumps(row), file=sys.stderr)
+                torch.cuda.empty_cache()
+            del banks
+            torch.cuda.empty_cache()
+        print(json.dumps({"metric": "Mixtral-8x7B MoE layer, A16 glue: gate_up product + silu * up vs "
+                                    "qt_gemm_wq_grouped_act_mul / qt_moe_gemm_wq_wide_act_mul",
                           "schemes": args.schemes, "E": E, "top_k": TOPK, "H": H, "I": I,
                           "device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}))
         return
