@@ -904,6 +904,44 @@ int qt_gemm_wq_skinny_multi(const void* X, int x_dtype, int M, int K, int64_t ld
 int qt_gemm_wq_skinny_act_mul(const void* X, int x_dtype, int M, int K, int64_t ldx, const qt_wq_weight* gate,
                               const qt_wq_weight* up, int act, void* H, int64_t ldh, qt_stream_t stream);
 
+/* qt_gemm_wq_gemv: the decode GEMV on the vector pipe for 1 <= M <= QT_WQ_GEMV_MAX_M rows, each weight row read as one
+ *   contiguous stream (single-sequence decode and small batches).  The arguments and the weight
+ *   definition are qt_gemm_wq_skinny's.  Taken: QT_W_INT4_PACKED and QT_W_INT8, G = 1 and G = K / 128, with and without
+ *   zp_w and bias, bf16 and fp16, any N >= 1, ldy >= N, ldx >= K, K a multiple of QT_WQ_GEMV_K_UNIT, and X, Wq and
+ *   ldx * 2 multiples of 16 bytes.  Everything else -- g_idx != NULL (actorder group runs on qt_gemm_wq_skinny), a
+ *   ragged K, M = 0 or M > QT_WQ_GEMV_MAX_M, a misaligned operand or pitch, a null pointer, a G that is neither 1 nor
+ *   K / 128, a dtype that is not 16-bit -- returns QT_ERR_INVALID before any launch, and qt_last_error names the reason.
+ *   Its numerics are its own, NOT the skinny kernel's bits and not F.linear's.  No MFMA: the weight operand is
+ *   w = round_to_dtype((q - zp) s), formed by the skinny kernel's statements, and the products run on
+ *   v_dot2_f32_{bf16,f16}, two 16-bit pairs per instruction into an fp32 accumulator.  A workgroup of 4 waves owns 4
+ *   weight rows; wave v takes the 128-column k-blocks [nkb v / 4, nkb (v + 1) / 4), nkb = K / 128, in slabs of 64 lane
+ *   pieces of 8, 16 or 32 consecutive columns (the width is a function of K and the format alone); a lane adds its
+ *   pieces in ascending column order into one accumulator per output, the 64 lane sums are added by a fixed xor tree
+ *   (32, 16, ..., 1), the waves' sums as ((c0 + c1) + c2) + c3, then the bias in fp32, then one rounding to x_dtype.
+ *   No atomics, no workspace: two runs give the same bits; row m of Y depends on row m of X alone, not on M; inputs
+ *   whose partial sums are all exact give round_to_dtype of the exact sum; otherwise
+ *   |y - y_exact| <= ulp_dtype(y) / 2 + K 2^-24 sum_k |x w|.  Every weight byte is read from memory once per launch.
+ *   No byte outside X [M, K] (pitch ldx), Wq, s_w / zp_w [N, G] and bias [N] is read; nothing outside Y[m < M, n < N]
+ *   is written.  (csrc/wq_gemv.hip) */
+int qt_gemm_wq_gemv(const void* X, int x_dtype, int M, int K, int64_t ldx, const void* Wq, int w_format, int N,
+                    const float* s_w, int G, const int8_t* zp_w, const int32_t* g_idx, const void* bias, void* Y,
+                    int64_t ldy, qt_stream_t stream);
+#define QT_WQ_GEMV_MAX_M 4
+#define QT_WQ_GEMV_K_UNIT 128
+
+/* qt_gemm_wq_gemv_act_mul: qt_gemm_wq_skinny_act_mul on qt_gemm_wq_gemv's kernel -- H [M, I] = act(X Wg^T) * (X Wu^T)
+ *   in x_dtype with row pitch ldh >= I, I = gate->N = up->N, act: QT_ACT_SILU.  Taken and refused:
+ *   qt_gemm_wq_gemv's conditions on X (1 <= M <= QT_WQ_GEMV_MAX_M) and on both weights; gate and up must agree in
+ *   format, N, G and zero-point presence, and carry no bias and no Y (H is the one output).
+ *   H is bit-identical to F.silu(qt_gemm_wq_gemv(X, Wg)) * qt_gemm_wq_gemv(X, Wu) as torch computes it on the device: a
+ *   workgroup owns 4 columns n of the gate weight and the same 4 of the up weight, a lane loads the activations of its
+ *   piece once and runs qt_gemm_wq_gemv's chain on each weight; both sums take that kernel's reduction, are rounded to
+ *   x_dtype, and qt_act_mul_quantize_i8's sequence a, a', p, h makes h (csrc/h16_act.h).  Deterministic, no atomics, no
+ *   workspace, no bias.  No byte outside X [M, K] (pitch ldx), the two Wq and their s_w / zp_w [I, G] is read; nothing
+ *   outside H[m < M, n < I] is written.  (csrc/wq_gemv.hip) */
+int qt_gemm_wq_gemv_act_mul(const void* X, int x_dtype, int M, int K, int64_t ldx, const qt_wq_weight* gate,
+                            const qt_wq_weight* up, int act, void* H, int64_t ldh, qt_stream_t stream);
+
 /* qt_rmsnorm: qt_rmsnorm_quantize_i8 without its quantiser, for readers of Y alone (the A16 runtime):
  *   steps 1 to 5 of that sequence word for word -- the same chunk walk, butterfly and wave order, the same fp64
  *   1 / sqrt, the same two roundings of step 5 -- so Y [M, K] (required, row pitch ldy >= K) and rstd [M] (may be NULL)

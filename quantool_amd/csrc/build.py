@@ -55,6 +55,8 @@ SOURCE_FLAGS = {
     "wq_tile.hip": _NO_PACKED_FP32,
     # the same statements (wq_tile_body.h): its rows must be qt_gemm_wq_tile's bit for bit
     "wq_moe_tile.hip": _NO_PACKED_FP32,
+    # frag_from_u's values again: its weight operand must be qt_dequantize_weight's element for element
+    "wq_gemv.hip": _NO_PACKED_FP32,
     # since qt_rmsnorm's instances joined it: Y must be the quantising instances' Y bit for bit, on every device
     "rmsnorm_quant.hip": _NO_PACKED_FP32,
 }

@@ -336,7 +336,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                    a16_experts_wide_tokens: int = 0, a8_fused_act: bool = False,
                    a8_fused_norm: bool = False, a16_panel_rows: int = 0, a16_fused_act: bool = False,
                    a16_fused_norm: bool = False, a8_w4_short_min_m: int = 0, a16_tile_rows: int = 0,
-                   a16_experts_tile_tokens: int = 0, a16_experts_fused_act: bool = False) -> nn.Module:
+                   a16_experts_tile_tokens: int = 0, a16_experts_fused_act: bool = False,
+                   a16_gemv_rows: int = 0) -> nn.Module:
     """Rebuild the model a ``save_pretrained`` / ``_save_compressed`` directory describes (one file or shards) with
     ``QuantizedLinear``s (A8 schemes) or, for A16 schemes, dequantised ``nn.Linear``s (``a16="dequantized"``, the
     default) or ``WeightOnlyLinear``s on the stored integer weights (``a16="packed"``) in place of its quantized Linears.
@@ -357,6 +358,11 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
     kernels above do not take run ``qt_gemm_wq_tile`` on the stored weights instead of dequantise + ``F.linear``:
     deterministic, but in a summation order of its own.  It is recorded under ``"a16_tile_rows"``.  A8
     checkpoints ignore it.
+    ``a16_gemv_rows`` (0, the default, or 1 ... 4; needs ``a16="packed"``) sets ``gemv_max_m`` on every
+    ``WeightOnlyLinear`` built, so inputs of up to that many rows run ``qt_gemm_wq_gemv`` -- and, under
+    ``a16_fused_act``, the MLP's gate / up pair ``qt_gemm_wq_gemv_act_mul`` -- in place of the skinny kernel:
+    deterministic and within the same bound, but in a summation order of its own.  It is recorded
+    under ``"a16_gemv_rows"``.  A8 checkpoints ignore it.
     ``a16_experts_wide_tokens`` (0, the default, or 129 ... ``A16_EXPERTS_WIDE_MAX_TOKENS``; needs
     ``a16_experts="packed"``) sets ``wide_max_tokens`` on every ``WeightOnlyExperts`` built, so calls of 129 to that many
     tokens route their rows and run ``qt_moe_gemm_wq_wide`` on the stored weights instead of dequantising both banks; it
@@ -434,6 +440,10 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         raise ValueError(f"a16_tile_rows={a16_tile_rows!r}: expected 0 or {tile_floor} and more")
     if a16_tile_rows and a16 != "packed":
         raise ValueError("a16_tile_rows needs a16='packed' (dequantised Linears have no stored weights to run on)")
+    if type(a16_gemv_rows) is not int or not 0 <= a16_gemv_rows <= 4:
+        raise ValueError(f"a16_gemv_rows={a16_gemv_rows!r}: expected 0 or 1 ... 4")
+    if a16_gemv_rows and a16 != "packed":
+        raise ValueError("a16_gemv_rows needs a16='packed' (dequantised Linears have no stored weights to run on)")
     if type(a16_experts_wide_tokens) is not int or not (
             a16_experts_wide_tokens == 0 or 129 <= a16_experts_wide_tokens <= A16_EXPERTS_WIDE_MAX_TOKENS):
         raise ValueError(f"a16_experts_wide_tokens={a16_experts_wide_tokens!r}: expected 0 or 129 ... "
@@ -537,6 +547,8 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
                 new.panel_max_m = a16_panel_rows
             if not a8 and a16_tile_rows:
                 new.tile_max_m = a16_tile_rows
+            if not a8 and a16_gemv_rows:
+                new.gemv_max_m = a16_gemv_rows
             _set_submodule(model, name, new)
         else:
             W = dequantized_weight(name, t, mdtype)
@@ -565,6 +577,7 @@ def load_quantized(path, device="cuda", dtype: Optional[torch.dtype] = None, a16
         model._qt_checkpoint["a16_stream_rows"] = a16_stream_rows
         model._qt_checkpoint["a16_panel_rows"] = a16_panel_rows
         model._qt_checkpoint["a16_tile_rows"] = a16_tile_rows
+        model._qt_checkpoint["a16_gemv_rows"] = a16_gemv_rows
         model._qt_checkpoint["a16_fused_act"] = a16_fused_act
         model._qt_checkpoint["a16_fused_norm"] = a16_fused_norm
         model._qt_checkpoint["dense_expert_banks"] = sorted(set(experts) - set(replaced))

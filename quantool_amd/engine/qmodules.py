@@ -385,7 +385,10 @@ class WeightOnlyLinear(nn.Module):
     not 0, <= ``panel_max_n``, where ``ops.gemm_wq_panel_supported`` holds.  With ``tile_max_m`` > 0, what those branches
     left of max(``skinny_max_m``, ``stream_max_m``) < M <= ``tile_max_m`` runs ``qt_gemm_wq_tile`` (deterministic, a
     row's bits independent of M, but a summation order of its own) on a Linear inside ``tile_min_k`` / ``tile_min_n`` /
-    ``tile_max_n``, where ``ops.gemm_wq_tile_supported`` holds.
+    ``tile_max_n``, where ``ops.gemm_wq_tile_supported`` holds.  With ``gemv_max_m`` > 0, 1 <= M <= ``gemv_max_m`` (at
+    most 4) runs ``qt_gemm_wq_gemv`` in place of the skinny kernel (the same guarantees, a summation order of its own)
+    on a Linear inside ``gemv_min_k`` / ``gemv_max_n``, where ``ops.gemm_wq_gemv_supported`` holds; a member of a
+    ``SharedOutputs`` asks that first.
 
     Buffers: ``weight_packed`` int32 [N, ceil(K/8)] (int4) or ``weight`` int8 [N, K]; ``weight_scale`` fp32 [N, G];
     ``weight_zero_point`` int8 [N, G] (optional); ``g_idx`` int32 [K] (optional, actorder ``group``); ``bias``
@@ -423,6 +426,13 @@ class WeightOnlyLinear(nn.Module):
     tile_min_k = 4096
     tile_min_n = 14336
     tile_max_n = 28672
+    # Row-stream GEMV on the vector pipe (``qt_gemm_wq_gemv``) in place of the skinny kernel up to this many rows (at
+    # most ``ops.WQ_GEMV_MAX_M``).  0, the default: never -- its summation order is its own, not the skinny kernel's
+    # (``load_quantized(..., a16_gemv_rows=)``).  Used only when it is not 0: from ``gemv_min_k`` input features and,
+    # when ``gemv_max_n`` is not 0, up to that many output features (0: no bound; DESIGN.md 4.32 says what was measured).
+    gemv_max_m = 0
+    gemv_min_k = 0
+    gemv_max_n = 0
 
     def __init__(self, in_features: int, out_features: int, weight: torch.Tensor, weight_scale: torch.Tensor,
                  weight_zero_point: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None,
@@ -458,7 +468,7 @@ class WeightOnlyLinear(nn.Module):
                 f"weights={'int4' if self.int4 else 'int8'}, groups={self.weight_scale.shape[1]}, "
                 f"zero_point={self.weight_zero_point is not None}, g_idx={self.g_idx is not None}, "
                 f"bias={self.bias is not None}, skinny_max_m={self.skinny_max_m}, stream_max_m={self.stream_max_m}, "
-                f"panel_max_m={self.panel_max_m}, tile_max_m={self.tile_max_m}")
+                f"panel_max_m={self.panel_max_m}, tile_max_m={self.tile_max_m}, gemv_max_m={self.gemv_max_m}")
 
     # A ``SharedOutputs`` this Linear is a member of (None, the default: it computes for itself).
     outputs_from = None
@@ -476,6 +486,13 @@ class WeightOnlyLinear(nn.Module):
                 y = self.outputs_from.take(self, x)
                 if y is not None:
                     return y
+            if (self.gemv_max_m > 0 and w.K >= self.gemv_min_k and (self.gemv_max_n == 0 or w.N <= self.gemv_max_n)
+                    and M <= min(self.gemv_max_m, ops.WQ_GEMV_MAX_M)):
+                # the attributes and the sizes decide first: ops' gemv names are read only past them
+                x2 = _rows(x, w.K)
+                if ops.gemm_wq_gemv_supported(x2, w.levels, w.scale, w.zero_point, w.g_idx):
+                    y = ops.gemm_wq_gemv(x2, w.levels, w.scale, zp_w=w.zero_point, bias=bias)
+                    return y.reshape(*x.shape[:-1], w.N)
             y = ops.gemm_wq_skinny(_rows(x, w.K), w.levels, w.scale, zp_w=w.zero_point, g_idx=w.g_idx, bias=bias)
             return y.reshape(*x.shape[:-1], w.N)
         if (self.stream_max_m > 0 and self.skinny_max_m < M <= self.stream_max_m and w.K >= self.stream_min_k
@@ -604,7 +621,9 @@ class WeightOnlyMLP(nn.Module):
     """A Llama-style MLP ``down_proj(act_fn(gate_proj(x)) * up_proj(x))`` of three ``WeightOnlyLinear``s.  At decode
     size -- 1 <= M <= ``fused_max_m`` rows on the device, where ``ops.gemm_wq_fused_supported`` holds for gate and up --
     the two GEMVs, SiLU and the multiply run as one launch, ``qt_gemm_wq_skinny_act_mul``, equal to the bit to the
-    four it replaces (include/quantool_amd.h), so the module changes speed alone.  Anything else runs the three
+    four it replaces (include/quantool_amd.h), so the module changes speed alone -- or, up to
+    min(``gate_proj.gemv_max_m``, ``up_proj.gemv_max_m``) rows, as ``qt_gemm_wq_gemv_act_mul``, equal to the bit to the
+    four launches those two Linears would run on ``qt_gemm_wq_gemv``.  Anything else runs the three
     children's own ``forward``, so their stream / panel settings still apply above 16 rows.  Opt-in:
     ``load_quantized(..., a16="packed", a16_fused_act=True)`` builds it where ``eligible`` holds.  The children keep
     their names, so state-dict keys do not move."""
@@ -652,7 +671,10 @@ class WeightOnlyMLP(nn.Module):
             x2 = _rows(x, K)
             wg, wu = _kernel_weight(gate), _kernel_weight(up)
             if M <= ops.WQ_FUSED_MAX_M and wg[0].device == x.device and ops.gemm_wq_fused_supported(x2, (wg, wu)):
-                h = ops.gemm_wq_skinny_act_mul(x2, wg[:3], wu[:3])
+                if M <= min(gate.gemv_max_m, up.gemv_max_m) and M <= ops.WQ_GEMV_MAX_M:
+                    h = ops.gemm_wq_gemv_act_mul(x2, wg[:3], wu[:3])
+                else:
+                    h = ops.gemm_wq_skinny_act_mul(x2, wg[:3], wu[:3])
                 return down(h.reshape(*x.shape[:-1], gate.out_features))
         return down(self.act_fn(gate(x)) * up(x))
 

@@ -169,6 +169,10 @@ SIGNATURES = {
     "qt_gemm_wq_skinny_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p]),
     "qt_gemm_wq_skinny_act_mul": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                                           c_int64, c_void_p]),
+    "qt_gemm_wq_gemv": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "qt_gemm_wq_gemv_act_mul": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_int64, c_void_p]),
     "qt_rmsnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int64, c_void_p,
                            c_void_p]),
     "qt_gemm_wq_grouped": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p,

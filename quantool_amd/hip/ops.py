@@ -1678,6 +1678,87 @@ def gemm_wq_skinny_act_mul(X: torch.Tensor, gate, up, act: str = "silu") -> torc
     return H
 
 
+WQ_GEMV_MAX_M = 4        # rows of X qt_gemm_wq_gemv takes (QT_WQ_GEMV_MAX_M)
+
+
+def _wq_gemv_refusal(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                     g_idx: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why ``qt_gemm_wq_gemv`` would refuse these operands, or None: the packed A16 16-byte path as
+    ``_wq_stream_refusal`` states it (its pitch bound is far above any the GEMV meets), at 1 to ``WQ_GEMV_MAX_M`` rows.
+    Host-only."""
+    why = _wq_stream_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is None and not 1 <= X.shape[0] <= WQ_GEMV_MAX_M:
+        why = f"1 <= M <= {WQ_GEMV_MAX_M} rows only, got X {tuple(X.shape)}"
+    return why
+
+
+def gemm_wq_gemv_supported(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor,
+                           zp_w: Optional[torch.Tensor] = None, g_idx: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``gemm_wq_gemv`` takes these operands: 1 to ``WQ_GEMV_MAX_M`` rows, no ``g_idx``, 16-bit X with unit
+    column stride, K a multiple of 128, G = 1 or K/128, X, Wq and X's row pitch 16-byte aligned.  Host-only."""
+    return _wq_gemv_refusal(X, Wq, s_w, zp_w, g_idx) is None
+
+
+def gemm_wq_gemv(X: torch.Tensor, Wq: torch.Tensor, s_w: torch.Tensor, zp_w: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *,
+                 g_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y = X W^T (+ bias) on the packed weights for 1 <= M <= ``WQ_GEMV_MAX_M`` rows (``qt_gemm_wq_gemv``): the decode
+    GEMV on the vector pipe, every weight row read as one contiguous stream, no MFMA.  Its numerics are its own: fp32
+    sums of w = round_to_dtype((q - zp) s) times x in the kernel's fixed order, then the bias, then one rounding --
+    deterministic, a row's bits independent of M, within the skinny kernel's error bound, but not bit-equal to
+    ``gemm_wq_skinny`` or to ``F.linear``.  ``out``: a caller-owned [M, N] view in X's dtype with unit column stride
+    (any row pitch).  ``g_idx`` is accepted only to be refused.  ``ValueError`` where ``gemm_wq_gemv_supported`` is
+    false, before the library is touched."""
+    why = _wq_gemv_refusal(X, Wq, s_w, zp_w, g_idx)
+    if why is not None:
+        raise ValueError(f"gemm_wq_gemv: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    fmt, N, K, G = _wq_weight(Wq, s_w, zp_w, g_idx, K)
+    if Wq.device != X.device:
+        raise ValueError(f"Wq is on {Wq.device}, X on {X.device}")
+    if bias is not None:
+        _req(bias, X.dtype, "bias", 1)
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"bias must be contiguous [{N}] in X's dtype")
+    if out is None:
+        out = torch.empty((M, N), dtype=X.dtype, device=X.device)
+    elif (out.shape != (M, N) or out.dtype != X.dtype or out.device != X.device or out.stride(1) != 1
+          or out.stride(0) < N):
+        raise ValueError(f"out must be [{M}, {N}] {X.dtype} on {X.device} with unit column stride and a row pitch >= N")
+    check("qt_gemm_wq_gemv", lib.qt_gemm_wq_gemv(
+        X.data_ptr(), code, M, K, X.stride(0), Wq.data_ptr(), fmt, N, s_w.data_ptr(), G, _ptr(zp_w), None,
+        _ptr(bias), out.data_ptr(), out.stride(0), _stream()))
+    return out
+
+
+def gemm_wq_gemv_act_mul(X: torch.Tensor, gate, up, act: str = "silu") -> torch.Tensor:
+    """``gemm_wq_skinny_act_mul`` on the row-stream GEMV (``qt_gemm_wq_gemv_act_mul``), 1 <= M <= ``WQ_GEMV_MAX_M``:
+    H [M, I] = act(X . wg^T) * (X . wu^T) in one launch, ``gate`` and ``up`` (Wq, s_w, zp_w) of equal N = I, format, G
+    and zero-point presence.  Bit-identical to ``F.silu(gemm_wq_gemv(X, *gate)) * gemm_wq_gemv(X, *up)`` on the
+    device.  ``ValueError`` where the operands are not taken, before the library is touched."""
+    gate, up = tuple(gate), tuple(up)
+    why = _wq_fused_refusal(X, [(*gate, None), (*up, None)])
+    if why is None and not X.shape[0] <= WQ_GEMV_MAX_M:
+        why = f"1 <= M <= {WQ_GEMV_MAX_M} rows only, got X {tuple(X.shape)}"
+    if why is None and gate[0].shape[0] != up[0].shape[0]:
+        why = f"gate has {gate[0].shape[0]} rows, up {up[0].shape[0]}"
+    if why is None and act not in ACTS:
+        why = f"act must be one of {sorted(ACTS)}, got {act!r}"
+    if why is not None:
+        raise ValueError(f"gemm_wq_gemv_act_mul: {why}")
+    lib = load()
+    code = _x2d(X, "X")
+    M, K = X.shape
+    table, (I, _) = _wq_weight_table(X, [(*gate, None, None), (*up, None, None)])
+    H = torch.empty((M, I), dtype=X.dtype, device=X.device)
+    check("qt_gemm_wq_gemv_act_mul", lib.qt_gemm_wq_gemv_act_mul(
+        X.data_ptr(), code, M, K, X.stride(0), ctypes.byref(table[0]), ctypes.byref(table[1]), ACTS[act], H.data_ptr(),
+        H.stride(0), _stream()))
+    return H
+
+
 def rmsnorm(X: torch.Tensor, weight: torch.Tensor, eps: float, return_rstd: bool = False):
     """``Y = weight * RMSNorm(X)`` alone (``qt_rmsnorm``): the Y, and with ``return_rstd`` the rstd, of
     ``rmsnorm_quantize_i8`` to the bit, with nothing quantised.  X [M, K] bf16 / fp16 (unit column stride, any row

@@ -50,6 +50,8 @@ so nothing is asserted of the logits: how many of the prompt's differ, and by ho
 (``logits_differ``, ``logits_max_abs_diff``) beside ``quantizing_norms``.
 ``--pair a16_fused`` / ``a16_norm`` / ``a16_both`` (W4A16 / W8A16, llama) load the checkpoint with ``a16="packed"`` as
 ``a16_off`` and with ``a16_fused_act``, ``a16_fused_norm`` or each alone and both, decoded in turn, twice.
+``--pair a16_gemv`` (the same checkpoints) decodes ``a16_off`` against ``a16_gemv`` (``a16_gemv_rows=4``),
+``a16_fused`` (``a16_fused_act``) and ``a16_gemv_fused`` (both), in turn, twice.
 ``--pair a16_experts_fused`` (W4A16 / W8A16, ``--model mixtral``) loads the checkpoint with packed expert banks as
 ``a16_experts_off`` and with ``a16_experts_fused_act=True`` as ``a16_experts_fused``: one decode step's
 logits must agree to the bit, and the tokens.
@@ -295,7 +297,10 @@ def a8_norm_modes(path: Path, dev, prompt: torch.Tensor, new: int, result: dict)
 A16_FUSED_PAIRS = {"a16_fused": {"a16_fused": {"a16_fused_act": True}},
                    "a16_norm": {"a16_norm": {"a16_fused_norm": True}},
                    "a16_both": {"a16_fused": {"a16_fused_act": True}, "a16_norm": {"a16_fused_norm": True},
-                                "a16_both": {"a16_fused_act": True, "a16_fused_norm": True}}}
+                                "a16_both": {"a16_fused_act": True, "a16_fused_norm": True}},
+                   # the row-stream GEMV alone, the fused MLP alone, and the two together
+                   "a16_gemv": {"a16_gemv": {"a16_gemv_rows": 4}, "a16_fused": {"a16_fused_act": True},
+                                "a16_gemv_fused": {"a16_gemv_rows": 4, "a16_fused_act": True}}}
 
 
 def a16_fused_modes(path: Path, dev, prompt: torch.Tensor, new: int, pair: str, result: dict) -> None:

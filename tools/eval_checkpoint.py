@@ -2,7 +2,7 @@
 
   python tools/eval_checkpoint.py <checkpoint dir> --tokens ids.pt [--batch-size 8] [--dtype bfloat16]
                                   [--a16 dequantized|packed] [--a16-experts dequantized|packed]
-                                  [--a16-stream-rows N] [--a16-panel-rows N] [--a16-tile-rows N]
+                                  [--a16-stream-rows N] [--a16-panel-rows N] [--a16-tile-rows N] [--a16-gemv-rows N]
                                   [--a16-experts-wide-tokens N] [--a16-experts-tile-tokens N]
                                   [--a16-experts-fused-act] [--a16-fused-act] [--a16-fused-norm] [--a8-fused-act]
                                   [--a8-fused-norm] [--a8-w4-short-min-m M] [--head logits|fused] [--against REF]
@@ -65,6 +65,9 @@ def main():
     ap.add_argument("--a16-tile-rows", type=int, default=0,
                     help="with --a16 packed: inputs of up to this many rows that the kernels above leave run "
                          "qt_gemm_wq_tile (a summation order of its own: the perplexity may move in its last digits)")
+    ap.add_argument("--a16-gemv-rows", type=int, default=0,
+                    help="with --a16 packed: inputs of up to this many rows (at most 4) run qt_gemm_wq_gemv in place of "
+                         "the skinny kernel (perplexity batches have more rows: it matters to decode alone)")
     ap.add_argument("--a16-experts-wide-tokens", type=int, default=0,
                     help="with --a16-experts packed: calls of 129 to this many tokens route their rows and run "
                          "qt_moe_gemm_wq_wide instead of dequantising the banks")
@@ -101,7 +104,8 @@ def main():
                            a16_experts_tile_tokens=args.a16_experts_tile_tokens,
                            a16_experts_fused_act=args.a16_experts_fused_act, a8_fused_act=args.a8_fused_act,
                            a8_fused_norm=args.a8_fused_norm, a16_fused_act=args.a16_fused_act,
-                           a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m)
+                           a16_fused_norm=args.a16_fused_norm, a8_w4_short_min_m=args.a8_w4_short_min_m,
+                           a16_gemv_rows=args.a16_gemv_rows)
     if args.device.startswith("cuda"):
         torch.cuda.synchronize()
     t1 = time.perf_counter()

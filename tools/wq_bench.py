@@ -31,6 +31,12 @@ scheme and M, ``ops.gemm_wq_panel`` against the dequantise + ``F.linear`` pair a
 48 rows and up, by the same method: ``ops.gemm_wq_tile`` against the dequantise + ``F.linear`` pair and,
 on the shapes and rows a ``WeightOnlyLinear`` would give it, ``ops.gemm_wq_panel``; ``pair_peak_mb`` / ``tile_peak_mb``
 are one call's peak allocation above the operands.
+
+  python tools/wq_bench.py --gemv [--gemv-ms 1,2,3,4] [--reps 30] [--warmup 5]
+
+1 - 4 rows, by the same method: ``ops.gemm_wq_gemv`` against ``ops.gemm_wq_skinny`` on q/k/v, o, k/v,
+gate/up, gate or up alone and down, and ``ops.gemm_wq_gemv_act_mul`` against ``ops.gemm_wq_skinny_act_mul`` on gate and
+up; TB/s of both over the packed bytes.
 """
 from __future__ import annotations
 
@@ -259,6 +265,44 @@ def fused_main(args):
                       "warmup": args.warmup, "rows": rows}))
 
 
+def gemv_main(args):
+    """--gemv: ``ops.gemm_wq_gemv`` against ``ops.gemm_wq_skinny`` at 1 - 4 rows, --stream's method (cold weights, the
+    two alternating call by call), and ``ops.gemm_wq_gemv_act_mul`` against ``ops.gemm_wq_skinny_act_mul`` on gate and
+    up [14336, 4096].  TB/s counts the packed weight, scale and zero-point bytes."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    names = [k for k in args.shapes.split(",") if k] if args.shapes != ",".join(SHAPES) else list(PANEL_SHAPES)
+    ms = [int(m) for m in args.gemv_ms.split(",") if m]
+    rows = []
+    for scheme in args.schemes.split(","):
+        for shape in names + ["act_mul"]:
+            N, K = STREAM_SHAPES["gate" if shape == "act_mul" else shape]
+            ws = [_cold_weights(N, K, scheme, dev, g) for _ in range(2 if shape == "act_mul" else 1)]
+            qbytes = sum(w[3] for w in ws)
+            n_cp = min(len(w[4]) for w in ws)
+
+            def call(new, i, X):
+                cp = [w[4][i % n_cp] for w in ws]
+                if shape == "act_mul":
+                    return (ops.gemm_wq_gemv_act_mul if new else ops.gemm_wq_skinny_act_mul)(X, *cp)
+                return (ops.gemm_wq_gemv if new else ops.gemm_wq_skinny)(X, cp[0][0], cp[0][1], zp_w=cp[0][2])
+
+            row = {"shape": shape, "N": N, "K": K, "scheme": scheme, "packed_mb": round(qbytes / 1e6, 2),
+                   "cold_copies": n_cp, "gemv": {}}
+            for M in ms:
+                X = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+                err = (call(True, 0, X).float() - call(False, 0, X).float()).abs().max().item()
+                ts = _alternate([lambda i: call(False, i, X), lambda i: call(True, i, X)], args.reps, args.warmup)
+                row["gemv"][M] = {"skinny_us": ts[0], "gemv_us": ts[1], "speedup": round(ts[0] / ts[1], 2),
+                                  "skinny_tbs": round(qbytes / ts[0] / 1e6, 3), "gemv_tbs": round(qbytes / ts[1] / 1e6, 3),
+                                  "max_abs_diff": err}
+            rows.append(row)
+            del ws
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "wq_bench --gemv", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+                      "warmup": args.warmup, "rows": rows}))
+
+
 def stream_main(args):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -314,6 +358,9 @@ def main():
     ap.add_argument("--fused", action="store_true", help="the fused decode forms (qt_gemm_wq_skinny_act_mul, "
                     "qt_gemm_wq_skinny_multi) against the skinny launches and torch glue they replace")
     ap.add_argument("--fused-ms", default="1,8,16")
+    ap.add_argument("--gemv", action="store_true", help="1 - 4 rows: qt_gemm_wq_gemv against qt_gemm_wq_skinny, and "
+                    "qt_gemm_wq_gemv_act_mul against qt_gemm_wq_skinny_act_mul")
+    ap.add_argument("--gemv-ms", default="1,2,3,4")
     ap.add_argument("--skinny-ms", default="1,2,4,8,16")
     ap.add_argument("--large-ms", default="4096,8192")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -326,6 +373,8 @@ def main():
         raise SystemExit("wq_bench needs a GPU")
     if args.fused:
         return fused_main(args)
+    if args.gemv:
+        return gemv_main(args)
     if args.stream:
         return stream_main(args)
     if args.panel:
